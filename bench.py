@@ -21,10 +21,20 @@ in the same run (the other GPUs idle) and efficiency = value / (N x that rate);
 `--curve` (own launcher only) first runs the smaller power-of-two replica counts
 and adds their values as `scaling_curve`.
 
-Output: ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event
-timed on the library's stream) and `cpu_baseline` (the reference's own
+Output: ONE JSON line on rank 0.  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, `whole_step_hbm`);
+`roofline` is null.  `--full` adds everything else: `roofline` (dominant
+kernel, HIP-event timed on the library's stream), the secondary legs
+(multi-sequence, serving, prefill, generation, drop-in; N > 1: batched decode
+and the sharded serving queue) and `cpu_baseline` (the reference's own
 AVX/OpenMP build from oracle/_ref when present, else the oracle port; bounded
-sample) objects.
+sample).
+
+`--dump-outputs DIR` writes what the timed path computed, after the timed
+steps: DIR/step_ids.npy (float64, the greedy id of each of the last min(K, 2048)
+timed steps in step order; its last entry is the last step's) and, on the ops path, also
+DIR/last_step_logits.npy (float32, the logits of the last step).  Weights and
+ids are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import importlib
@@ -97,7 +107,12 @@ def parse_args(argv=None):
     ap.add_argument("--kv-rows", action="store_true", help="wide decoders read the K / V cache rows as they lie (round 4's attention kernel) instead of "
                     "head-major shadows (A/B of csrc/gten_decode_attn_hm.h)")
     ap.add_argument("--no-wx-planes", action="store_true", help="f16 wide decoders: o and down as k_dec_mmv_f16 in two K planes instead of k_dec_wxp_f16 in eight (A/B)")
-    ap.add_argument("--brief", action="store_true", help="only the metric line: no secondary legs, no CPU baseline")
+    ap.add_argument("--brief", action="store_true", help="only the metric line: no secondary legs, no CPU baseline (also under --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the secondary legs, the CPU baseline and (N > 1) the batched / sharded-serving legs; "
+                         "off: a plain run times only the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/*.npy (float32 / float64)")
     ap.add_argument("--curve", action="store_true",
                     help="with --gpus N > 1 under this file's own launcher: first run 1, 2, 4, ... < N replicas (brief) and "
                          "report their values as `scaling_curve` in the N-replica line")
@@ -504,6 +519,15 @@ class Leg:
         return False
 
 
+def dump_outputs(d, step_ids, last_logits=None):
+    """--dump-outputs: the timed path's results as .npy files (a few hundred KB at most), so that two builds can be compared"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "step_ids.npy"), np.asarray(step_ids, dtype=np.float64))
+    if last_logits is not None:
+        np.save(os.path.join(d, "last_step_logits.npy"), np.asarray(last_logits, dtype=np.float32))
+
+
 def remove_synth_cache():
     """the per-node synthetic-weight cache in GTEN_SYNTH_CACHE_DIR (host/tinyllama_model.h load_synthetic_cached): removed by the
     node's first local rank once its replicas have loaded -- and again on the way out of main(), so that a run that failed
@@ -665,12 +689,16 @@ def worker(args, rank, local_rank, world, dist):
     else:
         model.set_fast_decode(False)
 
+    ops_out = {"ids": [], "logits": None}        # ops path: what its caller received (--dump-outputs)
+
     def step(n):
         if fused:
             model.decode_step(n, use_graph)      # asynchronous graph replay; argmax stays on the device
             return None
         lg = model.logits(toks[:n], n - 1)       # logits reach the host; greedy argmax there
-        return int(np.argmax(lg))
+        ops_out["logits"] = lg
+        ops_out["ids"].append(int(np.argmax(lg)))
+        return ops_out["ids"][-1]
 
     # fill the context with real decode steps (untimed), then warm up
     total = K + W
@@ -722,11 +750,18 @@ def worker(args, rank, local_rank, world, dist):
         dist.barrier()
     # barrier + synchronise on both sides of exactly K steps; MAX elapsed over ranks
     elapsed, total_tokens, per_rank = rep.timed_region(run_steps, sync, dist=dist, device=ddev, per_rank=True)
+    n_dump = min(K, 2048)                            # --dump-outputs: the last (at most 2048) timed steps' ids
+    if not fused:
+        step_ids = ops_out["ids"][-n_dump:]          # (before the call below adds one more)
     last = model.decode_result(n_of(W + K - 1, total)) if fused else step(n_of(W + K - 1, total))
+    if args.dump_outputs and rank == 0:
+        if fused:                                   # the ids stay on the device per position: read back after the timing
+            step_ids = [model.decode_result(n_of(i, total)) for i in range(W + K - n_dump, W + K)]
+        dump_outputs(args.dump_outputs, step_ids, None if fused else ops_out["logits"])
     # N > 1: one global prompt queue sharded over the replicas (north_star's per-prompt split), every rank its shard
     # through its own continuous-batching slots -- the aggregate serving rate beside the batch-1 rate of `value`
     sharded = None
-    if dist is not None and world > 1 and fused and args.serve > 0 and (args.serve_slots or args.wide_streams) > 1 and not args.brief:
+    if args.full and dist is not None and world > 1 and fused and args.serve > 0 and (args.serve_slots or args.wide_streams) > 1 and not args.brief:
         S = args.serve_slots or args.wide_streams
         # A failure on ONE rank (out of memory creating the slots, a serve error) must not take the already measured `value`
         # with it nor leave the other ranks in a collective: every rank reports whether it got this far, the leg runs only
@@ -758,7 +793,7 @@ def worker(args, rank, local_rank, world, dist):
                 pass
     # N > 1: the batched decode step on every replica (one decoder of 256 sequences per GPU), same bracketing as `value`
     batched = None
-    if dist is not None and world > 1 and fused and (args.serve_slots or args.wide_streams) > 1 and not args.brief:
+    if args.full and dist is not None and world > 1 and fused and (args.serve_slots or args.wide_streams) > 1 and not args.brief:
         S = 256 if not stub else 8
         bbatch, err = None, None
         try:
@@ -797,9 +832,9 @@ def worker(args, rank, local_rank, world, dist):
         model.close()
         return 0
 
-    # ---- roofline of the dominant kernel: HIP events on the library's stream
+    # ---- roofline of the dominant kernel: HIP events on the library's stream (--full: runs of its own)
     roofline = None
-    if not stub:
+    if args.full and not stub:
         P = min(16, K)
         hip.prof_enable(True)
         for i in range(P):
@@ -899,7 +934,7 @@ def worker(args, rank, local_rank, world, dist):
         out["metric"] = "STUB (no GPU work): " + out["metric"]
         out["data"] = "none: --engine stub sleeps instead of decoding (launcher / rendezvous test only)"
         out["config"]["path"] = "stub"
-    secondary = world == 1 and not args.brief and not stub
+    secondary = args.full and world == 1 and not args.brief and not stub
     # secondary (median and mean per step): the same K steps again with a synchronise after each one,
     # i.e. the latency a caller that waits for every token sees (`value` above queues the K steps back to back)
     if secondary and fused:
@@ -1199,7 +1234,7 @@ def worker(args, rank, local_rank, world, dist):
         except Exception as e:
             out["dropin"] = {"tok_s": None, "note": "drop-in leg unavailable: %r" % (e,)}
     # the CPU path beside it: once per run, on rank 0, after the other ranks have exited
-    if not args.no_cpu_baseline and not args.brief and not stub:
+    if args.full and not args.no_cpu_baseline and not args.brief and not stub:
         try:
             out["cpu_baseline"] = cpu_baseline(host, cfg, args.mode, args.seed, args.cpu_steps)
         except Exception as e:                      # the baseline is a reported extra, never the product path

@@ -93,7 +93,7 @@ def test_one_global_prompt_queue_is_sharded_over_the_replicas(n):
     """north_star's multi-GPU split: `--gpus N` ranks take replicas.shard_prompts(n_prompts, rank, N) of ONE global queue
     through their own slots; the N > 1 line carries the aggregate serving rate beside the batch-1 rate, and every prompt
     is served exactly once (an all-reduced counter per prompt)"""
-    p = run_bench("--gpus", str(n), "--serve", "24")
+    p = run_bench("--gpus", str(n), "--serve", "24", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     r = result_line(p)
     sv = r["sharded_serving"]
@@ -111,7 +111,7 @@ def test_batched_aggregates_sit_at_the_top_level_with_their_own_efficiency(n):
     """round-4 verdict: at N GPUs `value` is N x batch-1 (BASELINE.json's metric) while one GPU does ~40 x that batched -- the N > 1
     line carries the aggregate of the batched step (every replica its own 256 sequences) and of the sharded serving queue at the
     top level, each with an efficiency against rank 0 alone, measured in the same run.  World 8 is the driver's SCALE run."""
-    p = run_bench("--gpus", str(n), "--serve", "16", timeout=600)
+    p = run_bench("--gpus", str(n), "--serve", "16", "--full", timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     r = result_line(p)
     assert r["n_gpus"] == n and len(r["per_rank"]) == n
@@ -130,16 +130,40 @@ def test_batched_aggregates_sit_at_the_top_level_with_their_own_efficiency(n):
 
 
 def test_a_lost_request_is_reported():
-    p = run_bench("--gpus", "2", "--serve", "24", env={"GTEN_BENCH_STUB_DROP_RANK": "1"})
+    p = run_bench("--gpus", "2", "--serve", "24", "--full", env={"GTEN_BENCH_STUB_DROP_RANK": "1"})
     assert p.returncode == 0, p.stderr[-2000:]
     assert result_line(p)["sharded_serving"]["every_prompt_served_exactly_once"] is False
 
 
 def test_brief_runs_skip_the_sharded_queue():
-    p = run_bench("--gpus", "2", "--brief")
+    p = run_bench("--gpus", "2", "--full", "--brief")
     assert p.returncode == 0, p.stderr[-2000:]
     r = result_line(p)
     assert "sharded_serving" not in r and "batched_decode" not in r
+
+
+def test_plain_runs_time_only_the_headline():
+    """without --full a run does only what `value` needs: no roofline, no secondary or N > 1 legs, no CPU baseline"""
+    for n in (1, 2):
+        p = run_bench("--gpus", str(n), "--serve", "16")
+        assert p.returncode == 0, p.stderr[-2000:]
+        r = result_line(p)
+        assert r["steps"] == 12 and r["ms_per_step"] > 0 and r["value"] > 0 and r["roofline"] is None
+        assert not {"sharded_serving", "batched_decode", "cpu_baseline", "multi_stream", "serving", "prefill"} & set(r)
+
+
+def test_dump_outputs_writes_the_timed_steps_ids(tmp_path):
+    import numpy as np
+    got = []
+    for k in (1, 2):
+        d = tmp_path / str(k)
+        p = run_bench("--gpus", "1", "--dump-outputs", str(d))
+        assert p.returncode == 0, p.stderr[-2000:]
+        ids = np.load(d / "step_ids.npy")
+        assert ids.dtype == np.float64 and ids.shape == (12,)
+        assert int(ids[-1]) == result_line(p)["config"]["last_token"]
+        got.append(ids)
+    assert np.array_equal(got[0], got[1])                  # seeded inputs: the same arguments, the same outputs
 
 
 def test_shards_partition_the_queue():

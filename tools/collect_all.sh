@@ -44,7 +44,7 @@ fi
 
 # ---- 2. the multi-sequence legs
 if has 2; then
-COMMON="--no-cpu-baseline --no-graph --no-lanes --prefill 0 --generate 0 --serve 0 --steps 4 --warmup 2 --fill prefill"
+COMMON="--full --no-cpu-baseline --no-graph --no-lanes --prefill 0 --generate 0 --serve 0 --steps 4 --warmup 2 --fill prefill"
 for S in 8 64 256; do
   if [ $S -eq 8 ]; then SEL="--streams 8 --wide-streams 0"; else SEL="--streams 0 --wide-streams $S"; fi
   for C in FETCH_SIZE WRITE_SIZE; do
@@ -52,7 +52,7 @@ for S in 8 64 256; do
     echo "lanes$S $C rc=$?"
   done
 done
-timeout -k 10 400 $RP --kernel-trace --stats -d $OUT/stats_lanes256 -- python3 $R/bench.py --no-cpu-baseline --streams 0 --wide-streams 256 --no-lanes --prefill 0 --generate 0 --serve 0 --steps 32 --warmup 8 --fill prefill > $OUT/lanes256_bench.json 2> $OUT/lanes256_bench.err
+timeout -k 10 400 $RP --kernel-trace --stats -d $OUT/stats_lanes256 -- python3 $R/bench.py --full --no-cpu-baseline --streams 0 --wide-streams 256 --no-lanes --prefill 0 --generate 0 --serve 0 --steps 32 --warmup 8 --fill prefill > $OUT/lanes256_bench.json 2> $OUT/lanes256_bench.err
 echo "stats lanes256 rc=$?"
 cp "$(first_csv $OUT/stats_lanes256)" $OUT/${TAG}_lanes256_kernel_stats.csv; rm -rf $OUT/stats_lanes256
 fi
@@ -64,7 +64,7 @@ for P in 512 2048; do
   echo "stats prefill $P rc=$?"
   cp "$(first_csv $OUT/stats_pf$P)" $OUT/${TAG}_prefill${P}_kernel_stats.csv; rm -rf $OUT/stats_pf$P
 done
-PRE="--no-cpu-baseline --no-graph --streams 0 --wide-streams 0 --generate 0 --serve 0 --steps 2 --warmup 1 --fill prefill --prefill 2048"
+PRE="--full --no-cpu-baseline --no-graph --streams 0 --wide-streams 0 --generate 0 --serve 0 --steps 2 --warmup 1 --fill prefill --prefill 2048"
 for C in SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE; do
   timeout -k 10 300 $RP --kernel-trace --pmc $C -d $OUT/prefill_$C -- python3 $R/bench.py $PRE > $OUT/prefill_$C.json 2> $OUT/prefill_$C.err
   echo "prefill $C rc=$?"
@@ -72,7 +72,7 @@ done
 fi
 # ---- 4. read requests by size
 if has 4; then
-COMMON="--no-cpu-baseline --no-graph --no-lanes --prefill 0 --generate 0 --serve 0 --steps 4 --warmup 2 --fill prefill"
+COMMON="--full --no-cpu-baseline --no-graph --no-lanes --prefill 0 --generate 0 --serve 0 --steps 4 --warmup 2 --fill prefill"
 for C in TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum; do
   timeout -k 10 420 $RP --kernel-trace --pmc $C -d $OUT/lanes256_$C -- python3 $R/bench.py $COMMON --streams 0 --wide-streams 256 > $OUT/lanes256_$C.json 2> $OUT/lanes256_$C.err
   echo "lanes256 $C rc=$?"

@@ -1,5 +1,5 @@
 """Where a multi-lane decode step's wall time goes, from a rocprofv3 kernel trace (run on the GPU box):
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --no-cpu-baseline --streams 0 --wide-streams 256 --no-lanes \
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --no-cpu-baseline --streams 0 --wide-streams 256 --no-lanes \
         --prefill 0 --generate 0 --serve 0 --steps 16 --warmup 4 --fill prefill
     python3 tools/lane_timeline.py DIR > gpurun_out/lane_timeline.txt
 Takes a window of four steps of decoder dispatches (k_dec_*), splits them by hardware queue (a lane's launch chain stays on one), and

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/pmc_prefill_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ( while sleep 40; do echo tick; done ) & HB=$!
-ARGS="--no-cpu-baseline --no-graph --streams 0 --wide-streams 0 --generate 0 --serve 0 --steps 2 --warmup 1 --fill prefill --prefill 2048"
+ARGS="--full --no-cpu-baseline --no-graph --streams 0 --wide-streams 0 --generate 0 --serve 0 --steps 2 --warmup 1 --fill prefill --prefill 2048"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS --output-format csv -d $OUT/p1 -- python3 $R/bench.py $ARGS > /dev/null 2> $OUT/p1.err
 echo "p1 rc=$?"
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES --output-format csv -d $OUT/p2 -- python3 $R/bench.py $ARGS > /dev/null 2> $OUT/p2.err
