@@ -137,16 +137,21 @@ int gten_hip_set_decode_exact(int on);
  * not possible through this interface; a caller that writes cache rows with its own kernels restarts the sequence --
  * slot_start / step at another position / generate_multi -- to the same effect). */
 int gten_hip_set_kv_head_major(int on);
-/* gate | up (with the silu . mul chain) and the lm_head of lanes of 49-64 or 128 rows (q4 / q8 weights, K = 2048) as the streamed
- * kernels of csrc/gten_decode_ffn.h (on != 0, the default) or as k_dec_mmvh (+ k_dec_silumul_rows for q8) like every other shape
- * (0): the same sums bit for bit (tests/test_ffn_streamed_gpu.py), a launch-structure switch only.
- * Takes effect for steps enqueued or captured afterwards. */
+/* gate | up (with the silu . mul chain) and the lm_head of lanes of 49-64 or 128 rows as the streamed kernels of
+ * csrc/gten_decode_ffn.h (on != 0, the default) or as the launches every other shape takes (0): k_dec_mmvh (+ k_dec_silumul_rows
+ * for q8) for q4 / q8 weights, k_dec_mmv_f16 + k_dec_silumul_rows_f16 (gate | up) or k_dec_mmv_f16 (lm_head) for f16.  The
+ * streamed forms are taken at K = n_embd = 2048 only (q4, q8 and f16 alike; the f16 lm_head from 16 384 rows), the one width whose
+ * K slices match the slab kernels' wave ranges: the same sums bit for bit at every width (tests/test_ffn_streamed_gpu.py,
+ * tests/test_decode_widths_gpu.py), a launch-structure switch only.  Takes effect for steps enqueued or captured afterwards. */
 int gten_hip_set_ffn_streamed(int on);
 /* The o and down projections of f16 decoders of 16+ sequences (fast forms) as EIGHT K planes of 64-feature workgroups
  * (csrc/gten_decode_wxp.h; on != 0, the default) or as k_dec_mmv_f16 in two planes (0).  The two differ in the association of the f32
- * sums only (not in any rounding point of the reference); every wide f16 decoder takes the same form, so sequences agree bit for bit
- * whatever the batch they are decoded in.  Takes effect for steps enqueued or captured afterwards: set it before creating decoders
- * that are to agree. */
+ * sums only (not in any rounding point of the reference); every wide f16 decoder takes the same form for o and down.  Not every
+ * projection does: where n_embd % 512 == 0, gate | up runs in two K planes except at 17-32 rows per lane, and q | k | v -- when it
+ * is not in the four-plane kernel (1, 2, 4 or 8 heads per kv head) -- in two up to 32 rows only.  So a sequence gets the same bits
+ * from wide f16 decoders of 48 and 64 sequences and from lanes (128+), and from those of 16 or 32 sequences only where these split
+ * every projection alike (tests/test_decode_widths_gpu.py: f16_split).  Takes effect for steps enqueued or captured afterwards: set
+ * it before creating decoders that are to agree. */
 int gten_hip_set_wx_planes(int on);
 /* host-only self-test of the registry behind that guarantee (which ranges are watched, which writes hit them, whose flag is
  * set): needs no GPU and no gten_hip_init; returns 0 or the number of the first failing case */
@@ -268,7 +273,9 @@ int gten_hip_decoder_create(const gten_hip_decoder_desc* desc, const gten_hip_la
  * SHARE every weight pass (weights are streamed once per step, not once per sequence).  Per sequence
  * the results are bit-identical to the single-sequence decoder for n_seq <= 8 (n_seq >= 16: the linears follow
  * the matrix-core kernel's block order, i.e. the prefill numerics).  desc->logits is ignored: read a
- * sequence's logits with gten_hip_decoder_logits_seq.  All sequences are at the same position n. */
+ * sequence's logits with gten_hip_decoder_logits_seq.  All sequences are at the same position n.  Widths: those of
+ * gten_hip_decoder_create (n_embd <= 2048, n_ffn <= 6144); n_seq >= 16 also wants n_embd and n_ffn % 256 == 0, and q8 weights
+ * n_ffn <= 5632 (the down projection's weight slab). */
 int gten_hip_decoder_create_multi(const gten_hip_decoder_desc* desc, const gten_hip_layer_ptrs* layers,
                                   const gten_hip_kv_ptrs* kv, int n_seq, gten_hip_decoder** out);
 int gten_hip_decoder_destroy(gten_hip_decoder* dec);

@@ -480,7 +480,8 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     constexpr bool F16W = (WT == GTEN_F16);
     constexpr int NE = F16W ? 4 : 1;              // passes over an n_embd-wide row (<= 2048)
     constexpr int NF = F16W ? 11 : 3;             // passes over an n_ffn-wide row (<= 5632 / 6144)
-    const bool wideF = F16W ? (F > 2048) : (F > 2048);
+    constexpr int NF12 = F16W ? 12 : NF;          // f16 n_ffn past 5632 (<= 6144): twelve (eleven would leave the row's tail out of the sums)
+    const bool wideF = F > 2048, widerF = F16W && F > NF * 512;
     float* xbuf = (float*)dc->xbuf;
     float* hbuf = (float*)dc->hbuf;
     int rc;
@@ -526,8 +527,9 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
         dn.step = dc->step; dn.d_in = F; dn.n_mats = 1; set_mat(dn, 0, L.wdown, WT, E, F); dn.out = dc->down_raw;
         dn.act_q = dc->act_q; dn.act_d = dc->act_d; dn.act_sum = dc->act_sum;
         dn.act_f = dc->act_f;
-        rc = wideF ? launch_gemv8<WT, PRO_ACTQ8, NF, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E)
-                   : launch_gemv8<WT, PRO_ACTQ8, NE, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E);
+        rc = widerF ? launch_gemv8<WT, PRO_ACTQ8, NF12, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E)
+             : wideF ? launch_gemv8<WT, PRO_ACTQ8, NF, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E)
+                     : launch_gemv8<WT, PRO_ACTQ8, NE, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E);
         if (rc) return rc;
     }
     Gemv8Args hd{};
@@ -589,9 +591,9 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     const int E = d.n_embd, F = d.n_ffn, dh = E / d.n_heads, KV = dh * d.n_kv_heads, V = d.n_vocab;
     const size_t kv_pitch = gten_hip_row_bytes(d.adtype, KV);
     constexpr bool F16W = (WT == GTEN_F16);
-    constexpr int NE = F16W ? 4 : 1, NF = F16W ? 11 : 3;
+    constexpr int NE = F16W ? 4 : 1, NF = F16W ? 11 : 3, NF12 = F16W ? 12 : NF;      // (as enqueue_step_q8act)
     constexpr int RH = F16W ? 2 : 4;              // lm_head rows per wave
-    const bool wideF = F > 2048;
+    const bool wideF = F > 2048, widerF = F16W && F > NF * 512;
     float* xbuf = (float*)dc->xbuf;
     float* hbuf = (float*)dc->hbuf;
     int rc;
@@ -662,7 +664,8 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
         Gemv8Args dn = base;
         dn.d_in = F; dn.n_mats = 1; set_mat(dn, 0, L.wdown, WT, E, F); dn.out = dc->down_raw; dn.raw_stride = E;
         dn.act_q = dc->act_q; dn.act_d = dc->act_d; dn.act_sum = dc->act_sum; dn.act_f = dc->act_f;
-        rc = wideF ? launch_gemvm<WT, NF, 2, S, 256>(KT_DEC_GEMV_DOWN, dn, E) : launch_gemvm<WT, NE, 2, S, 256>(KT_DEC_GEMV_DOWN, dn, E);
+        rc = widerF ? launch_gemvm<WT, NF12, 2, S, 256>(KT_DEC_GEMV_DOWN, dn, E)
+             : wideF ? launch_gemvm<WT, NF, 2, S, 256>(KT_DEC_GEMV_DOWN, dn, E) : launch_gemvm<WT, NE, 2, S, 256>(KT_DEC_GEMV_DOWN, dn, E);
         if (rc) return rc;
     }
     Gemv8Args sf = base;
@@ -1119,9 +1122,10 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
         } else if (folded && WT == GTEN_Q8 && g_ffn_streamed && (S + 15) / 16 == 4 && E == 2048 && ks_gu == 2 && F % 32 == 0) {
             DEC_LAUNCH(KT_DEC_GEMV_GATEUP, (k_dec_ffn_q8<true, true>), dim3(F / 32), dim3(512), (size_t)2 * 4 * 4 * 1024, (const uint16_t*)b.stg_q, L.wgate, L.wup,
                        (uint16_t*)b.act_q, E, F, S, 0, 4);
-        } else if (WT == GTEN_F16 && g_ffn_streamed && ((S + 15) / 16 == 4 || S == 128) && E % 256 == 0 && (E / 128) % 2 == 0 && ks_gu == 2 && F % 32 == 0) {
+        } else if (WT == GTEN_F16 && g_ffn_streamed && ((S + 15) / 16 == 4 || S == 128) && E == 2048 && ks_gu == 2 && F % 32 == 0) {
             // f16: gate | up and the chain of a lane of four row tiles as one streamed launch (gten_decode_ffn.h) -- the bits of the
-            // k_dec_mmv_f16 + k_dec_silumul_rows_f16 pair below
+            // k_dec_mmv_f16 + k_dec_silumul_rows_f16 pair below.  Only at K = 2048: the kernel's K slices are four 32-element steps,
+            // the pair's wave ranges K / 16 elements (at K = 512 .. 1536 the f32 sums would associate differently)
             DEC_LAUNCH(KT_DEC_GEMV_GATEUP, k_dec_ffn_f16<true>, dim3(F / 32), dim3(512), (size_t)2 * 4 * 4 * 1024, (const uint16_t*)b.stg_q, (const uint16_t*)L.wgate,
                        (const uint16_t*)L.wup, (uint16_t*)b.act_q, E, F, S, (S + 15) / 16, 0);
         } else {
@@ -1270,6 +1274,10 @@ static int decoder_create_common(const gten_hip_decoder_desc* desc, const gten_h
                 "decoder_create: n_seq %d not in {1, 2, 4, 8, 16, 32, 48, 64, 128, 192, 256, 384, 512}", n_seq);
     GTR_REQUIRE(!wide || (d.n_ffn % 256 == 0 && d.n_embd % 256 == 0 && (dh * d.n_kv_heads) % 16 == 0),
                 "decoder_create: n_seq >= 16 runs the W.x on the matrix cores: n_embd and n_ffn %% 256 == 0");
+    // (q8 weights: a down-projection workgroup holds its 16 features x n_ffn bytes of weights in MMV_MAXP pieces per thread --
+    //  launch_mmvh / launch_mmv refuse a longer K at the first step, so refuse the decoder here)
+    GTR_REQUIRE(!wide || d.wdtype != GTEN_Q8 || d.n_ffn <= MMV_MAXP * 512,
+                "decoder_create: q8 weights with n_seq >= 16 want n_ffn <= %d (the down projection's weight slab), got %d", MMV_MAXP * 512, d.n_ffn);
     GTR_REQUIRE(n_seq == 1 || (kv && dh == 64), "decoder_create: multi-sequence decode needs the cache table and d_head 64");
     GTR_REQUIRE(n_seq > 1 || d.logits, "decoder_create: null logits pointer");
     if (n_seq > 1)

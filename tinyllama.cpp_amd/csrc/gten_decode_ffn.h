@@ -381,7 +381,8 @@ __global__ __launch_bounds__(512, FFN_OCC) void k_dec_ffn_q8(const uint16_t* __r
 // lane's activation rows) + k_dec_silumul_rows_f16.  Nothing to expand: a K slice is four 32-element steps x 64 weight rows = 1024
 // pieces of 16 bytes (two per thread: row, step, k-group -- 256 contiguous bytes per row), COPIED into the double-buffered chunk in
 // matrix-operand order; a wave's activation fragment is 16 bytes of its row tile's f16 rows (k_dec_mmv_f16's operands, natural element
-// order).  THE SAME SUMS as the pair, bit for bit: sixteen slices of four steps -- the eight wave ranges of k_dec_mmv_f16's first K
+// order).  THE SAME SUMS as the pair, bit for bit, at K = 2048 (the only width the launcher takes it at: elsewhere a wave range of
+// k_dec_mmv_f16 is not four steps long): sixteen slices of four steps -- the eight wave ranges of k_dec_mmv_f16's first K
 // plane, then the second's -- each accumulated in the matrix core from zero, added in order inside their plane; then
 // k_dec_silumul_rows_f16's arithmetic per element (plane 0 + plane 1, rounded to f16 where the modules store: gate, silu, up, product).
 // `frt` row tiles (1 .. 4: the f16 lanes are 64 rows): waves frt .. 7 copy weights and keep the barriers.

@@ -14,7 +14,8 @@
 // n_embd / 64 x 8 workgroups (256 for TinyLlama), each reading rows x K / 8 x 2 bytes of activations: a quarter of the bytes per CU.
 // The sums differ from k_dec_mmv_f16's in the association of the f32 additions only (eight plane sums of NBK steps each, added in plane
 // order, instead of two planes of eight wave ranges); EVERY f16 decoder of 16+ sequences takes this kernel for the shape, so lanes of
-// 128 rows, 64-sequence and 16-sequence decoders agree bit for bit (tests/test_multiseq_gpu.py, tests/test_ffn_streamed_gpu.py).
+// 128 rows, 64-sequence and 16-sequence decoders agree bit for bit where their other projections split K alike (include/gten_hip.h,
+// gten_hip_set_wx_planes; tests/test_multiseq_gpu.py, tests/test_ffn_streamed_gpu.py, tests/test_decode_widths_gpu.py).
 // (The q4 / q8 analogue was built and measured in this round and is not in the library: +1.8 % for 1.1 GB more planes per step,
 //  tools/experiments/gten_decode_wxp.h; for f16 the same change is 26.9 -> 9 us on the largest launch of the step.)
 // Up to three matrices concatenated along the output (q | k | v: every one a multiple of 64 wide, so a workgroup's 64 columns lie in one):
