@@ -24,7 +24,9 @@
 // then:       head (final norm + lm_head) -> argmax
 #include "gten_dev.h"
 #include "gten_rt.h"
+#include "gten_hip_sample.h"
 
+#include <cmath>
 #include <vector>
 #include <algorithm>
 
@@ -92,6 +94,7 @@ enum { EPI_RAW = 0, EPI_SILUMUL = 1, EPI_STAGE = 2, EPI_STAGE_FRAG = 3 };
 #include "gten_decode_attn_exact64.h"
 #include "gten_decode_attn_wide.h"
 #include "gten_decode_attn_hm.h"
+#include "gten_decode_sample.h"
 
 // --------------------------------------------------------------- host side
 
@@ -139,6 +142,13 @@ struct gten_hip_decoder {
     // left out of the step (its launch chain costs what a full lane costs however few slots are live); index = lane mask
     hipGraph_t graph_m[1 << DEC_MAX_LANES] = {}, graph_km[1 << DEC_MAX_LANES] = {};
     hipGraphExec_t exec_m[1 << DEC_MAX_LANES] = {}, exec_km[1 << DEC_MAX_LANES] = {};
+    // top-k sampling (gten_hip_decoder_set_sampling): every sequence's request on the device and on the host; while no sequence
+    // samples the step ends in k_dec_argmax (the graphs above), once one does in k_dec_sample -- the same graphs once more
+    SampleParam* samp = nullptr;        // [n_seq]
+    std::vector<SampleParam> samp_host;
+    int n_sampling = 0;                 // sequences with top_k >= 1
+    hipGraph_t s_graph = nullptr, s_graph_k = nullptr, s_graph_m[1 << DEC_MAX_LANES] = {}, s_graph_km[1 << DEC_MAX_LANES] = {};
+    hipGraphExec_t s_exec = nullptr, s_exec_k = nullptr, s_exec_m[1 << DEC_MAX_LANES] = {}, s_exec_km[1 << DEC_MAX_LANES] = {};
     unsigned lane_mask = 0;             // lanes the NEXT enqueue takes (0: all)
     int last_run_lanes = 0;             // lanes the last gten_hip_decoder_run took
     const float2* rope = nullptr;
@@ -170,7 +180,7 @@ struct gten_hip_decoder {
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
     int n_seq;
-    DecStep* step; int32_t* tokens; int32_t* result;
+    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -186,7 +196,7 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     const size_t planes = dc->n_seq >= 16 ? 2 : 1, H = (size_t)d.n_heads, C = (size_t)dc->n_chunks;
     LaneBufs b;
     b.n_seq = (int)SL;
-    b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2);
+    b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->samp + o;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -537,8 +547,12 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
-    DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(1), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
-               dc->n_best, dc->step, dc->result, 0, 0, dc->tokens, d.max_ctx + 1);
+    if (dc->n_sampling > 0)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1);
+    else
+        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(1), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
+                   dc->n_best, dc->step, dc->result, 0, 0, dc->tokens, d.max_ctx + 1);
     return 0;
 }
 
@@ -677,8 +691,12 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
-               dc->n_best, dc->step, dc->result, dc->n_best, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
+    if (dc->n_sampling > 0)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
+    else
+        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
+                   dc->n_best, dc->step, dc->result, dc->n_best, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
     return 0;
 }
 
@@ -1148,8 +1166,12 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     sf.act_q = b.stg_q; sf.act_d = b.stg_d; sf.act_sum = b.stg_sum; sf.act_f = b.stg_f;
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
-    DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)b.logits_m, (const int*)nullptr,
-               V, b.step, b.result, V, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
+    if (dc->n_sampling > 0)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
+                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
+    else
+        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)b.logits_m, (const int*)nullptr,
+                   V, b.step, b.result, V, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
     return 0;
 }
 
@@ -1336,6 +1358,9 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     GTR_CHECK(hipMemset(dc->tokens, 0, S * (size_t)(d.max_ctx + 1) * 4));
     GTR_CHECK(hipMalloc((void**)&dc->result, S * (size_t)(d.max_ctx + 2) * 4));
     GTR_CHECK(hipMemset(dc->result, 0, S * (size_t)(d.max_ctx + 2) * 4));
+    GTR_CHECK(hipMalloc((void**)&dc->samp, S * sizeof(SampleParam)));
+    GTR_CHECK(hipMemset(dc->samp, 0, S * sizeof(SampleParam)));              // every sequence greedy
+    dc->samp_host.assign(S, SampleParam{});
     const size_t planes = wide ? 2 : 1;                       // k_dec_mmv may split K over two workgroups: one output plane each
     GTR_CHECK(hipMalloc((void**)&dc->qkv_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)(E + 2 * KV) * 4));
     GTR_CHECK(hipMalloc((void**)&dc->proj_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)E * 4));      // (k_dec_wxp_f16: eight K planes)
@@ -1522,12 +1547,20 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
         if (dc->graph_m[m]) rel(hipGraphDestroy(dc->graph_m[m]));
         if (dc->exec_km[m]) rel(hipGraphExecDestroy(dc->exec_km[m]));
         if (dc->graph_km[m]) rel(hipGraphDestroy(dc->graph_km[m]));
+        if (dc->s_exec_m[m]) rel(hipGraphExecDestroy(dc->s_exec_m[m]));
+        if (dc->s_graph_m[m]) rel(hipGraphDestroy(dc->s_graph_m[m]));
+        if (dc->s_exec_km[m]) rel(hipGraphExecDestroy(dc->s_exec_km[m]));
+        if (dc->s_graph_km[m]) rel(hipGraphDestroy(dc->s_graph_km[m]));
     }
+    if (dc->s_exec) rel(hipGraphExecDestroy(dc->s_exec));
+    if (dc->s_graph) rel(hipGraphDestroy(dc->s_graph));
+    if (dc->s_exec_k) rel(hipGraphExecDestroy(dc->s_exec_k));
+    if (dc->s_graph_k) rel(hipGraphDestroy(dc->s_graph_k));
     kv_watch_remove(dc, nullptr);
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv};
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
     for (int g = 1; g < DEC_MAX_LANES; g++) {
@@ -1637,8 +1670,9 @@ static int run_steps_free(gten_hip_decoder* dc, int count)
     if (int rc = pre_run(dc)) return rc;
     if (prof_on()) { for (int i = 0; i < count; i++) if (int rc = run_step(dc, 0)) return rc; return 0; }
     const unsigned gs = graph_slot(dc);
-    hipGraph_t& graph_k = gs ? dc->graph_km[gs] : dc->graph_k;
-    hipGraphExec_t& exec_k = gs ? dc->exec_km[gs] : dc->exec_k;
+    const bool smp = dc->n_sampling > 0;
+    hipGraph_t& graph_k = smp ? (gs ? dc->s_graph_km[gs] : dc->s_graph_k) : (gs ? dc->graph_km[gs] : dc->graph_k);
+    hipGraphExec_t& exec_k = smp ? (gs ? dc->s_exec_km[gs] : dc->s_exec_k) : (gs ? dc->exec_km[gs] : dc->exec_k);
     while (count >= DEC_GRAPH_STEPS) {
         if (!exec_k) {
             GTR_CHECK(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
@@ -1663,8 +1697,9 @@ static int run_step(gten_hip_decoder* dc, int use_graph)
     if (int rc = pre_run(dc)) return rc;
     if (!use_graph || prof_on()) return enqueue(dc);    // event pairs cannot be recorded into a capture
     const unsigned gs = graph_slot(dc);
-    hipGraph_t& graph = gs ? dc->graph_m[gs] : dc->graph;
-    hipGraphExec_t& exec = gs ? dc->exec_m[gs] : dc->exec;
+    const bool smp = dc->n_sampling > 0;
+    hipGraph_t& graph = smp ? (gs ? dc->s_graph_m[gs] : dc->s_graph) : (gs ? dc->graph_m[gs] : dc->graph);
+    hipGraphExec_t& exec = smp ? (gs ? dc->s_exec_m[gs] : dc->s_exec) : (gs ? dc->exec_m[gs] : dc->exec);
     if (!exec) {
         GTR_CHECK(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
         const int rc = enqueue(dc);
@@ -2208,6 +2243,65 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
     GTR_CHECK(hipMemcpyAsync(logits_host, src, (size_t)dc->d.n_vocab * 4, hipMemcpyDeviceToHost, stream()));
     GTR_CHECK(hipStreamSynchronize(stream()));
     return persist_aborted(dc);
+}
+
+// ---- top-k sampling (include/gten_hip_sample.h, gten_decode_sample.h)
+static int sample_check(int top_k, float temp, const char* who)
+{
+    GTR_REQUIRE(top_k >= 0, "%s: top_k %d < 0", who, top_k);
+    GTR_REQUIRE(top_k == 0 || (std::isfinite(temp) && temp > 0.f), "%s: temperature %g must be finite and > 0 when top_k >= 1", who, (double)temp);
+    return 0;
+}
+
+int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, float temp, uint64_t seed, uint32_t stream_id)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_sampling: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    if (int rc = sample_check(top_k, temp, "decoder_set_sampling")) return rc;
+    GTR_REQUIRE(top_k == 0 || !dc->persist_on, "decoder_set_sampling: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    SampleParam& p = dc->samp_host[(size_t)seq];
+    dc->n_sampling += (top_k > 0 ? 1 : 0) - (p.top_k > 0 ? 1 : 0);
+    p = SampleParam{};
+    p.top_k = top_k;
+    p.temp = top_k > 0 ? temp : 0.f;
+    p.stream = stream_id;
+    p.seed_lo = (unsigned)(seed & 0xffffffffu);
+    p.seed_hi = (unsigned)(seed >> 32);
+    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+static SampleRowParam* g_rows_dev = nullptr;      // gten_hip_sample_rows' per-row requests (grow-only)
+static size_t g_rows_cap = 0;
+
+int gten_hip_sample_rows(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* top_k_host, const float* temp_host,
+                         uint64_t seed, const uint32_t* stream_host, const int32_t* position_host, int32_t* out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0, "sample_rows: %d rows of %d logits (n_vocab in [1, 65535]), stride %lld",
+                n_rows, n_vocab, row_stride);
+    if (n_rows == 0) return 0;
+    GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host, "sample_rows: null argument");
+    std::vector<SampleRowParam> rows((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows")) return rc;
+        GTR_REQUIRE(position_host[r] >= 0, "sample_rows: position %d of row %d", position_host[r], r);
+        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
+    }
+    if (g_rows_cap < (size_t)n_rows) {
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        if (g_rows_dev) GTR_CHECK(hipFree(g_rows_dev));
+        g_rows_dev = nullptr;
+        g_rows_cap = 0;
+        GTR_CHECK(hipMalloc((void**)&g_rows_dev, (size_t)n_rows * sizeof(SampleRowParam)));
+        g_rows_cap = (size_t)n_rows;
+    }
+    GTR_CHECK(hipMemcpyAsync(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam), hipMemcpyHostToDevice, stream()));
+    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, (const SampleRowParam*)g_rows_dev,
+               (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
+    return 0;
 }
 
 } // extern "C"

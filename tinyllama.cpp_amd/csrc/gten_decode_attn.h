@@ -484,6 +484,18 @@ __global__ __launch_bounds__(256) void k_dec_attn_one64(const unsigned long long
 }
 
 
+// The bookkeeping behind a step's id (one thread): result[n], the next input token when advance & 2, the advance of n.
+// Shared by k_dec_argmax and the sampler (gten_decode_sample.h).
+__device__ __forceinline__ void dec_pick_commit(DecStep* step, int32_t* __restrict__ result, int32_t* __restrict__ tokens, int idx)
+{
+    const int n = step->n;
+    result[n] = idx;                       // the id of the step that computed row n-1
+    const int adv = step->advance;
+    if (adv & 2) tokens[n] = idx;          // generation: the next step embeds it (tinyllama.cpp:426)
+    const int stop = step->stop;
+    if ((adv & 1) && (stop <= 0 || n < stop)) step->n = n + 1;          // free-running replay: the next launch decodes row n
+}
+
 // greedy argmax, strict '>' so the first maximum wins (tinyllama.cpp:416-424).
 // Works on (value, index) candidates: either the logits themselves (idx == null)
 // or the per-wave winners the lm_head kernel left behind.
@@ -518,11 +530,6 @@ __global__ __launch_bounds__(1024) void k_dec_argmax(const float* __restrict__ v
         for (int w = 1; w < (int)(blockDim.x >> 6); w++)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         if (idx == 0x7fffffff) idx = 0;
-        const int n = step->n;
-        result[n] = idx;                       // argmax of the step that computed row n-1
-        const int adv = step->advance;
-        if (adv & 2) tokens0[(size_t)blockIdx.x * tok_stride + n] = idx;   // greedy generation: the next step embeds it (tinyllama.cpp:426)
-        const int stop = step->stop;
-        if ((adv & 1) && (stop <= 0 || n < stop)) step->n = n + 1;          // free-running replay: the next launch decodes row n
+        dec_pick_commit(step, result, tokens0 + (size_t)blockIdx.x * tok_stride, idx);
     }
 }

@@ -95,6 +95,8 @@ class GtenHip:
         "gten_hip_decoder_lane_info", "gten_hip_set_lane_skip", "gten_hip_decoder_slot_start", "gten_hip_decoder_slot_start_until", "gten_hip_decoder_slot_park", "gten_hip_decoder_slot_bind", "gten_hip_decoder_slots_apply", "gten_hip_decoder_run", "gten_hip_decoder_run_lanes", "gten_hip_decoder_slot_ids", "gten_hip_decoder_slot_ids_all",
         "gten_hip_set_kv_head_major", "gten_hip_decoder_kv_info", "gten_hip_kv_watch_selftest", "gten_hip_set_ffn_streamed", "gten_hip_set_wx_planes",
     ]
+    # include/gten_hip_sample.h (top-k sampling on the device)
+    SAMPLE_SYMBOLS = ["gten_hip_decoder_set_sampling", "gten_hip_sample_rows"]
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -141,6 +143,8 @@ class GtenHip:
         self._persist_status = _sig(L, "gten_hip_persist_status", ci, [C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.c_void_p, ci])
         self._set_row_segments = _sig(L, "gten_hip_set_row_segments", ci, [C.c_void_p, ci])
         self._copy_ranges = _sig(L, "gten_hip_copy_ranges", ci, [C.c_void_p, ci])
+        self._set_sampling = _sig(L, "gten_hip_decoder_set_sampling", ci, [vp, ci, ci, C.c_float, C.c_uint64, C.c_uint32])
+        self._sample_rows = _sig(L, "gten_hip_sample_rows", ci, [vp, ci, ci, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp])
         self.initialised = False
 
     # -- runtime
@@ -185,6 +189,26 @@ class GtenHip:
             _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("bytes", C.c_size_t)]
         arr = (R * len(ranges))(*[R(int(d), int(s), int(b)) for d, s, b in ranges])
         self._check(self._copy_ranges(C.cast(arr, C.c_void_p), len(ranges)))
+
+    def sample_rows(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed, stream, position):
+        """ids of gten_hip_sample_rows (include/gten_hip_sample.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride
+        elements; top_k / temp / stream / position per row (scalars are broadcast).  Returns int32[n_rows]."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        out = DeviceBuffer(self, max(4 * n_rows, 4))
+        self._check(self._sample_rows(logits.ptr, n_rows, n_vocab, row_stride, kp, tp, C.c_uint64(int(seed)), sp, pp, out.ptr))
+        return out.download(np.int32)[:n_rows].copy()
+
+    def sample_rows_rc(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed=0, stream=0, position=1):
+        """the return code of one gten_hip_sample_rows call (argument checks); out is a scratch word"""
+        k, t = np.full(max(n_rows, 1), top_k, np.int32), np.full(max(n_rows, 1), temp, np.float32)
+        s, p = np.full(max(n_rows, 1), stream, np.uint32), np.full(max(n_rows, 1), position, np.int32)
+        out = DeviceBuffer(self, 4 * max(n_rows, 1))
+        return self._sample_rows(logits.ptr, n_rows, n_vocab, row_stride, k.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                 C.c_uint64(int(seed)), s.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p), out.ptr)
 
     def set_decode_exact(self, on):
         """exact forms of the decode step for decoders created from now on (include/gten_hip.h)"""

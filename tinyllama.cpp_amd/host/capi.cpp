@@ -5,15 +5,11 @@
 #include <cstring>
 #include <memory>
 
+#include "capi_handles.h"
 #include "tinyllama_model.h"
 #include "tokenizer.h"
 
 using namespace gten;
-
-struct gten_host_model {
-    gten_host_config cfg;
-    std::unique_ptr<TinyLlama> model;
-};
 
 namespace {
 
@@ -183,11 +179,6 @@ int gten_host_model_decode_result(gten_host_model* m, int n, int32_t* argmax_out
 }
 
 // ---- several sequences sharing one copy of the weights
-struct gten_host_batch {
-    gten_host_config cfg;
-    std::unique_ptr<TinyLlamaBatch> batch;
-};
-
 gten_host_batch* gten_host_batch_create(const gten_host_config* cfg, int n_seq)
 {
     if (!cfg || !(n_seq == 2 || n_seq == 4 || n_seq == 8 || (n_seq >= 16 && n_seq <= 64 && n_seq % 16 == 0) || (n_seq > 64 && n_seq <= 256 && n_seq % 64 == 0) || n_seq == 384 || n_seq == 512)) return nullptr;

@@ -1,0 +1,17 @@
+// capi_handles.h -- the handles behind include/gten_host.h's opaque types, shared by host/capi.cpp and host/capi_sample.cpp.
+#pragma once
+
+#include <memory>
+
+#include "../../include/gten_host.h"
+#include "tinyllama_model.h"
+
+struct gten_host_model {
+    gten_host_config cfg;
+    std::unique_ptr<gten::TinyLlama> model;
+};
+
+struct gten_host_batch {
+    gten_host_config cfg;
+    std::unique_ptr<gten::TinyLlamaBatch> batch;
+};

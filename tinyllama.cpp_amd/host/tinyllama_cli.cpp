@@ -63,31 +63,19 @@ static void run_greedy(const Options& o, std::string prompt, TinyLlama& model, T
     (o.ids ? std::cout : std::cerr) << '\n';
 }
 
-// top-k sampling (tinyllama.cpp:442-507): logits / temp, the k largest, softmax over them, one draw
-static void run_topk(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok)
+// top-k sampling (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler
+// (include/gten_hip_sample.h): the prompt's first id drawn from its logits in HBM, every later one inside the decode step.
+// The draw is keyed by (seed, stream, position): stream = the chat turn (0 for -p).
+static void run_topk(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
 {
-    std::mt19937 gen(o.seeded ? (uint32_t)o.seed : std::random_device{}());
     std::vector<int> enc = tok.encode(prompt);
     std::vector<int32_t> tokens(enc.begin(), enc.end());
-    tokens.reserve((size_t)o.n_predict);
-    const int n_vocab = model.params.n_vocab, k = std::min(o.topk, n_vocab);
-    std::vector<std::pair<double, int>> cand;
-    const int n_new = o.n_predict - (int)tokens.size();
-    for (int i = 0; i < n_new; i++) {
-        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
-        Tensor logits = model.logits(input, i == 0 ? 0 : input.numel() - 1);
-        const float* lg = const_cast<const Tensor&>(logits).data_ptr<float>();
-        cand.clear();
-        for (int j = 0; j < n_vocab; j++) cand.emplace_back((double)lg[j] / o.temp, j);
-        std::partial_sort(cand.begin(), cand.begin() + k, cand.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        std::vector<double> w((size_t)k);
-        for (int j = 0; j < k; j++) w[(size_t)j] = std::exp(cand[(size_t)j].first - cand[0].first);
-        std::discrete_distribution<int> dist(w.begin(), w.end());
-        const int id = cand[(size_t)dist(gen)].second;
-        if (id == tok.eos) break;
-        emit(o, tok, i == 0 ? 1 : tokens.back(), id);
-        tokens.push_back(id);
+    const size_t n_prompt = tokens.size();
+    if (sampled_generate(model, tokens, o.n_predict, tok.eos, o.topk, o.temp, seed, turn) < 0) {
+        std::cerr << "error: " << gten_hip_last_error() << "\n";
+        std::exit(EXIT_FAILURE);
     }
+    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
     (o.ids ? std::cout : std::cerr) << '\n';
 }
 
@@ -150,9 +138,15 @@ int main(int argc, char const* argv[])
     model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
 
+    uint64_t seed = o.seed;
+    if (!o.seeded) {
+        std::random_device rd;
+        seed = ((uint64_t)rd() << 32) | (uint64_t)rd();
+    }
+    uint32_t turn = 0;
     auto answer = [&](const std::string& prompt) {
         if (o.greedy) run_greedy(o, prompt, model, tokenizer);
-        else run_topk(o, prompt, model, tokenizer);
+        else run_topk(o, prompt, model, tokenizer, seed, turn++);
     };
     if (o.prompt.empty()) {
         std::cout << "Chat interface. Write your prompt and press enter to submit. Enter q or press ctrl+c to quit.\n";

@@ -25,6 +25,7 @@
 #include <deque>
 
 #include "../gten/gten.h"
+#include "../../include/gten_hip_sample.h"
 #include "synth.h"
 
 namespace gten {
@@ -195,6 +196,15 @@ public:
         GTEN_HIP_OK(gten_hip_decoder_generate(dec_, n_first, max_new, eos, out, &got));
         (void)lm_head_.acv.device_ptr_mut();          // the steps wrote logits in HBM: host mirror is stale
         return got;
+    }
+
+    // the request every later step of this model's decoder samples with (include/gten_hip_sample.h; top_k 0: greedy again).
+    // (only the sampled entry points call it: host/capi_sample.cpp, the command line program)
+    // Returns the library's code: a persistent decoder refuses top_k >= 1 (gten_hip_last_error says why)
+    int decode_set_sampling(int top_k, float temp, uint64_t seed, uint32_t stream)
+    {
+        ensure_decoder();
+        return gten_hip_decoder_set_sampling(dec_, 0, top_k, temp, seed, stream);
     }
 
     ~TinyLlama()
@@ -483,6 +493,15 @@ public:
     void prefill_many(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
                       std::vector<float*>* logits_out = nullptr)
     {
+        prefill_many_with(slots, prompts, first, logits_out, [](int, const float* lg, int n, int32_t* out) {
+            GTEN_HIP_OK(gten_hip_argmax_row(lg, n, out));
+        });
+    }
+    // ... with the first id of prompt k (its logits row lg on the device) written to out by pick(k, lg, n_vocab, out)
+    template <class Pick>
+    void prefill_many_with(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
+                           std::vector<float*>* logits_out, Pick pick)
+    {
         const int K = (int)slots.size();
         GTEN_ASSERTM(K >= 1 && K <= kPreMax && prompts.size() == slots.size(), "prefill_many: %d prompts", K);
         if (!pre_) {
@@ -521,7 +540,7 @@ public:
         int32_t* ids_dev = (int32_t*)first_ids_->device_ptr_mut();
         for (int k = 0; k < K; k++) {
             const Tensor lg = pre_->logits_of_row(hidden, starts[(size_t)k + 1] - 1);
-            GTEN_HIP_OK(gten_hip_argmax_row((const float*)lg.device_ptr(), lg.numel(), ids_dev + k));
+            pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
             if (logits_out && (*logits_out)[(size_t)k])
                 std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
         }
@@ -549,6 +568,28 @@ public:
         return best_i;
     }
 
+    // prefill() with the first id drawn by the device sampler (include/gten_hip_sample.h) at position prompt.size()
+    int prefill_sampled(int seq_i, const std::vector<int32_t>& prompt, int top_k, float temp, uint64_t seed, uint32_t stream)
+    {
+        const int32_t pos = (int32_t)prompt.size();
+        auto pick = [&](int, const float* lg, int n, int32_t* out) {
+            GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &top_k, &temp, seed, &stream, &pos, out));
+        };
+        if (batched_prompts() && (int)prompt.size() >= 16 && (int)prompt.size() <= kPreRows) {
+            std::vector<int> first;
+            std::vector<float*> lo{nullptr};
+            prefill_many_with({seq_i}, {&prompt}, &first, &lo, pick);
+            return first[0];
+        }
+        Tensor tk(prompt.data(), {(int)prompt.size()}, kInt32);
+        const Tensor lg = cset(seq_i).logits(tk, 0);
+        Tensor id({1}, kInt32);
+        pick(0, (const float*)lg.device_ptr(), lg.numel(), (int32_t*)id.device_ptr_mut());
+        int32_t got = -1;
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&got, id.device_ptr(), sizeof(got)));
+        return got;
+    }
+
     void decode_set_tokens(int seq_i, const int32_t* ids, int first, int count)
     {
         ensure_decoder();
@@ -572,6 +613,12 @@ public:
     {
         ensure_decoder();
         GTEN_HIP_OK(gten_hip_decoder_generate_multi(dec_, n_first, max_new_seq, max_new, eos, out, n_out));
+    }
+    // sequence seq_i's sampling request (include/gten_hip_sample.h; top_k 0: greedy again)
+    int decode_set_sampling(int seq_i, int top_k, float temp, uint64_t seed, uint32_t stream)
+    {
+        ensure_decoder();
+        return gten_hip_decoder_set_sampling(dec_, seq_i, top_k, temp, seed, stream);
     }
     // asynchronous: row n[q]-1 of sequence q (continuous batching)
     void decode_step_ragged(const int* n_per_seq, bool use_graph)
@@ -628,6 +675,51 @@ public:
     // (max_new_each, when given, bounds the new ids of prompt j by max_new_each[j] instead of max_new)
     ServeStats serve(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
                      std::vector<std::vector<int32_t>>* out, int max_new = 0, const int32_t* max_new_each = nullptr)
+    {
+        GreedyServe greedy;
+        return serve_with(prompts, max_tokens, eos, slice, out, max_new, max_new_each, greedy);
+    }
+    // How serve() picks ids.  Greedy: the prompt's argmax, the decoder's argmax.  SampledServe (include/gten_hip_sample.h):
+    // prompt j's request (top_k[j], temp[j], seed, stream j) draws its first id from the prompt's logits on the device and is
+    // set on whichever slot takes the prompt -- the ids depend on (seed, j) and the logits only, not on the slot or schedule.
+    struct GreedyServe {
+        static constexpr bool kSampled = false;
+        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int) { return b.prefill(c, row); }
+        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>&,
+                  std::vector<int>* first)
+        {
+            b.prefill_many(sets, ps, first);
+        }
+        int top_k(int) const { return 0; }
+        float temp(int) const { return 0.f; }
+        uint64_t seed = 0;
+    };
+    struct SampledServe {
+        static constexpr bool kSampled = true;
+        const int32_t* top_k_each;       // per prompt (null: top_k_all)
+        const float* temp_each;          // per prompt (null: temp_all)
+        int top_k_all;
+        float temp_all;
+        uint64_t seed;
+        int top_k(int j) const { return top_k_each ? top_k_each[j] : top_k_all; }
+        float temp(int j) const { return temp_each ? temp_each[j] : temp_all; }
+        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j) { return b.prefill_sampled(c, row, top_k(j), temp(j), seed, (uint32_t)j); }
+        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
+                  std::vector<int>* first)
+        {
+            std::vector<float*> lo((size_t)sets.size(), nullptr);
+            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
+                const int j = js[(size_t)k];
+                const int32_t kk = top_k(j), pos = (int32_t)ps[(size_t)k]->size();
+                const float t = temp(j);
+                const uint32_t st = (uint32_t)j;
+                GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &kk, &t, seed, &st, &pos, out));
+            });
+        }
+    };
+    template <class Pick>
+    ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
+                          std::vector<std::vector<int32_t>>* out, int max_new, const int32_t* max_new_each, Pick& pick)
     {
         using clock = std::chrono::steady_clock;
         ensure_decoder();
@@ -698,7 +790,7 @@ public:
                 if (P >= limit) continue;                                  // no room to generate: returned as is
                 const auto t0 = clock::now();
                 const int c = pool.back();
-                const int best_i = prefill(c, row);                        // this set's caches now hold rows [0, P) (waits for stream 1 only)
+                const int best_i = pick.first(*this, c, row, j);           // this set's caches now hold rows [0, P) (waits for stream 1 only)
                 st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
                 st.admissions++;
                 if (best_i == eos) continue;                               // ended at once: the set takes the next prompt
@@ -745,7 +837,7 @@ public:
             std::reverse(sets.begin(), sets.end());                          // (the order they would be popped in)
             std::vector<const std::vector<int32_t>*> ps;
             for (int j : js) ps.push_back(&prompts[(size_t)j]);
-            prefill_many(sets, ps, &first);
+            pick.many(*this, sets, ps, js, &first);
             st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
             std::vector<int> unused;
             for (size_t k = 0; k < js.size(); k++) {
@@ -811,6 +903,8 @@ public:
                     set_of[(size_t)q] = r.set; job[(size_t)q] = r.j; cur[(size_t)q] = r.cur; last[(size_t)q] = r.last;
                     // (all joining slots in one call below: their ids, step words and cache-table rows go up behind each other, one wait)
                     ap_seq.push_back(q); ap_first.push_back(r.cur); ap_last.push_back(r.last); ap_tok.push_back(row.data());
+                    if constexpr (Pick::kSampled)
+                        GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, pick.top_k(r.j), pick.temp(r.j), pick.seed, (uint32_t)r.j));
                     live[(size_t)q] = 1; n_live++;
                 }
             }
@@ -898,6 +992,8 @@ public:
         // generate -- addresses slot q as sequence q
         for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_slot_bind(dec_, q, set_kv(q)));
         rebind.done = true;
+        if constexpr (Pick::kSampled)
+            for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, 0, 0.f, 0, 0));     // every slot greedy again
         return st;
     }
 
@@ -1000,6 +1096,42 @@ inline int greedy_generate(TinyLlama& model, std::vector<int32_t>& tokens, const
     if (max_new <= 0) return n_first;
     std::vector<int32_t> out((size_t)max_new);
     const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
+    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
+    return (int)tokens.size();
+}
+
+// One id drawn on the device from a logits row in HBM (gten_hip_sample_rows): the id that will sit at position `pos`.
+inline int sample_row(const float* logits_dev, int n_vocab, int top_k, float temp, uint64_t seed, uint32_t stream, int pos)
+{
+    Tensor id({1}, kInt32);
+    const int32_t k = top_k, p = pos;
+    GTEN_HIP_OK(gten_hip_sample_rows(logits_dev, 1, n_vocab, 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
+    int32_t got = -1;
+    GTEN_HIP_OK(gten_hip_memcpy_d2h(&got, id.device_ptr(), sizeof(got)));
+    return got;
+}
+
+// greedy_generate with top-k sampling (include/gten_hip_sample.h): the prompt's first id is drawn from its logits on the
+// device, every later one by the decoder's sampler; the request is dropped again afterwards (the decoder's later steps
+// are greedy).  top_k 0 gives greedy_generate's ids.  -1 when the decoder refuses the request (gten_hip_last_error).
+inline int sampled_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
+                            uint64_t seed, uint32_t stream)
+{
+    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
+    {
+        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
+        const Tensor logits = model.logits(input, 0);
+        const int first = sample_row((const float*)logits.device_ptr(), logits.numel(), top_k, temp, seed, stream, (int)tokens.size());
+        if (first == eos) return (int)tokens.size();
+        tokens.push_back(first);
+    }
+    const int n_first = (int)tokens.size();
+    const int max_new = n_predict - n_first;
+    if (max_new <= 0) return n_first;
+    std::vector<int32_t> out((size_t)max_new);
+    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) return -1;
+    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
+    GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
     return (int)tokens.size();
 }

@@ -42,6 +42,8 @@ class GtenHost:
         "gten_host_batch_prefill", "gten_host_batch_prefill_many", "gten_host_batch_generate", "gten_host_batch_serve", "gten_host_batch_serve2", "gten_host_batch_set_serve_schedule", "gten_host_batch_set_serve_spares", "gten_host_batch_set_serve_ramp", "gten_host_batch_decode_begin", "gten_host_batch_decode_step", "gten_host_batch_decode_step_ragged",
         "gten_host_batch_decode_result", "gten_host_batch_logits", "gten_host_batch_time_family", "gten_host_batch_kv_info", "gten_host_batch_seq_steps",
     ]
+    # include/gten_host_sample.h (top-k sampling, host/capi_sample.cpp)
+    SAMPLE_SYMBOLS = ["gten_host_model_generate_topk", "gten_host_batch_generate_topk", "gten_host_batch_serve_topk"]
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -62,6 +64,10 @@ class GtenHost:
         self._logits = _sig(L, "gten_host_model_logits", ci, [vp, vp, ci, ci, vp])
         self._greedy = _sig(L, "gten_host_model_greedy", ci, [vp, vp, ci, ci, ci])
         self._generate = _sig(L, "gten_host_model_generate", ci, [vp, vp, ci, ci, ci])
+        self._generate_topk = _sig(L, "gten_host_model_generate_topk", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32])
+        self._bserve_topk = _sig(L, "gten_host_batch_serve_topk", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                      C.c_float, C.c_uint64])
+        self._bgen_topk = _sig(L, "gten_host_batch_generate_topk", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, vp, vp, vp])
         self._tok_create = _sig(L, "gten_host_tokenizer_create", vp, [C.c_char_p, ci])
         self._tok_free = _sig(L, "gten_host_tokenizer_free", None, [vp])
         self._tok_encode = _sig(L, "gten_host_tokenizer_encode", ci, [vp, C.c_char_p, ci, vp, ci])
@@ -250,6 +256,16 @@ class HostModel:
         total = self.host._generate(self.h, buf.ctypes.data_as(C.c_void_p), len(prompt), max_tokens, eos)
         return buf[:total].copy()
 
+    def generate_topk(self, prompt, max_tokens, eos, top_k, temp, seed, stream=0):
+        """generate() with every new id drawn by the device sampler (include/gten_host_sample.h; top_k 0: greedy)"""
+        buf = np.zeros(max(max_tokens, len(prompt)), np.int32)
+        buf[: len(prompt)] = prompt
+        total = self.host._generate_topk(self.h, buf.ctypes.data_as(C.c_void_p), len(prompt), max_tokens, eos, int(top_k), float(temp),
+                                         C.c_uint64(int(seed)), C.c_uint32(int(stream)))
+        if total < 0:
+            raise GtenHipError(f"generate_topk rc={total}")
+        return buf[:total].copy()
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -334,6 +350,23 @@ class HostBatch:
                                  out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p)), "batch_generate")
         return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
 
+    def generate_topk(self, prompts, max_tokens, eos, top_k, temp, seed, streams=None):
+        """generate() with every new id drawn by the device sampler; sequence q uses streams[q] (None: q)"""
+        assert len(prompts) == self.n_seq
+        mp = max(len(p) for p in prompts)
+        pr = np.zeros((self.n_seq, mp), np.int32)
+        npr = np.zeros(self.n_seq, np.int32)
+        for q, p in enumerate(prompts):
+            pr[q, : len(p)] = p
+            npr[q] = len(p)
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
+        out = np.zeros((self.n_seq, max_tokens), np.int32)
+        tot = np.zeros(self.n_seq, np.int32)
+        self._ck(self.host._bgen_topk(self.h, pr.ctypes.data_as(C.c_void_p), npr.ctypes.data_as(C.c_void_p), mp, max_tokens, eos, int(top_k),
+                                      float(temp), C.c_uint64(int(seed)), None if st is None else st.ctypes.data_as(C.c_void_p),
+                                      out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p)), "batch_generate_topk")
+        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+
     def set_serve_schedule(self, k):
         """tests: exactly k prompts beside every slice (0: as many as fit while it runs)"""
         self._ck(self.host._bsched(self.h, int(k)), "set_serve_schedule")
@@ -364,6 +397,30 @@ class HostBatch:
         self._ck(self.host._bserve(self.h, pr.ctypes.data_as(C.c_void_p), npr.ctypes.data_as(C.c_void_p), len(prompts), mp, max_tokens, eos,
                                    slice_steps, max_new, None if each is None else each.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p), len(st)),
                  "batch_serve")
+        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
+        return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
+
+    def serve_topk(self, prompts, max_tokens, eos, top_k, temp, seed, slice_steps=16, max_new=0, max_new_each=None):
+        """serve() with every new id drawn by the device sampler: top_k / temp a scalar or one value per prompt (top_k 0: greedy),
+        prompt j draws with stream j"""
+        mp = max(len(p) for p in prompts)
+        width = max(max_tokens, mp)
+        pr = np.zeros((len(prompts), mp), np.int32)
+        npr = np.zeros(len(prompts), np.int32)
+        for j, p in enumerate(prompts):
+            pr[j, : len(p)] = p
+            npr[j] = len(p)
+        out = np.zeros((len(prompts), width), np.int32)
+        tot = np.zeros(len(prompts), np.int32)
+        st = np.zeros(9, np.float64)
+        each = None if max_new_each is None else np.ascontiguousarray(max_new_each, dtype=np.int32)
+        ks = None if np.isscalar(top_k) else np.ascontiguousarray(top_k, dtype=np.int32)
+        ts = None if np.isscalar(temp) else np.ascontiguousarray(temp, dtype=np.float32)
+        assert (ks is None or len(ks) == len(prompts)) and (ts is None or len(ts) == len(prompts))
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self.host._bserve_topk(self.h, ptr(pr), ptr(npr), len(prompts), mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out),
+                                        ptr(tot), ptr(st), len(st), ptr(ks), ptr(ts), int(top_k) if ks is None else 0,
+                                        float(temp) if ts is None else 1.0, C.c_uint64(int(seed))), "batch_serve_topk")
         keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
         return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
 
