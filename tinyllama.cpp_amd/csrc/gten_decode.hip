@@ -25,6 +25,7 @@
 #include "gten_dev.h"
 #include "gten_rt.h"
 #include "gten_hip_sample.h"
+#include "gten_hip_ab.h"
 
 #include <cmath>
 #include <vector>
@@ -35,6 +36,8 @@ using namespace gtd;
 extern __shared__ __attribute__((aligned(16))) uint8_t g_smem[];
 
 #define DEC_CHUNK 256            // attention positions per workgroup
+#define ATT1V_VROW 68            // k_dec_attn_one64v: floats per V row in LDS (16-byte row stores without bank conflicts)
+#define ATT1V_PCOL 72            // k_dec_attn_one64v: floats per column group of p in LDS (conflict-free scattered stores)
 #define DEC_MAX_LANES 4           // lanes of up to 64 sequences in one decoder (256 sequences)
 #define DEC_ATT_MAXCH 8          // chunk partials / statistics a consumer requests up front (2048 positions)
 #define GEMVM_F16_LDS_LIMIT 65536  // multi-sequence f16 inputs are staged in LDS up to this many bytes (8 sequences x 2048 x f32; the launchers raise
@@ -159,6 +162,7 @@ struct gten_hip_decoder {
     // graph (fork behind the previous replay, join at the end), so the chains fill each other's gaps.  Per sequence the
     // kernels, their arguments and therefore the results are those of a 64-sequence decoder.
     bool exact = false;               // gten_hip_set_decode_exact at creation
+    bool attn_classic = false;        // gten_hip_set_decode_attn_classic at creation
     bool persist_on = false;          // gten_hip_set_decode_persistent at creation: the step as ONE persistent launch (gten_decode_persist.h)
     struct PersistState* persist = nullptr;
     // ---- head-major shadows of the K / V caches (gten_decode_attn_hm.h): decoders of 16+ sequences, Q8 activations, fast forms.
@@ -232,6 +236,16 @@ extern "C" int gten_hip_set_kv_head_major(int on)
 extern "C" int gten_hip_set_decode_exact(int on)
 {
     g_decode_exact = on != 0;
+    return 0;
+}
+// decoders created AFTERWARDS run the single-sequence d_head 64 attention as k_dec_attn_one64 (on != 0: the A/B control) or as
+// k_dec_attn_one64v (0, the default): the same bytes on a shorter p.V schedule.  g_attn_classic_now: the creating choice of the
+// decoder whose step is being enqueued.
+static bool g_attn_classic = false;
+static bool g_attn_classic_now = false;
+extern "C" int gten_hip_set_decode_attn_classic(int on)
+{
+    g_attn_classic = on != 0;
     return 0;
 }
 
@@ -382,6 +396,17 @@ static int launch_attention(const AttnArgs& t0, dim3 agrid, size_t smem1)
                                (unsigned long long)(uintptr_t)t.step, geo, (unsigned long long)(unsigned)t.n_embd | heads, (unsigned long long)(uintptr_t)t.vcache}};
         const bool multi = agrid.z > 1 || t.kv_tab != nullptr;
         const dim3 g64(agrid.y, agrid.x, agrid.z);     // (chunk, head, sequence)
+        if (!multi && !g_attn_classic_now) {
+            const size_t smem_v = 1152 + (size_t)(4 * ATT1V_PCOL + DEC_CHUNK) * 4 + (size_t)DEC_CHUNK * ATT1V_VROW * 4;
+            if (t.adtype == GTEN_Q8) {
+                GTR_CHECK(hipFuncSetAttribute((const void*)k_dec_attn_one64v<GTEN_Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v));
+                DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, k_dec_attn_one64v<GTEN_Q8>, g64, dim3(256), smem_v, hw, t);
+            } else {
+                GTR_CHECK(hipFuncSetAttribute((const void*)k_dec_attn_one64v<GTEN_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v));
+                DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, k_dec_attn_one64v<GTEN_F16>, g64, dim3(256), smem_v, hw, t);
+            }
+            return 0;
+        }
         if (t.adtype == GTEN_Q8) {
             if (multi) DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, (k_dec_attn_one64<GTEN_Q8, true>), g64, dim3(256), smem, hw, t);
             else DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, (k_dec_attn_one64<GTEN_Q8, false>), g64, dim3(256), smem, hw, t);
@@ -1211,6 +1236,7 @@ static int persist_prepare(gten_hip_decoder* dc);
 static int enqueue_lane(gten_hip_decoder* dc, int lane)
 {
     g_exact_now = dc->exact;
+    g_attn_classic_now = dc->attn_classic;
     // single sequence, Q8 activations: the whole step as one persistent launch (a family-restricted timing replay wants
     // the launch chain's kernels)
 #if GTEN_WITH_PERSIST
@@ -1325,6 +1351,7 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     dc->d = d;
     dc->n_seq = n_seq;
     dc->exact = g_decode_exact;
+    dc->attn_classic = g_attn_classic;
     dc->persist_on = g_persist_on;
     {
         // Rows per lane: 128 where the folded W.x form runs eight row tiles per workgroup (k_dec_mmvh<.., 8, ..>: every expanded

@@ -483,6 +483,209 @@ __global__ __launch_bounds__(256) void k_dec_attn_one64(const unsigned long long
     }
 }
 
+// ---- k_dec_attn_one64<ADT, false> on a shorter p.V schedule: the same bytes (single sequence; Q8 and f16 activations)
+//
+// k_dec_attn_one64 keeps the V chunk in LDS as it lies in the cache, so each of a thread's 64 dependent p.V terms costs three
+// scalar-width LDS reads (p, the quant byte, the block delta) and a convert and a multiply before its multiply-add.  Here
+// each thread turns ITS OWN V row (in registers since kernel entry) into f32 once, between the scores and the max barrier,
+// and the p.V loop reads one conflict-free dword per term plus its probabilities as 16 broadcast 16-byte reads:
+//   * (float)q * fp16(delta) is exact in f32 (8 x 11 significant bits), and it is the very product the old loop forms per
+//     term; f16 V widens exactly.  The term is still p * v rounded, then added: -ffp-contract=off, no fma;
+//   * every (e, cg) chain runs over positions cg, cg + 4, ... in order, the four chains join as ((g0 + g1) + g2) + g3, the
+//     softmax statistics come from the same trees: att_part and stats are bit-identical to k_dec_attn_one64's;
+//   * a ragged last chunk runs all 64 terms: rows at or beyond n are zeros and so are their probabilities.  The sum starts
+//     at +0 and x + y == 0 rounds to +0, so it never holds -0, and adding +0 = +0 * +0 leaves it unchanged.
+// LDS: the head-vector scratch (1152 B), p as [cg][k] with 72-float columns (bank-conflict-free stores), the chain sums,
+// V as [position][68 floats] (16-byte row stores conflict-free, one row per p.V step across the wave).
+template <int ADT>
+__global__ __launch_bounds__(256) void k_dec_attn_one64v(const unsigned long long h0, const unsigned long long h1, const unsigned long long h2,
+                                                        const unsigned long long h3, const unsigned long long h4, const unsigned long long h5,
+                                                        const unsigned long long h6, const AttnArgs a0)
+{
+    AttnArgs a = a0;
+    a.qkv_raw = from_word<float>(h0); a.rope_now = from_word<float2>(h1); a.kcache = (uint8_t*)from_word<uint8_t>(h2);
+    a.step = from_word<DecStep>(h3); a.kv_pitch = (size_t)(unsigned)(h4 & 0xffffffffull); a.max_ctx = (int)(h4 >> 32);
+    a.n_embd = (int)(unsigned)(h5 & 0xffffffffull); a.n_heads = (int)((h5 >> 32) & 0xffu); a.n_kv = (int)((h5 >> 40) & 0xffu); a.grp_shift1 = (int)(h5 >> 48);
+    a.vcache = (uint8_t*)from_word<uint8_t>(h6);
+    constexpr int dh = 64, nblk = 2;
+    constexpr int NW = (ADT == GTEN_Q8) ? 17 : 32;     // dwords per kv-head slice
+    constexpr int VS = ATT1V_VROW, PS = ATT1V_PCOL;     // floats per V row / per p column group in LDS
+    const int h = blockIdx.y, chunk = blockIdx.x, c0 = chunk * DEC_CHUNK;
+    const int grp = a.grp_shift1 ? (1 << (a.grp_shift1 - 1)) : a.n_heads / a.n_kv, g = a.grp_shift1 ? (h >> (a.grp_shift1 - 1)) : h / grp;
+    const int kv_dim = a.n_kv * dh;
+    const size_t head_bytes = (ADT == GTEN_Q8) ? (size_t)nblk * GTEN_Q8_BYTES : (size_t)dh * 2;
+
+    float* red = (float*)g_smem;                 // 16
+    float* qf = red + 16 + dh;                   // dh
+    float* kf = qf + dh;                         // dh
+    float* qd = kf + dh;                         // 8
+    float* kd = qd + 8;                          // 8
+    uint16_t* d16 = (uint16_t*)(kd + 8);         // 16 halves
+    int8_t* qi8 = (int8_t*)(d16 + 16);           // dh
+    int8_t* ki8 = qi8 + dh;                      // dh
+    int8_t* vi8 = ki8 + dh;                      // dh
+    float* pt = (float*)(g_smem + 1152);         // 4 x PS: p of position cg + 4 k at pt[cg * PS + k]
+    float* part = pt + 4 * PS;                   // 256
+    float* vf = part + DEC_CHUNK;                // DEC_CHUNK x VS
+
+    // ---- entry requests: k_dec_attn_one64's
+    const int c = c0 + threadIdx.x;
+    const int t = threadIdx.x & 63, pw = threadIdx.x >> 6;
+    const int roff = (pw == 1) ? a.n_embd + g * dh : (pw == 2) ? a.n_embd + kv_dim + g * dh : h * dh;
+    const float raw = a.qkv_raw[roff + t];
+    const float2 rot = a.rope_now[t & 31];
+    __builtin_amdgcn_sched_barrier(0);
+    const int cs = min(c, a.max_ctx - 1);
+    const unsigned pitch_w = (unsigned)(a.kv_pitch >> 2);
+    const gmem_u32 kp = as_global(a.kcache + (size_t)g * head_bytes) + (unsigned)cs * pitch_w;
+    unsigned kw[NW];
+    unsigned vw[NW];
+    {
+        const gmem_u32 vp = as_global(a.vcache + (size_t)g * head_bytes) + (unsigned)cs * pitch_w;
+        typedef unsigned u4u __attribute__((ext_vector_type(4), aligned(4)));
+#pragma unroll
+        for (int j = 0; j + 4 <= NW; j += 4) {
+            const u4u kq = *(const __attribute__((address_space(1))) u4u*)(kp + j);
+            const u4u vq = *(const __attribute__((address_space(1))) u4u*)(vp + j);
+            kw[j] = kq.x; kw[j + 1] = kq.y; kw[j + 2] = kq.z; kw[j + 3] = kq.w;
+            vw[j] = vq.x; vw[j + 1] = vq.y; vw[j + 2] = vq.z; vw[j + 3] = vq.w;
+        }
+#pragma unroll
+        for (int j = NW & ~3; j < NW; j++) { kw[j] = kp[j]; vw[j] = vp[j]; }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const int n = a.step->n, pos = n - 1;
+    if (c0 >= n) return;
+
+    const bool has_new = (pos >= c0) && (pos < c0 + DEC_CHUNK);
+    const bool writer = has_new && (h == g * grp);
+    float vnew = 0.f;                             // wave 2: the new v row's element t (exact storage value)
+    if (pw < 3) {
+        int8_t* dq = (pw == 0) ? qi8 : (pw == 1) ? ki8 : vi8;
+        float* dd = (pw == 0) ? qd : (pw == 1) ? kd : kd + 4;
+        const float v = head_prep_cs(raw, true, pw != 2, rot, dh, ADT, dq, dd, d16 + 4 * pw);
+        if (pw == 0) qf[t] = v;
+        if (pw == 1) kf[t] = v;
+        if (pw == 2) vnew = v;
+        if (pw >= 1 && writer) {
+            uint8_t* row = ((pw == 1) ? a.kcache : a.vcache) + (size_t)pos * a.kv_pitch + (size_t)g * head_bytes;
+            if (ADT == GTEN_Q8) {
+                uint8_t* blk = row + (size_t)(t >> 5) * GTEN_Q8_BYTES;
+                store_global<uint8_t>(blk + 2 + (t & 31), (uint8_t)dq[t]);
+                if ((t & 31) == 0) store_global<uint16_t>(blk, d16[4 * pw + (t >> 5)]);
+            } else {
+                store_global<uint16_t>((uint16_t*)row + t, f2h(v));
+            }
+        }
+    }
+    __syncthreads();                                         // q (and the new k row) for every wave
+
+    // ---- scores (k_dec_attn_one64's arithmetic)
+    const float scale = 1.0f / sqrtf((float)dh);
+    float acc = 0.f;
+    if (ADT == GTEN_Q8) {
+        const int* qi = (const int*)qi8;
+        int isum = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) isum = dot4(qi[j], (int)__builtin_amdgcn_alignbit(kw[j + 1], kw[j], 16), isum);
+        acc += (float)isum * (qd[0] * h2f((uint16_t)(kw[0] & 0xffffu)));
+        isum = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) isum = dot4(qi[8 + j], (int)kw[9 + j], isum);
+        acc += (float)isum * (qd[1] * h2f((uint16_t)(kw[8] >> 16)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 32; j++) {
+            acc += qf[2 * j] * h2f((uint16_t)(kw[j] & 0xffffu));
+            acc += qf[2 * j + 1] * h2f((uint16_t)(kw[j] >> 16));
+        }
+    }
+    if (has_new) {
+        float accn = 0.f;
+        if (ADT == GTEN_Q8) {
+            const int* qi = (const int*)qi8;
+            const int* ki = (const int*)ki8;
+#pragma unroll
+            for (int b = 0; b < nblk; b++) {
+                int isum = 0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) isum = dot4(qi[b * 8 + j], ki[b * 8 + j], isum);
+                accn += (float)isum * (qd[b] * kd[b]);
+            }
+        } else {
+            for (int e = 0; e < dh; e++) accn += qf[e] * kf[e];
+        }
+        if (c == pos) acc = accn;
+    }
+    const float sc = (c < n) ? acc * scale : -INFINITY;
+
+    // ---- this thread's V row as f32 into LDS (zeros at and beyond n); the new position's row is the new v row, from wave 2
+    if (c != pos) {
+        const bool live = c < n;
+        float4* dst = (float4*)(vf + threadIdx.x * VS);
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            float f[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int e = 4 * j + i;
+                float x;
+                if (ADT == GTEN_Q8) {
+                    const int b = (e < 32) ? 2 + e : 4 + e;                  // byte of the 68-byte slice: [d0 | q0 x 32 | d1 | q1 x 32]
+                    const int q = (int)(int8_t)(uint8_t)(vw[b >> 2] >> (8 * (b & 3)));
+                    const float d = h2f((uint16_t)((e < 32) ? (vw[0] & 0xffffu) : (vw[8] >> 16)));
+                    x = (float)q * d;
+                } else {
+                    x = h2f((uint16_t)((e & 1) ? (vw[e >> 1] >> 16) : (vw[e >> 1] & 0xffffu)));
+                }
+                f[i] = live ? x : 0.f;
+            }
+            dst[j] = make_float4(f[0], f[1], f[2], f[3]);
+        }
+    }
+    if (has_new && pw == 2) vf[(pos - c0) * VS + t] = vnew;
+
+    const float mx = block_max_n<4>(sc, red);               // red: first use; the sum takes its own words
+    const float ex = (c < n) ? expf(sc - mx) : 0.f;
+    const float sm = block_sum_n<4>(ex, red + 4);
+
+    // ---- probabilities against the chunk's own statistics, rounded to the activation dtype in registers
+    float pr = (c < n) ? ex / sm : 0.f;
+    if (ADT == GTEN_Q8) {
+        const Q8Scale s8 = q8_scale_from_absmax(max32(fabsf(pr)));
+        if (c < n) pr = (float)q8_round(pr, s8.scale) * s8.ddeq;
+    } else {
+        pr = h2f(f2h(pr));
+    }
+    pt[(threadIdx.x & 3) * PS + (threadIdx.x >> 2)] = pr;
+    __syncthreads();                                         // p, and every V row
+
+    // ---- p . V: chain (e, cg) over positions cg, cg + 4, ..., cg + 252
+    const int e = threadIdx.x & 63, cg = threadIdx.x >> 6;
+    const float* vcol = vf + cg * VS + e;
+    const float4* pc = (const float4*)(pt + cg * PS);
+    float o = 0.f;
+#pragma unroll
+    for (int j = 0; j < DEC_CHUNK / 16; j++) {
+        const float4 p4 = pc[j];
+        o = o + p4.x * vcol[(4 * j + 0) * 4 * VS];
+        o = o + p4.y * vcol[(4 * j + 1) * 4 * VS];
+        o = o + p4.z * vcol[(4 * j + 2) * 4 * VS];
+        o = o + p4.w * vcol[(4 * j + 3) * 4 * VS];
+    }
+    part[threadIdx.x] = o;
+    __syncthreads();
+    if (threadIdx.x < dh) {
+        float r = 0.f;
+        for (int gi = 0; gi < 4; gi++) r += part[gi * dh + threadIdx.x];
+        a.att_part[((size_t)h * a.n_chunks + chunk) * dh + threadIdx.x] = r;
+    }
+    if (threadIdx.x == 64) {
+        a.stats[((size_t)h * a.n_chunks + chunk) * 2 + 0] = mx;
+        a.stats[((size_t)h * a.n_chunks + chunk) * 2 + 1] = sm;
+    }
+}
+
 
 // The bookkeeping behind a step's id (one thread): result[n], the next input token when advance & 2, the advance of n.
 // Shared by k_dec_argmax and the sampler (gten_decode_sample.h).

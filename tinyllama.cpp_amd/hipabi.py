@@ -97,6 +97,7 @@ class GtenHip:
     ]
     # include/gten_hip_sample.h (top-k sampling on the device)
     SAMPLE_SYMBOLS = ["gten_hip_decoder_set_sampling", "gten_hip_sample_rows"]
+    AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -134,6 +135,7 @@ class GtenHip:
         self._block_rows = _sig(L, "gten_hip_block_rows", ci, [C.POINTER(BlockDesc), ci, ci])
         self._set_block_rows = _sig(L, "gten_hip_set_block_rows", ci, [ci])
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
+        self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
         self._decode_persistent = _sig(L, "gten_hip_set_decode_persistent", ci, [ci])
         self._kv_head_major = _sig(L, "gten_hip_set_kv_head_major", ci, [ci])
         self._kv_watch_selftest = _sig(L, "gten_hip_kv_watch_selftest", ci, [])
@@ -213,6 +215,11 @@ class GtenHip:
     def set_decode_exact(self, on):
         """exact forms of the decode step for decoders created from now on (include/gten_hip.h)"""
         self._check(self._decode_exact(1 if on else 0))
+
+    def set_decode_attn_classic(self, on):
+        """decoders created from now on: the single-sequence attention as k_dec_attn_one64 (the A/B control) or, by default,
+        k_dec_attn_one64v -- the same bytes (include/gten_hip_ab.h)"""
+        self._check(self._decode_attn_classic(1 if on else 0))
 
     def set_kv_head_major(self, on):
         """decoders of 16+ sequences created from now on: head-major shadows of the K / V caches (default) or the cache rows as they lie"""
