@@ -11,6 +11,8 @@
 #include <vector>
 #include <algorithm>
 #include "gten_rt.h"
+#include "gten_hip_score.h"
+#include "gten_row_logprobs.h"
 
 #include <cstdlib>
 
@@ -968,6 +970,27 @@ int gten_hip_argmax_row(const float* logits, int n, int32_t* out)
     GTR_REQUIRE(logits && out && n > 0, "argmax_row: bad arguments");
     kv_watch_touch(out, 4);
     GTR_LAUNCH(KT_ELEMWISE, k_argmax_row, dim3(1), dim3(1024), 0, logits, n, out);
+    return 0;
+}
+
+// ---- log-softmax of f32 logits rows read at one target id per row (include/gten_hip_score.h; kernel: gten_row_logprobs.h)
+int gten_hip_row_logprobs(const float* logits, int n_rows, int n_vocab, long long row_stride,
+                          const int32_t* targets, float* logprob_out, int32_t* rank_out, int32_t* argmax_out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(logits && targets && logprob_out, "row_logprobs: null pointer");
+    GTR_REQUIRE(n_vocab >= 1 && row_stride >= n_vocab, "row_logprobs: bad n_vocab %d / row_stride %lld", n_vocab, row_stride);
+    GTR_REQUIRE(n_rows >= 1 && n_rows <= 65535, "row_logprobs: bad n_rows %d", n_rows);
+    kv_watch_touch(logprob_out, (size_t)n_rows * 4);
+    if (rank_out) kv_watch_touch(rank_out, (size_t)n_rows * 4);
+    if (argmax_out) kv_watch_touch(argmax_out, (size_t)n_rows * 4);
+    const bool vec = ((uintptr_t)logits % 16 == 0) && (row_stride % 4 == 0);
+    if (vec)
+        GTR_LAUNCH(KT_ROW_LOGPROBS, k_row_logprobs<true>, dim3(n_rows), dim3(LP_THREADS), 0, logits, n_vocab, row_stride, targets,
+                   logprob_out, rank_out, argmax_out);
+    else
+        GTR_LAUNCH(KT_ROW_LOGPROBS, k_row_logprobs<false>, dim3(n_rows), dim3(LP_THREADS), 0, logits, n_vocab, row_stride, targets,
+                   logprob_out, rank_out, argmax_out);
     return 0;
 }
 

@@ -98,6 +98,7 @@ class GtenHip:
     # include/gten_hip_sample.h (top-k sampling on the device)
     SAMPLE_SYMBOLS = ["gten_hip_decoder_set_sampling", "gten_hip_sample_rows"]
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
+    SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -147,6 +148,8 @@ class GtenHip:
         self._copy_ranges = _sig(L, "gten_hip_copy_ranges", ci, [C.c_void_p, ci])
         self._set_sampling = _sig(L, "gten_hip_decoder_set_sampling", ci, [vp, ci, ci, C.c_float, C.c_uint64, C.c_uint32])
         self._sample_rows = _sig(L, "gten_hip_sample_rows", ci, [vp, ci, ci, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp])
+        self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
+        self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -211,6 +214,27 @@ class GtenHip:
         out = DeviceBuffer(self, 4 * max(n_rows, 1))
         return self._sample_rows(logits.ptr, n_rows, n_vocab, row_stride, k.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                  C.c_uint64(int(seed)), s.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p), out.ptr)
+
+    def row_logprobs(self, logits, n_rows, n_vocab, row_stride, targets):
+        """gten_hip_row_logprobs (include/gten_hip_score.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride elements;
+        targets int32[n_rows] (-1: not scored).  Returns (logprob f32[n_rows], rank int32[n_rows], argmax int32[n_rows])."""
+        t = DeviceBuffer.from_numpy(self, np.ascontiguousarray(targets, dtype=np.int32))
+        out = DeviceBuffer(self, 12 * n_rows)
+        self._check(self._row_logprobs(logits.ptr, n_rows, n_vocab, row_stride, t.ptr, out.ptr, out.ptr + 4 * n_rows, out.ptr + 8 * n_rows))
+        got = out.download(np.uint8)
+        return got[: 4 * n_rows].view(np.float32).copy(), got[4 * n_rows: 8 * n_rows].view(np.int32).copy(), got[8 * n_rows:].view(np.int32).copy()
+
+    def row_logprobs_rc(self, logits, n_rows, n_vocab, row_stride):
+        """the return code of one gten_hip_row_logprobs call (argument checks); targets / outputs are scratch words"""
+        buf = DeviceBuffer(self, 16 * max(n_rows, 1))
+        buf.zero()
+        return self._row_logprobs(logits.ptr, n_rows, n_vocab, row_stride, buf.ptr, buf.ptr + 4 * max(n_rows, 1), None, None)
+
+    def argmax_row(self, logits, n, offset=0):
+        """gten_hip_argmax_row on the f32 row at byte `offset` of a DeviceBuffer: the greedy id (strict >, first maximum)"""
+        out = DeviceBuffer(self, 4)
+        self._check(self._argmax_row(logits.ptr + offset, n, out.ptr))
+        return int(out.download(np.int32)[0])
 
     def set_decode_exact(self, on):
         """exact forms of the decode step for decoders created from now on (include/gten_hip.h)"""

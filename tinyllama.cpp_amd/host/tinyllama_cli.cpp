@@ -3,9 +3,12 @@
 // forward path it drives is libgten_hip.so.  Differences from the reference's main(): no model download step (there is
 // no network here: --model PATH, default models/tinyllama.<fp16|q8|q4>.gten as there), --tokenizer PATH (default
 // tokenizer.bin), --seed for the top-k sampler, --ids to print token ids instead of text (tests); greedy sampling runs
-// with the sampler on the device (gten::greedy_generate).
+// with the sampler on the device (gten::greedy_generate); --score PATH prints the log-likelihood of a text file
+// (include/gten_host_score.h) instead of generating.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <iterator>
 #include <fstream>
 #include <iostream>
 #include <random>
@@ -34,13 +37,17 @@ Optional args.
 --model PATH :     .gten checkpoint [default=models/tinyllama.<fp16|q8|q4>.gten].
 --tokenizer PATH : vocabulary file [default=tokenizer.bin].
 --seed S : seed of the top-k sampler [default: random].
---ids :    print token ids instead of text.
+--ids :    print token ids instead of text (with --score: one `id logprob rank` line per scored id).
+--score PATH : score the text of PATH (plain BPE, no chat template) instead of generating: windows of at most
+           --ctx ids, each [1] + the next ctx-1 text ids, so that every text id is scored once.  Prints
+           `score: tokens=T nll=<mean -logprob> ppl=<exp(nll)> greedy=<fraction of ids that were the argmax>`.
+--ctx N :  window length for --score. Minimum is 17 and max is 2048. [default=2048].
 )";
 
 struct Options {
     Dtype model_dtype = kFloat16;
-    std::string model_path, tokenizer_path = "tokenizer.bin", prompt;
-    int n_predict = 768, topk = 50;
+    std::string model_path, tokenizer_path = "tokenizer.bin", prompt, score_path;
+    int n_predict = 768, topk = 50, ctx = 2048;
     float temp = 0.9f;
     bool greedy = false, ids = false, seeded = false;
     uint64_t seed = 0;
@@ -79,6 +86,42 @@ static void run_topk(const Options& o, std::string prompt, TinyLlama& model, Tok
     (o.ids ? std::cout : std::cerr) << '\n';
 }
 
+// --score: the file's plain BPE ids in windows [1] + up to ctx - 1 text ids, all windows through score_many (BOS is context
+// only: every text id is scored exactly once, against the logits of the row before it)
+static int run_score(const Options& o, TinyLlama& model, Tokenizer& tok)
+{
+    std::ifstream f{o.score_path, std::ios::binary};
+    if (!f.is_open()) { std::cerr << "error: cannot open " << o.score_path << ".\n"; return EXIT_FAILURE; }
+    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    const std::vector<int> ids = tok.encode_plain(text);
+    std::vector<int32_t> tokens, targets, starts{0};
+    for (size_t i = 0; i < ids.size(); i += (size_t)o.ctx - 1) {
+        const size_t take = std::min(ids.size() - i, (size_t)o.ctx - 1);
+        tokens.push_back(1);
+        tokens.insert(tokens.end(), ids.begin() + (long)i, ids.begin() + (long)(i + take));
+        targets.insert(targets.end(), ids.begin() + (long)i, ids.begin() + (long)(i + take));
+        targets.push_back(-1);
+        starts.push_back((int32_t)tokens.size());
+    }
+    const int T = (int)ids.size();
+    double nll = 0.0;
+    int greedy = 0;
+    if (T > 0) {
+        std::vector<float> lp(tokens.size());
+        std::vector<int32_t> rank(tokens.size());
+        model.score_many(tokens.data(), starts.data(), (int)starts.size() - 1, targets.data(), lp.data(), rank.data());
+        for (size_t i = 0; i < tokens.size(); i++) {
+            if (targets[i] < 0) continue;
+            nll -= lp[i];
+            greedy += rank[i] == 0;
+            if (o.ids) std::printf("%d %.9g %d\n", targets[i], lp[i], rank[i]);
+        }
+        nll /= T;
+    }
+    std::printf("score: tokens=%d nll=%.9g ppl=%.9g greedy=%.9g\n", T, nll, std::exp(nll), T > 0 ? (double)greedy / T : 0.0);
+    return 0;
+}
+
 int main(int argc, char const* argv[])
 {
     Options o;
@@ -98,6 +141,13 @@ int main(int argc, char const* argv[])
         else if (arg == "-p") o.prompt = value("prompt");
         else if (arg == "--model") o.model_path = value("model");
         else if (arg == "--tokenizer") o.tokenizer_path = value("tokenizer");
+        else if (arg == "--score") o.score_path = value("score");
+        else if (arg == "--ctx") {
+            int v = 0;
+            try { v = std::stoi(value("ctx")); } catch (...) { std::cerr << "Invalid ctx value.\n"; return -1; }
+            if (v < 17 || v > 2048) { std::cerr << "ctx must be gte 17 and lte 2048.\n"; return -1; }
+            o.ctx = v;
+        }
         else if (arg == "--seed") { o.seed = std::strtoull(value("seed"), nullptr, 10); o.seeded = true; }
         else if (arg == "--npred") {
             int v = 0;
@@ -134,9 +184,10 @@ int main(int argc, char const* argv[])
     dtype.wdtype = o.model_dtype;
     dtype.adtype = (o.model_dtype == kFloat16) ? kFloat16 : kQint8;          // tinyllama.cpp:258-265
 
-    TinyLlama model{o.n_predict, dtype};
+    TinyLlama model{o.score_path.empty() ? o.n_predict : o.ctx, dtype};
     model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
+    if (!o.score_path.empty()) return run_score(o, model, tokenizer);
 
     uint64_t seed = o.seed;
     if (!o.seeded) {

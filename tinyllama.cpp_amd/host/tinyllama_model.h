@@ -26,6 +26,7 @@
 
 #include "../gten/gten.h"
 #include "../../include/gten_hip_sample.h"
+#include "../../include/gten_hip_score.h"
 #include "synth.h"
 
 namespace gten {
@@ -79,8 +80,13 @@ public:
             (void)lm_head_.acv.device_ptr_mut();      // the step wrote the logits in HBM: host mirror is stale
             return lm_head_.acv;
         }
-        // operator by operator (this class drives its own decoder above; with the fast path switched off the
-        // modules must not record the row for theirs either -- gten/modules.h)
+        return lm_head_.forward(final_rows(tokens, start_pos));
+    }
+
+    // rows [start_pos, n) through the blocks and the final norm, operator by operator (this class drives its own decoder
+    // above; with the fast path switched off the modules must not record the row for theirs either -- gten/modules.h)
+    Tensor final_rows(const Tensor& tokens, const int start_pos)
+    {
         struct OpsOnly {
             bool was = detail::fused_rows_enabled();
             OpsOnly() { detail::fused_rows_enabled() = false; }
@@ -88,8 +94,7 @@ public:
         } ops_only;
         Tensor x = tok_emb_.forward(tokens, start_pos);
         for (auto& block : blocks_) x = block.forward(x, start_pos);
-        x = norm_.forward(x, start_pos);
-        return lm_head_.forward(x);
+        return norm_.forward(x, start_pos);
     }
 
     // ---- several prompts as ONE row matrix (TinyLlamaBatch::prefill_many; include/gten_hip.h, gten_hip_set_row_segments):
@@ -119,6 +124,126 @@ public:
         return lm_head_.forward(v);                           // EmbeddingLinear computes the last row of what it is given
     }
     AttentionBlock& block(int i) { return blocks_[(size_t)i]; }
+
+    // ---- scoring given ids (include/gten_host_score.h): the lm_head over EVERY computed row, in chunks of
+    // at most kScoreChunk rows into an f32 scratch this object owns (row pitch padded to 16 bytes), each chunk read by
+    // gten_hip_row_logprobs.  Chunks start at the first row of a text, so a row's logits depend on the text alone.
+    static constexpr int kScoreChunk = 512;
+    static constexpr int kScoreRows = 4096;    // rows of one score_many group (GTEN_SEG_MAX_ROWS)
+    static constexpr int kScoreTexts = 32;     // texts of one score_many group
+    long long score_stride() const { return ((long long)params.n_vocab + 3) & ~3LL; }
+
+    // the lm_head of rows [0, rows) of x (dtype code xdt, pitch bytes), handed chunk by chunk to fn(logits, first row, rows, stride)
+    template <class Fn>
+    void lm_head_rows(const void* x, int xdt, size_t pitch, int rows, Fn fn)
+    {
+        const long long stride = score_stride();
+        if (!score_logits_) GTEN_HIP_OK(gten_hip_malloc(&score_logits_, (size_t)kScoreChunk * (size_t)stride * sizeof(float)));
+        for (int r0 = 0; r0 < rows; r0 += kScoreChunk) {
+            const int cr = std::min(kScoreChunk, rows - r0);
+            GTEN_HIP_OK(gten_hip_matmul_2d((const uint8_t*)x + (size_t)r0 * pitch, xdt, pitch, lm_head_.weight.device_weight(),
+                                           dtype_code(dtype_.wdtype), score_logits_, GTEN_F32, (size_t)stride * sizeof(float), cr,
+                                           params.n_embd, params.n_vocab, 0));
+            fn((const float*)score_logits_, r0, cr, stride);
+        }
+    }
+    // rows [start_pos, n) of tokens computed as logits() computes them, their lm_head handed to fn as above (one new row on
+    // the fused decoder: its logits buffer is the row)
+    template <class Fn>
+    void rows_logits(const Tensor& tokens, const int start_pos, Fn fn)
+    {
+        const int rows = tokens.numel() - start_pos;
+        if (fast_decode_ && rows == 1 && tokens.is_host_external()) {
+            const Tensor lg = logits(tokens, start_pos);
+            fn((const float*)lg.device_ptr(), 0, 1, (long long)params.n_vocab);
+            return;
+        }
+        const Tensor h = final_rows(tokens, start_pos);
+        const size_t pitch = (size_t)h.bstride(0);
+        lm_head_rows((const uint8_t*)h.device_ptr() + (size_t)start_pos * pitch, dtype_code(h.dtype()), pitch, rows, fn);
+    }
+    // ... scored against targets already on the device (one per row); log-probs and ranks into lp / rk on the device
+    void score_dev(const Tensor& tokens, const int start_pos, const int32_t* tdev, float* lp, int32_t* rk)
+    {
+        rows_logits(tokens, start_pos, [&](const float* lg, int r0, int cr, long long stride) {
+            GTEN_HIP_OK(gten_hip_row_logprobs(lg, cr, params.n_vocab, stride, tdev + r0, lp + r0, rk + r0, nullptr));
+        });
+    }
+    // gten_host_model_score: targets (host) -> log-probs / ranks (host; rank_host may be null), one copy back at the end
+    void score(const Tensor& tokens, const int start_pos, const int32_t* targets, float* lp_host, int32_t* rank_host)
+    {
+        const int rows = tokens.numel() - start_pos;
+        int32_t* io = score_io(rows);
+        GTEN_HIP_OK(gten_hip_memcpy_h2d(io, targets, (size_t)rows * sizeof(int32_t)));
+        score_dev(tokens, start_pos, io, (float*)(io + rows), io + 2 * rows);
+        score_copy_back(io + rows, rows, lp_host, rank_host);
+    }
+    // gten_host_model_logits_all: f32 [n - start_pos][n_vocab] on the host
+    void logits_all(const Tensor& tokens, const int start_pos, float* out)
+    {
+        const int V = params.n_vocab;
+        std::vector<float> stage;
+        rows_logits(tokens, start_pos, [&](const float* lg, int r0, int cr, long long stride) {
+            stage.resize((size_t)cr * (size_t)stride);
+            GTEN_HIP_OK(gten_hip_memcpy_d2h(stage.data(), lg, stage.size() * sizeof(float)));
+            for (int r = 0; r < cr; r++) std::memcpy(out + (size_t)(r0 + r) * V, stage.data() + (size_t)r * stride, (size_t)V * sizeof(float));
+        });
+    }
+    // gten_host_model_score_many: text k = tokens[starts[k] .. starts[k + 1]) (1 .. min(2048, context) ids each), scored from
+    // position 0.  Texts of 16..2048 ids share row-segment groups (hidden_rows on a second TinyLlama of kScoreRows rows that
+    // aliases these weights) of at most kScoreTexts texts / kScoreRows rows, formed in order; the lm_head then runs per text.
+    // Other texts -- or all of them, where the configuration has no segmented prompt path -- go one by one through score_dev.
+    void score_many(const int32_t* tokens, const int32_t* starts, int n_texts, const int32_t* targets, float* lp_host, int32_t* rank_host)
+    {
+        const int total = starts[n_texts];
+        int32_t* io = score_io(total);
+        GTEN_HIP_OK(gten_hip_memcpy_h2d(io, targets, (size_t)total * sizeof(int32_t)));
+        float* lp = (float*)(io + total);
+        int32_t* rk = io + 2 * total;
+        const bool seg = gten_hip_row_segments_ok(params.n_embd, params.n_ffn, params.n_heads, params.n_query_groups,
+                                                  dtype_code(dtype_.wdtype), dtype_code(dtype_.adtype)) == 1;
+        std::vector<int> group;
+        int group_rows = 0;
+        auto flush = [&]() {
+            if (group.empty()) return;
+            if (!pre_) {
+                pre_.reset(new TinyLlama(kScoreRows, dtype_, params));
+                pre_->set_fast_decode(false);
+                for (int w = 0; w < n_weights(); w++) pre_->weight(w) = weight(w);
+            }
+            std::vector<int32_t> ids, st{0};
+            for (int k : group) {
+                ids.insert(ids.end(), tokens + starts[k], tokens + starts[k + 1]);
+                st.push_back((int32_t)ids.size());
+            }
+            Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
+            const Tensor h = pre_->hidden_rows(tk, st);
+            const size_t pitch = (size_t)h.bstride(0);
+            const uint8_t* hp = (const uint8_t*)h.device_ptr();
+            for (size_t g = 0; g < group.size(); g++) {
+                const int off = starts[group[g]];
+                lm_head_rows(hp + (size_t)st[g] * pitch, dtype_code(h.dtype()), pitch, st[g + 1] - st[g],
+                             [&](const float* lg, int r0, int cr, long long stride) {
+                                 GTEN_HIP_OK(gten_hip_row_logprobs(lg, cr, params.n_vocab, stride, io + off + r0, lp + off + r0, rk + off + r0, nullptr));
+                             });
+            }
+            group.clear();
+            group_rows = 0;
+        };
+        for (int k = 0; k < n_texts; k++) {
+            const int len = starts[k + 1] - starts[k];
+            if (!seg || len < 16 || len > 2048) {
+                Tensor tk(tokens + starts[k], {len}, kInt32);
+                score_dev(tk, 0, io + starts[k], lp + starts[k], rk + starts[k]);
+                continue;
+            }
+            if ((int)group.size() == kScoreTexts || group_rows + len > kScoreRows) flush();
+            group.push_back(k);
+            group_rows += len;
+        }
+        flush();
+        score_copy_back(io + total, total, lp_host, rank_host);
+    }
 
     // ---- single-token decode fast path (include/gten_hip.h, "decode fast path")
     void set_fast_decode(bool on) { fast_decode_ = on; }
@@ -210,6 +335,8 @@ public:
     ~TinyLlama()
     {
         if (dec_) gten_hip_decoder_destroy(dec_);
+        if (score_logits_) gten_hip_free(score_logits_);
+        if (score_io_) gten_hip_free(score_io_);
     }
     TinyLlama(const TinyLlama&) = delete;
     TinyLlama& operator=(const TinyLlama&) = delete;
@@ -399,6 +526,32 @@ private:
     std::vector<AttentionBlock> blocks_;
     gten_hip_decoder* dec_ = nullptr;
     bool fast_decode_ = [] { const char* e = std::getenv("GTEN_HIP_FAST_DECODE"); return !(e && e[0] == '0'); }();
+    // scoring (allocated on first use): the lm_head chunk [kScoreChunk][score_stride()] f32, the per-call device words
+    // [targets][log-probs][ranks], and the segmented-prompt model of score_many
+    void* score_logits_ = nullptr;
+    void* score_io_ = nullptr;
+    size_t score_io_bytes_ = 0;
+    std::unique_ptr<TinyLlama> pre_;
+
+    int32_t* score_io(int rows)
+    {
+        const size_t need = (size_t)rows * 3 * sizeof(int32_t);
+        if (need > score_io_bytes_) {
+            if (score_io_) GTEN_HIP_OK(gten_hip_free(score_io_));
+            score_io_ = nullptr;
+            GTEN_HIP_OK(gten_hip_malloc(&score_io_, need));
+            score_io_bytes_ = need;
+        }
+        return (int32_t*)score_io_;
+    }
+    // log-probs then ranks, `rows` words each, in ONE copy
+    void score_copy_back(const int32_t* dev, int rows, float* lp_host, int32_t* rank_host)
+    {
+        std::vector<int32_t> got((size_t)rows * 2);
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(got.data(), dev, got.size() * sizeof(int32_t)));
+        std::memcpy(lp_host, got.data(), (size_t)rows * sizeof(float));
+        if (rank_host) std::memcpy(rank_host, got.data() + rows, (size_t)rows * sizeof(int32_t));
+    }
 
     // The decoder works on the SAME HBM tensors the modules own: weights (packed
     // at load), the K/V caches (= attn.key.acv / attn.value.acv) and the logits

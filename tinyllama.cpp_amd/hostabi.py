@@ -44,6 +44,7 @@ class GtenHost:
     ]
     # include/gten_host_sample.h (top-k sampling, host/capi_sample.cpp)
     SAMPLE_SYMBOLS = ["gten_host_model_generate_topk", "gten_host_batch_generate_topk", "gten_host_batch_serve_topk"]
+    SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -68,6 +69,9 @@ class GtenHost:
         self._bserve_topk = _sig(L, "gten_host_batch_serve_topk", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                       C.c_float, C.c_uint64])
         self._bgen_topk = _sig(L, "gten_host_batch_generate_topk", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, vp, vp, vp])
+        self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
+        self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
+        self._score_many = _sig(L, "gten_host_model_score_many", ci, [vp, vp, vp, ci, vp, vp, vp])
         self._tok_create = _sig(L, "gten_host_tokenizer_create", vp, [C.c_char_p, ci])
         self._tok_free = _sig(L, "gten_host_tokenizer_free", None, [vp])
         self._tok_encode = _sig(L, "gten_host_tokenizer_encode", ci, [vp, C.c_char_p, ci, vp, ci])
@@ -207,6 +211,60 @@ class HostModel:
         if rc:
             raise GtenHipError(f"logits rc={rc}")
         return out
+
+    def score_rc(self, tokens, start_pos=0, targets=None):
+        """(return code, log-probs f32[n - start_pos], ranks int32[n - start_pos]) of gten_host_model_score (include/gten_host_score.h).
+        Row start_pos + i is scored against targets[i]; by default the next id, tokens[start_pos + 1:] + [-1] (-1: not scored)."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        rows = max(len(tokens) - start_pos, 1)
+        if targets is None:
+            targets = np.append(tokens[start_pos + 1:], -1)
+        targets = np.ascontiguousarray(targets, dtype=np.int32)
+        if len(targets) < rows:
+            targets = np.append(targets, np.full(rows - len(targets), -1, np.int32))
+        lp, rk = np.zeros(rows, np.float32), np.zeros(rows, np.int32)
+        rc = self.host._score(self.h, tokens.ctypes.data_as(C.c_void_p), len(tokens), start_pos, targets.ctypes.data_as(C.c_void_p),
+                              lp.ctypes.data_as(C.c_void_p), rk.ctypes.data_as(C.c_void_p))
+        return rc, lp, rk
+
+    def score(self, tokens, start_pos=0, targets=None):
+        """(log-probs, ranks) of rows [start_pos, n): see score_rc"""
+        rc, lp, rk = self.score_rc(tokens, start_pos, targets)
+        if rc:
+            raise GtenHipError(f"score rc={rc}")
+        return lp, rk
+
+    def logits_all(self, tokens, start_pos=0):
+        """f32 [n - start_pos][n_vocab]: the lm_head of every computed row (gten_host_model_logits_all)"""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.zeros((len(tokens) - start_pos, self.cfg.n_vocab), np.float32)
+        rc = self.host._logits_all(self.h, tokens.ctypes.data_as(C.c_void_p), len(tokens), start_pos, out.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise GtenHipError(f"logits_all rc={rc}")
+        return out
+
+    def score_many_rc(self, texts, targets=None):
+        """(return code, [log-probs per text], [ranks per text]) of gten_host_model_score_many: every text scored from position 0
+        against its next ids (by default) or targets[k]"""
+        texts = [np.ascontiguousarray(t, dtype=np.int32) for t in texts]
+        if targets is None:
+            targets = [np.append(t[1:], -1) for t in texts]
+        starts = np.zeros(len(texts) + 1, np.int32)
+        starts[1:] = np.cumsum([len(t) for t in texts])
+        toks = np.ascontiguousarray(np.concatenate(texts) if texts else np.zeros(0, np.int32), dtype=np.int32)
+        tg = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for t in targets]) if texts else np.zeros(0, np.int32), dtype=np.int32)
+        total = int(starts[-1])
+        lp, rk = np.zeros(max(total, 1), np.float32), np.zeros(max(total, 1), np.int32)
+        rc = self.host._score_many(self.h, toks.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), len(texts),
+                                   tg.ctypes.data_as(C.c_void_p), lp.ctypes.data_as(C.c_void_p), rk.ctypes.data_as(C.c_void_p))
+        return rc, [lp[starts[k]:starts[k + 1]].copy() for k in range(len(texts))], [rk[starts[k]:starts[k + 1]].copy() for k in range(len(texts))]
+
+    def score_many(self, texts, targets=None):
+        """([log-probs per text], [ranks per text]): see score_many_rc"""
+        rc, lp, rk = self.score_many_rc(texts, targets)
+        if rc:
+            raise GtenHipError(f"score_many rc={rc}")
+        return lp, rk
 
     def set_fast_decode(self, on):
         self.host._setfast(self.h, 1 if on else 0)
