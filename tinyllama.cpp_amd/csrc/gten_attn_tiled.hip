@@ -107,11 +107,18 @@ constexpr int AT_PHPITCH = AT_TILE + 8;      // halfs per probability row (528 b
 constexpr int AT_VTPITCH = AT_VSUB + 8;      // halfs per element row of the transposed V sub-tile (144 bytes)
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-template <bool FAST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_tiled_q8(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
-                                                       const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
-                                                       size_t q_pitch, size_t kv_pitch, size_t out_pitch,
-                                                       int n_heads, int n_kv, int n, int start_pos, _Float16* __restrict__ a16)
+// One row tile.  The kernels below are this body behind two ways of finding the tile's rows:
+//   PFX false: row tile rt of ONE prompt whose rows [start_pos, n) are new, K / V rows of every position in k / v;
+//   PFX true:  row tile rt of a prompt that CONTINUES a shared prefix of start_pos positions (k_attn_prefix_*): positions
+//              [0, start_pos) are rows of kpre / vpre, positions [start_pos, n) rows of k / v -- q, k, v, out and a16 arrive
+//              moved so that `position x pitch` lands on the prompt's row of the row matrix.  The select is per position,
+//              wherever the kernel forms a K / V row address; everything else is the same instructions.
+template <bool FAST, bool PFX>
+__device__ __forceinline__ void attn_tiled_q8_body(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                   const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                   size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                   int n_heads, int n_kv, int n, int start_pos, _Float16* __restrict__ a16,
+                                                   const int rt, const uint8_t* __restrict__ kpre, const uint8_t* __restrict__ vpre)
 {
     constexpr int P_BYTES = FAST ? AT_ROWS * AT_PHPITCH * 2 : AT_ROWS * AT_PPITCH * 4;
     constexpr int V_BYTES = FAST ? 64 * AT_VTPITCH * 2 + AT_ROWS * 64 * 4 : AT_VSUB * 64 * 4;
@@ -125,7 +132,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     __shared__ float s_row[AT_ROWS];
 
     const int h = blockIdx.x;
-    const int rt = gridDim.y - 1 - blockIdx.y;            // long (late) row tiles are scheduled first
     const int r0 = start_pos + rt * AT_ROWS;
     const int g = h / (n_heads / n_kv);
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lc = l & 15, lq = l >> 4;
@@ -133,6 +139,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int ntile = r_last / AT_TILE + 1;
     const uint8_t* kbase = k + (size_t)g * 68;
     const uint8_t* vbase = v + (size_t)g * 68;
+    const uint8_t* kpbase = PFX ? kpre + (size_t)g * 68 : nullptr;
+    const uint8_t* vpbase = PFX ? vpre + (size_t)g * 68 : nullptr;
+    // this kv head's slice of position c
+    auto krow = [&](int c) { return (PFX && c < start_pos ? kpbase : kbase) + (size_t)c * kv_pitch; };
+    auto vrow = [&](int c) { return (PFX && c < start_pos ? vpbase : vbase) + (size_t)c * kv_pitch; };
 
     QFrag qf;
 #pragma unroll
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
             if (c - lc > r_last) continue;                 // wave-uniform: nothing of this column group is visible
             float s[2][4];
-            tile_scores(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+            tile_scores(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
             for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -213,7 +224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
                 if (c - lc > r_last) continue;
                 float s[2][4];
-                tile_scores(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+                tile_scores(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
                 for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -264,7 +275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     float vdel = 0.f;
     auto vload = [&](int c0) {
         const int pos = threadIdx.x >> 2, qtr = threadIdx.x & 3, b = qtr >> 1;
-        const uint8_t* vs_ = vbase + (size_t)min(c0 + pos, n - 1) * kv_pitch;
+        const uint8_t* vs_ = vrow(min(c0 + pos, n - 1));
         vraw = *(const U4*)(vs_ + 2 + 34 * b + 16 * (qtr & 1));
         vdel = h2f(*(const uint16_t*)(vs_ + 34 * b));
     };
@@ -282,7 +293,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 continue;
             }
             float s[2][4];
-            tile_scores(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+            tile_scores(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
             for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -349,7 +360,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             {
                 // stage 64 positions of this kv head's V slice as f32: thread = (position, quarter of the 64 elements)
                 const int pos = threadIdx.x >> 2, qtr = threadIdx.x & 3, b = qtr >> 1;
-                const uint8_t* vs_ = vbase + (size_t)min(c0 + pos, n - 1) * kv_pitch;
+                const uint8_t* vs_ = vrow(min(c0 + pos, n - 1));
                 U4 raw = vraw;
                 float d = vdel;
                 if (!FAST) {
@@ -488,11 +499,12 @@ __device__ __forceinline__ void tile_scores_f16(const QFragH& q, const uint8_t* 
 // FAST (the default): p.V on the matrix cores as in k_attn_tiled_q8<true> -- the f16 probabilities and the f16 V elements
 // ARE the operands (no extra rounding at all: only the order of the f32 additions differs from the four stride-4
 // accumulators), the V sub-tile staged transposed, one v_mfma_f32_16x16x32_f16 per 32 positions of 16 rows x 16 elements.
-template <bool FAST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_tiled_f16(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
-                                                        const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
-                                                        size_t q_pitch, size_t kv_pitch, size_t out_pitch,
-                                                        int n_heads, int n_kv, int n, int start_pos)
+template <bool FAST, bool PFX>
+__device__ __forceinline__ void attn_tiled_f16_body(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                    const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                    size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                    int n_heads, int n_kv, int n, int start_pos,
+                                                    const int rt, const uint8_t* __restrict__ kpre, const uint8_t* __restrict__ vpre)
 {
     __shared__ __attribute__((aligned(16))) float s_p[AT_ROWS * AT_PPITCH];
     __shared__ __attribute__((aligned(16))) float s_v[AT_VSUB * 64];
@@ -504,7 +516,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     __shared__ float s_row[AT_ROWS];
 
     const int h = blockIdx.x;
-    const int rt = gridDim.y - 1 - blockIdx.y;
     const int r0 = start_pos + rt * AT_ROWS;
     const int g = h / (n_heads / n_kv);
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, lc = l & 15, lq = l >> 4;
@@ -512,6 +523,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int ntile = r_last / AT_TILE + 1;
     const uint8_t* kbase = k + (size_t)g * 128;
     const uint8_t* vbase = v + (size_t)g * 128;
+    const uint8_t* kpbase = PFX ? kpre + (size_t)g * 128 : nullptr;
+    const uint8_t* vpbase = PFX ? vpre + (size_t)g * 128 : nullptr;
+    auto krow = [&](int c) { return (PFX && c < start_pos ? kpbase : kbase) + (size_t)c * kv_pitch; };
+    auto vrow = [&](int c) { return (PFX && c < start_pos ? vpbase : vbase) + (size_t)c * kv_pitch; };
 
     QFragH qf;
 #pragma unroll
@@ -537,7 +552,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
                 if (c - lc > r_last) continue;
                 float s[2][4];
-                tile_scores_f16(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+                tile_scores_f16(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
                 for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -596,7 +611,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
             if (c - lc > r_last) continue;
             float s[2][4];
-            tile_scores_f16(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+            tile_scores_f16(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
             for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -637,7 +652,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                 const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
                 if (c - lc > r_last) continue;
                 float s[2][4];
-                tile_scores_f16(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+                tile_scores_f16(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
                 for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -683,7 +698,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             const int c = t * AT_TILE + 64 * w + 16 * cg + lc;
             float s[2][4];
             const bool any = c - lc <= r_last;
-            if (any) tile_scores_f16(qf, kbase + (size_t)min(c, n - 1) * kv_pitch, lq, s);
+            if (any) tile_scores_f16(qf, krow(min(c, n - 1)), lq, s);
 #pragma unroll
             for (int rg = 0; rg < 2; rg++)
 #pragma unroll
@@ -701,7 +716,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
             {
                 // stage 64 positions of this kv head's V slice as f32: thread = (position, quarter of the 64 elements)
                 const int pos = threadIdx.x >> 2, qtr = threadIdx.x & 3;
-                const uint8_t* vs_ = vbase + (size_t)min(c0 + pos, n - 1) * kv_pitch + 32 * qtr;
+                const uint8_t* vs_ = vrow(min(c0 + pos, n - 1)) + 32 * qtr;
                 const uint4 r0w = *(const uint4*)vs_, r1w = *(const uint4*)(vs_ + 16);
                 const unsigned raw[8] = {r0w.x, r0w.y, r0w.z, r0w.w, r1w.x, r1w.y, r1w.z, r1w.w};
                 float* dst = s_v + pos * 64 + 16 * qtr;
@@ -770,6 +785,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     }
 }
 
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_tiled_q8(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                       const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                       size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                       int n_heads, int n_kv, int n, int start_pos, _Float16* __restrict__ a16)
+{
+    // long (late) row tiles are scheduled first
+    attn_tiled_q8_body<FAST, false>(q, k, v, out, q_pitch, kv_pitch, out_pitch, n_heads, n_kv, n, start_pos, a16, (int)(gridDim.y - 1 - blockIdx.y), nullptr, nullptr);
+}
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_tiled_f16(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                        const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                        size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                        int n_heads, int n_kv, int n, int start_pos)
+{
+    attn_tiled_f16_body<FAST, false>(q, k, v, out, q_pitch, kv_pitch, out_pitch, n_heads, n_kv, n, start_pos, (int)(gridDim.y - 1 - blockIdx.y), nullptr, nullptr);
+}
+
+// ---- ALL the prompts of a row matrix that continue one shared prefix, in one launch (gten_hip_block_rows_prefixed).
+// grid = (head, row tile over all prompts); tiles[blockIdx.y] = (first matrix row of the tile's prompt, its rows, the tile's
+// index inside the prompt), long tiles first.  The prompt's rows are positions prefix_len .. prefix_len + rows - 1: the
+// base pointers move back by prefix_len - first rows, so that the body's `position x pitch` lands on matrix row
+// first + (position - prefix_len) for every position it reads there (>= prefix_len; earlier ones are rows of kpre / vpre).
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_prefix_q8(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                       const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                       size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                       int n_heads, int n_kv, int prefix_len, const int4* __restrict__ tiles,
+                                                       const uint8_t* __restrict__ kpre, const uint8_t* __restrict__ vpre, _Float16* __restrict__ a16)
+{
+    const int4 t = tiles[blockIdx.y];
+    const ptrdiff_t mv = (ptrdiff_t)t.x - prefix_len;
+    attn_tiled_q8_body<FAST, true>(q + mv * (ptrdiff_t)q_pitch, k + mv * (ptrdiff_t)kv_pitch, v + mv * (ptrdiff_t)kv_pitch, out + mv * (ptrdiff_t)out_pitch,
+                                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv, prefix_len + t.y, prefix_len,
+                                   a16 ? a16 + (size_t)t.x * (n_heads * 64) : nullptr, t.z, kpre, vpre);
+}
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_prefix_f16(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                        const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                        size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                        int n_heads, int n_kv, int prefix_len, const int4* __restrict__ tiles,
+                                                        const uint8_t* __restrict__ kpre, const uint8_t* __restrict__ vpre)
+{
+    const int4 t = tiles[blockIdx.y];
+    const ptrdiff_t mv = (ptrdiff_t)t.x - prefix_len;
+    attn_tiled_f16_body<FAST, true>(q + mv * (ptrdiff_t)q_pitch, k + mv * (ptrdiff_t)kv_pitch, v + mv * (ptrdiff_t)kv_pitch, out + mv * (ptrdiff_t)out_pitch,
+                                    q_pitch, kv_pitch, out_pitch, n_heads, n_kv, prefix_len + t.y, prefix_len, t.z, kpre, vpre);
+}
+
 } // namespace
 
 int gten_launch_attn_tiled_f16(const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch,
@@ -797,5 +861,30 @@ int gten_launch_attn_tiled(const void* q, const void* k, const void* v, void* ou
     else
         GTR_LAUNCH(KT_ATTN_TILED, k_attn_tiled_q8<true>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v,
                    (uint8_t*)out, q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, n, start_pos, (_Float16*)a16);
+    return 0;
+}
+
+int gten_launch_attn_prefix(int f16, const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                            int n_heads, int n_kv_heads, int prefix_len, const void* tiles, int n_tiles, const void* k_prefix, const void* v_prefix, void* a16)
+{
+    const dim3 grid(n_heads, n_tiles);
+    const bool exact = gtr::prefill_exact();
+    if (f16) {
+        if (exact)
+            GTR_LAUNCH(KT_ATTN_TILED, k_attn_prefix_f16<false>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                       q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, prefix_len, (const int4*)tiles, (const uint8_t*)k_prefix, (const uint8_t*)v_prefix);
+        else
+            GTR_LAUNCH(KT_ATTN_TILED, k_attn_prefix_f16<true>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                       q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, prefix_len, (const int4*)tiles, (const uint8_t*)k_prefix, (const uint8_t*)v_prefix);
+        return 0;
+    }
+    if (exact)
+        GTR_LAUNCH(KT_ATTN_TILED, k_attn_prefix_q8<false>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, prefix_len, (const int4*)tiles, (const uint8_t*)k_prefix, (const uint8_t*)v_prefix,
+                   (_Float16*)nullptr);
+    else
+        GTR_LAUNCH(KT_ATTN_TILED, k_attn_prefix_q8<true>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, prefix_len, (const int4*)tiles, (const uint8_t*)k_prefix, (const uint8_t*)v_prefix,
+                   (_Float16*)a16);
     return 0;
 }

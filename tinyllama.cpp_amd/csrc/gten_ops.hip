@@ -11,6 +11,7 @@
 #include <vector>
 #include <algorithm>
 #include "gten_rt.h"
+#include "gten_hip_prefix.h"
 #include "gten_hip_score.h"
 #include "gten_row_logprobs.h"
 
@@ -298,15 +299,11 @@ __global__ __launch_bounds__(256) void k_rope(uint8_t* __restrict__ x, int dtype
     store_row(v, dtype, d, row);
 }
 
-// the same for TWO matrices in one launch (q and k of a prompt: blockIdx.y picks the matrix)
-__global__ __launch_bounds__(256) void k_rope2(uint8_t* __restrict__ x0, size_t pitch0, int d0, uint8_t* __restrict__ x1, size_t pitch1, int d1,
-                                               int dtype, int d_head, int start_pos, const float2* __restrict__ table)
+// the same for TWO matrices in one launch (q and k of a prompt: blockIdx.y picks the matrix).  One row of d elements at
+// position r:
+__device__ __forceinline__ void rope2_row(uint8_t* __restrict__ row, int d, int dtype, int d_head, int r, const float2* __restrict__ table)
 {
     float* v = (float*)g_smem;
-    const int r = start_pos + blockIdx.x;
-    const bool second = blockIdx.y != 0;
-    const int d = second ? d1 : d0;
-    uint8_t* row = second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0;
     load_row_f32(row, dtype, d, v);
     __syncthreads();
     const int half = d_head >> 1;
@@ -320,17 +317,30 @@ __global__ __launch_bounds__(256) void k_rope2(uint8_t* __restrict__ x0, size_t 
     __syncthreads();
     store_row(v, dtype, d, row);
 }
+__global__ __launch_bounds__(256) void k_rope2(uint8_t* __restrict__ x0, size_t pitch0, int d0, uint8_t* __restrict__ x1, size_t pitch1, int d1,
+                                               int dtype, int d_head, int start_pos, const float2* __restrict__ table)
+{
+    const int r = start_pos + blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? d1 : d0, dtype, d_head, r, table);
+}
+// ... for the rows of SEVERAL prompts that continue a shared prefix (gten_hip_block_rows_prefixed): matrix row r sits at
+// position prefix_len + row_pos[r], row_pos[r] = r - (first row of its prompt)
+__global__ __launch_bounds__(256) void k_rope2_rows(uint8_t* __restrict__ x0, size_t pitch0, int d0, uint8_t* __restrict__ x1, size_t pitch1, int d1,
+                                                    int dtype, int d_head, int prefix_len, const int* __restrict__ row_pos, const float2* __restrict__ table)
+{
+    const int r = blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? d1 : d0, dtype, d_head, prefix_len + row_pos[r], table);
+}
 
 // ... and for Q8 rows with 64-wide heads, ONE WAVE per (row, matrix): lane L owns block L -- the first (even L) or second
 // (odd L) half of head L / 2 -- and takes its partner's 32 values from the neighbouring lane; k_rope's arithmetic per
 // element, the row in registers, dword loads and stores (8 -> 4 us per launch on a 256-id prompt).
-__global__ __launch_bounds__(64) void k_rope2_q8w(uint8_t* __restrict__ x0, size_t pitch0, int nblk0, uint8_t* __restrict__ x1, size_t pitch1, int nblk1,
-                                                  int start_pos, const float2* __restrict__ table)
+__device__ __forceinline__ void rope2_q8w_row(uint8_t* __restrict__ row, int nblk, int r, const float2* __restrict__ table)
 {
-    const int L = threadIdx.x, odd = L & 1, r = start_pos + blockIdx.x;
-    const bool second = blockIdx.y != 0;
-    if (L >= (second ? nblk1 : nblk0)) return;
-    uint8_t* row = second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0;
+    const int L = threadIdx.x, odd = L & 1;
+    if (L >= nblk) return;
     const unsigned* pw = (const unsigned*)(row + (size_t)(L >> 1) * 68) + (odd ? 8 : 0);
     unsigned dw[9];
 #pragma unroll
@@ -365,6 +375,21 @@ __global__ __launch_bounds__(64) void k_rope2_q8w(uint8_t* __restrict__ x0, size
         pq[j] = wd;
     }
     store_q8_block_lane(row, L, pq, sc.d16);
+}
+__global__ __launch_bounds__(64) void k_rope2_q8w(uint8_t* __restrict__ x0, size_t pitch0, int nblk0, uint8_t* __restrict__ x1, size_t pitch1, int nblk1,
+                                                  int start_pos, const float2* __restrict__ table)
+{
+    const int r = start_pos + blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_q8w_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? nblk1 : nblk0, r, table);
+}
+// (the rows of several prompts behind a shared prefix: k_rope2_rows)
+__global__ __launch_bounds__(64) void k_rope2_q8w_rows(uint8_t* __restrict__ x0, size_t pitch0, int nblk0, uint8_t* __restrict__ x1, size_t pitch1, int nblk1,
+                                                       int prefix_len, const int* __restrict__ row_pos, const float2* __restrict__ table)
+{
+    const int r = blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_q8w_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? nblk1 : nblk0, prefix_len + row_pos[r], table);
 }
 static bool rope_q8w_ok(const void* x, size_t pitch, int dtype, int d, int d_head)
 {
@@ -1038,7 +1063,10 @@ int gten_hip_set_block_rows(int on)
 // sequence: the f16 copy of an input is made once for the matrices that share it, q | k | v and gate | up are one W.x launch
 // each, q and k are rotated in one launch, silu and the product are one pass, and the two residual sums ride in the
 // epilogues of the o and down projections.  Every buffer ends with the bytes the module sequence leaves in it.
-int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
+// (pfx, gten_hip_block_rows_prefixed: the segments' rows continue a shared prefix -- RoPE and attention are one launch each
+//  for all of them; every other launch is the segmented call's)
+struct PrefixRows { const void* k; const void* v; int len; const int* tiles; int n_tiles; const int* row_pos; };
+static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, const PrefixRows* pfx)
 {
     GTR_NEED_INIT();
     GTR_REQUIRE(b, "block_rows: null descriptor");
@@ -1086,12 +1114,19 @@ int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
             const float2* table = nullptr;
             if ((rc = rope_table(dh, &table))) return rc;
             // (row segments: every prompt from position 0 -- base pointers moved to its first row, start_pos 0)
-            for (const auto& sg : segs) {
+            if (pfx)
+                GTR_LAUNCH(KT_ROPE, k_rope2_rows, dim3(n, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q, hE, E, (uint8_t*)b->k, hKV, KV, GTEN_F16, dh, pfx->len,
+                           pfx->row_pos, table);
+            else for (const auto& sg : segs) {
                 const size_t r0 = seg ? (size_t)sg.first : 0;
                 GTR_LAUNCH(KT_ROPE, k_rope2, dim3(sg.second, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q + r0 * hE, hE, E, (uint8_t*)b->k + r0 * hKV, hKV, KV,
                            GTEN_F16, dh, seg ? 0 : start_pos, table);
             }
         }
+        if (pfx) {
+            if ((rc = gten_launch_attn_prefix(1, b->q, b->k, b->v, b->attn_out, hE, hKV, hE, b->n_heads, b->n_kv_heads, pfx->len, pfx->tiles, pfx->n_tiles,
+                                              pfx->k, pfx->v, nullptr))) return rc;
+        } else
         for (const auto& sg : segs) {
             const size_t r0 = seg ? (size_t)sg.first : 0;
             if ((rc = gten_launch_attn_tiled_f16((const uint8_t*)b->q + r0 * hE, (const uint8_t*)b->k + r0 * hKV, (const uint8_t*)b->v + r0 * hKV,
@@ -1158,6 +1193,13 @@ int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
         if ((rc = rope_table(dh, &table))) return rc;
         const bool wave_rows = rope_q8w_ok(b->q, pE, GTEN_Q8, E, dh) && rope_q8w_ok(b->k, pKV, GTEN_Q8, KV, dh);
         // (row segments: every prompt from position 0 -- base pointers moved to its first row, start_pos 0)
+        if (pfx) {
+            if (wave_rows)
+                GTR_LAUNCH(KT_ROPE, k_rope2_q8w_rows, dim3(n, 2), dim3(64), 0, (uint8_t*)b->q, pE, E / 32, (uint8_t*)b->k, pKV, KV / 32, pfx->len, pfx->row_pos, table);
+            else
+                GTR_LAUNCH(KT_ROPE, k_rope2_rows, dim3(n, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q, pE, E, (uint8_t*)b->k, pKV, KV, GTEN_Q8, dh, pfx->len,
+                           pfx->row_pos, table);
+        } else
         for (const auto& sg : segs) {
             const size_t r0 = seg ? (size_t)sg.first : 0;
             uint8_t* qs = (uint8_t*)b->q + r0 * pE;
@@ -1168,6 +1210,10 @@ int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
                 GTR_LAUNCH(KT_ROPE, k_rope2, dim3(sg.second, 2), dim3(256), (size_t)E * 4, qs, pE, E, ks, pKV, KV, GTEN_Q8, dh, seg ? 0 : start_pos, table);
         }
     }
+    if (pfx) {
+        if ((rc = gten_launch_attn_prefix(0, b->q, b->k, b->v, b->attn_out, pE, pKV, pE, b->n_heads, b->n_kv_heads, pfx->len, pfx->tiles, pfx->n_tiles,
+                                          pfx->k, pfx->v, fold ? (void*)a16 : nullptr))) return rc;
+    } else
     for (const auto& sg : segs) {
         const size_t r0 = seg ? (size_t)sg.first : 0;
         if ((rc = gten_launch_attn_tiled((const uint8_t*)b->q + r0 * pE, (const uint8_t*)b->k + r0 * pKV, (const uint8_t*)b->v + r0 * pKV,
@@ -1204,6 +1250,59 @@ int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
         if ((rc = gten_launch_matmul_mfma_multi(b->gate, pF, b->wdtype, m, GTEN_Q8, n, F, start_pos, fold))) return rc;
     }
     return 0;
+}
+
+int gten_hip_block_rows(const gten_hip_block_desc* b, int n, int start_pos)
+{
+    return block_rows_impl(b, n, start_pos, nullptr);
+}
+
+// The prefixed call's device tables, one per library stream: the row tiles of all segments (first matrix row of the segment,
+// its rows, tile index; long tiles first) and behind them every matrix row's index inside its segment.  They depend on the
+// segments alone, so the blocks of a model share one upload (on the calling stream, which is waited for: a prompt batch
+// starts on an idle stream anyway, and the host vector is free again at once).
+struct PrefixTables {
+    std::vector<int32_t> seg;      // the segments the device copy was made for
+    int* dev = nullptr;
+    int n_tiles = 0;
+};
+static PrefixTables g_pfx_tab[2];
+static constexpr int kPfxTileCap = GTEN_SEG_MAX_ROWS / 32 + GTEN_SEG_MAX_ROWS / GTEN_MFMA_MIN_ROWS;     // every segment ends with one partial tile at most
+
+int gten_hip_block_rows_prefixed(const gten_hip_block_desc* b, int n, const void* k_prefix, const void* v_prefix, int prefix_len)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(b, "block_rows_prefixed: null descriptor");
+    GTR_REQUIRE(!g_seg.empty(), "block_rows_prefixed: no row segments are set (gten_hip_set_row_segments)");
+    GTR_REQUIRE(k_prefix && v_prefix && ((uintptr_t)k_prefix & 15) == 0 && ((uintptr_t)v_prefix & 15) == 0, "block_rows_prefixed: null or unaligned prefix rows");
+    GTR_REQUIRE(prefix_len >= 1, "block_rows_prefixed: a prefix of %d rows", prefix_len);
+    int longest = 0;
+    for (size_t k = 0; k + 1 < g_seg.size(); k++) longest = std::max(longest, g_seg[k + 1] - g_seg[k]);
+    GTR_REQUIRE(prefix_len + longest <= GTEN_ROPE_MAX_POS, "block_rows_prefixed: prefix %d + a segment of %d rows (at most %d positions)", prefix_len, longest,
+                GTEN_ROPE_MAX_POS);
+    PrefixTables& t = g_pfx_tab[stream_index() & 1];
+    if (!t.dev) GTR_CHECK(hipMalloc((void**)&t.dev, ((size_t)kPfxTileCap * 4 + GTEN_SEG_MAX_ROWS) * sizeof(int)));
+    if (t.seg != g_seg) {
+        std::vector<int> host((size_t)kPfxTileCap * 4 + GTEN_SEG_MAX_ROWS, 0);
+        int most = 0, nt = 0;
+        for (size_t k = 0; k + 1 < g_seg.size(); k++) most = std::max(most, (g_seg[k + 1] - g_seg[k] + 31) / 32);
+        for (int ti = most - 1; ti >= 0; ti--)
+            for (size_t k = 0; k + 1 < g_seg.size(); k++) {
+                const int rows = g_seg[k + 1] - g_seg[k];
+                if (ti * 32 >= rows) continue;
+                host[(size_t)nt * 4] = g_seg[k]; host[(size_t)nt * 4 + 1] = rows; host[(size_t)nt * 4 + 2] = ti;
+                nt++;
+            }
+        GTR_REQUIRE(nt <= kPfxTileCap, "block_rows_prefixed: %d row tiles", nt);
+        for (size_t k = 0; k + 1 < g_seg.size(); k++)
+            for (int r = g_seg[k]; r < g_seg[k + 1]; r++) host[(size_t)kPfxTileCap * 4 + (size_t)r] = r - g_seg[k];
+        GTR_CHECK(hipMemcpyAsync(t.dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, stream()));
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        t.seg = g_seg;
+        t.n_tiles = nt;
+    }
+    const PrefixRows pfx{k_prefix, v_prefix, prefix_len, t.dev, t.n_tiles, t.dev + (size_t)kPfxTileCap * 4};
+    return block_rows_impl(b, n, 0, &pfx);
 }
 
 int gten_hip_row_segments_ok(int n_embd, int n_ffn, int n_heads, int n_kv_heads, int wdtype, int adtype)

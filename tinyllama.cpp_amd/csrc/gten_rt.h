@@ -104,6 +104,11 @@ int gten_launch_attn_tiled(const void* q, const void* k, const void* v, void* ou
 // ... and for f16 activations (f16 MFMA scores: agrees with the row kernel to f32 summation order, not byte for byte)
 int gten_launch_attn_tiled_f16(const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch,
                                size_t out_pitch, int n, int n_heads, int n_kv_heads, int start_pos);
+// ... and for ALL the prompts of a row matrix that continue one shared prefix (include/gten_hip_prefix.h): `tiles` = n_tiles
+// device entries (first matrix row of the prompt, its rows, tile index inside it, 0), long tiles first; f16: the activation dtype
+int gten_launch_attn_prefix(int f16, const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                            int n_heads, int n_kv_heads, int prefix_len, const void* tiles, int n_tiles, const void* k_prefix, const void* v_prefix,
+                            void* a16);
 
 namespace gtr {
 const int* row_segments(int* n_segments);   // gten_hip_set_row_segments: starts[0 .. n] or null

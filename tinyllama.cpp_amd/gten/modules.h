@@ -96,6 +96,22 @@ inline PendingRow& pending_row()
     return p;
 }
 
+// Rows that continue a shared prefix (include/gten_hip_prefix.h; TinyLlama::hidden_rows_prefixed).  While `len` > 0 every
+// AttentionBlock::forward_rows hands its descriptor to `call` with the next layer's prefix K / V rows instead of calling
+// gten_hip_block_rows.  `call` is installed by the translation unit that links the entry point (host/capi_prefix.cpp):
+// nothing in this header refers to it, so code built on these headers alone does not need the symbol.
+struct PrefixedRows {
+    int (*call)(const gten_hip_block_desc* b, int n, const void* k_prefix, const void* v_prefix, int prefix_len) = nullptr;
+    std::vector<std::pair<const void*, const void*>> kv;      // per layer: the prefix's K and V rows
+    int len = 0;
+    size_t layer = 0;                                         // the next block's layer
+};
+inline PrefixedRows& prefixed_rows()
+{
+    static PrefixedRows p;
+    return p;
+}
+
 inline bool& fused_rows_enabled()
 {
     static bool on = [] { const char* e = std::getenv("GTEN_HIP_FAST_DECODE"); return !(e && e[0] == '0'); }();
@@ -536,6 +552,13 @@ private:
         b.ffn_norm_out = ffn_norm.acv.device_ptr_mut();
         b.gate = ffn_gate_proj.acv.device_ptr_mut(); b.up = ffn_up_proj.acv.device_ptr_mut(); b.down = ffn_down_proj.acv.device_ptr_mut();
         b.out = attn_res.acv.device_ptr_mut();
+        detail::PrefixedRows& pr = detail::prefixed_rows();
+        if (pr.len > 0) {
+            GTEN_ASSERTM(pr.call && pr.layer < pr.kv.size() && start_pos == 0, "prefixed rows: layer %zu of %zu", pr.layer, pr.kv.size());
+            const auto& kv = pr.kv[pr.layer++];
+            GTEN_HIP_OK(pr.call(&b, n, kv.first, kv.second, pr.len));      // (not handled: an error too -- the modules know no prefix)
+            return true;
+        }
         const int rc = gten_hip_block_rows(&b, n, start_pos);
         if (rc == GTEN_HIP_NOT_HANDLED) return false;
         GTEN_HIP_OK(rc);

@@ -99,6 +99,7 @@ class GtenHip:
     SAMPLE_SYMBOLS = ["gten_hip_decoder_set_sampling", "gten_hip_sample_rows"]
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
+    PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -134,6 +135,7 @@ class GtenHip:
         self._attn = _sig(L, "gten_hip_qkv_attn", ci, [vp, vp, vp, vp, ci, sz, sz, sz, ci, ci, ci, ci, ci])
         self._prefill_exact = _sig(L, "gten_hip_set_prefill_exact", ci, [ci])
         self._block_rows = _sig(L, "gten_hip_block_rows", ci, [C.POINTER(BlockDesc), ci, ci])
+        self._block_rows_prefixed = _sig(L, "gten_hip_block_rows_prefixed", ci, [C.POINTER(BlockDesc), ci, vp, vp, ci])
         self._set_block_rows = _sig(L, "gten_hip_set_block_rows", ci, [ci])
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
         self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
@@ -298,6 +300,20 @@ class GtenHip:
         for k, v in bufs.items():
             setattr(d, k, v.ptr)
         rc = self._block_rows(C.byref(d), n, start_pos)
+        if rc == 1:
+            return False
+        self._check(rc)
+        return True
+
+    def block_rows_prefixed(self, n, ints, bufs, k_prefix, v_prefix, prefix_len):
+        """gten_hip_block_rows_prefixed (include/gten_hip_prefix.h): block_rows for segments whose rows continue a shared prefix;
+        k_prefix / v_prefix: DeviceBuffers (or device addresses) of the prefix's K / V rows of this layer"""
+        d = BlockDesc()
+        for k, v in ints.items():
+            setattr(d, k, int(v))
+        for k, v in bufs.items():
+            setattr(d, k, v.ptr)
+        rc = self._block_rows_prefixed(C.byref(d), n, getattr(k_prefix, "ptr", k_prefix), getattr(v_prefix, "ptr", v_prefix), int(prefix_len))
         if rc == 1:
             return False
         self._check(rc)

@@ -117,6 +117,25 @@ public:
         for (auto& block : blocks_) x = block.forward(x, 0);
         return norm_.forward(x, 0);
     }
+    // hidden_rows for prompts that all begin with the SAME prefix_len ids (include/gten_hip_prefix.h): `tokens`
+    // holds only what follows the prefix in each prompt, `prefix` is the model object whose K / V tensors hold the prefix's
+    // rows [0, prefix_len).  This object's K / V tensors then hold the prompts' remaining rows, at their rows of the matrix.
+    Tensor hidden_rows_prefixed(const Tensor& tokens, const std::vector<int32_t>& starts, TinyLlama& prefix, int prefix_len)
+    {
+        struct Scope {
+            detail::PrefixedRows& pr = detail::prefixed_rows();
+            Scope(TinyLlama& m, int len)
+            {
+                GTEN_ASSERTM(pr.call && len > 0, "hidden_rows_prefixed: no device entry point installed (prefix %d)", len);
+                pr.kv.clear();
+                for (auto& blk : m.blocks_) pr.kv.push_back({blk.attn.key.acv.device_ptr(), blk.attn.value.acv.device_ptr()});
+                pr.layer = 0;
+                pr.len = len;
+            }
+            ~Scope() { pr.len = 0; pr.kv.clear(); }
+        } scope(prefix, prefix_len);
+        return hidden_rows(tokens, starts);
+    }
     Tensor logits_of_row(const Tensor& hidden, int row)
     {
         Tensor v = hidden;                                    // (a shallow handle: the same storage, its own shape)
@@ -616,6 +635,8 @@ public:
         for (size_t i = 1; i < seqs_.size(); i++)
             for (int w = 0; w < seqs_[0]->n_weights(); w++) seqs_[i]->weight(w) = seqs_[0]->weight(w);
         pre_.reset();                                        // (the shared prompt matrix aliases the weights too: rebuilt on next use)
+        prefix_set_.reset();                                 // (... and the prefix set, whose rows were computed with the old weights)
+        prefix_ids_.clear();
         // the shared decoder holds device pointers to the weights and to every cache set it was ever bound to (the spares among
         // them): it goes before they do and is rebuilt on next use
         if (dec_) { GTEN_HIP_OK(gten_hip_decoder_destroy(dec_)); dec_ = nullptr; }
@@ -657,50 +678,128 @@ public:
     {
         const int K = (int)slots.size();
         GTEN_ASSERTM(K >= 1 && K <= kPreMax && prompts.size() == slots.size(), "prefill_many: %d prompts", K);
-        if (!pre_) {
-            pre_.reset(new TinyLlama(kPreRows, dtype_, params_));
-            pre_->set_fast_decode(false);
-            for (int w = 0; w < seqs_[0]->n_weights(); w++) pre_->weight(w) = seqs_[0]->weight(w);
-        }
-        std::vector<int32_t> ids, starts{0};
-        for (const auto* p : prompts) {
-            GTEN_ASSERTM((int)p->size() >= 16 && (int)p->size() <= n_ctx_, "prefill_many: a prompt of %zu ids", p->size());
-            ids.insert(ids.end(), p->begin(), p->end());
-            starts.push_back((int32_t)ids.size());
-        }
-        GTEN_ASSERTM((int)ids.size() <= kPreRows, "prefill_many: %zu rows (at most %d)", ids.size(), kPreRows);
-        Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
-        const Tensor hidden = pre_->hidden_rows(tk, starts);
-        // every prompt's K / V rows into its own caches: one launch per layer
-        std::vector<gten_hip_copy_range> ranges;
-        for (int l = 0; l < params_.n_layers; l++) {
-            ranges.clear();
-            AttentionBlock& src = pre_->block(l);
-            const size_t pitch = (size_t)src.attn.key.acv.bstride(0);
-            for (int k = 0; k < K; k++) {
-                AttentionBlock& dst = cset(slots[(size_t)k]).block(l);
-                const size_t off = (size_t)starts[(size_t)k] * pitch, bytes = prompts[(size_t)k]->size() * pitch;
-                ranges.push_back({dst.attn.key.acv.device_ptr_mut(), (const uint8_t*)src.attn.key.acv.device_ptr() + off, bytes});
-                ranges.push_back({dst.attn.value.acv.device_ptr_mut(), (const uint8_t*)src.attn.value.acv.device_ptr() + off, bytes});
-            }
-            GTEN_HIP_OK(gten_hip_copy_ranges(ranges.data(), (int)ranges.size()));
-        }
+        ensure_pre();
+        for (const auto* p : prompts) GTEN_ASSERTM((int)p->size() >= 16 && (int)p->size() <= n_ctx_, "prefill_many: a prompt of %zu ids", p->size());
         first->assign((size_t)K, 0);
         // a prompt's first id: its logits row stays on the device and so does the sampler (gten_hip_argmax_row, the greedy rule
         // of tinyllama.cpp:416-424) -- the K ids come back in ONE 4 K-byte copy and one wait instead of K copies of 128 KB, K
         // waits and K host loops over the vocabulary (round 4); a caller that wants a prompt's logits gets them as before
         if (!first_ids_) first_ids_.reset(new Tensor({kPreMax}, kInt32));
         int32_t* ids_dev = (int32_t*)first_ids_->device_ptr_mut();
-        for (int k = 0; k < K; k++) {
-            const Tensor lg = pre_->logits_of_row(hidden, starts[(size_t)k + 1] - 1);
-            pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
-            if (logits_out && (*logits_out)[(size_t)k])
-                std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
-        }
+        // the prompts that begin with the shared prefix (set_prefix) are one row matrix of what follows it, the others one of
+        // whole prompts: two calls at most
+        std::vector<int> shared, plain;
+        for (int k = 0; k < K; k++) (shares_prefix(*prompts[(size_t)k]) ? shared : plain).push_back(k);
+        if (!shared.empty()) prefill_group(shared, (int)prefix_ids_.size(), slots, prompts, logits_out, ids_dev, pick);
+        if (!plain.empty()) prefill_group(plain, 0, slots, prompts, logits_out, ids_dev, pick);
         std::vector<int32_t> got((size_t)K);
         GTEN_HIP_OK(gten_hip_memcpy_d2h(got.data(), ids_dev, (size_t)K * sizeof(int32_t)));
         for (int k = 0; k < K; k++) (*first)[(size_t)k] = got[(size_t)k];
     }
+
+    // ---- a shared prefix (include/gten_host_prefix.h): the ids every later prompt may begin with, processed
+    // ONCE onto a cache set of its own.  A prompt that begins with them and has at least 16 ids of its own takes the short
+    // way in prefill_many_with: only its own rows are computed (hidden_rows_prefixed), its slot's caches get a copy of the
+    // prefix set's K / V rows in front of them.  Same bytes as the whole prompt: rows are independent in segmented calls.
+    // 0; -1: bad arguments (16 <= n, n + 17 <= context); -2: this batch does not process prompts as segments
+    int set_prefix(const int32_t* tokens, int n)
+    {
+        if (n == 0) { prefix_ids_.clear(); return 0; }
+        if (!tokens || n < 16 || n + 17 > n_ctx_ || n > kPreRows) return -1;
+        if (!batched_prompts() || !detail::prefixed_rows().call) return -2;
+        ensure_pre();
+        if (!prefix_set_) {
+            prefix_set_.reset(new TinyLlama(n_ctx_, dtype_, params_));
+            for (int w = 0; w < seqs_[0]->n_weights(); w++) prefix_set_->weight(w) = seqs_[0]->weight(w);
+        }
+        prefix_ids_.clear();                                   // (nothing shares a half-written set)
+        std::vector<int32_t> ids(tokens, tokens + n);
+        Tensor tk(ids.data(), {n}, kInt32);
+        (void)pre_->hidden_rows(tk, {0, n});
+        for (int l = 0; l < params_.n_layers; l++) {
+            AttentionBlock& src = pre_->block(l);
+            AttentionBlock& dst = prefix_set_->block(l);
+            const size_t bytes = (size_t)n * (size_t)src.attn.key.acv.bstride(0);
+            const gten_hip_copy_range r[2] = {{dst.attn.key.acv.device_ptr_mut(), src.attn.key.acv.device_ptr(), bytes},
+                                              {dst.attn.value.acv.device_ptr_mut(), src.attn.value.acv.device_ptr(), bytes}};
+            GTEN_HIP_OK(gten_hip_copy_ranges(r, 2));
+        }
+        GTEN_HIP_OK(gten_hip_sync());                          // (the set is read from either stream afterwards)
+        prefix_ids_ = std::move(ids);
+        return 0;
+    }
+    int prefix_len() const { return (int)prefix_ids_.size(); }
+    unsigned long long prompts_shared() const { return prompts_shared_; }
+    unsigned long long rows_computed() const { return rows_computed_; }
+    bool shares_prefix(const std::vector<int32_t>& p) const
+    {
+        const size_t P = prefix_ids_.size();
+        return P > 0 && p.size() >= P + 16 && std::equal(prefix_ids_.begin(), prefix_ids_.end(), p.begin());
+    }
+    // rows of the row matrix that prompt p costs
+    int computed_rows(const std::vector<int32_t>& p) const { return (int)p.size() - (shares_prefix(p) ? (int)prefix_ids_.size() : 0); }
+
+private:
+    void ensure_pre()
+    {
+        if (pre_) return;
+        pre_.reset(new TinyLlama(kPreRows, dtype_, params_));
+        pre_->set_fast_decode(false);
+        for (int w = 0; w < seqs_[0]->n_weights(); w++) pre_->weight(w) = seqs_[0]->weight(w);
+    }
+    // prompts[idx[..]] as ONE row matrix: whole (P = 0) or what follows the shared prefix of P ids
+    template <class Pick>
+    void prefill_group(const std::vector<int>& idx, int P, const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts,
+                       std::vector<float*>* logits_out, int32_t* ids_dev, Pick& pick)
+    {
+        std::vector<int32_t> ids, starts{0};
+        for (int k : idx) {
+            const std::vector<int32_t>& p = *prompts[(size_t)k];
+            ids.insert(ids.end(), p.begin() + P, p.end());
+            starts.push_back((int32_t)ids.size());
+        }
+        GTEN_ASSERTM((int)ids.size() <= kPreRows, "prefill_many: %zu rows (at most %d)", ids.size(), kPreRows);
+        rows_computed_ += ids.size();
+        if (P > 0) prompts_shared_ += idx.size();
+        Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
+        const Tensor hidden = P > 0 ? pre_->hidden_rows_prefixed(tk, starts, *prefix_set_, P) : pre_->hidden_rows(tk, starts);
+        // every prompt's K / V rows into its own caches (behind a copy of the prefix set's rows when it shares them): one
+        // launch per layer, two when the ranges do not fit one
+        std::vector<gten_hip_copy_range> ranges;
+        auto flush = [&]() {
+            if (!ranges.empty()) GTEN_HIP_OK(gten_hip_copy_ranges(ranges.data(), (int)ranges.size()));
+            ranges.clear();
+        };
+        for (int l = 0; l < params_.n_layers; l++) {
+            AttentionBlock& src = pre_->block(l);
+            const size_t pitch = (size_t)src.attn.key.acv.bstride(0);
+            for (size_t i = 0; i < idx.size(); i++) {
+                const int k = idx[i];
+                if (ranges.size() + (P > 0 ? 4 : 2) > (size_t)GTEN_HIP_MAX_COPY_RANGES) flush();
+                AttentionBlock& dst = cset(slots[(size_t)k]).block(l);
+                uint8_t* dk = (uint8_t*)dst.attn.key.acv.device_ptr_mut();
+                uint8_t* dv = (uint8_t*)dst.attn.value.acv.device_ptr_mut();
+                if (P > 0) {
+                    AttentionBlock& pre = prefix_set_->block(l);
+                    ranges.push_back({dk, pre.attn.key.acv.device_ptr(), (size_t)P * pitch});
+                    ranges.push_back({dv, pre.attn.value.acv.device_ptr(), (size_t)P * pitch});
+                }
+                const size_t off = (size_t)starts[i] * pitch, bytes = (size_t)(starts[i + 1] - starts[i]) * pitch;
+                ranges.push_back({dk + (size_t)P * pitch, (const uint8_t*)src.attn.key.acv.device_ptr() + off, bytes});
+                ranges.push_back({dv + (size_t)P * pitch, (const uint8_t*)src.attn.value.acv.device_ptr() + off, bytes});
+            }
+            flush();
+        }
+        for (size_t i = 0; i < idx.size(); i++) {
+            const int k = idx[i];
+            const Tensor lg = pre_->logits_of_row(hidden, starts[i + 1] - 1);
+            pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
+            if (logits_out && (*logits_out)[(size_t)k])
+                std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
+        }
+    }
+
+public:
     // one prompt onto sequence seq_i's caches; returns the argmax of its logits (logits_out may be null)
     int prefill(int seq_i, const std::vector<int32_t>& prompt, float* logits_out = nullptr)
     {
@@ -970,14 +1069,15 @@ public:
                 const int P = (int)prompts[(size_t)j].size();
                 GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
                 if (!batched || P < 16) break;                               // (short prompt: one by one below)
-                if (rows + P > kPreRows) break;
+                const int cost = computed_rows(prompts[(size_t)j]);          // (a prompt behind the shared prefix: its own rows only)
+                if (rows + cost > kPreRows) break;
                 next++;
                 (*out)[(size_t)j] = prompts[(size_t)j];
                 st.prompt_tokens += P;
                 const int mn = max_new_each ? max_new_each[j] : max_new;
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);
                 if (P >= limit) continue;                                    // no room to generate: returned as is
-                js.push_back(j); limits.push_back(limit); rows += P;
+                js.push_back(j); limits.push_back(limit); rows += cost;
             }
             if (js.empty()) {
                 if (next >= prompts.size()) return false;
@@ -1165,6 +1265,10 @@ private:
     std::vector<std::unique_ptr<TinyLlama>> spares_;   // spare cache sets of serve()
     std::vector<std::vector<gten_hip_kv_ptrs>> set_kv_;      // per cache set: its layers' cache pointers (gten_hip_decoder_slot_bind)
     std::unique_ptr<TinyLlama> pre_;         // the shared row matrix of batched prompt processing (prefill_many), made on first use
+    std::unique_ptr<TinyLlama> prefix_set_;  // the cache set that holds the shared prefix's K / V rows (set_prefix)
+    std::vector<int32_t> prefix_ids_;        // the shared prefix (empty: none)
+    unsigned long long prompts_shared_ = 0;  // prompts that took the short way
+    unsigned long long rows_computed_ = 0;   // prompt rows computed in segmented calls (the prefix's own rows not counted)
     std::unique_ptr<Tensor> first_ids_;      // [kPreMax] int32 on the device: the prompts' first ids (gten_hip_argmax_row)
     gten_hip_decoder* dec_ = nullptr;
     int n_ctx_;

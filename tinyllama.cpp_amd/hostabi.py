@@ -45,6 +45,7 @@ class GtenHost:
     # include/gten_host_sample.h (top-k sampling, host/capi_sample.cpp)
     SAMPLE_SYMBOLS = ["gten_host_model_generate_topk", "gten_host_batch_generate_topk", "gten_host_batch_serve_topk"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
+    PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -102,6 +103,8 @@ class GtenHost:
         self._btime = _sig(L, "gten_host_batch_time_family", ci, [vp, ci, ci, ci, C.POINTER(C.c_double), C.POINTER(ci)])
         self._bseqsteps = _sig(L, "gten_host_batch_seq_steps", ci, [vp, ci, vp, ci, ci, ci])
         self._bkvinfo = _sig(L, "gten_host_batch_kv_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
+        self._bsetprefix = _sig(L, "gten_host_batch_set_prefix", ci, [vp, vp, ci])
+        self._bprefixinfo = _sig(L, "gten_host_batch_prefix_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self._synthw = _sig(L, "gten_host_synth_weight", ci, [cfgp, C.c_uint64, ci, vp, sz])
         self._writeg = _sig(L, "gten_host_write_gten", ci, [cfgp, C.c_uint64, C.c_char_p])
         self._stoks = _sig(L, "gten_host_synthetic_tokens", None, [vp, ci, C.c_uint32, ci])
@@ -481,6 +484,22 @@ class HostBatch:
                                         float(temp) if ts is None else 1.0, C.c_uint64(int(seed))), "batch_serve_topk")
         keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
         return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
+
+    def set_prefix_rc(self, tokens):
+        """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""
+        tokens = np.ascontiguousarray([] if tokens is None else tokens, dtype=np.int32)
+        return self.host._bsetprefix(self.h, tokens.ctypes.data_as(C.c_void_p) if len(tokens) else None, len(tokens))
+
+    def set_prefix(self, tokens):
+        """the ids later prompts may begin with (None / []: none), processed once: a prompt that begins with them and has at
+        least 16 ids of its own is computed from there on, with the same logits, ids and cache rows (include/gten_host_prefix.h)"""
+        self._ck(self.set_prefix_rc(tokens), "batch_set_prefix")
+
+    def prefix_info(self):
+        """(prefix length, prompts that took the short way so far, prompt rows computed so far in segmented calls)"""
+        n, sh, rows = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._ck(self.host._bprefixinfo(self.h, C.byref(n), C.byref(sh), C.byref(rows)), "batch_prefix_info")
+        return n.value, sh.value, rows.value
 
     def decode_result(self, seq, n):
         out = C.c_int32(-1)

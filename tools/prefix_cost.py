@@ -1,0 +1,204 @@
+#!/usr/bin/env python3
+"""What a shared prompt prefix buys on the serving queue, one JSON line on stdout
+(tools/prefix_cost.py [--out profiles/prefix_cost.json] [--merge FILE ...]).
+
+Without --step this is a driver: it runs the steps below one after the other, each as a child process of its own under
+`timeout` (one process on the GPU at a time), stops at the first one that fails, and merges their results.
+
+  --step kernels   one full-size block (q4 weights, Q8 activations), the rows that follow a 256-id prefix in as many
+                   prompts of 64..256 ids as fit 4096 rows: per-layer time of the batched RoPE and attention launches
+                   (HIP events of the in-library profiler), the per-segment launches of the plain path on the same rows,
+                   and the whole prompts (prefix + their rows) the plain way; wall time of the whole block call for each.
+  --step serve     full-size synthetic q4, 256 slots, a queue of 1024 prompts -- the 256-id prefix plus 64..256 ids of
+                   their own, budgets of 32..224 new ids: served with the prefix unset and set, three times each in
+                   alternation: new tok/s, prefill_s, rows computed; the ids of both ways compared.
+                   On a build without the feature (the parent commit) only the unset runs are made: the baseline.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+PREFIX, SLOTS, QUEUE, CTX, REPS = 256, 256, 1024, 2048, 3
+STEP_LIMIT_S = {"kernels": 240, "serve": 600}
+
+
+def queue(host, cfg):
+    rng = np.random.default_rng(2025)
+    own = rng.integers(64, 257, QUEUE)
+    budgets = rng.integers(32, 225, QUEUE).astype(np.int32)
+    prefix = [int(t) for t in host.synthetic_tokens(PREFIX, seed=424242, n_vocab=cfg.n_vocab)]
+    prompts = [prefix + [int(t) for t in host.synthetic_tokens(int(n), seed=9000 + j, n_vocab=cfg.n_vocab)] for j, n in enumerate(own)]
+    return prefix, prompts, budgets
+
+
+def step_serve():
+    pkg = load_package()
+    pkg.hipabi.load(0)
+    host = pkg.load_host()
+    cfg = host.default_config(4, 3)
+    cfg.max_ctx = CTX
+    b = host.batch(cfg, SLOTS)
+    b.load_synthetic(4242)
+    prefix, prompts, budgets = queue(host, cfg)
+    has = hasattr(b, "set_prefix")
+    res = {"slots": SLOTS, "prompts": QUEUE, "prefix_ids": PREFIX, "own_ids": "64..256", "feature_in_build": has, "runs": []}
+    b.serve(prompts[:SLOTS], CTX, -1, 8, max_new=4)                       # warm-up: graphs, first-use allocations
+    if has:
+        b.set_prefix(prefix)
+        b.serve(prompts[:SLOTS], CTX, -1, 8, max_new=4)
+        b.set_prefix(None)
+    ids = {}
+    for rep in range(REPS):
+        for mode in (("unset", "set") if has else ("unset",)):
+            rows0 = 0
+            if has:
+                b.set_prefix(prefix if mode == "set" else None)
+                rows0 = b.prefix_info()[2]
+            t0 = time.perf_counter()
+            got, st = b.serve(prompts, CTX, -1, 8, max_new_each=budgets)
+            wall = time.perf_counter() - t0
+            run = {"prefix": mode, "rep": rep, "new_tok_s": round(st["new_tokens"] / wall, 1), "wall_s": round(wall, 4),
+                   "prefill_s": round(st["prefill_s"], 4), "decode_s": round(st["decode_s"], 4), "new_tokens": int(st["new_tokens"]),
+                   "prompt_tokens": int(st["prompt_tokens"])}
+            if has:
+                run["rows_computed"] = int(b.prefix_info()[2] - rows0)
+            res["runs"].append(run)
+            ids.setdefault(mode, got)
+    if has:
+        b.set_prefix(None)
+        res["same_ids_set_and_unset"] = bool(all(np.array_equal(x, y) for x, y in zip(ids["unset"], ids["set"])))
+    for mode in ids:
+        r = [x for x in res["runs"] if x["prefix"] == mode]
+        res[mode] = {"new_tok_s_median": float(np.median([x["new_tok_s"] for x in r])), "new_tok_s_min_max": [min(x["new_tok_s"] for x in r), max(x["new_tok_s"] for x in r)],
+                     "prefill_s_median": float(np.median([x["prefill_s"] for x in r])), "rows_computed": r[0].get("rows_computed")}
+    b.close()
+    return res
+
+
+def step_kernels():
+    pkg = load_package()
+    hip = pkg.hipabi.load(0)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle import orc
+    orc.build(ref=False)
+    oracle = orc.load_oracle()
+    from helpers import Q4, Q8, act_rows, rng, row_bytes
+    from test_block_rows_gpu import alloc_acts, make_block
+    E, H, KVH, F = 2048, 32, 4, 5632
+    r = rng(11)
+    w, widths = make_block(hip, oracle, r, Q4, E, H, KVH, F, 0)
+    own = []
+    for n in np.random.default_rng(2025).integers(64, 257, 64):
+        if sum(own) + int(n) > 4096:
+            break
+        own.append(int(n))
+    n_suf = sum(own)
+    ints = dict(adtype=Q8, wdtype=Q4, n_embd=E, n_heads=H, n_kv_heads=KVH, n_ffn=F)
+    rows = act_rows(oracle, r, PREFIX + n_suf, E, Q8)[0]
+    pre_rows, suf_rows = rows[:PREFIX], rows[PREFIX:]
+    starts = [0] + [int(x) for x in np.cumsum(own)]
+
+    def bufs_for(n, inp):
+        bufs = dict(w)
+        bufs.update(alloc_acts(hip, widths, n, 0, Q8))
+        bufs["inp"] = hip.upload(inp)
+        return bufs
+
+    b_pre = bufs_for(PREFIX, pre_rows)
+    hip.set_row_segments([0, PREFIX])
+    assert hip.block_rows(PREFIX, 0, ints, b_pre)
+    b_suf = bufs_for(n_suf, suf_rows)
+    # the whole prompts the plain way, in calls of at most 4096 rows
+    groups, cur = [], []
+    for k, n in enumerate(own):
+        if sum(PREFIX + own[i] for i in cur) + PREFIX + n > 4096:
+            groups.append(cur)
+            cur = []
+        cur.append(k)
+    groups.append(cur)
+    whole = []
+    for g in groups:
+        inp = np.concatenate([np.concatenate([pre_rows, suf_rows[starts[k]:starts[k + 1]]]) for k in g])
+        st = [0] + [int(x) for x in np.cumsum([PREFIX + own[k] for k in g])]
+        whole.append((st, bufs_for(st[-1], inp)))
+
+    def prefixed():
+        hip.set_row_segments(starts)
+        assert hip.block_rows_prefixed(n_suf, ints, b_suf, b_pre["k"], b_pre["v"], PREFIX)
+
+    def plain_suffixes():
+        hip.set_row_segments(starts)
+        assert hip.block_rows(n_suf, 0, ints, b_suf)
+
+    def plain_whole():
+        for st, bufs in whole:
+            hip.set_row_segments(st)
+            assert hip.block_rows(st[-1], 0, ints, bufs)
+
+    def measure(fn, reps=20):
+        fn()
+        hip.sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        hip.sync()
+        wall_us = 1e6 * (time.perf_counter() - t0) / reps
+        hip.prof_enable(True)
+        fn()
+        prof = hip.prof_read()
+        hip.prof_enable(False)
+        out = {"block_wall_us": round(wall_us, 1)}
+        for fam, key in (("rotary_emb", "rope"), ("qkv_attn_tiled", "attention")):
+            n, ms = prof.get(fam, (0, 0.0))
+            out[key] = {"launches": n, "us": round(1e3 * ms, 1)}
+        out["all_launches_us"] = round(1e3 * sum(ms for _, ms in prof.values()), 1)
+        return out
+
+    res = {"prompts": len(own), "rows_after_the_prefix": n_suf, "prefix_ids": PREFIX, "whole_prompt_calls": len(groups),
+           "prefixed": measure(prefixed), "plain_on_the_same_rows_no_prefix": measure(plain_suffixes), "whole_prompts_plain": measure(plain_whole)}
+    hip.set_row_segments(None)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--step", choices=sorted(STEP_LIMIT_S), default=None)
+    ap.add_argument("--merge", nargs="*", default=[], help="name=file.json: results measured elsewhere (the parent commit's runs) recorded beside these")
+    a = ap.parse_args()
+    if a.step:
+        res = {"serve": step_serve, "kernels": step_kernels}[a.step]()
+        print(json.dumps(res))
+        return 0
+    res = {"what": "shared prompt prefix, TinyLlama-1.1B q4 synthetic, %d slots, %d prompts = %d shared ids + 64..256 of their own" % (SLOTS, QUEUE, PREFIX)}
+    for step in ("kernels", "serve"):
+        p = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step],
+                           capture_output=True, text=True)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+            sys.stderr.write("\nprefix_cost: step %s ended with %d: stopping\n" % (step, p.returncode))
+            return 1
+        res[step] = json.loads(p.stdout.strip().splitlines()[-1])
+    for item in a.merge:
+        name, path = item.split("=", 1)
+        with open(path) as f:
+            res[name] = json.load(f)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
