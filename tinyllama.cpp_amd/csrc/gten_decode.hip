@@ -26,6 +26,7 @@
 #include "gten_rt.h"
 #include "gten_hip_sample.h"
 #include "gten_hip_ab.h"
+#include "gten_hip_prefix_decode.h"
 
 #include <cmath>
 #include <vector>
@@ -173,6 +174,22 @@ struct gten_hip_decoder {
     size_t hm_seq_stride = 0, hm_cache_bytes = 0, hm_chunk_bytes = 0;
     std::vector<char> hm_dirty;
     unsigned long long hm_imports = 0, hm_import_launches = 0;
+    // ---- a shared prefix (gten_hip_decoder_prefix_set, include/gten_hip_prefix_decode.h; decoders with shadows only).  pfx_hm: ONE more
+    // shadow, laid out as a sequence's, imported from the prefix set's rows [0, pfx_len) (pfx_stale: before the next sharing step);
+    // allocated by the first prefix_set, which also drops the captured graphs: from then on the step launches the _pfx kernels.
+    // share_rows[q]: the caller's promise for sequence q (gten_hip_decoder_slot_share; 0: none); share_cur[q]: the leading chunks
+    // q reads from pfx_hm = the value of share_dev[q] after the queued work -- its own shadow need not hold them.
+    // hm_dirty[q] & 1: somebody wrote q's rows (or bound others) -- that ends a promise; & 2: q was (re)started -- that does not.
+    uint8_t* pfx_hm = nullptr;
+    int* share_dev = nullptr;           // [n_seq] on the device, beside `step`
+    const void** pfx_tab = nullptr;     // device: [n_layers][k | v] of the prefix set
+    DecStep* pfx_step = nullptr;        // device: {pfx_len + 1} (the import kernels read a sequence's rows as step.n - 1)
+    std::vector<const void*> pfx_kv;    // the same on the host (watched: pfx_dirty)
+    int pfx_len = 0;
+    char pfx_dirty = 0;
+    bool pfx_stale = false;
+    std::vector<int> share_rows, share_cur;
+    unsigned long long pfx_imports = 0, hm_skip_imports = 0;
     // every decoder: do the caches it appends to overlap a watch of ANOTHER decoder (cached per registry epoch)
     unsigned long long watch_epoch = 0;
     bool watch_foreign = false;
@@ -228,6 +245,14 @@ static bool g_lane_skip = false;         // gten_hip_decoder_run leaves lanes wi
 // the cache rows as they lie (0: k_dec_attn_mm_g, round 4's kernel -- kept for the A/B and as the reference the tests hold
 // the new kernel to)
 static bool g_kv_head_major = true;
+// gten_hip_set_prefix_decode_shared: gten_hip_decoder_slot_share records promises (1) or nothing (0: every sequence decodes on
+// its own shadow, as before -- the tests' and the measurement's other side).  ON by default: tools/prefix_cost.py --decode measures
+// the shared step and the serving queue faster with it on by far more than the off runs' own spread.
+#define PFX_SHARED_DEFAULT true
+static bool g_pfx_shared = PFX_SHARED_DEFAULT;
+// host side, beside AttnArgs: the prefix shadow of the layer (K; V follows it) and the lane's shared counts -- k null: the decoder
+// holds no prefix shadow and launches the kernels it always did
+struct PfxArgs { const uint8_t* k = nullptr; const int* share = nullptr; };
 extern "C" int gten_hip_set_kv_head_major(int on)
 {
     g_kv_head_major = on != 0;
@@ -295,13 +320,20 @@ static bool grouped_one_pass(const AttnArgs& t, int n_seq)
 }
 
 template <int GRP, int ADT>
-static int launch_attention_g(const AttnArgs& t, int n_seq)
+static int launch_attention_g(const AttnArgs& t, int n_seq, const PfxArgs& pfx)
 {
     constexpr size_t NW = (ADT == GTEN_Q8) ? 17 : 32;
     const dim3 grid(n_seq, t.n_chunks, t.n_kv);
     if constexpr (ADT == GTEN_Q8) if (grouped_mm(t, n_seq) && t.hm_k) {
         // head-major shadows: one wave per (sequence, kv head, chunk), HM_WAVES consecutive chunks per workgroup
         const int n_cq = (t.n_chunks + HM_WAVES - 1) / HM_WAVES;
+        if (pfx.k) {
+            if (n_seq >= 128)
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_pfx<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+            else
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_pfx<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+            return 0;
+        }
         if (n_seq >= 128) DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq);
         else DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq);
         return 0;
@@ -330,6 +362,13 @@ static int launch_attention_g(const AttnArgs& t, int n_seq)
     }
     if constexpr (ADT == GTEN_F16) if (grouped_hm_f16(t, n_seq)) {
         const int n_cq = (t.n_chunks + HM_WAVES - 1) / HM_WAVES;
+        if (pfx.k) {
+            if (n_seq >= 128)
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfx<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+            else
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfx<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+            return 0;
+        }
         if (n_seq >= 128) DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq);
         else DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq);
         return 0;
@@ -355,21 +394,21 @@ static int launch_attention_g(const AttnArgs& t, int n_seq)
     return 0;
 }
 
-static int launch_attention_grouped(const AttnArgs& t, int n_seq)
+static int launch_attention_grouped(const AttnArgs& t, int n_seq, const PfxArgs& pfx = PfxArgs{})
 {
     if (t.adtype == GTEN_Q8) {
         switch (t.n_heads / t.n_kv) {
-        case 8: return launch_attention_g<8, GTEN_Q8>(t, n_seq);
-        case 4: return launch_attention_g<4, GTEN_Q8>(t, n_seq);
-        case 2: return launch_attention_g<2, GTEN_Q8>(t, n_seq);
-        default: return launch_attention_g<1, GTEN_Q8>(t, n_seq);
+        case 8: return launch_attention_g<8, GTEN_Q8>(t, n_seq, pfx);
+        case 4: return launch_attention_g<4, GTEN_Q8>(t, n_seq, pfx);
+        case 2: return launch_attention_g<2, GTEN_Q8>(t, n_seq, pfx);
+        default: return launch_attention_g<1, GTEN_Q8>(t, n_seq, pfx);
         }
     }
     switch (t.n_heads / t.n_kv) {
-    case 8: return launch_attention_g<8, GTEN_F16>(t, n_seq);
-    case 4: return launch_attention_g<4, GTEN_F16>(t, n_seq);
-    case 2: return launch_attention_g<2, GTEN_F16>(t, n_seq);
-    default: return launch_attention_g<1, GTEN_F16>(t, n_seq);
+    case 8: return launch_attention_g<8, GTEN_F16>(t, n_seq, pfx);
+    case 4: return launch_attention_g<4, GTEN_F16>(t, n_seq, pfx);
+    case 2: return launch_attention_g<2, GTEN_F16>(t, n_seq, pfx);
+    default: return launch_attention_g<1, GTEN_F16>(t, n_seq, pfx);
     }
 }
 
@@ -1131,10 +1170,12 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
             t.hm_k = dc->hm + (size_t)lane * S * dc->hm_seq_stride + (size_t)l * 2 * dc->hm_cache_bytes;
             t.hm_seq_stride = dc->hm_seq_stride; t.hm_cache_bytes = dc->hm_cache_bytes;
         }
+        PfxArgs pfx;
+        if (dc->pfx_hm) { pfx.k = dc->pfx_hm + (size_t)l * 2 * dc->hm_cache_bytes; pfx.share = dc->share_dev + (size_t)lane * S; }
         const dim3 agrid(d.n_heads, dc->n_chunks, S);
         const size_t smem1 = (size_t)(16 + 3 * dh + 16) * 4 + 32 + (size_t)3 * dh + 64;
         if (!grouped_known) { grouped = attention_grouped_ok(t, S); grouped_known = true; }
-        if ((rc = grouped ? launch_attention_grouped(t, S) : launch_attention(t, agrid, smem1))) return rc;
+        if ((rc = grouped ? launch_attention_grouped(t, S, pfx) : launch_attention(t, agrid, smem1))) return rc;
         Gemv8Args sa = base;
         sa.d_in = E; sa.att_part = b.att_part; sa.d_head = dh; sa.d_head_shift = __builtin_ctz(dh); sa.n_chunks = dc->n_chunks;
         sa.att_stats = b.stats; sa.stats_stride = d.n_heads * dc->n_chunks * 2;
@@ -1587,7 +1628,8 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp};
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp,
+                    dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
     for (int g = 1; g < DEC_MAX_LANES; g++) {
@@ -1635,7 +1677,34 @@ static int run_step(gten_hip_decoder* dc, int use_graph);
 //      stream the steps follow on, so whatever ordered the rows' writers ahead of the steps orders them ahead of this.
 static void hm_mark_all(gten_hip_decoder* dc)
 {
-    std::fill(dc->hm_dirty.begin(), dc->hm_dirty.end(), (char)1);
+    for (char& f : dc->hm_dirty) f |= 2;               // ((re)started, not written: a sharing promise survives it, gten_hip_decoder_slot_share)
+}
+// sequence q is stepped at context length n next: a promise that reaches past its cached rows [0, n - 1) ends here (the step
+// appends row n - 1 to the sequence's own rows and shadow)
+static void share_at_start(gten_hip_decoder* dc, int q, int n)
+{
+    if (!dc->share_rows.empty() && dc->share_rows[(size_t)q] > n - 1) dc->share_rows[(size_t)q] = 0;
+}
+static void share_end(gten_hip_decoder* dc, int q)
+{
+    if (!dc->share_rows.empty()) dc->share_rows[(size_t)q] = 0;
+}
+// the captured graphs of a decoder (its next steps capture again)
+static hipError_t drop_graphs(gten_hip_decoder* dc)
+{
+    hipError_t first = hipSuccess;
+    auto rel = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
+    auto drop = [&](hipGraphExec_t& e, hipGraph_t& g) {
+        if (e) rel(hipGraphExecDestroy(e));
+        if (g) rel(hipGraphDestroy(g));
+        e = nullptr; g = nullptr;
+    };
+    drop(dc->exec, dc->graph); drop(dc->exec_k, dc->graph_k); drop(dc->s_exec, dc->s_graph); drop(dc->s_exec_k, dc->s_graph_k);
+    for (int m = 0; m < (1 << DEC_MAX_LANES); m++) {
+        drop(dc->exec_m[m], dc->graph_m[m]); drop(dc->exec_km[m], dc->graph_km[m]);
+        drop(dc->s_exec_m[m], dc->s_graph_m[m]); drop(dc->s_exec_km[m], dc->s_graph_km[m]);
+    }
+    return first;
 }
 static int pre_run(gten_hip_decoder* dc)
 {
@@ -1661,9 +1730,58 @@ static int pre_run(gten_hip_decoder* dc)
     if (!dc->hm) return 0;
     HmImportList items{};
     const size_t kv_pitch = gten_hip_row_bytes(d.adtype, (d.n_embd / d.n_heads) * d.n_kv_heads);
+    // 3. a decoder with a prefix shadow: the shared counts follow the promises (on the stream, ahead of the imports and the
+    //    steps), whoever loses chunks is imported in full, and the prefix shadow is (re)imported before anybody reads it --
+    //    after every sharing sequence was taken off it, since the counts above are written first
+    auto import_launch = [&](const HmImportList& it, const DecStep* step, const void* const* tab, uint8_t* base, const int* share) -> int {
+        const dim3 grid(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, it.n);
+        if (d.adtype == GTEN_Q8)
+            GTR_LAUNCH(KT_PACK, k_kv_import_hm_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 68, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
+                       d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
+        else
+            GTR_LAUNCH(KT_PACK, k_kv_import_hm_f16_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 33 * 4, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
+                       d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
+        return 0;
+    };
+    if (dc->pfx_hm) {
+        if (dc->pfx_dirty) {                           // somebody wrote into the prefix set's rows: nobody shares what the shadow holds
+            dc->pfx_dirty = 0;
+            dc->pfx_stale = true;
+            std::fill(dc->share_rows.begin(), dc->share_rows.end(), 0);
+        }
+        HmShareList sl{};
+        auto flush_sl = [&]() -> int {
+            if (sl.n == 0) return 0;
+            GTR_LAUNCH(KT_PACK, k_hm_share_set, dim3(1), dim3(64), 0, sl, dc->share_dev);
+            sl.n = 0;
+            return 0;
+        };
+        bool any = false;
+        for (int q = 0; q < dc->n_seq; q++) {
+            if (dc->share_rows[(size_t)q] && (dc->hm_dirty[(size_t)q] & 1)) dc->share_rows[(size_t)q] = 0;      // written since the promise
+            const int want = dc->pfx_len > 0 ? dc->share_rows[(size_t)q] / DEC_CHUNK : 0;
+            any = any || want > 0;
+            if (want == dc->share_cur[(size_t)q]) continue;
+            if (want < dc->share_cur[(size_t)q]) dc->hm_dirty[(size_t)q] |= 2;                              // its own shadow lacks those chunks
+            dc->share_cur[(size_t)q] = want;
+            sl.item[sl.n++] = (unsigned short)((unsigned)q | ((unsigned)want << 10));
+            if (sl.n == (int)(sizeof(sl.item) / sizeof(sl.item[0])))
+                if (int rc = flush_sl()) return rc;
+        }
+        if (int rc = flush_sl()) return rc;
+        if (any && dc->pfx_stale) {
+            HmImportList one{};
+            one.n = 1;
+            if (int rc = import_launch(one, dc->pfx_step, (const void* const*)dc->pfx_tab, dc->pfx_hm, nullptr)) return rc;
+            dc->pfx_stale = false;
+            dc->pfx_imports++;
+        }
+    }
     auto flush = [&]() -> int {
         if (items.n == 0) return 0;
-        if (d.adtype == GTEN_Q8)
+        if (dc->pfx_hm) {
+            if (int rc = import_launch(items, (const DecStep*)dc->step, (const void* const*)dc->kv_tab, dc->hm, dc->share_dev)) return rc;
+        } else if (d.adtype == GTEN_Q8)
             GTR_LAUNCH(KT_PACK, k_kv_import_hm, dim3(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, items.n), dim3(256), (size_t)DEC_CHUNK * 68, items,
                        (const DecStep*)dc->step, (const void* const*)dc->kv_tab, dc->hm, dc->hm_seq_stride, dc->hm_cache_bytes, d.n_layers, d.n_kv_heads,
                        dc->n_chunks, d.max_ctx, kv_pitch);
@@ -1680,6 +1798,7 @@ static int pre_run(gten_hip_decoder* dc)
         if (!dc->hm_dirty[(size_t)q]) continue;
         dc->hm_dirty[(size_t)q] = 0;
         items.seq[items.n++] = q;
+        if (dc->pfx_hm && dc->share_cur[(size_t)q] > 0) dc->hm_skip_imports++;
         if (items.n == (int)(sizeof(items.seq) / sizeof(items.seq[0])))
             if (int rc = flush()) return rc;
     }
@@ -1748,6 +1867,7 @@ int gten_hip_decoder_step(gten_hip_decoder* dc, int n, int use_graph)
     // The step's position lives on the device and the argmax kernel advances it,
     // so consecutive steps need no host-side update at all.  (All sequences of a
     // multi-sequence decoder are at the same position.)
+    for (int q = 0; q < dc->n_seq; q++) share_at_start(dc, q, n);
     if (dc->dev_n != n || !dc->dev_ns.empty()) {
         hm_mark_all(dc);                              // not the continuation of this decoder's own steps: the rows are the caller's
         std::vector<DecStep> st((size_t)dc->n_seq, DecStep{n, 1});
@@ -1768,6 +1888,7 @@ int gten_hip_decoder_steps(gten_hip_decoder* dc, int n_first, int count, int use
     GTR_REQUIRE(dc && count >= 0 && n_first >= 1 && n_first + count - 1 <= dc->d.max_ctx, "decoder_steps: steps [%d, %d) outside [1, %d]",
                 n_first, n_first + count, dc ? dc->d.max_ctx : 0);
     if (count == 0) return 0;
+    for (int q = 0; q < dc->n_seq; q++) share_at_start(dc, q, n_first);
     if (dc->dev_n != n_first || !dc->dev_ns.empty()) {
         hm_mark_all(dc);
         std::vector<DecStep> st((size_t)dc->n_seq, DecStep{n_first, 1});
@@ -1790,6 +1911,7 @@ int gten_hip_decoder_step_ragged(gten_hip_decoder* dc, const int* n_per_seq, int
     GTR_REQUIRE(dc && n_per_seq, "decoder_step_ragged: null argument");
     for (int q = 0; q < dc->n_seq; q++)
         GTR_REQUIRE(n_per_seq[q] >= 1 && n_per_seq[q] <= dc->d.max_ctx, "decoder_step_ragged: n[%d]=%d outside [1, %d]", q, n_per_seq[q], dc->d.max_ctx);
+    for (int q = 0; q < dc->n_seq; q++) share_at_start(dc, q, n_per_seq[q]);
     bool same = (int)dc->dev_ns.size() == dc->n_seq;
     for (int q = 0; same && q < dc->n_seq; q++) same = dc->dev_ns[q] == n_per_seq[q];
     if (!same) {
@@ -1862,6 +1984,7 @@ int gten_hip_decoder_generate_multi(gten_hip_decoder* dc, const int* n_first, co
         last[q] = std::min(ctx, n_first[q] + room - 1);
         live[q] = last[q] >= n_first[q];
         st[q] = DecStep{n_first[q], live[q] ? 3 : 0};
+        share_at_start(dc, q, n_first[q]);
         n_out[q] = 0;
         n_live += live[q];
     }
@@ -1926,6 +2049,7 @@ static int slots_view(gten_hip_decoder* dc)
         for (int q = 0; q < dc->n_seq; q++)
             if (int rc = slot_caches(dc, q, true)) return rc;
         hm_mark_all(dc);
+        std::fill(dc->share_rows.begin(), dc->share_rows.end(), 0);      // (parked: see gten_hip_decoder_slot_share)
     }
     dc->dev_n = -1;
     dc->dev_ns.clear();
@@ -1956,7 +2080,8 @@ int gten_hip_decoder_slot_start_until(gten_hip_decoder* dc, int seq, int n_first
     if (int rc = slots_view(dc)) return rc;
     if (int rc = slot_caches(dc, seq, false)) return rc;
     dc->slots[(size_t)seq] = DecStep{n_first, 3, n_last};
-    if (dc->hm) dc->hm_dirty[(size_t)seq] = 1;         // a (re)started sequence: its rows [0, n_first - 1) are the caller's
+    if (dc->hm) dc->hm_dirty[(size_t)seq] |= 2;        // a (re)started sequence: its rows [0, n_first - 1) are the caller's
+    share_at_start(dc, seq, n_first);
     GTR_CHECK(hipMemcpyAsync(dc->step + seq, &dc->slots[(size_t)seq], sizeof(DecStep), hipMemcpyHostToDevice, stream()));
     GTR_CHECK(hipStreamSynchronize(stream()));
     return 0;
@@ -1990,8 +2115,10 @@ int gten_hip_decoder_slots_apply(gten_hip_decoder* dc, int count, const int* seq
     for (int i = 0; i < count; i++) {
         const int q = seqs[i];
         const bool park = n_first[i] == 0;
+        if (park) { if (dc->slots[(size_t)q].advance & 1) share_end(dc, q); }          // (a started slot is parked: its mark ends)
+        else share_at_start(dc, q, n_first[i]);
         dc->slots[(size_t)q] = park ? DecStep{1, 0, 0} : DecStep{n_first[i], 3, n_last[i]};
-        if (dc->hm && !park) dc->hm_dirty[(size_t)q] = 1;
+        if (dc->hm && !park) dc->hm_dirty[(size_t)q] |= 2;
         if (!dc->kv_parked.empty() && (bool)dc->kv_parked[(size_t)q] != park) {
             const void** row = rows.data() + (size_t)i * L * 2;            // (alive until the wait below)
             for (size_t l = 0; l < L; l++) {
@@ -2017,6 +2144,7 @@ int gten_hip_decoder_slot_park(gten_hip_decoder* dc, int seq)
     if (int rc = slots_view(dc)) return rc;
     if (int rc = slot_caches(dc, seq, true)) return rc;
     DecStep& s = dc->slots[(size_t)seq];
+    if (s.advance & 1) share_end(dc, seq);             // (a started slot is parked: its mark ends)
     s.n = 1;
     s.advance = 0;
     s.stop = 0;
@@ -2047,6 +2175,7 @@ int gten_hip_decoder_slot_bind(gten_hip_decoder* dc, int seq, const gten_hip_kv_
         kv_watch_remove(dc, flag);
         for (size_t i = 0; i < (size_t)dc->d.n_layers * 2; i++) kv_watch_add(dc->kv_real[off + i], cache_bytes, dc, flag);
         *flag = 1;
+        share_end(dc, seq);                            // (other rows: whatever was promised about the old ones is over)
     }
     return 0;
 }
@@ -2149,6 +2278,7 @@ int gten_hip_decoder_time_family(gten_hip_decoder* dc, int family, int n, int re
     dc->dev_n = -1;
     dc->dev_ns.clear();
     hm_mark_all(dc);
+    for (int q = 0; q < dc->n_seq; q++) share_at_start(dc, q, n);
     if (int rc_ = pre_run(dc)) return rc_;
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
@@ -2244,6 +2374,95 @@ int gten_hip_decoder_kv_info(gten_hip_decoder* dc, int* head_major, unsigned lon
     if (head_major) *head_major = dc->hm ? 1 : 0;
     if (seq_imports) *seq_imports = dc->hm_imports;
     if (import_launches) *import_launches = dc->hm_import_launches;
+    return 0;
+}
+
+/* ---- decode slots that share a prefix read ONE copy of its K / V (include/gten_hip_prefix_decode.h) */
+int gten_hip_set_prefix_decode_shared(int on)
+{
+    g_pfx_shared = on < 0 ? PFX_SHARED_DEFAULT : on != 0;
+    return 0;
+}
+
+int gten_hip_decoder_prefix_set(gten_hip_decoder* dc, const gten_hip_kv_ptrs* kv, int prefix_len)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && prefix_len >= 0, "decoder_prefix_set: bad arguments");
+    if (!dc->hm) return 0;                             // no shadows (<= 8 sequences, exact forms, set_kv_head_major(0)): nothing to share
+    const gten_hip_decoder_desc& d = dc->d;
+    if (kv && prefix_len > 0) {
+        GTR_REQUIRE(prefix_len <= d.max_ctx, "decoder_prefix_set: prefix of %d rows, context %d", prefix_len, d.max_ctx);
+        for (int l = 0; l < d.n_layers; l++) GTR_REQUIRE(kv[l].kcache && kv[l].vcache, "decoder_prefix_set: null cache pointer (layer %d)", l);
+    }
+    // every sequence comes off the shadow first: the next pre_run zeroes its count and imports its own rows in full, ahead of
+    // any import of the prefix shadow
+    std::fill(dc->share_rows.begin(), dc->share_rows.end(), 0);
+    kv_watch_remove(dc, &dc->pfx_dirty);
+    dc->pfx_dirty = 0;
+    dc->pfx_len = 0;
+    dc->pfx_kv.clear();
+    if (!kv || prefix_len == 0) return 0;
+    // (k_hm_share_set's entries are sequence | chunks << 10 in 16 bits)
+    GTR_REQUIRE(dc->n_seq <= 1024 && dc->n_chunks < 64, "decoder_prefix_set: %d sequences (at most 1024) x %d chunks (at most 63)", dc->n_seq, dc->n_chunks);
+    const size_t L2 = (size_t)d.n_layers * 2;
+    if (!dc->pfx_hm) {
+        // first use: the prefix shadow, the shared counts -- and the step's attention becomes the _pfx instantiation, so the graphs
+        // captured so far go
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        GTR_CHECK(drop_graphs(dc));
+        GTR_CHECK(hipMalloc((void**)&dc->share_dev, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMemset(dc->share_dev, 0, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMalloc((void**)&dc->pfx_tab, L2 * sizeof(void*)));
+        GTR_CHECK(hipMalloc((void**)&dc->pfx_step, sizeof(DecStep)));
+        dc->share_rows.assign((size_t)dc->n_seq, 0);
+        dc->share_cur.assign((size_t)dc->n_seq, 0);
+        GTR_CHECK(hipMalloc((void**)&dc->pfx_hm, dc->hm_seq_stride));
+        GTR_CHECK(hipMemset(dc->pfx_hm, 0, dc->hm_seq_stride));
+    }
+    for (int l = 0; l < d.n_layers; l++) { dc->pfx_kv.push_back(kv[l].kcache); dc->pfx_kv.push_back(kv[l].vcache); }
+    const DecStep st{prefix_len + 1, 0, 0};
+    GTR_CHECK(hipMemcpyAsync(dc->pfx_tab, dc->pfx_kv.data(), L2 * sizeof(void*), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(dc->pfx_step, &st, sizeof(DecStep), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));         // (`st` lives on this stack frame)
+    const size_t cache_bytes = (size_t)d.max_ctx * gten_hip_row_bytes(d.adtype, (d.n_embd / d.n_heads) * d.n_kv_heads);
+    for (const void* c : dc->pfx_kv) kv_watch_add(c, cache_bytes, dc, &dc->pfx_dirty);
+    dc->pfx_len = prefix_len;
+    dc->pfx_stale = true;
+    return 0;
+}
+
+int gten_hip_decoder_slot_share(gten_hip_decoder* dc, int seq, int rows)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_slot_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
+    if (!dc->hm) return 0;
+    if (rows == 0) { share_end(dc, seq); return 0; }
+    GTR_REQUIRE(dc->pfx_len > 0 && rows <= dc->pfx_len, "decoder_slot_share: %d rows, the prefix has %d", rows, dc->pfx_len);
+    // the sequence's next step, where the decoder knows it: a started slot, or -- outside the slot view -- a sequence that was
+    // stepped and whose rows nobody wrote since
+    int n_next = 0;
+    if (!dc->slots.empty()) { if (dc->slots[(size_t)seq].advance & 1) n_next = dc->slots[(size_t)seq].n; }
+    else if (!dc->hm_dirty[(size_t)seq]) n_next = !dc->dev_ns.empty() ? dc->dev_ns[(size_t)seq] : std::max(dc->dev_n, 0);
+    GTR_REQUIRE(n_next == 0 || rows <= n_next - 1, "decoder_slot_share: %d rows, sequence %d is at position %d", rows, seq, n_next - 1);
+    if (!g_pfx_shared) return 0;                       // (switched off: nothing is recorded)
+    dc->share_rows[(size_t)seq] = rows;
+    if (dc->hm_dirty[(size_t)seq]) dc->hm_dirty[(size_t)seq] = 2;       // what was written BEFORE the promise is what it speaks about
+    return 0;
+}
+
+int gten_hip_decoder_prefix_info(gten_hip_decoder* dc, int seq, int* prefix_len, int* seq_chunks, unsigned long long* prefix_imports,
+                                 unsigned long long* imports_skipping)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_prefix_info: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    // (the chunks a step enqueued NOW would read from the prefix shadow: the promise as pre_run would take it)
+    int chunks = 0;
+    if (dc->pfx_hm && dc->pfx_len > 0 && !dc->pfx_dirty && dc->share_rows[(size_t)seq] && !(dc->hm_dirty[(size_t)seq] & 1))
+        chunks = dc->share_rows[(size_t)seq] / DEC_CHUNK;
+    if (prefix_len) *prefix_len = dc->pfx_len;
+    if (seq_chunks) *seq_chunks = chunks;
+    if (prefix_imports) *prefix_imports = dc->pfx_imports;
+    if (imports_skipping) *imports_skipping = dc->hm_skip_imports;
     return 0;
 }
 

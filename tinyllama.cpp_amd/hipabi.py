@@ -100,6 +100,8 @@ class GtenHip:
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
+    PREFIX_DECODE_SYMBOLS = ["gten_hip_decoder_prefix_set", "gten_hip_decoder_slot_share", "gten_hip_decoder_prefix_info",
+                             "gten_hip_set_prefix_decode_shared"]          # include/gten_hip_prefix_decode.h
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -137,6 +139,7 @@ class GtenHip:
         self._block_rows = _sig(L, "gten_hip_block_rows", ci, [C.POINTER(BlockDesc), ci, ci])
         self._block_rows_prefixed = _sig(L, "gten_hip_block_rows_prefixed", ci, [C.POINTER(BlockDesc), ci, vp, vp, ci])
         self._set_block_rows = _sig(L, "gten_hip_set_block_rows", ci, [ci])
+        self._prefix_decode_shared = _sig(L, "gten_hip_set_prefix_decode_shared", ci, [ci])
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
         self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
         self._decode_persistent = _sig(L, "gten_hip_set_decode_persistent", ci, [ci])
@@ -246,6 +249,10 @@ class GtenHip:
         """decoders created from now on: the single-sequence attention as k_dec_attn_one64 (the A/B control) or, by default,
         k_dec_attn_one64v -- the same bytes (include/gten_hip_ab.h)"""
         self._check(self._decode_attn_classic(1 if on else 0))
+
+    def set_prefix_decode_shared(self, on):
+        """decode slots behind a shared prefix read ONE copy of its K / V (default) or each its own (include/gten_hip_prefix_decode.h)"""
+        self._check(self._prefix_decode_shared(-1 if on is None else 1 if on else 0))    # (None: the default again)
 
     def set_kv_head_major(self, on):
         """decoders of 16+ sequences created from now on: head-major shadows of the K / V caches (default) or the cache rows as they lie"""

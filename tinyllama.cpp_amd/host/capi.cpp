@@ -388,6 +388,7 @@ int gten_host_batch_seq_steps(gten_host_batch* b, int seq, const int32_t* tokens
         n_first + steps - 1 > count)
         return -1;
     TinyLlama& m = b->batch->seq(seq);                 // the sequence's own model object: its single-sequence decoder on the SAME caches
+    b->batch->forget_share(seq);                       // (its rows are rewritten: whatever they were marked to share is over)
     m.decode_set_tokens(tokens, 0, count);
     m.decode_steps(n_first, steps, true);
     return 0;

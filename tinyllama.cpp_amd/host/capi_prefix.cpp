@@ -1,8 +1,11 @@
-// capi_prefix.cpp -- flat C exports of the shared prompt prefix (include/gten_host_prefix.h).  Kept apart from capi.cpp: this
-// is the only translation unit that refers to the prefixed device entry point (include/gten_hip_prefix.h); it hands it to
-// the headers' hook (gten/modules.h, detail::prefixed_rows) when the library is loaded.
+// capi_prefix.cpp -- flat C exports of the shared prompt prefix (include/gten_host_prefix.h, include/gten_host_prefix_decode.h).
+// Kept apart from capi.cpp: this is the only translation unit that refers to the prefixed device entry points
+// (include/gten_hip_prefix.h, include/gten_hip_prefix_decode.h); it hands them to the headers' hooks (gten/modules.h,
+// detail::prefixed_rows; host/tinyllama_model.h, detail::prefix_decode) when the library is loaded.
 #include "../../include/gten_host_prefix.h"
+#include "../../include/gten_host_prefix_decode.h"
 #include "../../include/gten_hip_prefix.h"
+#include "../../include/gten_hip_prefix_decode.h"
 
 #include "capi_handles.h"
 
@@ -12,6 +15,9 @@ namespace {
 
 const bool installed = [] {
     detail::prefixed_rows().call = gten_hip_block_rows_prefixed;
+    detail::prefix_decode().prefix_set = gten_hip_decoder_prefix_set;
+    detail::prefix_decode().slot_share = gten_hip_decoder_slot_share;
+    detail::prefix_decode().info = gten_hip_decoder_prefix_info;
     return true;
 }();
 
@@ -33,5 +39,21 @@ int gten_host_batch_prefix_info(gten_host_batch* b, int* n_prefix, unsigned long
     if (rows_computed) *rows_computed = b->batch->rows_computed();
     return 0;
 }
+
+int gten_host_batch_prefix_decode_info(gten_host_batch* b, int seq, int* n_prefix, int* seq_chunks, unsigned long long* prefix_imports,
+                                       unsigned long long* imports_skipping)
+{
+    if (!b || seq < 0 || seq >= b->batch->n_seq()) return -1;
+    b->batch->prefix_decode_info(seq, n_prefix, seq_chunks, prefix_imports, imports_skipping);
+    return 0;
+}
+
+int gten_host_batch_prefix_decode_share(gten_host_batch* b, int seq, int rows)
+{
+    if (!b || seq < 0 || seq >= b->batch->n_seq() || rows < 0) return -1;
+    return b->batch->slot_share_rc(seq, rows);
+}
+
+int gten_host_set_prefix_decode_shared(int on) { return gten_hip_set_prefix_decode_shared(on); }
 
 } // extern "C"

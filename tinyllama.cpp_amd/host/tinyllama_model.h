@@ -595,6 +595,24 @@ public:
 // gten/tensor.h:24-29), so the weights exist once in HBM.  Prefill goes through each object's
 // operator path; single-token steps of all sequences go through one multi-sequence decoder that
 // streams every weight once per step.
+namespace detail {
+// The shared decoder's prefix entry points (include/gten_hip_prefix_decode.h): decode slots whose caches begin with the shared
+// prefix's rows read ONE copy of them.  host/capi_prefix.cpp installs them when the library is loaded -- this header and
+// host/capi.cpp name no such symbol, so they go on linking against the test stand-in of include/gten_hip.h alone; without
+// them every sequence decodes on its own copy, as before.
+struct PrefixDecode {
+    int (*prefix_set)(gten_hip_decoder* dec, const gten_hip_kv_ptrs* kv, int prefix_len) = nullptr;
+    int (*slot_share)(gten_hip_decoder* dec, int seq, int rows) = nullptr;
+    int (*info)(gten_hip_decoder* dec, int seq, int* prefix_len, int* seq_chunks, unsigned long long* prefix_imports,
+                unsigned long long* imports_skipping) = nullptr;
+};
+inline PrefixDecode& prefix_decode()
+{
+    static PrefixDecode p;
+    return p;
+}
+} // namespace detail
+
 class TinyLlamaBatch {
 public:
     TinyLlamaBatch(int n_seq, int n_ctx, ModuleDtype dtype, TinyLLamaParams p = TinyLLamaParams{}) : n_ctx_{n_ctx}, dtype_{dtype}, params_{p}
@@ -642,6 +660,7 @@ public:
         if (dec_) { GTEN_HIP_OK(gten_hip_decoder_destroy(dec_)); dec_ = nullptr; }
         spares_.clear();                                     // (... and so do the spare cache sets)
         set_kv_.clear();
+        set_share_.clear();
     }
     void load_synthetic(uint64_t seed)
     {
@@ -704,7 +723,7 @@ public:
     // 0; -1: bad arguments (16 <= n, n + 17 <= context); -2: this batch does not process prompts as segments
     int set_prefix(const int32_t* tokens, int n)
     {
-        if (n == 0) { prefix_ids_.clear(); return 0; }
+        if (n == 0) { prefix_ids_.clear(); decoder_prefix(false); return 0; }
         if (!tokens || n < 16 || n + 17 > n_ctx_ || n > kPreRows) return -1;
         if (!batched_prompts() || !detail::prefixed_rows().call) return -2;
         ensure_pre();
@@ -713,6 +732,9 @@ public:
             for (int w = 0; w < seqs_[0]->n_weights(); w++) prefix_set_->weight(w) = seqs_[0]->weight(w);
         }
         prefix_ids_.clear();                                   // (nothing shares a half-written set)
+        // ... and no decode slot goes on reading the shadow of rows that are about to be replaced: every sharing sequence is
+        // back on its own copy before the set is overwritten (the same set is reused in place)
+        decoder_prefix(false);
         std::vector<int32_t> ids(tokens, tokens + n);
         Tensor tk(ids.data(), {n}, kInt32);
         (void)pre_->hidden_rows(tk, {0, n});
@@ -726,8 +748,33 @@ public:
         }
         GTEN_HIP_OK(gten_hip_sync());                          // (the set is read from either stream afterwards)
         prefix_ids_ = std::move(ids);
+        // the decode side: the shared decoder exists from here on, so that every mark made below reaches it at once and whatever
+        // writes a marked set's rows afterwards is seen by its watch
+        ensure_decoder();
+        decoder_prefix(true);
         return 0;
     }
+    // the shared decoder's view (gten_hip_decoder_prefix_info): prefix length it holds, chunks sequence seq_i reads from the
+    // prefix shadow, imports of that shadow, sequence imports that skipped shared chunks.  All 0 where nothing is installed.
+    void prefix_decode_info(int seq_i, int* n_prefix, int* seq_chunks, unsigned long long* prefix_imports, unsigned long long* imports_skipping)
+    {
+        if (n_prefix) *n_prefix = 0;
+        if (seq_chunks) *seq_chunks = 0;
+        if (prefix_imports) *prefix_imports = 0;
+        if (imports_skipping) *imports_skipping = 0;
+        if (!detail::prefix_decode().info) return;
+        ensure_decoder();
+        GTEN_HIP_OK(detail::prefix_decode().info(dec_, seq_i, n_prefix, seq_chunks, prefix_imports, imports_skipping));
+    }
+    // gten_hip_decoder_slot_share on the shared decoder, return code and all (tests: the refusals)
+    int slot_share_rc(int seq_i, int rows)
+    {
+        if (!detail::prefix_decode().slot_share) return 0;
+        ensure_decoder();
+        return detail::prefix_decode().slot_share(dec_, seq_i, rows);
+    }
+    // cache set c's rows were written by somebody else than a prompt of this class (gten_host_batch_seq_steps): its mark goes
+    void forget_share(int c) { if (c >= 0 && c < (int)set_share_.size()) set_share_[(size_t)c] = 0; }
     int prefix_len() const { return (int)prefix_ids_.size(); }
     unsigned long long prompts_shared() const { return prompts_shared_; }
     unsigned long long rows_computed() const { return rows_computed_; }
@@ -790,6 +837,16 @@ private:
             }
             flush();
         }
+        // "SHARES P ROWS": a set that just received a copy of the prefix rows carries the mark until another prompt is written
+        // onto it; outside serve() set c is what sequence c decodes on, and the decoder hears of it now (after the copies above
+        // were announced: a later write into the set ends the promise on the decoder's side).  Inside serve() the mark travels
+        // with the set and becomes gten_hip_decoder_slot_share when a slot is started on it.
+        for (size_t i = 0; i < idx.size(); i++) {
+            const int c = slots[(size_t)idx[i]];
+            share_mark(c) = P;
+            if (P > 0 && !in_serve_ && c < n_seq() && dec_ && detail::prefix_decode().slot_share)
+                (void)detail::prefix_decode().slot_share(dec_, c, P);     // (refused -- the sequence is mid-run at a position inside the prefix --: it decodes on its own copy)
+        }
         for (size_t i = 0; i < idx.size(); i++) {
             const int k = idx[i];
             const Tensor lg = pre_->logits_of_row(hidden, starts[i + 1] - 1);
@@ -809,6 +866,7 @@ public:
             prefill_many({seq_i}, {&prompt}, &first, &lo);
             return first[0];
         }
+        share_mark(seq_i) = 0;
         Tensor tk(prompt.data(), {(int)prompt.size()}, kInt32);
         const Tensor lg = cset(seq_i).logits(tk, 0);                 // operator path on this cache set's own model object
         const float* p = lg.data_ptr<float>();
@@ -833,6 +891,7 @@ public:
             prefill_many_with({seq_i}, {&prompt}, &first, &lo, pick);
             return first[0];
         }
+        share_mark(seq_i) = 0;
         Tensor tk(prompt.data(), {(int)prompt.size()}, kInt32);
         const Tensor lg = cset(seq_i).logits(tk, 0);
         Tensor id({1}, kInt32);
@@ -1014,6 +1073,17 @@ public:
         // Whatever way this function is left (a failed check ends the process, but an allocation may throw), every slot goes back
         // to its own sequence's caches: a decoder left bound to spare or foreign sets would read and write the wrong rows in the
         // decode_step / generate that follows -- and dangle once share_weights() drops the spares.
+        // (while the queue runs, cache sets are bound to slots by the scheduler and carry their "shares P rows" marks with them; the
+        //  slots go back to their own sets afterwards, so no mark outlives the queue -- however this function is left)
+        struct ServeMarks {
+            TinyLlamaBatch* b;
+            explicit ServeMarks(TinyLlamaBatch* b_) : b{b_} { b->in_serve_ = true; }
+            ~ServeMarks()
+            {
+                b->in_serve_ = false;
+                std::fill(b->set_share_.begin(), b->set_share_.end(), 0);
+            }
+        } serve_marks{this};
         struct Rebind {
             TinyLlamaBatch* b; int S; bool done = false;
             void run()
@@ -1163,6 +1233,10 @@ public:
             }
             if (!ap_seq.empty())
                 GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), ap_tok.data()));
+            // the joining slots whose sets begin with the shared prefix's rows read them from the decoder's one copy
+            if (detail::prefix_decode().slot_share)
+                for (const int q : ap_seq)
+                    if (const int P = share_mark(set_of[(size_t)q]); P > 0) (void)detail::prefix_decode().slot_share(dec_, q, P);     // (refused: the slot decodes on its own copy, as in prefill_group)
             if (n_live == 0) return;
             // (a slot whose run ends inside the slice repeats its last step until the slice is over, slot_start_until: the slice
             //  is cut only when EVERY live slot ends earlier)
@@ -1277,6 +1351,28 @@ private:
     int serve_schedule_ = 0;
     int serve_spares_ = -1;
     int serve_ramp_ = 100;
+    std::vector<int> set_share_;             // per cache set: its rows [0, P) are a copy of the prefix set's (0: no such mark)
+    bool in_serve_ = false;                  // serve() is running: sets are bound to slots by the scheduler
+
+    int& share_mark(int c)
+    {
+        if ((int)set_share_.size() < n_sets()) set_share_.resize((size_t)n_sets(), 0);
+        return set_share_[(size_t)c];
+    }
+    // the prefix set's caches to the shared decoder (on) or "no prefix" (off): either way every slot is taken off the shared
+    // copy first and every mark is void -- they spoke of the previous prefix
+    void decoder_prefix(bool on)
+    {
+        std::fill(set_share_.begin(), set_share_.end(), 0);
+        if (!dec_ || !detail::prefix_decode().prefix_set) return;
+        if (!on || prefix_ids_.empty() || !prefix_set_) { GTEN_HIP_OK(detail::prefix_decode().prefix_set(dec_, nullptr, 0)); return; }
+        gten_hip_decoder_desc di;
+        std::vector<gten_hip_layer_ptrs> Li;
+        prefix_set_->describe(&di, &Li);
+        std::vector<gten_hip_kv_ptrs> kv;
+        for (auto& p : Li) kv.push_back(gten_hip_kv_ptrs{p.kcache, p.vcache});
+        GTEN_HIP_OK(detail::prefix_decode().prefix_set(dec_, kv.data(), (int)prefix_ids_.size()));
+    }
 
     const gten_hip_kv_ptrs* set_kv(int c)
     {
@@ -1304,6 +1400,7 @@ private:
             for (auto& p : Li) kv.push_back(gten_hip_kv_ptrs{p.kcache, p.vcache});
         }
         GTEN_HIP_OK(gten_hip_decoder_create_multi(&d, L.data(), kv.data(), (int)seqs_.size(), &dec_));
+        decoder_prefix(true);                                  // (a prefix set before the decoder existed)
     }
 };
 

@@ -46,6 +46,8 @@ class GtenHost:
     SAMPLE_SYMBOLS = ["gten_host_model_generate_topk", "gten_host_batch_generate_topk", "gten_host_batch_serve_topk"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
+    PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
+                             "gten_host_set_prefix_decode_shared"]                                          # include/gten_host_prefix_decode.h
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -105,6 +107,10 @@ class GtenHost:
         self._bkvinfo = _sig(L, "gten_host_batch_kv_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self._bsetprefix = _sig(L, "gten_host_batch_set_prefix", ci, [vp, vp, ci])
         self._bprefixinfo = _sig(L, "gten_host_batch_prefix_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
+        self._bpdinfo = _sig(L, "gten_host_batch_prefix_decode_info", ci,
+                             [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
+        self._bpdshare = _sig(L, "gten_host_batch_prefix_decode_share", ci, [vp, ci, ci])
+        self._pdshared = _sig(L, "gten_host_set_prefix_decode_shared", ci, [ci])
         self._synthw = _sig(L, "gten_host_synth_weight", ci, [cfgp, C.c_uint64, ci, vp, sz])
         self._writeg = _sig(L, "gten_host_write_gten", ci, [cfgp, C.c_uint64, C.c_char_p])
         self._stoks = _sig(L, "gten_host_synthetic_tokens", None, [vp, ci, C.c_uint32, ci])
@@ -126,6 +132,12 @@ class GtenHost:
         rc = self._writeg(C.byref(cfg), seed, path.encode())
         if rc:
             raise GtenHipError(f"gten_host_write_gten rc={rc}")
+
+    def set_prefix_decode_shared(self, on):
+        """process-wide: decode slots behind a shared prefix read one copy of its K / V (default) or each its own"""
+        rc = self._pdshared(-1 if on is None else 1 if on else 0)    # (None: the default again)
+        if rc:
+            raise GtenHipError(f"gten_host_set_prefix_decode_shared rc={rc}")
 
     def synthetic_tokens(self, count, seed=12345, n_vocab=32003):
         out = np.zeros(count, np.int32)
@@ -500,6 +512,17 @@ class HostBatch:
         n, sh, rows = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
         self._ck(self.host._bprefixinfo(self.h, C.byref(n), C.byref(sh), C.byref(rows)), "batch_prefix_info")
         return n.value, sh.value, rows.value
+
+    def prefix_decode_info(self, seq=0):
+        """the shared decoder's side of the prefix (include/gten_host_prefix_decode.h): (prefix length it holds, leading chunks of 256
+        positions sequence `seq` reads from the ONE copy, imports of that copy so far, sequence imports that skipped shared chunks)"""
+        n, ch, pi, sk = C.c_int(0), C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._ck(self.host._bpdinfo(self.h, seq, C.byref(n), C.byref(ch), C.byref(pi), C.byref(sk)), "batch_prefix_decode_info")
+        return n.value, ch.value, pi.value, sk.value
+
+    def prefix_decode_share_rc(self, seq, rows):
+        """gten_hip_decoder_slot_share(seq, rows) on the shared decoder: 0, or the refusal's code"""
+        return self.host._bpdshare(self.h, seq, rows)
 
     def decode_result(self, seq, n):
         out = C.c_int32(-1)

@@ -13,6 +13,13 @@ Without --step this is a driver: it runs the steps below one after the other, ea
                    their own, budgets of 32..224 new ids: served with the prefix unset and set, three times each in
                    alternation: new tok/s, prefill_s, rows computed; the ids of both ways compared.
                    On a build without the feature (the parent commit) only the unset runs are made: the baseline.
+  --step decode    the DECODE side (decode slots behind the prefix read one copy of its K / V, include/gten_hip_prefix_decode.h):
+                   full-size synthetic q4, 256 slots, a 1024-id prefix plus 64..256 ids of their own, the prefix set both ways and
+                   gten_hip_set_prefix_decode_shared off / on, three times each in alternation: (a) the attention family's launch
+                   time (gten_hip_decoder_time_family at the longest context), (b) ms per shared ragged step.
+  --step serve_decode   (c) the serving queue of --step serve behind the 1024-id prefix, the switch off / on, three runs each in
+                   alternation: new tok/s, and the ids of both ways compared.
+  (--decode: the driver runs these two instead of kernels and serve; results go to profiles/prefix_decode_cost.json)
 """
 import argparse
 import json
@@ -28,14 +35,15 @@ sys.path.insert(0, ROOT)
 from __graft_entry__ import load_package  # noqa: E402
 
 PREFIX, SLOTS, QUEUE, CTX, REPS = 256, 256, 1024, 2048, 3
-STEP_LIMIT_S = {"kernels": 240, "serve": 600}
+STEP_LIMIT_S = {"kernels": 240, "serve": 600, "decode": 420, "serve_decode": 600}
+DEC_PREFIX = 1024
 
 
-def queue(host, cfg):
+def queue(host, cfg, n_prefix=PREFIX):
     rng = np.random.default_rng(2025)
     own = rng.integers(64, 257, QUEUE)
     budgets = rng.integers(32, 225, QUEUE).astype(np.int32)
-    prefix = [int(t) for t in host.synthetic_tokens(PREFIX, seed=424242, n_vocab=cfg.n_vocab)]
+    prefix = [int(t) for t in host.synthetic_tokens(n_prefix, seed=424242, n_vocab=cfg.n_vocab)]
     prompts = [prefix + [int(t) for t in host.synthetic_tokens(int(n), seed=9000 + j, n_vocab=cfg.n_vocab)] for j, n in enumerate(own)]
     return prefix, prompts, budgets
 
@@ -80,6 +88,92 @@ def step_serve():
         r = [x for x in res["runs"] if x["prefix"] == mode]
         res[mode] = {"new_tok_s_median": float(np.median([x["new_tok_s"] for x in r])), "new_tok_s_min_max": [min(x["new_tok_s"] for x in r), max(x["new_tok_s"] for x in r)],
                      "prefill_s_median": float(np.median([x["prefill_s"] for x in r])), "rows_computed": r[0].get("rows_computed")}
+    b.close()
+    return res
+
+
+def spread(values):
+    return {"median": round(float(np.median(values)), 4), "min_max": [round(float(min(values)), 4), round(float(max(values)), 4)]}
+
+
+def full_size_batch():
+    pkg = load_package()
+    hip = pkg.hipabi.load(0)
+    host = pkg.load_host()
+    cfg = host.default_config(4, 3)
+    cfg.max_ctx = CTX
+    b = host.batch(cfg, SLOTS)
+    b.load_synthetic(4242)
+    return hip, host, cfg, b
+
+
+def step_decode():
+    hip, host, cfg, b = full_size_batch()
+    prefix, prompts, _ = queue(host, cfg, DEC_PREFIX)
+    prompts = prompts[:SLOTS]
+    steps = 32
+    streams = [p + [int(t) for t in host.synthetic_tokens(steps + 8, seed=7000 + q, n_vocab=cfg.n_vocab)] for q, p in enumerate(prompts)]
+    fam = hip.prof_family_index("decode_attn_score")
+    n_long = max(len(p) for p in prompts) + 1
+    b.set_prefix(prefix)
+    res = {"slots": SLOTS, "prefix_ids": DEC_PREFIX, "own_ids": "64..256", "steps_timed": steps, "attention_family_context": n_long, "runs": []}
+    last = {}
+    for rep in range(REPS + 1):                                            # (rep 0: warm-up -- graphs, first-use allocations)
+        for mode in ("off", "on"):
+            host.set_prefix_decode_shared(mode == "on")
+            for i in range(0, SLOTS, 3):                                   # (a call takes 4096 ids: three prompts of at most 1280)
+                b.prefill_many(list(range(i, min(i + 3, SLOTS))), prompts[i:i + 3], want=False)
+            for q, s_ in enumerate(streams):
+                b.decode_begin(q, s_)
+            sharing = sum(1 for q in range(SLOTS) if b.prefix_decode_info(q)[1] > 0)
+            for t in (1, 2):                                               # (imports, graph capture)
+                b.decode_step_ragged([len(p) + t for p in prompts], use_graph=True)
+            hip.sync()
+            t0 = time.perf_counter()
+            for t in range(3, 3 + steps):
+                b.decode_step_ragged([len(p) + t for p in prompts], use_graph=True)
+            hip.sync()
+            ms = 1e3 * (time.perf_counter() - t0) / steps
+            last[mode] = np.stack([b.logits(q) for q in (0, 1, SLOTS // 2, SLOTS - 1)])
+            us, launches = b.time_family(fam, n_long, 20)
+            if rep:
+                res["runs"].append({"shared": mode, "rep": rep, "ms_per_step": round(ms, 4), "attn_launch_us": round(us, 2),
+                                    "attn_launches_per_step": launches, "sequences_sharing": sharing})
+    host.set_prefix_decode_shared(None)
+    res["same_logits_on_and_off"] = bool(np.array_equal(last["off"], last["on"]))
+    for mode in ("off", "on"):
+        r = [x for x in res["runs"] if x["shared"] == mode]
+        res[mode] = {"ms_per_step": spread([x["ms_per_step"] for x in r]), "attn_launch_us": spread([x["attn_launch_us"] for x in r]),
+                     "sequences_sharing": r[0]["sequences_sharing"]}
+    b.close()
+    return res
+
+
+def step_serve_decode():
+    hip, host, cfg, b = full_size_batch()
+    prefix, prompts, budgets = queue(host, cfg, DEC_PREFIX)
+    b.set_prefix(prefix)
+    res = {"slots": SLOTS, "prompts": QUEUE, "prefix_ids": DEC_PREFIX, "own_ids": "64..256", "runs": []}
+    for mode in ("off", "on"):                                             # warm-up
+        host.set_prefix_decode_shared(mode == "on")
+        b.serve(prompts[:SLOTS], CTX, -1, 8, max_new=4)
+    ids = {}
+    for rep in range(REPS):
+        for mode in ("off", "on"):
+            host.set_prefix_decode_shared(mode == "on")
+            skip0 = b.prefix_decode_info()[3]
+            t0 = time.perf_counter()
+            got, st = b.serve(prompts, CTX, -1, 8, max_new_each=budgets)
+            wall = time.perf_counter() - t0
+            res["runs"].append({"shared": mode, "rep": rep, "new_tok_s": round(st["new_tokens"] / wall, 1), "wall_s": round(wall, 4),
+                                "prefill_s": round(st["prefill_s"], 4), "decode_s": round(st["decode_s"], 4), "new_tokens": int(st["new_tokens"]),
+                                "imports_skipping_shared_chunks": int(b.prefix_decode_info()[3] - skip0)})
+            ids.setdefault(mode, got)
+    host.set_prefix_decode_shared(None)
+    res["same_ids_on_and_off"] = bool(all(np.array_equal(x, y) for x, y in zip(ids["off"], ids["on"])))
+    for mode in ("off", "on"):
+        r = [x["new_tok_s"] for x in res["runs"] if x["shared"] == mode]
+        res[mode] = {"new_tok_s": spread(r)}
     b.close()
     return res
 
@@ -173,14 +267,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", choices=sorted(STEP_LIMIT_S), default=None)
+    ap.add_argument("--decode", action="store_true", help="the decode side: steps decode and serve_decode")
     ap.add_argument("--merge", nargs="*", default=[], help="name=file.json: results measured elsewhere (the parent commit's runs) recorded beside these")
     a = ap.parse_args()
     if a.step:
-        res = {"serve": step_serve, "kernels": step_kernels}[a.step]()
+        res = {"serve": step_serve, "kernels": step_kernels, "decode": step_decode, "serve_decode": step_serve_decode}[a.step]()
         print(json.dumps(res))
         return 0
     res = {"what": "shared prompt prefix, TinyLlama-1.1B q4 synthetic, %d slots, %d prompts = %d shared ids + 64..256 of their own" % (SLOTS, QUEUE, PREFIX)}
-    for step in ("kernels", "serve"):
+    if a.decode:
+        res["what"] = "decode slots behind a shared prefix read one copy of its K / V, TinyLlama-1.1B q4 synthetic, %d slots, %d shared ids + 64..256 of their own" % (SLOTS, DEC_PREFIX)
+    for step in (("decode", "serve_decode") if a.decode else ("kernels", "serve")):
         p = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step],
                            capture_output=True, text=True)
         if p.returncode != 0:
