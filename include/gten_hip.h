@@ -128,8 +128,8 @@ int gten_hip_set_prefill_exact(int on);
  * of the probabilities, fp16 operand rounding in the wide W.x and p.V).  Up to 8 sequences and contexts <= 256 both forms
  * are the same bytes. */
 int gten_hip_set_decode_exact(int on);
-/* The single-sequence attention kernel's A/B control (round 5's k_dec_attn_one64 against the default k_dec_attn_one64v, the
- * same bytes) is declared in include/gten_hip_ab.h. */
+/* The single-sequence attention kernel's three-way A/B control (the default k_dec_attn_one64w with helper waves, round 5's
+ * k_dec_attn_one64, the one-wave-per-SIMD k_dec_attn_one64v: the same bytes) is declared in include/gten_hip_ab.h. */
 /* Decoders of 16+ sequences created AFTERWARDS (Q8 activations, fast forms) keep HEAD-MAJOR SHADOWS of their sequences' K / V
  * caches (on != 0, the default; round 5, csrc/gten_decode_attn_hm.h) or read the cache rows as they lie (0: round 4's kernel).
  * The caches themselves keep the reference's row layout [max_ctx][kv_dim] (gten/modules.cpp:188-201) for every reader and

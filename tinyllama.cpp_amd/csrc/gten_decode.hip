@@ -37,8 +37,8 @@ using namespace gtd;
 extern __shared__ __attribute__((aligned(16))) uint8_t g_smem[];
 
 #define DEC_CHUNK 256            // attention positions per workgroup
-#define ATT1V_VROW 68            // k_dec_attn_one64v: floats per V row in LDS (16-byte row stores without bank conflicts)
-#define ATT1V_PCOL 72            // k_dec_attn_one64v: floats per column group of p in LDS (conflict-free scattered stores)
+#define ATT1V_VROW 68            // k_dec_attn_one64v / one64w: floats per V row in LDS (16-byte row stores without bank conflicts)
+#define ATT1V_PCOL 72            // k_dec_attn_one64v / one64w: floats per column group of p in LDS (conflict-free scattered stores)
 #define DEC_MAX_LANES 4           // lanes of up to 64 sequences in one decoder (256 sequences)
 #define DEC_ATT_MAXCH 8          // chunk partials / statistics a consumer requests up front (2048 positions)
 #define GEMVM_F16_LDS_LIMIT 65536  // multi-sequence f16 inputs are staged in LDS up to this many bytes (8 sequences x 2048 x f32; the launchers raise
@@ -95,6 +95,7 @@ enum { EPI_RAW = 0, EPI_SILUMUL = 1, EPI_STAGE = 2, EPI_STAGE_FRAG = 3 };
 #include "gten_decode_ffn.h"
 #include "gten_decode_wxp.h"
 #include "gten_decode_attn.h"
+#include "gten_decode_attn_w.h"
 #include "gten_decode_attn_exact64.h"
 #include "gten_decode_attn_wide.h"
 #include "gten_decode_attn_hm.h"
@@ -163,7 +164,7 @@ struct gten_hip_decoder {
     // graph (fork behind the previous replay, join at the end), so the chains fill each other's gaps.  Per sequence the
     // kernels, their arguments and therefore the results are those of a 64-sequence decoder.
     bool exact = false;               // gten_hip_set_decode_exact at creation
-    bool attn_classic = false;        // gten_hip_set_decode_attn_classic at creation
+    int attn_classic = 0;             // gten_hip_set_decode_attn_classic at creation (0 / 1 / 2)
     bool persist_on = false;          // gten_hip_set_decode_persistent at creation: the step as ONE persistent launch (gten_decode_persist.h)
     struct PersistState* persist = nullptr;
     // ---- head-major shadows of the K / V caches (gten_decode_attn_hm.h): decoders of 16+ sequences, Q8 activations, fast forms.
@@ -263,14 +264,16 @@ extern "C" int gten_hip_set_decode_exact(int on)
     g_decode_exact = on != 0;
     return 0;
 }
-// decoders created AFTERWARDS run the single-sequence d_head 64 attention as k_dec_attn_one64 (on != 0: the A/B control) or as
-// k_dec_attn_one64v (0, the default): the same bytes on a shorter p.V schedule.  g_attn_classic_now: the creating choice of the
-// decoder whose step is being enqueued.
-static bool g_attn_classic = false;
-static bool g_attn_classic_now = false;
-extern "C" int gten_hip_set_decode_attn_classic(int on)
+// decoders created AFTERWARDS run the single-sequence d_head 64 attention as k_dec_attn_one64w (0, the default: the chain on
+// waves 0-3, V widened by helper waves 4-7), as k_dec_attn_one64 (1: the A/B control) or as k_dec_attn_one64v (2: one wave per
+// SIMD on the shorter p.V schedule) -- the same bytes from all three.  g_attn_classic_now: the creating choice of the decoder
+// whose step is being enqueued.
+static int g_attn_classic = 0;
+static int g_attn_classic_now = 0;
+extern "C" int gten_hip_set_decode_attn_classic(int v)
 {
-    g_attn_classic = on != 0;
+    GTR_REQUIRE(v >= 0 && v <= 2, "gten_hip_set_decode_attn_classic: %d is not 0, 1 or 2", v);
+    g_attn_classic = v;
     return 0;
 }
 
@@ -435,8 +438,18 @@ static int launch_attention(const AttnArgs& t0, dim3 agrid, size_t smem1)
                                (unsigned long long)(uintptr_t)t.step, geo, (unsigned long long)(unsigned)t.n_embd | heads, (unsigned long long)(uintptr_t)t.vcache}};
         const bool multi = agrid.z > 1 || t.kv_tab != nullptr;
         const dim3 g64(agrid.y, agrid.x, agrid.z);     // (chunk, head, sequence)
-        if (!multi && !g_attn_classic_now) {
+        if (!multi && g_attn_classic_now != 1) {
             const size_t smem_v = 1152 + (size_t)(4 * ATT1V_PCOL + DEC_CHUNK) * 4 + (size_t)DEC_CHUNK * ATT1V_VROW * 4;
+            if (g_attn_classic_now == 0) {                   // two waves per SIMD: the chain and its helpers
+                if (t.adtype == GTEN_Q8) {
+                    GTR_CHECK(hipFuncSetAttribute((const void*)k_dec_attn_one64w<GTEN_Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v));
+                    DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, k_dec_attn_one64w<GTEN_Q8>, g64, dim3(512), smem_v, hw, t);
+                } else {
+                    GTR_CHECK(hipFuncSetAttribute((const void*)k_dec_attn_one64w<GTEN_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v));
+                    DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, k_dec_attn_one64w<GTEN_F16>, g64, dim3(512), smem_v, hw, t);
+                }
+                return 0;
+            }
             if (t.adtype == GTEN_Q8) {
                 GTR_CHECK(hipFuncSetAttribute((const void*)k_dec_attn_one64v<GTEN_Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_v));
                 DEC_LAUNCH_HOT(KT_DEC_ATTN_SCORE, k_dec_attn_one64v<GTEN_Q8>, g64, dim3(256), smem_v, hw, t);

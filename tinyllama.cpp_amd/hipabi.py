@@ -246,9 +246,9 @@ class GtenHip:
         self._check(self._decode_exact(1 if on else 0))
 
     def set_decode_attn_classic(self, on):
-        """decoders created from now on: the single-sequence attention as k_dec_attn_one64 (the A/B control) or, by default,
-        k_dec_attn_one64v -- the same bytes (include/gten_hip_ab.h)"""
-        self._check(self._decode_attn_classic(1 if on else 0))
+        """decoders created from now on: the single-sequence attention as k_dec_attn_one64w (0 / False, the default), as
+        k_dec_attn_one64 (1 / True, the A/B control) or as k_dec_attn_one64v (2) -- the same bytes (include/gten_hip_ab.h)"""
+        self._check(self._decode_attn_classic(int(on)))
 
     def set_prefix_decode_shared(self, on):
         """decode slots behind a shared prefix read ONE copy of its K / V (default) or each its own (include/gten_hip_prefix_decode.h)"""
