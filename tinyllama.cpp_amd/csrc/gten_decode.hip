@@ -25,6 +25,7 @@
 #include "gten_dev.h"
 #include "gten_rt.h"
 #include "gten_hip_sample.h"
+#include "gten_hip_bias.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 
@@ -152,6 +153,12 @@ struct gten_hip_decoder {
     SampleParam* samp = nullptr;        // [n_seq]
     std::vector<SampleParam> samp_host;
     int n_sampling = 0;                 // sequences with top_k >= 1
+    // bias tables (include/gten_hip_bias.h): [GTEN_HIP_BIAS_TABLES][n_vocab] f32, made by the first call that needs them.
+    // A bound sequence (SampleParam::table1 > 0) makes the step end in the sampler like a sampling one does; from the first binding on
+    // (bias_on: the graphs captured before are dropped once) that launch is k_dec_sample_b, which treats unbound sequences as k_dec_sample does.
+    float* bias = nullptr;
+    int n_bound = 0;                    // sequences with a table
+    bool bias_on = false;
     hipGraph_t s_graph = nullptr, s_graph_k = nullptr, s_graph_m[1 << DEC_MAX_LANES] = {}, s_graph_km[1 << DEC_MAX_LANES] = {};
     hipGraphExec_t s_exec = nullptr, s_exec_k = nullptr, s_exec_m[1 << DEC_MAX_LANES] = {}, s_exec_km[1 << DEC_MAX_LANES] = {};
     unsigned lane_mask = 0;             // lanes the NEXT enqueue takes (0: all)
@@ -198,6 +205,9 @@ struct gten_hip_decoder {
     hipStream_t lane_stream[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};    // capture / eager side streams of lanes 1..
     hipEvent_t lane_fork = nullptr, lane_join[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
 };
+
+// the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples or has a bias table
+static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->n_sampling + dc->n_bound > 0; }
 
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
@@ -624,7 +634,10 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
-    if (dc->n_sampling > 0)
+    if (sampler_on(dc) && dc->bias_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
+    else if (sampler_on(dc))
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
                    dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1);
     else
@@ -768,7 +781,10 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    if (dc->n_sampling > 0)
+    if (sampler_on(dc) && dc->bias_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
+    else if (sampler_on(dc))
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
                    dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
     else
@@ -1245,7 +1261,10 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     sf.act_q = b.stg_q; sf.act_d = b.stg_d; sf.act_sum = b.stg_sum; sf.act_f = b.stg_f;
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
-    if (dc->n_sampling > 0)
+    if (sampler_on(dc) && dc->bias_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
+                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias);
+    else if (sampler_on(dc))
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
                    b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
     else
@@ -1641,7 +1660,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
@@ -1829,7 +1848,7 @@ static int run_steps_free(gten_hip_decoder* dc, int count)
     if (int rc = pre_run(dc)) return rc;
     if (prof_on()) { for (int i = 0; i < count; i++) if (int rc = run_step(dc, 0)) return rc; return 0; }
     const unsigned gs = graph_slot(dc);
-    const bool smp = dc->n_sampling > 0;
+    const bool smp = sampler_on(dc);
     hipGraph_t& graph_k = smp ? (gs ? dc->s_graph_km[gs] : dc->s_graph_k) : (gs ? dc->graph_km[gs] : dc->graph_k);
     hipGraphExec_t& exec_k = smp ? (gs ? dc->s_exec_km[gs] : dc->s_exec_k) : (gs ? dc->exec_km[gs] : dc->exec_k);
     while (count >= DEC_GRAPH_STEPS) {
@@ -1856,7 +1875,7 @@ static int run_step(gten_hip_decoder* dc, int use_graph)
     if (int rc = pre_run(dc)) return rc;
     if (!use_graph || prof_on()) return enqueue(dc);    // event pairs cannot be recorded into a capture
     const unsigned gs = graph_slot(dc);
-    const bool smp = dc->n_sampling > 0;
+    const bool smp = sampler_on(dc);
     hipGraph_t& graph = smp ? (gs ? dc->s_graph_m[gs] : dc->s_graph) : (gs ? dc->graph_m[gs] : dc->graph);
     hipGraphExec_t& exec = smp ? (gs ? dc->s_exec_m[gs] : dc->s_exec) : (gs ? dc->exec_m[gs] : dc->exec);
     if (!exec) {
@@ -2520,7 +2539,11 @@ int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, floa
     GTR_REQUIRE(top_k == 0 || !dc->persist_on, "decoder_set_sampling: the persistent step (gten_hip_set_decode_persistent) has no sampler");
     SampleParam& p = dc->samp_host[(size_t)seq];
     dc->n_sampling += (top_k > 0 ? 1 : 0) - (p.top_k > 0 ? 1 : 0);
+    const int table1 = p.table1;
+    const unsigned until = p.until;
     p = SampleParam{};
+    p.table1 = table1;           // (the bias binding is gten_hip_decoder_set_seq_bias's half of the request)
+    p.until = until;
     p.top_k = top_k;
     p.temp = top_k > 0 ? temp : 0.f;
     p.stream = stream_id;
@@ -2533,6 +2556,22 @@ int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, floa
 
 static SampleRowParam* g_rows_dev = nullptr;      // gten_hip_sample_rows' per-row requests (grow-only)
 static size_t g_rows_cap = 0;
+
+// the per-row requests of one operator call on the device (g_rows_dev, grown when needed), queued on the stream
+static int rows_upload(const std::vector<SampleRowParam>& rows)
+{
+    const size_t n_rows = rows.size();
+    if (g_rows_cap < n_rows) {
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        if (g_rows_dev) GTR_CHECK(hipFree(g_rows_dev));
+        g_rows_dev = nullptr;
+        g_rows_cap = 0;
+        GTR_CHECK(hipMalloc((void**)&g_rows_dev, n_rows * sizeof(SampleRowParam)));
+        g_rows_cap = n_rows;
+    }
+    GTR_CHECK(hipMemcpyAsync(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam), hipMemcpyHostToDevice, stream()));
+    return 0;
+}
 
 int gten_hip_sample_rows(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* top_k_host, const float* temp_host,
                          uint64_t seed, const uint32_t* stream_host, const int32_t* position_host, int32_t* out)
@@ -2548,17 +2587,108 @@ int gten_hip_sample_rows(const float* logits, int n_rows, int n_vocab, long long
         GTR_REQUIRE(position_host[r] >= 0, "sample_rows: position %d of row %d", position_host[r], r);
         rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
     }
-    if (g_rows_cap < (size_t)n_rows) {
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        if (g_rows_dev) GTR_CHECK(hipFree(g_rows_dev));
-        g_rows_dev = nullptr;
-        g_rows_cap = 0;
-        GTR_CHECK(hipMalloc((void**)&g_rows_dev, (size_t)n_rows * sizeof(SampleRowParam)));
-        g_rows_cap = (size_t)n_rows;
-    }
-    GTR_CHECK(hipMemcpyAsync(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam), hipMemcpyHostToDevice, stream()));
+    if (int rc = rows_upload(rows)) return rc;
     GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, (const SampleRowParam*)g_rows_dev,
                (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
+    return 0;
+}
+
+// ---- bias tables (include/gten_hip_bias.h, gten_decode_sample.h)
+static int bias_ensure(gten_hip_decoder* dc)
+{
+    if (dc->bias) return 0;
+    const size_t bytes = (size_t)GTEN_HIP_BIAS_TABLES * (size_t)dc->d.n_vocab * sizeof(float);
+    GTR_CHECK(hipMalloc((void**)&dc->bias, bytes));
+    GTR_CHECK(hipMemsetAsync(dc->bias, 0, bytes, stream()));                 // every table: no bias
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_set_bias_table(gten_hip_decoder* dc, int table, const int32_t* ids_host, const float* values_host, int n, float fill)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_set_bias_table: null decoder");
+    GTR_REQUIRE(!dc->persist_on, "decoder_set_bias_table: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    GTR_REQUIRE(table >= 0 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_bias_table: table %d outside [0, %d)", table, GTEN_HIP_BIAS_TABLES);
+    GTR_REQUIRE(n >= 0 && (n == 0 || (ids_host && values_host)), "decoder_set_bias_table: %d pairs, null lists", n);
+    const int V = dc->d.n_vocab;
+    auto value_ok = [](float v) { return v == -INFINITY || (std::isfinite(v) && std::fabs(v) <= GTEN_HIP_BIAS_MAX); };
+    GTR_REQUIRE(value_ok(fill), "decoder_set_bias_table: fill %g (finite with |b| <= 1e30, or -inf)", (double)fill);
+    std::vector<float> row((size_t)V, fill);
+    std::vector<char> seen((size_t)V, 0);
+    for (int i = 0; i < n; i++) {
+        const int id = ids_host[i];
+        GTR_REQUIRE(id >= 0 && id < V, "decoder_set_bias_table: id %d outside [0, %d)", id, V);
+        GTR_REQUIRE(!seen[(size_t)id], "decoder_set_bias_table: id %d is listed twice", id);
+        GTR_REQUIRE(value_ok(values_host[i]), "decoder_set_bias_table: value %g of id %d (finite with |b| <= 1e30, or -inf)", (double)values_host[i], id);
+        seen[(size_t)id] = 1;
+        row[(size_t)id] = values_host[i];
+    }
+    bool any = false;
+    for (int j = 0; j < V && !any; j++) any = row[(size_t)j] > -INFINITY;
+    GTR_REQUIRE(any, "decoder_set_bias_table: table %d would ban every id", table);
+    if (int rc = bias_ensure(dc)) return rc;
+    GTR_CHECK(hipMemcpyAsync(dc->bias + (size_t)table * (size_t)V, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `row` lives on this stack frame
+    return 0;
+}
+
+int gten_hip_decoder_set_seq_bias(gten_hip_decoder* dc, int seq, int table, int until)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_seq_bias: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(table >= -1 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_seq_bias: table %d outside [-1, %d)", table, GTEN_HIP_BIAS_TABLES);
+    GTR_REQUIRE(until >= 0, "decoder_set_seq_bias: until %d < 0", until);
+    GTR_REQUIRE(table < 0 || !dc->persist_on, "decoder_set_seq_bias: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    SampleParam& p = dc->samp_host[(size_t)seq];
+    if (table >= 0 && !dc->bias_on) {
+        // the first binding of this decoder: from now on its sampler launch is the one that knows the tables
+        if (int rc = bias_ensure(dc)) return rc;
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        GTR_CHECK(drop_graphs(dc));
+        dc->bias_on = true;
+    }
+    dc->n_bound += (table >= 0 ? 1 : 0) - (p.table1 > 0 ? 1 : 0);
+    p.table1 = table + 1;
+    p.until = table >= 0 ? (unsigned)until : 0u;
+    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_bias_info(gten_hip_decoder* dc, int* n_tables, int32_t* table_host, int32_t* until_host, int table, const float** table_row)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_bias_info: null decoder");
+    if (n_tables) *n_tables = GTEN_HIP_BIAS_TABLES;
+    for (int q = 0; q < dc->n_seq; q++) {
+        const SampleParam& p = dc->samp_host[(size_t)q];
+        if (table_host) table_host[q] = p.table1 - 1;
+        if (until_host) until_host[q] = p.table1 > 0 ? (int32_t)p.until : 0;
+    }
+    if (table_row) *table_row = (dc->bias && table >= 0 && table < GTEN_HIP_BIAS_TABLES) ? dc->bias + (size_t)table * (size_t)dc->d.n_vocab : nullptr;
+    return 0;
+}
+
+int gten_hip_sample_rows_biased(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                                const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                                const int32_t* position_host, int32_t* out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0 && bias_stride >= 0,
+                "sample_rows_biased: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", n_rows, n_vocab, row_stride, bias_stride);
+    if (n_rows == 0) return 0;
+    GTR_REQUIRE(logits && bias && out && top_k_host && temp_host && stream_host && position_host, "sample_rows_biased: null argument");
+    std::vector<SampleRowParam> rows((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows_biased")) return rc;
+        GTR_REQUIRE(position_host[r] >= 0, "sample_rows_biased: position %d of row %d", position_host[r], r);
+        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
+    }
+    if (int rc = rows_upload(rows)) return rc;
+    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_b, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, bias, bias_stride,
+               (const SampleRowParam*)g_rows_dev, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
     GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
     return 0;
 }

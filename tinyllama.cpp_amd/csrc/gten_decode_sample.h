@@ -18,7 +18,9 @@ struct SampleParam {             // one sequence's request (gten_hip_decoder_set
     float temp;
     unsigned stream;
     unsigned seed_lo, seed_hi;
-    unsigned pad[3];
+    int table1;                  // bias table + 1 (0: none), so that a zeroed request is "greedy, no table"
+    unsigned until;              // the table holds for positions < until (0: for every position)
+    unsigned pad;
 };
 struct SampleRowParam {          // one row of gten_hip_sample_rows; 16 bytes
     int top_k;
@@ -136,16 +138,28 @@ __device__ __forceinline__ void smp_find_digit(unsigned kk, SmpShared& sm)
     __syncthreads();
 }
 
+// element i of the row the draw is made from: the logit, or (BIAS) y_i = x_i + b_i -- one f32 add, formed anew
+// wherever the row is read (the add is deterministic: every pass sees the same y)
+template <bool BIAS>
+__device__ __forceinline__ float smp_at(const float* __restrict__ x, const float* __restrict__ b, int i)
+{
+    if constexpr (BIAS) return x[i] + b[i];
+    else return x[i];
+}
+
 // One row: the id of the contract (top_k >= 1) or the greedy argmax (top_k == 0).  Every thread returns it.
-__device__ __forceinline__ int smp_row(const float* __restrict__ x, int n, int top_k, float temp, unsigned pos, unsigned stream,
-                                       unsigned k0, unsigned k1, SmpShared& sm)
+// BIAS: the row is y = x + b (b: a bias table's row; -inf = banned -- its key sorts below every finite value and its score is
+// -inf, so it is never the argmax while one entry is above -inf); the unbiased instance never touches b.
+template <bool BIAS>
+__device__ __forceinline__ int smp_row(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
+                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm)
 {
     const int t = threadIdx.x;
     if (top_k <= 0) {
         float best = -INFINITY;
         int idx = 0x7fffffff;
         for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = x[i];
+            const float v = smp_at<BIAS>(x, b, i);
             if (v > best || (v == best && i < idx)) { best = v; idx = i; }
         }
         return smp_block_argmax(best, idx, sm);
@@ -161,7 +175,7 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ x, int n, int t
         if (shift == 24) {
             for (int base = 0; base < n; base += SMP_THREADS) {         // (every lane runs every trip: smp_hist_add is per wave)
                 const int i = base + t;
-                const float v = i < n ? x[i] : -INFINITY;
+                const float v = i < n ? smp_at<BIAS>(x, b, i) : -INFINITY;
                 mx = fmaxf(mx, v);
                 if (!all) smp_hist_add(sm, i < n, smp_key(v) >> 24);
             }
@@ -170,7 +184,7 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ x, int n, int t
         } else {
             for (int base = 0; base < n; base += SMP_THREADS) {
                 const int i = base + t;
-                const unsigned key = i < n ? smp_key(x[i]) : 0u;
+                const unsigned key = i < n ? smp_key(smp_at<BIAS>(x, b, i)) : 0u;
                 smp_hist_add(sm, i < n && (key & mask) == prefix, (key >> shift) & 255u);
             }
             __syncthreads();
@@ -189,7 +203,7 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ x, int n, int t
                 for (int i = t; i < 256; i += SMP_THREADS) sm.hist[i] = 0u;
                 __syncthreads();
                 for (int i = t; i < n; i += SMP_THREADS)
-                    if (smp_key(x[i]) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
+                    if (smp_key(smp_at<BIAS>(x, b, i)) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
                 __syncthreads();
                 smp_find_digit(kk, sm);
                 const unsigned di = 255u - sm.word[0], ri = sm.word[1];
@@ -204,7 +218,7 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ x, int n, int t
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i = t; i < n; i += SMP_THREADS) {
-        const float v = x[i];
+        const float v = smp_at<BIAS>(x, b, i);
         const unsigned key = smp_key(v) & mask;
         if (key > prefix || (key == prefix && i <= ilim)) {
             const float s = (v - mx) / temp + smp_gumbel((unsigned)i, pos, stream, k0, k1);
@@ -224,7 +238,7 @@ __global__ __launch_bounds__(SMP_THREADS) void k_dec_sample(const float* __restr
     const SampleParam p = par0[blockIdx.x];
     DecStep* step = step0 + blockIdx.x;
     const unsigned pos = (unsigned)step->n;
-    const int idx = smp_row(logits0 + (size_t)blockIdx.x * row_stride, n_vocab, p.top_k, p.temp, pos, p.stream, p.seed_lo, p.seed_hi, sm);
+    const int idx = smp_row<false>(logits0 + (size_t)blockIdx.x * row_stride, nullptr, n_vocab, p.top_k, p.temp, pos, p.stream, p.seed_lo, p.seed_hi, sm);
     if (threadIdx.x == 0) dec_pick_commit(step, result0 + (size_t)blockIdx.x * result_stride, tokens0 + (size_t)blockIdx.x * tok_stride, idx);
 }
 
@@ -234,6 +248,38 @@ __global__ __launch_bounds__(SMP_THREADS) void k_sample_rows(const float* __rest
 {
     __shared__ SmpShared sm;
     const SampleRowParam p = par[blockIdx.x];
-    const int idx = smp_row(logits + (size_t)blockIdx.x * (size_t)row_stride, n_vocab, p.top_k, p.temp, p.pos, p.stream, seed_lo, seed_hi, sm);
+    const int idx = smp_row<false>(logits + (size_t)blockIdx.x * (size_t)row_stride, nullptr, n_vocab, p.top_k, p.temp, p.pos, p.stream, seed_lo, seed_hi, sm);
+    if (threadIdx.x == 0) out[blockIdx.x] = idx;
+}
+
+// ---- bias tables (include/gten_hip_bias.h).  k_dec_sample with the decoder's tables: a sequence whose request
+// names a table (table1 > 0) that still holds at this position draws from y = x + b, every other one exactly as k_dec_sample does
+// -- the choice is per workgroup, outside the select.  bias0: [tables][n_vocab] f32.
+__global__ __launch_bounds__(SMP_THREADS) void k_dec_sample_b(const float* __restrict__ logits0, int n_vocab, int row_stride, const SampleParam* __restrict__ par0,
+                                                             DecStep* step0, int32_t* __restrict__ result0, int result_stride,
+                                                             int32_t* __restrict__ tokens0, int tok_stride, const float* __restrict__ bias0)
+{
+    __shared__ SmpShared sm;
+    const SampleParam p = par0[blockIdx.x];
+    DecStep* step = step0 + blockIdx.x;
+    const unsigned pos = (unsigned)step->n;
+    const float* x = logits0 + (size_t)blockIdx.x * row_stride;
+    int idx;
+    if (p.table1 > 0 && (p.until == 0u || pos < p.until))
+        idx = smp_row<true>(x, bias0 + (size_t)(p.table1 - 1) * (size_t)n_vocab, n_vocab, p.top_k, p.temp, pos, p.stream, p.seed_lo, p.seed_hi, sm);
+    else
+        idx = smp_row<false>(x, nullptr, n_vocab, p.top_k, p.temp, pos, p.stream, p.seed_lo, p.seed_hi, sm);
+    if (threadIdx.x == 0) dec_pick_commit(step, result0 + (size_t)blockIdx.x * result_stride, tokens0 + (size_t)blockIdx.x * tok_stride, idx);
+}
+
+// gten_hip_sample_rows_biased: k_sample_rows on y = x + b, row r's bias at bias + r * bias_stride (0: one row for all)
+__global__ __launch_bounds__(SMP_THREADS) void k_sample_rows_b(const float* __restrict__ logits, int n_vocab, long long row_stride,
+                                                              const float* __restrict__ bias, long long bias_stride,
+                                                              const SampleRowParam* __restrict__ par, unsigned seed_lo, unsigned seed_hi, int32_t* __restrict__ out)
+{
+    __shared__ SmpShared sm;
+    const SampleRowParam p = par[blockIdx.x];
+    const int idx = smp_row<true>(logits + (size_t)blockIdx.x * (size_t)row_stride, bias + (size_t)blockIdx.x * (size_t)bias_stride, n_vocab, p.top_k, p.temp,
+                                  p.pos, p.stream, seed_lo, seed_hi, sm);
     if (threadIdx.x == 0) out[blockIdx.x] = idx;
 }

@@ -97,6 +97,9 @@ class GtenHip:
     ]
     # include/gten_hip_sample.h (top-k sampling on the device)
     SAMPLE_SYMBOLS = ["gten_hip_decoder_set_sampling", "gten_hip_sample_rows"]
+    # include/gten_hip_bias.h (bias tables: constrained generation on the device)
+    BIAS_SYMBOLS = ["gten_hip_decoder_set_bias_table", "gten_hip_decoder_set_seq_bias", "gten_hip_sample_rows_biased", "gten_hip_decoder_bias_info"]
+    BIAS_TABLES = 16                                             # GTEN_HIP_BIAS_TABLES
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
@@ -153,6 +156,10 @@ class GtenHip:
         self._copy_ranges = _sig(L, "gten_hip_copy_ranges", ci, [C.c_void_p, ci])
         self._set_sampling = _sig(L, "gten_hip_decoder_set_sampling", ci, [vp, ci, ci, C.c_float, C.c_uint64, C.c_uint32])
         self._sample_rows = _sig(L, "gten_hip_sample_rows", ci, [vp, ci, ci, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp])
+        self._sample_rows_biased = _sig(L, "gten_hip_sample_rows_biased", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp])
+        self._set_bias_table = _sig(L, "gten_hip_decoder_set_bias_table", ci, [vp, ci, vp, vp, ci, C.c_float])
+        self._set_seq_bias = _sig(L, "gten_hip_decoder_set_seq_bias", ci, [vp, ci, ci, ci])
+        self._bias_info = _sig(L, "gten_hip_decoder_bias_info", ci, [vp, C.POINTER(ci), vp, vp, ci, C.POINTER(vp)])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
@@ -219,6 +226,19 @@ class GtenHip:
         out = DeviceBuffer(self, 4 * max(n_rows, 1))
         return self._sample_rows(logits.ptr, n_rows, n_vocab, row_stride, k.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
                                  C.c_uint64(int(seed)), s.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p), out.ptr)
+
+    def sample_rows_biased(self, logits, bias, n_rows, n_vocab, row_stride, bias_stride, top_k, temp, seed, stream, position):
+        """ids of gten_hip_sample_rows_biased (include/gten_hip_bias.h): sample_rows on logits + bias, `bias` a DeviceBuffer of f32
+        rows, row r at r * bias_stride elements (0: one row for all).  Returns int32[n_rows]."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        out = DeviceBuffer(self, max(4 * n_rows, 4))
+        self._check(self._sample_rows_biased(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr, bias_stride, kp, tp, C.c_uint64(int(seed)), sp, pp,
+                                             out.ptr))
+        return out.download(np.int32)[:n_rows].copy()
 
     def row_logprobs(self, logits, n_rows, n_vocab, row_stride, targets):
         """gten_hip_row_logprobs (include/gten_hip_score.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride elements;

@@ -4,7 +4,8 @@
 // no network here: --model PATH, default models/tinyllama.<fp16|q8|q4>.gten as there), --tokenizer PATH (default
 // tokenizer.bin), --seed for the top-k sampler, --ids to print token ids instead of text (tests); greedy sampling runs
 // with the sampler on the device (gten::greedy_generate); --score PATH prints the log-likelihood of a text file
-// (include/gten_host_score.h) instead of generating.
+// (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
+// of the model's decoder (include/gten_hip_bias.h), in both generation modes.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -42,6 +43,9 @@ Optional args.
            --ctx ids, each [1] + the next ctx-1 text ids, so that every text id is scored once.  Prints
            `score: tokens=T nll=<mean -logprob> ppl=<exp(nll)> greedy=<fraction of ids that were the argmax>`.
 --ctx N :  window length for --score. Minimum is 17 and max is 2048. [default=2048].
+--ban ID[,ID...] :   token ids that are never generated (greedy and top-k alike).
+--allow ID[,ID...] : the only token ids that may be generated. With --ban: those of them that are not banned.
+--min-new N : --ban / --allow hold for the first N generated ids only; N must be gte 1. [default: for all of them]
 )";
 
 struct Options {
@@ -51,12 +55,66 @@ struct Options {
     float temp = 0.9f;
     bool greedy = false, ids = false, seeded = false;
     uint64_t seed = 0;
+    std::vector<int32_t> ban, allow;         // --ban / --allow (bias table 0)
+    int min_new = 0;
+    bool constrained() const { return !ban.empty() || !allow.empty(); }
 };
 
 static void emit(const Options& o, Tokenizer& tok, int prev, int id)
 {
     if (o.ids) std::cout << id << ' ';
     else std::cerr << tok.decode(prev, id);
+}
+
+// "ID[,ID...]" -> ids in [0, n_vocab), none twice; false (with a message) otherwise
+static bool parse_id_list(const char* what, const std::string& text, int n_vocab, std::vector<int32_t>* out)
+{
+    out->clear();
+    size_t pos = 0;
+    while (pos <= text.size()) {
+        const size_t comma = std::min(text.find(',', pos), text.size());
+        const std::string item = text.substr(pos, comma - pos);
+        size_t used = 0;
+        long v = -1;
+        try { v = std::stol(item, &used); } catch (...) { used = 0; }
+        if (item.empty() || used != item.size()) { std::cerr << "Invalid " << what << " value: ids are integers separated by commas.\n"; return false; }
+        if (v < 0 || v >= n_vocab) { std::cerr << what << " ids must be gte 0 and lt " << n_vocab << ".\n"; return false; }
+        if (std::find(out->begin(), out->end(), (int32_t)v) != out->end()) { std::cerr << what << " lists id " << v << " twice.\n"; return false; }
+        out->push_back((int32_t)v);
+        pos = comma + 1;
+    }
+    return true;
+}
+
+// --ban / --allow as bias table 0 of the model's decoder: allow -> everything else banned, ban -> those ids banned
+static void set_constraint(const Options& o, TinyLlama& model)
+{
+    std::vector<int32_t> ids = o.allow;
+    std::vector<float> values(o.allow.size(), 0.f);
+    for (const int32_t id : o.ban) {
+        const auto it = std::find(ids.begin(), ids.end(), id);
+        if (it != ids.end()) values[(size_t)(it - ids.begin())] = -INFINITY;
+        else { ids.push_back(id); values.push_back(-INFINITY); }
+    }
+    const float fill = o.allow.empty() ? 0.f : -INFINITY;
+    if (gten_hip_decoder_set_bias_table(model.decoder_handle(), 0, ids.data(), values.data(), (int)ids.size(), fill) != 0) {
+        std::cerr << "error: " << gten_hip_last_error() << "\n";
+        std::exit(EXIT_FAILURE);
+    }
+}
+
+// either generation mode under table 0 (top_k 0: greedy over the biased logits)
+static void run_constrained(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
+{
+    std::vector<int> enc = tok.encode(prompt);
+    std::vector<int32_t> tokens(enc.begin(), enc.end());
+    const size_t n_prompt = tokens.size();
+    if (biased_generate(model, tokens, o.n_predict, tok.eos, o.greedy ? 0 : o.topk, o.temp, seed, turn, 0, o.min_new) < 0) {
+        std::cerr << "error: " << gten_hip_last_error() << "\n";
+        std::exit(EXIT_FAILURE);
+    }
+    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
+    (o.ids ? std::cout : std::cerr) << '\n';
 }
 
 // greedy: the prompt as in the reference, every later id from the device-side sampler
@@ -164,10 +222,24 @@ int main(int argc, char const* argv[])
             try { v = std::stoi(value("topk")); } catch (...) { std::cerr << "Invalid topk value.\n"; return -1; }
             if (v < 1 || v > 32003) { std::cerr << "topk must be gte 1 and lte " << 32003 << ".\n"; return -1; }
             o.topk = v;
+        } else if (arg == "--ban") {
+            if (!parse_id_list("ban", value("ban"), 32003, &o.ban)) return -1;
+        } else if (arg == "--allow") {
+            if (!parse_id_list("allow", value("allow"), 32003, &o.allow)) return -1;
+        } else if (arg == "--min-new") {
+            int v = 0;
+            try { v = std::stoi(value("min-new")); } catch (...) { std::cerr << "Invalid min-new value.\n"; return -1; }
+            if (v < 1 || v > 2048) { std::cerr << "min-new must be gte 1 and lte 2048.\n"; return -1; }
+            o.min_new = v;
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
         }
+    }
+    if (o.min_new > 0 && !o.constrained()) { std::cerr << "min-new needs --ban or --allow.\n"; return -1; }
+    if (!o.allow.empty() && std::all_of(o.allow.begin(), o.allow.end(), [&](int32_t id) { return std::find(o.ban.begin(), o.ban.end(), id) != o.ban.end(); })) {
+        std::cerr << "--ban bans every id of --allow.\n";
+        return -1;
     }
     if (o.model_path.empty()) o.model_path = "models/tinyllama." + model_id + ".gten";
 
@@ -194,9 +266,11 @@ int main(int argc, char const* argv[])
         std::random_device rd;
         seed = ((uint64_t)rd() << 32) | (uint64_t)rd();
     }
+    if (o.constrained()) set_constraint(o, model);
     uint32_t turn = 0;
     auto answer = [&](const std::string& prompt) {
-        if (o.greedy) run_greedy(o, prompt, model, tokenizer);
+        if (o.constrained()) run_constrained(o, prompt, model, tokenizer, seed, turn++);
+        else if (o.greedy) run_greedy(o, prompt, model, tokenizer);
         else run_topk(o, prompt, model, tokenizer, seed, turn++);
     };
     if (o.prompt.empty()) {

@@ -26,6 +26,7 @@
 
 #include "../gten/gten.h"
 #include "../../include/gten_hip_sample.h"
+#include "../../include/gten_hip_bias.h"
 #include "../../include/gten_hip_score.h"
 #include "synth.h"
 
@@ -349,6 +350,13 @@ public:
     {
         ensure_decoder();
         return gten_hip_decoder_set_sampling(dec_, 0, top_k, temp, seed, stream);
+    }
+
+    // the fused decoder itself, for the entry points that live outside this header (bias tables: host/capi_bias.cpp)
+    gten_hip_decoder* decoder_handle()
+    {
+        ensure_decoder();
+        return dec_;
     }
 
     ~TinyLlama()
@@ -882,9 +890,14 @@ public:
     int prefill_sampled(int seq_i, const std::vector<int32_t>& prompt, int top_k, float temp, uint64_t seed, uint32_t stream)
     {
         const int32_t pos = (int32_t)prompt.size();
-        auto pick = [&](int, const float* lg, int n, int32_t* out) {
+        return prefill_picked(seq_i, prompt, [&](int, const float* lg, int n, int32_t* out) {
             GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &top_k, &temp, seed, &stream, &pos, out));
-        };
+        });
+    }
+    // prefill() with the first id chosen on the device by pick(0, logits row in HBM, n_vocab, id out in HBM)
+    template <class PickRow>
+    int prefill_picked(int seq_i, const std::vector<int32_t>& prompt, PickRow pick)
+    {
         if (batched_prompts() && (int)prompt.size() >= 16 && (int)prompt.size() <= kPreRows) {
             std::vector<int> first;
             std::vector<float*> lo{nullptr};
@@ -930,6 +943,12 @@ public:
     {
         ensure_decoder();
         return gten_hip_decoder_set_sampling(dec_, seq_i, top_k, temp, seed, stream);
+    }
+    // the shared decoder itself, for the entry points that live outside this header (bias tables: host/capi_bias.cpp)
+    gten_hip_decoder* decoder_handle()
+    {
+        ensure_decoder();
+        return dec_;
     }
     // asynchronous: row n[q]-1 of sequence q (continuous batching)
     void decode_step_ragged(const int* n_per_seq, bool use_graph)
@@ -994,7 +1013,7 @@ public:
     // prompt j's request (top_k[j], temp[j], seed, stream j) draws its first id from the prompt's logits on the device and is
     // set on whichever slot takes the prompt -- the ids depend on (seed, j) and the logits only, not on the slot or schedule.
     struct GreedyServe {
-        static constexpr bool kSampled = false;
+        static constexpr bool kSampled = false, kBiased = false;
         int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int) { return b.prefill(c, row); }
         void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>&,
                   std::vector<int>* first)
@@ -1006,7 +1025,7 @@ public:
         uint64_t seed = 0;
     };
     struct SampledServe {
-        static constexpr bool kSampled = true;
+        static constexpr bool kSampled = true, kBiased = false;
         const int32_t* top_k_each;       // per prompt (null: top_k_all)
         const float* temp_each;          // per prompt (null: temp_all)
         int top_k_all;
@@ -1027,6 +1046,48 @@ public:
                 GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &kk, &t, seed, &st, &pos, out));
             });
         }
+    };
+    // SampledServe under bias tables (include/gten_hip_bias.h): prompt j names a table (-1: none) that holds for its
+    // first min_new new ids (0: for all of them).  The first id is drawn from the prompt's logits under the same table; the binding
+    // is set on whichever slot takes the prompt, beside its request, and every slot is unbound again when the queue is done.
+    struct BiasedServe {
+        static constexpr bool kSampled = true, kBiased = true;
+        const int32_t* top_k_each;       // per prompt (null: top_k_all)
+        const float* temp_each;          // per prompt (null: temp_all)
+        int top_k_all;
+        float temp_all;
+        uint64_t seed;
+        const int32_t* table_each;       // per prompt (null: none has a table)
+        const int32_t* min_new_each;     // per prompt (null: 0)
+        gten_hip_decoder* dec;
+        int top_k(int j) const { return top_k_each ? top_k_each[j] : top_k_all; }
+        float temp(int j) const { return temp_each ? temp_each[j] : temp_all; }
+        int table(int j) const { return table_each ? table_each[j] : -1; }
+        int until(int j, int n_prompt) const { return (min_new_each && min_new_each[j] > 0) ? n_prompt + min_new_each[j] : 0; }
+        // the id at position `pos` = the prompt's length: under the table unless it has run out already (it cannot: min_new >= 1)
+        void draw(int j, const float* lg, int n, int32_t pos, int32_t* out) const
+        {
+            const int32_t kk = top_k(j);
+            const float t = temp(j);
+            const uint32_t st = (uint32_t)j;
+            const float* row = nullptr;
+            if (table(j) >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table(j), &row));
+            if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n, 0, row, 0, &kk, &t, seed, &st, &pos, out));
+            else GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &kk, &t, seed, &st, &pos, out));
+        }
+        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
+        {
+            return b.prefill_picked(c, row, [&](int, const float* lg, int n, int32_t* out) { draw(j, lg, n, (int32_t)row.size(), out); });
+        }
+        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
+                  std::vector<int>* first)
+        {
+            std::vector<float*> lo((size_t)sets.size(), nullptr);
+            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
+                draw(js[(size_t)k], lg, n, (int32_t)ps[(size_t)k]->size(), out);
+            });
+        }
+        void bind(int q, int j, int n_prompt) const { GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, q, table(j), table(j) >= 0 ? until(j, n_prompt) : 0)); }
     };
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
@@ -1228,6 +1289,7 @@ public:
                     ap_seq.push_back(q); ap_first.push_back(r.cur); ap_last.push_back(r.last); ap_tok.push_back(row.data());
                     if constexpr (Pick::kSampled)
                         GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, pick.top_k(r.j), pick.temp(r.j), pick.seed, (uint32_t)r.j));
+                    if constexpr (Pick::kBiased) pick.bind(q, r.j, (int)prompts[(size_t)r.j].size());      // (travels with the request: also when a sequence moves in the tail)
                     live[(size_t)q] = 1; n_live++;
                 }
             }
@@ -1321,6 +1383,8 @@ public:
         rebind.done = true;
         if constexpr (Pick::kSampled)
             for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, 0, 0.f, 0, 0));     // every slot greedy again
+        if constexpr (Pick::kBiased)
+            for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec_, q, -1, 0));                // ... and unbound
         return st;
     }
 
@@ -1486,6 +1550,44 @@ inline int sampled_generate(TinyLlama& model, std::vector<int32_t>& tokens, cons
     if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) return -1;
     const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
     GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
+    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
+    return (int)tokens.size();
+}
+
+// sampled_generate under bias table `table` of the model's decoder (include/gten_hip_bias.h; -1: none), which holds
+// for the first min_new new ids (0: for all of them): the prompt's first id is drawn from y = logits + table row by the operator,
+// every later one inside the decode step.  top_k 0: greedy over y.  Request and binding are dropped again afterwards.
+// -1 when the decoder refuses (gten_hip_last_error).
+inline int biased_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
+                           uint64_t seed, uint32_t stream, int table, int min_new)
+{
+    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
+    gten_hip_decoder* dec = model.decoder_handle();
+    const int until = (table >= 0 && min_new > 0) ? (int)tokens.size() + min_new : 0;
+    if (gten_hip_decoder_set_seq_bias(dec, 0, table, until) != 0) return -1;
+    auto unbind = [&]() { GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, 0, -1, 0)); };
+    {
+        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
+        const Tensor logits = model.logits(input, 0);
+        const float* row = nullptr;
+        if (table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table, &row));
+        Tensor id({1}, kInt32);
+        const int32_t k = top_k, p = (int32_t)tokens.size();
+        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased((const float*)logits.device_ptr(), 1, logits.numel(), 0, row, 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
+        else GTEN_HIP_OK(gten_hip_sample_rows((const float*)logits.device_ptr(), 1, logits.numel(), 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
+        int32_t first = -1;
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
+        if (first == eos) { unbind(); return (int)tokens.size(); }
+        tokens.push_back(first);
+    }
+    const int n_first = (int)tokens.size();
+    const int max_new = n_predict - n_first;
+    if (max_new <= 0) { unbind(); return n_first; }
+    std::vector<int32_t> out((size_t)max_new);
+    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) { unbind(); return -1; }
+    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
+    GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
+    unbind();
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
     return (int)tokens.size();
 }

@@ -44,6 +44,10 @@ class GtenHost:
     ]
     # include/gten_host_sample.h (top-k sampling, host/capi_sample.cpp)
     SAMPLE_SYMBOLS = ["gten_host_model_generate_topk", "gten_host_batch_generate_topk", "gten_host_batch_serve_topk"]
+    # include/gten_host_bias.h (bias tables: constrained generation, host/capi_bias.cpp)
+    BIAS_SYMBOLS = ["gten_host_model_set_bias_table", "gten_host_batch_set_bias_table", "gten_host_batch_set_sampling", "gten_host_batch_set_seq_bias",
+                    "gten_host_batch_bias_info", "gten_host_model_set_seq_bias", "gten_host_model_set_sampling", "gten_host_model_step_logits", "gten_host_model_generate_biased", "gten_host_batch_generate_biased",
+                    "gten_host_batch_serve_biased"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -72,6 +76,18 @@ class GtenHost:
         self._bserve_topk = _sig(L, "gten_host_batch_serve_topk", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                       C.c_float, C.c_uint64])
         self._bgen_topk = _sig(L, "gten_host_batch_generate_topk", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, vp, vp, vp])
+        self._m_bias_table = _sig(L, "gten_host_model_set_bias_table", ci, [vp, ci, vp, vp, ci, C.c_float])
+        self._b_bias_table = _sig(L, "gten_host_batch_set_bias_table", ci, [vp, ci, vp, vp, ci, C.c_float])
+        self._b_set_sampling = _sig(L, "gten_host_batch_set_sampling", ci, [vp, ci, ci, C.c_float, C.c_uint64, C.c_uint32])
+        self._b_seq_bias = _sig(L, "gten_host_batch_set_seq_bias", ci, [vp, ci, ci, ci])
+        self._m_seq_bias = _sig(L, "gten_host_model_set_seq_bias", ci, [vp, ci, ci])
+        self._m_set_sampling = _sig(L, "gten_host_model_set_sampling", ci, [vp, ci, C.c_float, C.c_uint64, C.c_uint32])
+        self._m_step_logits = _sig(L, "gten_host_model_step_logits", ci, [vp, vp])
+        self._b_bias_info = _sig(L, "gten_host_batch_bias_info", ci, [vp, vp, vp])
+        self._generate_biased = _sig(L, "gten_host_model_generate_biased", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci])
+        self._bgen_biased = _sig(L, "gten_host_batch_generate_biased", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp])
+        self._bserve_biased = _sig(L, "gten_host_batch_serve_biased", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                          C.c_float, C.c_uint64, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
         self._score_many = _sig(L, "gten_host_model_score_many", ci, [vp, vp, vp, ci, vp, vp, vp])
@@ -153,6 +169,24 @@ class GtenHost:
     def tokenizer(self, path, vocab_size=32000):
         """host/tokenizer.h on a vocabulary file (host only: no GPU needed)"""
         return HostTokenizer(self, path, vocab_size)
+
+
+def bias_pairs(pairs=(), fill=0.0, allow=None):
+    """(ids int32[], values f32[], fill) of a bias table request (include/gten_hip_bias.h): `pairs` = [(id, value)] over `fill` for every
+    other id; allow=[ids] is the shorthand for "only these ids": fill -inf, the ids at 0 (pairs may still bias or ban some of them)."""
+    if allow is not None:
+        merged = {int(i): 0.0 for i in allow}
+        if len(merged) != len(list(allow)):
+            raise ValueError("allow lists an id twice")
+        for i, v in pairs:
+            if int(i) in merged:
+                merged[int(i)] = float(v)
+            else:
+                raise ValueError(f"pair id {i} is not among the allowed ids")
+        pairs, fill = list(merged.items()), -np.inf
+    ids = np.ascontiguousarray([int(i) for i, _ in pairs], dtype=np.int32)
+    values = np.ascontiguousarray([float(v) for _, v in pairs], dtype=np.float32)
+    return ids, values, float(fill)
 
 
 class HostTokenizer:
@@ -339,6 +373,45 @@ class HostModel:
             raise GtenHipError(f"generate_topk rc={total}")
         return buf[:total].copy()
 
+    def set_bias_table_rc(self, table, pairs=(), fill=0.0, allow=None):
+        """gten_host_model_set_bias_table's return code (0, or the refusal: the table keeps its contents)"""
+        ids, values, fill = bias_pairs(pairs, fill, allow)
+        return self.host._m_bias_table(self.h, int(table), ids.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p), len(ids), C.c_float(fill))
+
+    def set_bias_table(self, table, pairs=(), fill=0.0, allow=None):
+        """bias table `table` of this model's decoder := fill everywhere, then value at id for (id, value) in pairs; allow=[ids]:
+        only these ids (include/gten_host_bias.h)"""
+        rc = self.set_bias_table_rc(table, pairs, fill, allow)
+        if rc:
+            raise GtenHipError(f"set_bias_table rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def set_seq_bias_rc(self, table, until=0):
+        return self.host._m_seq_bias(self.h, int(table), int(until))
+
+    def set_sampling(self, top_k, temp=1.0, seed=0, stream=0):
+        """the request of the steps the caller drives (decode_step): top_k 0 = greedy"""
+        rc = self.host._m_set_sampling(self.h, int(top_k), float(temp), C.c_uint64(int(seed)), C.c_uint32(int(stream)))
+        if rc:
+            raise GtenHipError(f"set_sampling rc={rc}")
+
+    def step_logits(self):
+        """the logits row of the last decode step (f32 [n_vocab])"""
+        out = np.zeros(self.cfg.n_vocab, np.float32)
+        rc = self.host._m_step_logits(self.h, out.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise GtenHipError(f"step_logits rc={rc}")
+        return out
+
+    def generate_biased(self, prompt, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, table=-1, min_new=0):
+        """generate_topk() under bias table `table` (-1: none), which holds for the first min_new new ids (0: all); top_k 0: greedy"""
+        buf = np.zeros(max(max_tokens, len(prompt)), np.int32)
+        buf[: len(prompt)] = prompt
+        total = self.host._generate_biased(self.h, buf.ctypes.data_as(C.c_void_p), len(prompt), max_tokens, eos, int(top_k), float(temp),
+                                           C.c_uint64(int(seed)), C.c_uint32(int(stream)), int(table), int(min_new))
+        if total < 0:
+            raise GtenHipError(f"generate_biased rc={total}")
+        return buf[:total].copy()
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -496,6 +569,102 @@ class HostBatch:
                                         float(temp) if ts is None else 1.0, C.c_uint64(int(seed))), "batch_serve_topk")
         keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
         return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
+
+    def set_bias_table_rc(self, table, pairs=(), fill=0.0, allow=None):
+        """gten_host_batch_set_bias_table's return code (0, or the refusal: the table keeps its contents)"""
+        ids, values, fill = bias_pairs(pairs, fill, allow)
+        return self.host._b_bias_table(self.h, int(table), ids.ctypes.data_as(C.c_void_p), values.ctypes.data_as(C.c_void_p), len(ids), C.c_float(fill))
+
+    def set_bias_table(self, table, pairs=(), fill=0.0, allow=None):
+        """bias table `table` of the shared decoder := fill everywhere, then value at id for (id, value) in pairs; allow=[ids]: only
+        these ids (include/gten_host_bias.h)"""
+        rc = self.set_bias_table_rc(table, pairs, fill, allow)
+        if rc:
+            raise GtenHipError(f"batch_set_bias_table rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def set_sampling(self, seq, top_k, temp=1.0, seed=0, stream=0):
+        """sequence seq's request for the steps the caller drives (decode_step): top_k 0 = greedy"""
+        self._ck(self.host._b_set_sampling(self.h, int(seq), int(top_k), float(temp), C.c_uint64(int(seed)), C.c_uint32(int(stream))), "batch_set_sampling")
+
+    def set_seq_bias_rc(self, seq, table, until=0):
+        return self.host._b_seq_bias(self.h, int(seq), int(table), int(until))
+
+    def set_seq_bias(self, seq, table, until=0):
+        """sequence seq draws under `table` at positions < until (0: always); table -1 clears it"""
+        self._ck(self.set_seq_bias_rc(seq, table, until), "batch_set_seq_bias")
+
+    def bias_info(self):
+        """(number of tables, table per sequence [-1: none], until per sequence)"""
+        t, u = np.zeros(self.n_seq, np.int32), np.zeros(self.n_seq, np.int32)
+        n = self.host._b_bias_info(self.h, t.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p))
+        if n < 0:
+            raise GtenHipError(f"batch_bias_info rc={n}")
+        return n, t, u
+
+    @staticmethod
+    def _each(v, n, dt):
+        """(array or None, scalar): a per-item list, or one value for all"""
+        if v is None or np.isscalar(v):
+            return None, v
+        a = np.ascontiguousarray(v, dtype=dt)
+        assert len(a) == n
+        return a, None
+
+    def generate_biased(self, prompts, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, tables=None, min_new=None):
+        """generate_topk() with a request per sequence: top_k / temp a scalar or a list, tables[q] (-1 / None: no table) and
+        min_new[q] (0 / None: the table holds throughout)"""
+        assert len(prompts) == self.n_seq
+        mp = max(len(p) for p in prompts)
+        pr = np.zeros((self.n_seq, mp), np.int32)
+        npr = np.zeros(self.n_seq, np.int32)
+        for q, p in enumerate(prompts):
+            pr[q, : len(p)] = p
+            npr[q] = len(p)
+        (ks, k1), (ts, t1) = self._each(top_k, self.n_seq, np.int32), self._each(temp, self.n_seq, np.float32)
+        st, st1 = self._each(streams, self.n_seq, np.uint32)
+        if st is None and st1 is not None:
+            st = np.full(self.n_seq, st1, np.uint32)
+        tb, tb1 = self._each(tables, self.n_seq, np.int32)
+        mn, mn1 = self._each(min_new, self.n_seq, np.int32)
+        if tb is None and tb1 is not None:
+            tb = np.full(self.n_seq, tb1, np.int32)
+        if mn is None and mn1 is not None:
+            mn = np.full(self.n_seq, mn1, np.int32)
+        out = np.zeros((self.n_seq, max_tokens), np.int32)
+        tot = np.zeros(self.n_seq, np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self.host._bgen_biased(self.h, ptr(pr), ptr(npr), mp, max_tokens, eos, ptr(ks), ptr(ts), 0 if ks is not None else int(k1),
+                                        1.0 if ts is not None else float(t1), C.c_uint64(int(seed)), ptr(st), ptr(tb), ptr(mn), ptr(out), ptr(tot)),
+                 "batch_generate_biased")
+        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+
+    def serve_biased(self, prompts, max_tokens, eos, top_k, temp, seed, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None):
+        """serve_topk() with a bias table (-1: none) and a min_new (0: the table holds throughout) per prompt"""
+        n = len(prompts)
+        mp = max(len(p) for p in prompts)
+        width = max(max_tokens, mp)
+        pr = np.zeros((n, mp), np.int32)
+        npr = np.zeros(n, np.int32)
+        for j, p in enumerate(prompts):
+            pr[j, : len(p)] = p
+            npr[j] = len(p)
+        out = np.zeros((n, width), np.int32)
+        tot = np.zeros(n, np.int32)
+        st = np.zeros(9, np.float64)
+        each, _ = self._each(max_new_each, n, np.int32)
+        (ks, k1), (ts, t1) = self._each(top_k, n, np.int32), self._each(temp, n, np.float32)
+        tb, tb1 = self._each(tables, n, np.int32)
+        mn, mn1 = self._each(min_new, n, np.int32)
+        if tb is None and tb1 is not None:
+            tb = np.full(n, tb1, np.int32)
+        if mn is None and mn1 is not None:
+            mn = np.full(n, mn1, np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self.host._bserve_biased(self.h, ptr(pr), ptr(npr), n, mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out), ptr(tot),
+                                          ptr(st), len(st), ptr(ks), ptr(ts), 0 if ks is not None else int(k1), 1.0 if ts is not None else float(t1),
+                                          C.c_uint64(int(seed)), ptr(tb), ptr(mn)), "batch_serve_biased")
+        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
+        return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(keys, st.tolist()))
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""
