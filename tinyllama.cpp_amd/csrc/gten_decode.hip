@@ -26,6 +26,7 @@
 #include "gten_rt.h"
 #include "gten_hip_sample.h"
 #include "gten_hip_bias.h"
+#include "gten_hip_logprobs.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 
@@ -101,6 +102,8 @@ enum { EPI_RAW = 0, EPI_SILUMUL = 1, EPI_STAGE = 2, EPI_STAGE_FRAG = 3 };
 #include "gten_decode_attn_wide.h"
 #include "gten_decode_attn_hm.h"
 #include "gten_decode_sample.h"
+#include "gten_decode_logprobs.h"
+static_assert(LP_TOP == GTEN_HIP_LOGPROBS_TOP && sizeof(LpRecord) == GTEN_HIP_LOGPROBS_RECORD_BYTES, "gten_decode_logprobs.h and include/gten_hip_logprobs.h disagree");
 
 // --------------------------------------------------------------- host side
 
@@ -159,6 +162,13 @@ struct gten_hip_decoder {
     float* bias = nullptr;
     int n_bound = 0;                    // sequences with a table
     bool bias_on = false;
+    // log-probs of the generated ids (include/gten_hip_logprobs.h): [n_seq][max_ctx + 2] records indexed by n like `result`,
+    // made by the first request (lp_on: the graphs captured before are dropped once).  An asking sequence (SampleParam::lp1 > 0) makes the
+    // step end in the sampler launch like a sampling one does; from the first request on that launch is k_dec_sample_lp, which treats
+    // sequences that do not ask as k_dec_sample / k_dec_sample_b do.
+    LpRecord* lp = nullptr;
+    int n_asking = 0;                   // sequences with a log-prob request
+    bool lp_on = false;
     hipGraph_t s_graph = nullptr, s_graph_k = nullptr, s_graph_m[1 << DEC_MAX_LANES] = {}, s_graph_km[1 << DEC_MAX_LANES] = {};
     hipGraphExec_t s_exec = nullptr, s_exec_k = nullptr, s_exec_m[1 << DEC_MAX_LANES] = {}, s_exec_km[1 << DEC_MAX_LANES] = {};
     unsigned lane_mask = 0;             // lanes the NEXT enqueue takes (0: all)
@@ -206,13 +216,13 @@ struct gten_hip_decoder {
     hipEvent_t lane_fork = nullptr, lane_join[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
 };
 
-// the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples or has a bias table
-static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->n_sampling + dc->n_bound > 0; }
+// the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table or asks for log-probs
+static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->n_sampling + dc->n_bound + dc->n_asking > 0; }
 
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
     int n_seq;
-    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp;
+    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -229,6 +239,7 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     LaneBufs b;
     b.n_seq = (int)SL;
     b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->samp + o;
+    b.lp = dc->lp ? dc->lp + o * (d.max_ctx + 2) : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -634,7 +645,10 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
-    if (sampler_on(dc) && dc->bias_on)
+    if (sampler_on(dc) && dc->lp_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
+    else if (sampler_on(dc) && dc->bias_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
                    dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
     else if (sampler_on(dc))
@@ -781,7 +795,10 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    if (sampler_on(dc) && dc->bias_on)
+    if (sampler_on(dc) && dc->lp_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
+    else if (sampler_on(dc) && dc->bias_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
                    dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
     else if (sampler_on(dc))
@@ -1261,7 +1278,10 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     sf.act_q = b.stg_q; sf.act_d = b.stg_d; sf.act_sum = b.stg_sum; sf.act_f = b.stg_f;
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
-    if (sampler_on(dc) && dc->bias_on)
+    if (sampler_on(dc) && dc->lp_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
+                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias, b.lp, d.max_ctx + 2);
+    else if (sampler_on(dc) && dc->bias_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
                    b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias);
     else if (sampler_on(dc))
@@ -1660,7 +1680,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias, dc->lp,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
@@ -2540,10 +2560,11 @@ int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, floa
     SampleParam& p = dc->samp_host[(size_t)seq];
     dc->n_sampling += (top_k > 0 ? 1 : 0) - (p.top_k > 0 ? 1 : 0);
     const int table1 = p.table1;
-    const unsigned until = p.until;
+    const unsigned until = p.until, lp1 = p.lp1;
     p = SampleParam{};
     p.table1 = table1;           // (the bias binding is gten_hip_decoder_set_seq_bias's half of the request)
     p.until = until;
+    p.lp1 = lp1;                 // (and the log-prob request gten_hip_decoder_set_logprobs's)
     p.top_k = top_k;
     p.temp = top_k > 0 ? temp : 0.f;
     p.stream = stream_id;
@@ -2690,6 +2711,84 @@ int gten_hip_sample_rows_biased(const float* logits, int n_rows, int n_vocab, lo
     GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_b, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, bias, bias_stride,
                (const SampleRowParam*)g_rows_dev, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
     GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
+    return 0;
+}
+
+// ---- log-probs of the generated ids (include/gten_hip_logprobs.h, gten_decode_logprobs.h)
+int gten_hip_decoder_set_logprobs(gten_hip_decoder* dc, int seq, int n_top)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_set_logprobs: n_top %d outside [-1, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(n_top < 0 || !dc->persist_on, "decoder_set_logprobs: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    SampleParam& p = dc->samp_host[(size_t)seq];
+    if (n_top >= 0 && !dc->lp_on) {
+        // the first request of this decoder: the record buffer, and from now on its sampler launch is the one that writes records
+        const size_t bytes = (size_t)dc->n_seq * (size_t)(dc->d.max_ctx + 2) * sizeof(LpRecord);
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        if (!dc->lp) {
+            GTR_CHECK(hipMalloc((void**)&dc->lp, bytes));
+            GTR_CHECK(hipMemsetAsync(dc->lp, 0, bytes, stream()));
+            GTR_CHECK(hipStreamSynchronize(stream()));
+        }
+        GTR_CHECK(drop_graphs(dc));
+        dc->lp_on = true;
+    }
+    dc->n_asking += (n_top >= 0 ? 1 : 0) - (p.lp1 > 0u ? 1 : 0);
+    p.lp1 = (unsigned)(n_top + 1);
+    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_logprobs(gten_hip_decoder* dc, int seq, int n_from, int count, int n_top, float* logprob_host, int32_t* top_id_host,
+                              float* top_logprob_host)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(count >= 0 && n_from >= 0 && n_from + count <= dc->d.max_ctx + 2, "decoder_logprobs: positions [%d, %d + %d) outside [0, %d)", n_from, n_from,
+                count, dc->d.max_ctx + 2);
+    GTR_REQUIRE(dc->lp, "decoder_logprobs: no sequence of this decoder has asked for log-probs (gten_hip_decoder_set_logprobs)");
+    if (count == 0) return 0;
+    GTR_REQUIRE(logprob_host && (n_top == 0 || (top_id_host && top_logprob_host)), "decoder_logprobs: null output");
+    std::vector<LpRecord> rec((size_t)count);
+    GTR_CHECK(hipMemcpyAsync(rec.data(), dc->lp + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + n_from, rec.size() * sizeof(LpRecord), hipMemcpyDeviceToHost,
+                             stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    for (int i = 0; i < count; i++) {
+        logprob_host[i] = rec[(size_t)i].logprob;
+        for (int j = 0; j < n_top; j++) {
+            top_id_host[(size_t)i * n_top + j] = rec[(size_t)i].top_id[j];
+            top_logprob_host[(size_t)i * n_top + j] = rec[(size_t)i].top_logprob[j];
+        }
+    }
+    return persist_aborted(dc);
+}
+
+int gten_hip_decoder_logprobs_info(gten_hip_decoder* dc, int* top_cap, int32_t* n_top_host, const void** records, long long* seq_stride_bytes,
+                                   int* record_bytes)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_logprobs_info: null decoder");
+    if (top_cap) *top_cap = GTEN_HIP_LOGPROBS_TOP;
+    if (n_top_host) for (int q = 0; q < dc->n_seq; q++) n_top_host[q] = (int32_t)dc->samp_host[(size_t)q].lp1 - 1;
+    if (records) *records = dc->lp;
+    if (seq_stride_bytes) *seq_stride_bytes = (long long)(dc->d.max_ctx + 2) * (long long)sizeof(LpRecord);
+    if (record_bytes) *record_bytes = (int)sizeof(LpRecord);
+    return 0;
+}
+
+int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* ids, int n_top, float* logprob_out,
+                              int32_t* top_id_out, float* top_logprob_out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(n_vocab >= 1 && row_stride >= n_vocab, "row_top_logprobs: rows of %d logits (>= 1), stride %lld (>= n_vocab)", n_vocab, row_stride);
+    GTR_REQUIRE(n_rows >= 1 && n_rows <= 65535, "row_top_logprobs: %d rows outside [1, 65535]", n_rows);
+    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "row_top_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(logits && ids && logprob_out && (n_top == 0 || (top_id_out && top_logprob_out)), "row_top_logprobs: null argument");
+    GTR_LAUNCH(KT_DEC_SAMPLE, k_row_top_logprobs, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, ids, n_top, logprob_out, top_id_out,
+               top_logprob_out);
     return 0;
 }
 

@@ -20,7 +20,7 @@ struct SampleParam {             // one sequence's request (gten_hip_decoder_set
     unsigned seed_lo, seed_hi;
     int table1;                  // bias table + 1 (0: none), so that a zeroed request is "greedy, no table"
     unsigned until;              // the table holds for positions < until (0: for every position)
-    unsigned pad;
+    unsigned lp1;                // log-prob request n_top + 1 (0: none), read by k_dec_sample_lp only (gten_decode_logprobs.h)
 };
 struct SampleRowParam {          // one row of gten_hip_sample_rows; 16 bytes
     int top_k;

@@ -100,6 +100,9 @@ class GtenHip:
     # include/gten_hip_bias.h (bias tables: constrained generation on the device)
     BIAS_SYMBOLS = ["gten_hip_decoder_set_bias_table", "gten_hip_decoder_set_seq_bias", "gten_hip_sample_rows_biased", "gten_hip_decoder_bias_info"]
     BIAS_TABLES = 16                                             # GTEN_HIP_BIAS_TABLES
+    # include/gten_hip_logprobs.h (log-probs and top-N alternatives of the generated ids)
+    LOGPROBS_SYMBOLS = ["gten_hip_decoder_set_logprobs", "gten_hip_decoder_logprobs", "gten_hip_decoder_logprobs_info", "gten_hip_row_top_logprobs"]
+    LOGPROBS_TOP = 20                                            # GTEN_HIP_LOGPROBS_TOP
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
@@ -160,6 +163,10 @@ class GtenHip:
         self._set_bias_table = _sig(L, "gten_hip_decoder_set_bias_table", ci, [vp, ci, vp, vp, ci, C.c_float])
         self._set_seq_bias = _sig(L, "gten_hip_decoder_set_seq_bias", ci, [vp, ci, ci, ci])
         self._bias_info = _sig(L, "gten_hip_decoder_bias_info", ci, [vp, C.POINTER(ci), vp, vp, ci, C.POINTER(vp)])
+        self._set_logprobs = _sig(L, "gten_hip_decoder_set_logprobs", ci, [vp, ci, ci])
+        self._dec_logprobs = _sig(L, "gten_hip_decoder_logprobs", ci, [vp, ci, ci, ci, ci, vp, vp, vp])
+        self._logprobs_info = _sig(L, "gten_hip_decoder_logprobs_info", ci, [vp, C.POINTER(ci), vp, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(ci)])
+        self._row_top_logprobs = _sig(L, "gten_hip_row_top_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, ci, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
@@ -248,6 +255,29 @@ class GtenHip:
         self._check(self._row_logprobs(logits.ptr, n_rows, n_vocab, row_stride, t.ptr, out.ptr, out.ptr + 4 * n_rows, out.ptr + 8 * n_rows))
         got = out.download(np.uint8)
         return got[: 4 * n_rows].view(np.float32).copy(), got[4 * n_rows: 8 * n_rows].view(np.int32).copy(), got[8 * n_rows:].view(np.int32).copy()
+
+    def row_top_logprobs(self, logits, n_rows, n_vocab, row_stride, ids, n_top):
+        """gten_hip_row_top_logprobs (include/gten_hip_logprobs.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride elements;
+        ids int32[n_rows] the chosen ids (-1: none, a scalar is broadcast).  Returns (logprob f32[n_rows], top_id int32[n_rows][n_top],
+        top_logprob f32[n_rows][n_top]); entries from min(n_top, n_vocab) on are -1 / 0."""
+        t = DeviceBuffer.from_numpy(self, np.ascontiguousarray(np.broadcast_to(np.asarray(ids, dtype=np.int32), (n_rows,))))
+        w = max(n_top, 1)
+        out = DeviceBuffer(self, 4 * n_rows * (1 + 2 * w))
+        self._check(self._row_top_logprobs(logits.ptr, n_rows, n_vocab, row_stride, t.ptr, n_top, out.ptr, out.ptr + 4 * n_rows,
+                                           out.ptr + 4 * n_rows * (1 + w)))
+        self.sync()
+        got = out.download(np.uint8)
+        lp = got[: 4 * n_rows].view(np.float32).copy()
+        ti = got[4 * n_rows: 4 * n_rows * (1 + w)].view(np.int32).reshape(n_rows, w)[:, :n_top].copy()
+        tl = got[4 * n_rows * (1 + w):].view(np.float32).reshape(n_rows, w)[:, :n_top].copy()
+        return lp, ti, tl
+
+    def row_top_logprobs_rc(self, logits, n_rows, n_vocab, row_stride, n_top):
+        """the return code of one gten_hip_row_top_logprobs call (argument checks); ids / outputs are scratch words"""
+        buf = DeviceBuffer(self, 4 * max(n_rows, 1) * 48)
+        buf.zero()
+        r = 4 * max(n_rows, 1)
+        return self._row_top_logprobs(logits.ptr, n_rows, n_vocab, row_stride, buf.ptr, n_top, buf.ptr + r, buf.ptr + 2 * r, buf.ptr + 24 * r)
 
     def row_logprobs_rc(self, logits, n_rows, n_vocab, row_stride):
         """the return code of one gten_hip_row_logprobs call (argument checks); targets / outputs are scratch words"""

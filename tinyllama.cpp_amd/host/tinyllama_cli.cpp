@@ -5,7 +5,8 @@
 // tokenizer.bin), --seed for the top-k sampler, --ids to print token ids instead of text (tests); greedy sampling runs
 // with the sampler on the device (gten::greedy_generate); --score PATH prints the log-likelihood of a text file
 // (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
-// of the model's decoder (include/gten_hip_bias.h), in both generation modes.
+// of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
+// most likely alternatives (include/gten_hip_logprobs.h) after the text.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -46,6 +47,8 @@ Optional args.
 --ban ID[,ID...] :   token ids that are never generated (greedy and top-k alike).
 --allow ID[,ID...] : the only token ids that may be generated. With --ban: those of them that are not banned.
 --min-new N : --ban / --allow hold for the first N generated ids only; N must be gte 1. [default: for all of them]
+--logprobs N : after the text, one line per generated id: `id logprob` and the N most likely ids of its step as `id:logprob`,
+           from the unconstrained, untempered logits. N must be gte 0 and lte 20. Combines with --ban / --allow / --min-new.
 )";
 
 struct Options {
@@ -57,6 +60,7 @@ struct Options {
     uint64_t seed = 0;
     std::vector<int32_t> ban, allow;         // --ban / --allow (bias table 0)
     int min_new = 0;
+    int logprobs = -1;                       // --logprobs N (-1: off)
     bool constrained() const { return !ban.empty() || !allow.empty(); }
 };
 
@@ -115,6 +119,29 @@ static void run_constrained(const Options& o, std::string prompt, TinyLlama& mod
     }
     for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
     (o.ids ? std::cout : std::cerr) << '\n';
+}
+
+// either generation mode with --logprobs (under table 0 when constrained): the ids, then one record line per generated id
+static void run_logprobs(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
+{
+    std::vector<int> enc = tok.encode(prompt);
+    std::vector<int32_t> tokens(enc.begin(), enc.end()), top_id;
+    std::vector<float> logprob, top_lp;
+    const size_t n_prompt = tokens.size();
+    if (logprobs_generate(model, tokens, o.n_predict, tok.eos, o.greedy ? 0 : o.topk, o.temp, seed, turn, o.constrained() ? 0 : -1, o.min_new, o.logprobs,
+                          &logprob, &top_id, &top_lp) < 0) {
+        std::cerr << "error: " << gten_hip_last_error() << "\n";
+        std::exit(EXIT_FAILURE);
+    }
+    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
+    (o.ids ? std::cout : std::cerr) << '\n';
+    std::cout.flush();
+    for (size_t i = n_prompt; i < tokens.size(); i++) {
+        std::printf("%d %.9g", tokens[i], logprob[i]);
+        for (int a = 0; a < o.logprobs; a++) std::printf(" %d:%.9g", top_id[i * (size_t)o.logprobs + a], top_lp[i * (size_t)o.logprobs + a]);
+        std::printf("\n");
+    }
+    std::fflush(stdout);
 }
 
 // greedy: the prompt as in the reference, every later id from the device-side sampler
@@ -231,6 +258,14 @@ int main(int argc, char const* argv[])
             try { v = std::stoi(value("min-new")); } catch (...) { std::cerr << "Invalid min-new value.\n"; return -1; }
             if (v < 1 || v > 2048) { std::cerr << "min-new must be gte 1 and lte 2048.\n"; return -1; }
             o.min_new = v;
+        } else if (arg == "--logprobs") {
+            const std::string text = value("logprobs");
+            size_t used = 0;
+            int v = -1;
+            try { v = std::stoi(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size()) { std::cerr << "Invalid logprobs value.\n"; return -1; }
+            if (v < 0 || v > GTEN_HIP_LOGPROBS_TOP) { std::cerr << "logprobs must be gte 0 and lte " << GTEN_HIP_LOGPROBS_TOP << ".\n"; return -1; }
+            o.logprobs = v;
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
@@ -269,7 +304,8 @@ int main(int argc, char const* argv[])
     if (o.constrained()) set_constraint(o, model);
     uint32_t turn = 0;
     auto answer = [&](const std::string& prompt) {
-        if (o.constrained()) run_constrained(o, prompt, model, tokenizer, seed, turn++);
+        if (o.logprobs >= 0) run_logprobs(o, prompt, model, tokenizer, seed, turn++);
+        else if (o.constrained()) run_constrained(o, prompt, model, tokenizer, seed, turn++);
         else if (o.greedy) run_greedy(o, prompt, model, tokenizer);
         else run_topk(o, prompt, model, tokenizer, seed, turn++);
     };

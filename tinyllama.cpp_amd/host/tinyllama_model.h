@@ -27,6 +27,7 @@
 #include "../gten/gten.h"
 #include "../../include/gten_hip_sample.h"
 #include "../../include/gten_hip_bias.h"
+#include "../../include/gten_hip_logprobs.h"
 #include "../../include/gten_hip_score.h"
 #include "synth.h"
 
@@ -1013,7 +1014,7 @@ public:
     // prompt j's request (top_k[j], temp[j], seed, stream j) draws its first id from the prompt's logits on the device and is
     // set on whichever slot takes the prompt -- the ids depend on (seed, j) and the logits only, not on the slot or schedule.
     struct GreedyServe {
-        static constexpr bool kSampled = false, kBiased = false;
+        static constexpr bool kSampled = false, kBiased = false, kLogprobs = false;
         int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int) { return b.prefill(c, row); }
         void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>&,
                   std::vector<int>* first)
@@ -1025,7 +1026,7 @@ public:
         uint64_t seed = 0;
     };
     struct SampledServe {
-        static constexpr bool kSampled = true, kBiased = false;
+        static constexpr bool kSampled = true, kBiased = false, kLogprobs = false;
         const int32_t* top_k_each;       // per prompt (null: top_k_all)
         const float* temp_each;          // per prompt (null: temp_all)
         int top_k_all;
@@ -1051,7 +1052,7 @@ public:
     // first min_new new ids (0: for all of them).  The first id is drawn from the prompt's logits under the same table; the binding
     // is set on whichever slot takes the prompt, beside its request, and every slot is unbound again when the queue is done.
     struct BiasedServe {
-        static constexpr bool kSampled = true, kBiased = true;
+        static constexpr bool kSampled = true, kBiased = true, kLogprobs = false;
         const int32_t* top_k_each;       // per prompt (null: top_k_all)
         const float* temp_each;          // per prompt (null: temp_all)
         int top_k_all;
@@ -1089,6 +1090,96 @@ public:
         }
         void bind(int q, int j, int n_prompt) const { GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, q, table(j), table(j) >= 0 ? until(j, n_prompt) : 0)); }
     };
+    // BiasedServe with log-prob records (include/gten_hip_logprobs.h): prompt j asks with n_top(j) (-1: it does not).
+    // The first id's record comes from gten_hip_row_top_logprobs on the prompt's logits row, the row the id is drawn from; the request
+    // is set on whichever slot takes the prompt; the slot's records are read when the prompt ends or moves (collect), before the slot
+    // is started again; every slot's request is cleared when the queue is done.  Rows of the outputs are `row_len` positions long.
+    struct LpServe : BiasedServe {
+        static constexpr bool kLogprobs = true;
+        const int32_t* n_top_each;       // per prompt (null: nobody asks)
+        int n_top_max, row_len;
+        float* logprob;                  // [prompts][row_len]
+        int32_t* top_id;                 // [prompts][row_len][n_top_max]
+        float* top_lp;
+        void* scratch = nullptr;         // device: kPreMax first-id records (logprob | ids | logprobs)
+        int scratch_rows = 0;
+        LpServe(const BiasedServe& b, const int32_t* n_top_each_, int n_top_max_, int row_len_, float* logprob_, int32_t* top_id_, float* top_lp_)
+            : BiasedServe(b), n_top_each{n_top_each_}, n_top_max{n_top_max_}, row_len{row_len_}, logprob{logprob_}, top_id{top_id_}, top_lp{top_lp_} {}
+        LpServe(const LpServe&) = delete;
+        ~LpServe() { if (scratch) gten_hip_free(scratch); }
+        int n_top(int j) const { return n_top_each ? n_top_each[j] : -1; }
+        size_t rec_bytes() const { return sizeof(float) + (size_t)GTEN_HIP_LOGPROBS_TOP * (sizeof(int32_t) + sizeof(float)); }
+        uint8_t* rec(int k)
+        {
+            return (uint8_t*)scratch + (size_t)k * rec_bytes();
+        }
+        void ensure(int rows)
+        {
+            if (rows <= scratch_rows) return;
+            if (scratch) GTEN_HIP_OK(gten_hip_free(scratch));
+            scratch = nullptr;
+            GTEN_HIP_OK(gten_hip_malloc(&scratch, (size_t)rows * rec_bytes()));
+            scratch_rows = rows;
+        }
+        // the record of the id just drawn into `id` (device) from row lg, into scratch record k (same stream, behind the draw)
+        void first_record(int k, int j, const float* lg, int n, const int32_t* id)
+        {
+            if (n_top(j) < 0) return;
+            uint8_t* r = rec(k);
+            GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n, n, id, n_top(j), (float*)r, (int32_t*)(r + 4), (float*)(r + 4 + 4 * GTEN_HIP_LOGPROBS_TOP)));
+        }
+        // scratch record k -> prompt j's outputs at position pos (the stream has been waited for: the id was read back)
+        void first_store(int k, int j, int pos)
+        {
+            if (n_top(j) < 0 || pos >= row_len) return;
+            std::vector<uint8_t> h(rec_bytes());
+            GTEN_HIP_OK(gten_hip_memcpy_d2h(h.data(), rec(k), h.size()));
+            const int m = std::min(n_top(j), n_top_max);
+            std::memcpy(&logprob[(size_t)j * row_len + pos], h.data(), sizeof(float));
+            if (m > 0) {
+                std::memcpy(top_id + ((size_t)j * row_len + pos) * n_top_max, h.data() + 4, (size_t)m * sizeof(int32_t));
+                std::memcpy(top_lp + ((size_t)j * row_len + pos) * n_top_max, h.data() + 4 + 4 * GTEN_HIP_LOGPROBS_TOP, (size_t)m * sizeof(float));
+            }
+        }
+        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
+        {
+            ensure(1);
+            const int id = b.prefill_picked(c, row, [&](int, const float* lg, int n, int32_t* out) {
+                this->draw(j, lg, n, (int32_t)row.size(), out);
+                first_record(0, j, lg, n, out);
+            });
+            first_store(0, j, (int)row.size());
+            return id;
+        }
+        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
+                  std::vector<int>* first)
+        {
+            ensure((int)sets.size());
+            std::vector<float*> lo((size_t)sets.size(), nullptr);
+            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
+                this->draw(js[(size_t)k], lg, n, (int32_t)ps[(size_t)k]->size(), out);
+                first_record(k, js[(size_t)k], lg, n, out);
+            });
+            for (size_t k = 0; k < js.size(); k++) first_store((int)k, js[k], (int)ps[k]->size());
+        }
+        void ask(int q, int j) const { GTEN_HIP_OK(gten_hip_decoder_set_logprobs(this->dec, q, n_top(j))); }
+        // slot q's records of positions [from, from + count) are prompt j's
+        void collect(int q, int j, int from, int count)
+        {
+            if (n_top(j) < 0) return;
+            count = std::min(count, row_len - from);
+            if (count <= 0) return;
+            const int m = std::min(n_top(j), n_top_max);
+            std::vector<int32_t> ids((size_t)count * (size_t)std::max(m, 1));
+            std::vector<float> lps((size_t)count * (size_t)std::max(m, 1));
+            GTEN_HIP_OK(gten_hip_decoder_logprobs(this->dec, q, from, count, m, &logprob[(size_t)j * row_len + from], ids.data(), lps.data()));
+            for (int i = 0; i < count && m > 0; i++) {
+                std::memcpy(top_id + ((size_t)j * row_len + from + i) * n_top_max, ids.data() + (size_t)i * m, (size_t)m * sizeof(int32_t));
+                std::memcpy(top_lp + ((size_t)j * row_len + from + i) * n_top_max, lps.data() + (size_t)i * m, (size_t)m * sizeof(float));
+            }
+        }
+        void clear(int q) const { GTEN_HIP_OK(gten_hip_decoder_set_logprobs(this->dec, q, -1)); }
+    };
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
                           std::vector<std::vector<int32_t>>* out, int max_new, const int32_t* max_new_each, Pick& pick)
@@ -1101,6 +1192,7 @@ public:
         // per slot: prompt index (-1: free), next step, last step, the cache set it decodes on (-1: none)
         std::vector<int> job((size_t)S, -1), cur((size_t)S, 0), last((size_t)S, 0), set_of((size_t)S, -1);
         std::vector<char> live((size_t)S, 0);
+        std::vector<int> lp_from((size_t)S, 0);                            // (Pick::kLogprobs) the first position whose record slot q has not handed over
         // CACHE SETS (round 4).  A prompt is processed onto a free cache set, not onto a free slot: besides the S sets the
         // sequences own there are `spare` more, so that prompts are ready BEFORE the slots that will take them end -- a slot
         // that ends in a harvest gets a ready prompt's set bound (gten_hip_decoder_slot_bind) and joins the very next slice
@@ -1262,6 +1354,7 @@ public:
                     ap_seq.clear(); ap_first.clear(); ap_last.clear();
                     for (int q = emptiest * lane_rows; q < (emptiest + 1) * lane_rows; q++) {
                         if (!live[(size_t)q]) continue;
+                        if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], cur[(size_t)q] - lp_from[(size_t)q]);
                         ready.push_back(Ready{job[(size_t)q], set_of[(size_t)q], cur[(size_t)q], last[(size_t)q]});
                         ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);
                         set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
@@ -1290,6 +1383,7 @@ public:
                     if constexpr (Pick::kSampled)
                         GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, pick.top_k(r.j), pick.temp(r.j), pick.seed, (uint32_t)r.j));
                     if constexpr (Pick::kBiased) pick.bind(q, r.j, (int)prompts[(size_t)r.j].size());      // (travels with the request: also when a sequence moves in the tail)
+                    if constexpr (Pick::kLogprobs) { pick.ask(q, r.j); lp_from[(size_t)q] = r.cur; }
                     live[(size_t)q] = 1; n_live++;
                 }
             }
@@ -1333,6 +1427,8 @@ public:
                 }
                 cur[(size_t)q] += got;
                 if (stop || cur[(size_t)q] > last[(size_t)q]) {
+                    // (the records of the ids kept: an eos and what follows it are not stored)
+                    if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], (int)row.size() - lp_from[(size_t)q]);
                     ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);                  // parked, all of them at once below
                     pool.push_back(set_of[(size_t)q]);
                     set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
@@ -1385,6 +1481,8 @@ public:
             for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, 0, 0.f, 0, 0));     // every slot greedy again
         if constexpr (Pick::kBiased)
             for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec_, q, -1, 0));                // ... and unbound
+        if constexpr (Pick::kLogprobs)
+            for (int q = 0; q < S; q++) pick.clear(q);                                                             // ... and nobody asks
         return st;
     }
 
@@ -1590,6 +1688,72 @@ inline int biased_generate(TinyLlama& model, std::vector<int32_t>& tokens, const
     unbind();
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
     return (int)tokens.size();
+}
+
+// biased_generate that also reports every new id's log-prob and its n_top alternatives (include/gten_hip_logprobs.h):
+// logprob [tokens.size()], top_id / top_lp [tokens.size()][n_top], aligned with the ids (prompt positions: 0 / -1).  The first new
+// id's record comes from gten_hip_row_top_logprobs on the prompt's logits row, the row the id is drawn from; the later ones are the
+// decoder's records.  Request, binding and log-prob request are dropped again afterwards.  -1 when the decoder refuses.
+inline int logprobs_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
+                             uint64_t seed, uint32_t stream, int table, int min_new, int n_top, std::vector<float>* logprob,
+                             std::vector<int32_t>* top_id, std::vector<float>* top_lp)
+{
+    const size_t W = (size_t)n_top;
+    auto size_outputs = [&]() {
+        logprob->resize(tokens.size(), 0.f);
+        top_id->resize(tokens.size() * W, -1);
+        top_lp->resize(tokens.size() * W, 0.f);
+    };
+    logprob->clear(); top_id->clear(); top_lp->clear();
+    size_outputs();
+    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
+    gten_hip_decoder* dec = model.decoder_handle();
+    const int until = (table >= 0 && min_new > 0) ? (int)tokens.size() + min_new : 0;
+    if (gten_hip_decoder_set_seq_bias(dec, 0, table, until) != 0) return -1;
+    auto drop = [&]() {
+        GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
+        GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, 0, -1, 0));
+        GTEN_HIP_OK(gten_hip_decoder_set_logprobs(dec, 0, -1));
+    };
+    if (gten_hip_decoder_set_logprobs(dec, 0, n_top) != 0) { drop(); return -1; }
+    {
+        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
+        const Tensor logits = model.logits(input, 0);
+        const float* lg = (const float*)logits.device_ptr();
+        const float* row = nullptr;
+        if (table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table, &row));
+        Tensor id({1}, kInt32), rec_lp({1}, kFloat32), rec_id({GTEN_HIP_LOGPROBS_TOP}, kInt32), rec_tl({GTEN_HIP_LOGPROBS_TOP}, kFloat32);
+        int32_t* id_dev = (int32_t*)id.device_ptr_mut();
+        const int32_t k = top_k, p = (int32_t)tokens.size();
+        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, logits.numel(), 0, row, 0, &k, &temp, seed, &stream, &p, id_dev));
+        else GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, logits.numel(), 0, &k, &temp, seed, &stream, &p, id_dev));
+        GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, logits.numel(), logits.numel(), id_dev, n_top, (float*)rec_lp.device_ptr_mut(),
+                                              (int32_t*)rec_id.device_ptr_mut(), (float*)rec_tl.device_ptr_mut()));
+        int32_t first = -1;
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
+        if (first == eos) { drop(); return (int)tokens.size(); }
+        tokens.push_back(first);
+        size_outputs();
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&logprob->back(), rec_lp.device_ptr(), sizeof(float)));
+        if (n_top > 0) {
+            GTEN_HIP_OK(gten_hip_memcpy_d2h(top_id->data() + (tokens.size() - 1) * W, rec_id.device_ptr(), W * sizeof(int32_t)));
+            GTEN_HIP_OK(gten_hip_memcpy_d2h(top_lp->data() + (tokens.size() - 1) * W, rec_tl.device_ptr(), W * sizeof(float)));
+        }
+    }
+    const int n_first = (int)tokens.size();
+    const int max_new = n_predict - n_first;
+    if (max_new <= 0) { drop(); return n_first; }
+    std::vector<int32_t> out((size_t)max_new);
+    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) { drop(); return -1; }
+    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
+    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
+    size_outputs();
+    int rc = 0;
+    if (got > 0)
+        rc = gten_hip_decoder_logprobs(dec, 0, n_first, got, n_top, logprob->data() + n_first, top_id->data() + (size_t)n_first * W,
+                                       top_lp->data() + (size_t)n_first * W);
+    drop();
+    return rc ? -1 : (int)tokens.size();
 }
 
 } // namespace gten

@@ -48,6 +48,10 @@ class GtenHost:
     BIAS_SYMBOLS = ["gten_host_model_set_bias_table", "gten_host_batch_set_bias_table", "gten_host_batch_set_sampling", "gten_host_batch_set_seq_bias",
                     "gten_host_batch_bias_info", "gten_host_model_set_seq_bias", "gten_host_model_set_sampling", "gten_host_model_step_logits", "gten_host_model_generate_biased", "gten_host_batch_generate_biased",
                     "gten_host_batch_serve_biased"]
+    # include/gten_host_logprobs.h (log-probs and top-N alternatives of the generated ids, host/capi_logprobs.cpp)
+    LOGPROBS_SYMBOLS = ["gten_host_model_set_logprobs", "gten_host_batch_set_logprobs", "gten_host_model_logprobs", "gten_host_batch_logprobs",
+                        "gten_host_model_generate_lp", "gten_host_batch_generate_lp", "gten_host_batch_serve_lp", "gten_host_model_score_top"]
+    LOGPROBS_TOP = 20                                            # GTEN_HIP_LOGPROBS_TOP
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -88,6 +92,16 @@ class GtenHost:
         self._bgen_biased = _sig(L, "gten_host_batch_generate_biased", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp])
         self._bserve_biased = _sig(L, "gten_host_batch_serve_biased", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                           C.c_float, C.c_uint64, vp, vp])
+        self._m_set_lp = _sig(L, "gten_host_model_set_logprobs", ci, [vp, ci])
+        self._b_set_lp = _sig(L, "gten_host_batch_set_logprobs", ci, [vp, ci, ci])
+        self._m_lp = _sig(L, "gten_host_model_logprobs", ci, [vp, ci, ci, ci, vp, vp, vp])
+        self._b_lp = _sig(L, "gten_host_batch_logprobs", ci, [vp, ci, ci, ci, ci, vp, vp, vp])
+        self._generate_lp = _sig(L, "gten_host_model_generate_lp", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci, vp, vp, vp])
+        self._bgen_lp = _sig(L, "gten_host_batch_generate_lp", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
+                                                                    vp, ci, vp, vp, vp])
+        self._bserve_lp = _sig(L, "gten_host_batch_serve_lp", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                  C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp])
+        self._score_top = _sig(L, "gten_host_model_score_top", ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
         self._score_many = _sig(L, "gten_host_model_score_many", ci, [vp, vp, vp, ci, vp, vp, vp])
@@ -276,12 +290,32 @@ class HostModel:
                               lp.ctypes.data_as(C.c_void_p), rk.ctypes.data_as(C.c_void_p))
         return rc, lp, rk
 
-    def score(self, tokens, start_pos=0, targets=None):
-        """(log-probs, ranks) of rows [start_pos, n): see score_rc"""
+    def score(self, tokens, start_pos=0, targets=None, n_top=None):
+        """(log-probs, ranks) of rows [start_pos, n): see score_rc.  With n_top (0 .. 20) also the top-N of every scored row:
+        (log-probs, ranks, top ids int32[rows][n_top], top log-probs f32[rows][n_top]) (gten_host_model_score_top)"""
+        if n_top is not None:
+            return self.score_top(tokens, start_pos, targets, n_top)
         rc, lp, rk = self.score_rc(tokens, start_pos, targets)
         if rc:
             raise GtenHipError(f"score rc={rc}")
         return lp, rk
+
+    def score_top(self, tokens, start_pos=0, targets=None, n_top=0):
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        rows = max(len(tokens) - start_pos, 1)
+        if targets is None:
+            targets = np.append(tokens[start_pos + 1:], -1)
+        targets = np.ascontiguousarray(targets, dtype=np.int32)
+        if len(targets) < rows:
+            targets = np.append(targets, np.full(rows - len(targets), -1, np.int32))
+        lp, rk = np.zeros(rows, np.float32), np.zeros(rows, np.int32)
+        ti, tl = np.full((rows, max(int(n_top), 0)), -1, np.int32), np.zeros((rows, max(int(n_top), 0)), np.float32)
+        rc = self.host._score_top(self.h, tokens.ctypes.data_as(C.c_void_p), len(tokens), start_pos, targets.ctypes.data_as(C.c_void_p), int(n_top),
+                                  lp.ctypes.data_as(C.c_void_p), rk.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                                  tl.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise GtenHipError(f"score_top rc={rc}")
+        return lp, rk, ti, tl
 
     def logits_all(self, tokens, start_pos=0):
         """f32 [n - start_pos][n_vocab]: the lm_head of every computed row (gten_host_model_logits_all)"""
@@ -411,6 +445,38 @@ class HostModel:
         if total < 0:
             raise GtenHipError(f"generate_biased rc={total}")
         return buf[:total].copy()
+
+    def set_logprobs_rc(self, n_top):
+        return self.host._m_set_lp(self.h, int(n_top))
+
+    def set_logprobs(self, n_top):
+        """the decoder's steps commit a log-prob record with n_top alternatives from now on (-1: off; include/gten_host_logprobs.h)"""
+        rc = self.set_logprobs_rc(n_top)
+        if rc:
+            raise GtenHipError(f"set_logprobs rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def logprobs(self, n_from, count, n_top):
+        """(logprob f32[count], top_id int32[count][n_top], top_logprob f32[count][n_top]) of positions [n_from, n_from + count)"""
+        lp, ti, tl = np.zeros(count, np.float32), np.full((count, n_top), -1, np.int32), np.zeros((count, n_top), np.float32)
+        rc = self.host._m_lp(self.h, int(n_from), int(count), int(n_top), lp.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                             tl.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise GtenHipError(f"logprobs rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return lp, ti, tl
+
+    def generate_logprobs(self, prompt, max_tokens, n_top, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, table=-1, min_new=0):
+        """generate_biased() plus every new id's record: (ids, logprob f32[len(ids)], top_id int32[len(ids)][n_top], top_logprob);
+        prompt positions hold 0 / -1"""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        lp, ti, tl = np.zeros(width, np.float32), np.full((width, n_top), -1, np.int32), np.zeros((width, n_top), np.float32)
+        total = self.host._generate_lp(self.h, buf.ctypes.data_as(C.c_void_p), len(prompt), max_tokens, eos, int(top_k), float(temp),
+                                       C.c_uint64(int(seed)), C.c_uint32(int(stream)), int(table), int(min_new), int(n_top),
+                                       lp.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p))
+        if total < 0:
+            raise GtenHipError(f"generate_logprobs rc={total}: {self.host.hip._err().decode(errors='replace')}")
+        return buf[:total].copy(), lp[:total].copy(), ti[:total].copy(), tl[:total].copy()
 
     def close(self):
         if self.h:
@@ -665,6 +731,97 @@ class HostBatch:
                                           C.c_uint64(int(seed)), ptr(tb), ptr(mn)), "batch_serve_biased")
         keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
         return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(keys, st.tolist()))
+
+    def set_logprobs_rc(self, seq, n_top):
+        return self.host._b_set_lp(self.h, int(seq), int(n_top))
+
+    def set_logprobs(self, seq, n_top):
+        """sequence seq's steps commit a log-prob record with n_top alternatives from now on (-1: off; include/gten_host_logprobs.h)"""
+        rc = self.set_logprobs_rc(seq, n_top)
+        if rc:
+            raise GtenHipError(f"batch_set_logprobs rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def logprobs(self, seq, n_from, count, n_top):
+        """(logprob f32[count], top_id int32[count][n_top], top_logprob f32[count][n_top]) of sequence seq's positions [n_from, n_from + count)"""
+        lp, ti, tl = np.zeros(count, np.float32), np.full((count, n_top), -1, np.int32), np.zeros((count, n_top), np.float32)
+        rc = self.host._b_lp(self.h, int(seq), int(n_from), int(count), int(n_top), lp.ctypes.data_as(C.c_void_p), ti.ctypes.data_as(C.c_void_p),
+                             tl.ctypes.data_as(C.c_void_p))
+        if rc:
+            raise GtenHipError(f"batch_logprobs rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return lp, ti, tl
+
+    @staticmethod
+    def _n_tops(n_top, n):
+        """(int32[n] or None, width of the outputs) of a per-item n_top request (a scalar: for all; None / -1: that item does not ask)"""
+        if n_top is None:
+            return None, 0
+        a = np.full(n, n_top, np.int32) if np.isscalar(n_top) else np.ascontiguousarray([-1 if v is None else v for v in n_top], dtype=np.int32)
+        assert len(a) == n
+        return a, max(int(a.max()), 0)
+
+    def generate_logprobs(self, prompts, max_tokens, n_top, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, tables=None, min_new=None):
+        """generate_biased() plus the records of the sequences that ask (n_top a scalar or a list, -1 / None: not this one): returns
+        (ids per sequence, logprob [n_seq][max_tokens], top_id [n_seq][max_tokens][max n_top], top_logprob), aligned with the ids"""
+        assert len(prompts) == self.n_seq
+        mp = max(len(p) for p in prompts)
+        pr = np.zeros((self.n_seq, mp), np.int32)
+        npr = np.zeros(self.n_seq, np.int32)
+        for q, p in enumerate(prompts):
+            pr[q, : len(p)] = p
+            npr[q] = len(p)
+        (ks, k1), (ts, t1) = self._each(top_k, self.n_seq, np.int32), self._each(temp, self.n_seq, np.float32)
+        st, st1 = self._each(streams, self.n_seq, np.uint32)
+        if st is None and st1 is not None:
+            st = np.full(self.n_seq, st1, np.uint32)
+        tb, tb1 = self._each(tables, self.n_seq, np.int32)
+        mn, mn1 = self._each(min_new, self.n_seq, np.int32)
+        if tb is None and tb1 is not None:
+            tb = np.full(self.n_seq, tb1, np.int32)
+        if mn is None and mn1 is not None:
+            mn = np.full(self.n_seq, mn1, np.int32)
+        nt, width = self._n_tops(n_top, self.n_seq)
+        out = np.zeros((self.n_seq, max_tokens), np.int32)
+        tot = np.zeros(self.n_seq, np.int32)
+        lp = np.zeros((self.n_seq, max_tokens), np.float32)
+        ti, tl = np.full((self.n_seq, max_tokens, width), -1, np.int32), np.zeros((self.n_seq, max_tokens, width), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self.host._bgen_lp(self.h, ptr(pr), ptr(npr), mp, max_tokens, eos, ptr(ks), ptr(ts), 0 if ks is not None else int(k1),
+                                    1.0 if ts is not None else float(t1), C.c_uint64(int(seed)), ptr(st), ptr(tb), ptr(mn), ptr(out), ptr(tot),
+                                    ptr(nt), width, ptr(lp), ptr(ti), ptr(tl)), "batch_generate_lp")
+        return [out[q, : tot[q]].copy() for q in range(self.n_seq)], lp, ti, tl
+
+    def serve_logprobs(self, prompts, max_tokens, eos, top_k, temp, seed, n_top, tables=None, min_new=None, slice_steps=16, max_new=0,
+                       max_new_each=None):
+        """serve_biased() plus the records of the prompts that ask (n_top per prompt, -1 / None: not this one): returns
+        (ids per prompt, stats, logprob [n][width], top_id [n][width][max n_top], top_logprob), width = max(max_tokens, longest prompt)"""
+        n = len(prompts)
+        mp = max(len(p) for p in prompts)
+        width = max(max_tokens, mp)
+        pr = np.zeros((n, mp), np.int32)
+        npr = np.zeros(n, np.int32)
+        for j, p in enumerate(prompts):
+            pr[j, : len(p)] = p
+            npr[j] = len(p)
+        out = np.zeros((n, width), np.int32)
+        tot = np.zeros(n, np.int32)
+        st = np.zeros(9, np.float64)
+        each, _ = self._each(max_new_each, n, np.int32)
+        (ks, k1), (ts, t1) = self._each(top_k, n, np.int32), self._each(temp, n, np.float32)
+        tb, tb1 = self._each(tables, n, np.int32)
+        mn, mn1 = self._each(min_new, n, np.int32)
+        if tb is None and tb1 is not None:
+            tb = np.full(n, tb1, np.int32)
+        if mn is None and mn1 is not None:
+            mn = np.full(n, mn1, np.int32)
+        nt, tw = self._n_tops(n_top, n)
+        lp = np.zeros((n, width), np.float32)
+        ti, tl = np.full((n, width, tw), -1, np.int32), np.zeros((n, width, tw), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self.host._bserve_lp(self.h, ptr(pr), ptr(npr), n, mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out), ptr(tot),
+                                      ptr(st), len(st), ptr(ks), ptr(ts), 0 if ks is not None else int(k1), 1.0 if ts is not None else float(t1),
+                                      C.c_uint64(int(seed)), ptr(tb), ptr(mn), ptr(nt), tw, ptr(lp), ptr(ti), ptr(tl)), "batch_serve_lp")
+        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
+        return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(keys, st.tolist())), lp, ti, tl
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""The cost of log-prob records on the device, one JSON line on stdout
+(tools/logprobs_cost.py [--parent-root DIR] [--out profiles/logprobs_cost.json]).
+
+Full-size TinyLlama, q4 weights, synthetic.  For 1, 64 and 256 sequences: ms per sampled decode step (k 40, T 0.9) over the
+steps that end at n = CTX, measured as tools/bias_cost.py does (generation from prompts of CTX - STEPS ids timed up to CTX ids
+and up to one new id, the difference divided by the STEPS - 1 decode steps between them: the prompt and the first id cancel),
+three repeats each (the best, and `spread` = the largest difference between two repeats), in three states:
+  parent   the PARENT COMMIT'S BUILD: a checkout of the commit before this feature, built, at --parent-root; measured by a
+           child process that loads that tree's package (this script with --child-root).  Left out when no root is given;
+  no_ask   this build, no sequence asking: the step ends in k_dec_sample, as the parent's does;
+  ask5     n_top = 5 on every sequence: the step ends in k_dec_sample_lp and every sequence commits a record.
+And the sampler launch alone on one real logits row (in-library profiler): the draw, and the record operator with n_top 5 --
+the two parts of k_dec_sample_lp for a sequence that asks.  Nothing here is a threshold."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+CTX, K, TEMP, SEED, N_TOP = 512, 40, 0.9, 7, 5
+WIDTHS = (1, 64, 256)
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    return time.perf_counter() - t0
+
+
+def step_ms(gen, steps, repeats=3):
+    """(ms per step of gen(max_tokens) over the last `steps` steps before CTX, spread of the repeats)"""
+    gen(CTX - steps + 1)                                      # warm: graphs captured, prompt path compiled
+    got = []
+    for _ in range(repeats):
+        t_all = timed(lambda: gen(CTX))
+        t_one = timed(lambda: gen(CTX - steps + 1))
+        got.append(1e3 * (t_all - t_one) / (steps - 1))
+    return min(got), max(got) - min(got)
+
+
+def measure(root, steps, ask):
+    """{width: {state: ms, state_spread: ms}} with the package of the tree at `root`; ask: also the ask5 state and the launches"""
+    sys.path.insert(0, root)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    hip = pkg.hipabi.load(0)
+    host = pkg.load_host()
+    cfg = host.default_config(4, 3)
+    cfg.max_ctx = CTX
+    P = CTX - steps
+    res, extra = {}, {}
+    for S in WIDTHS:
+        o = host.model(cfg) if S == 1 else host.batch(cfg, S)
+        o.load_synthetic(4242)
+        prompts = [list(host.synthetic_tokens(P, seed=(3 if S == 1 else 10 + q), n_vocab=cfg.n_vocab)) for q in range(S)]
+        if S == 1:
+            plain = lambda mt: o.generate_topk(prompts[0], mt, -1, K, TEMP, SEED)                             # noqa: E731
+            asking = lambda mt: o.generate_logprobs(prompts[0], mt, N_TOP, -1, K, TEMP, SEED)                 # noqa: E731
+        else:
+            plain = lambda mt: o.generate_topk(prompts, mt, -1, K, TEMP, SEED)                                # noqa: E731
+            asking = lambda mt: o.generate_logprobs(prompts, mt, N_TOP, -1, K, TEMP, SEED)                    # noqa: E731
+        out = {}
+        for name, gen in (("no_ask", plain),) + ((("ask5", asking),) if ask else ()):
+            ms, spread = step_ms(gen, steps)
+            out[name] = round(ms, 4)
+            out[name + "_spread"] = round(spread, 4)
+        res[str(S)] = out
+        if S == 1 and ask:
+            import numpy as np
+            row = o.logits(prompts[0], 0)
+            buf = pkg.hipabi.DeviceBuffer.from_numpy(hip, row[None, :])
+            ids = np.array([int(np.argmax(row))], np.int32)
+            for name, call in (("decode_sample_us", lambda i: hip.sample_rows(buf, 1, cfg.n_vocab, 0, K, TEMP, SEED, 0, P + i)),
+                               ("record_n_top_5_us", lambda i: hip.row_top_logprobs(buf, 1, cfg.n_vocab, cfg.n_vocab, ids, N_TOP))):
+                call(0)
+                hip.prof_enable(True)
+                n0, ms0 = hip.prof_read().get("decode_sample", (0, 0.0))     # (whatever the profiler already holds)
+                for i in range(200):
+                    call(i)
+                n, ms = hip.prof_read()["decode_sample"]
+                hip.prof_enable(False)
+                extra[name] = round(1e3 * (ms - ms0) / (n - n0), 2)
+        o.close()
+    return res, extra
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--child-root", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child_root:
+        res, _ = measure(a.child_root, a.steps, ask=False)
+        print(json.dumps(res))
+        return
+    res = {"what": f"log-prob record cost, TinyLlama-1.1B q4 synthetic, ctx {CTX}, k {K}, T {TEMP}, n_top {N_TOP}", "steps": a.steps, "ms_per_step": {}}
+    parent = None
+    if a.parent_root:
+        # (a fresh child process, before this one opens the GPU)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-root", os.path.abspath(a.parent_root), "--steps", str(a.steps)],
+                           capture_output=True, text=True, timeout=1500)
+        if r.returncode != 0:
+            raise SystemExit("the parent's measurement failed:\n" + r.stderr[-2000:])
+        parent = json.loads(r.stdout.strip().splitlines()[-1])
+    own, extra = measure(ROOT, a.steps, ask=True)
+    for S in map(str, WIDTHS):
+        out = {}
+        if parent:
+            out["parent"], out["parent_spread"] = parent[S]["no_ask"], parent[S]["no_ask_spread"]
+        out.update(own[S])
+        if parent:
+            out["no_ask_over_parent"] = round(out["no_ask"] / out["parent"], 4)
+            out["ask5_over_parent"] = round(out["ask5"] / out["parent"], 4)
+        out["ask5_over_no_ask"] = round(out["ask5"] / out["no_ask"], 4)
+        res["ms_per_step"][S] = out
+    res.update(extra)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
