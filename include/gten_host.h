@@ -105,7 +105,7 @@ int  gten_host_batch_generate(gten_host_batch* b, const int32_t* prompts, const 
                               int32_t* out, int32_t* n_total);
 /* Continuous batching: a queue of n_prompts prompts ([n_prompts][max_prompt], prompt j uses its first n_prompt[j] ids) served
  * through the batch's n_seq slots -- a slot whose sequence has ended (eos, `max_tokens` ids in all, or the context) takes the
- * next prompt at once while the other slots go on decoding (TinyLlamaBatch::serve, host/tinyllama_model.h; device side:
+ * next prompt at once while the other slots go on decoding (TinyLlamaBatch::serve_with, host/tinyllama_model.h; device side:
  * gten_hip_decoder_slot_start / _run / _slot_ids).  `slice` = shared steps between two looks at the results; max_new > 0
  * additionally bounds the ids generated per prompt (max_new_each, when not NULL: prompt j's own bound).
  * out is [n_prompts][max(max_tokens, max_prompt)] (prompt + new ids), n_total [n_prompts]; stats (may be NULL) receives SIX

@@ -1,6 +1,6 @@
 """-m gpu: continuous batching (round-1 verdict "slot admission/eviction").  A queue of prompts is
 served through the slots of a multi-sequence decoder: a slot whose sequence ended takes the next prompt while the
-others go on (TinyLlamaBatch::serve; gten_hip_decoder_slot_start / _slot_park / _run / _slot_ids).  Up to 8 slots every
+others go on (TinyLlamaBatch::serve_with; gten_hip_decoder_slot_start / _slot_park / _run / _slot_ids).  Up to 8 slots every
 sequence's ids must be EXACTLY those of generating it alone on the single-sequence decoder."""
 import numpy as np
 import pytest

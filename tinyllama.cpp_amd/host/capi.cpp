@@ -6,7 +6,6 @@
 #include <memory>
 
 #include "capi_handles.h"
-#include "tinyllama_model.h"
 #include "tokenizer.h"
 
 using namespace gten;
@@ -105,11 +104,7 @@ int gten_host_model_greedy(gten_host_model* m, int32_t* tokens, int n_prompt, in
 
 int gten_host_model_generate(gten_host_model* m, int32_t* tokens, int n_prompt, int max_tokens, int eos)
 {
-    std::vector<int32_t> t(tokens, tokens + n_prompt);
-    t.reserve((size_t)max_tokens);
-    const int total = greedy_generate(*m->model, t, max_tokens, eos);
-    std::memcpy(tokens, t.data(), (size_t)total * sizeof(int32_t));
-    return total;
+    return generate_in_place<0>(*m->model, tokens, n_prompt, max_tokens, eos);
 }
 
 // ---- tokenizer (host/tokenizer.h): ids and pieces of the reference's tokenizer.h on the same vocabulary file
@@ -268,43 +263,11 @@ int gten_host_batch_decode_step_ragged(gten_host_batch* b, const int32_t* n_per_
     return 0;
 }
 
-// prompts [n_seq][max_prompt] (sequence q uses its first n_prompt[q] ids): each prompt is processed on its sequence's
-// own caches (the reference's logits() call, host argmax of the first new id), then all sequences generate together
-// with the sampler on the device.  out is [n_seq][max_tokens]: prompt + new ids; n_total [n_seq].
 int gten_host_batch_generate(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
                              int32_t* out, int32_t* n_total)
 {
     if (!prompts || !n_prompt || !out || !n_total || max_tokens <= 0) return -1;
-    const int S = b->batch->n_seq();
-    std::vector<int> n_first((size_t)S), room((size_t)S);
-    int max_new = 0;
-    for (int q = 0; q < S; q++) {
-        const int P = n_prompt[q];
-        if (P <= 0 || P > max_prompt || P >= max_tokens || P >= b->cfg.max_ctx) return -1;
-        int32_t* row = out + (size_t)q * max_tokens;
-        std::memcpy(row, prompts + (size_t)q * max_prompt, (size_t)P * sizeof(int32_t));
-        const int best_i = b->batch->prefill(q, std::vector<int32_t>(row, row + P));
-        row[P] = best_i;                                          // (an eos here ends the sequence below)
-        n_first[q] = P + 1;
-        b->batch->decode_set_tokens(q, row, 0, P + 1);
-        // this sequence's own room; none when the prompt's argmax is already eos (the sequence is then parked from the start
-        // instead of being decoded for the longest sequence's length)
-        room[(size_t)q] = (best_i == eos) ? 0 : max_tokens - (P + 1);
-        max_new = std::max(max_new, room[(size_t)q]);
-    }
-    std::vector<int32_t> gen((size_t)S * (size_t)std::max(max_new, 1));
-    std::vector<int> n_out((size_t)S, 0);
-    b->batch->decode_generate(n_first.data(), max_new, eos, gen.data(), n_out.data(), room.data());
-    for (int q = 0; q < S; q++) {
-        int32_t* row = out + (size_t)q * max_tokens;
-        int total = n_first[q];
-        if (row[total - 1] == eos) { n_total[q] = total - 1; continue; }
-        const int room = max_tokens - total;
-        const int take = std::min(n_out[q], room);
-        std::memcpy(row + total, gen.data() + (size_t)q * max_new, (size_t)take * sizeof(int32_t));
-        n_total[q] = total + take;
-    }
-    return 0;
+    return generate_batch<0>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos, Requests{}, out, n_total);
 }
 
 int gten_host_batch_set_serve_schedule(gten_host_batch* b, int k)
@@ -332,26 +295,9 @@ int gten_host_batch_serve2(gten_host_batch* b, const int32_t* prompts, const int
                            int max_tokens, int eos, int slice, int max_new, const int32_t* max_new_each, int32_t* out, int32_t* n_total, double* stats,
                            int n_stats)
 {
-    if (!prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_tokens <= 0 || slice <= 0 || n_stats < 0) return -1;
-    std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
-    for (int j = 0; j < n_prompts; j++) {
-        if (n_prompt[j] <= 0 || n_prompt[j] > max_prompt || n_prompt[j] > b->cfg.max_ctx) return -1;
-        ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
-    }
-    const TinyLlamaBatch::ServeStats st = b->batch->serve(ps, max_tokens, eos, slice, &res, max_new, max_new_each);
-    for (int j = 0; j < n_prompts; j++) {
-        const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, n_prompt[j]));
-        std::memcpy(out + (size_t)j * std::max(max_tokens, max_prompt), res[(size_t)j].data(), (size_t)take * sizeof(int32_t));
-        n_total[j] = take;
-    }
-    if (stats) {
-        // (exactly n_stats doubles are written: a caller sized for an older, shorter list stays inside its array)
-        const double all[] = {(double)st.prompt_tokens, (double)st.new_tokens, (double)st.steps, (double)st.admissions, st.prefill_s, st.decode_s,
-                              (double)st.lane_steps, (double)st.lane_rows, (double)st.moved};
-        const int have = (int)(sizeof(all) / sizeof(all[0]));
-        for (int i = 0; i < n_stats; i++) stats[i] = i < have ? all[i] : 0.0;
-    }
-    return 0;
+    if (!prompts || !n_prompt || !out || !n_total || n_stats < 0) return -1;
+    return serve_queue<0>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                          stats, n_stats);
 }
 
 /* the entry point as first published: SIX doubles (a caller compiled against that header holds double[6]) */

@@ -1,10 +1,10 @@
-// capi_handles.h -- the handles behind include/gten_host.h's opaque types, shared by host/capi.cpp and host/capi_sample.cpp.
+// capi_handles.h -- the handles behind include/gten_host.h's opaque types, shared by the host/capi*.cpp files.
 #pragma once
 
 #include <memory>
 
 #include "../../include/gten_host.h"
-#include "tinyllama_model.h"
+#include "generate.h"
 
 struct gten_host_model {
     gten_host_config cfg;

@@ -1,0 +1,440 @@
+// generate.h -- choosing the next id, once for every entry point above the C ABI of libgten_hip.so: greedy, top-k sampling
+// (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h) and log-prob records
+// (include/gten_hip_logprobs.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
+// compile-time mask says which device entry points the flow may name.
+//
+// Why a mask and not a run-time switch: host/capi.cpp links against a stand-in of include/gten_hip.h alone
+// (tests/test_host_sanitize_cpu.py), host/capi.cpp + host/capi_sample.cpp against that plus the sampler's
+// (tests/test_sampler_cpu.py).  So every flow here is a template on the mask, the stages it does not have are discarded with
+// `if constexpr`, and each flow is instantiated where its stages may be named: mask 0 in host/capi.cpp, kSampled in
+// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, all three in host/capi_logprobs.cpp (and in the command line
+// program, which links against the library itself).  That is the only reason those files are separate.
+#pragma once
+
+#include <cmath>
+
+#include "tinyllama_model.h"
+#include "../../include/gten_hip_sample.h"
+#include "../../include/gten_hip_bias.h"
+#include "../../include/gten_hip_logprobs.h"
+
+namespace gten {
+
+enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u };
+
+// What one prompt or sequence asks for.  The defaults: greedy, no table, no records.
+struct Request {
+    int top_k = 0;               // 0: greedy
+    float temp = 0.f;
+    uint64_t seed = 0;
+    uint32_t stream = 0;         // the draw at a position is keyed by (seed, stream, position)
+    int table = -1;              // bias table (-1: none) ...
+    int min_new = 0;             // ... which holds for the first min_new new ids (0: for all of them)
+    int n_top = -1;              // alternatives per log-prob record (0: the id's own log-prob only; -1: no records)
+    // the first position the table no longer holds at, for a prompt of n_prompt ids (0: it holds throughout)
+    int until(int n_prompt) const { return (table >= 0 && min_new > 0) ? n_prompt + min_new : 0; }
+};
+
+inline bool request_ok(int top_k, float temp) { return top_k >= 0 && (top_k == 0 || (std::isfinite(temp) && temp > 0.f)); }
+inline bool binding_ok(int table, int min_new) { return table >= -1 && table < GTEN_HIP_BIAS_TABLES && min_new >= 0; }
+inline bool asking_ok(int n_top, int n_top_max) { return n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP && n_top <= n_top_max; }
+
+// the requests of a fixed batch's sequences or of a queue's prompts, as the C ABI passes them
+struct Requests {
+    Each<int32_t> top_k{nullptr, 0};
+    Each<float> temp{nullptr, 0.f};
+    uint64_t seed = 0;
+    const uint32_t* stream = nullptr;        // (null: item j draws with stream j)
+    Each<int32_t> table{nullptr, -1}, min_new{nullptr, 0}, n_top{nullptr, -1};
+    static Requests of(const int32_t* top_k, int top_k_all, const float* temp, float temp_all, uint64_t seed, const uint32_t* stream = nullptr,
+                       const int32_t* table = nullptr, const int32_t* min_new = nullptr, const int32_t* n_top = nullptr)
+    {
+        return {{top_k, top_k_all}, {temp, temp_all}, seed, stream, {table, -1}, {min_new, 0}, {n_top, -1}};
+    }
+    Request operator[](int j) const { return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j]}; }
+    bool ok(int n, int n_top_max) const
+    {
+        for (int j = 0; j < n; j++)
+            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max)) return false;
+        return true;
+    }
+};
+
+// gten_hip_row_top_logprobs' outputs for one row, behind each other on the device: the record of a prompt's first id
+struct FirstRecord {
+    float logprob;
+    int32_t top_id[GTEN_HIP_LOGPROBS_TOP];
+    float top_lp[GTEN_HIP_LOGPROBS_TOP];
+};
+struct FirstRecords {
+    FirstRecord* dev = nullptr;
+    int rows = 0;
+    FirstRecords() = default;
+    FirstRecords(const FirstRecords&) = delete;
+    ~FirstRecords() { if (dev) gten_hip_free(dev); }
+    void ensure(int n)
+    {
+        if (n <= rows) return;
+        if (dev) GTEN_HIP_OK(gten_hip_free(dev));
+        dev = nullptr;
+        GTEN_HIP_OK(gten_hip_malloc((void**)&dev, (size_t)n * sizeof(FirstRecord)));
+        rows = n;
+    }
+};
+
+// A caller's record outputs: one entry per position, top_id / top_lp n_top_max wide.  No record: log-probs 0, ids -1.
+struct RecordRows {
+    float* logprob = nullptr;
+    int32_t* top_id = nullptr;
+    float* top_lp = nullptr;
+    int n_top_max = 0;
+    RecordRows from(size_t pos) const { return {logprob + pos, top_id + pos * (size_t)n_top_max, top_lp + pos * (size_t)n_top_max, n_top_max}; }
+    void blank(size_t positions) const
+    {
+        std::fill(logprob, logprob + positions, 0.f);
+        if (n_top_max > 0) {
+            std::fill(top_id, top_id + positions * (size_t)n_top_max, -1);
+            std::fill(top_lp, top_lp + positions * (size_t)n_top_max, 0.f);
+        }
+    }
+    // `count` records of n_top entries each (ids and lps dense) into the positions from `pos` on
+    void store(size_t pos, int count, int n_top, const float* lp, const int32_t* ids, const float* lps) const
+    {
+        std::memcpy(logprob + pos, lp, (size_t)count * sizeof(float));
+        for (int i = 0; i < count && n_top > 0; i++) {
+            std::memcpy(top_id + (pos + (size_t)i) * (size_t)n_top_max, ids + (size_t)i * n_top, (size_t)n_top * sizeof(int32_t));
+            std::memcpy(top_lp + (pos + (size_t)i) * (size_t)n_top_max, lps + (size_t)i * n_top, (size_t)n_top * sizeof(float));
+        }
+    }
+    // a first id's record from the device (the stream has been waited for: the id was read back)
+    void store_first(size_t pos, int n_top, const FirstRecord* dev) const
+    {
+        FirstRecord r;
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&r, dev, sizeof(r)));
+        store(pos, 1, n_top, &r.logprob, r.top_id, r.top_lp);
+    }
+    // the decoder's records of sequence seq at positions [pos, pos + count)
+    int store_decoded(gten_hip_decoder* dec, int seq, int pos, int count, int n_top) const
+    {
+        if (count <= 0) return 0;
+        std::vector<int32_t> ids((size_t)count * (size_t)std::max(n_top, 1));
+        std::vector<float> lps(ids.size()), lp((size_t)count);
+        if (const int rc = gten_hip_decoder_logprobs(dec, seq, pos, count, n_top, lp.data(), ids.data(), lps.data())) return rc;
+        store((size_t)pos, count, n_top, lp.data(), ids.data(), lps.data());
+        return 0;
+    }
+};
+
+// The id that will sit at position `pos`, drawn on the device from the logits row lg into id_dev: plain or under the request's
+// table, plus its record into rec_dev when the request asks.  (The only draw from a prompt's row outside the decoder.)
+template <unsigned M>
+void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, FirstRecord* rec_dev)
+{
+    static_assert(M & kSampled, "greedy takes the argmax of the prompt's logits on the host");
+    const int32_t k = r.top_k;
+    const float* row = nullptr;
+    if constexpr ((M & kBiased) != 0) {
+        if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
+        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    }
+    if (!row) GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n_vocab, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    if constexpr ((M & kLogprobs) != 0)
+        if (r.n_top >= 0) GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n_vocab, n_vocab, id_dev, r.n_top, &rec_dev->logprob, rec_dev->top_id, rec_dev->top_lp));
+}
+
+// Requests on a decoder's slots [0, n_slots), taken back when the scope ends: whatever way a flow is left, every kind of request
+// it has set is cleared on every slot -- the decoder's later steps are greedy, unbound and record nothing.
+template <unsigned M>
+struct SlotRequests {
+    gten_hip_decoder* dec;
+    int n_slots;
+    bool bound = false, sampling = false;
+    SlotRequests(gten_hip_decoder* dec_, int n_slots_) : dec{dec_}, n_slots{n_slots_} {}
+    SlotRequests(const SlotRequests&) = delete;
+    ~SlotRequests() { clear(); }
+    // table and log-prob request of a prompt of n_prompt ids (a decoder that refuses them says so here, before any work)
+    int bind(int q, const Request& r, int n_prompt)
+    {
+        (void)q; (void)r; (void)n_prompt;
+        if constexpr ((M & (kBiased | kLogprobs)) != 0) bound = true;
+        if constexpr ((M & kBiased) != 0)
+            if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
+        if constexpr ((M & kLogprobs) != 0)
+            if (const int rc = gten_hip_decoder_set_logprobs(dec, q, r.n_top)) return rc;
+        return 0;
+    }
+    // the sampling request of the decode steps that follow
+    int sample(int q, const Request& r)
+    {
+        (void)q; (void)r;
+        if constexpr ((M & kSampled) != 0) {
+            sampling = true;
+            return gten_hip_decoder_set_sampling(dec, q, r.top_k, r.temp, r.seed, r.stream);
+        }
+        return 0;
+    }
+    // 0, or the code of the last call that failed
+    int clear()
+    {
+        int rc = 0;
+        if constexpr ((M & kSampled) != 0)
+            for (int q = 0; sampling && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_sampling(dec, q, 0, 0.f, 0, 0)) rc = r;
+        if constexpr ((M & kBiased) != 0)
+            for (int q = 0; bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_seq_bias(dec, q, -1, 0)) rc = r;
+        if constexpr ((M & kLogprobs) != 0)
+            for (int q = 0; bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_logprobs(dec, q, -1)) rc = r;
+        bound = sampling = false;
+        return rc;
+    }
+};
+
+// ---- one sequence.  The prompt is processed as in the reference (iteration 0 of greedy_sample); its first id is the host
+// argmax of its logits (mask 0) or draw_first's; every later id comes from back-to-back graph replays whose sampler feeds the
+// next step on the device -- no logits copy, no host round trip per token.  Mask 0 gives greedy_sample's ids (tested), top_k 0
+// gives mask 0's.  With kLogprobs `rows` (max(n_predict, prompt) positions, blanked here once the decoder has accepted the requests)
+// receives the new ids' records at their positions.
+// Returns the number of ids in `tokens`; -1 when the decoder refuses a request (gten_hip_last_error).
+template <unsigned M>
+int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, const Request& r = {}, const RecordRows& rows = {})
+{
+    const int n_prompt = (int)tokens.size();
+    auto blank = [&]() {
+        if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)std::max(n_predict, n_prompt));
+    };
+    if (n_prompt >= n_predict) { blank(); return n_prompt; }
+    gten_hip_decoder* dec = nullptr;
+    if constexpr (M != 0) dec = model.decoder_handle();
+    SlotRequests<M> slot(dec, 1);
+    if (slot.bind(0, r, n_prompt) != 0) return -1;
+    blank();
+    {
+        Tensor input{tokens.data(), {n_prompt}, kInt32};
+        const Tensor logits = model.logits(input, 0);
+        int32_t first = 0;
+        if constexpr (M == 0) {
+            const float* p = logits.data_ptr<float>();
+            float best = -std::numeric_limits<float>::infinity();
+            for (int j = 0; j < logits.numel(); j++)
+                if (p[j] > best) { best = p[j]; first = j; }
+        } else {
+            Tensor id({1}, kInt32);
+            FirstRecords rec;
+            if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
+            draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev);
+            GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
+            if constexpr ((M & kLogprobs) != 0)
+                if (first != eos && r.n_top >= 0) rows.store_first((size_t)n_prompt, r.n_top, rec.dev);
+        }
+        if (first == eos) return n_prompt;
+        tokens.push_back(first);
+    }
+    const int n_first = n_prompt + 1;
+    const int max_new = n_predict - n_first;
+    if (max_new <= 0) return n_first;
+    std::vector<int32_t> out((size_t)max_new);
+    if (slot.sample(0, r) != 0) return -1;
+    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
+    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
+    if constexpr ((M & kLogprobs) != 0)
+        if (r.n_top >= 0 && rows.store_decoded(dec, 0, n_first, got, r.n_top) != 0) return -1;
+    return slot.clear() ? -1 : (int)tokens.size();
+}
+
+// generate() on a caller's array: `tokens` holds n_prompt ids and has room for max(max_tokens, n_prompt)
+template <unsigned M>
+int generate_in_place(TinyLlama& model, int32_t* tokens, int n_prompt, int max_tokens, int eos, const Request& r = {}, const RecordRows& rows = {})
+{
+    std::vector<int32_t> t(tokens, tokens + n_prompt);
+    t.reserve((size_t)std::max(max_tokens, n_prompt));
+    const int total = generate<M>(model, t, max_tokens, eos, r, rows);
+    if (total > 0) std::memcpy(tokens, t.data(), (size_t)total * sizeof(int32_t));
+    return total;
+}
+
+// the first id of `prompt` processed onto cache set `set` of a batch: TinyLlamaBatch::prefill's argmax (mask 0) or draw_first's
+template <unsigned M>
+int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, const Request& r, FirstRecord* rec_dev)
+{
+    if constexpr (M == 0) {
+        (void)r; (void)rec_dev;
+        return b.prefill(set, prompt);
+    } else {
+        gten_hip_decoder* dec = nullptr;
+        if constexpr ((M & kBiased) != 0) dec = b.decoder_handle();
+        return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) { draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev); });
+    }
+}
+
+// ---- a fixed batch (gten_host_batch_generate and its _topk / _biased / _lp forms).  prompts [n_seq][max_prompt] (sequence q uses
+// its first n_prompt[q] ids): every request is set first (a refusal comes before any work), each prompt is processed on its
+// sequence's own caches and its first id chosen from its logits row, then all sequences generate together with the sampler on
+// the device.  out is [n_seq][max_tokens]: prompt + new ids; n_total [n_seq]; rows (kLogprobs) [n_seq][max_tokens] positions.
+// 0; -1: bad arguments (nothing was touched); otherwise the code of the decoder call that refused.
+template <unsigned M>
+int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
+                   const Requests& reqs, int32_t* out, int32_t* n_total, const RecordRows& rows = {})
+{
+    const int S = batch.n_seq();
+    for (int q = 0; q < S; q++)
+        if (n_prompt[q] <= 0 || n_prompt[q] > max_prompt || n_prompt[q] >= max_tokens || n_prompt[q] >= max_ctx) return -1;
+    if (!reqs.ok(S, rows.n_top_max)) return -1;
+    if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)S * (size_t)max_tokens);
+    gten_hip_decoder* dec = nullptr;
+    if constexpr (M != 0) dec = batch.decoder_handle();
+    SlotRequests<M> slots(dec, S);
+    for (int q = 0; q < S; q++)
+        if (const int rc = slots.bind(q, reqs[q], n_prompt[q])) return rc;
+    std::vector<int32_t> first((size_t)S);
+    FirstRecords rec;
+    if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
+    for (int q = 0; q < S; q++) {
+        const int P = n_prompt[q];
+        int32_t* row = out + (size_t)q * max_tokens;
+        std::memcpy(row, prompts + (size_t)q * max_prompt, (size_t)P * sizeof(int32_t));
+        const Request r = reqs[q];
+        first[(size_t)q] = first_id<M>(batch, q, std::vector<int32_t>(row, row + P), r, rec.dev);
+        if constexpr ((M & kLogprobs) != 0)
+            if (r.n_top >= 0 && first[(size_t)q] != eos) rows.from((size_t)q * max_tokens).store_first((size_t)P, r.n_top, rec.dev);
+    }
+    std::vector<int> n_first((size_t)S), room((size_t)S);
+    int max_new = 0;
+    for (int q = 0; q < S; q++) {
+        const int P = n_prompt[q];
+        int32_t* row = out + (size_t)q * max_tokens;
+        row[P] = first[(size_t)q];                                 // (an eos here ends the sequence below)
+        n_first[(size_t)q] = P + 1;
+        batch.decode_set_tokens(q, row, 0, P + 1);
+        if (const int rc = slots.sample(q, reqs[q])) return rc;
+        // this sequence's own room; none when its first id is already eos (the sequence is then parked from the start instead of
+        // being decoded for the longest sequence's length)
+        room[(size_t)q] = (first[(size_t)q] == eos) ? 0 : max_tokens - (P + 1);
+        max_new = std::max(max_new, room[(size_t)q]);
+    }
+    std::vector<int32_t> gen((size_t)S * (size_t)std::max(max_new, 1));
+    std::vector<int> n_out((size_t)S, 0);
+    batch.decode_generate(n_first.data(), max_new, eos, gen.data(), n_out.data(), room.data());
+    for (int q = 0; q < S; q++) {
+        int32_t* row = out + (size_t)q * max_tokens;
+        const int total = n_first[(size_t)q];
+        if (row[total - 1] == eos) { n_total[q] = total - 1; continue; }
+        const int take = std::min(n_out[(size_t)q], max_tokens - total);
+        std::memcpy(row + total, gen.data() + (size_t)q * max_new, (size_t)take * sizeof(int32_t));
+        n_total[q] = total + take;
+        if constexpr ((M & kLogprobs) != 0)
+            if (const int n_top = reqs[q].n_top; n_top >= 0)
+                if (const int rc = rows.from((size_t)q * max_tokens).store_decoded(dec, q, total, take, n_top)) return rc;
+    }
+    return slots.clear();
+}
+
+// ---- How TinyLlamaBatch::serve_with picks ids.  Prompt j's request (reqs[j]; stream j) draws its first id from the prompt's
+// logits row on the device -- under its table, with its record -- and is set on whichever slot takes the prompt, also when a
+// sequence moves in the tail: the ids depend on (seed, j) and the logits only, not on the slot or schedule.  A slot's records
+// are read when its prompt ends or moves (collect), before the slot is started again.  Every slot's requests are cleared when
+// the queue is done.  Mask 0: the prompt's argmax, the decoder's argmax, nothing set.  `rows` is [prompts][row_len] positions.
+template <unsigned M>
+struct ServePolicy {
+    static constexpr bool kLogprobs = (M & gten::kLogprobs) != 0;
+    Requests reqs;
+    RecordRows rows;
+    int row_len;
+    SlotRequests<M> slots;
+    FirstRecords rec;
+    ServePolicy(gten_hip_decoder* dec, int n_slots, const Requests& reqs_, const RecordRows& rows_ = {}, int row_len_ = 0)
+        : reqs{reqs_}, rows{rows_}, row_len{row_len_}, slots(dec, n_slots) {}
+    RecordRows rows_of(int j) const { return rows.from((size_t)j * (size_t)row_len); }
+    FirstRecord* rec_of(int k) const { return kLogprobs ? rec.dev + k : nullptr; }
+    void store_first(int k, int j, int pos)
+    {
+        if (reqs.n_top[j] >= 0 && pos < row_len) rows_of(j).store_first((size_t)pos, reqs.n_top[j], rec_of(k));
+    }
+    int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
+    {
+        if constexpr (kLogprobs) rec.ensure(1);
+        const int id = first_id<M>(b, c, row, reqs[j], rec.dev);
+        if constexpr (kLogprobs) store_first(0, j, (int)row.size());
+        return id;
+    }
+    void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
+              std::vector<int>* first)
+    {
+        if constexpr (M == 0) {
+            (void)js;
+            b.prefill_many(sets, ps, first);
+        } else {
+            if constexpr (kLogprobs) rec.ensure((int)sets.size());
+            std::vector<float*> lo((size_t)sets.size(), nullptr);
+            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
+                draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k));
+            });
+            if constexpr (kLogprobs)
+                for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
+        }
+    }
+    // prompt j (n_prompt ids) starts, or goes on, in slot q
+    void apply(int q, int j, int n_prompt)
+    {
+        const Request r = reqs[j];
+        GTEN_HIP_OK(slots.sample(q, r));
+        GTEN_HIP_OK(slots.bind(q, r, n_prompt));
+    }
+    // slot q's records of positions [from, from + count) are prompt j's
+    void collect(int q, int j, int from, int count)
+    {
+        if (reqs.n_top[j] >= 0) GTEN_HIP_OK(rows_of(j).store_decoded(slots.dec, q, from, std::min(count, row_len - from), reqs.n_top[j]));
+    }
+    void clear() { GTEN_HIP_OK(slots.clear()); }
+};
+
+// ---- gten_host_batch_serve2's packing around a queue (and its _topk / _biased / _lp forms): the prompts in, a decoder that
+// refuses tables or records heard before the queue starts, the rows and the stats list out.  out and rows are
+// max(max_tokens, max_prompt) positions per prompt.  0; -1: bad arguments; otherwise the code of the decoder's refusal.
+template <unsigned M>
+int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
+                int eos, int slice, int max_new, const int32_t* max_new_each, int32_t* out, int32_t* n_total, double* stats, int n_stats,
+                const Requests& reqs = {}, const RecordRows& rows = {})
+{
+    if (n_prompts <= 0 || max_tokens <= 0 || slice <= 0) return -1;
+    for (int j = 0; j < n_prompts; j++)
+        if (n_prompt[j] <= 0 || n_prompt[j] > max_prompt || n_prompt[j] > max_ctx) return -1;
+    if (!reqs.ok(n_prompts, rows.n_top_max)) return -1;
+    const int row_len = std::max(max_tokens, max_prompt);
+    gten_hip_decoder* dec = nullptr;
+    if constexpr (M != 0) dec = batch.decoder_handle();
+    if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)n_prompts * (size_t)row_len);
+    // (slot 0 is as it was at once)
+    if constexpr ((M & kBiased) != 0)
+        if (reqs.table.each) {
+            if (const int rc = gten_hip_decoder_set_seq_bias(dec, 0, 0, 0)) return rc;
+            if (const int rc = gten_hip_decoder_set_seq_bias(dec, 0, -1, 0)) return rc;
+        }
+    if constexpr ((M & kLogprobs) != 0)
+        if (reqs.n_top.each) {
+            if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, 0)) return rc;
+            if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, -1)) return rc;
+        }
+    std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
+    for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
+    ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len);
+    const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, pick);
+    for (int j = 0; j < n_prompts; j++) {
+        const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, n_prompt[j]));
+        std::memcpy(out + (size_t)j * row_len, res[(size_t)j].data(), (size_t)take * sizeof(int32_t));
+        n_total[j] = take;
+        // (a first id that was the eos is not stored: neither is its record)
+        if constexpr ((M & kLogprobs) != 0) rows.from((size_t)j * row_len + (size_t)take).blank((size_t)(row_len - take));
+    }
+    if (stats) {
+        // (exactly n_stats doubles are written: a caller sized for an older, shorter list stays inside its array)
+        const double all[] = {(double)st.prompt_tokens, (double)st.new_tokens, (double)st.steps, (double)st.admissions, st.prefill_s, st.decode_s,
+                              (double)st.lane_steps, (double)st.lane_rows, (double)st.moved};
+        const int have = (int)(sizeof(all) / sizeof(all[0]));
+        for (int i = 0; i < n_stats; i++) stats[i] = i < have ? all[i] : 0.0;
+    }
+    return 0;
+}
+
+} // namespace gten

@@ -3,7 +3,7 @@
 // forward path it drives is libgten_hip.so.  Differences from the reference's main(): no model download step (there is
 // no network here: --model PATH, default models/tinyllama.<fp16|q8|q4>.gten as there), --tokenizer PATH (default
 // tokenizer.bin), --seed for the top-k sampler, --ids to print token ids instead of text (tests); greedy sampling runs
-// with the sampler on the device (gten::greedy_generate); --score PATH prints the log-likelihood of a text file
+// with the sampler on the device (host/generate.h); --score PATH prints the log-likelihood of a text file
 // (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
 // of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
 // most likely alternatives (include/gten_hip_logprobs.h) after the text.
@@ -18,7 +18,7 @@
 #include <string_view>
 #include <vector>
 
-#include "tinyllama_model.h"
+#include "generate.h"
 #include "tokenizer.h"
 
 using namespace gten;
@@ -107,68 +107,47 @@ static void set_constraint(const Options& o, TinyLlama& model)
     }
 }
 
-// either generation mode under table 0 (top_k 0: greedy over the biased logits)
-static void run_constrained(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
+// One answer (host/generate.h).  Plain greedy: the prompt as in the reference, every later id from the device-side argmax, nothing set
+// on the decoder.  Top-k (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler,
+// keyed by (seed, stream = the chat turn, position).  --ban / --allow: either mode under table 0 (top_k 0: greedy over the biased
+// logits).  --logprobs: after the ids, one record line per generated id.  The flow names only the stages the options ask for.
+static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t* turn)
 {
     std::vector<int> enc = tok.encode(prompt);
     std::vector<int32_t> tokens(enc.begin(), enc.end());
-    const size_t n_prompt = tokens.size();
-    if (biased_generate(model, tokens, o.n_predict, tok.eos, o.greedy ? 0 : o.topk, o.temp, seed, turn, 0, o.min_new) < 0) {
-        std::cerr << "error: " << gten_hip_last_error() << "\n";
-        std::exit(EXIT_FAILURE);
-    }
-    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
-    (o.ids ? std::cout : std::cerr) << '\n';
-}
-
-// either generation mode with --logprobs (under table 0 when constrained): the ids, then one record line per generated id
-static void run_logprobs(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
-{
-    std::vector<int> enc = tok.encode(prompt);
-    std::vector<int32_t> tokens(enc.begin(), enc.end()), top_id;
+    const size_t n_prompt = tokens.size(), width = std::max(n_prompt, (size_t)o.n_predict), W = (size_t)std::max(o.logprobs, 0);
     std::vector<float> logprob, top_lp;
-    const size_t n_prompt = tokens.size();
-    if (logprobs_generate(model, tokens, o.n_predict, tok.eos, o.greedy ? 0 : o.topk, o.temp, seed, turn, o.constrained() ? 0 : -1, o.min_new, o.logprobs,
-                          &logprob, &top_id, &top_lp) < 0) {
+    std::vector<int32_t> top_id;
+    int rc = 0;
+    if (o.greedy && !o.constrained() && o.logprobs < 0) {
+        rc = generate<0>(model, tokens, o.n_predict, tok.eos);
+    } else {
+        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs};
+        if (o.logprobs >= 0) {
+            logprob.resize(width);
+            top_id.resize(width * W);
+            top_lp.resize(width * W);
+            rc = generate<kSampled | kBiased | kLogprobs>(model, tokens, o.n_predict, tok.eos, r, RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W});
+        } else if (o.constrained()) {
+            rc = generate<kSampled | kBiased>(model, tokens, o.n_predict, tok.eos, r);
+        } else {
+            rc = generate<kSampled>(model, tokens, o.n_predict, tok.eos, r);
+        }
+    }
+    if (rc < 0) {
         std::cerr << "error: " << gten_hip_last_error() << "\n";
         std::exit(EXIT_FAILURE);
     }
     for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
     (o.ids ? std::cout : std::cerr) << '\n';
+    if (o.logprobs < 0) return;
     std::cout.flush();
     for (size_t i = n_prompt; i < tokens.size(); i++) {
         std::printf("%d %.9g", tokens[i], logprob[i]);
-        for (int a = 0; a < o.logprobs; a++) std::printf(" %d:%.9g", top_id[i * (size_t)o.logprobs + a], top_lp[i * (size_t)o.logprobs + a]);
+        for (size_t a = 0; a < W; a++) std::printf(" %d:%.9g", top_id[i * W + a], top_lp[i * W + a]);
         std::printf("\n");
     }
     std::fflush(stdout);
-}
-
-// greedy: the prompt as in the reference, every later id from the device-side sampler
-static void run_greedy(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok)
-{
-    std::vector<int> enc = tok.encode(prompt);
-    std::vector<int32_t> tokens(enc.begin(), enc.end());
-    const size_t n_prompt = tokens.size();
-    greedy_generate(model, tokens, o.n_predict, tok.eos);
-    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
-    (o.ids ? std::cout : std::cerr) << '\n';
-}
-
-// top-k sampling (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler
-// (include/gten_hip_sample.h): the prompt's first id drawn from its logits in HBM, every later one inside the decode step.
-// The draw is keyed by (seed, stream, position): stream = the chat turn (0 for -p).
-static void run_topk(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t turn)
-{
-    std::vector<int> enc = tok.encode(prompt);
-    std::vector<int32_t> tokens(enc.begin(), enc.end());
-    const size_t n_prompt = tokens.size();
-    if (sampled_generate(model, tokens, o.n_predict, tok.eos, o.topk, o.temp, seed, turn) < 0) {
-        std::cerr << "error: " << gten_hip_last_error() << "\n";
-        std::exit(EXIT_FAILURE);
-    }
-    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
-    (o.ids ? std::cout : std::cerr) << '\n';
 }
 
 // --score: the file's plain BPE ids in windows [1] + up to ctx - 1 text ids, all windows through score_many (BOS is context
@@ -303,12 +282,7 @@ int main(int argc, char const* argv[])
     }
     if (o.constrained()) set_constraint(o, model);
     uint32_t turn = 0;
-    auto answer = [&](const std::string& prompt) {
-        if (o.logprobs >= 0) run_logprobs(o, prompt, model, tokenizer, seed, turn++);
-        else if (o.constrained()) run_constrained(o, prompt, model, tokenizer, seed, turn++);
-        else if (o.greedy) run_greedy(o, prompt, model, tokenizer);
-        else run_topk(o, prompt, model, tokenizer, seed, turn++);
-    };
+    auto answer = [&](const std::string& prompt) { run(o, prompt, model, tokenizer, seed, &turn); };
     if (o.prompt.empty()) {
         std::cout << "Chat interface. Write your prompt and press enter to submit. Enter q or press ctrl+c to quit.\n";
         std::string prompt;

@@ -1,8 +1,8 @@
 // tinyllama_model.h -- the caller of the hot path: model wiring, .gten loader
 // and greedy loop, written against the HBM-backed gten API.  Counterpart of the
 // reference's tinyllama.cpp:12-76 (params, TinyLlama), 301-392 (loader) and
-// 395-440 (greedy sampler); CLI, tokenizer and top-k sampling are out of scope
-// (SURVEY 8(f) rank 4).
+// 395-440 (greedy sampler).  Generation with the sampler on the device -- greedy,
+// top-k, bias tables, log-prob records -- is host/generate.h.
 #pragma once
 
 #include <algorithm>
@@ -25,9 +25,6 @@
 #include <deque>
 
 #include "../gten/gten.h"
-#include "../../include/gten_hip_sample.h"
-#include "../../include/gten_hip_bias.h"
-#include "../../include/gten_hip_logprobs.h"
 #include "../../include/gten_hip_score.h"
 #include "synth.h"
 
@@ -344,16 +341,7 @@ public:
         return got;
     }
 
-    // the request every later step of this model's decoder samples with (include/gten_hip_sample.h; top_k 0: greedy again).
-    // (only the sampled entry points call it: host/capi_sample.cpp, the command line program)
-    // Returns the library's code: a persistent decoder refuses top_k >= 1 (gten_hip_last_error says why)
-    int decode_set_sampling(int top_k, float temp, uint64_t seed, uint32_t stream)
-    {
-        ensure_decoder();
-        return gten_hip_decoder_set_sampling(dec_, 0, top_k, temp, seed, stream);
-    }
-
-    // the fused decoder itself, for the entry points that live outside this header (bias tables: host/capi_bias.cpp)
+    // the fused decoder itself, for what sets requests on it (host/generate.h, host/capi_bias.cpp, host/capi_logprobs.cpp)
     gten_hip_decoder* decoder_handle()
     {
         ensure_decoder();
@@ -622,6 +610,14 @@ inline PrefixDecode& prefix_decode()
 }
 } // namespace detail
 
+// an array with one value per item, or one value for all of them
+template <class T>
+struct Each {
+    const T* each;
+    T all;
+    T operator[](int j) const { return each ? each[j] : all; }
+};
+
 class TinyLlamaBatch {
 public:
     TinyLlamaBatch(int n_seq, int n_ctx, ModuleDtype dtype, TinyLLamaParams p = TinyLLamaParams{}) : n_ctx_{n_ctx}, dtype_{dtype}, params_{p}
@@ -887,14 +883,6 @@ public:
         return best_i;
     }
 
-    // prefill() with the first id drawn by the device sampler (include/gten_hip_sample.h) at position prompt.size()
-    int prefill_sampled(int seq_i, const std::vector<int32_t>& prompt, int top_k, float temp, uint64_t seed, uint32_t stream)
-    {
-        const int32_t pos = (int32_t)prompt.size();
-        return prefill_picked(seq_i, prompt, [&](int, const float* lg, int n, int32_t* out) {
-            GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &top_k, &temp, seed, &stream, &pos, out));
-        });
-    }
     // prefill() with the first id chosen on the device by pick(0, logits row in HBM, n_vocab, id out in HBM)
     template <class PickRow>
     int prefill_picked(int seq_i, const std::vector<int32_t>& prompt, PickRow pick)
@@ -939,13 +927,7 @@ public:
         ensure_decoder();
         GTEN_HIP_OK(gten_hip_decoder_generate_multi(dec_, n_first, max_new_seq, max_new, eos, out, n_out));
     }
-    // sequence seq_i's sampling request (include/gten_hip_sample.h; top_k 0: greedy again)
-    int decode_set_sampling(int seq_i, int top_k, float temp, uint64_t seed, uint32_t stream)
-    {
-        ensure_decoder();
-        return gten_hip_decoder_set_sampling(dec_, seq_i, top_k, temp, seed, stream);
-    }
-    // the shared decoder itself, for the entry points that live outside this header (bias tables: host/capi_bias.cpp)
+    // the shared decoder itself, for what sets requests on it (host/generate.h, host/capi_bias.cpp, host/capi_logprobs.cpp)
     gten_hip_decoder* decoder_handle()
     {
         ensure_decoder();
@@ -1003,186 +985,12 @@ public:
     // (lane_steps: shared steps x the lanes each of them ran -- a lane whose slots are all parked is left out of a run; lane_rows:
     //  slots per lane; new ids / (lane_steps x lane_rows) is the share of COMPUTED slot-steps that produced an id)
     struct ServeStats { int64_t prompt_tokens = 0, new_tokens = 0, steps = 0, admissions = 0, lane_steps = 0, moved = 0; int lane_rows = 0; double prefill_s = 0.0, decode_s = 0.0; };
-    // (max_new_each, when given, bounds the new ids of prompt j by max_new_each[j] instead of max_new)
-    ServeStats serve(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
-                     std::vector<std::vector<int32_t>>* out, int max_new = 0, const int32_t* max_new_each = nullptr)
-    {
-        GreedyServe greedy;
-        return serve_with(prompts, max_tokens, eos, slice, out, max_new, max_new_each, greedy);
-    }
-    // How serve() picks ids.  Greedy: the prompt's argmax, the decoder's argmax.  SampledServe (include/gten_hip_sample.h):
-    // prompt j's request (top_k[j], temp[j], seed, stream j) draws its first id from the prompt's logits on the device and is
-    // set on whichever slot takes the prompt -- the ids depend on (seed, j) and the logits only, not on the slot or schedule.
-    struct GreedyServe {
-        static constexpr bool kSampled = false, kBiased = false, kLogprobs = false;
-        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int) { return b.prefill(c, row); }
-        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>&,
-                  std::vector<int>* first)
-        {
-            b.prefill_many(sets, ps, first);
-        }
-        int top_k(int) const { return 0; }
-        float temp(int) const { return 0.f; }
-        uint64_t seed = 0;
-    };
-    struct SampledServe {
-        static constexpr bool kSampled = true, kBiased = false, kLogprobs = false;
-        const int32_t* top_k_each;       // per prompt (null: top_k_all)
-        const float* temp_each;          // per prompt (null: temp_all)
-        int top_k_all;
-        float temp_all;
-        uint64_t seed;
-        int top_k(int j) const { return top_k_each ? top_k_each[j] : top_k_all; }
-        float temp(int j) const { return temp_each ? temp_each[j] : temp_all; }
-        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j) { return b.prefill_sampled(c, row, top_k(j), temp(j), seed, (uint32_t)j); }
-        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
-                  std::vector<int>* first)
-        {
-            std::vector<float*> lo((size_t)sets.size(), nullptr);
-            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
-                const int j = js[(size_t)k];
-                const int32_t kk = top_k(j), pos = (int32_t)ps[(size_t)k]->size();
-                const float t = temp(j);
-                const uint32_t st = (uint32_t)j;
-                GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &kk, &t, seed, &st, &pos, out));
-            });
-        }
-    };
-    // SampledServe under bias tables (include/gten_hip_bias.h): prompt j names a table (-1: none) that holds for its
-    // first min_new new ids (0: for all of them).  The first id is drawn from the prompt's logits under the same table; the binding
-    // is set on whichever slot takes the prompt, beside its request, and every slot is unbound again when the queue is done.
-    struct BiasedServe {
-        static constexpr bool kSampled = true, kBiased = true, kLogprobs = false;
-        const int32_t* top_k_each;       // per prompt (null: top_k_all)
-        const float* temp_each;          // per prompt (null: temp_all)
-        int top_k_all;
-        float temp_all;
-        uint64_t seed;
-        const int32_t* table_each;       // per prompt (null: none has a table)
-        const int32_t* min_new_each;     // per prompt (null: 0)
-        gten_hip_decoder* dec;
-        int top_k(int j) const { return top_k_each ? top_k_each[j] : top_k_all; }
-        float temp(int j) const { return temp_each ? temp_each[j] : temp_all; }
-        int table(int j) const { return table_each ? table_each[j] : -1; }
-        int until(int j, int n_prompt) const { return (min_new_each && min_new_each[j] > 0) ? n_prompt + min_new_each[j] : 0; }
-        // the id at position `pos` = the prompt's length: under the table unless it has run out already (it cannot: min_new >= 1)
-        void draw(int j, const float* lg, int n, int32_t pos, int32_t* out) const
-        {
-            const int32_t kk = top_k(j);
-            const float t = temp(j);
-            const uint32_t st = (uint32_t)j;
-            const float* row = nullptr;
-            if (table(j) >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table(j), &row));
-            if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n, 0, row, 0, &kk, &t, seed, &st, &pos, out));
-            else GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n, 0, &kk, &t, seed, &st, &pos, out));
-        }
-        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
-        {
-            return b.prefill_picked(c, row, [&](int, const float* lg, int n, int32_t* out) { draw(j, lg, n, (int32_t)row.size(), out); });
-        }
-        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
-                  std::vector<int>* first)
-        {
-            std::vector<float*> lo((size_t)sets.size(), nullptr);
-            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
-                draw(js[(size_t)k], lg, n, (int32_t)ps[(size_t)k]->size(), out);
-            });
-        }
-        void bind(int q, int j, int n_prompt) const { GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, q, table(j), table(j) >= 0 ? until(j, n_prompt) : 0)); }
-    };
-    // BiasedServe with log-prob records (include/gten_hip_logprobs.h): prompt j asks with n_top(j) (-1: it does not).
-    // The first id's record comes from gten_hip_row_top_logprobs on the prompt's logits row, the row the id is drawn from; the request
-    // is set on whichever slot takes the prompt; the slot's records are read when the prompt ends or moves (collect), before the slot
-    // is started again; every slot's request is cleared when the queue is done.  Rows of the outputs are `row_len` positions long.
-    struct LpServe : BiasedServe {
-        static constexpr bool kLogprobs = true;
-        const int32_t* n_top_each;       // per prompt (null: nobody asks)
-        int n_top_max, row_len;
-        float* logprob;                  // [prompts][row_len]
-        int32_t* top_id;                 // [prompts][row_len][n_top_max]
-        float* top_lp;
-        void* scratch = nullptr;         // device: kPreMax first-id records (logprob | ids | logprobs)
-        int scratch_rows = 0;
-        LpServe(const BiasedServe& b, const int32_t* n_top_each_, int n_top_max_, int row_len_, float* logprob_, int32_t* top_id_, float* top_lp_)
-            : BiasedServe(b), n_top_each{n_top_each_}, n_top_max{n_top_max_}, row_len{row_len_}, logprob{logprob_}, top_id{top_id_}, top_lp{top_lp_} {}
-        LpServe(const LpServe&) = delete;
-        ~LpServe() { if (scratch) gten_hip_free(scratch); }
-        int n_top(int j) const { return n_top_each ? n_top_each[j] : -1; }
-        size_t rec_bytes() const { return sizeof(float) + (size_t)GTEN_HIP_LOGPROBS_TOP * (sizeof(int32_t) + sizeof(float)); }
-        uint8_t* rec(int k)
-        {
-            return (uint8_t*)scratch + (size_t)k * rec_bytes();
-        }
-        void ensure(int rows)
-        {
-            if (rows <= scratch_rows) return;
-            if (scratch) GTEN_HIP_OK(gten_hip_free(scratch));
-            scratch = nullptr;
-            GTEN_HIP_OK(gten_hip_malloc(&scratch, (size_t)rows * rec_bytes()));
-            scratch_rows = rows;
-        }
-        // the record of the id just drawn into `id` (device) from row lg, into scratch record k (same stream, behind the draw)
-        void first_record(int k, int j, const float* lg, int n, const int32_t* id)
-        {
-            if (n_top(j) < 0) return;
-            uint8_t* r = rec(k);
-            GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n, n, id, n_top(j), (float*)r, (int32_t*)(r + 4), (float*)(r + 4 + 4 * GTEN_HIP_LOGPROBS_TOP)));
-        }
-        // scratch record k -> prompt j's outputs at position pos (the stream has been waited for: the id was read back)
-        void first_store(int k, int j, int pos)
-        {
-            if (n_top(j) < 0 || pos >= row_len) return;
-            std::vector<uint8_t> h(rec_bytes());
-            GTEN_HIP_OK(gten_hip_memcpy_d2h(h.data(), rec(k), h.size()));
-            const int m = std::min(n_top(j), n_top_max);
-            std::memcpy(&logprob[(size_t)j * row_len + pos], h.data(), sizeof(float));
-            if (m > 0) {
-                std::memcpy(top_id + ((size_t)j * row_len + pos) * n_top_max, h.data() + 4, (size_t)m * sizeof(int32_t));
-                std::memcpy(top_lp + ((size_t)j * row_len + pos) * n_top_max, h.data() + 4 + 4 * GTEN_HIP_LOGPROBS_TOP, (size_t)m * sizeof(float));
-            }
-        }
-        int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
-        {
-            ensure(1);
-            const int id = b.prefill_picked(c, row, [&](int, const float* lg, int n, int32_t* out) {
-                this->draw(j, lg, n, (int32_t)row.size(), out);
-                first_record(0, j, lg, n, out);
-            });
-            first_store(0, j, (int)row.size());
-            return id;
-        }
-        void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
-                  std::vector<int>* first)
-        {
-            ensure((int)sets.size());
-            std::vector<float*> lo((size_t)sets.size(), nullptr);
-            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
-                this->draw(js[(size_t)k], lg, n, (int32_t)ps[(size_t)k]->size(), out);
-                first_record(k, js[(size_t)k], lg, n, out);
-            });
-            for (size_t k = 0; k < js.size(); k++) first_store((int)k, js[k], (int)ps[k]->size());
-        }
-        void ask(int q, int j) const { GTEN_HIP_OK(gten_hip_decoder_set_logprobs(this->dec, q, n_top(j))); }
-        // slot q's records of positions [from, from + count) are prompt j's
-        void collect(int q, int j, int from, int count)
-        {
-            if (n_top(j) < 0) return;
-            count = std::min(count, row_len - from);
-            if (count <= 0) return;
-            const int m = std::min(n_top(j), n_top_max);
-            std::vector<int32_t> ids((size_t)count * (size_t)std::max(m, 1));
-            std::vector<float> lps((size_t)count * (size_t)std::max(m, 1));
-            GTEN_HIP_OK(gten_hip_decoder_logprobs(this->dec, q, from, count, m, &logprob[(size_t)j * row_len + from], ids.data(), lps.data()));
-            for (int i = 0; i < count && m > 0; i++) {
-                std::memcpy(top_id + ((size_t)j * row_len + from + i) * n_top_max, ids.data() + (size_t)i * m, (size_t)m * sizeof(int32_t));
-                std::memcpy(top_lp + ((size_t)j * row_len + from + i) * n_top_max, lps.data() + (size_t)i * m, (size_t)m * sizeof(float));
-            }
-        }
-        void clear(int q) const { GTEN_HIP_OK(gten_hip_decoder_set_logprobs(this->dec, q, -1)); }
-    };
+    // How the ids are picked is `pick`'s business (host/generate.h, ServePolicy): the first id of a prompt processed onto a cache
+    // set (first / many), the requests of the slot that takes it (apply), its log-prob records (collect), everything off again (clear).
+    // (max_new[j] > 0 additionally bounds the new ids of prompt j)
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
-                          std::vector<std::vector<int32_t>>* out, int max_new, const int32_t* max_new_each, Pick& pick)
+                          std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Pick& pick)
     {
         using clock = std::chrono::steady_clock;
         ensure_decoder();
@@ -1260,7 +1068,7 @@ public:
                 const int P = (int)row.size();
                 GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
                 st.prompt_tokens += P;
-                const int mn = max_new_each ? max_new_each[j] : max_new;
+                const int mn = max_new[j];
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);   // ids in all
                 if (P >= limit) continue;                                  // no room to generate: returned as is
                 const auto t0 = clock::now();
@@ -1297,7 +1105,7 @@ public:
                 next++;
                 (*out)[(size_t)j] = prompts[(size_t)j];
                 st.prompt_tokens += P;
-                const int mn = max_new_each ? max_new_each[j] : max_new;
+                const int mn = max_new[j];
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);
                 if (P >= limit) continue;                                    // no room to generate: returned as is
                 js.push_back(j); limits.push_back(limit); rows += cost;
@@ -1380,10 +1188,8 @@ public:
                     set_of[(size_t)q] = r.set; job[(size_t)q] = r.j; cur[(size_t)q] = r.cur; last[(size_t)q] = r.last;
                     // (all joining slots in one call below: their ids, step words and cache-table rows go up behind each other, one wait)
                     ap_seq.push_back(q); ap_first.push_back(r.cur); ap_last.push_back(r.last); ap_tok.push_back(row.data());
-                    if constexpr (Pick::kSampled)
-                        GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, pick.top_k(r.j), pick.temp(r.j), pick.seed, (uint32_t)r.j));
-                    if constexpr (Pick::kBiased) pick.bind(q, r.j, (int)prompts[(size_t)r.j].size());      // (travels with the request: also when a sequence moves in the tail)
-                    if constexpr (Pick::kLogprobs) { pick.ask(q, r.j); lp_from[(size_t)q] = r.cur; }
+                    pick.apply(q, r.j, (int)prompts[(size_t)r.j].size());                                  // (travels with the prompt: also when a sequence moves in the tail)
+                    lp_from[(size_t)q] = r.cur;
                     live[(size_t)q] = 1; n_live++;
                 }
             }
@@ -1477,12 +1283,7 @@ public:
         // generate -- addresses slot q as sequence q
         for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_slot_bind(dec_, q, set_kv(q)));
         rebind.done = true;
-        if constexpr (Pick::kSampled)
-            for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_sampling(dec_, q, 0, 0.f, 0, 0));     // every slot greedy again
-        if constexpr (Pick::kBiased)
-            for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec_, q, -1, 0));                // ... and unbound
-        if constexpr (Pick::kLogprobs)
-            for (int q = 0; q < S; q++) pick.clear(q);                                                             // ... and nobody asks
+        pick.clear();                                                      // every slot greedy again, unbound, and nobody asks
         return st;
     }
 
@@ -1587,173 +1388,6 @@ inline int greedy_sample(TinyLlama& model, std::vector<int32_t>& tokens, const i
         tokens.push_back(best_i);
     }
     return (int)tokens.size();
-}
-
-// The same loop with the sampler on the device: the prompt is processed as in the reference (iteration 0 above, host
-// argmax of its logits), every later token comes from back-to-back graph replays whose argmax feeds the next step on the
-// device -- no logits copy, no host argmax, no host round trip per token.  Same ids as greedy_sample (tested).
-inline int greedy_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos)
-{
-    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
-    {
-        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
-        Tensor logits = model.logits(input, 0);
-        const int n = logits.numel();
-        const float* p = const_cast<const Tensor&>(logits).data_ptr<float>();
-        float best = -std::numeric_limits<float>::infinity();
-        int best_i = 0;
-        for (int j = 0; j < n; j++)
-            if (p[j] > best) { best = p[j]; best_i = j; }
-        if (best_i == eos) return (int)tokens.size();
-        tokens.push_back(best_i);
-    }
-    const int n_first = (int)tokens.size();
-    const int max_new = n_predict - n_first;
-    if (max_new <= 0) return n_first;
-    std::vector<int32_t> out((size_t)max_new);
-    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
-    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
-    return (int)tokens.size();
-}
-
-// One id drawn on the device from a logits row in HBM (gten_hip_sample_rows): the id that will sit at position `pos`.
-inline int sample_row(const float* logits_dev, int n_vocab, int top_k, float temp, uint64_t seed, uint32_t stream, int pos)
-{
-    Tensor id({1}, kInt32);
-    const int32_t k = top_k, p = pos;
-    GTEN_HIP_OK(gten_hip_sample_rows(logits_dev, 1, n_vocab, 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
-    int32_t got = -1;
-    GTEN_HIP_OK(gten_hip_memcpy_d2h(&got, id.device_ptr(), sizeof(got)));
-    return got;
-}
-
-// greedy_generate with top-k sampling (include/gten_hip_sample.h): the prompt's first id is drawn from its logits on the
-// device, every later one by the decoder's sampler; the request is dropped again afterwards (the decoder's later steps
-// are greedy).  top_k 0 gives greedy_generate's ids.  -1 when the decoder refuses the request (gten_hip_last_error).
-inline int sampled_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
-                            uint64_t seed, uint32_t stream)
-{
-    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
-    {
-        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
-        const Tensor logits = model.logits(input, 0);
-        const int first = sample_row((const float*)logits.device_ptr(), logits.numel(), top_k, temp, seed, stream, (int)tokens.size());
-        if (first == eos) return (int)tokens.size();
-        tokens.push_back(first);
-    }
-    const int n_first = (int)tokens.size();
-    const int max_new = n_predict - n_first;
-    if (max_new <= 0) return n_first;
-    std::vector<int32_t> out((size_t)max_new);
-    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) return -1;
-    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
-    GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
-    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
-    return (int)tokens.size();
-}
-
-// sampled_generate under bias table `table` of the model's decoder (include/gten_hip_bias.h; -1: none), which holds
-// for the first min_new new ids (0: for all of them): the prompt's first id is drawn from y = logits + table row by the operator,
-// every later one inside the decode step.  top_k 0: greedy over y.  Request and binding are dropped again afterwards.
-// -1 when the decoder refuses (gten_hip_last_error).
-inline int biased_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
-                           uint64_t seed, uint32_t stream, int table, int min_new)
-{
-    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
-    gten_hip_decoder* dec = model.decoder_handle();
-    const int until = (table >= 0 && min_new > 0) ? (int)tokens.size() + min_new : 0;
-    if (gten_hip_decoder_set_seq_bias(dec, 0, table, until) != 0) return -1;
-    auto unbind = [&]() { GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, 0, -1, 0)); };
-    {
-        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
-        const Tensor logits = model.logits(input, 0);
-        const float* row = nullptr;
-        if (table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table, &row));
-        Tensor id({1}, kInt32);
-        const int32_t k = top_k, p = (int32_t)tokens.size();
-        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased((const float*)logits.device_ptr(), 1, logits.numel(), 0, row, 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
-        else GTEN_HIP_OK(gten_hip_sample_rows((const float*)logits.device_ptr(), 1, logits.numel(), 0, &k, &temp, seed, &stream, &p, (int32_t*)id.device_ptr_mut()));
-        int32_t first = -1;
-        GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
-        if (first == eos) { unbind(); return (int)tokens.size(); }
-        tokens.push_back(first);
-    }
-    const int n_first = (int)tokens.size();
-    const int max_new = n_predict - n_first;
-    if (max_new <= 0) { unbind(); return n_first; }
-    std::vector<int32_t> out((size_t)max_new);
-    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) { unbind(); return -1; }
-    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
-    GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
-    unbind();
-    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
-    return (int)tokens.size();
-}
-
-// biased_generate that also reports every new id's log-prob and its n_top alternatives (include/gten_hip_logprobs.h):
-// logprob [tokens.size()], top_id / top_lp [tokens.size()][n_top], aligned with the ids (prompt positions: 0 / -1).  The first new
-// id's record comes from gten_hip_row_top_logprobs on the prompt's logits row, the row the id is drawn from; the later ones are the
-// decoder's records.  Request, binding and log-prob request are dropped again afterwards.  -1 when the decoder refuses.
-inline int logprobs_generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, int top_k, float temp,
-                             uint64_t seed, uint32_t stream, int table, int min_new, int n_top, std::vector<float>* logprob,
-                             std::vector<int32_t>* top_id, std::vector<float>* top_lp)
-{
-    const size_t W = (size_t)n_top;
-    auto size_outputs = [&]() {
-        logprob->resize(tokens.size(), 0.f);
-        top_id->resize(tokens.size() * W, -1);
-        top_lp->resize(tokens.size() * W, 0.f);
-    };
-    logprob->clear(); top_id->clear(); top_lp->clear();
-    size_outputs();
-    if ((int)tokens.size() >= n_predict) return (int)tokens.size();
-    gten_hip_decoder* dec = model.decoder_handle();
-    const int until = (table >= 0 && min_new > 0) ? (int)tokens.size() + min_new : 0;
-    if (gten_hip_decoder_set_seq_bias(dec, 0, table, until) != 0) return -1;
-    auto drop = [&]() {
-        GTEN_HIP_OK(model.decode_set_sampling(0, 0.f, 0, 0));
-        GTEN_HIP_OK(gten_hip_decoder_set_seq_bias(dec, 0, -1, 0));
-        GTEN_HIP_OK(gten_hip_decoder_set_logprobs(dec, 0, -1));
-    };
-    if (gten_hip_decoder_set_logprobs(dec, 0, n_top) != 0) { drop(); return -1; }
-    {
-        Tensor input{tokens.data(), {(int)tokens.size()}, kInt32};
-        const Tensor logits = model.logits(input, 0);
-        const float* lg = (const float*)logits.device_ptr();
-        const float* row = nullptr;
-        if (table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, table, &row));
-        Tensor id({1}, kInt32), rec_lp({1}, kFloat32), rec_id({GTEN_HIP_LOGPROBS_TOP}, kInt32), rec_tl({GTEN_HIP_LOGPROBS_TOP}, kFloat32);
-        int32_t* id_dev = (int32_t*)id.device_ptr_mut();
-        const int32_t k = top_k, p = (int32_t)tokens.size();
-        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, logits.numel(), 0, row, 0, &k, &temp, seed, &stream, &p, id_dev));
-        else GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, logits.numel(), 0, &k, &temp, seed, &stream, &p, id_dev));
-        GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, logits.numel(), logits.numel(), id_dev, n_top, (float*)rec_lp.device_ptr_mut(),
-                                              (int32_t*)rec_id.device_ptr_mut(), (float*)rec_tl.device_ptr_mut()));
-        int32_t first = -1;
-        GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
-        if (first == eos) { drop(); return (int)tokens.size(); }
-        tokens.push_back(first);
-        size_outputs();
-        GTEN_HIP_OK(gten_hip_memcpy_d2h(&logprob->back(), rec_lp.device_ptr(), sizeof(float)));
-        if (n_top > 0) {
-            GTEN_HIP_OK(gten_hip_memcpy_d2h(top_id->data() + (tokens.size() - 1) * W, rec_id.device_ptr(), W * sizeof(int32_t)));
-            GTEN_HIP_OK(gten_hip_memcpy_d2h(top_lp->data() + (tokens.size() - 1) * W, rec_tl.device_ptr(), W * sizeof(float)));
-        }
-    }
-    const int n_first = (int)tokens.size();
-    const int max_new = n_predict - n_first;
-    if (max_new <= 0) { drop(); return n_first; }
-    std::vector<int32_t> out((size_t)max_new);
-    if (model.decode_set_sampling(top_k, temp, seed, stream) != 0) { drop(); return -1; }
-    const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
-    tokens.insert(tokens.end(), out.begin(), out.begin() + got);
-    size_outputs();
-    int rc = 0;
-    if (got > 0)
-        rc = gten_hip_decoder_logprobs(dec, 0, n_first, got, n_top, logprob->data() + n_first, top_id->data() + (size_t)n_first * W,
-                                       top_lp->data() + (size_t)n_first * W);
-    drop();
-    return rc ? -1 : (int)tokens.size();
 }
 
 } // namespace gten

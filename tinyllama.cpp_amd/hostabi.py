@@ -203,6 +203,62 @@ def bias_pairs(pairs=(), fill=0.0, allow=None):
     return ids, values, float(fill)
 
 
+SERVE_STATS = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
+
+
+def _ptr(a):
+    """a numpy array (or None) as a C pointer argument; the pointer keeps the array alive"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _pack(prompts):
+    """(prompts as one zero-padded int32 matrix [n][longest], lengths int32 [n], longest)"""
+    mp = max(len(p) for p in prompts)
+    pr, npr = np.zeros((len(prompts), mp), np.int32), np.zeros(len(prompts), np.int32)
+    for j, p in enumerate(prompts):
+        pr[j, : len(p)] = p
+        npr[j] = len(p)
+    return pr, npr, mp
+
+
+def _each(v, n, dt, full=False):
+    """(array or None, scalar) of a per-item list or one value for all; full: the one value becomes an array too (None stays None)"""
+    if v is None:
+        return None, None
+    if np.isscalar(v):
+        return (np.full(n, v, dt), None) if full else (None, v)
+    a = np.ascontiguousarray(v, dtype=dt)
+    assert len(a) == n
+    return a, None
+
+
+def _request_args(n, top_k, temp, seed):
+    """top_k / temp (a scalar or one value per item) and the seed as the C ABI takes them: arrays or null, then the values for all"""
+    (ks, k1), (ts, t1) = _each(top_k, n, np.int32), _each(temp, n, np.float32)
+    return [_ptr(ks), _ptr(ts), 0 if ks is not None else int(k1), 1.0 if ts is not None else float(t1), C.c_uint64(int(seed))]
+
+
+def _full_args(n, *pairs):
+    """(value, dtype) pairs -- streams, tables, min_new: None, one value for all or one per item -- as full arrays or null"""
+    return [_ptr(_each(v, n, dt, full=True)[0]) for v, dt in pairs]
+
+
+def _n_tops(n_top, n):
+    """(int32[n] or None, width of the outputs) of a per-item n_top request (a scalar: for all; None / -1: that item does not ask)"""
+    if n_top is None:
+        return None, 0
+    a = np.full(n, n_top, np.int32) if np.isscalar(n_top) else np.ascontiguousarray([-1 if v is None else v for v in n_top], dtype=np.int32)
+    assert len(a) == n
+    return a, max(int(a.max()), 0)
+
+
+def _records(n_top, n, width):
+    """the record arguments behind a per-item n_top request, and the outputs they fill: ([n_top, widest, lp, ids, lps], (lp, ids, lps))"""
+    nt, tw = _n_tops(n_top, n)
+    lp, ti, tl = np.zeros((n, width), np.float32), np.full((n, width, tw), -1, np.int32), np.zeros((n, width, tw), np.float32)
+    return [_ptr(nt), tw, _ptr(lp), _ptr(ti), _ptr(tl)], (lp, ti, tl)
+
+
 class HostTokenizer:
     def __init__(self, host, path, vocab_size):
         self.host = host
@@ -547,37 +603,32 @@ class HostBatch:
         assert len(ns) == self.n_seq
         self._ck(self.host._bstepr(self.h, ns.ctypes.data_as(C.c_void_p), 1 if use_graph else 0), "batch_decode_step_ragged")
 
+    def _generate(self, fn, what, prompts, max_tokens, eos, requests=(), records=()):
+        """one fixed-batch entry point: fn(handle, prompts, lengths, longest, max_tokens, eos, *requests, ids out, totals out, *records)"""
+        assert len(prompts) == self.n_seq
+        pr, npr, mp = _pack(prompts)
+        out, tot = np.zeros((self.n_seq, max_tokens), np.int32), np.zeros(self.n_seq, np.int32)
+        self._ck(fn(self.h, _ptr(pr), _ptr(npr), mp, max_tokens, eos, *requests, _ptr(out), _ptr(tot), *records), what)
+        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+
+    def _serve(self, fn, what, prompts, max_tokens, eos, slice_steps, max_new, max_new_each, *extra):
+        """one serve entry point: gten_host_batch_serve2's arguments, then `extra`; returns (ids per prompt, the stats dict)"""
+        n = len(prompts)
+        pr, npr, mp = _pack(prompts)
+        out, tot, st = np.zeros((n, max(max_tokens, mp)), np.int32), np.zeros(n, np.int32), np.zeros(len(SERVE_STATS), np.float64)
+        each, _ = _each(max_new_each, n, np.int32)
+        self._ck(fn(self.h, _ptr(pr), _ptr(npr), n, mp, max_tokens, eos, slice_steps, max_new, _ptr(each), _ptr(out), _ptr(tot), _ptr(st), len(st), *extra), what)
+        return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(SERVE_STATS, st.tolist()))
+
     def generate(self, prompts, max_tokens, eos=-1):
         """greedy generation of every sequence (sampler on the device): list of id arrays, one per sequence, prompt included"""
-        assert len(prompts) == self.n_seq
-        mp = max(len(p) for p in prompts)
-        pr = np.zeros((self.n_seq, mp), np.int32)
-        npr = np.zeros(self.n_seq, np.int32)
-        for q, p in enumerate(prompts):
-            pr[q, : len(p)] = p
-            npr[q] = len(p)
-        out = np.zeros((self.n_seq, max_tokens), np.int32)
-        tot = np.zeros(self.n_seq, np.int32)
-        self._ck(self.host._bgen(self.h, pr.ctypes.data_as(C.c_void_p), npr.ctypes.data_as(C.c_void_p), mp, max_tokens, eos,
-                                 out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p)), "batch_generate")
-        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+        return self._generate(self.host._bgen, "batch_generate", prompts, max_tokens, eos)
 
     def generate_topk(self, prompts, max_tokens, eos, top_k, temp, seed, streams=None):
         """generate() with every new id drawn by the device sampler; sequence q uses streams[q] (None: q)"""
-        assert len(prompts) == self.n_seq
-        mp = max(len(p) for p in prompts)
-        pr = np.zeros((self.n_seq, mp), np.int32)
-        npr = np.zeros(self.n_seq, np.int32)
-        for q, p in enumerate(prompts):
-            pr[q, : len(p)] = p
-            npr[q] = len(p)
         st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
-        out = np.zeros((self.n_seq, max_tokens), np.int32)
-        tot = np.zeros(self.n_seq, np.int32)
-        self._ck(self.host._bgen_topk(self.h, pr.ctypes.data_as(C.c_void_p), npr.ctypes.data_as(C.c_void_p), mp, max_tokens, eos, int(top_k),
-                                      float(temp), C.c_uint64(int(seed)), None if st is None else st.ctypes.data_as(C.c_void_p),
-                                      out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p)), "batch_generate_topk")
-        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+        return self._generate(self.host._bgen_topk, "batch_generate_topk", prompts, max_tokens, eos,
+                              [int(top_k), float(temp), C.c_uint64(int(seed)), _ptr(st)])
 
     def set_serve_schedule(self, k):
         """tests: exactly k prompts beside every slice (0: as many as fit while it runs)"""
@@ -594,47 +645,13 @@ class HostBatch:
     def serve(self, prompts, max_tokens, eos=-1, slice_steps=16, max_new=0, max_new_each=None):
         """continuous batching: the queue `prompts` (any number) through this batch's slots; returns (list of id
         arrays -- prompt + new ids, one per prompt, in queue order -- and a dict of counters)"""
-        mp = max(len(p) for p in prompts)
-        width = max(max_tokens, mp)
-        pr = np.zeros((len(prompts), mp), np.int32)
-        npr = np.zeros(len(prompts), np.int32)
-        for j, p in enumerate(prompts):
-            pr[j, : len(p)] = p
-            npr[j] = len(p)
-        out = np.zeros((len(prompts), width), np.int32)
-        tot = np.zeros(len(prompts), np.int32)
-        st = np.zeros(9, np.float64)
-        each = None if max_new_each is None else np.ascontiguousarray(max_new_each, dtype=np.int32)
-        assert each is None or len(each) == len(prompts)
-        self._ck(self.host._bserve(self.h, pr.ctypes.data_as(C.c_void_p), npr.ctypes.data_as(C.c_void_p), len(prompts), mp, max_tokens, eos,
-                                   slice_steps, max_new, None if each is None else each.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), tot.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p), len(st)),
-                 "batch_serve")
-        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
-        return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
+        return self._serve(self.host._bserve, "batch_serve", prompts, max_tokens, eos, slice_steps, max_new, max_new_each)
 
     def serve_topk(self, prompts, max_tokens, eos, top_k, temp, seed, slice_steps=16, max_new=0, max_new_each=None):
         """serve() with every new id drawn by the device sampler: top_k / temp a scalar or one value per prompt (top_k 0: greedy),
         prompt j draws with stream j"""
-        mp = max(len(p) for p in prompts)
-        width = max(max_tokens, mp)
-        pr = np.zeros((len(prompts), mp), np.int32)
-        npr = np.zeros(len(prompts), np.int32)
-        for j, p in enumerate(prompts):
-            pr[j, : len(p)] = p
-            npr[j] = len(p)
-        out = np.zeros((len(prompts), width), np.int32)
-        tot = np.zeros(len(prompts), np.int32)
-        st = np.zeros(9, np.float64)
-        each = None if max_new_each is None else np.ascontiguousarray(max_new_each, dtype=np.int32)
-        ks = None if np.isscalar(top_k) else np.ascontiguousarray(top_k, dtype=np.int32)
-        ts = None if np.isscalar(temp) else np.ascontiguousarray(temp, dtype=np.float32)
-        assert (ks is None or len(ks) == len(prompts)) and (ts is None or len(ts) == len(prompts))
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self.host._bserve_topk(self.h, ptr(pr), ptr(npr), len(prompts), mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out),
-                                        ptr(tot), ptr(st), len(st), ptr(ks), ptr(ts), int(top_k) if ks is None else 0,
-                                        float(temp) if ts is None else 1.0, C.c_uint64(int(seed))), "batch_serve_topk")
-        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
-        return [out[j, : tot[j]].copy() for j in range(len(prompts))], dict(zip(keys, st.tolist()))
+        return self._serve(self.host._bserve_topk, "batch_serve_topk", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                           *_request_args(len(prompts), top_k, temp, seed))
 
     def set_bias_table_rc(self, table, pairs=(), fill=0.0, allow=None):
         """gten_host_batch_set_bias_table's return code (0, or the refusal: the table keeps its contents)"""
@@ -667,70 +684,18 @@ class HostBatch:
             raise GtenHipError(f"batch_bias_info rc={n}")
         return n, t, u
 
-    @staticmethod
-    def _each(v, n, dt):
-        """(array or None, scalar): a per-item list, or one value for all"""
-        if v is None or np.isscalar(v):
-            return None, v
-        a = np.ascontiguousarray(v, dtype=dt)
-        assert len(a) == n
-        return a, None
-
     def generate_biased(self, prompts, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, tables=None, min_new=None):
         """generate_topk() with a request per sequence: top_k / temp a scalar or a list, tables[q] (-1 / None: no table) and
         min_new[q] (0 / None: the table holds throughout)"""
-        assert len(prompts) == self.n_seq
-        mp = max(len(p) for p in prompts)
-        pr = np.zeros((self.n_seq, mp), np.int32)
-        npr = np.zeros(self.n_seq, np.int32)
-        for q, p in enumerate(prompts):
-            pr[q, : len(p)] = p
-            npr[q] = len(p)
-        (ks, k1), (ts, t1) = self._each(top_k, self.n_seq, np.int32), self._each(temp, self.n_seq, np.float32)
-        st, st1 = self._each(streams, self.n_seq, np.uint32)
-        if st is None and st1 is not None:
-            st = np.full(self.n_seq, st1, np.uint32)
-        tb, tb1 = self._each(tables, self.n_seq, np.int32)
-        mn, mn1 = self._each(min_new, self.n_seq, np.int32)
-        if tb is None and tb1 is not None:
-            tb = np.full(self.n_seq, tb1, np.int32)
-        if mn is None and mn1 is not None:
-            mn = np.full(self.n_seq, mn1, np.int32)
-        out = np.zeros((self.n_seq, max_tokens), np.int32)
-        tot = np.zeros(self.n_seq, np.int32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self.host._bgen_biased(self.h, ptr(pr), ptr(npr), mp, max_tokens, eos, ptr(ks), ptr(ts), 0 if ks is not None else int(k1),
-                                        1.0 if ts is not None else float(t1), C.c_uint64(int(seed)), ptr(st), ptr(tb), ptr(mn), ptr(out), ptr(tot)),
-                 "batch_generate_biased")
-        return [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+        n = self.n_seq
+        return self._generate(self.host._bgen_biased, "batch_generate_biased", prompts, max_tokens, eos,
+                              _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)))
 
     def serve_biased(self, prompts, max_tokens, eos, top_k, temp, seed, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None):
         """serve_topk() with a bias table (-1: none) and a min_new (0: the table holds throughout) per prompt"""
         n = len(prompts)
-        mp = max(len(p) for p in prompts)
-        width = max(max_tokens, mp)
-        pr = np.zeros((n, mp), np.int32)
-        npr = np.zeros(n, np.int32)
-        for j, p in enumerate(prompts):
-            pr[j, : len(p)] = p
-            npr[j] = len(p)
-        out = np.zeros((n, width), np.int32)
-        tot = np.zeros(n, np.int32)
-        st = np.zeros(9, np.float64)
-        each, _ = self._each(max_new_each, n, np.int32)
-        (ks, k1), (ts, t1) = self._each(top_k, n, np.int32), self._each(temp, n, np.float32)
-        tb, tb1 = self._each(tables, n, np.int32)
-        mn, mn1 = self._each(min_new, n, np.int32)
-        if tb is None and tb1 is not None:
-            tb = np.full(n, tb1, np.int32)
-        if mn is None and mn1 is not None:
-            mn = np.full(n, mn1, np.int32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self.host._bserve_biased(self.h, ptr(pr), ptr(npr), n, mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out), ptr(tot),
-                                          ptr(st), len(st), ptr(ks), ptr(ts), 0 if ks is not None else int(k1), 1.0 if ts is not None else float(t1),
-                                          C.c_uint64(int(seed)), ptr(tb), ptr(mn)), "batch_serve_biased")
-        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
-        return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(keys, st.tolist()))
+        return self._serve(self.host._bserve_biased, "batch_serve_biased", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                           *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)))
 
     def set_logprobs_rc(self, seq, n_top):
         return self.host._b_set_lp(self.h, int(seq), int(n_top))
@@ -750,78 +715,24 @@ class HostBatch:
             raise GtenHipError(f"batch_logprobs rc={rc}: {self.host.hip._err().decode(errors='replace')}")
         return lp, ti, tl
 
-    @staticmethod
-    def _n_tops(n_top, n):
-        """(int32[n] or None, width of the outputs) of a per-item n_top request (a scalar: for all; None / -1: that item does not ask)"""
-        if n_top is None:
-            return None, 0
-        a = np.full(n, n_top, np.int32) if np.isscalar(n_top) else np.ascontiguousarray([-1 if v is None else v for v in n_top], dtype=np.int32)
-        assert len(a) == n
-        return a, max(int(a.max()), 0)
-
     def generate_logprobs(self, prompts, max_tokens, n_top, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, tables=None, min_new=None):
         """generate_biased() plus the records of the sequences that ask (n_top a scalar or a list, -1 / None: not this one): returns
         (ids per sequence, logprob [n_seq][max_tokens], top_id [n_seq][max_tokens][max n_top], top_logprob), aligned with the ids"""
-        assert len(prompts) == self.n_seq
-        mp = max(len(p) for p in prompts)
-        pr = np.zeros((self.n_seq, mp), np.int32)
-        npr = np.zeros(self.n_seq, np.int32)
-        for q, p in enumerate(prompts):
-            pr[q, : len(p)] = p
-            npr[q] = len(p)
-        (ks, k1), (ts, t1) = self._each(top_k, self.n_seq, np.int32), self._each(temp, self.n_seq, np.float32)
-        st, st1 = self._each(streams, self.n_seq, np.uint32)
-        if st is None and st1 is not None:
-            st = np.full(self.n_seq, st1, np.uint32)
-        tb, tb1 = self._each(tables, self.n_seq, np.int32)
-        mn, mn1 = self._each(min_new, self.n_seq, np.int32)
-        if tb is None and tb1 is not None:
-            tb = np.full(self.n_seq, tb1, np.int32)
-        if mn is None and mn1 is not None:
-            mn = np.full(self.n_seq, mn1, np.int32)
-        nt, width = self._n_tops(n_top, self.n_seq)
-        out = np.zeros((self.n_seq, max_tokens), np.int32)
-        tot = np.zeros(self.n_seq, np.int32)
-        lp = np.zeros((self.n_seq, max_tokens), np.float32)
-        ti, tl = np.full((self.n_seq, max_tokens, width), -1, np.int32), np.zeros((self.n_seq, max_tokens, width), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self.host._bgen_lp(self.h, ptr(pr), ptr(npr), mp, max_tokens, eos, ptr(ks), ptr(ts), 0 if ks is not None else int(k1),
-                                    1.0 if ts is not None else float(t1), C.c_uint64(int(seed)), ptr(st), ptr(tb), ptr(mn), ptr(out), ptr(tot),
-                                    ptr(nt), width, ptr(lp), ptr(ti), ptr(tl)), "batch_generate_lp")
-        return [out[q, : tot[q]].copy() for q in range(self.n_seq)], lp, ti, tl
+        n = self.n_seq
+        args, rec = _records(n_top, n, max_tokens)
+        ids = self._generate(self.host._bgen_lp, "batch_generate_lp", prompts, max_tokens, eos,
+                             _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)), args)
+        return (ids, *rec)
 
     def serve_logprobs(self, prompts, max_tokens, eos, top_k, temp, seed, n_top, tables=None, min_new=None, slice_steps=16, max_new=0,
                        max_new_each=None):
         """serve_biased() plus the records of the prompts that ask (n_top per prompt, -1 / None: not this one): returns
         (ids per prompt, stats, logprob [n][width], top_id [n][width][max n_top], top_logprob), width = max(max_tokens, longest prompt)"""
         n = len(prompts)
-        mp = max(len(p) for p in prompts)
-        width = max(max_tokens, mp)
-        pr = np.zeros((n, mp), np.int32)
-        npr = np.zeros(n, np.int32)
-        for j, p in enumerate(prompts):
-            pr[j, : len(p)] = p
-            npr[j] = len(p)
-        out = np.zeros((n, width), np.int32)
-        tot = np.zeros(n, np.int32)
-        st = np.zeros(9, np.float64)
-        each, _ = self._each(max_new_each, n, np.int32)
-        (ks, k1), (ts, t1) = self._each(top_k, n, np.int32), self._each(temp, n, np.float32)
-        tb, tb1 = self._each(tables, n, np.int32)
-        mn, mn1 = self._each(min_new, n, np.int32)
-        if tb is None and tb1 is not None:
-            tb = np.full(n, tb1, np.int32)
-        if mn is None and mn1 is not None:
-            mn = np.full(n, mn1, np.int32)
-        nt, tw = self._n_tops(n_top, n)
-        lp = np.zeros((n, width), np.float32)
-        ti, tl = np.full((n, width, tw), -1, np.int32), np.zeros((n, width, tw), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self.host._bserve_lp(self.h, ptr(pr), ptr(npr), n, mp, max_tokens, eos, slice_steps, max_new, ptr(each), ptr(out), ptr(tot),
-                                      ptr(st), len(st), ptr(ks), ptr(ts), 0 if ks is not None else int(k1), 1.0 if ts is not None else float(t1),
-                                      C.c_uint64(int(seed)), ptr(tb), ptr(mn), ptr(nt), tw, ptr(lp), ptr(ti), ptr(tl)), "batch_serve_lp")
-        keys = ("prompt_tokens", "new_tokens", "steps", "admissions", "prefill_s", "decode_s", "lane_steps", "lane_rows", "moved")
-        return [out[j, : tot[j]].copy() for j in range(n)], dict(zip(keys, st.tolist())), lp, ti, tl
+        args, rec = _records(n_top, n, max(max_tokens, max(len(p) for p in prompts)))
+        ids, st = self._serve(self.host._bserve_lp, "batch_serve_lp", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                              *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args)
+        return (ids, st, *rec)
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""
