@@ -27,6 +27,7 @@
 #include "gten_hip_sample.h"
 #include "gten_hip_bias.h"
 #include "gten_hip_logprobs.h"
+#include "gten_hip_nucleus.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 
@@ -104,6 +105,9 @@ enum { EPI_RAW = 0, EPI_SILUMUL = 1, EPI_STAGE = 2, EPI_STAGE_FRAG = 3 };
 #include "gten_decode_sample.h"
 #include "gten_decode_logprobs.h"
 static_assert(LP_TOP == GTEN_HIP_LOGPROBS_TOP && sizeof(LpRecord) == GTEN_HIP_LOGPROBS_RECORD_BYTES, "gten_decode_logprobs.h and include/gten_hip_logprobs.h disagree");
+#include "gten_decode_nucleus.h"
+static_assert(CUT_MASS_BITS == GTEN_HIP_NUCLEUS_MASS_BITS && sizeof(CutInfo) == GTEN_HIP_NUCLEUS_INFO_BYTES && sizeof(CutInfo) == sizeof(gten_hip_cut_info),
+              "gten_decode_nucleus.h and include/gten_hip_nucleus.h disagree");
 
 // --------------------------------------------------------------- host side
 
@@ -169,6 +173,12 @@ struct gten_hip_decoder {
     LpRecord* lp = nullptr;
     int n_asking = 0;                   // sequences with a log-prob request
     bool lp_on = false;
+    // top-p / min-p cuts (include/gten_hip_nucleus.h): [n_seq] beside `samp`, made by the first sequence that sets a cut
+    // (cut_on: the graphs captured before are dropped once).  From then on the sampler launch is k_dec_sample_cut, which treats sequences
+    // without a cut as k_dec_sample_lp does.  A cut only acts on a sampling sequence, so it does not enter sampler_on.
+    CutParam* cut = nullptr;
+    std::vector<CutParam> cut_host;
+    bool cut_on = false;
     hipGraph_t s_graph = nullptr, s_graph_k = nullptr, s_graph_m[1 << DEC_MAX_LANES] = {}, s_graph_km[1 << DEC_MAX_LANES] = {};
     hipGraphExec_t s_exec = nullptr, s_exec_k = nullptr, s_exec_m[1 << DEC_MAX_LANES] = {}, s_exec_km[1 << DEC_MAX_LANES] = {};
     unsigned lane_mask = 0;             // lanes the NEXT enqueue takes (0: all)
@@ -222,7 +232,7 @@ static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->n_samplin
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
     int n_seq;
-    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp;
+    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp; const CutParam* cut;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -240,6 +250,7 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     b.n_seq = (int)SL;
     b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->samp + o;
     b.lp = dc->lp ? dc->lp + o * (d.max_ctx + 2) : nullptr;
+    b.cut = dc->cut ? dc->cut + o : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -645,7 +656,10 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
-    if (sampler_on(dc) && dc->lp_on)
+    if (sampler_on(dc) && dc->cut_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2, (const CutParam*)dc->cut);
+    else if (sampler_on(dc) && dc->lp_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
                    dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
     else if (sampler_on(dc) && dc->bias_on)
@@ -795,7 +809,10 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    if (sampler_on(dc) && dc->lp_on)
+    if (sampler_on(dc) && dc->cut_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
+                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2, (const CutParam*)dc->cut);
+    else if (sampler_on(dc) && dc->lp_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
                    dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
     else if (sampler_on(dc) && dc->bias_on)
@@ -1278,7 +1295,10 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     sf.act_q = b.stg_q; sf.act_d = b.stg_d; sf.act_sum = b.stg_sum; sf.act_f = b.stg_f;
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
-    if (sampler_on(dc) && dc->lp_on)
+    if (sampler_on(dc) && dc->cut_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
+                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias, b.lp, d.max_ctx + 2, b.cut);
+    else if (sampler_on(dc) && dc->lp_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
                    b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias, b.lp, d.max_ctx + 2);
     else if (sampler_on(dc) && dc->bias_on)
@@ -1680,7 +1700,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias, dc->lp,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias, dc->lp, dc->cut,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
@@ -2789,6 +2809,95 @@ int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long
     GTR_REQUIRE(logits && ids && logprob_out && (n_top == 0 || (top_id_out && top_logprob_out)), "row_top_logprobs: null argument");
     GTR_LAUNCH(KT_DEC_SAMPLE, k_row_top_logprobs, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, ids, n_top, logprob_out, top_id_out,
                top_logprob_out);
+    return 0;
+}
+
+// ---- top-p / min-p cuts (include/gten_hip_nucleus.h, gten_decode_nucleus.h)
+static int cut_check(float top_p, float min_p, const char* who)
+{
+    GTR_REQUIRE(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "%s: top_p %g outside (0, 1]", who, (double)top_p);
+    GTR_REQUIRE(std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f, "%s: min_p %g outside [0, 1]", who, (double)min_p);
+    return 0;
+}
+static CutParam cut_param(float top_p, float min_p)
+{
+    return CutParam{top_p, min_p > 0.f ? (float)std::log((double)min_p) : -INFINITY, min_p, (top_p == 1.f && min_p == 0.f) ? 0u : 1u};
+}
+
+int gten_hip_decoder_set_cut(gten_hip_decoder* dc, int seq, float top_p, float min_p)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_cut: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    if (int rc = cut_check(top_p, min_p, "decoder_set_cut")) return rc;
+    const CutParam c = cut_param(top_p, min_p);
+    GTR_REQUIRE(c.on == 0u || !dc->persist_on, "decoder_set_cut: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    if (c.on == 0u && !dc->cut_on) return 0;       // nobody has ever cut: nothing to clear
+    if (!dc->cut_on) {
+        // the first cut of this decoder: the array, and from now on its sampler launch is the one that reads it
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        dc->cut_host.assign((size_t)dc->n_seq, cut_param(1.f, 0.f));
+        if (!dc->cut) GTR_CHECK(hipMalloc((void**)&dc->cut, (size_t)dc->n_seq * sizeof(CutParam)));
+        GTR_CHECK(hipMemcpyAsync(dc->cut, dc->cut_host.data(), dc->cut_host.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        GTR_CHECK(drop_graphs(dc));
+        dc->cut_on = true;
+    }
+    dc->cut_host[(size_t)seq] = c;
+    GTR_CHECK(hipMemcpyAsync(dc->cut + seq, &dc->cut_host[(size_t)seq], sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_cut_info(gten_hip_decoder* dc, float* top_p_host, float* min_p_host, float* t_host, int* on)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_cut_info: null decoder");
+    for (int q = 0; q < dc->n_seq; q++) {
+        const CutParam c = dc->cut_on ? dc->cut_host[(size_t)q] : cut_param(1.f, 0.f);
+        if (top_p_host) top_p_host[q] = c.top_p;
+        if (min_p_host) min_p_host[q] = c.min_p;
+        if (t_host) t_host[q] = c.t;
+    }
+    if (on) *on = dc->cut_on ? 1 : 0;
+    return 0;
+}
+
+static CutParam* g_cut_dev = nullptr;             // gten_hip_sample_rows_cut's per-row cuts (grow-only)
+static size_t g_cut_cap = 0;
+
+int gten_hip_sample_rows_cut(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                             const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                             const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out,
+                             gten_hip_cut_info* info_out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0 && bias_stride >= 0,
+                "sample_rows_cut: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", n_rows, n_vocab, row_stride, bias_stride);
+    if (n_rows == 0) return 0;
+    GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host && top_p_host && min_p_host, "sample_rows_cut: null argument");
+    std::vector<SampleRowParam> rows((size_t)n_rows);
+    std::vector<CutParam> cuts((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows_cut")) return rc;
+        if (int rc = cut_check(top_p_host[r], min_p_host[r], "sample_rows_cut")) return rc;
+        GTR_REQUIRE(position_host[r] >= 0, "sample_rows_cut: position %d of row %d", position_host[r], r);
+        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
+        cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
+    }
+    if (int rc = rows_upload(rows)) return rc;
+    if (g_cut_cap < (size_t)n_rows) {
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        if (g_cut_dev) GTR_CHECK(hipFree(g_cut_dev));
+        g_cut_dev = nullptr;
+        g_cut_cap = 0;
+        GTR_CHECK(hipMalloc((void**)&g_cut_dev, (size_t)n_rows * sizeof(CutParam)));
+        g_cut_cap = (size_t)n_rows;
+    }
+    GTR_CHECK(hipMemcpyAsync(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_cut, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, bias, bias_stride,
+               (const SampleRowParam*)g_rows_dev, (const CutParam*)g_cut_dev, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out,
+               (CutInfo*)info_out);
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` and `cuts` live on this stack frame
     return 0;
 }
 

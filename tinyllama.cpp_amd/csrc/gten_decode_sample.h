@@ -147,24 +147,17 @@ __device__ __forceinline__ float smp_at(const float* __restrict__ x, const float
     else return x[i];
 }
 
-// One row: the id of the contract (top_k >= 1) or the greedy argmax (top_k == 0).  Every thread returns it.
-// BIAS: the row is y = x + b (b: a bias table's row; -inf = banned -- its key sorts below every finite value and its score is
-// -inf, so it is never the argmax while one entry is above -inf); the unbiased instance never touches b.
+// The candidates of one row (top_k >= 1): element i is one when (smp_key(y_i) & mask) > prefix, or == prefix with i <= ilim; mx = max y.
+// Every thread returns the same four values.  (smp_row and, under a cut, smp_row_cut of gten_decode_nucleus.h draw from them.)
+struct SmpSelect {
+    unsigned mask, prefix;
+    int ilim;
+    float mx;
+};
 template <bool BIAS>
-__device__ __forceinline__ int smp_row(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
-                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm)
+__device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, SmpShared& sm)
 {
     const int t = threadIdx.x;
-    if (top_k <= 0) {
-        float best = -INFINITY;
-        int idx = 0x7fffffff;
-        for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = smp_at<BIAS>(x, b, i);
-            if (v > best || (v == best && i < idx)) { best = v; idx = i; }
-        }
-        return smp_block_argmax(best, idx, sm);
-    }
-    // candidates: (key & mask) > prefix, or == prefix with index <= ilim
     unsigned mask = 0u, prefix = 0u, kk = (unsigned)min(top_k, n);
     int ilim = 0x7fffffff;
     float mx = -INFINITY;
@@ -215,6 +208,30 @@ __device__ __forceinline__ int smp_row(const float* __restrict__ x, const float*
             ilim = (int)ipre;                       // the kk-th lowest index among the ties (indices < 65536)
         }
     }
+    return SmpSelect{mask, prefix, ilim, mx};
+}
+
+// One row: the id of the contract (top_k >= 1) or the greedy argmax (top_k == 0).  Every thread returns it.
+// BIAS: the row is y = x + b (b: a bias table's row; -inf = banned -- its key sorts below every finite value and its score is
+// -inf, so it is never the argmax while one entry is above -inf); the unbiased instance never touches b.
+template <bool BIAS>
+__device__ __forceinline__ int smp_row(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
+                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm)
+{
+    const int t = threadIdx.x;
+    if (top_k <= 0) {
+        float best = -INFINITY;
+        int idx = 0x7fffffff;
+        for (int i = t; i < n; i += SMP_THREADS) {
+            const float v = smp_at<BIAS>(x, b, i);
+            if (v > best || (v == best && i < idx)) { best = v; idx = i; }
+        }
+        return smp_block_argmax(best, idx, sm);
+    }
+    const SmpSelect c = smp_select<BIAS>(x, b, n, top_k, sm);
+    const unsigned mask = c.mask, prefix = c.prefix;
+    const int ilim = c.ilim;
+    const float mx = c.mx;
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i = t; i < n; i += SMP_THREADS) {

@@ -103,6 +103,9 @@ class GtenHip:
     # include/gten_hip_logprobs.h (log-probs and top-N alternatives of the generated ids)
     LOGPROBS_SYMBOLS = ["gten_hip_decoder_set_logprobs", "gten_hip_decoder_logprobs", "gten_hip_decoder_logprobs_info", "gten_hip_row_top_logprobs"]
     LOGPROBS_TOP = 20                                            # GTEN_HIP_LOGPROBS_TOP
+    # include/gten_hip_nucleus.h (top-p / min-p cuts of the draw)
+    NUCLEUS_SYMBOLS = ["gten_hip_decoder_set_cut", "gten_hip_decoder_cut_info", "gten_hip_sample_rows_cut"]
+    CUT_INFO = np.dtype([("Z", np.uint64), ("n_cand", np.int32), ("n_nucleus", np.int32), ("n_minp", np.int32), ("n_keep", np.int32)])   # gten_hip_cut_info
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
@@ -167,6 +170,9 @@ class GtenHip:
         self._dec_logprobs = _sig(L, "gten_hip_decoder_logprobs", ci, [vp, ci, ci, ci, ci, vp, vp, vp])
         self._logprobs_info = _sig(L, "gten_hip_decoder_logprobs_info", ci, [vp, C.POINTER(ci), vp, C.POINTER(vp), C.POINTER(C.c_longlong), C.POINTER(ci)])
         self._row_top_logprobs = _sig(L, "gten_hip_row_top_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, ci, vp, vp, vp])
+        self._set_cut = _sig(L, "gten_hip_decoder_set_cut", ci, [vp, ci, C.c_float, C.c_float])
+        self._cut_info = _sig(L, "gten_hip_decoder_cut_info", ci, [vp, vp, vp, vp, C.POINTER(ci)])
+        self._sample_rows_cut = _sig(L, "gten_hip_sample_rows_cut", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
@@ -246,6 +252,45 @@ class GtenHip:
         self._check(self._sample_rows_biased(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr, bias_stride, kp, tp, C.c_uint64(int(seed)), sp, pp,
                                              out.ptr))
         return out.download(np.int32)[:n_rows].copy()
+
+    def sample_rows_cut(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed, stream, position, top_p, min_p, bias=None, bias_stride=0,
+                        info=True):
+        """gten_hip_sample_rows_cut (include/gten_hip_nucleus.h): sample_rows (sample_rows_biased when `bias` is given) with row r cut
+        by (top_p[r], min_p[r]); scalars are broadcast.  Returns (ids int32[n_rows], info) -- info a structured array of dtype CUT_INFO
+        (Z, n_cand, n_nucleus, n_minp, n_keep), or None with info=False."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        (tpv, tpp), (mpv, mpp) = per_row(top_p, np.float32), per_row(min_p, np.float32)
+        out = DeviceBuffer(self, max(4 * n_rows, 4))
+        inf = DeviceBuffer(self, max(self.CUT_INFO.itemsize * n_rows, 8)) if info else None
+        self._check(self._sample_rows_cut(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr if bias is not None else None, bias_stride, kp, tp,
+                                          C.c_uint64(int(seed)), sp, pp, tpp, mpp, out.ptr, inf.ptr if info else None))
+        ids = out.download(np.int32)[:n_rows].copy()
+        return ids, (inf.download(np.uint8)[: self.CUT_INFO.itemsize * n_rows].view(self.CUT_INFO).copy() if info else None)
+
+    def sample_rows_cut_rc(self, logits, n_rows, n_vocab, row_stride, top_k=40, temp=1.0, top_p=0.9, min_p=0.0):
+        """the return code of one gten_hip_sample_rows_cut call (argument checks); out is a scratch word"""
+        m = max(n_rows, 1)
+        k, t = np.full(m, top_k, np.int32), np.full(m, temp, np.float32)
+        s, p = np.zeros(m, np.uint32), np.ones(m, np.int32)
+        a, b = np.full(m, top_p, np.float32), np.full(m, min_p, np.float32)
+        out = DeviceBuffer(self, 4 * m)
+        v = lambda z: z.ctypes.data_as(C.c_void_p)
+        return self._sample_rows_cut(logits.ptr, n_rows, n_vocab, row_stride, None, 0, v(k), v(t), C.c_uint64(0), v(s), v(p), v(a), v(b), out.ptr, None)
+
+    def decoder_set_cut(self, dec, seq, top_p, min_p):
+        """gten_hip_decoder_set_cut on a raw decoder handle: sequence `seq` draws under (top_p, min_p); (1, 0) clears it"""
+        self._check(self._set_cut(dec, int(seq), C.c_float(top_p), C.c_float(min_p)))
+
+    def decoder_cut_info(self, dec, n_seq):
+        """gten_hip_decoder_cut_info: (top_p f32[n_seq], min_p f32[n_seq], t f32[n_seq], on)"""
+        a, b, t = np.zeros(n_seq, np.float32), np.zeros(n_seq, np.float32), np.zeros(n_seq, np.float32)
+        on = C.c_int(0)
+        self._check(self._cut_info(dec, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), C.byref(on)))
+        return a, b, t, bool(on.value)
 
     def row_logprobs(self, logits, n_rows, n_vocab, row_stride, targets):
         """gten_hip_row_logprobs (include/gten_hip_score.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride elements;

@@ -1,14 +1,14 @@
 // generate.h -- choosing the next id, once for every entry point above the C ABI of libgten_hip.so: greedy, top-k sampling
 // (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h) and log-prob records
-// (include/gten_hip_logprobs.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
+// (include/gten_hip_logprobs.h) and top-p / min-p cuts (include/gten_hip_nucleus.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
 // compile-time mask says which device entry points the flow may name.
 //
 // Why a mask and not a run-time switch: host/capi.cpp links against a stand-in of include/gten_hip.h alone
 // (tests/test_host_sanitize_cpu.py), host/capi.cpp + host/capi_sample.cpp against that plus the sampler's
 // (tests/test_sampler_cpu.py).  So every flow here is a template on the mask, the stages it does not have are discarded with
 // `if constexpr`, and each flow is instantiated where its stages may be named: mask 0 in host/capi.cpp, kSampled in
-// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, all three in host/capi_logprobs.cpp (and in the command line
-// program, which links against the library itself).  That is the only reason those files are separate.
+// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, all four in host/capi_nucleus.cpp
+// (and in the command line program, which links against the library itself).  That is the only reason those files are separate.
 #pragma once
 
 #include <cmath>
@@ -17,10 +17,11 @@
 #include "../../include/gten_hip_sample.h"
 #include "../../include/gten_hip_bias.h"
 #include "../../include/gten_hip_logprobs.h"
+#include "../../include/gten_hip_nucleus.h"
 
 namespace gten {
 
-enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u };
+enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u };
 
 // What one prompt or sequence asks for.  The defaults: greedy, no table, no records.
 struct Request {
@@ -31,6 +32,8 @@ struct Request {
     int table = -1;              // bias table (-1: none) ...
     int min_new = 0;             // ... which holds for the first min_new new ids (0: for all of them)
     int n_top = -1;              // alternatives per log-prob record (0: the id's own log-prob only; -1: no records)
+    float top_p = 1.f, min_p = 0.f;      // the cut of the draw ((1, 0): none; ignored by a greedy request)
+    bool cuts() const { return top_k > 0 && !(top_p == 1.f && min_p == 0.f); }
     // the first position the table no longer holds at, for a prompt of n_prompt ids (0: it holds throughout)
     int until(int n_prompt) const { return (table >= 0 && min_new > 0) ? n_prompt + min_new : 0; }
 };
@@ -38,6 +41,7 @@ struct Request {
 inline bool request_ok(int top_k, float temp) { return top_k >= 0 && (top_k == 0 || (std::isfinite(temp) && temp > 0.f)); }
 inline bool binding_ok(int table, int min_new) { return table >= -1 && table < GTEN_HIP_BIAS_TABLES && min_new >= 0; }
 inline bool asking_ok(int n_top, int n_top_max) { return n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP && n_top <= n_top_max; }
+inline bool cut_ok(float top_p, float min_p) { return std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f && std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f; }
 
 // the requests of a fixed batch's sequences or of a queue's prompts, as the C ABI passes them
 struct Requests {
@@ -46,16 +50,21 @@ struct Requests {
     uint64_t seed = 0;
     const uint32_t* stream = nullptr;        // (null: item j draws with stream j)
     Each<int32_t> table{nullptr, -1}, min_new{nullptr, 0}, n_top{nullptr, -1};
+    Each<float> top_p{nullptr, 1.f}, min_p{nullptr, 0.f};
     static Requests of(const int32_t* top_k, int top_k_all, const float* temp, float temp_all, uint64_t seed, const uint32_t* stream = nullptr,
-                       const int32_t* table = nullptr, const int32_t* min_new = nullptr, const int32_t* n_top = nullptr)
+                       const int32_t* table = nullptr, const int32_t* min_new = nullptr, const int32_t* n_top = nullptr,
+                       const float* top_p = nullptr, float top_p_all = 1.f, const float* min_p = nullptr, float min_p_all = 0.f)
     {
-        return {{top_k, top_k_all}, {temp, temp_all}, seed, stream, {table, -1}, {min_new, 0}, {n_top, -1}};
+        return {{top_k, top_k_all}, {temp, temp_all}, seed, stream, {table, -1}, {min_new, 0}, {n_top, -1}, {top_p, top_p_all}, {min_p, min_p_all}};
     }
-    Request operator[](int j) const { return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j]}; }
+    Request operator[](int j) const
+    {
+        return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j]};
+    }
     bool ok(int n, int n_top_max) const
     {
         for (int j = 0; j < n; j++)
-            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max)) return false;
+            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j])) return false;
         return true;
     }
 };
@@ -88,9 +97,15 @@ struct RecordRows {
     int32_t* top_id = nullptr;
     float* top_lp = nullptr;
     int n_top_max = 0;
-    RecordRows from(size_t pos) const { return {logprob + pos, top_id + pos * (size_t)n_top_max, top_lp + pos * (size_t)n_top_max, n_top_max}; }
+    // (a caller none of whose requests asks may pass no outputs at all)
+    RecordRows from(size_t pos) const
+    {
+        if (!logprob) return *this;
+        return {logprob + pos, top_id + pos * (size_t)n_top_max, top_lp + pos * (size_t)n_top_max, n_top_max};
+    }
     void blank(size_t positions) const
     {
+        if (!logprob) return;
         std::fill(logprob, logprob + positions, 0.f);
         if (n_top_max > 0) {
             std::fill(top_id, top_id + positions * (size_t)n_top_max, -1);
@@ -133,11 +148,18 @@ void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_
     static_assert(M & kSampled, "greedy takes the argmax of the prompt's logits on the host");
     const int32_t k = r.top_k;
     const float* row = nullptr;
-    if constexpr ((M & kBiased) != 0) {
+    bool drawn = false;
+    if constexpr ((M & kBiased) != 0)
         if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
-        if (row) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    if constexpr ((M & kNucleus) != 0)
+        if (r.cuts()) {
+            GTEN_HIP_OK(gten_hip_sample_rows_cut(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &r.top_p, &r.min_p, id_dev, nullptr));
+            drawn = true;
+        }
+    if constexpr ((M & kBiased) != 0) {
+        if (row && !drawn) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
     }
-    if (!row) GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n_vocab, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    if (!row && !drawn) GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n_vocab, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
     if constexpr ((M & kLogprobs) != 0)
         if (r.n_top >= 0) GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n_vocab, n_vocab, id_dev, r.n_top, &rec_dev->logprob, rec_dev->top_id, rec_dev->top_lp));
 }
@@ -156,11 +178,14 @@ struct SlotRequests {
     int bind(int q, const Request& r, int n_prompt)
     {
         (void)q; (void)r; (void)n_prompt;
-        if constexpr ((M & (kBiased | kLogprobs)) != 0) bound = true;
+        if constexpr ((M & (kBiased | kLogprobs | kNucleus)) != 0) bound = true;
         if constexpr ((M & kBiased) != 0)
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
         if constexpr ((M & kLogprobs) != 0)
             if (const int rc = gten_hip_decoder_set_logprobs(dec, q, r.n_top)) return rc;
+        if constexpr ((M & kNucleus) != 0)
+            // (a greedy request's cut could never act: it is not passed on, so it does not switch a decoder to the cut launch)
+            if (const int rc = gten_hip_decoder_set_cut(dec, q, r.cuts() ? r.top_p : 1.f, r.cuts() ? r.min_p : 0.f)) return rc;
         return 0;
     }
     // the sampling request of the decode steps that follow
@@ -186,6 +211,9 @@ struct SlotRequests {
         if constexpr ((M & kLogprobs) != 0)
             for (int q = 0; bound && q < n_slots; q++)
                 if (const int r = gten_hip_decoder_set_logprobs(dec, q, -1)) rc = r;
+        if constexpr ((M & kNucleus) != 0)
+            for (int q = 0; bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_cut(dec, q, 1.f, 0.f)) rc = r;
         bound = sampling = false;
         return rc;
     }
@@ -263,7 +291,7 @@ int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, con
         return b.prefill(set, prompt);
     } else {
         gten_hip_decoder* dec = nullptr;
-        if constexpr ((M & kBiased) != 0) dec = b.decoder_handle();
+        if constexpr ((M & (kBiased | kNucleus)) != 0) dec = b.decoder_handle();
         return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) { draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev); });
     }
 }
@@ -416,6 +444,12 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
             if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, 0)) return rc;
             if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, -1)) return rc;
         }
+    if constexpr ((M & kNucleus) != 0)
+        for (int j = 0, cutting = 0; j < n_prompts && !cutting; j++)
+            if ((cutting = reqs[j].cuts())) {
+                if (const int rc = gten_hip_decoder_set_cut(dec, 0, reqs[j].top_p, reqs[j].min_p)) return rc;
+                if (const int rc = gten_hip_decoder_set_cut(dec, 0, 1.f, 0.f)) return rc;
+            }
     std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
     for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
     ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len);

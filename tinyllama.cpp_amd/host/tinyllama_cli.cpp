@@ -6,7 +6,7 @@
 // with the sampler on the device (host/generate.h); --score PATH prints the log-likelihood of a text file
 // (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
 // of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
-// most likely alternatives (include/gten_hip_logprobs.h) after the text.
+// most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -49,6 +49,10 @@ Optional args.
 --min-new N : --ban / --allow hold for the first N generated ids only; N must be gte 1. [default: for all of them]
 --logprobs N : after the text, one line per generated id: `id logprob` and the N most likely ids of its step as `id:logprob`,
            from the unconstrained, untempered logits. N must be gte 0 and lte 20. Combines with --ban / --allow / --min-new.
+--top-p F : nucleus sampling: draw from the fewest of the top-k ids whose probability mass reaches F. F must be gt 0 and lte 1.
+           [default=1: off]. With --topk 32003: over the whole vocabulary. Not with -greedy or --score.
+--min-p F : draw only from ids at least F times as likely as the most likely one. F must be gte 0 and lte 1. [default=0: off].
+           Not with -greedy or --score.
 )";
 
 struct Options {
@@ -61,6 +65,9 @@ struct Options {
     std::vector<int32_t> ban, allow;         // --ban / --allow (bias table 0)
     int min_new = 0;
     int logprobs = -1;                       // --logprobs N (-1: off)
+    float top_p = 1.f, min_p = 0.f;          // --top-p / --min-p ((1, 0): off)
+    bool cut_given = false;
+    bool cuts() const { return !(top_p == 1.f && min_p == 0.f); }
     bool constrained() const { return !ban.empty() || !allow.empty(); }
 };
 
@@ -110,7 +117,8 @@ static void set_constraint(const Options& o, TinyLlama& model)
 // One answer (host/generate.h).  Plain greedy: the prompt as in the reference, every later id from the device-side argmax, nothing set
 // on the decoder.  Top-k (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler,
 // keyed by (seed, stream = the chat turn, position).  --ban / --allow: either mode under table 0 (top_k 0: greedy over the biased
-// logits).  --logprobs: after the ids, one record line per generated id.  The flow names only the stages the options ask for.
+// logits).  --logprobs: after the ids, one record line per generated id.  --top-p / --min-p: the draw under a cut.  The flow names only
+// the stages the options ask for.
 static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t* turn)
 {
     std::vector<int> enc = tok.encode(prompt);
@@ -122,8 +130,17 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
     if (o.greedy && !o.constrained() && o.logprobs < 0) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
     } else {
-        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs};
-        if (o.logprobs >= 0) {
+        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p};
+        if (o.cuts()) {
+            RecordRows rows;
+            if (o.logprobs >= 0) {
+                logprob.resize(width);
+                top_id.resize(width * W);
+                top_lp.resize(width * W);
+                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
+            }
+            rc = generate<kSampled | kBiased | kLogprobs | kNucleus>(model, tokens, o.n_predict, tok.eos, r, rows);
+        } else if (o.logprobs >= 0) {
             logprob.resize(width);
             top_id.resize(width * W);
             top_lp.resize(width * W);
@@ -245,11 +262,29 @@ int main(int argc, char const* argv[])
             if (text.empty() || used != text.size()) { std::cerr << "Invalid logprobs value.\n"; return -1; }
             if (v < 0 || v > GTEN_HIP_LOGPROBS_TOP) { std::cerr << "logprobs must be gte 0 and lte " << GTEN_HIP_LOGPROBS_TOP << ".\n"; return -1; }
             o.logprobs = v;
+        } else if (arg == "--top-p" || arg == "--min-p") {
+            const bool is_top = arg == "--top-p";
+            const char* name = is_top ? "top-p" : "min-p";
+            const std::string text = value(name);
+            size_t used = 0;
+            float v = -1.f;
+            try { v = std::stof(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size() || !std::isfinite(v)) { std::cerr << "Invalid " << name << " value.\n"; return -1; }
+            if (is_top) {
+                if (!(v > 0.f && v <= 1.f)) { std::cerr << "top-p must be gt 0 and lte 1.\n"; return -1; }
+                o.top_p = v;
+            } else {
+                if (!(v >= 0.f && v <= 1.f)) { std::cerr << "min-p must be gte 0 and lte 1.\n"; return -1; }
+                o.min_p = v;
+            }
+            o.cut_given = true;
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
         }
     }
+    if (o.cut_given && o.greedy) { std::cerr << "top-p and min-p need top-k sampling: not with -greedy.\n"; return -1; }
+    if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
     if (o.min_new > 0 && !o.constrained()) { std::cerr << "min-new needs --ban or --allow.\n"; return -1; }
     if (!o.allow.empty() && std::all_of(o.allow.begin(), o.allow.end(), [&](int32_t id) { return std::find(o.ban.begin(), o.ban.end(), id) != o.ban.end(); })) {
         std::cerr << "--ban bans every id of --allow.\n";

@@ -52,6 +52,9 @@ class GtenHost:
     LOGPROBS_SYMBOLS = ["gten_host_model_set_logprobs", "gten_host_batch_set_logprobs", "gten_host_model_logprobs", "gten_host_batch_logprobs",
                         "gten_host_model_generate_lp", "gten_host_batch_generate_lp", "gten_host_batch_serve_lp", "gten_host_model_score_top"]
     LOGPROBS_TOP = 20                                            # GTEN_HIP_LOGPROBS_TOP
+    # include/gten_host_nucleus.h (top-p / min-p cuts of the draw, host/capi_nucleus.cpp)
+    NUCLEUS_SYMBOLS = ["gten_host_model_set_cut", "gten_host_batch_set_cut", "gten_host_model_cut_info", "gten_host_batch_cut_info",
+                       "gten_host_model_generate_nucleus", "gten_host_batch_generate_nucleus", "gten_host_batch_serve_nucleus"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -101,6 +104,16 @@ class GtenHost:
                                                                     vp, ci, vp, vp, vp])
         self._bserve_lp = _sig(L, "gten_host_batch_serve_lp", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                   C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp])
+        self._m_set_cut = _sig(L, "gten_host_model_set_cut", ci, [vp, C.c_float, C.c_float])
+        self._b_set_cut = _sig(L, "gten_host_batch_set_cut", ci, [vp, ci, C.c_float, C.c_float])
+        self._m_cut_info = _sig(L, "gten_host_model_cut_info", ci, [vp, vp, vp, vp])
+        self._b_cut_info = _sig(L, "gten_host_batch_cut_info", ci, [vp, vp, vp, vp])
+        self._generate_nuc = _sig(L, "gten_host_model_generate_nucleus", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
+                                                                              C.c_float, C.c_float, vp, vp, vp])
+        self._bgen_nuc = _sig(L, "gten_host_batch_generate_nucleus", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
+                                                                          vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float])
+        self._bserve_nuc = _sig(L, "gten_host_batch_serve_nucleus", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                         C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float])
         self._score_top = _sig(L, "gten_host_model_score_top", ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
@@ -257,6 +270,12 @@ def _records(n_top, n, width):
     nt, tw = _n_tops(n_top, n)
     lp, ti, tl = np.zeros((n, width), np.float32), np.full((n, width, tw), -1, np.int32), np.zeros((n, width, tw), np.float32)
     return [_ptr(nt), tw, _ptr(lp), _ptr(ti), _ptr(tl)], (lp, ti, tl)
+
+
+def _cut_args(n, top_p, min_p):
+    """top_p / min_p (a scalar or one value per item) as the C ABI takes them: arrays or null, then the values for all"""
+    (ps, p1), (ms, m1) = _each(top_p, n, np.float32), _each(min_p, n, np.float32)
+    return [_ptr(ps), _ptr(ms), C.c_float(1.0 if ps is not None else float(p1)), C.c_float(0.0 if ms is not None else float(m1))]
 
 
 class HostTokenizer:
@@ -534,6 +553,41 @@ class HostModel:
             raise GtenHipError(f"generate_logprobs rc={total}: {self.host.hip._err().decode(errors='replace')}")
         return buf[:total].copy(), lp[:total].copy(), ti[:total].copy(), tl[:total].copy()
 
+    def set_cut_rc(self, top_p, min_p):
+        return self.host._m_set_cut(self.h, C.c_float(top_p), C.c_float(min_p))
+
+    def set_cut(self, top_p=1.0, min_p=0.0):
+        """the decoder's sampled steps draw under the cut (top_p, min_p) from now on ((1, 0): off; include/gten_host_nucleus.h)"""
+        rc = self.set_cut_rc(top_p, min_p)
+        if rc:
+            raise GtenHipError(f"set_cut rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def cut_info(self):
+        """(top_p, min_p, t = f32(log(min_p)), whether the decoder has ever had a cut set)"""
+        a, b, t = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32)
+        on = self.host._m_cut_info(self.h, _ptr(a), _ptr(b), _ptr(t))
+        if on < 0:
+            raise GtenHipError(f"cut_info rc={on}")
+        return a[0], b[0], t[0], bool(on)
+
+    def generate_nucleus(self, prompt, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, top_p=1.0, min_p=0.0, table=-1, min_new=0,
+                         n_top=None):
+        """generate_biased() with the draw cut by (top_p, min_p) (include/gten_host_nucleus.h); n_top None: the ids; otherwise
+        generate_logprobs()'s tuple (ids, logprob, top_id, top_logprob)"""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        ask = n_top is not None and n_top >= 0
+        w = int(n_top) if ask else 0
+        lp, ti, tl = np.zeros(width, np.float32), np.full((width, w), -1, np.int32), np.zeros((width, w), np.float32)
+        total = self.host._generate_nuc(self.h, _ptr(buf), len(prompt), max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)),
+                                        C.c_uint32(int(stream)), int(table), int(min_new), w if ask else -1, C.c_float(top_p), C.c_float(min_p),
+                                        _ptr(lp) if ask else None, _ptr(ti) if ask else None, _ptr(tl) if ask else None)
+        if total < 0:
+            raise GtenHipError(f"generate_nucleus rc={total}: {self.host.hip._err().decode(errors='replace')}")
+        ids = buf[:total].copy()
+        return (ids, lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else ids
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -733,6 +787,48 @@ class HostBatch:
         ids, st = self._serve(self.host._bserve_lp, "batch_serve_lp", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
                               *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args)
         return (ids, st, *rec)
+
+    def set_cut_rc(self, seq, top_p, min_p):
+        return self.host._b_set_cut(self.h, int(seq), C.c_float(top_p), C.c_float(min_p))
+
+    def set_cut(self, seq, top_p=1.0, min_p=0.0):
+        """sequence seq's sampled steps draw under the cut (top_p, min_p) from now on ((1, 0): off; include/gten_host_nucleus.h)"""
+        rc = self.set_cut_rc(seq, top_p, min_p)
+        if rc:
+            raise GtenHipError(f"batch_set_cut rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def cut_info(self):
+        """(top_p f32[n_seq], min_p f32[n_seq], t f32[n_seq] = f32(log(min_p)), whether the shared decoder has ever had a cut set)"""
+        a, b, t = np.zeros(self.n_seq, np.float32), np.zeros(self.n_seq, np.float32), np.zeros(self.n_seq, np.float32)
+        on = self.host._b_cut_info(self.h, _ptr(a), _ptr(b), _ptr(t))
+        if on < 0:
+            raise GtenHipError(f"batch_cut_info rc={on}")
+        return a, b, t, bool(on)
+
+    def generate_nucleus(self, prompts, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, top_p=1.0, min_p=0.0, tables=None,
+                         min_new=None, n_top=None):
+        """generate_biased() with a cut per sequence (top_p / min_p a scalar or a list); n_top None: the ids per sequence, otherwise
+        generate_logprobs()'s tuple"""
+        n = self.n_seq
+        args, rec = _records(n_top, n, max_tokens)
+        if n_top is None:
+            args = [None, 0, None, None, None]
+        ids = self._generate(self.host._bgen_nuc, "batch_generate_nucleus", prompts, max_tokens, eos,
+                             _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)),
+                             args + _cut_args(n, top_p, min_p))
+        return ids if n_top is None else (ids, *rec)
+
+    def serve_nucleus(self, prompts, max_tokens, eos, top_k, temp, seed, top_p=1.0, min_p=0.0, tables=None, min_new=None, n_top=None,
+                      slice_steps=16, max_new=0, max_new_each=None):
+        """serve_biased() with a cut per prompt; n_top None: (ids per prompt, stats), otherwise serve_logprobs()'s tuple"""
+        n = len(prompts)
+        args, rec = _records(n_top, n, max(max_tokens, max(len(p) for p in prompts)))
+        if n_top is None:
+            args = [None, 0, None, None, None]
+        ids, st = self._serve(self.host._bserve_nuc, "batch_serve_nucleus", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                              *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args,
+                              *_cut_args(n, top_p, min_p))
+        return (ids, st) if n_top is None else (ids, st, *rec)
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""
