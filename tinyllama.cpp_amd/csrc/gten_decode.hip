@@ -113,6 +113,33 @@ static_assert(CUT_MASS_BITS == GTEN_HIP_NUCLEUS_MASS_BITS && sizeof(CutInfo) == 
 
 using namespace gtr;
 
+struct CapturedGraph { hipGraph_t graph; hipGraphExec_t exec; };
+
+// What a decoder's sequences ask of the end of a step, beyond the greedy id.  Every sequence has one request (SampleParam), on the
+// device and on the host; each setter owns its fields of it: top-k sampling (gten_hip_decoder_set_sampling, include/gten_hip_sample.h)
+// top_k .. seed, a bias table (include/gten_hip_bias.h) table1 and until, a log-prob request (include/gten_hip_logprobs.h) lp1.
+//
+// The step ends in ONE launch, chosen by launch_step_end: k_dec_argmax while no sequence samples, is bound to a table or asks for
+// log-probs (sampler_on), the sampler launch once one does -- two sets of graphs.  Which sampler kernel that launch is follows from
+// the features this decoder has EVER used, the latest rung first: k_dec_sample_cut (cut_on), k_dec_sample_lp (lp_on),
+// k_dec_sample_b (bias_on), k_dec_sample.  Each rung treats a sequence without its feature exactly as the rung below does, so a
+// feature switched off again costs nothing but the wider kernel.  A feature's buffer is made by its first use (first_use(), in
+// gten_decode_sampler_api.h), which also drops the graphs captured so far, once: they hold the rung below.
+struct SamplerState {
+    SampleParam* samp = nullptr;        // [n_seq]
+    std::vector<SampleParam> samp_host;
+    int n_sampling = 0;                 // sequences with top_k >= 1
+    float* bias = nullptr;              // [GTEN_HIP_BIAS_TABLES][n_vocab] f32; also made by the first gten_hip_decoder_set_bias_table
+    int n_bound = 0;                    // sequences with a table (SampleParam::table1 > 0)
+    bool bias_on = false;
+    LpRecord* lp = nullptr;             // [n_seq][max_ctx + 2] records indexed by n like `result`
+    int n_asking = 0;                   // sequences with a log-prob request (SampleParam::lp1 > 0)
+    bool lp_on = false;
+    CutParam* cut = nullptr;            // [n_seq] top-p / min-p cuts beside `samp` (include/gten_hip_nucleus.h).  A cut only
+    std::vector<CutParam> cut_host;     // acts on a sampling sequence, so it does not enter sampler_on
+    bool cut_on = false;
+};
+
 struct gten_hip_decoder {
     gten_hip_decoder_desc d;
     std::vector<gten_hip_layer_ptrs> layers;
@@ -147,40 +174,13 @@ struct gten_hip_decoder {
     float* logits_m = nullptr;     // [n_seq][n_vocab]
     float* gu_raw = nullptr;       // [n_seq][2 n_ffn] raw gate | up rows (wide decode, n_seq >= 16)
     int n_chunks = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    hipGraph_t graph_k = nullptr;       // DEC_GRAPH_STEPS consecutive steps in one graph (the position lives on the device and
-    hipGraphExec_t exec_k = nullptr;    // the last kernel of a step advances it): one replay per DEC_GRAPH_STEPS tokens
-    // continuous batching (gten_hip_decoder_run): the same two graphs per SUBSET of lanes -- a lane whose slots are all parked is
-    // left out of the step (its launch chain costs what a full lane costs however few slots are live); index = lane mask
-    hipGraph_t graph_m[1 << DEC_MAX_LANES] = {}, graph_km[1 << DEC_MAX_LANES] = {};
-    hipGraphExec_t exec_m[1 << DEC_MAX_LANES] = {}, exec_km[1 << DEC_MAX_LANES] = {};
-    // top-k sampling (gten_hip_decoder_set_sampling): every sequence's request on the device and on the host; while no sequence
-    // samples the step ends in k_dec_argmax (the graphs above), once one does in k_dec_sample -- the same graphs once more
-    SampleParam* samp = nullptr;        // [n_seq]
-    std::vector<SampleParam> samp_host;
-    int n_sampling = 0;                 // sequences with top_k >= 1
-    // bias tables (include/gten_hip_bias.h): [GTEN_HIP_BIAS_TABLES][n_vocab] f32, made by the first call that needs them.
-    // A bound sequence (SampleParam::table1 > 0) makes the step end in the sampler like a sampling one does; from the first binding on
-    // (bias_on: the graphs captured before are dropped once) that launch is k_dec_sample_b, which treats unbound sequences as k_dec_sample does.
-    float* bias = nullptr;
-    int n_bound = 0;                    // sequences with a table
-    bool bias_on = false;
-    // log-probs of the generated ids (include/gten_hip_logprobs.h): [n_seq][max_ctx + 2] records indexed by n like `result`,
-    // made by the first request (lp_on: the graphs captured before are dropped once).  An asking sequence (SampleParam::lp1 > 0) makes the
-    // step end in the sampler launch like a sampling one does; from the first request on that launch is k_dec_sample_lp, which treats
-    // sequences that do not ask as k_dec_sample / k_dec_sample_b do.
-    LpRecord* lp = nullptr;
-    int n_asking = 0;                   // sequences with a log-prob request
-    bool lp_on = false;
-    // top-p / min-p cuts (include/gten_hip_nucleus.h): [n_seq] beside `samp`, made by the first sequence that sets a cut
-    // (cut_on: the graphs captured before are dropped once).  From then on the sampler launch is k_dec_sample_cut, which treats sequences
-    // without a cut as k_dec_sample_lp does.  A cut only acts on a sampling sequence, so it does not enter sampler_on.
-    CutParam* cut = nullptr;
-    std::vector<CutParam> cut_host;
-    bool cut_on = false;
-    hipGraph_t s_graph = nullptr, s_graph_k = nullptr, s_graph_m[1 << DEC_MAX_LANES] = {}, s_graph_km[1 << DEC_MAX_LANES] = {};
-    hipGraphExec_t s_exec = nullptr, s_exec_k = nullptr, s_exec_m[1 << DEC_MAX_LANES] = {}, s_exec_km[1 << DEC_MAX_LANES] = {};
+    // the captured graphs, [sampler_on][one step | DEC_GRAPH_STEPS steps][graph_slot].  DEC_GRAPH_STEPS consecutive steps fit one
+    // graph because the position lives on the device and the last kernel of a step advances it: one replay per DEC_GRAPH_STEPS
+    // tokens.  Slot 0 holds every lane; continuous batching (gten_hip_decoder_run) keeps the same graphs per SUBSET of lanes, slot =
+    // lane mask -- a lane whose slots are all parked is left out of the step (its launch chain costs what a full lane costs however
+    // few slots are live).  graph_exec() captures an entry on first use, drop_graphs() releases them all.
+    CapturedGraph graphs[2][2][1 << DEC_MAX_LANES] = {};
+    SamplerState smp;
     unsigned lane_mask = 0;             // lanes the NEXT enqueue takes (0: all)
     int last_run_lanes = 0;             // lanes the last gten_hip_decoder_run took
     const float2* rope = nullptr;
@@ -227,7 +227,45 @@ struct gten_hip_decoder {
 };
 
 // the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table or asks for log-probs
-static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->n_sampling + dc->n_bound + dc->n_asking > 0; }
+static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking > 0; }
+
+// where the step of one lane ends: what the sampler launch reads and writes, and the four arguments of k_dec_argmax in which the
+// three step forms differ (the others -- tables, row lengths -- are the decoder's)
+struct StepEnd {
+    int rows;                           // grid: sequences of the lane
+    const float* logits; int row_stride;
+    const SampleParam* samp;
+    DecStep* step;
+    int32_t* result; int result_stride;
+    int32_t* tokens;
+    LpRecord* lp;
+    const CutParam* cut;
+    const float* best_val; const int* best_idx; int n_best, best_stride;      // k_dec_argmax: candidates per sequence
+};
+
+// the one launch a step ends in (SamplerState, above)
+static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
+{
+    const SamplerState& s = dc->smp;
+    const int V = dc->d.n_vocab, tok_stride = dc->d.max_ctx + 1, rec_stride = dc->d.max_ctx + 2;
+    const dim3 grid(e.rows), block(SMP_THREADS);
+    const bool on = sampler_on(dc);
+    if (on && s.cut_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, grid, block, 0, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens, tok_stride,
+                   (const float*)s.bias, e.lp, rec_stride, e.cut);
+    else if (on && s.lp_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, grid, block, 0, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens, tok_stride,
+                   (const float*)s.bias, e.lp, rec_stride);
+    else if (on && s.bias_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, grid, block, 0, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens, tok_stride,
+                   (const float*)s.bias);
+    else if (on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, grid, block, 0, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens, tok_stride);
+    else
+        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, grid, dim3(1024), 0, e.best_val, e.best_idx, e.n_best, e.step, e.result, e.best_stride, e.result_stride,
+                   e.tokens, tok_stride);
+    return 0;
+}
 
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
@@ -248,9 +286,9 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     const size_t planes = dc->n_seq >= 16 ? 2 : 1, H = (size_t)d.n_heads, C = (size_t)dc->n_chunks;
     LaneBufs b;
     b.n_seq = (int)SL;
-    b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->samp + o;
-    b.lp = dc->lp ? dc->lp + o * (d.max_ctx + 2) : nullptr;
-    b.cut = dc->cut ? dc->cut + o : nullptr;
+    b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->smp.samp + o;
+    b.lp = dc->smp.lp ? dc->smp.lp + o * (d.max_ctx + 2) : nullptr;
+    b.cut = dc->smp.cut ? dc->smp.cut + o : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -656,22 +694,9 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
-    if (sampler_on(dc) && dc->cut_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2, (const CutParam*)dc->cut);
-    else if (sampler_on(dc) && dc->lp_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
-    else if (sampler_on(dc) && dc->bias_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
-    else if (sampler_on(dc))
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(1), dim3(SMP_THREADS), 0, (const float*)d.logits, d.n_vocab, 0, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, 0, dc->tokens, d.max_ctx + 1);
-    else
-        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(1), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
-                   dc->n_best, dc->step, dc->result, 0, 0, dc->tokens, d.max_ctx + 1);
-    return 0;
+    // (one sequence: no strides; the argmax joins lm_head's per-wave winners)
+    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut,
+                                       dc->best_val, dc->best_idx, dc->n_best, 0});
 }
 
 // ---- one decode step of n_seq sequences that share every weight pass
@@ -809,22 +834,8 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    if (sampler_on(dc) && dc->cut_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2, (const CutParam*)dc->cut);
-    else if (sampler_on(dc) && dc->lp_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias, dc->lp, d.max_ctx + 2);
-    else if (sampler_on(dc) && dc->bias_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1, (const float*)dc->bias);
-    else if (sampler_on(dc))
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)dc->logits_m, V, V, (const SampleParam*)dc->samp,
-                   dc->step, dc->result, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
-    else
-        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)dc->best_val, (const int*)dc->best_idx,
-                   dc->n_best, dc->step, dc->result, dc->n_best, d.max_ctx + 2, dc->tokens, d.max_ctx + 1);
-    return 0;
+    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut,
+                                       dc->best_val, dc->best_idx, dc->n_best, dc->n_best});
 }
 
 static size_t mmv_lds_bytes(int wt, int rt, int ft, int d_in, int ks)
@@ -1295,22 +1306,8 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     sf.act_q = b.stg_q; sf.act_d = b.stg_d; sf.act_sum = b.stg_sum; sf.act_f = b.stg_f;
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
-    if (sampler_on(dc) && dc->cut_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
-                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias, b.lp, d.max_ctx + 2, b.cut);
-    else if (sampler_on(dc) && dc->lp_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_lp, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
-                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias, b.lp, d.max_ctx + 2);
-    else if (sampler_on(dc) && dc->bias_on)
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_b, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
-                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1, (const float*)dc->bias);
-    else if (sampler_on(dc))
-        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample, dim3(S), dim3(SMP_THREADS), 0, (const float*)b.logits_m, V, V, b.samp,
-                   b.step, b.result, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
-    else
-        DEC_LAUNCH(KT_DEC_ARGMAX, k_dec_argmax, dim3(S), dim3(1024), 0, (const float*)b.logits_m, (const int*)nullptr,
-                   V, b.step, b.result, V, d.max_ctx + 2, b.tokens, d.max_ctx + 1);
-    return 0;
+    // (the matrix-core lm_head keeps no winners: the argmax reads the logits rows; the bias tables are the decoder's, not a lane's)
+    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.logits_m, nullptr, V, V});
 }
 
 template <int WT>
@@ -1498,9 +1495,9 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     GTR_CHECK(hipMemset(dc->tokens, 0, S * (size_t)(d.max_ctx + 1) * 4));
     GTR_CHECK(hipMalloc((void**)&dc->result, S * (size_t)(d.max_ctx + 2) * 4));
     GTR_CHECK(hipMemset(dc->result, 0, S * (size_t)(d.max_ctx + 2) * 4));
-    GTR_CHECK(hipMalloc((void**)&dc->samp, S * sizeof(SampleParam)));
-    GTR_CHECK(hipMemset(dc->samp, 0, S * sizeof(SampleParam)));              // every sequence greedy
-    dc->samp_host.assign(S, SampleParam{});
+    GTR_CHECK(hipMalloc((void**)&dc->smp.samp, S * sizeof(SampleParam)));
+    GTR_CHECK(hipMemset(dc->smp.samp, 0, S * sizeof(SampleParam)));          // every sequence greedy
+    dc->smp.samp_host.assign(S, SampleParam{});
     const size_t planes = wide ? 2 : 1;                       // k_dec_mmv may split K over two workgroups: one output plane each
     GTR_CHECK(hipMalloc((void**)&dc->qkv_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)(E + 2 * KV) * 4));
     GTR_CHECK(hipMalloc((void**)&dc->proj_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)E * 4));      // (k_dec_wxp_f16: eight K planes)
@@ -1657,6 +1654,21 @@ static int persist_prepare(gten_hip_decoder* dc) { dc->persist_on = false; retur
 static hipError_t persist_free(gten_hip_decoder*) { return hipSuccess; }
 #endif
 
+// release the captured graphs of a decoder (its next steps capture again): every release is attempted, the first failure reported
+static hipError_t drop_graphs(gten_hip_decoder* dc)
+{
+    hipError_t first = hipSuccess;
+    auto rel = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
+    for (auto& by_steps : dc->graphs)
+        for (auto& by_slot : by_steps)
+            for (CapturedGraph& c : by_slot) {
+                if (c.exec) rel(hipGraphExecDestroy(c.exec));
+                if (c.graph) rel(hipGraphDestroy(c.graph));
+                c = CapturedGraph{};
+            }
+    return first;
+}
+
 extern "C" {
 
 int gten_hip_decoder_create(const gten_hip_decoder_desc* desc, const gten_hip_layer_ptrs* layers, gten_hip_decoder** out)
@@ -1678,29 +1690,12 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     // (every release is attempted; the first failure is what the call reports)
     hipError_t first = hipSuccess;
     auto rel = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
-    if (dc->exec) rel(hipGraphExecDestroy(dc->exec));
-    if (dc->graph) rel(hipGraphDestroy(dc->graph));
-    if (dc->exec_k) rel(hipGraphExecDestroy(dc->exec_k));
-    if (dc->graph_k) rel(hipGraphDestroy(dc->graph_k));
-    for (int m = 0; m < (1 << DEC_MAX_LANES); m++) {
-        if (dc->exec_m[m]) rel(hipGraphExecDestroy(dc->exec_m[m]));
-        if (dc->graph_m[m]) rel(hipGraphDestroy(dc->graph_m[m]));
-        if (dc->exec_km[m]) rel(hipGraphExecDestroy(dc->exec_km[m]));
-        if (dc->graph_km[m]) rel(hipGraphDestroy(dc->graph_km[m]));
-        if (dc->s_exec_m[m]) rel(hipGraphExecDestroy(dc->s_exec_m[m]));
-        if (dc->s_graph_m[m]) rel(hipGraphDestroy(dc->s_graph_m[m]));
-        if (dc->s_exec_km[m]) rel(hipGraphExecDestroy(dc->s_exec_km[m]));
-        if (dc->s_graph_km[m]) rel(hipGraphDestroy(dc->s_graph_km[m]));
-    }
-    if (dc->s_exec) rel(hipGraphExecDestroy(dc->s_exec));
-    if (dc->s_graph) rel(hipGraphDestroy(dc->s_graph));
-    if (dc->s_exec_k) rel(hipGraphExecDestroy(dc->s_exec_k));
-    if (dc->s_graph_k) rel(hipGraphDestroy(dc->s_graph_k));
+    rel(drop_graphs(dc));
     kv_watch_remove(dc, nullptr);
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->samp, dc->bias, dc->lp, dc->cut,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
@@ -1760,23 +1755,6 @@ static void share_at_start(gten_hip_decoder* dc, int q, int n)
 static void share_end(gten_hip_decoder* dc, int q)
 {
     if (!dc->share_rows.empty()) dc->share_rows[(size_t)q] = 0;
-}
-// the captured graphs of a decoder (its next steps capture again)
-static hipError_t drop_graphs(gten_hip_decoder* dc)
-{
-    hipError_t first = hipSuccess;
-    auto rel = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
-    auto drop = [&](hipGraphExec_t& e, hipGraph_t& g) {
-        if (e) rel(hipGraphExecDestroy(e));
-        if (g) rel(hipGraphDestroy(g));
-        e = nullptr; g = nullptr;
-    };
-    drop(dc->exec, dc->graph); drop(dc->exec_k, dc->graph_k); drop(dc->s_exec, dc->s_graph); drop(dc->s_exec_k, dc->s_graph_k);
-    for (int m = 0; m < (1 << DEC_MAX_LANES); m++) {
-        drop(dc->exec_m[m], dc->graph_m[m]); drop(dc->exec_km[m], dc->graph_km[m]);
-        drop(dc->s_exec_m[m], dc->s_graph_m[m]); drop(dc->s_exec_km[m], dc->s_graph_km[m]);
-    }
-    return first;
 }
 static int pre_run(gten_hip_decoder* dc)
 {
@@ -1883,27 +1861,33 @@ static unsigned graph_slot(const gten_hip_decoder* dc)
     const unsigned all = (1u << dc->lanes) - 1u, m = dc->lane_mask & all;
     return (dc->lanes <= 1 || m == 0 || m == all) ? 0u : m;
 }
+// the executable graph of `steps` (1 or DEC_GRAPH_STEPS) consecutive steps of the decoder as it stands -- sampler on or off, the
+// lanes dc->lane_mask selects -- captured on first use
+static int graph_exec(gten_hip_decoder* dc, int steps, hipGraphExec_t* out)
+{
+    CapturedGraph& c = dc->graphs[sampler_on(dc) ? 1 : 0][steps == 1 ? 0 : 1][graph_slot(dc)];
+    if (!c.exec) {
+        GTR_CHECK(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue(dc, steps);
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(stream(), &g);
+        if (rc) { if (g) hipGraphDestroy(g); return rc; }
+        GTR_CHECK(e);
+        c.graph = g;
+        GTR_CHECK(hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0));
+    }
+    *out = c.exec;
+    return 0;
+}
+
 static int run_steps_free(gten_hip_decoder* dc, int count)
 {
     if (int rc = pre_run(dc)) return rc;
     if (prof_on()) { for (int i = 0; i < count; i++) if (int rc = run_step(dc, 0)) return rc; return 0; }
-    const unsigned gs = graph_slot(dc);
-    const bool smp = sampler_on(dc);
-    hipGraph_t& graph_k = smp ? (gs ? dc->s_graph_km[gs] : dc->s_graph_k) : (gs ? dc->graph_km[gs] : dc->graph_k);
-    hipGraphExec_t& exec_k = smp ? (gs ? dc->s_exec_km[gs] : dc->s_exec_k) : (gs ? dc->exec_km[gs] : dc->exec_k);
-    while (count >= DEC_GRAPH_STEPS) {
-        if (!exec_k) {
-            GTR_CHECK(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
-            const int rc = enqueue(dc, DEC_GRAPH_STEPS);
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(stream(), &g);
-            if (rc) { if (g) hipGraphDestroy(g); return rc; }
-            GTR_CHECK(e);
-            graph_k = g;
-            GTR_CHECK(hipGraphInstantiate(&exec_k, graph_k, nullptr, nullptr, 0));
-        }
+    for (; count >= DEC_GRAPH_STEPS; count -= DEC_GRAPH_STEPS) {
+        hipGraphExec_t exec_k = nullptr;
+        if (int rc = graph_exec(dc, DEC_GRAPH_STEPS, &exec_k)) return rc;
         GTR_CHECK(hipGraphLaunch(exec_k, stream()));
-        count -= DEC_GRAPH_STEPS;
     }
     for (int i = 0; i < count; i++)
         if (int rc = run_step(dc, 1)) return rc;
@@ -1914,20 +1898,8 @@ static int run_step(gten_hip_decoder* dc, int use_graph)
 {
     if (int rc = pre_run(dc)) return rc;
     if (!use_graph || prof_on()) return enqueue(dc);    // event pairs cannot be recorded into a capture
-    const unsigned gs = graph_slot(dc);
-    const bool smp = sampler_on(dc);
-    hipGraph_t& graph = smp ? (gs ? dc->s_graph_m[gs] : dc->s_graph) : (gs ? dc->graph_m[gs] : dc->graph);
-    hipGraphExec_t& exec = smp ? (gs ? dc->s_exec_m[gs] : dc->s_exec) : (gs ? dc->exec_m[gs] : dc->exec);
-    if (!exec) {
-        GTR_CHECK(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue(dc);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(stream(), &g);
-        if (rc) { if (g) hipGraphDestroy(g); return rc; }
-        GTR_CHECK(e);
-        graph = g;
-        GTR_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    }
+    hipGraphExec_t exec = nullptr;
+    if (int rc = graph_exec(dc, 1, &exec)) return rc;
     GTR_CHECK(hipGraphLaunch(exec, stream()));
     return 0;
 }
@@ -2563,342 +2535,7 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
     return persist_aborted(dc);
 }
 
-// ---- top-k sampling (include/gten_hip_sample.h, gten_decode_sample.h)
-static int sample_check(int top_k, float temp, const char* who)
-{
-    GTR_REQUIRE(top_k >= 0, "%s: top_k %d < 0", who, top_k);
-    GTR_REQUIRE(top_k == 0 || (std::isfinite(temp) && temp > 0.f), "%s: temperature %g must be finite and > 0 when top_k >= 1", who, (double)temp);
-    return 0;
-}
-
-int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, float temp, uint64_t seed, uint32_t stream_id)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_sampling: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    if (int rc = sample_check(top_k, temp, "decoder_set_sampling")) return rc;
-    GTR_REQUIRE(top_k == 0 || !dc->persist_on, "decoder_set_sampling: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    SampleParam& p = dc->samp_host[(size_t)seq];
-    dc->n_sampling += (top_k > 0 ? 1 : 0) - (p.top_k > 0 ? 1 : 0);
-    const int table1 = p.table1;
-    const unsigned until = p.until, lp1 = p.lp1;
-    p = SampleParam{};
-    p.table1 = table1;           // (the bias binding is gten_hip_decoder_set_seq_bias's half of the request)
-    p.until = until;
-    p.lp1 = lp1;                 // (and the log-prob request gten_hip_decoder_set_logprobs's)
-    p.top_k = top_k;
-    p.temp = top_k > 0 ? temp : 0.f;
-    p.stream = stream_id;
-    p.seed_lo = (unsigned)(seed & 0xffffffffu);
-    p.seed_hi = (unsigned)(seed >> 32);
-    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-static SampleRowParam* g_rows_dev = nullptr;      // gten_hip_sample_rows' per-row requests (grow-only)
-static size_t g_rows_cap = 0;
-
-// the per-row requests of one operator call on the device (g_rows_dev, grown when needed), queued on the stream
-static int rows_upload(const std::vector<SampleRowParam>& rows)
-{
-    const size_t n_rows = rows.size();
-    if (g_rows_cap < n_rows) {
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        if (g_rows_dev) GTR_CHECK(hipFree(g_rows_dev));
-        g_rows_dev = nullptr;
-        g_rows_cap = 0;
-        GTR_CHECK(hipMalloc((void**)&g_rows_dev, n_rows * sizeof(SampleRowParam)));
-        g_rows_cap = n_rows;
-    }
-    GTR_CHECK(hipMemcpyAsync(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam), hipMemcpyHostToDevice, stream()));
-    return 0;
-}
-
-int gten_hip_sample_rows(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* top_k_host, const float* temp_host,
-                         uint64_t seed, const uint32_t* stream_host, const int32_t* position_host, int32_t* out)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0, "sample_rows: %d rows of %d logits (n_vocab in [1, 65535]), stride %lld",
-                n_rows, n_vocab, row_stride);
-    if (n_rows == 0) return 0;
-    GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host, "sample_rows: null argument");
-    std::vector<SampleRowParam> rows((size_t)n_rows);
-    for (int r = 0; r < n_rows; r++) {
-        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows")) return rc;
-        GTR_REQUIRE(position_host[r] >= 0, "sample_rows: position %d of row %d", position_host[r], r);
-        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
-    }
-    if (int rc = rows_upload(rows)) return rc;
-    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, (const SampleRowParam*)g_rows_dev,
-               (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
-    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
-    return 0;
-}
-
-// ---- bias tables (include/gten_hip_bias.h, gten_decode_sample.h)
-static int bias_ensure(gten_hip_decoder* dc)
-{
-    if (dc->bias) return 0;
-    const size_t bytes = (size_t)GTEN_HIP_BIAS_TABLES * (size_t)dc->d.n_vocab * sizeof(float);
-    GTR_CHECK(hipMalloc((void**)&dc->bias, bytes));
-    GTR_CHECK(hipMemsetAsync(dc->bias, 0, bytes, stream()));                 // every table: no bias
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-int gten_hip_decoder_set_bias_table(gten_hip_decoder* dc, int table, const int32_t* ids_host, const float* values_host, int n, float fill)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc, "decoder_set_bias_table: null decoder");
-    GTR_REQUIRE(!dc->persist_on, "decoder_set_bias_table: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    GTR_REQUIRE(table >= 0 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_bias_table: table %d outside [0, %d)", table, GTEN_HIP_BIAS_TABLES);
-    GTR_REQUIRE(n >= 0 && (n == 0 || (ids_host && values_host)), "decoder_set_bias_table: %d pairs, null lists", n);
-    const int V = dc->d.n_vocab;
-    auto value_ok = [](float v) { return v == -INFINITY || (std::isfinite(v) && std::fabs(v) <= GTEN_HIP_BIAS_MAX); };
-    GTR_REQUIRE(value_ok(fill), "decoder_set_bias_table: fill %g (finite with |b| <= 1e30, or -inf)", (double)fill);
-    std::vector<float> row((size_t)V, fill);
-    std::vector<char> seen((size_t)V, 0);
-    for (int i = 0; i < n; i++) {
-        const int id = ids_host[i];
-        GTR_REQUIRE(id >= 0 && id < V, "decoder_set_bias_table: id %d outside [0, %d)", id, V);
-        GTR_REQUIRE(!seen[(size_t)id], "decoder_set_bias_table: id %d is listed twice", id);
-        GTR_REQUIRE(value_ok(values_host[i]), "decoder_set_bias_table: value %g of id %d (finite with |b| <= 1e30, or -inf)", (double)values_host[i], id);
-        seen[(size_t)id] = 1;
-        row[(size_t)id] = values_host[i];
-    }
-    bool any = false;
-    for (int j = 0; j < V && !any; j++) any = row[(size_t)j] > -INFINITY;
-    GTR_REQUIRE(any, "decoder_set_bias_table: table %d would ban every id", table);
-    if (int rc = bias_ensure(dc)) return rc;
-    GTR_CHECK(hipMemcpyAsync(dc->bias + (size_t)table * (size_t)V, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));    // `row` lives on this stack frame
-    return 0;
-}
-
-int gten_hip_decoder_set_seq_bias(gten_hip_decoder* dc, int seq, int table, int until)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_seq_bias: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    GTR_REQUIRE(table >= -1 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_seq_bias: table %d outside [-1, %d)", table, GTEN_HIP_BIAS_TABLES);
-    GTR_REQUIRE(until >= 0, "decoder_set_seq_bias: until %d < 0", until);
-    GTR_REQUIRE(table < 0 || !dc->persist_on, "decoder_set_seq_bias: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    SampleParam& p = dc->samp_host[(size_t)seq];
-    if (table >= 0 && !dc->bias_on) {
-        // the first binding of this decoder: from now on its sampler launch is the one that knows the tables
-        if (int rc = bias_ensure(dc)) return rc;
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        GTR_CHECK(drop_graphs(dc));
-        dc->bias_on = true;
-    }
-    dc->n_bound += (table >= 0 ? 1 : 0) - (p.table1 > 0 ? 1 : 0);
-    p.table1 = table + 1;
-    p.until = table >= 0 ? (unsigned)until : 0u;
-    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-int gten_hip_decoder_bias_info(gten_hip_decoder* dc, int* n_tables, int32_t* table_host, int32_t* until_host, int table, const float** table_row)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc, "decoder_bias_info: null decoder");
-    if (n_tables) *n_tables = GTEN_HIP_BIAS_TABLES;
-    for (int q = 0; q < dc->n_seq; q++) {
-        const SampleParam& p = dc->samp_host[(size_t)q];
-        if (table_host) table_host[q] = p.table1 - 1;
-        if (until_host) until_host[q] = p.table1 > 0 ? (int32_t)p.until : 0;
-    }
-    if (table_row) *table_row = (dc->bias && table >= 0 && table < GTEN_HIP_BIAS_TABLES) ? dc->bias + (size_t)table * (size_t)dc->d.n_vocab : nullptr;
-    return 0;
-}
-
-int gten_hip_sample_rows_biased(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
-                                const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
-                                const int32_t* position_host, int32_t* out)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0 && bias_stride >= 0,
-                "sample_rows_biased: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", n_rows, n_vocab, row_stride, bias_stride);
-    if (n_rows == 0) return 0;
-    GTR_REQUIRE(logits && bias && out && top_k_host && temp_host && stream_host && position_host, "sample_rows_biased: null argument");
-    std::vector<SampleRowParam> rows((size_t)n_rows);
-    for (int r = 0; r < n_rows; r++) {
-        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows_biased")) return rc;
-        GTR_REQUIRE(position_host[r] >= 0, "sample_rows_biased: position %d of row %d", position_host[r], r);
-        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
-    }
-    if (int rc = rows_upload(rows)) return rc;
-    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_b, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, bias, bias_stride,
-               (const SampleRowParam*)g_rows_dev, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out);
-    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` lives on this stack frame
-    return 0;
-}
-
-// ---- log-probs of the generated ids (include/gten_hip_logprobs.h, gten_decode_logprobs.h)
-int gten_hip_decoder_set_logprobs(gten_hip_decoder* dc, int seq, int n_top)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    GTR_REQUIRE(n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_set_logprobs: n_top %d outside [-1, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
-    GTR_REQUIRE(n_top < 0 || !dc->persist_on, "decoder_set_logprobs: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    SampleParam& p = dc->samp_host[(size_t)seq];
-    if (n_top >= 0 && !dc->lp_on) {
-        // the first request of this decoder: the record buffer, and from now on its sampler launch is the one that writes records
-        const size_t bytes = (size_t)dc->n_seq * (size_t)(dc->d.max_ctx + 2) * sizeof(LpRecord);
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        if (!dc->lp) {
-            GTR_CHECK(hipMalloc((void**)&dc->lp, bytes));
-            GTR_CHECK(hipMemsetAsync(dc->lp, 0, bytes, stream()));
-            GTR_CHECK(hipStreamSynchronize(stream()));
-        }
-        GTR_CHECK(drop_graphs(dc));
-        dc->lp_on = true;
-    }
-    dc->n_asking += (n_top >= 0 ? 1 : 0) - (p.lp1 > 0u ? 1 : 0);
-    p.lp1 = (unsigned)(n_top + 1);
-    GTR_CHECK(hipMemcpyAsync(dc->samp + seq, &p, sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-int gten_hip_decoder_logprobs(gten_hip_decoder* dc, int seq, int n_from, int count, int n_top, float* logprob_host, int32_t* top_id_host,
-                              float* top_logprob_host)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
-    GTR_REQUIRE(count >= 0 && n_from >= 0 && n_from + count <= dc->d.max_ctx + 2, "decoder_logprobs: positions [%d, %d + %d) outside [0, %d)", n_from, n_from,
-                count, dc->d.max_ctx + 2);
-    GTR_REQUIRE(dc->lp, "decoder_logprobs: no sequence of this decoder has asked for log-probs (gten_hip_decoder_set_logprobs)");
-    if (count == 0) return 0;
-    GTR_REQUIRE(logprob_host && (n_top == 0 || (top_id_host && top_logprob_host)), "decoder_logprobs: null output");
-    std::vector<LpRecord> rec((size_t)count);
-    GTR_CHECK(hipMemcpyAsync(rec.data(), dc->lp + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + n_from, rec.size() * sizeof(LpRecord), hipMemcpyDeviceToHost,
-                             stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    for (int i = 0; i < count; i++) {
-        logprob_host[i] = rec[(size_t)i].logprob;
-        for (int j = 0; j < n_top; j++) {
-            top_id_host[(size_t)i * n_top + j] = rec[(size_t)i].top_id[j];
-            top_logprob_host[(size_t)i * n_top + j] = rec[(size_t)i].top_logprob[j];
-        }
-    }
-    return persist_aborted(dc);
-}
-
-int gten_hip_decoder_logprobs_info(gten_hip_decoder* dc, int* top_cap, int32_t* n_top_host, const void** records, long long* seq_stride_bytes,
-                                   int* record_bytes)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc, "decoder_logprobs_info: null decoder");
-    if (top_cap) *top_cap = GTEN_HIP_LOGPROBS_TOP;
-    if (n_top_host) for (int q = 0; q < dc->n_seq; q++) n_top_host[q] = (int32_t)dc->samp_host[(size_t)q].lp1 - 1;
-    if (records) *records = dc->lp;
-    if (seq_stride_bytes) *seq_stride_bytes = (long long)(dc->d.max_ctx + 2) * (long long)sizeof(LpRecord);
-    if (record_bytes) *record_bytes = (int)sizeof(LpRecord);
-    return 0;
-}
-
-int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* ids, int n_top, float* logprob_out,
-                              int32_t* top_id_out, float* top_logprob_out)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(n_vocab >= 1 && row_stride >= n_vocab, "row_top_logprobs: rows of %d logits (>= 1), stride %lld (>= n_vocab)", n_vocab, row_stride);
-    GTR_REQUIRE(n_rows >= 1 && n_rows <= 65535, "row_top_logprobs: %d rows outside [1, 65535]", n_rows);
-    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "row_top_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
-    GTR_REQUIRE(logits && ids && logprob_out && (n_top == 0 || (top_id_out && top_logprob_out)), "row_top_logprobs: null argument");
-    GTR_LAUNCH(KT_DEC_SAMPLE, k_row_top_logprobs, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, ids, n_top, logprob_out, top_id_out,
-               top_logprob_out);
-    return 0;
-}
-
-// ---- top-p / min-p cuts (include/gten_hip_nucleus.h, gten_decode_nucleus.h)
-static int cut_check(float top_p, float min_p, const char* who)
-{
-    GTR_REQUIRE(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "%s: top_p %g outside (0, 1]", who, (double)top_p);
-    GTR_REQUIRE(std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f, "%s: min_p %g outside [0, 1]", who, (double)min_p);
-    return 0;
-}
-static CutParam cut_param(float top_p, float min_p)
-{
-    return CutParam{top_p, min_p > 0.f ? (float)std::log((double)min_p) : -INFINITY, min_p, (top_p == 1.f && min_p == 0.f) ? 0u : 1u};
-}
-
-int gten_hip_decoder_set_cut(gten_hip_decoder* dc, int seq, float top_p, float min_p)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_cut: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    if (int rc = cut_check(top_p, min_p, "decoder_set_cut")) return rc;
-    const CutParam c = cut_param(top_p, min_p);
-    GTR_REQUIRE(c.on == 0u || !dc->persist_on, "decoder_set_cut: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    if (c.on == 0u && !dc->cut_on) return 0;       // nobody has ever cut: nothing to clear
-    if (!dc->cut_on) {
-        // the first cut of this decoder: the array, and from now on its sampler launch is the one that reads it
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        dc->cut_host.assign((size_t)dc->n_seq, cut_param(1.f, 0.f));
-        if (!dc->cut) GTR_CHECK(hipMalloc((void**)&dc->cut, (size_t)dc->n_seq * sizeof(CutParam)));
-        GTR_CHECK(hipMemcpyAsync(dc->cut, dc->cut_host.data(), dc->cut_host.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        GTR_CHECK(drop_graphs(dc));
-        dc->cut_on = true;
-    }
-    dc->cut_host[(size_t)seq] = c;
-    GTR_CHECK(hipMemcpyAsync(dc->cut + seq, &dc->cut_host[(size_t)seq], sizeof(CutParam), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipStreamSynchronize(stream()));
-    return 0;
-}
-
-int gten_hip_decoder_cut_info(gten_hip_decoder* dc, float* top_p_host, float* min_p_host, float* t_host, int* on)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc, "decoder_cut_info: null decoder");
-    for (int q = 0; q < dc->n_seq; q++) {
-        const CutParam c = dc->cut_on ? dc->cut_host[(size_t)q] : cut_param(1.f, 0.f);
-        if (top_p_host) top_p_host[q] = c.top_p;
-        if (min_p_host) min_p_host[q] = c.min_p;
-        if (t_host) t_host[q] = c.t;
-    }
-    if (on) *on = dc->cut_on ? 1 : 0;
-    return 0;
-}
-
-static CutParam* g_cut_dev = nullptr;             // gten_hip_sample_rows_cut's per-row cuts (grow-only)
-static size_t g_cut_cap = 0;
-
-int gten_hip_sample_rows_cut(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
-                             const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
-                             const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out,
-                             gten_hip_cut_info* info_out)
-{
-    GTR_NEED_INIT();
-    GTR_REQUIRE(n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0 && bias_stride >= 0,
-                "sample_rows_cut: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", n_rows, n_vocab, row_stride, bias_stride);
-    if (n_rows == 0) return 0;
-    GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host && top_p_host && min_p_host, "sample_rows_cut: null argument");
-    std::vector<SampleRowParam> rows((size_t)n_rows);
-    std::vector<CutParam> cuts((size_t)n_rows);
-    for (int r = 0; r < n_rows; r++) {
-        if (int rc = sample_check(top_k_host[r], temp_host[r], "sample_rows_cut")) return rc;
-        if (int rc = cut_check(top_p_host[r], min_p_host[r], "sample_rows_cut")) return rc;
-        GTR_REQUIRE(position_host[r] >= 0, "sample_rows_cut: position %d of row %d", position_host[r], r);
-        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
-        cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
-    }
-    if (int rc = rows_upload(rows)) return rc;
-    if (g_cut_cap < (size_t)n_rows) {
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        if (g_cut_dev) GTR_CHECK(hipFree(g_cut_dev));
-        g_cut_dev = nullptr;
-        g_cut_cap = 0;
-        GTR_CHECK(hipMalloc((void**)&g_cut_dev, (size_t)n_rows * sizeof(CutParam)));
-        g_cut_cap = (size_t)n_rows;
-    }
-    GTR_CHECK(hipMemcpyAsync(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
-    GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_cut, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, bias, bias_stride,
-               (const SampleRowParam*)g_rows_dev, (const CutParam*)g_cut_dev, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), out,
-               (CutInfo*)info_out);
-    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` and `cuts` live on this stack frame
-    return 0;
-}
+// sampling, bias tables, log-probs and cuts: the setters of SamplerState and the row operators
+#include "gten_decode_sampler_api.h"
 
 } // extern "C"

@@ -1,0 +1,327 @@
+// gten_decode_sampler_api.h -- the sampler's entry points: top-k sampling (include/gten_hip_sample.h), bias tables
+// (include/gten_hip_bias.h), log-probs of the generated ids (include/gten_hip_logprobs.h, §3.11) and top-p / min-p
+// cuts (include/gten_hip_nucleus.h, §3.12).  Host code only; included by gten_decode.hip inside its extern "C" block, behind the
+// decoder's other entry points.  The kernels are in gten_decode_sample.h, gten_decode_logprobs.h and gten_decode_nucleus.h; what
+// the decoder keeps of a request, and which launch a step ends in, is SamplerState's comment in gten_decode.hip.
+
+// ---- what the setters share
+static int sample_check(int top_k, float temp, const char* who)
+{
+    GTR_REQUIRE(top_k >= 0, "%s: top_k %d < 0", who, top_k);
+    GTR_REQUIRE(top_k == 0 || (std::isfinite(temp) && temp > 0.f), "%s: temperature %g must be finite and > 0 when top_k >= 1", who, (double)temp);
+    return 0;
+}
+static int cut_check(float top_p, float min_p, const char* who)
+{
+    GTR_REQUIRE(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f, "%s: top_p %g outside (0, 1]", who, (double)top_p);
+    GTR_REQUIRE(std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f, "%s: min_p %g outside [0, 1]", who, (double)min_p);
+    return 0;
+}
+static CutParam cut_param(float top_p, float min_p)
+{
+    return CutParam{top_p, min_p > 0.f ? (float)std::log((double)min_p) : -INFINITY, min_p, (top_p == 1.f && min_p == 0.f) ? 0u : 1u};
+}
+
+// sequence `seq`'s request as the host holds it, to the device (the steps queued before it have finished when this returns)
+static int request_upload(gten_hip_decoder* dc, int seq)
+{
+    GTR_CHECK(hipMemcpyAsync(dc->smp.samp + seq, &dc->smp.samp_host[(size_t)seq], sizeof(SampleParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+// The first use of a feature on this decoder (`on` is its SamplerState flag): with nothing in flight, `make` allocates and
+// initialises what the feature needs (a buffer that an earlier call already made is kept); then the graphs captured so far are
+// dropped -- they end in the rung below -- and from now on launch_step_end takes the feature's rung.
+static int first_use(gten_hip_decoder* dc, bool& on, int (*make)(gten_hip_decoder*))
+{
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    if (int rc = make(dc)) return rc;
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    GTR_CHECK(drop_graphs(dc));
+    on = true;
+    return 0;
+}
+static int bias_make(gten_hip_decoder* dc)          // every table: no bias
+{
+    if (dc->smp.bias) return 0;
+    const size_t bytes = (size_t)GTEN_HIP_BIAS_TABLES * (size_t)dc->d.n_vocab * sizeof(float);
+    GTR_CHECK(hipMalloc((void**)&dc->smp.bias, bytes));
+    GTR_CHECK(hipMemsetAsync(dc->smp.bias, 0, bytes, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+static int lp_make(gten_hip_decoder* dc)            // every record zeroed
+{
+    if (dc->smp.lp) return 0;
+    const size_t bytes = (size_t)dc->n_seq * (size_t)(dc->d.max_ctx + 2) * sizeof(LpRecord);
+    GTR_CHECK(hipMalloc((void**)&dc->smp.lp, bytes));
+    GTR_CHECK(hipMemsetAsync(dc->smp.lp, 0, bytes, stream()));
+    return 0;
+}
+static int cut_make(gten_hip_decoder* dc)           // every sequence: no cut
+{
+    SamplerState& s = dc->smp;
+    s.cut_host.assign((size_t)dc->n_seq, cut_param(1.f, 0.f));
+    if (!s.cut) GTR_CHECK(hipMalloc((void**)&s.cut, (size_t)dc->n_seq * sizeof(CutParam)));
+    GTR_CHECK(hipMemcpyAsync(s.cut, s.cut_host.data(), s.cut_host.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+    return 0;
+}
+
+// ---- the decoder's requests
+int gten_hip_decoder_set_sampling(gten_hip_decoder* dc, int seq, int top_k, float temp, uint64_t seed, uint32_t stream_id)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_sampling: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    if (int rc = sample_check(top_k, temp, "decoder_set_sampling")) return rc;
+    GTR_REQUIRE(top_k == 0 || !dc->persist_on, "decoder_set_sampling: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    SampleParam& p = dc->smp.samp_host[(size_t)seq];
+    dc->smp.n_sampling += (top_k > 0 ? 1 : 0) - (p.top_k > 0 ? 1 : 0);
+    p.top_k = top_k;
+    p.temp = top_k > 0 ? temp : 0.f;
+    p.stream = stream_id;
+    p.seed_lo = (unsigned)(seed & 0xffffffffu);
+    p.seed_hi = (unsigned)(seed >> 32);
+    return request_upload(dc, seq);
+}
+
+int gten_hip_decoder_set_bias_table(gten_hip_decoder* dc, int table, const int32_t* ids_host, const float* values_host, int n, float fill)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_set_bias_table: null decoder");
+    GTR_REQUIRE(!dc->persist_on, "decoder_set_bias_table: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    GTR_REQUIRE(table >= 0 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_bias_table: table %d outside [0, %d)", table, GTEN_HIP_BIAS_TABLES);
+    GTR_REQUIRE(n >= 0 && (n == 0 || (ids_host && values_host)), "decoder_set_bias_table: %d pairs, null lists", n);
+    const int V = dc->d.n_vocab;
+    auto value_ok = [](float v) { return v == -INFINITY || (std::isfinite(v) && std::fabs(v) <= GTEN_HIP_BIAS_MAX); };
+    GTR_REQUIRE(value_ok(fill), "decoder_set_bias_table: fill %g (finite with |b| <= 1e30, or -inf)", (double)fill);
+    std::vector<float> row((size_t)V, fill);
+    std::vector<char> seen((size_t)V, 0);
+    for (int i = 0; i < n; i++) {
+        const int id = ids_host[i];
+        GTR_REQUIRE(id >= 0 && id < V, "decoder_set_bias_table: id %d outside [0, %d)", id, V);
+        GTR_REQUIRE(!seen[(size_t)id], "decoder_set_bias_table: id %d is listed twice", id);
+        GTR_REQUIRE(value_ok(values_host[i]), "decoder_set_bias_table: value %g of id %d (finite with |b| <= 1e30, or -inf)", (double)values_host[i], id);
+        seen[(size_t)id] = 1;
+        row[(size_t)id] = values_host[i];
+    }
+    bool any = false;
+    for (int j = 0; j < V && !any; j++) any = row[(size_t)j] > -INFINITY;
+    GTR_REQUIRE(any, "decoder_set_bias_table: table %d would ban every id", table);
+    if (int rc = bias_make(dc)) return rc;
+    GTR_CHECK(hipMemcpyAsync(dc->smp.bias + (size_t)table * (size_t)V, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `row` lives on this stack frame
+    return 0;
+}
+
+int gten_hip_decoder_set_seq_bias(gten_hip_decoder* dc, int seq, int table, int until)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_seq_bias: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(table >= -1 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_seq_bias: table %d outside [-1, %d)", table, GTEN_HIP_BIAS_TABLES);
+    GTR_REQUIRE(until >= 0, "decoder_set_seq_bias: until %d < 0", until);
+    GTR_REQUIRE(table < 0 || !dc->persist_on, "decoder_set_seq_bias: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    if (table >= 0 && !dc->smp.bias_on)
+        if (int rc = first_use(dc, dc->smp.bias_on, bias_make)) return rc;
+    SampleParam& p = dc->smp.samp_host[(size_t)seq];
+    dc->smp.n_bound += (table >= 0 ? 1 : 0) - (p.table1 > 0 ? 1 : 0);
+    p.table1 = table + 1;
+    p.until = table >= 0 ? (unsigned)until : 0u;
+    return request_upload(dc, seq);
+}
+
+int gten_hip_decoder_bias_info(gten_hip_decoder* dc, int* n_tables, int32_t* table_host, int32_t* until_host, int table, const float** table_row)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_bias_info: null decoder");
+    if (n_tables) *n_tables = GTEN_HIP_BIAS_TABLES;
+    for (int q = 0; q < dc->n_seq; q++) {
+        const SampleParam& p = dc->smp.samp_host[(size_t)q];
+        if (table_host) table_host[q] = p.table1 - 1;
+        if (until_host) until_host[q] = p.table1 > 0 ? (int32_t)p.until : 0;
+    }
+    if (table_row)
+        *table_row = (dc->smp.bias && table >= 0 && table < GTEN_HIP_BIAS_TABLES) ? dc->smp.bias + (size_t)table * (size_t)dc->d.n_vocab : nullptr;
+    return 0;
+}
+
+int gten_hip_decoder_set_logprobs(gten_hip_decoder* dc, int seq, int n_top)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_set_logprobs: n_top %d outside [-1, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(n_top < 0 || !dc->persist_on, "decoder_set_logprobs: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    if (n_top >= 0 && !dc->smp.lp_on)
+        if (int rc = first_use(dc, dc->smp.lp_on, lp_make)) return rc;
+    SampleParam& p = dc->smp.samp_host[(size_t)seq];
+    dc->smp.n_asking += (n_top >= 0 ? 1 : 0) - (p.lp1 > 0u ? 1 : 0);
+    p.lp1 = (unsigned)(n_top + 1);
+    return request_upload(dc, seq);
+}
+
+int gten_hip_decoder_logprobs(gten_hip_decoder* dc, int seq, int n_from, int count, int n_top, float* logprob_host, int32_t* top_id_host,
+                              float* top_logprob_host)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_logprobs: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "decoder_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(count >= 0 && n_from >= 0 && n_from + count <= dc->d.max_ctx + 2, "decoder_logprobs: positions [%d, %d + %d) outside [0, %d)", n_from, n_from,
+                count, dc->d.max_ctx + 2);
+    GTR_REQUIRE(dc->smp.lp, "decoder_logprobs: no sequence of this decoder has asked for log-probs (gten_hip_decoder_set_logprobs)");
+    if (count == 0) return 0;
+    GTR_REQUIRE(logprob_host && (n_top == 0 || (top_id_host && top_logprob_host)), "decoder_logprobs: null output");
+    std::vector<LpRecord> rec((size_t)count);
+    GTR_CHECK(hipMemcpyAsync(rec.data(), dc->smp.lp + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + n_from, rec.size() * sizeof(LpRecord), hipMemcpyDeviceToHost,
+                             stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    for (int i = 0; i < count; i++) {
+        logprob_host[i] = rec[(size_t)i].logprob;
+        for (int j = 0; j < n_top; j++) {
+            top_id_host[(size_t)i * n_top + j] = rec[(size_t)i].top_id[j];
+            top_logprob_host[(size_t)i * n_top + j] = rec[(size_t)i].top_logprob[j];
+        }
+    }
+    return persist_aborted(dc);
+}
+
+int gten_hip_decoder_logprobs_info(gten_hip_decoder* dc, int* top_cap, int32_t* n_top_host, const void** records, long long* seq_stride_bytes,
+                                   int* record_bytes)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_logprobs_info: null decoder");
+    if (top_cap) *top_cap = GTEN_HIP_LOGPROBS_TOP;
+    if (n_top_host) for (int q = 0; q < dc->n_seq; q++) n_top_host[q] = (int32_t)dc->smp.samp_host[(size_t)q].lp1 - 1;
+    if (records) *records = dc->smp.lp;
+    if (seq_stride_bytes) *seq_stride_bytes = (long long)(dc->d.max_ctx + 2) * (long long)sizeof(LpRecord);
+    if (record_bytes) *record_bytes = (int)sizeof(LpRecord);
+    return 0;
+}
+
+int gten_hip_decoder_set_cut(gten_hip_decoder* dc, int seq, float top_p, float min_p)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_cut: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    if (int rc = cut_check(top_p, min_p, "decoder_set_cut")) return rc;
+    const CutParam c = cut_param(top_p, min_p);
+    GTR_REQUIRE(c.on == 0u || !dc->persist_on, "decoder_set_cut: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    if (c.on == 0u && !dc->smp.cut_on) return 0;       // nobody has ever cut: nothing to clear
+    if (!dc->smp.cut_on)
+        if (int rc = first_use(dc, dc->smp.cut_on, cut_make)) return rc;
+    dc->smp.cut_host[(size_t)seq] = c;
+    GTR_CHECK(hipMemcpyAsync(dc->smp.cut + seq, &dc->smp.cut_host[(size_t)seq], sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_cut_info(gten_hip_decoder* dc, float* top_p_host, float* min_p_host, float* t_host, int* on)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_cut_info: null decoder");
+    for (int q = 0; q < dc->n_seq; q++) {
+        const CutParam c = dc->smp.cut_on ? dc->smp.cut_host[(size_t)q] : cut_param(1.f, 0.f);
+        if (top_p_host) top_p_host[q] = c.top_p;
+        if (min_p_host) min_p_host[q] = c.min_p;
+        if (t_host) t_host[q] = c.t;
+    }
+    if (on) *on = dc->smp.cut_on ? 1 : 0;
+    return 0;
+}
+
+// ---- the row operators: the sampler on rows of logits that are not a decoder's
+struct GrowBuf { void* dev = nullptr; size_t bytes = 0; };      // a device buffer that only grows
+static GrowBuf g_rows_dev, g_cut_dev;                           // the per-row requests and cuts of one operator call
+
+// `bytes` of the host's to the device buffer (grown when needed), queued on the stream
+static int grow_upload(GrowBuf& b, const void* host, size_t bytes)
+{
+    if (b.bytes < bytes) {
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        if (b.dev) GTR_CHECK(hipFree(b.dev));
+        b = GrowBuf{};
+        GTR_CHECK(hipMalloc(&b.dev, bytes));
+        b.bytes = bytes;
+    }
+    GTR_CHECK(hipMemcpyAsync(b.dev, host, bytes, hipMemcpyHostToDevice, stream()));
+    return 0;
+}
+
+// the three operators differ in what they take: ROWS_PLAIN no bias and no cuts, ROWS_BIASED a bias it requires, ROWS_CUT cuts and a
+// bias it accepts (null: none).  `who` names the operator in every message.
+enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT };
+static int sample_rows_common(const char* who, RowsLevel level, const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias,
+                              long long bias_stride, const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                              const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out, gten_hip_cut_info* info_out)
+{
+    GTR_NEED_INIT();
+    const bool shape_ok = n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0;
+    if (level == ROWS_PLAIN)
+        GTR_REQUIRE(shape_ok, "%s: %d rows of %d logits (n_vocab in [1, 65535]), stride %lld", who, n_rows, n_vocab, row_stride);
+    else
+        GTR_REQUIRE(shape_ok && bias_stride >= 0, "%s: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", who, n_rows, n_vocab, row_stride,
+                    bias_stride);
+    if (n_rows == 0) return 0;
+    GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host && (level != ROWS_BIASED || bias) &&
+                (level != ROWS_CUT || (top_p_host && min_p_host)), "%s: null argument", who);
+    std::vector<SampleRowParam> rows((size_t)n_rows);
+    std::vector<CutParam> cuts(level == ROWS_CUT ? (size_t)n_rows : 0);
+    for (int r = 0; r < n_rows; r++) {
+        if (int rc = sample_check(top_k_host[r], temp_host[r], who)) return rc;
+        if (level == ROWS_CUT)
+            if (int rc = cut_check(top_p_host[r], min_p_host[r], who)) return rc;
+        GTR_REQUIRE(position_host[r] >= 0, "%s: position %d of row %d", who, position_host[r], r);
+        rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
+        if (level == ROWS_CUT) cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
+    }
+    if (int rc = grow_upload(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam))) return rc;
+    const SampleRowParam* par = (const SampleRowParam*)g_rows_dev.dev;
+    const unsigned seed_lo = (unsigned)(seed & 0xffffffffu), seed_hi = (unsigned)(seed >> 32);
+    const dim3 grid(n_rows), block(SMP_THREADS);
+    if (level == ROWS_CUT) {
+        if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_cut, grid, block, 0, logits, n_vocab, row_stride, bias, bias_stride, par, (const CutParam*)g_cut_dev.dev,
+                   seed_lo, seed_hi, out, (CutInfo*)info_out);
+    } else if (level == ROWS_BIASED) {
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_b, grid, block, 0, logits, n_vocab, row_stride, bias, bias_stride, par, seed_lo, seed_hi, out);
+    } else {
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows, grid, block, 0, logits, n_vocab, row_stride, par, seed_lo, seed_hi, out);
+    }
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `rows` and `cuts` live on this stack frame
+    return 0;
+}
+
+int gten_hip_sample_rows(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* top_k_host, const float* temp_host,
+                         uint64_t seed, const uint32_t* stream_host, const int32_t* position_host, int32_t* out)
+{
+    return sample_rows_common("sample_rows", ROWS_PLAIN, logits, n_rows, n_vocab, row_stride, nullptr, 0, top_k_host, temp_host, seed, stream_host,
+                              position_host, nullptr, nullptr, out, nullptr);
+}
+
+int gten_hip_sample_rows_biased(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                                const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                                const int32_t* position_host, int32_t* out)
+{
+    return sample_rows_common("sample_rows_biased", ROWS_BIASED, logits, n_rows, n_vocab, row_stride, bias, bias_stride, top_k_host, temp_host, seed,
+                              stream_host, position_host, nullptr, nullptr, out, nullptr);
+}
+
+int gten_hip_sample_rows_cut(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                             const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                             const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out,
+                             gten_hip_cut_info* info_out)
+{
+    return sample_rows_common("sample_rows_cut", ROWS_CUT, logits, n_rows, n_vocab, row_stride, bias, bias_stride, top_k_host, temp_host, seed, stream_host,
+                              position_host, top_p_host, min_p_host, out, info_out);
+}
+
+int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* ids, int n_top, float* logprob_out,
+                              int32_t* top_id_out, float* top_logprob_out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(n_vocab >= 1 && row_stride >= n_vocab, "row_top_logprobs: rows of %d logits (>= 1), stride %lld (>= n_vocab)", n_vocab, row_stride);
+    GTR_REQUIRE(n_rows >= 1 && n_rows <= 65535, "row_top_logprobs: %d rows outside [1, 65535]", n_rows);
+    GTR_REQUIRE(n_top >= 0 && n_top <= GTEN_HIP_LOGPROBS_TOP, "row_top_logprobs: n_top %d outside [0, %d]", n_top, GTEN_HIP_LOGPROBS_TOP);
+    GTR_REQUIRE(logits && ids && logprob_out && (n_top == 0 || (top_id_out && top_logprob_out)), "row_top_logprobs: null argument");
+    GTR_LAUNCH(KT_DEC_SAMPLE, k_row_top_logprobs, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, ids, n_top, logprob_out, top_id_out,
+               top_logprob_out);
+    return 0;
+}
