@@ -28,6 +28,7 @@
 #include "gten_hip_bias.h"
 #include "gten_hip_logprobs.h"
 #include "gten_hip_nucleus.h"
+#include "gten_hip_penalty.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 
@@ -108,6 +109,7 @@ static_assert(LP_TOP == GTEN_HIP_LOGPROBS_TOP && sizeof(LpRecord) == GTEN_HIP_LO
 #include "gten_decode_nucleus.h"
 static_assert(CUT_MASS_BITS == GTEN_HIP_NUCLEUS_MASS_BITS && sizeof(CutInfo) == GTEN_HIP_NUCLEUS_INFO_BYTES && sizeof(CutInfo) == sizeof(gten_hip_cut_info),
               "gten_decode_nucleus.h and include/gten_hip_nucleus.h disagree");
+#include "gten_decode_penalty.h"
 
 // --------------------------------------------------------------- host side
 
@@ -119,9 +121,9 @@ struct CapturedGraph { hipGraph_t graph; hipGraphExec_t exec; };
 // device and on the host; each setter owns its fields of it: top-k sampling (gten_hip_decoder_set_sampling, include/gten_hip_sample.h)
 // top_k .. seed, a bias table (include/gten_hip_bias.h) table1 and until, a log-prob request (include/gten_hip_logprobs.h) lp1.
 //
-// The step ends in ONE launch, chosen by launch_step_end: k_dec_argmax while no sequence samples, is bound to a table or asks for
-// log-probs (sampler_on), the sampler launch once one does -- two sets of graphs.  Which sampler kernel that launch is follows from
-// the features this decoder has EVER used, the latest rung first: k_dec_sample_cut (cut_on), k_dec_sample_lp (lp_on),
+// The step ends in ONE launch, chosen by launch_step_end: k_dec_argmax while no sequence samples, is bound to a table, asks for
+// log-probs or is penalised (sampler_on), the sampler launch once one does -- two sets of graphs.  Which sampler kernel that launch is
+// follows from the features this decoder has EVER used, the latest rung first: k_dec_sample_pen (pen_on), k_dec_sample_cut (cut_on), k_dec_sample_lp (lp_on),
 // k_dec_sample_b (bias_on), k_dec_sample.  Each rung treats a sequence without its feature exactly as the rung below does, so a
 // feature switched off again costs nothing but the wider kernel.  A feature's buffer is made by its first use (first_use(), in
 // gten_decode_sampler_api.h), which also drops the graphs captured so far, once: they hold the rung below.
@@ -138,6 +140,11 @@ struct SamplerState {
     CutParam* cut = nullptr;            // [n_seq] top-p / min-p cuts beside `samp` (include/gten_hip_nucleus.h).  A cut only
     std::vector<CutParam> cut_host;     // acts on a sampling sequence, so it does not enter sampler_on
     bool cut_on = false;
+    PenParam* pen = nullptr;            // [n_seq] penalties beside `samp` (include/gten_hip_penalty.h).  A penalty moves a greedy
+    std::vector<PenParam> pen_host;     // sequence's id too, so it enters sampler_on as a bound table does
+    int n_penalised = 0;                // sequences whose penalty is on
+    size_t pen_lds = 0;                 // k_dec_sample_pen's dynamic LDS: the counts of one row
+    bool pen_on = false;
 };
 
 struct gten_hip_decoder {
@@ -226,8 +233,8 @@ struct gten_hip_decoder {
     hipEvent_t lane_fork = nullptr, lane_join[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
 };
 
-// the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table or asks for log-probs
-static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking > 0; }
+// the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table, asks for log-probs or is penalised
+static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking + dc->smp.n_penalised > 0; }
 
 // where the step of one lane ends: what the sampler launch reads and writes, and the four arguments of k_dec_argmax in which the
 // three step forms differ (the others -- tables, row lengths -- are the decoder's)
@@ -240,6 +247,7 @@ struct StepEnd {
     int32_t* tokens;
     LpRecord* lp;
     const CutParam* cut;
+    const PenParam* pen;
     const float* best_val; const int* best_idx; int n_best, best_stride;      // k_dec_argmax: candidates per sequence
 };
 
@@ -250,7 +258,10 @@ static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
     const int V = dc->d.n_vocab, tok_stride = dc->d.max_ctx + 1, rec_stride = dc->d.max_ctx + 2;
     const dim3 grid(e.rows), block(SMP_THREADS);
     const bool on = sampler_on(dc);
-    if (on && s.cut_on)
+    if (on && s.pen_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_pen, grid, block, s.pen_lds, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens,
+                   tok_stride, (const float*)s.bias, e.lp, rec_stride, e.cut, e.pen);
+    else if (on && s.cut_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_cut, grid, block, 0, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens, tok_stride,
                    (const float*)s.bias, e.lp, rec_stride, e.cut);
     else if (on && s.lp_on)
@@ -270,7 +281,7 @@ static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
 // the rows of every per-sequence buffer that belong to one lane (lane 0 of a single-lane decoder: the buffers themselves)
 struct LaneBufs {
     int n_seq;
-    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp; const CutParam* cut;
+    DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp; const CutParam* cut; const PenParam* pen;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -289,6 +300,7 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     b.step = dc->step + o; b.tokens = dc->tokens + o * (d.max_ctx + 1); b.result = dc->result + o * (d.max_ctx + 2); b.samp = dc->smp.samp + o;
     b.lp = dc->smp.lp ? dc->smp.lp + o * (d.max_ctx + 2) : nullptr;
     b.cut = dc->smp.cut ? dc->smp.cut + o : nullptr;
+    b.pen = dc->smp.pen ? dc->smp.pen + o : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -695,7 +707,7 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
     // (one sequence: no strides; the argmax joins lm_head's per-wave winners)
-    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut,
+    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen,
                                        dc->best_val, dc->best_idx, dc->n_best, 0});
 }
 
@@ -834,7 +846,7 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut,
+    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen,
                                        dc->best_val, dc->best_idx, dc->n_best, dc->n_best});
 }
 
@@ -1307,7 +1319,7 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
     // (the matrix-core lm_head keeps no winners: the argmax reads the logits rows; the bias tables are the decoder's, not a lane's)
-    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.logits_m, nullptr, V, V});
+    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.pen, b.logits_m, nullptr, V, V});
 }
 
 template <int WT>
@@ -1695,7 +1707,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));

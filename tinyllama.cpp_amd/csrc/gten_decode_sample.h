@@ -140,11 +140,33 @@ __device__ __forceinline__ void smp_find_digit(unsigned kk, SmpShared& sm)
 
 // element i of the row the draw is made from: the logit, or (BIAS) y_i = x_i + b_i -- one f32 add, formed anew
 // wherever the row is read (the add is deterministic: every pass sees the same y)
-template <bool BIAS>
-__device__ __forceinline__ float smp_at(const float* __restrict__ x, const float* __restrict__ b, int i)
+//
+// PEN (include/gten_hip_penalty.h): the logit is first penalised by the count c_i of id i in the sequence's window,
+// p_i = x_i for c_i == 0, otherwise (x_i > 0 ? x_i / r : x_i * r) - ((float)c_i * freq + pres), every operation rounded to f32 on its
+// own; then the table, y_i = p_i + b_i.  The counts are dense u16, two per LDS word (pen_count, gten_decode_penalty.h).  An instance
+// without PEN never touches `pen`.
+struct PenRow {
+    const unsigned* cnt;         // LDS: (n_vocab + 1) / 2 words, id i in half (i & 1) of word i >> 1
+    float r, freq, pres;
+};
+__device__ __forceinline__ float pen_apply(float x, unsigned c, const PenRow& pen)
 {
-    if constexpr (BIAS) return x[i] + b[i];
-    else return x[i];
+    if (c == 0u) return x;
+    const float u = x > 0.f ? __fdiv_rn(x, pen.r) : __fmul_rn(x, pen.r);
+    const float t = __fadd_rn(__fmul_rn((float)c, pen.freq), pen.pres);
+    return __fsub_rn(u, t);
+}
+template <bool BIAS, bool PEN = false>
+__device__ __forceinline__ float smp_at(const float* __restrict__ x, const float* __restrict__ b, int i, const PenRow& pen = PenRow{})
+{
+    if constexpr (PEN) {
+        const float p = pen_apply(x[i], (pen.cnt[i >> 1] >> ((i & 1) << 4)) & 0xffffu, pen);
+        if constexpr (BIAS) return __fadd_rn(p, b[i]);
+        else return p;
+    } else {
+        if constexpr (BIAS) return x[i] + b[i];
+        else return x[i];
+    }
 }
 
 // The candidates of one row (top_k >= 1): element i is one when (smp_key(y_i) & mask) > prefix, or == prefix with i <= ilim; mx = max y.
@@ -154,8 +176,9 @@ struct SmpSelect {
     int ilim;
     float mx;
 };
-template <bool BIAS>
-__device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, SmpShared& sm)
+template <bool BIAS, bool PEN = false>
+__device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, SmpShared& sm,
+                                                const PenRow& pen = PenRow{})
 {
     const int t = threadIdx.x;
     unsigned mask = 0u, prefix = 0u, kk = (unsigned)min(top_k, n);
@@ -168,7 +191,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
         if (shift == 24) {
             for (int base = 0; base < n; base += SMP_THREADS) {         // (every lane runs every trip: smp_hist_add is per wave)
                 const int i = base + t;
-                const float v = i < n ? smp_at<BIAS>(x, b, i) : -INFINITY;
+                const float v = i < n ? smp_at<BIAS, PEN>(x, b, i, pen) : -INFINITY;
                 mx = fmaxf(mx, v);
                 if (!all) smp_hist_add(sm, i < n, smp_key(v) >> 24);
             }
@@ -177,7 +200,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
         } else {
             for (int base = 0; base < n; base += SMP_THREADS) {
                 const int i = base + t;
-                const unsigned key = i < n ? smp_key(smp_at<BIAS>(x, b, i)) : 0u;
+                const unsigned key = i < n ? smp_key(smp_at<BIAS, PEN>(x, b, i, pen)) : 0u;
                 smp_hist_add(sm, i < n && (key & mask) == prefix, (key >> shift) & 255u);
             }
             __syncthreads();
@@ -196,7 +219,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
                 for (int i = t; i < 256; i += SMP_THREADS) sm.hist[i] = 0u;
                 __syncthreads();
                 for (int i = t; i < n; i += SMP_THREADS)
-                    if (smp_key(smp_at<BIAS>(x, b, i)) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
+                    if (smp_key(smp_at<BIAS, PEN>(x, b, i, pen)) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
                 __syncthreads();
                 smp_find_digit(kk, sm);
                 const unsigned di = 255u - sm.word[0], ri = sm.word[1];
@@ -214,28 +237,28 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
 // One row: the id of the contract (top_k >= 1) or the greedy argmax (top_k == 0).  Every thread returns it.
 // BIAS: the row is y = x + b (b: a bias table's row; -inf = banned -- its key sorts below every finite value and its score is
 // -inf, so it is never the argmax while one entry is above -inf); the unbiased instance never touches b.
-template <bool BIAS>
+template <bool BIAS, bool PEN = false>
 __device__ __forceinline__ int smp_row(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
-                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm)
+                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm, const PenRow& pen = PenRow{})
 {
     const int t = threadIdx.x;
     if (top_k <= 0) {
         float best = -INFINITY;
         int idx = 0x7fffffff;
         for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = smp_at<BIAS>(x, b, i);
+            const float v = smp_at<BIAS, PEN>(x, b, i, pen);
             if (v > best || (v == best && i < idx)) { best = v; idx = i; }
         }
         return smp_block_argmax(best, idx, sm);
     }
-    const SmpSelect c = smp_select<BIAS>(x, b, n, top_k, sm);
+    const SmpSelect c = smp_select<BIAS, PEN>(x, b, n, top_k, sm, pen);
     const unsigned mask = c.mask, prefix = c.prefix;
     const int ilim = c.ilim;
     const float mx = c.mx;
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i = t; i < n; i += SMP_THREADS) {
-        const float v = smp_at<BIAS>(x, b, i);
+        const float v = smp_at<BIAS, PEN>(x, b, i, pen);
         const unsigned key = smp_key(v) & mask;
         if (key > prefix || (key == prefix && i <= ilim)) {
             const float s = (v - mx) / temp + smp_gumbel((unsigned)i, pos, stream, k0, k1);

@@ -1,7 +1,8 @@
 // gten_decode_sampler_api.h -- the sampler's entry points: top-k sampling (include/gten_hip_sample.h), bias tables
 // (include/gten_hip_bias.h), log-probs of the generated ids (include/gten_hip_logprobs.h, §3.11) and top-p / min-p
-// cuts (include/gten_hip_nucleus.h, §3.12).  Host code only; included by gten_decode.hip inside its extern "C" block, behind the
-// decoder's other entry points.  The kernels are in gten_decode_sample.h, gten_decode_logprobs.h and gten_decode_nucleus.h; what
+// cuts (include/gten_hip_nucleus.h, §3.12) and penalties on repeated ids (include/gten_hip_penalty.h, §3.14).  Host code only; included
+// by gten_decode.hip inside its extern "C" block, behind the decoder's other entry points.  The kernels are in gten_decode_sample.h,
+// gten_decode_logprobs.h, gten_decode_nucleus.h and gten_decode_penalty.h; what
 // the decoder keeps of a request, and which launch a step ends in, is SamplerState's comment in gten_decode.hip.
 
 // ---- what the setters share
@@ -20,6 +21,32 @@ static int cut_check(float top_p, float min_p, const char* who)
 static CutParam cut_param(float top_p, float min_p)
 {
     return CutParam{top_p, min_p > 0.f ? (float)std::log((double)min_p) : -INFINITY, min_p, (top_p == 1.f && min_p == 0.f) ? 0u : 1u};
+}
+static int pen_check(float r, float freq, float pres, const char* who)
+{
+    GTR_REQUIRE(std::isfinite(r) && r >= GTEN_HIP_PENALTY_R_MIN && r <= GTEN_HIP_PENALTY_R_MAX, "%s: repetition penalty %g outside [1/8, 8]", who, (double)r);
+    GTR_REQUIRE(std::isfinite(freq) && std::fabs(freq) <= GTEN_HIP_PENALTY_ADD_MAX, "%s: frequency penalty %g (finite, |.| <= 100)", who, (double)freq);
+    GTR_REQUIRE(std::isfinite(pres) && std::fabs(pres) <= GTEN_HIP_PENALTY_ADD_MAX, "%s: presence penalty %g (finite, |.| <= 100)", who, (double)pres);
+    return 0;
+}
+static PenParam pen_param(float r, float freq, float pres, int start, int last_n)
+{
+    const bool off = r == 1.f && freq == 0.f && pres == 0.f;
+    return PenParam{r, freq, pres, off ? 0 : start, off ? 0 : last_n, off ? 0u : 1u, {0u, 0u}};
+}
+// the counts of one row of n_vocab ids beside `kernel`'s own LDS: refused where they do not fit the CU's 160 KiB; otherwise the kernel's
+// dynamic LDS limit is raised to them (outside any capture) and *lds is their size
+#define PEN_LDS_CU (160 * 1024)
+static int pen_fit(const void* kernel, int n_vocab, const char* who, size_t* lds)
+{
+    hipFuncAttributes fa;
+    GTR_CHECK(hipFuncGetAttributes(&fa, kernel));
+    const size_t need = pen_lds_bytes(n_vocab);
+    GTR_REQUIRE(fa.sharedSizeBytes + need <= (size_t)PEN_LDS_CU, "%s: the counts of %d ids (%zu bytes) do not fit the workgroup's LDS beside the sampler's %zu",
+                who, n_vocab, need, (size_t)fa.sharedSizeBytes);
+    GTR_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
+    *lds = need;
+    return 0;
 }
 
 // sequence `seq`'s request as the host holds it, to the device (the steps queued before it have finished when this returns)
@@ -65,6 +92,15 @@ static int cut_make(gten_hip_decoder* dc)           // every sequence: no cut
     s.cut_host.assign((size_t)dc->n_seq, cut_param(1.f, 0.f));
     if (!s.cut) GTR_CHECK(hipMalloc((void**)&s.cut, (size_t)dc->n_seq * sizeof(CutParam)));
     GTR_CHECK(hipMemcpyAsync(s.cut, s.cut_host.data(), s.cut_host.size() * sizeof(CutParam), hipMemcpyHostToDevice, stream()));
+    return 0;
+}
+static int pen_make(gten_hip_decoder* dc)           // every sequence: no penalty; the kernel's LDS limit raised before any capture
+{
+    SamplerState& s = dc->smp;
+    if (int rc = pen_fit((const void*)k_dec_sample_pen, dc->d.n_vocab, "decoder_set_penalty", &s.pen_lds)) return rc;
+    s.pen_host.assign((size_t)dc->n_seq, pen_param(1.f, 0.f, 0.f, 0, 0));
+    if (!s.pen) GTR_CHECK(hipMalloc((void**)&s.pen, (size_t)dc->n_seq * sizeof(PenParam)));
+    GTR_CHECK(hipMemcpyAsync(s.pen, s.pen_host.data(), s.pen_host.size() * sizeof(PenParam), hipMemcpyHostToDevice, stream()));
     return 0;
 }
 
@@ -227,9 +263,56 @@ int gten_hip_decoder_cut_info(gten_hip_decoder* dc, float* top_p_host, float* mi
     return 0;
 }
 
+int gten_hip_decoder_set_penalty(gten_hip_decoder* dc, int seq, float r, float freq, float pres, int start, int last_n)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_penalty: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    if (int rc = pen_check(r, freq, pres, "decoder_set_penalty")) return rc;
+    GTR_REQUIRE(start >= 0 && last_n >= 0, "decoder_set_penalty: window start %d, last_n %d (both >= 0)", start, last_n);
+    const PenParam p = pen_param(r, freq, pres, start, last_n);
+    GTR_REQUIRE(p.on == 0u || !dc->persist_on, "decoder_set_penalty: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    GTR_REQUIRE(p.on == 0u || dc->d.max_ctx < GTEN_HIP_PENALTY_HISTORY_MAX, "decoder_set_penalty: max_ctx %d >= %d (a count is 16 bits)", dc->d.max_ctx,
+                GTEN_HIP_PENALTY_HISTORY_MAX);
+    if (p.on == 0u && !dc->smp.pen_on) return 0;       // nobody has ever penalised: nothing to clear
+    if (!dc->smp.pen_on)
+        if (int rc = first_use(dc, dc->smp.pen_on, pen_make)) return rc;
+    PenParam& h = dc->smp.pen_host[(size_t)seq];
+    dc->smp.n_penalised += (p.on ? 1 : 0) - (h.on ? 1 : 0);
+    h = p;
+    GTR_CHECK(hipMemcpyAsync(dc->smp.pen + seq, &h, sizeof(PenParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_penalty_info(gten_hip_decoder* dc, float* r_host, float* freq_host, float* pres_host, int32_t* start_host, int32_t* last_n_host,
+                                  int* on)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_penalty_info: null decoder");
+    for (int q = 0; q < dc->n_seq; q++) {
+        const PenParam p = dc->smp.pen_on ? dc->smp.pen_host[(size_t)q] : pen_param(1.f, 0.f, 0.f, 0, 0);
+        if (r_host) r_host[q] = p.r;
+        if (freq_host) freq_host[q] = p.freq;
+        if (pres_host) pres_host[q] = p.pres;
+        if (start_host) start_host[q] = p.start;
+        if (last_n_host) last_n_host[q] = p.last_n;
+    }
+    if (on) *on = dc->smp.pen_on ? 1 : 0;
+    return 0;
+}
+
 // ---- the row operators: the sampler on rows of logits that are not a decoder's
 struct GrowBuf { void* dev = nullptr; size_t bytes = 0; };      // a device buffer that only grows
 static GrowBuf g_rows_dev, g_cut_dev;                           // the per-row requests and cuts of one operator call
+static GrowBuf g_pen_dev, g_hist_dev, g_off_dev;                // ... and their penalties, windows and window offsets
+
+// what the penalty operators add to a call: every row's window and penalty; y_out: write the rows out instead of drawing from them
+struct PenRows {
+    const int32_t *hist, *off;
+    const float *r, *freq, *pres;
+    float* y_out;
+    long long y_stride;
+};
 
 // `bytes` of the host's to the device buffer (grown when needed), queued on the stream
 static int grow_upload(GrowBuf& b, const void* host, size_t bytes)
@@ -245,12 +328,36 @@ static int grow_upload(GrowBuf& b, const void* host, size_t bytes)
     return 0;
 }
 
-// the three operators differ in what they take: ROWS_PLAIN no bias and no cuts, ROWS_BIASED a bias it requires, ROWS_CUT cuts and a
-// bias it accepts (null: none).  `who` names the operator in every message.
-enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT };
+// every row's window and penalty of a penalty operator, checked and uploaded (g_pen_dev, g_hist_dev, g_off_dev)
+static int pen_rows_upload(const char* who, const PenRows& pen, int n_rows)
+{
+    GTR_REQUIRE(pen.off && pen.r && pen.freq && pen.pres, "%s: null argument", who);
+    GTR_REQUIRE(pen.off[0] == 0, "%s: the first window offset is %d, not 0", who, pen.off[0]);
+    std::vector<PenParam> pens((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        if (int rc = pen_check(pen.r[r], pen.freq[r], pen.pres[r], who)) return rc;
+        const long long len = (long long)pen.off[r + 1] - (long long)pen.off[r];
+        GTR_REQUIRE(len >= 0 && len <= GTEN_HIP_PENALTY_HISTORY_MAX, "%s: window of row %d has %lld ids (0 .. %d)", who, r, len, GTEN_HIP_PENALTY_HISTORY_MAX);
+        pens[(size_t)r] = pen_param(pen.r[r], pen.freq[r], pen.pres[r], 0, 0);
+    }
+    const size_t n_hist = (size_t)pen.off[n_rows];
+    GTR_REQUIRE(n_hist == 0 || pen.hist, "%s: %zu window ids, null list", who, n_hist);
+    if (int rc = grow_upload(g_pen_dev, pens.data(), pens.size() * sizeof(PenParam))) return rc;
+    if (int rc = grow_upload(g_off_dev, pen.off, ((size_t)n_rows + 1) * sizeof(int32_t))) return rc;
+    const int32_t none = 0;                                                     // (no ids at all: one word nobody reads)
+    if (int rc = grow_upload(g_hist_dev, n_hist ? pen.hist : &none, std::max(n_hist, (size_t)1) * sizeof(int32_t))) return rc;
+    GTR_CHECK(hipStreamSynchronize(stream()));    // `pens` and `none` live on this stack frame
+    return 0;
+}
+
+// the operators differ in what they take: ROWS_PLAIN no bias and no cuts, ROWS_BIASED a bias it requires, ROWS_CUT cuts and a bias it
+// accepts (null: none), ROWS_PEN those and every row's window and penalty (`pen`; with pen->y_out the rows are written out and nothing
+// is drawn: no request is looked at).  `who` names the operator in every message.
+enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT, ROWS_PEN };
 static int sample_rows_common(const char* who, RowsLevel level, const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias,
                               long long bias_stride, const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
-                              const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out, gten_hip_cut_info* info_out)
+                              const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out, gten_hip_cut_info* info_out,
+                              const PenRows* pen = nullptr)
 {
     GTR_NEED_INIT();
     const bool shape_ok = n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0;
@@ -259,24 +366,46 @@ static int sample_rows_common(const char* who, RowsLevel level, const float* log
     else
         GTR_REQUIRE(shape_ok && bias_stride >= 0, "%s: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", who, n_rows, n_vocab, row_stride,
                     bias_stride);
+    const dim3 grid(n_rows), block(SMP_THREADS);
+    if (level == ROWS_PEN && pen->y_out) {
+        GTR_REQUIRE(pen->y_stride >= n_vocab || n_rows <= 1, "%s: output stride %lld < n_vocab %d", who, pen->y_stride, n_vocab);
+        if (n_rows == 0) return 0;
+        GTR_REQUIRE(logits, "%s: null argument", who);
+        if (int rc = pen_rows_upload(who, *pen, n_rows)) return rc;
+        size_t lds = 0;
+        if (int rc = pen_fit((const void*)k_penalize_rows, n_vocab, who, &lds)) return rc;
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_penalize_rows, grid, block, lds, logits, n_vocab, row_stride, bias, bias_stride, (const PenParam*)g_pen_dev.dev,
+                   (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, pen->y_out, pen->y_stride);
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        return 0;
+    }
     if (n_rows == 0) return 0;
+    const bool cutting = level == ROWS_CUT || level == ROWS_PEN;
     GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host && (level != ROWS_BIASED || bias) &&
-                (level != ROWS_CUT || (top_p_host && min_p_host)), "%s: null argument", who);
+                (!cutting || (top_p_host && min_p_host)), "%s: null argument", who);
     std::vector<SampleRowParam> rows((size_t)n_rows);
-    std::vector<CutParam> cuts(level == ROWS_CUT ? (size_t)n_rows : 0);
+    std::vector<CutParam> cuts(cutting ? (size_t)n_rows : 0);
     for (int r = 0; r < n_rows; r++) {
         if (int rc = sample_check(top_k_host[r], temp_host[r], who)) return rc;
-        if (level == ROWS_CUT)
+        if (cutting)
             if (int rc = cut_check(top_p_host[r], min_p_host[r], who)) return rc;
         GTR_REQUIRE(position_host[r] >= 0, "%s: position %d of row %d", who, position_host[r], r);
         rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
-        if (level == ROWS_CUT) cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
+        if (cutting) cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
     }
+    if (level == ROWS_PEN)
+        if (int rc = pen_rows_upload(who, *pen, n_rows)) return rc;
     if (int rc = grow_upload(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam))) return rc;
     const SampleRowParam* par = (const SampleRowParam*)g_rows_dev.dev;
     const unsigned seed_lo = (unsigned)(seed & 0xffffffffu), seed_hi = (unsigned)(seed >> 32);
-    const dim3 grid(n_rows), block(SMP_THREADS);
-    if (level == ROWS_CUT) {
+    if (level == ROWS_PEN) {
+        size_t lds = 0;
+        if (int rc = pen_fit((const void*)k_sample_rows_pen, n_vocab, who, &lds)) return rc;
+        if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_pen, grid, block, lds, logits, n_vocab, row_stride, bias, bias_stride, par, (const CutParam*)g_cut_dev.dev,
+                   (const PenParam*)g_pen_dev.dev, (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, seed_lo, seed_hi, out,
+                   (CutInfo*)info_out);
+    } else if (level == ROWS_CUT) {
         if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
         GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_cut, grid, block, 0, logits, n_vocab, row_stride, bias, bias_stride, par, (const CutParam*)g_cut_dev.dev,
                    seed_lo, seed_hi, out, (CutInfo*)info_out);
@@ -311,6 +440,27 @@ int gten_hip_sample_rows_cut(const float* logits, int n_rows, int n_vocab, long 
 {
     return sample_rows_common("sample_rows_cut", ROWS_CUT, logits, n_rows, n_vocab, row_stride, bias, bias_stride, top_k_host, temp_host, seed, stream_host,
                               position_host, top_p_host, min_p_host, out, info_out);
+}
+
+int gten_hip_penalize_rows(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                           const int32_t* hist_host, const int32_t* hist_offset_host, const float* r_host, const float* freq_host,
+                           const float* pres_host, float* y_out, long long y_stride)
+{
+    GTR_REQUIRE(y_out && y_stride >= 0, "penalize_rows: null output or stride %lld", y_stride);
+    const PenRows pen{hist_host, hist_offset_host, r_host, freq_host, pres_host, y_out, y_stride};
+    return sample_rows_common("penalize_rows", ROWS_PEN, logits, n_rows, n_vocab, row_stride, bias, bias_stride, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, &pen);
+}
+
+int gten_hip_sample_rows_pen(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                             const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                             const int32_t* position_host, const float* top_p_host, const float* min_p_host, const int32_t* hist_host,
+                             const int32_t* hist_offset_host, const float* r_host, const float* freq_host, const float* pres_host,
+                             int32_t* out, gten_hip_cut_info* info_out)
+{
+    const PenRows pen{hist_host, hist_offset_host, r_host, freq_host, pres_host, nullptr, 0};
+    return sample_rows_common("sample_rows_pen", ROWS_PEN, logits, n_rows, n_vocab, row_stride, bias, bias_stride, top_k_host, temp_host, seed, stream_host,
+                              position_host, top_p_host, min_p_host, out, info_out, &pen);
 }
 
 int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long long row_stride, const int32_t* ids, int n_top, float* logprob_out,

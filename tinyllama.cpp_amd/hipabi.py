@@ -106,6 +106,9 @@ class GtenHip:
     # include/gten_hip_nucleus.h (top-p / min-p cuts of the draw)
     NUCLEUS_SYMBOLS = ["gten_hip_decoder_set_cut", "gten_hip_decoder_cut_info", "gten_hip_sample_rows_cut"]
     CUT_INFO = np.dtype([("Z", np.uint64), ("n_cand", np.int32), ("n_nucleus", np.int32), ("n_minp", np.int32), ("n_keep", np.int32)])   # gten_hip_cut_info
+    # include/gten_hip_penalty.h (repetition / frequency / presence penalties on the ids a sequence already holds)
+    PENALTY_SYMBOLS = ["gten_hip_decoder_set_penalty", "gten_hip_decoder_penalty_info", "gten_hip_penalize_rows", "gten_hip_sample_rows_pen"]
+    PENALTY_HISTORY_MAX = 65535                                  # GTEN_HIP_PENALTY_HISTORY_MAX
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
@@ -173,6 +176,11 @@ class GtenHip:
         self._set_cut = _sig(L, "gten_hip_decoder_set_cut", ci, [vp, ci, C.c_float, C.c_float])
         self._cut_info = _sig(L, "gten_hip_decoder_cut_info", ci, [vp, vp, vp, vp, C.POINTER(ci)])
         self._sample_rows_cut = _sig(L, "gten_hip_sample_rows_cut", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp])
+        self._set_penalty = _sig(L, "gten_hip_decoder_set_penalty", ci, [vp, ci, C.c_float, C.c_float, C.c_float, ci, ci])
+        self._penalty_info = _sig(L, "gten_hip_decoder_penalty_info", ci, [vp, vp, vp, vp, vp, vp, C.POINTER(ci)])
+        self._penalize_rows = _sig(L, "gten_hip_penalize_rows", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_longlong])
+        self._sample_rows_pen = _sig(L, "gten_hip_sample_rows_pen", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp, vp,
+                                                                         vp, vp, vp, vp, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
@@ -280,6 +288,76 @@ class GtenHip:
         out = DeviceBuffer(self, 4 * m)
         v = lambda z: z.ctypes.data_as(C.c_void_p)
         return self._sample_rows_cut(logits.ptr, n_rows, n_vocab, row_stride, None, 0, v(k), v(t), C.c_uint64(0), v(s), v(p), v(a), v(b), out.ptr, None)
+
+    @staticmethod
+    def _windows(hist, n_rows):
+        """(ids int32[total], offsets int32[n_rows + 1]) of per-row windows: a list of n_rows id lists, or one list for every row"""
+        if n_rows and (len(hist) == 0 or np.isscalar(hist[0])):
+            hist = [hist] * n_rows
+        assert len(hist) == n_rows
+        off = np.zeros(n_rows + 1, np.int32)
+        off[1:] = np.cumsum([len(h) for h in hist])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(h, np.int32).reshape(-1) for h in hist]) if n_rows else [], dtype=np.int32)
+        return ids, off
+
+    def penalize_rows(self, logits, n_rows, n_vocab, row_stride, hist, r, freq, pres, bias=None, bias_stride=0):
+        """gten_hip_penalize_rows (include/gten_hip_penalty.h): the rows the draw would be made from, f32[n_rows][n_vocab].  `hist`: row
+        r's window of ids, a list per row (or one list for all); r / freq / pres per row (scalars are broadcast)."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (rr, rp), (ff, fp), (pp_, ppp) = per_row(r, np.float32), per_row(freq, np.float32), per_row(pres, np.float32)
+        ids, off = self._windows(hist, n_rows)
+        out = DeviceBuffer(self, max(4 * n_rows * n_vocab, 4))
+        self._check(self._penalize_rows(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr if bias is not None else None, bias_stride,
+                                        ids.ctypes.data_as(C.c_void_p) if len(ids) else None, off.ctypes.data_as(C.c_void_p), rp, fp, ppp, out.ptr, n_vocab))
+        return out.download(np.float32)[: n_rows * n_vocab].reshape(n_rows, n_vocab).copy()
+
+    def sample_rows_pen(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed, stream, position, hist, r, freq, pres, top_p=1.0, min_p=0.0,
+                        bias=None, bias_stride=0, info=False):
+        """gten_hip_sample_rows_pen (include/gten_hip_penalty.h): sample_rows_cut with row r penalised by (r, freq, pres) over its window
+        hist[r].  Returns (ids int32[n_rows], info or None) like sample_rows_cut."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        (a, tpp), (b, mpp) = per_row(top_p, np.float32), per_row(min_p, np.float32)
+        (rr, rp), (ff, fp), (pr_, prp) = per_row(r, np.float32), per_row(freq, np.float32), per_row(pres, np.float32)
+        ids, off = self._windows(hist, n_rows)
+        out = DeviceBuffer(self, max(4 * n_rows, 4))
+        inf = DeviceBuffer(self, max(self.CUT_INFO.itemsize * n_rows, 8)) if info else None
+        self._check(self._sample_rows_pen(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr if bias is not None else None, bias_stride, kp, tp,
+                                          C.c_uint64(int(seed)), sp, pp, tpp, mpp, ids.ctypes.data_as(C.c_void_p) if len(ids) else None,
+                                          off.ctypes.data_as(C.c_void_p), rp, fp, prp, out.ptr, inf.ptr if info else None))
+        got = out.download(np.int32)[:n_rows].copy()
+        return got, (inf.download(np.uint8)[: self.CUT_INFO.itemsize * n_rows].view(self.CUT_INFO).copy() if info else None)
+
+    def sample_rows_pen_rc(self, logits, n_rows, n_vocab, row_stride, hist=(), r=1.1, freq=0.0, pres=0.0, top_k=40, temp=1.0):
+        """the return code of one gten_hip_sample_rows_pen call (argument checks); out is a scratch word"""
+        m = max(n_rows, 1)
+        f = lambda v, dt: np.full(m, v, dt)                                                          # noqa: E731
+        k, t, s, p, a, b = f(top_k, np.int32), f(temp, np.float32), f(0, np.uint32), f(1, np.int32), f(1.0, np.float32), f(0.0, np.float32)
+        rr, ff, pp = f(r, np.float32), f(freq, np.float32), f(pres, np.float32)
+        ids, off = self._windows(list(hist), m)
+        out = DeviceBuffer(self, 4 * m)
+        v = lambda z: z.ctypes.data_as(C.c_void_p)                                                  # noqa: E731
+        return self._sample_rows_pen(logits.ptr, n_rows, n_vocab, row_stride, None, 0, v(k), v(t), C.c_uint64(0), v(s), v(p), v(a), v(b),
+                                     v(ids) if len(ids) else None, v(off), v(rr), v(ff), v(pp), out.ptr, None)
+
+    def decoder_set_penalty(self, dec, seq, r, freq, pres, start=0, last_n=0):
+        """gten_hip_decoder_set_penalty on a raw decoder handle: sequence `seq` is penalised by (r, freq, pres) over the window
+        (start, last_n) of its own ids; (1, 0, 0) clears it"""
+        self._check(self._set_penalty(dec, int(seq), C.c_float(r), C.c_float(freq), C.c_float(pres), int(start), int(last_n)))
+
+    def decoder_penalty_info(self, dec, n_seq):
+        """gten_hip_decoder_penalty_info: (r f32[n_seq], freq, pres, start int32[n_seq], last_n, on)"""
+        r, f, p = np.zeros(n_seq, np.float32), np.zeros(n_seq, np.float32), np.zeros(n_seq, np.float32)
+        s, l = np.zeros(n_seq, np.int32), np.zeros(n_seq, np.int32)
+        on = C.c_int(0)
+        v = lambda z: z.ctypes.data_as(C.c_void_p)                                                  # noqa: E731
+        self._check(self._penalty_info(dec, v(r), v(f), v(p), v(s), v(l), C.byref(on)))
+        return r, f, p, s, l, bool(on.value)
 
     def decoder_set_cut(self, dec, seq, top_p, min_p):
         """gten_hip_decoder_set_cut on a raw decoder handle: sequence `seq` draws under (top_p, min_p); (1, 0) clears it"""

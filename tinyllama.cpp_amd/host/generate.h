@@ -1,13 +1,14 @@
 // generate.h -- choosing the next id, once for every entry point above the C ABI of libgten_hip.so: greedy, top-k sampling
 // (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h) and log-prob records
-// (include/gten_hip_logprobs.h) and top-p / min-p cuts (include/gten_hip_nucleus.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
+// (include/gten_hip_logprobs.h), top-p / min-p cuts (include/gten_hip_nucleus.h) and penalties on
+// repeated ids (include/gten_hip_penalty.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
 // compile-time mask says which device entry points the flow may name.
 //
 // Why a mask and not a run-time switch: host/capi.cpp links against a stand-in of include/gten_hip.h alone
 // (tests/test_host_sanitize_cpu.py), host/capi.cpp + host/capi_sample.cpp against that plus the sampler's
 // (tests/test_sampler_cpu.py).  So every flow here is a template on the mask, the stages it does not have are discarded with
 // `if constexpr`, and each flow is instantiated where its stages may be named: mask 0 in host/capi.cpp, kSampled in
-// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, all four in host/capi_nucleus.cpp
+// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, four in host/capi_nucleus.cpp, all five in host/capi_penalty.cpp
 // (and in the command line program, which links against the library itself).  That is the only reason those files are separate.
 #pragma once
 
@@ -18,10 +19,13 @@
 #include "../../include/gten_hip_bias.h"
 #include "../../include/gten_hip_logprobs.h"
 #include "../../include/gten_hip_nucleus.h"
+#include "../../include/gten_hip_penalty.h"
 
 namespace gten {
 
-enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u };
+// (kPenalty -- include/gten_hip_penalty.h, DESIGN.md §3.14, instantiated in host/capi_penalty.cpp -- requires kSampled: a penalised
+// greedy request takes its first id from the device too)
+enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u };
 
 // What one prompt or sequence asks for.  The defaults: greedy, no table, no records.
 struct Request {
@@ -33,7 +37,12 @@ struct Request {
     int min_new = 0;             // ... which holds for the first min_new new ids (0: for all of them)
     int n_top = -1;              // alternatives per log-prob record (0: the id's own log-prob only; -1: no records)
     float top_p = 1.f, min_p = 0.f;      // the cut of the draw ((1, 0): none; ignored by a greedy request)
+    float rep = 1.f, freq = 0.f, pres = 0.f;     // the penalties on ids the sequence already holds ((1, 0, 0): none; they act on greedy too)
+    int last_n = 0;                      // ... counted over the last last_n positions (0: all of them) ...
+    bool count_prompt = true;            // ... the prompt's included, or only what was generated
     bool cuts() const { return top_k > 0 && !(top_p == 1.f && min_p == 0.f); }
+    bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
+    int start(int n_prompt) const { return count_prompt ? 0 : n_prompt; }
     // the first position the table no longer holds at, for a prompt of n_prompt ids (0: it holds throughout)
     int until(int n_prompt) const { return (table >= 0 && min_new > 0) ? n_prompt + min_new : 0; }
 };
@@ -42,6 +51,11 @@ inline bool request_ok(int top_k, float temp) { return top_k >= 0 && (top_k == 0
 inline bool binding_ok(int table, int min_new) { return table >= -1 && table < GTEN_HIP_BIAS_TABLES && min_new >= 0; }
 inline bool asking_ok(int n_top, int n_top_max) { return n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP && n_top <= n_top_max; }
 inline bool cut_ok(float top_p, float min_p) { return std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f && std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f; }
+inline bool penalty_ok(float rep, float freq, float pres, int last_n)
+{
+    return std::isfinite(rep) && rep >= GTEN_HIP_PENALTY_R_MIN && rep <= GTEN_HIP_PENALTY_R_MAX && std::isfinite(freq) &&
+           std::fabs(freq) <= GTEN_HIP_PENALTY_ADD_MAX && std::isfinite(pres) && std::fabs(pres) <= GTEN_HIP_PENALTY_ADD_MAX && last_n >= 0;
+}
 
 // the requests of a fixed batch's sequences or of a queue's prompts, as the C ABI passes them
 struct Requests {
@@ -51,20 +65,36 @@ struct Requests {
     const uint32_t* stream = nullptr;        // (null: item j draws with stream j)
     Each<int32_t> table{nullptr, -1}, min_new{nullptr, 0}, n_top{nullptr, -1};
     Each<float> top_p{nullptr, 1.f}, min_p{nullptr, 0.f};
+    Each<float> rep{nullptr, 1.f}, freq{nullptr, 0.f}, pres{nullptr, 0.f};
+    Each<int32_t> last_n{nullptr, 0}, count_prompt{nullptr, 1};
+    // these requests with a penalty per item (each list may be null: the value for all)
+    Requests penalised(const float* rep_, float rep_all, const float* freq_, float freq_all, const float* pres_, float pres_all, const int32_t* last_n_,
+                       int last_n_all, const int32_t* count_prompt_, int count_prompt_all) const
+    {
+        Requests r = *this;
+        r.rep = {rep_, rep_all}; r.freq = {freq_, freq_all}; r.pres = {pres_, pres_all};
+        r.last_n = {last_n_, last_n_all}; r.count_prompt = {count_prompt_, count_prompt_all};
+        return r;
+    }
     static Requests of(const int32_t* top_k, int top_k_all, const float* temp, float temp_all, uint64_t seed, const uint32_t* stream = nullptr,
                        const int32_t* table = nullptr, const int32_t* min_new = nullptr, const int32_t* n_top = nullptr,
                        const float* top_p = nullptr, float top_p_all = 1.f, const float* min_p = nullptr, float min_p_all = 0.f)
     {
-        return {{top_k, top_k_all}, {temp, temp_all}, seed, stream, {table, -1}, {min_new, 0}, {n_top, -1}, {top_p, top_p_all}, {min_p, min_p_all}};
+        Requests r;
+        r.top_k = {top_k, top_k_all}; r.temp = {temp, temp_all}; r.seed = seed; r.stream = stream;
+        r.table = {table, -1}; r.min_new = {min_new, 0}; r.n_top = {n_top, -1}; r.top_p = {top_p, top_p_all}; r.min_p = {min_p, min_p_all};
+        return r;
     }
     Request operator[](int j) const
     {
-        return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j]};
+        return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j],
+                rep[j], freq[j], pres[j], last_n[j], count_prompt[j] != 0};
     }
     bool ok(int n, int n_top_max) const
     {
         for (int j = 0; j < n; j++)
-            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j])) return false;
+            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j]) ||
+                !penalty_ok(rep[j], freq[j], pres[j], last_n[j])) return false;
         return true;
     }
 };
@@ -142,8 +172,11 @@ struct RecordRows {
 
 // The id that will sit at position `pos`, drawn on the device from the logits row lg into id_dev: plain or under the request's
 // table, plus its record into rec_dev when the request asks.  (The only draw from a prompt's row outside the decoder.)
+// A penalising request (kPenalty) draws from the row penalised by the prompt's window of ids[0, pos) -- the window the decoder's
+// first step would read from its own copy of them.
 template <unsigned M>
-void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, FirstRecord* rec_dev)
+void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, FirstRecord* rec_dev,
+                const int32_t* ids = nullptr)
 {
     static_assert(M & kSampled, "greedy takes the argmax of the prompt's logits on the host");
     const int32_t k = r.top_k;
@@ -151,8 +184,17 @@ void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_
     bool drawn = false;
     if constexpr ((M & kBiased) != 0)
         if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
+    if constexpr ((M & kPenalty) != 0)
+        if (r.penalises()) {
+            const int32_t lo = std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos);
+            const int32_t off[2] = {0, pos - lo};
+            const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
+            GTEN_HIP_OK(gten_hip_sample_rows_pen(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p, ids + lo, off, &r.rep, &r.freq,
+                                                 &r.pres, id_dev, nullptr));
+            drawn = true;
+        }
     if constexpr ((M & kNucleus) != 0)
-        if (r.cuts()) {
+        if (r.cuts() && !drawn) {
             GTEN_HIP_OK(gten_hip_sample_rows_cut(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &r.top_p, &r.min_p, id_dev, nullptr));
             drawn = true;
         }
@@ -178,7 +220,7 @@ struct SlotRequests {
     int bind(int q, const Request& r, int n_prompt)
     {
         (void)q; (void)r; (void)n_prompt;
-        if constexpr ((M & (kBiased | kLogprobs | kNucleus)) != 0) bound = true;
+        if constexpr ((M & (kBiased | kLogprobs | kNucleus | kPenalty)) != 0) bound = true;
         if constexpr ((M & kBiased) != 0)
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
         if constexpr ((M & kLogprobs) != 0)
@@ -186,6 +228,11 @@ struct SlotRequests {
         if constexpr ((M & kNucleus) != 0)
             // (a greedy request's cut could never act: it is not passed on, so it does not switch a decoder to the cut launch)
             if (const int rc = gten_hip_decoder_set_cut(dec, q, r.cuts() ? r.top_p : 1.f, r.cuts() ? r.min_p : 0.f)) return rc;
+        if constexpr ((M & kPenalty) != 0) {
+            const bool on = r.penalises();
+            if (const int rc = gten_hip_decoder_set_penalty(dec, q, on ? r.rep : 1.f, on ? r.freq : 0.f, on ? r.pres : 0.f, on ? r.start(n_prompt) : 0,
+                                                            on ? r.last_n : 0)) return rc;
+        }
         return 0;
     }
     // the sampling request of the decode steps that follow
@@ -214,6 +261,9 @@ struct SlotRequests {
         if constexpr ((M & kNucleus) != 0)
             for (int q = 0; bound && q < n_slots; q++)
                 if (const int r = gten_hip_decoder_set_cut(dec, q, 1.f, 0.f)) rc = r;
+        if constexpr ((M & kPenalty) != 0)
+            for (int q = 0; bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_penalty(dec, q, 1.f, 0.f, 0.f, 0, 0)) rc = r;
         bound = sampling = false;
         return rc;
     }
@@ -251,7 +301,7 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
             Tensor id({1}, kInt32);
             FirstRecords rec;
             if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
-            draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev);
+            draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev, tokens.data());
             GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
             if constexpr ((M & kLogprobs) != 0)
                 if (first != eos && r.n_top >= 0) rows.store_first((size_t)n_prompt, r.n_top, rec.dev);
@@ -292,7 +342,9 @@ int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, con
     } else {
         gten_hip_decoder* dec = nullptr;
         if constexpr ((M & (kBiased | kNucleus)) != 0) dec = b.decoder_handle();
-        return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) { draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev); });
+        return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) {
+            draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev, prompt.data());
+        });
     }
 }
 
@@ -396,7 +448,7 @@ struct ServePolicy {
             if constexpr (kLogprobs) rec.ensure((int)sets.size());
             std::vector<float*> lo((size_t)sets.size(), nullptr);
             b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
-                draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k));
+                draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data());
             });
             if constexpr (kLogprobs)
                 for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
@@ -449,6 +501,12 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
             if ((cutting = reqs[j].cuts())) {
                 if (const int rc = gten_hip_decoder_set_cut(dec, 0, reqs[j].top_p, reqs[j].min_p)) return rc;
                 if (const int rc = gten_hip_decoder_set_cut(dec, 0, 1.f, 0.f)) return rc;
+            }
+    if constexpr ((M & kPenalty) != 0)
+        for (int j = 0, pen = 0; j < n_prompts && !pen; j++)
+            if ((pen = reqs[j].penalises())) {
+                if (const int rc = gten_hip_decoder_set_penalty(dec, 0, reqs[j].rep, reqs[j].freq, reqs[j].pres, 0, reqs[j].last_n)) return rc;
+                if (const int rc = gten_hip_decoder_set_penalty(dec, 0, 1.f, 0.f, 0.f, 0, 0)) return rc;
             }
     std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
     for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);

@@ -6,7 +6,8 @@
 // with the sampler on the device (host/generate.h); --score PATH prints the log-likelihood of a text file
 // (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
 // of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
-// most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h).
+// most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h);
+// --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -53,6 +54,11 @@ Optional args.
            [default=1: off]. With --topk 32003: over the whole vocabulary. Not with -greedy or --score.
 --min-p F : draw only from ids at least F times as likely as the most likely one. F must be gte 0 and lte 1. [default=0: off].
            Not with -greedy or --score.
+--repeat-penalty R : ids the answer or the prompt already holds are made less likely: a positive logit is divided by R, a negative
+           one multiplied. R must be gte 0.125 and lte 8. [default=1: off]. Works with -greedy too. Not with --score.
+--frequency-penalty F : subtract F from the logit of such an id once per occurrence. |F| must be lte 100. [default=0: off].
+--presence-penalty P : subtract P from the logit of such an id once. |P| must be lte 100. [default=0: off].
+--repeat-last-n N : the penalties look at the last N ids only; N must be gte 0. [default=0: at all of them]
 )";
 
 struct Options {
@@ -68,6 +74,10 @@ struct Options {
     float top_p = 1.f, min_p = 0.f;          // --top-p / --min-p ((1, 0): off)
     bool cut_given = false;
     bool cuts() const { return !(top_p == 1.f && min_p == 0.f); }
+    float rep = 1.f, freq = 0.f, pres = 0.f; // --repeat-penalty / --frequency-penalty / --presence-penalty ((1, 0, 0): off)
+    int last_n = 0;                          // --repeat-last-n (0: every id so far)
+    bool pen_given = false;
+    bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     bool constrained() const { return !ban.empty() || !allow.empty(); }
 };
 
@@ -127,11 +137,21 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
     std::vector<float> logprob, top_lp;
     std::vector<int32_t> top_id;
     int rc = 0;
-    if (o.greedy && !o.constrained() && o.logprobs < 0) {
+    if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises()) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
     } else {
-        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p};
-        if (o.cuts()) {
+        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p,
+                        o.rep, o.freq, o.pres, o.last_n, true};
+        if (o.penalises()) {
+            RecordRows rows;
+            if (o.logprobs >= 0) {
+                logprob.resize(width);
+                top_id.resize(width * W);
+                top_lp.resize(width * W);
+                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
+            }
+            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty>(model, tokens, o.n_predict, tok.eos, r, rows);
+        } else if (o.cuts()) {
             RecordRows rows;
             if (o.logprobs >= 0) {
                 logprob.resize(width);
@@ -278,6 +298,30 @@ int main(int argc, char const* argv[])
                 o.min_p = v;
             }
             o.cut_given = true;
+        } else if (arg == "--repeat-penalty" || arg == "--frequency-penalty" || arg == "--presence-penalty") {
+            const char* name = arg == "--repeat-penalty" ? "repeat-penalty" : arg == "--frequency-penalty" ? "frequency-penalty" : "presence-penalty";
+            const std::string text = value(name);
+            size_t used = 0;
+            float v = 0.f;
+            try { v = std::stof(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size() || !std::isfinite(v)) { std::cerr << "Invalid " << name << " value.\n"; return -1; }
+            if (arg == "--repeat-penalty") {
+                if (!(v >= GTEN_HIP_PENALTY_R_MIN && v <= GTEN_HIP_PENALTY_R_MAX)) { std::cerr << "repeat-penalty must be gte 0.125 and lte 8.\n"; return -1; }
+                o.rep = v;
+            } else {
+                if (!(std::fabs(v) <= GTEN_HIP_PENALTY_ADD_MAX)) { std::cerr << name << " must be gte -100 and lte 100.\n"; return -1; }
+                (arg == "--frequency-penalty" ? o.freq : o.pres) = v;
+            }
+            o.pen_given = true;
+        } else if (arg == "--repeat-last-n") {
+            const std::string text = value("repeat-last-n");
+            size_t used = 0;
+            int v = -1;
+            try { v = std::stoi(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size()) { std::cerr << "Invalid repeat-last-n value.\n"; return -1; }
+            if (v < 0) { std::cerr << "repeat-last-n must be gte 0.\n"; return -1; }
+            o.last_n = v;
+            o.pen_given = true;
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
@@ -285,6 +329,7 @@ int main(int argc, char const* argv[])
     }
     if (o.cut_given && o.greedy) { std::cerr << "top-p and min-p need top-k sampling: not with -greedy.\n"; return -1; }
     if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
+    if (o.pen_given && !o.score_path.empty()) { std::cerr << "the repeat, frequency and presence penalties do not apply to --score.\n"; return -1; }
     if (o.min_new > 0 && !o.constrained()) { std::cerr << "min-new needs --ban or --allow.\n"; return -1; }
     if (!o.allow.empty() && std::all_of(o.allow.begin(), o.allow.end(), [&](int32_t id) { return std::find(o.ban.begin(), o.ban.end(), id) != o.ban.end(); })) {
         std::cerr << "--ban bans every id of --allow.\n";

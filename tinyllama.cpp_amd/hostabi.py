@@ -22,6 +22,12 @@ class HostConfig(C.Structure):
         return out + [(1, E, F16), (V, E, W)]
 
 
+class HostPenalties(C.Structure):
+    """gten_host_penalties (include/gten_host_penalty.h)"""
+    _fields_ = ([(k, C.c_void_p) for k in ("rep", "freq", "pres", "last_n", "count_prompt")] +
+                [(k, C.c_float) for k in ("rep_all", "freq_all", "pres_all")] + [(k, C.c_int32) for k in ("last_n_all", "count_prompt_all")])
+
+
 def _sig(lib, name, res, args):
     f = getattr(lib, name)
     f.restype = res
@@ -55,6 +61,9 @@ class GtenHost:
     # include/gten_host_nucleus.h (top-p / min-p cuts of the draw, host/capi_nucleus.cpp)
     NUCLEUS_SYMBOLS = ["gten_host_model_set_cut", "gten_host_batch_set_cut", "gten_host_model_cut_info", "gten_host_batch_cut_info",
                        "gten_host_model_generate_nucleus", "gten_host_batch_generate_nucleus", "gten_host_batch_serve_nucleus"]
+    # include/gten_host_penalty.h (repetition / frequency / presence penalties, host/capi_penalty.cpp)
+    PENALTY_SYMBOLS = ["gten_host_model_set_penalty", "gten_host_batch_set_penalty", "gten_host_model_penalty_info", "gten_host_batch_penalty_info",
+                       "gten_host_model_generate_penalized", "gten_host_batch_generate_penalized", "gten_host_batch_serve_penalized"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -114,6 +123,17 @@ class GtenHost:
                                                                           vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float])
         self._bserve_nuc = _sig(L, "gten_host_batch_serve_nucleus", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                          C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float])
+        pen = C.POINTER(HostPenalties)
+        self._m_set_pen = _sig(L, "gten_host_model_set_penalty", ci, [vp, C.c_float, C.c_float, C.c_float, ci, ci])
+        self._b_set_pen = _sig(L, "gten_host_batch_set_penalty", ci, [vp, ci, C.c_float, C.c_float, C.c_float, ci, ci])
+        self._m_pen_info = _sig(L, "gten_host_model_penalty_info", ci, [vp, vp, vp, vp, vp, vp])
+        self._b_pen_info = _sig(L, "gten_host_batch_penalty_info", ci, [vp, vp, vp, vp, vp, vp])
+        self._generate_pen = _sig(L, "gten_host_model_generate_penalized", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
+                                                                                C.c_float, C.c_float, vp, vp, vp, pen])
+        self._bgen_pen = _sig(L, "gten_host_batch_generate_penalized", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
+                                                                            vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen])
+        self._bserve_pen = _sig(L, "gten_host_batch_serve_penalized", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                           C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen])
         self._score_top = _sig(L, "gten_host_model_score_top", ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
@@ -276,6 +296,16 @@ def _cut_args(n, top_p, min_p):
     """top_p / min_p (a scalar or one value per item) as the C ABI takes them: arrays or null, then the values for all"""
     (ps, p1), (ms, m1) = _each(top_p, n, np.float32), _each(min_p, n, np.float32)
     return [_ptr(ps), _ptr(ms), C.c_float(1.0 if ps is not None else float(p1)), C.c_float(0.0 if ms is not None else float(m1))]
+
+
+def _penalty_arg(n, rep, freq, pres, last_n, count_prompt):
+    """the gten_host_penalties of a call: each value a scalar for everybody or one per item.  The struct keeps its arrays alive."""
+    (r, r1), (f, f1), (p, p1) = _each(rep, n, np.float32), _each(freq, n, np.float32), _each(pres, n, np.float32)
+    (l, l1), (c, c1) = _each(last_n, n, np.int32), _each([int(bool(v)) for v in count_prompt] if not np.isscalar(count_prompt) else int(bool(count_prompt)), n, np.int32)
+    s = HostPenalties(_ptr(r), _ptr(f), _ptr(p), _ptr(l), _ptr(c), 1.0 if r is not None else float(r1), 0.0 if f is not None else float(f1),
+                      0.0 if p is not None else float(p1), 0 if l is not None else int(l1), 1 if c is not None else int(c1))
+    s._keep = (r, f, p, l, c)
+    return s
 
 
 class HostTokenizer:
@@ -588,6 +618,44 @@ class HostModel:
         ids = buf[:total].copy()
         return (ids, lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else ids
 
+    def set_penalty_rc(self, rep, freq=0.0, pres=0.0, start=0, last_n=0):
+        return self.host._m_set_pen(self.h, C.c_float(rep), C.c_float(freq), C.c_float(pres), int(start), int(last_n))
+
+    def set_penalty(self, rep=1.0, freq=0.0, pres=0.0, start=0, last_n=0):
+        """the decoder's steps penalise the ids at positions [max(start, n - last_n), n) of its own ids from now on ((1, 0, 0): off;
+        last_n 0: no limit; include/gten_host_penalty.h)"""
+        rc = self.set_penalty_rc(rep, freq, pres, start, last_n)
+        if rc:
+            raise GtenHipError(f"set_penalty rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def penalty_info(self):
+        """(rep, freq, pres, start, last_n, whether the decoder has ever had a penalty set)"""
+        r, f, p, s, l = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        on = self.host._m_pen_info(self.h, _ptr(r), _ptr(f), _ptr(p), _ptr(s), _ptr(l))
+        if on < 0:
+            raise GtenHipError(f"penalty_info rc={on}")
+        return r[0], f[0], p[0], int(s[0]), int(l[0]), bool(on)
+
+    def generate_penalized(self, prompt, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                           count_prompt=True, top_p=1.0, min_p=0.0, table=-1, min_new=0, n_top=None):
+        """generate_nucleus() with the ids the sequence already holds penalised (include/gten_host_penalty.h): rep divides a positive
+        logit (multiplies a negative one), freq is subtracted per occurrence, pres once; over the last last_n positions (0: all), the
+        prompt's included or not.  top_k 0: penalised greedy."""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        ask = n_top is not None and n_top >= 0
+        w = int(n_top) if ask else 0
+        lp, ti, tl = np.zeros(width, np.float32), np.full((width, w), -1, np.int32), np.zeros((width, w), np.float32)
+        pen = _penalty_arg(1, float(rep), float(freq), float(pres), int(last_n), bool(count_prompt))
+        total = self.host._generate_pen(self.h, _ptr(buf), len(prompt), max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)),
+                                        C.c_uint32(int(stream)), int(table), int(min_new), w if ask else -1, C.c_float(top_p), C.c_float(min_p),
+                                        _ptr(lp) if ask else None, _ptr(ti) if ask else None, _ptr(tl) if ask else None, C.byref(pen))
+        if total < 0:
+            raise GtenHipError(f"generate_penalized rc={total}: {self.host.hip._err().decode(errors='replace')}")
+        ids = buf[:total].copy()
+        return (ids, lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else ids
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -828,6 +896,51 @@ class HostBatch:
         ids, st = self._serve(self.host._bserve_nuc, "batch_serve_nucleus", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
                               *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args,
                               *_cut_args(n, top_p, min_p))
+        return (ids, st) if n_top is None else (ids, st, *rec)
+
+    def set_penalty_rc(self, seq, rep, freq=0.0, pres=0.0, start=0, last_n=0):
+        return self.host._b_set_pen(self.h, int(seq), C.c_float(rep), C.c_float(freq), C.c_float(pres), int(start), int(last_n))
+
+    def set_penalty(self, seq, rep=1.0, freq=0.0, pres=0.0, start=0, last_n=0):
+        """sequence seq's steps penalise the ids at positions [max(start, n - last_n), n) of its own ids from now on ((1, 0, 0): off;
+        include/gten_host_penalty.h)"""
+        rc = self.set_penalty_rc(seq, rep, freq, pres, start, last_n)
+        if rc:
+            raise GtenHipError(f"batch_set_penalty rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def penalty_info(self):
+        """(rep f32[n_seq], freq, pres, start int32[n_seq], last_n, whether the shared decoder has ever had a penalty set)"""
+        n = self.n_seq
+        r, f, p, s, l = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        on = self.host._b_pen_info(self.h, _ptr(r), _ptr(f), _ptr(p), _ptr(s), _ptr(l))
+        if on < 0:
+            raise GtenHipError(f"batch_penalty_info rc={on}")
+        return r, f, p, s, l, bool(on)
+
+    def generate_penalized(self, prompts, max_tokens, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                           count_prompt=True, top_p=1.0, min_p=0.0, tables=None, min_new=None, n_top=None):
+        """generate_nucleus() with a penalty per sequence (rep / freq / pres / last_n / count_prompt a scalar or a list)"""
+        n = self.n_seq
+        args, rec = _records(n_top, n, max_tokens)
+        if n_top is None:
+            args = [None, 0, None, None, None]
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        ids = self._generate(self.host._bgen_pen, "batch_generate_penalized", prompts, max_tokens, eos,
+                             _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)),
+                             args + _cut_args(n, top_p, min_p) + [C.byref(pen)])
+        return ids if n_top is None else (ids, *rec)
+
+    def serve_penalized(self, prompts, max_tokens, eos, top_k, temp, seed, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True, top_p=1.0,
+                        min_p=0.0, tables=None, min_new=None, n_top=None, slice_steps=16, max_new=0, max_new_each=None):
+        """serve_nucleus() with a penalty per prompt; n_top None: (ids per prompt, stats), otherwise serve_logprobs()'s tuple"""
+        n = len(prompts)
+        args, rec = _records(n_top, n, max(max_tokens, max(len(p) for p in prompts)))
+        if n_top is None:
+            args = [None, 0, None, None, None]
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        ids, st = self._serve(self.host._bserve_pen, "batch_serve_penalized", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                              *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args,
+                              *_cut_args(n, top_p, min_p), C.byref(pen))
         return (ids, st) if n_top is None else (ids, st, *rec)
 
     def set_prefix_rc(self, tokens):
