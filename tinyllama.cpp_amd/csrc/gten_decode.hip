@@ -29,6 +29,7 @@
 #include "gten_hip_logprobs.h"
 #include "gten_hip_nucleus.h"
 #include "gten_hip_penalty.h"
+#include "gten_hip_fsm.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 
@@ -110,6 +111,7 @@ static_assert(LP_TOP == GTEN_HIP_LOGPROBS_TOP && sizeof(LpRecord) == GTEN_HIP_LO
 static_assert(CUT_MASS_BITS == GTEN_HIP_NUCLEUS_MASS_BITS && sizeof(CutInfo) == GTEN_HIP_NUCLEUS_INFO_BYTES && sizeof(CutInfo) == sizeof(gten_hip_cut_info),
               "gten_decode_nucleus.h and include/gten_hip_nucleus.h disagree");
 #include "gten_decode_penalty.h"
+#include "gten_decode_fsm.h"
 
 // --------------------------------------------------------------- host side
 
@@ -145,6 +147,17 @@ struct SamplerState {
     int n_penalised = 0;                // sequences whose penalty is on
     size_t pen_lds = 0;                 // k_dec_sample_pen's dynamic LDS: the counts of one row
     bool pen_on = false;
+    // the automaton pool and the sequences' bindings (include/gten_hip_fsm.h).  A bound sequence's greedy id moves
+    // too, so it enters sampler_on as a penalised one does
+    uint16_t* fsm_next = nullptr;       // [fsm_states][n_vocab]
+    uint8_t* fsm_flags = nullptr;       // [fsm_states]
+    std::vector<uint8_t> fsm_flags_host;
+    int fsm_states = 0;
+    FsmParam* fsm = nullptr;            // [n_seq] bindings beside `samp`
+    std::vector<FsmParam> fsm_host;
+    int32_t* fsm_state = nullptr;       // [n_seq][max_ctx + 2] the state per position, laid out like `result`
+    int n_fsm = 0;                      // sequences that are bound
+    bool fsm_on = false;
 };
 
 struct gten_hip_decoder {
@@ -234,7 +247,7 @@ struct gten_hip_decoder {
 };
 
 // the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table, asks for log-probs or is penalised
-static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking + dc->smp.n_penalised > 0; }
+static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking + dc->smp.n_penalised + dc->smp.n_fsm > 0; }
 
 // where the step of one lane ends: what the sampler launch reads and writes, and the four arguments of k_dec_argmax in which the
 // three step forms differ (the others -- tables, row lengths -- are the decoder's)
@@ -248,6 +261,7 @@ struct StepEnd {
     LpRecord* lp;
     const CutParam* cut;
     const PenParam* pen;
+    const FsmParam* fsm; int32_t* fsm_state;
     const float* best_val; const int* best_idx; int n_best, best_stride;      // k_dec_argmax: candidates per sequence
 };
 
@@ -258,7 +272,11 @@ static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
     const int V = dc->d.n_vocab, tok_stride = dc->d.max_ctx + 1, rec_stride = dc->d.max_ctx + 2;
     const dim3 grid(e.rows), block(SMP_THREADS);
     const bool on = sampler_on(dc);
-    if (on && s.pen_on)
+    if (on && s.fsm_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_fsm, grid, block, s.pen_lds, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens,
+                   tok_stride, (const float*)s.bias, e.lp, rec_stride, e.cut, e.pen, (const uint16_t*)s.fsm_next, (const uint8_t*)s.fsm_flags, s.fsm_states,
+                   e.fsm, e.fsm_state);
+    else if (on && s.pen_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_pen, grid, block, s.pen_lds, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens,
                    tok_stride, (const float*)s.bias, e.lp, rec_stride, e.cut, e.pen);
     else if (on && s.cut_on)
@@ -282,6 +300,7 @@ static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
 struct LaneBufs {
     int n_seq;
     DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp; const CutParam* cut; const PenParam* pen;
+    const FsmParam* fsm; int32_t* fsm_state;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -301,6 +320,8 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     b.lp = dc->smp.lp ? dc->smp.lp + o * (d.max_ctx + 2) : nullptr;
     b.cut = dc->smp.cut ? dc->smp.cut + o : nullptr;
     b.pen = dc->smp.pen ? dc->smp.pen + o : nullptr;
+    b.fsm = dc->smp.fsm ? dc->smp.fsm + o : nullptr;
+    b.fsm_state = dc->smp.fsm_state ? dc->smp.fsm_state + o * (d.max_ctx + 2) : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -707,7 +728,7 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
     // (one sequence: no strides; the argmax joins lm_head's per-wave winners)
-    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen,
+    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state,
                                        dc->best_val, dc->best_idx, dc->n_best, 0});
 }
 
@@ -846,7 +867,7 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen,
+    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state,
                                        dc->best_val, dc->best_idx, dc->n_best, dc->n_best});
 }
 
@@ -1319,7 +1340,7 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
     // (the matrix-core lm_head keeps no winners: the argmax reads the logits rows; the bias tables are the decoder's, not a lane's)
-    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.pen, b.logits_m, nullptr, V, V});
+    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.pen, b.fsm, b.fsm_state, b.logits_m, nullptr, V, V});
 }
 
 template <int WT>
@@ -1707,7 +1728,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm_next, dc->smp.fsm_flags, dc->smp.fsm, dc->smp.fsm_state,
                     dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
     for (void* b : bufs) if (b) rel(hipFree(b));
     rel(persist_free(dc));
@@ -1984,6 +2005,17 @@ int gten_hip_decoder_step_ragged(gten_hip_decoder* dc, const int* n_per_seq, int
     return run_step(dc, use_graph);
 }
 
+// whether sequence q is bound to an automaton (include/gten_hip_fsm.h), and whether `state` is a final state of the pool: the id that
+// entered a final state ends its sequence as an eos does, but is kept
+static inline bool fsm_bound(const gten_hip_decoder* dc, int q) { return dc->smp.fsm_on && dc->smp.fsm_host[(size_t)q].on != 0u; }
+// ... and whether the id at position n of the bound sequence q was chosen under its automaton: the row's entries behind the binding's
+// position are whatever an earlier binding left there (an ended sequence leaves a run of final states) and are never looked at
+static inline bool fsm_covers(const gten_hip_decoder* dc, int q, int n) { return n >= dc->smp.fsm_host[(size_t)q].pos; }
+static inline bool fsm_final(const gten_hip_decoder* dc, int state)
+{
+    return state >= 0 && state < dc->smp.fsm_states && (dc->smp.fsm_flags_host[(size_t)state] & GTEN_HIP_FSM_FINAL) != 0;
+}
+
 // Greedy generation without the host in the loop (single-sequence decoders): steps n_first, n_first + 1, ... replay the
 // graph back to back, each one's argmax written on the device as the next step's input token; the host reads the ids in
 // slices of `GEN_SLICE` steps and stops at `eos` (the steps queued past it only touched rows that no longer matter).
@@ -2002,16 +2034,19 @@ int gten_hip_decoder_generate(gten_hip_decoder* dc, int n_first, int max_new, in
     dc->dev_ns.clear();
     if (int rc_ = slots_leave(dc)) return rc_;
     int got = 0;
-    std::vector<int32_t> ids(GEN_SLICE);
+    std::vector<int32_t> ids(GEN_SLICE), sts(GEN_SLICE);
+    const bool bound = fsm_bound(dc, 0);               // (its state rows are read beside the ids: sts[i] is the state id i entered)
     for (int n = n_first; n <= last;) {
         const int cnt = std::min(GEN_SLICE, last - n + 1);
         if (int rc = run_steps_free(dc, cnt)) return rc;
         GTR_CHECK(hipMemcpyAsync(ids.data(), dc->result + n, (size_t)cnt * 4, hipMemcpyDeviceToHost, stream()));
+        if (bound) GTR_CHECK(hipMemcpyAsync(sts.data(), dc->smp.fsm_state + n + 1, (size_t)cnt * 4, hipMemcpyDeviceToHost, stream()));
         GTR_CHECK(hipStreamSynchronize(stream()));
         bool stop = false;
         for (int i = 0; i < cnt; i++) {
             if (ids[i] == eos) { stop = true; break; }
             out_host[got++] = ids[i];
+            if (bound && fsm_covers(dc, 0, n + i) && fsm_final(dc, sts[i])) { stop = true; break; }
         }
         if (stop) break;
         n += cnt;
@@ -2050,7 +2085,7 @@ int gten_hip_decoder_generate_multi(gten_hip_decoder* dc, const int* n_first, co
     dc->dev_ns.clear();
     hm_mark_all(dc);
     if (int rc_ = slots_leave(dc)) return rc_;
-    std::vector<int32_t> ids((size_t)GEN_SLICE);
+    std::vector<int32_t> ids((size_t)GEN_SLICE), sts((size_t)GEN_SLICE);
     while (n_live > 0) {
         int cnt = GEN_SLICE;
         for (int q = 0; q < S; q++) if (live[q]) cnt = std::min(cnt, last[q] - cur[q] + 1);   // nobody runs past its last step
@@ -2059,10 +2094,15 @@ int gten_hip_decoder_generate_multi(gten_hip_decoder* dc, const int* n_first, co
         for (int q = 0; q < S; q++) {
             if (!live[q]) continue;
             GTR_CHECK(hipMemcpy(ids.data(), dc->result + (size_t)q * (ctx + 2) + cur[q], (size_t)cnt * 4, hipMemcpyDeviceToHost));
+            const bool bound = fsm_bound(dc, q);
+            if (bound) GTR_CHECK(hipMemcpy(sts.data(), dc->smp.fsm_state + (size_t)q * (ctx + 2) + cur[q] + 1, (size_t)cnt * 4, hipMemcpyDeviceToHost));
             bool stop = false;
             for (int i = 0; i < cnt && !stop; i++) {
                 if (ids[i] == eos) stop = true;
-                else out_host[(size_t)q * max_new + n_out[q]++] = ids[i];
+                else {
+                    out_host[(size_t)q * max_new + n_out[q]++] = ids[i];
+                    if (bound && fsm_covers(dc, q, cur[q] + i) && fsm_final(dc, sts[i])) stop = true;
+                }
             }
             cur[q] += cnt;
             if (stop || cur[q] > last[q]) {

@@ -103,14 +103,14 @@ __device__ __forceinline__ void cut_find_digit(unsigned long long need, CutShare
 
 // One row under a cut: the id of the contract (top_k >= 1; the caller sends greedy rows to smp_row).  Every thread returns
 // it; thread 0 writes *info when info is not null.  top_p in (0, 1], t <= 0 (-inf: no min-p).
-template <bool BIAS, bool PEN = false>
+template <bool BIAS, bool PEN = false, bool FSM = false>
 __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
                                            unsigned stream, unsigned k0, unsigned k1, float top_p, float tmin, CutInfo* __restrict__ info,
-                                           SmpShared& sm, CutShared& cs, const PenRow& pen = PenRow{})
+                                           SmpShared& sm, CutShared& cs, const PenRow& pen = PenRow{}, const FsmRow& fsm = FsmRow{})
 {
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     // 1. the candidates, as smp_row finds them: (key & mask) > prefix, or == prefix with index <= ilim
-    const SmpSelect sel = smp_select<BIAS, PEN>(x, b, n, top_k, sm, pen);
+    const SmpSelect sel = smp_select<BIAS, PEN, FSM>(x, b, n, top_k, sm, pen, fsm);
     const unsigned mask = sel.mask, prefix = sel.prefix;
     const int ilim = sel.ilim, n_cand = min(top_k, n);
     const float mx = sel.mx;
@@ -122,7 +122,7 @@ __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const fl
         cs.cq[t] = 0ull;
         __syncthreads();
         for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = smp_at<BIAS, PEN>(x, b, i, pen);
+            const float v = smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm);
             const unsigned key = smp_key(v), km = key & mask;
             if (km > prefix || (km == prefix && i <= ilim)) {
                 const unsigned slot = atomicAdd(&cs.have, 1u);
@@ -183,7 +183,7 @@ __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const fl
         unsigned long long z = 0ull;
         unsigned c = 0u;
         for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = smp_at<BIAS, PEN>(x, b, i, pen);
+            const float v = smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm);
             const unsigned km = smp_key(v) & mask;
             if (km > prefix || (km == prefix && i <= ilim)) {
                 const float a = cut_score(v, mx, temp);
@@ -210,7 +210,7 @@ __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const fl
             __syncthreads();
             for (int base = 0; base < n; base += SMP_THREADS) {         // (every lane runs every trip: cut_mass_add is per wave)
                 const int i = base + t;
-                const float v = i < n ? smp_at<BIAS, PEN>(x, b, i, pen) : -INFINITY;
+                const float v = i < n ? smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm) : -INFINITY;
                 const unsigned key = smp_key(v), km = key & mask;
                 const bool cand = i < n && (km > prefix || (km == prefix && i <= ilim));
                 const unsigned long long q = cand && (key & cmask) == ckey ? cut_mass(cut_score(v, mx, temp)) : 0ull;
@@ -233,7 +233,7 @@ __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const fl
             for (int i = t; i < 256; i += SMP_THREADS) sm.hist[i] = 0u;
             __syncthreads();
             for (int i = t; i < n; i += SMP_THREADS) {
-                const unsigned key = smp_key(smp_at<BIAS, PEN>(x, b, i, pen)), km = key & mask;
+                const unsigned key = smp_key(smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm)), km = key & mask;
                 if (key == ckey && (km > prefix || i <= ilim) && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
             }
             __syncthreads();
@@ -251,7 +251,7 @@ __device__ __forceinline__ int smp_row_cut(const float* __restrict__ x, const fl
     int idx = 0x7fffffff;
     unsigned c = 0u;
     for (int i = t; i < n; i += SMP_THREADS) {
-        const float v = smp_at<BIAS, PEN>(x, b, i, pen);
+        const float v = smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm);
         const unsigned key = smp_key(v), km = key & mask;
         if (km > prefix || (km == prefix && i <= ilim)) {
             const bool in = key > ckey || (key == ckey && i <= clim);

@@ -156,10 +156,22 @@ __device__ __forceinline__ float pen_apply(float x, unsigned c, const PenRow& pe
     const float t = __fadd_rn(__fmul_rn((float)c, pen.freq), pen.pres);
     return __fsub_rn(u, t);
 }
-template <bool BIAS, bool PEN = false>
-__device__ __forceinline__ float smp_at(const float* __restrict__ x, const float* __restrict__ b, int i, const PenRow& pen = PenRow{})
+//
+// FSM (include/gten_hip_fsm.h): the mask form.  `fsm.next` is the row of the sequence's state in the automaton pool,
+// one u16 per id; where it says FSM_DEAD the element is -inf, otherwise it is the element of the form below, bits untouched -- the
+// penalty first, the mask second.  One u16 load per element read.  An instance without FSM never touches `fsm`.
+#define FSM_DEAD 0xFFFFu
+struct FsmRow {
+    const uint16_t* next;        // next[i]: the state after id i, or FSM_DEAD
+};
+template <bool BIAS, bool PEN = false, bool FSM = false>
+__device__ __forceinline__ float smp_at(const float* __restrict__ x, const float* __restrict__ b, int i, const PenRow& pen = PenRow{},
+                                        const FsmRow& fsm = FsmRow{})
 {
-    if constexpr (PEN) {
+    if constexpr (FSM) {
+        const float p = smp_at<BIAS, PEN, false>(x, b, i, pen);
+        return fsm.next[i] == FSM_DEAD ? -INFINITY : p;
+    } else if constexpr (PEN) {
         const float p = pen_apply(x[i], (pen.cnt[i >> 1] >> ((i & 1) << 4)) & 0xffffu, pen);
         if constexpr (BIAS) return __fadd_rn(p, b[i]);
         else return p;
@@ -176,9 +188,9 @@ struct SmpSelect {
     int ilim;
     float mx;
 };
-template <bool BIAS, bool PEN = false>
+template <bool BIAS, bool PEN = false, bool FSM = false>
 __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, SmpShared& sm,
-                                                const PenRow& pen = PenRow{})
+                                                const PenRow& pen = PenRow{}, const FsmRow& fsm = FsmRow{})
 {
     const int t = threadIdx.x;
     unsigned mask = 0u, prefix = 0u, kk = (unsigned)min(top_k, n);
@@ -191,7 +203,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
         if (shift == 24) {
             for (int base = 0; base < n; base += SMP_THREADS) {         // (every lane runs every trip: smp_hist_add is per wave)
                 const int i = base + t;
-                const float v = i < n ? smp_at<BIAS, PEN>(x, b, i, pen) : -INFINITY;
+                const float v = i < n ? smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm) : -INFINITY;
                 mx = fmaxf(mx, v);
                 if (!all) smp_hist_add(sm, i < n, smp_key(v) >> 24);
             }
@@ -200,7 +212,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
         } else {
             for (int base = 0; base < n; base += SMP_THREADS) {
                 const int i = base + t;
-                const unsigned key = i < n ? smp_key(smp_at<BIAS, PEN>(x, b, i, pen)) : 0u;
+                const unsigned key = i < n ? smp_key(smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm)) : 0u;
                 smp_hist_add(sm, i < n && (key & mask) == prefix, (key >> shift) & 255u);
             }
             __syncthreads();
@@ -219,7 +231,7 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
                 for (int i = t; i < 256; i += SMP_THREADS) sm.hist[i] = 0u;
                 __syncthreads();
                 for (int i = t; i < n; i += SMP_THREADS)
-                    if (smp_key(smp_at<BIAS, PEN>(x, b, i, pen)) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
+                    if (smp_key(smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm)) == prefix && ((unsigned)i & imask) == ipre) atomicAdd(&sm.hist[255u - (((unsigned)i >> s) & 255u)], 1u);
                 __syncthreads();
                 smp_find_digit(kk, sm);
                 const unsigned di = 255u - sm.word[0], ri = sm.word[1];
@@ -237,28 +249,29 @@ __device__ __forceinline__ SmpSelect smp_select(const float* __restrict__ x, con
 // One row: the id of the contract (top_k >= 1) or the greedy argmax (top_k == 0).  Every thread returns it.
 // BIAS: the row is y = x + b (b: a bias table's row; -inf = banned -- its key sorts below every finite value and its score is
 // -inf, so it is never the argmax while one entry is above -inf); the unbiased instance never touches b.
-template <bool BIAS, bool PEN = false>
+template <bool BIAS, bool PEN = false, bool FSM = false>
 __device__ __forceinline__ int smp_row(const float* __restrict__ x, const float* __restrict__ b, int n, int top_k, float temp, unsigned pos,
-                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm, const PenRow& pen = PenRow{})
+                                       unsigned stream, unsigned k0, unsigned k1, SmpShared& sm, const PenRow& pen = PenRow{},
+                                       const FsmRow& fsm = FsmRow{})
 {
     const int t = threadIdx.x;
     if (top_k <= 0) {
         float best = -INFINITY;
         int idx = 0x7fffffff;
         for (int i = t; i < n; i += SMP_THREADS) {
-            const float v = smp_at<BIAS, PEN>(x, b, i, pen);
+            const float v = smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm);
             if (v > best || (v == best && i < idx)) { best = v; idx = i; }
         }
         return smp_block_argmax(best, idx, sm);
     }
-    const SmpSelect c = smp_select<BIAS, PEN>(x, b, n, top_k, sm, pen);
+    const SmpSelect c = smp_select<BIAS, PEN, FSM>(x, b, n, top_k, sm, pen, fsm);
     const unsigned mask = c.mask, prefix = c.prefix;
     const int ilim = c.ilim;
     const float mx = c.mx;
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i = t; i < n; i += SMP_THREADS) {
-        const float v = smp_at<BIAS, PEN>(x, b, i, pen);
+        const float v = smp_at<BIAS, PEN, FSM>(x, b, i, pen, fsm);
         const unsigned key = smp_key(v) & mask;
         if (key > prefix || (key == prefix && i <= ilim)) {
             const float s = (v - mx) / temp + smp_gumbel((unsigned)i, pos, stream, k0, k1);

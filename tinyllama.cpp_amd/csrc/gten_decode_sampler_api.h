@@ -157,6 +157,8 @@ int gten_hip_decoder_set_seq_bias(gten_hip_decoder* dc, int seq, int table, int 
     GTR_REQUIRE(table >= -1 && table < GTEN_HIP_BIAS_TABLES, "decoder_set_seq_bias: table %d outside [-1, %d)", table, GTEN_HIP_BIAS_TABLES);
     GTR_REQUIRE(until >= 0, "decoder_set_seq_bias: until %d < 0", until);
     GTR_REQUIRE(table < 0 || !dc->persist_on, "decoder_set_seq_bias: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    GTR_REQUIRE(table < 0 || !dc->smp.fsm_on || dc->smp.fsm_host[(size_t)seq].on == 0u,
+                "decoder_set_seq_bias: sequence %d is bound to an automaton (gten_hip_decoder_set_seq_fsm): a table and an automaton do not compose", seq);
     if (table >= 0 && !dc->smp.bias_on)
         if (int rc = first_use(dc, dc->smp.bias_on, bias_make)) return rc;
     SampleParam& p = dc->smp.samp_host[(size_t)seq];
@@ -353,11 +355,27 @@ static int pen_rows_upload(const char* who, const PenRows& pen, int n_rows)
 // the operators differ in what they take: ROWS_PLAIN no bias and no cuts, ROWS_BIASED a bias it requires, ROWS_CUT cuts and a bias it
 // accepts (null: none), ROWS_PEN those and every row's window and penalty (`pen`; with pen->y_out the rows are written out and nothing
 // is drawn: no request is looked at).  `who` names the operator in every message.
-enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT, ROWS_PEN };
+// ROWS_FSM (include/gten_hip_fsm.h, §3.15): ROWS_PEN without a bias, every row in a state of the caller's pool (`fsm`).
+enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT, ROWS_PEN, ROWS_FSM };
+struct FsmRows {
+    const uint16_t* next; const uint8_t* flags;      // the pool, on the device
+    int n_states;
+    const int32_t* state_host;                       // [n_rows]; -1: not bound
+    int32_t* next_out;                               // device [n_rows] or null
+};
+static GrowBuf g_state_dev;                          // the rows' states of one ROWS_FSM call
+static int fsm_rows_upload(const char* who, const FsmRows& f, int n_rows)
+{
+    GTR_REQUIRE(f.next && f.flags && f.state_host, "%s: null argument", who);
+    GTR_REQUIRE(f.n_states >= 1 && f.n_states <= GTEN_HIP_FSM_MAX_STATES, "%s: a pool of %d states (1 .. %d)", who, f.n_states, GTEN_HIP_FSM_MAX_STATES);
+    for (int r = 0; r < n_rows; r++)
+        GTR_REQUIRE(f.state_host[r] >= -1 && f.state_host[r] < f.n_states, "%s: state %d of row %d outside [-1, %d)", who, f.state_host[r], r, f.n_states);
+    return grow_upload(g_state_dev, f.state_host, (size_t)n_rows * sizeof(int32_t));
+}
 static int sample_rows_common(const char* who, RowsLevel level, const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias,
                               long long bias_stride, const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
                               const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out, gten_hip_cut_info* info_out,
-                              const PenRows* pen = nullptr)
+                              const PenRows* pen = nullptr, const FsmRows* fsm = nullptr)
 {
     GTR_NEED_INIT();
     const bool shape_ok = n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0;
@@ -367,12 +385,21 @@ static int sample_rows_common(const char* who, RowsLevel level, const float* log
         GTR_REQUIRE(shape_ok && bias_stride >= 0, "%s: %d rows of %d logits (n_vocab in [1, 65535]), strides %lld, %lld", who, n_rows, n_vocab, row_stride,
                     bias_stride);
     const dim3 grid(n_rows), block(SMP_THREADS);
-    if (level == ROWS_PEN && pen->y_out) {
+    if ((level == ROWS_PEN || level == ROWS_FSM) && pen->y_out) {
         GTR_REQUIRE(pen->y_stride >= n_vocab || n_rows <= 1, "%s: output stride %lld < n_vocab %d", who, pen->y_stride, n_vocab);
         if (n_rows == 0) return 0;
         GTR_REQUIRE(logits, "%s: null argument", who);
         if (int rc = pen_rows_upload(who, *pen, n_rows)) return rc;
         size_t lds = 0;
+        if (level == ROWS_FSM) {
+            if (int rc = fsm_rows_upload(who, *fsm, n_rows)) return rc;
+            if (int rc = pen_fit((const void*)k_mask_rows_fsm, n_vocab, who, &lds)) return rc;
+            GTR_LAUNCH(KT_DEC_SAMPLE, k_mask_rows_fsm, grid, block, lds, logits, n_vocab, row_stride, (const PenParam*)g_pen_dev.dev,
+                       (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, fsm->next, fsm->flags, fsm->n_states, (const int32_t*)g_state_dev.dev,
+                       pen->y_out, pen->y_stride);
+            GTR_CHECK(hipStreamSynchronize(stream()));
+            return 0;
+        }
         if (int rc = pen_fit((const void*)k_penalize_rows, n_vocab, who, &lds)) return rc;
         GTR_LAUNCH(KT_DEC_SAMPLE, k_penalize_rows, grid, block, lds, logits, n_vocab, row_stride, bias, bias_stride, (const PenParam*)g_pen_dev.dev,
                    (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, pen->y_out, pen->y_stride);
@@ -380,7 +407,7 @@ static int sample_rows_common(const char* who, RowsLevel level, const float* log
         return 0;
     }
     if (n_rows == 0) return 0;
-    const bool cutting = level == ROWS_CUT || level == ROWS_PEN;
+    const bool cutting = level == ROWS_CUT || level == ROWS_PEN || level == ROWS_FSM;
     GTR_REQUIRE(logits && out && top_k_host && temp_host && stream_host && position_host && (level != ROWS_BIASED || bias) &&
                 (!cutting || (top_p_host && min_p_host)), "%s: null argument", who);
     std::vector<SampleRowParam> rows((size_t)n_rows);
@@ -393,12 +420,21 @@ static int sample_rows_common(const char* who, RowsLevel level, const float* log
         rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
         if (cutting) cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
     }
-    if (level == ROWS_PEN)
+    if (level == ROWS_PEN || level == ROWS_FSM)
         if (int rc = pen_rows_upload(who, *pen, n_rows)) return rc;
+    if (level == ROWS_FSM)
+        if (int rc = fsm_rows_upload(who, *fsm, n_rows)) return rc;
     if (int rc = grow_upload(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam))) return rc;
     const SampleRowParam* par = (const SampleRowParam*)g_rows_dev.dev;
     const unsigned seed_lo = (unsigned)(seed & 0xffffffffu), seed_hi = (unsigned)(seed >> 32);
-    if (level == ROWS_PEN) {
+    if (level == ROWS_FSM) {
+        size_t lds = 0;
+        if (int rc = pen_fit((const void*)k_sample_rows_fsm, n_vocab, who, &lds)) return rc;
+        if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_fsm, grid, block, lds, logits, n_vocab, row_stride, par, (const CutParam*)g_cut_dev.dev,
+                   (const PenParam*)g_pen_dev.dev, (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, fsm->next, fsm->flags, fsm->n_states,
+                   (const int32_t*)g_state_dev.dev, seed_lo, seed_hi, out, fsm->next_out, (CutInfo*)info_out);
+    } else if (level == ROWS_PEN) {
         size_t lds = 0;
         if (int rc = pen_fit((const void*)k_sample_rows_pen, n_vocab, who, &lds)) return rc;
         if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
@@ -474,4 +510,189 @@ int gten_hip_row_top_logprobs(const float* logits, int n_rows, int n_vocab, long
     GTR_LAUNCH(KT_DEC_SAMPLE, k_row_top_logprobs, dim3(n_rows), dim3(SMP_THREADS), 0, logits, n_vocab, row_stride, ids, n_top, logprob_out, top_id_out,
                top_logprob_out);
     return 0;
+}
+
+// ---- token automata (include/gten_hip_fsm.h)
+int gten_hip_fsm_check(const uint16_t* next_host, const uint8_t* flags_host, long long n_states, long long n_vocab, long long* where)
+{
+    if (where) *where = -1;
+    if (!next_host || !flags_host || n_states < 1 || n_states > GTEN_HIP_FSM_MAX_STATES || n_vocab < 1) return GTEN_HIP_FSM_BAD_STATES;
+    if ((unsigned long long)n_states * (unsigned long long)n_vocab * 2ull > GTEN_HIP_FSM_MAX_BYTES) return GTEN_HIP_FSM_TOO_LARGE;
+    for (long long s = 0; s < n_states; s++) {
+        const uint16_t* row = next_host + (size_t)s * (size_t)n_vocab;
+        bool any = false;
+        for (long long i = 0; i < n_vocab; i++) {
+            if (row[i] == GTEN_HIP_FSM_DEAD) continue;
+            if (row[i] >= n_states) { if (where) *where = s; return GTEN_HIP_FSM_BAD_ENTRY; }
+            any = true;
+        }
+        if (!any && !(flags_host[s] & GTEN_HIP_FSM_FINAL)) { if (where) *where = s; return GTEN_HIP_FSM_STUCK; }
+    }
+    return GTEN_HIP_FSM_OK;
+}
+
+int gten_hip_decoder_set_fsm(gten_hip_decoder* dc, const uint16_t* next_host, const uint8_t* flags_host, int n_states)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_set_fsm: null decoder");
+    GTR_REQUIRE(!dc->persist_on, "decoder_set_fsm: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    SamplerState& s = dc->smp;
+    GTR_REQUIRE(s.n_fsm == 0, "decoder_set_fsm: %d sequences are bound to the present pool (gten_hip_decoder_set_seq_fsm(.., -1, 0) first)", s.n_fsm);
+    const bool drop = !next_host && !flags_host && n_states == 0;
+    if (!drop) {
+        long long where = -1;
+        const int bad = gten_hip_fsm_check(next_host, flags_host, n_states, dc->d.n_vocab, &where);
+        GTR_REQUIRE(bad != GTEN_HIP_FSM_BAD_STATES, "decoder_set_fsm: %d states (1 .. %d), or a null table", n_states, GTEN_HIP_FSM_MAX_STATES);
+        GTR_REQUIRE(bad != GTEN_HIP_FSM_TOO_LARGE, "decoder_set_fsm: %d states of %d ids are more than %llu bytes", n_states, dc->d.n_vocab,
+                    (unsigned long long)GTEN_HIP_FSM_MAX_BYTES);
+        GTR_REQUIRE(bad != GTEN_HIP_FSM_BAD_ENTRY, "decoder_set_fsm: state %lld has an entry that is neither a state nor DEAD", where);
+        GTR_REQUIRE(bad != GTEN_HIP_FSM_STUCK, "decoder_set_fsm: state %lld is not final and allows no id", where);
+    }
+    GTR_CHECK(hipStreamSynchronize(stream()));             // (no step in flight reads the pool that goes)
+    uint16_t* next = nullptr;
+    uint8_t* flags = nullptr;
+    if (!drop) {
+        // the new pool is complete on the device before the old one goes: a refusal or a failed allocation leaves the previous pool
+        const size_t bytes = (size_t)n_states * (size_t)dc->d.n_vocab * sizeof(uint16_t);
+        GTR_CHECK(hipMalloc((void**)&next, bytes));
+        if (hipMalloc((void**)&flags, (size_t)n_states) != hipSuccess) { (void)hipFree(next); GTR_REQUIRE(false, "decoder_set_fsm: out of device memory"); }
+        GTR_CHECK(hipMemcpyAsync(next, next_host, bytes, hipMemcpyHostToDevice, stream()));
+        GTR_CHECK(hipMemcpyAsync(flags, flags_host, (size_t)n_states, hipMemcpyHostToDevice, stream()));
+        GTR_CHECK(hipStreamSynchronize(stream()));
+    }
+    // (the pool's pointers and size are arguments of the captured step-end launch: graphs that hold the old ones go)
+    if (s.fsm_on) GTR_CHECK(drop_graphs(dc));
+    if (s.fsm_next) GTR_CHECK(hipFree(s.fsm_next));
+    if (s.fsm_flags) GTR_CHECK(hipFree(s.fsm_flags));
+    s.fsm_next = next; s.fsm_flags = flags; s.fsm_states = drop ? 0 : n_states;
+    if (drop) s.fsm_flags_host.clear();
+    else s.fsm_flags_host.assign(flags_host, flags_host + n_states);
+    return 0;
+}
+
+static int fsm_make(gten_hip_decoder* dc)           // every sequence: unbound; the state rows zeroed
+{
+    SamplerState& s = dc->smp;
+    // (this rung counts a penalised sequence's window too: its dynamic LDS limit is raised here, before any capture, whether a
+    //  penalty came first or comes later -- pen_make fixes the size the launch passes)
+    size_t lds = 0;
+    if (int rc = pen_fit((const void*)k_dec_sample_fsm, dc->d.n_vocab, "decoder_set_seq_fsm", &lds)) return rc;
+    s.fsm_host.assign((size_t)dc->n_seq, FsmParam{-1, 0, 0u, {0u, 0u, 0u, 0u, 0u}});
+    const size_t rows = (size_t)dc->n_seq * (size_t)(dc->d.max_ctx + 2) * sizeof(int32_t);
+    if (!s.fsm) GTR_CHECK(hipMalloc((void**)&s.fsm, (size_t)dc->n_seq * sizeof(FsmParam)));
+    if (!s.fsm_state) GTR_CHECK(hipMalloc((void**)&s.fsm_state, rows));
+    GTR_CHECK(hipMemcpyAsync(s.fsm, s.fsm_host.data(), s.fsm_host.size() * sizeof(FsmParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemsetAsync(s.fsm_state, 0, rows, stream()));
+    return 0;
+}
+
+int gten_hip_decoder_set_seq_fsm(gten_hip_decoder* dc, int seq, int state, int pos)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_seq_fsm: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    SamplerState& s = dc->smp;
+    if (state < 0) {
+        GTR_REQUIRE(state == -1, "decoder_set_seq_fsm: state %d (-1 unbinds)", state);
+        if (!s.fsm_on) return 0;                         // nobody has ever been bound: nothing to clear
+        pos = 0;
+    } else {
+        GTR_REQUIRE(!dc->persist_on, "decoder_set_seq_fsm: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+        GTR_REQUIRE(s.fsm_states > 0, "decoder_set_seq_fsm: the decoder has no pool (gten_hip_decoder_set_fsm)");
+        GTR_REQUIRE(state < s.fsm_states, "decoder_set_seq_fsm: state %d outside the pool's [0, %d)", state, s.fsm_states);
+        GTR_REQUIRE(pos >= 1 && pos <= dc->d.max_ctx, "decoder_set_seq_fsm: position %d outside [1, %d]", pos, dc->d.max_ctx);
+        GTR_REQUIRE(s.samp_host[(size_t)seq].table1 == 0,
+                    "decoder_set_seq_fsm: sequence %d is bound to bias table %d (gten_hip_decoder_set_seq_bias): a table and an automaton do not compose", seq,
+                    s.samp_host[(size_t)seq].table1 - 1);
+        if (!s.fsm_on)
+            if (int rc = first_use(dc, s.fsm_on, fsm_make)) return rc;
+    }
+    FsmParam& h = s.fsm_host[(size_t)seq];
+    s.n_fsm += (state >= 0 ? 1 : 0) - (h.on ? 1 : 0);
+    h = FsmParam{state, pos, state >= 0 ? 1u : 0u, {0u, 0u, 0u, 0u, 0u}};
+    const int32_t st = state;
+    if (state >= 0)
+        GTR_CHECK(hipMemcpyAsync(s.fsm_state + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + pos, &st, sizeof(st), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(s.fsm + seq, &h, sizeof(FsmParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    return 0;
+}
+
+int gten_hip_decoder_fsm_info(gten_hip_decoder* dc, int* n_states, int32_t* state_host, int32_t* pos_host, int* on, int row_seq, int row_from,
+                              int row_count, int32_t* row_host, const uint16_t** next_dev, const uint8_t** flags_dev)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_fsm_info: null decoder");
+    const SamplerState& s = dc->smp;
+    if (n_states) *n_states = s.fsm_states;
+    for (int q = 0; q < dc->n_seq; q++) {
+        const bool b = s.fsm_on && s.fsm_host[(size_t)q].on != 0u;
+        if (state_host) state_host[q] = b ? s.fsm_host[(size_t)q].state : -1;
+        if (pos_host) pos_host[q] = b ? s.fsm_host[(size_t)q].pos : 0;
+    }
+    if (on) *on = s.fsm_on ? 1 : 0;
+    if (next_dev) *next_dev = s.fsm_next;
+    if (flags_dev) *flags_dev = s.fsm_flags;
+    if (row_host) {
+        GTR_REQUIRE(row_seq >= 0 && row_seq < dc->n_seq && row_from >= 0 && row_count >= 0 && row_from + row_count <= dc->d.max_ctx + 2,
+                    "decoder_fsm_info: entries [%d, %d + %d) of sequence %d's state row (%d entries, %d sequences)", row_from, row_from, row_count, row_seq,
+                    dc->d.max_ctx + 2, dc->n_seq);
+        if (!s.fsm_state) std::fill(row_host, row_host + row_count, 0);
+        else if (row_count > 0) {
+            GTR_CHECK(hipStreamSynchronize(stream()));
+            GTR_CHECK(hipMemcpy(row_host, s.fsm_state + (size_t)row_seq * (size_t)(dc->d.max_ctx + 2) + row_from, (size_t)row_count * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+int gten_hip_decoder_slot_states(gten_hip_decoder* dc, int seq, int n_from, int count, int32_t* states_host)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && states_host && seq >= 0 && seq < dc->n_seq, "decoder_slot_states: bad arguments");
+    GTR_REQUIRE(n_from >= 0 && count >= 0 && n_from + count <= dc->d.max_ctx + 2, "decoder_slot_states: entries [%d, %d) outside [0, %d)", n_from, n_from + count,
+                dc->d.max_ctx + 2);
+    GTR_REQUIRE(dc->smp.fsm_state, "decoder_slot_states: no sequence of this decoder has been bound to an automaton (gten_hip_decoder_set_seq_fsm)");
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    if (count > 0)
+        GTR_CHECK(hipMemcpy(states_host, dc->smp.fsm_state + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + n_from, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the penalties of an automaton operator's rows: the caller's, or "none" for every row when it passes no window offsets
+struct FsmPenDefaults {
+    std::vector<int32_t> off;
+    std::vector<float> one, zero;
+    PenRows rows(int n_rows, const int32_t* hist, const int32_t* off_host, const float* r, const float* freq, const float* pres, float* y_out, long long y_stride)
+    {
+        if (off_host) return PenRows{hist, off_host, r, freq, pres, y_out, y_stride};
+        off.assign((size_t)std::max(n_rows, 0) + 1, 0);
+        one.assign((size_t)std::max(n_rows, 1), 1.f);
+        zero.assign((size_t)std::max(n_rows, 1), 0.f);
+        return PenRows{nullptr, off.data(), one.data(), zero.data(), zero.data(), y_out, y_stride};
+    }
+};
+
+int gten_hip_mask_rows_fsm(const float* logits, int n_rows, int n_vocab, long long row_stride, const uint16_t* next, const uint8_t* flags, int n_states,
+                           const int32_t* state_host, const int32_t* hist_host, const int32_t* hist_offset_host, const float* r_host,
+                           const float* freq_host, const float* pres_host, float* y_out, long long y_stride)
+{
+    GTR_REQUIRE(y_out && y_stride >= 0, "mask_rows_fsm: null output or stride %lld", y_stride);
+    FsmPenDefaults d;
+    const PenRows pen = d.rows(n_rows, hist_host, hist_offset_host, r_host, freq_host, pres_host, y_out, y_stride);
+    const FsmRows fsm{next, flags, n_states, state_host, nullptr};
+    return sample_rows_common("mask_rows_fsm", ROWS_FSM, logits, n_rows, n_vocab, row_stride, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, &pen, &fsm);
+}
+
+int gten_hip_sample_rows_fsm(const float* logits, int n_rows, int n_vocab, long long row_stride, const uint16_t* next, const uint8_t* flags, int n_states,
+                             const int32_t* state_host, const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
+                             const int32_t* position_host, const float* top_p_host, const float* min_p_host, const int32_t* hist_host,
+                             const int32_t* hist_offset_host, const float* r_host, const float* freq_host, const float* pres_host, int32_t* out,
+                             int32_t* next_state_out, gten_hip_cut_info* info_out)
+{
+    FsmPenDefaults d;
+    const PenRows pen = d.rows(n_rows, hist_host, hist_offset_host, r_host, freq_host, pres_host, nullptr, 0);
+    const FsmRows fsm{next, flags, n_states, state_host, next_state_out};
+    return sample_rows_common("sample_rows_fsm", ROWS_FSM, logits, n_rows, n_vocab, row_stride, nullptr, 0, top_k_host, temp_host, seed, stream_host,
+                              position_host, top_p_host, min_p_host, out, info_out, &pen, &fsm);
 }

@@ -109,6 +109,11 @@ class GtenHip:
     # include/gten_hip_penalty.h (repetition / frequency / presence penalties on the ids a sequence already holds)
     PENALTY_SYMBOLS = ["gten_hip_decoder_set_penalty", "gten_hip_decoder_penalty_info", "gten_hip_penalize_rows", "gten_hip_sample_rows_pen"]
     PENALTY_HISTORY_MAX = 65535                                  # GTEN_HIP_PENALTY_HISTORY_MAX
+    # include/gten_hip_fsm.h (token automata: stop sequences and masked grammars)
+    FSM_SYMBOLS = ["gten_hip_fsm_check", "gten_hip_decoder_set_fsm", "gten_hip_decoder_set_seq_fsm", "gten_hip_decoder_fsm_info",
+                   "gten_hip_decoder_slot_states", "gten_hip_mask_rows_fsm", "gten_hip_sample_rows_fsm"]
+    FSM_DEAD = 0xFFFF                                            # GTEN_HIP_FSM_DEAD
+    FSM_MAX_BYTES = 1 << 30                                      # GTEN_HIP_FSM_MAX_BYTES
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
@@ -181,6 +186,18 @@ class GtenHip:
         self._penalize_rows = _sig(L, "gten_hip_penalize_rows", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_longlong])
         self._sample_rows_pen = _sig(L, "gten_hip_sample_rows_pen", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, C.c_uint64, vp, vp, vp, vp,
                                                                          vp, vp, vp, vp, vp, vp, vp])
+        self._fsm_check = _sig(L, "gten_hip_fsm_check", ci, [vp, vp, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong)])
+        self._set_fsm = _sig(L, "gten_hip_decoder_set_fsm", ci, [vp, vp, vp, ci])
+        self._set_seq_fsm = _sig(L, "gten_hip_decoder_set_seq_fsm", ci, [vp, ci, ci, ci])
+        self._fsm_info = _sig(L, "gten_hip_decoder_fsm_info", ci, [vp, C.POINTER(ci), vp, vp, C.POINTER(ci), ci, ci, ci, vp, C.POINTER(vp), C.POINTER(vp)])
+        self._slot_states = _sig(L, "gten_hip_decoder_slot_states", ci, [vp, ci, ci, ci, vp])
+        self._slot_start_until = _sig(L, "gten_hip_decoder_slot_start_until", ci, [vp, ci, ci, ci])
+        self._slot_park = _sig(L, "gten_hip_decoder_slot_park", ci, [vp, ci])
+        self._decoder_run = _sig(L, "gten_hip_decoder_run", ci, [vp, ci])
+        self._slot_ids = _sig(L, "gten_hip_decoder_slot_ids", ci, [vp, ci, ci, ci, vp])
+        self._mask_rows_fsm = _sig(L, "gten_hip_mask_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, C.c_longlong])
+        self._sample_rows_fsm = _sig(L, "gten_hip_sample_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
+                                                                         vp, vp, vp, vp, vp, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self.initialised = False
@@ -358,6 +375,113 @@ class GtenHip:
         v = lambda z: z.ctypes.data_as(C.c_void_p)                                                  # noqa: E731
         self._check(self._penalty_info(dec, v(r), v(f), v(p), v(s), v(l), C.byref(on)))
         return r, f, p, s, l, bool(on.value)
+
+    # ---- include/gten_hip_fsm.h
+    def fsm_check(self, nxt, flags, n_vocab, n_states=None):
+        """gten_hip_fsm_check on host tables (no device needed): (code, offending state or -1).  nxt: u16 [S][n_vocab], flags: u8 [S];
+        n_states overrides S (the tables are then not looked at beyond what the early checks need)."""
+        nxt = np.ascontiguousarray(nxt, dtype=np.uint16)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        where = C.c_longlong(-1)
+        code = self._fsm_check(nxt.ctypes.data_as(C.c_void_p) if nxt.size else None, flags.ctypes.data_as(C.c_void_p) if flags.size else None,
+                               int(len(flags) if n_states is None else n_states), int(n_vocab), C.byref(where))
+        return code, int(where.value)
+
+    def fsm_upload(self, nxt, flags):
+        """a pool's tables as device buffers for the row operators: (next DeviceBuffer, flags DeviceBuffer, n_states)"""
+        nxt = np.ascontiguousarray(nxt, dtype=np.uint16)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        dn, df = DeviceBuffer(self, max(nxt.nbytes, 4)), DeviceBuffer(self, max(flags.nbytes, 4))
+        dn.upload(nxt)
+        df.upload(flags)
+        return dn, df, len(flags)
+
+    def mask_rows_fsm(self, logits, n_rows, n_vocab, row_stride, pool, states, hist=None, r=1.0, freq=0.0, pres=0.0):
+        """gten_hip_mask_rows_fsm: the rows the draw would be made from, f32[n_rows][n_vocab].  pool: fsm_upload()'s tuple; states: one
+        per row (-1: not bound); hist None: no penalties, otherwise as in penalize_rows."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (st, stp), (rr, rp), (ff, fp), (pp_, ppp) = per_row(states, np.int32), per_row(r, np.float32), per_row(freq, np.float32), per_row(pres, np.float32)
+        ids, off = self._windows(hist, n_rows) if hist is not None else (np.zeros(0, np.int32), None)
+        out = DeviceBuffer(self, max(4 * n_rows * n_vocab, 4))
+        self._check(self._mask_rows_fsm(logits.ptr, n_rows, n_vocab, row_stride, pool[0].ptr, pool[1].ptr, pool[2], stp,
+                                        ids.ctypes.data_as(C.c_void_p) if len(ids) else None, off.ctypes.data_as(C.c_void_p) if off is not None else None,
+                                        rp, fp, ppp, out.ptr, n_vocab))
+        return out.download(np.float32)[: n_rows * n_vocab].reshape(n_rows, n_vocab).copy()
+
+    def sample_rows_fsm(self, logits, n_rows, n_vocab, row_stride, pool, states, top_k, temp, seed, stream, position, hist=None, r=1.0, freq=0.0,
+                        pres=0.0, top_p=1.0, min_p=0.0, info=False):
+        """gten_hip_sample_rows_fsm: sample_rows_pen (no bias) with row r in state states[r] of the pool.  Returns (ids int32[n_rows],
+        next states int32[n_rows], info or None)."""
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n_rows,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        (a, tpp), (b, mpp), (st, stp) = per_row(top_p, np.float32), per_row(min_p, np.float32), per_row(states, np.int32)
+        (rr, rp), (ff, fp), (pr_, prp) = per_row(r, np.float32), per_row(freq, np.float32), per_row(pres, np.float32)
+        ids, off = self._windows(hist, n_rows) if hist is not None else (np.zeros(0, np.int32), None)
+        out, nxt = DeviceBuffer(self, max(4 * n_rows, 4)), DeviceBuffer(self, max(4 * n_rows, 4))
+        inf = DeviceBuffer(self, max(self.CUT_INFO.itemsize * n_rows, 8)) if info else None
+        self._check(self._sample_rows_fsm(logits.ptr, n_rows, n_vocab, row_stride, pool[0].ptr, pool[1].ptr, pool[2], stp, kp, tp, C.c_uint64(int(seed)),
+                                          sp, pp, tpp, mpp, ids.ctypes.data_as(C.c_void_p) if len(ids) else None,
+                                          off.ctypes.data_as(C.c_void_p) if off is not None else None, rp, fp, prp, out.ptr, nxt.ptr,
+                                          inf.ptr if info else None))
+        got, after = out.download(np.int32)[:n_rows].copy(), nxt.download(np.int32)[:n_rows].copy()
+        return got, after, (inf.download(np.uint8)[: self.CUT_INFO.itemsize * n_rows].view(self.CUT_INFO).copy() if info else None)
+
+    def decoder_set_fsm_rc(self, dec, nxt, flags, n_states=None):
+        """the return code of gten_hip_decoder_set_fsm (nxt None: the pool is dropped)"""
+        if nxt is None:
+            return self._set_fsm(dec, None, None, 0)
+        nxt = np.ascontiguousarray(nxt, dtype=np.uint16)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        return self._set_fsm(dec, nxt.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p), int(len(flags) if n_states is None else n_states))
+
+    def decoder_set_fsm(self, dec, nxt, flags):
+        """gten_hip_decoder_set_fsm on a raw decoder handle: the decoder's automaton pool becomes (nxt u16 [S][n_vocab], flags u8 [S])"""
+        self._check(self.decoder_set_fsm_rc(dec, nxt, flags))
+
+    def decoder_set_seq_fsm_rc(self, dec, seq, state, pos=0):
+        return self._set_seq_fsm(dec, int(seq), int(state), int(pos))
+
+    def decoder_set_seq_fsm(self, dec, seq, state, pos=0):
+        """gten_hip_decoder_set_seq_fsm: the id at position pos of sequence seq is chosen in `state`; -1 unbinds"""
+        self._check(self._set_seq_fsm(dec, int(seq), int(state), int(pos)))
+
+    def decoder_fsm_info(self, dec, n_seq, row_seq=None, row_from=0, row_count=0):
+        """gten_hip_decoder_fsm_info: (n_states, state int32[n_seq], pos int32[n_seq], on, row int32[row_count] or None)"""
+        st, ps = np.zeros(n_seq, np.int32), np.zeros(n_seq, np.int32)
+        S, on = C.c_int(0), C.c_int(0)
+        row = np.zeros(max(row_count, 1), np.int32) if row_seq is not None else None
+        v = lambda z: z.ctypes.data_as(C.c_void_p)                                                  # noqa: E731
+        self._check(self._fsm_info(dec, C.byref(S), v(st), v(ps), C.byref(on), int(row_seq or 0), int(row_from), int(row_count),
+                                   v(row) if row is not None else None, None, None))
+        return S.value, st, ps, bool(on.value), (row[:row_count].copy() if row is not None else None)
+
+    def decoder_slot_states(self, dec, seq, n_from, count):
+        """gten_hip_decoder_slot_states: int32[count], entry i the state the id at position n_from + i is chosen in"""
+        out = np.zeros(max(count, 1), np.int32)
+        self._check(self._slot_states(dec, int(seq), int(n_from), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:count].copy()
+
+    def decoder_slot_start_until(self, dec, seq, n_first, n_last=0):
+        """gten_hip_decoder_slot_start_until: slot seq runs free from step n_first and repeats step n_last once it is there (0: never)"""
+        self._check(self._slot_start_until(dec, int(seq), int(n_first), int(n_last)))
+
+    def decoder_slot_park(self, dec, seq):
+        self._check(self._slot_park(dec, int(seq)))
+
+    def decoder_run(self, dec, steps):
+        """gten_hip_decoder_run: `steps` shared steps of every started slot, free-running"""
+        self._check(self._decoder_run(dec, int(steps)))
+
+    def decoder_slot_ids(self, dec, seq, n_from, count):
+        """gten_hip_decoder_slot_ids: int32[count], the ids of steps [n_from, n_from + count) of slot seq"""
+        out = np.zeros(max(count, 1), np.int32)
+        self._check(self._slot_ids(dec, int(seq), int(n_from), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:count].copy()
 
     def decoder_set_cut(self, dec, seq, top_p, min_p):
         """gten_hip_decoder_set_cut on a raw decoder handle: sequence `seq` draws under (top_p, min_p); (1, 0) clears it"""

@@ -1,14 +1,14 @@
 // generate.h -- choosing the next id, once for every entry point above the C ABI of libgten_hip.so: greedy, top-k sampling
 // (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h) and log-prob records
 // (include/gten_hip_logprobs.h), top-p / min-p cuts (include/gten_hip_nucleus.h) and penalties on
-// repeated ids (include/gten_hip_penalty.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
+// repeated ids (include/gten_hip_penalty.h) and token automata (include/gten_hip_fsm.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
 // compile-time mask says which device entry points the flow may name.
 //
 // Why a mask and not a run-time switch: host/capi.cpp links against a stand-in of include/gten_hip.h alone
 // (tests/test_host_sanitize_cpu.py), host/capi.cpp + host/capi_sample.cpp against that plus the sampler's
 // (tests/test_sampler_cpu.py).  So every flow here is a template on the mask, the stages it does not have are discarded with
 // `if constexpr`, and each flow is instantiated where its stages may be named: mask 0 in host/capi.cpp, kSampled in
-// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, four in host/capi_nucleus.cpp, all five in host/capi_penalty.cpp
+// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, four in host/capi_nucleus.cpp, five in host/capi_penalty.cpp, all six in host/capi_fsm.cpp
 // (and in the command line program, which links against the library itself).  That is the only reason those files are separate.
 #pragma once
 
@@ -20,12 +20,17 @@
 #include "../../include/gten_hip_logprobs.h"
 #include "../../include/gten_hip_nucleus.h"
 #include "../../include/gten_hip_penalty.h"
+#include "../../include/gten_hip_fsm.h"
 
 namespace gten {
 
 // (kPenalty -- include/gten_hip_penalty.h, DESIGN.md §3.14, instantiated in host/capi_penalty.cpp -- requires kSampled: a penalised
 // greedy request takes its first id from the device too)
-enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u };
+// (kFsm -- include/gten_hip_fsm.h, DESIGN.md §3.15, instantiated in host/capi_fsm.cpp -- requires kSampled for the same reason)
+enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u, kFsm = 32u };
+
+// why a prompt's generation ended (kFsm flows report it per item)
+enum : int { kEndedByLength = 0, kEndedByEos = 1, kEndedByFinal = 2 };
 
 // What one prompt or sequence asks for.  The defaults: greedy, no table, no records.
 struct Request {
@@ -40,6 +45,7 @@ struct Request {
     float rep = 1.f, freq = 0.f, pres = 0.f;     // the penalties on ids the sequence already holds ((1, 0, 0): none; they act on greedy too)
     int last_n = 0;                      // ... counted over the last last_n positions (0: all of them) ...
     bool count_prompt = true;            // ... the prompt's included, or only what was generated
+    int fsm_start = -1;                  // the state of the decoder's automaton pool the first new id is chosen in (-1: no automaton)
     bool cuts() const { return top_k > 0 && !(top_p == 1.f && min_p == 0.f); }
     bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     int start(int n_prompt) const { return count_prompt ? 0 : n_prompt; }
@@ -51,6 +57,7 @@ inline bool request_ok(int top_k, float temp) { return top_k >= 0 && (top_k == 0
 inline bool binding_ok(int table, int min_new) { return table >= -1 && table < GTEN_HIP_BIAS_TABLES && min_new >= 0; }
 inline bool asking_ok(int n_top, int n_top_max) { return n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP && n_top <= n_top_max; }
 inline bool cut_ok(float top_p, float min_p) { return std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f && std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f; }
+inline bool fsm_ok(int fsm_start, int table) { return fsm_start >= -1 && fsm_start < GTEN_HIP_FSM_MAX_STATES && !(fsm_start >= 0 && table >= 0); }
 inline bool penalty_ok(float rep, float freq, float pres, int last_n)
 {
     return std::isfinite(rep) && rep >= GTEN_HIP_PENALTY_R_MIN && rep <= GTEN_HIP_PENALTY_R_MAX && std::isfinite(freq) &&
@@ -67,6 +74,14 @@ struct Requests {
     Each<float> top_p{nullptr, 1.f}, min_p{nullptr, 0.f};
     Each<float> rep{nullptr, 1.f}, freq{nullptr, 0.f}, pres{nullptr, 0.f};
     Each<int32_t> last_n{nullptr, 0}, count_prompt{nullptr, 1};
+    Each<int32_t> fsm_start{nullptr, -1};
+    // these requests with a start state per item (null: fsm_all for everybody)
+    Requests bound_to(const int32_t* starts, int fsm_all = -1) const
+    {
+        Requests r = *this;
+        r.fsm_start = {starts, fsm_all};
+        return r;
+    }
     // these requests with a penalty per item (each list may be null: the value for all)
     Requests penalised(const float* rep_, float rep_all, const float* freq_, float freq_all, const float* pres_, float pres_all, const int32_t* last_n_,
                        int last_n_all, const int32_t* count_prompt_, int count_prompt_all) const
@@ -88,13 +103,13 @@ struct Requests {
     Request operator[](int j) const
     {
         return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j],
-                rep[j], freq[j], pres[j], last_n[j], count_prompt[j] != 0};
+                rep[j], freq[j], pres[j], last_n[j], count_prompt[j] != 0, fsm_start[j]};
     }
     bool ok(int n, int n_top_max) const
     {
         for (int j = 0; j < n; j++)
             if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j]) ||
-                !penalty_ok(rep[j], freq[j], pres[j], last_n[j])) return false;
+                !penalty_ok(rep[j], freq[j], pres[j], last_n[j]) || !fsm_ok(fsm_start[j], table[j])) return false;
         return true;
     }
 };
@@ -170,13 +185,49 @@ struct RecordRows {
     }
 };
 
+// What a flow keeps of a decoder's automaton pool on the host (kFsm): the flags, read once -- the pool cannot change while a sequence
+// is bound -- and one device word for the next state gten_hip_sample_rows_fsm returns with a first id (`after`: that state, -1 for a
+// banned id, which only a row whose allowed logits are all -inf yields).
+struct FsmHost {
+    gten_hip_decoder* dec = nullptr;
+    std::vector<uint8_t> flags;
+    int32_t* word = nullptr;             // device
+    int32_t after = -1;
+    explicit FsmHost(gten_hip_decoder* dec_ = nullptr) : dec{dec_} {}
+    FsmHost(const FsmHost&) = delete;
+    ~FsmHost() { if (word) gten_hip_free(word); }
+    int32_t* next_state_dev()
+    {
+        if (!word) GTEN_HIP_OK(gten_hip_malloc((void**)&word, sizeof(int32_t)));
+        return word;
+    }
+    void read_after()
+    {
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&after, word, sizeof(after)));
+        if (after < 0 || after >= GTEN_HIP_FSM_MAX_STATES) after = -1;
+    }
+    bool final(int state)
+    {
+        if (flags.empty()) {
+            const uint8_t* dev = nullptr;
+            int S = 0;
+            GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, &dev));
+            flags.resize((size_t)std::max(S, 1), 0);
+            if (S > 0) GTEN_HIP_OK(gten_hip_memcpy_d2h(flags.data(), dev, (size_t)S));
+        }
+        return state >= 0 && (size_t)state < flags.size() && (flags[(size_t)state] & GTEN_HIP_FSM_FINAL) != 0;
+    }
+};
+
 // The id that will sit at position `pos`, drawn on the device from the logits row lg into id_dev: plain or under the request's
 // table, plus its record into rec_dev when the request asks.  (The only draw from a prompt's row outside the decoder.)
 // A penalising request (kPenalty) draws from the row penalised by the prompt's window of ids[0, pos) -- the window the decoder's
 // first step would read from its own copy of them.
+// A bound request (kFsm) draws in its start state from the row masked by the decoder's pool (gten_hip_sample_rows_fsm: the penalty
+// first, the mask second; no table); fsm->after receives the state the id entered, from the operator itself.
 template <unsigned M>
 void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, FirstRecord* rec_dev,
-                const int32_t* ids = nullptr)
+                const int32_t* ids = nullptr, FsmHost* fsm = nullptr)
 {
     static_assert(M & kSampled, "greedy takes the argmax of the prompt's logits on the host");
     const int32_t k = r.top_k;
@@ -184,8 +235,23 @@ void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_
     bool drawn = false;
     if constexpr ((M & kBiased) != 0)
         if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
+    if constexpr ((M & kFsm) != 0)
+        if (r.fsm_start >= 0) {
+            const uint16_t* next = nullptr;
+            const uint8_t* flags = nullptr;
+            int S = 0;
+            GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, &next, &flags));
+            const bool pen = (M & kPenalty) != 0 && r.penalises();
+            const int32_t lo = pen ? std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos) : pos;
+            const int32_t off[2] = {0, pos - lo};
+            const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
+            GTEN_HIP_OK(gten_hip_sample_rows_fsm(lg, 1, n_vocab, 0, next, flags, S, &r.fsm_start, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p,
+                                                 pen ? ids + lo : nullptr, pen ? off : nullptr, &r.rep, &r.freq, &r.pres, id_dev, fsm ? fsm->next_state_dev() : nullptr, nullptr));
+            if (fsm) fsm->read_after();
+            drawn = true;
+        }
     if constexpr ((M & kPenalty) != 0)
-        if (r.penalises()) {
+        if (r.penalises() && !drawn) {
             const int32_t lo = std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos);
             const int32_t off[2] = {0, pos - lo};
             const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
@@ -206,13 +272,21 @@ void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_
         if (r.n_top >= 0) GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n_vocab, n_vocab, id_dev, r.n_top, &rec_dev->logprob, rec_dev->top_id, rec_dev->top_lp));
 }
 
+// the state sequence q's id at position `pos` is chosen in, as the steps left it
+inline int fsm_state_at(gten_hip_decoder* dec, int q, int pos)
+{
+    int32_t s = -1;
+    GTEN_HIP_OK(gten_hip_decoder_slot_states(dec, q, pos, 1, &s));
+    return s;
+}
+
 // Requests on a decoder's slots [0, n_slots), taken back when the scope ends: whatever way a flow is left, every kind of request
 // it has set is cleared on every slot -- the decoder's later steps are greedy, unbound and record nothing.
 template <unsigned M>
 struct SlotRequests {
     gten_hip_decoder* dec;
     int n_slots;
-    bool bound = false, sampling = false;
+    bool bound = false, sampling = false, fsm_bound = false;
     SlotRequests(gten_hip_decoder* dec_, int n_slots_) : dec{dec_}, n_slots{n_slots_} {}
     SlotRequests(const SlotRequests&) = delete;
     ~SlotRequests() { clear(); }
@@ -221,6 +295,17 @@ struct SlotRequests {
     {
         (void)q; (void)r; (void)n_prompt;
         if constexpr ((M & (kBiased | kLogprobs | kNucleus | kPenalty)) != 0) bound = true;
+        // (a slot that carried a bound prompt is unbound before a table may be set on it: the two do not compose)
+        if constexpr ((M & kFsm) != 0) {
+            if (fsm_bound)
+                if (const int rc = gten_hip_decoder_set_seq_fsm(dec, q, -1, 0)) return rc;
+            // (a start state outside the decoder's pool is refused here, before any work, in the setter's own words)
+            if (r.fsm_start >= 0) {
+                int S = 0;
+                if (const int rc = gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr)) return rc;
+                if (r.fsm_start >= S) return gten_hip_decoder_set_seq_fsm(dec, q, r.fsm_start, 1);
+            }
+        }
         if constexpr ((M & kBiased) != 0)
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
         if constexpr ((M & kLogprobs) != 0)
@@ -232,6 +317,17 @@ struct SlotRequests {
             const bool on = r.penalises();
             if (const int rc = gten_hip_decoder_set_penalty(dec, q, on ? r.rep : 1.f, on ? r.freq : 0.f, on ? r.pres : 0.f, on ? r.start(n_prompt) : 0,
                                                             on ? r.last_n : 0)) return rc;
+        }
+        return 0;
+    }
+    // "the id at position pos of slot q is chosen in `state`" for the decode steps that follow (state < 0: not bound)
+    int fsm(int q, int state, int pos)
+    {
+        (void)q; (void)state; (void)pos;
+        if constexpr ((M & kFsm) != 0) {
+            if (state < 0) return fsm_bound ? gten_hip_decoder_set_seq_fsm(dec, q, -1, 0) : 0;
+            fsm_bound = true;
+            return gten_hip_decoder_set_seq_fsm(dec, q, state, pos);
         }
         return 0;
     }
@@ -264,7 +360,10 @@ struct SlotRequests {
         if constexpr ((M & kPenalty) != 0)
             for (int q = 0; bound && q < n_slots; q++)
                 if (const int r = gten_hip_decoder_set_penalty(dec, q, 1.f, 0.f, 0.f, 0, 0)) rc = r;
-        bound = sampling = false;
+        if constexpr ((M & kFsm) != 0)
+            for (int q = 0; fsm_bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_seq_fsm(dec, q, -1, 0)) rc = r;
+        bound = sampling = fsm_bound = false;
         return rc;
     }
 };
@@ -276,9 +375,13 @@ struct SlotRequests {
 // receives the new ids' records at their positions.
 // Returns the number of ids in `tokens`; -1 when the decoder refuses a request (gten_hip_last_error).
 template <unsigned M>
-int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, const Request& r = {}, const RecordRows& rows = {})
+int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, const Request& r = {}, const RecordRows& rows = {},
+             int* ended_by = nullptr, int max_ctx = 0)
 {
     const int n_prompt = (int)tokens.size();
+    int ended = kEndedByLength, state = -1;
+    struct Report { int* out; const int& v; ~Report() { if (out) *out = v; } } report{ended_by, ended};
+    (void)state;
     auto blank = [&]() {
         if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)std::max(n_predict, n_prompt));
     };
@@ -286,6 +389,7 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = model.decoder_handle();
     SlotRequests<M> slot(dec, 1);
+    FsmHost fh(dec);
     if (slot.bind(0, r, n_prompt) != 0) return -1;
     blank();
     {
@@ -301,21 +405,32 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
             Tensor id({1}, kInt32);
             FirstRecords rec;
             if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
-            draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev, tokens.data());
+            draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev, tokens.data(), &fh);
+            state = fh.after;
             GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
             if constexpr ((M & kLogprobs) != 0)
                 if (first != eos && r.n_top >= 0) rows.store_first((size_t)n_prompt, r.n_top, rec.dev);
         }
-        if (first == eos) return n_prompt;
+        if (first == eos) { ended = kEndedByEos; return n_prompt; }
         tokens.push_back(first);
     }
     const int n_first = n_prompt + 1;
+    // (a first id that is itself final: the prompt plus that id)
+    if constexpr ((M & kFsm) != 0)
+        if (r.fsm_start >= 0 && fh.final(state)) { ended = kEndedByFinal; return n_first; }
     const int max_new = n_predict - n_first;
     if (max_new <= 0) return n_first;
     std::vector<int32_t> out((size_t)max_new);
     if (slot.sample(0, r) != 0) return -1;
+    if constexpr ((M & kFsm) != 0)
+        if (r.fsm_start >= 0 && slot.fsm(0, state, n_first) != 0) return -1;
     const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
+    // (fewer ids than the steps that could run: an eos.  The context bounds them too; a caller that does not say how long it is
+    //  keeps max_tokens inside it)
+    if (got < (max_ctx > 0 ? std::min(max_new, max_ctx - n_first + 1) : max_new)) ended = kEndedByEos;
+    if constexpr ((M & kFsm) != 0)
+        if (r.fsm_start >= 0 && got > 0 && fh.final(fsm_state_at(dec, 0, n_first + got))) ended = kEndedByFinal;
     if constexpr ((M & kLogprobs) != 0)
         if (r.n_top >= 0 && rows.store_decoded(dec, 0, n_first, got, r.n_top) != 0) return -1;
     return slot.clear() ? -1 : (int)tokens.size();
@@ -323,27 +438,28 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
 
 // generate() on a caller's array: `tokens` holds n_prompt ids and has room for max(max_tokens, n_prompt)
 template <unsigned M>
-int generate_in_place(TinyLlama& model, int32_t* tokens, int n_prompt, int max_tokens, int eos, const Request& r = {}, const RecordRows& rows = {})
+int generate_in_place(TinyLlama& model, int32_t* tokens, int n_prompt, int max_tokens, int eos, const Request& r = {}, const RecordRows& rows = {},
+                      int* ended_by = nullptr, int max_ctx = 0)
 {
     std::vector<int32_t> t(tokens, tokens + n_prompt);
     t.reserve((size_t)std::max(max_tokens, n_prompt));
-    const int total = generate<M>(model, t, max_tokens, eos, r, rows);
+    const int total = generate<M>(model, t, max_tokens, eos, r, rows, ended_by, max_ctx);
     if (total > 0) std::memcpy(tokens, t.data(), (size_t)total * sizeof(int32_t));
     return total;
 }
 
 // the first id of `prompt` processed onto cache set `set` of a batch: TinyLlamaBatch::prefill's argmax (mask 0) or draw_first's
 template <unsigned M>
-int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, const Request& r, FirstRecord* rec_dev)
+int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, const Request& r, FirstRecord* rec_dev, FsmHost* fsm = nullptr)
 {
     if constexpr (M == 0) {
-        (void)r; (void)rec_dev;
+        (void)r; (void)rec_dev; (void)fsm;
         return b.prefill(set, prompt);
     } else {
         gten_hip_decoder* dec = nullptr;
-        if constexpr ((M & (kBiased | kNucleus)) != 0) dec = b.decoder_handle();
+        if constexpr ((M & (kBiased | kNucleus | kFsm)) != 0) dec = b.decoder_handle();
         return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) {
-            draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev, prompt.data());
+            draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev, prompt.data(), fsm);
         });
     }
 }
@@ -355,7 +471,7 @@ int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, con
 // 0; -1: bad arguments (nothing was touched); otherwise the code of the decoder call that refused.
 template <unsigned M>
 int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
-                   const Requests& reqs, int32_t* out, int32_t* n_total, const RecordRows& rows = {})
+                   const Requests& reqs, int32_t* out, int32_t* n_total, const RecordRows& rows = {}, int32_t* ended_by = nullptr)
 {
     const int S = batch.n_seq();
     for (int q = 0; q < S; q++)
@@ -365,9 +481,11 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = batch.decoder_handle();
     SlotRequests<M> slots(dec, S);
+    FsmHost fh(dec);
     for (int q = 0; q < S; q++)
         if (const int rc = slots.bind(q, reqs[q], n_prompt[q])) return rc;
-    std::vector<int32_t> first((size_t)S);
+    std::vector<int32_t> first((size_t)S), state((size_t)S, -1);
+    std::vector<char> final_first((size_t)S, 0);                  // (kFsm) the first id entered a final state: the prompt plus that id
     FirstRecords rec;
     if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
     for (int q = 0; q < S; q++) {
@@ -375,7 +493,11 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
         int32_t* row = out + (size_t)q * max_tokens;
         std::memcpy(row, prompts + (size_t)q * max_prompt, (size_t)P * sizeof(int32_t));
         const Request r = reqs[q];
-        first[(size_t)q] = first_id<M>(batch, q, std::vector<int32_t>(row, row + P), r, rec.dev);
+        first[(size_t)q] = first_id<M>(batch, q, std::vector<int32_t>(row, row + P), r, rec.dev, &fh);
+        if constexpr ((M & kFsm) != 0) {
+            state[(size_t)q] = fh.after;
+            final_first[(size_t)q] = r.fsm_start >= 0 && first[(size_t)q] != eos && fh.final(state[(size_t)q]);
+        }
         if constexpr ((M & kLogprobs) != 0)
             if (r.n_top >= 0 && first[(size_t)q] != eos) rows.from((size_t)q * max_tokens).store_first((size_t)P, r.n_top, rec.dev);
     }
@@ -388,9 +510,12 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
         n_first[(size_t)q] = P + 1;
         batch.decode_set_tokens(q, row, 0, P + 1);
         if (const int rc = slots.sample(q, reqs[q])) return rc;
+        if constexpr ((M & kFsm) != 0)
+            if (reqs[q].fsm_start >= 0 && first[(size_t)q] != eos && !final_first[(size_t)q])
+                if (const int rc = slots.fsm(q, state[(size_t)q], P + 1)) return rc;
         // this sequence's own room; none when its first id is already eos (the sequence is then parked from the start instead of
         // being decoded for the longest sequence's length)
-        room[(size_t)q] = (first[(size_t)q] == eos) ? 0 : max_tokens - (P + 1);
+        room[(size_t)q] = (first[(size_t)q] == eos || final_first[(size_t)q]) ? 0 : max_tokens - (P + 1);
         max_new = std::max(max_new, room[(size_t)q]);
     }
     std::vector<int32_t> gen((size_t)S * (size_t)std::max(max_new, 1));
@@ -399,10 +524,15 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
     for (int q = 0; q < S; q++) {
         int32_t* row = out + (size_t)q * max_tokens;
         const int total = n_first[(size_t)q];
-        if (row[total - 1] == eos) { n_total[q] = total - 1; continue; }
+        if (ended_by) ended_by[q] = kEndedByLength;
+        if (row[total - 1] == eos) { n_total[q] = total - 1; if (ended_by) ended_by[q] = kEndedByEos; continue; }
+        if (final_first[(size_t)q]) { n_total[q] = total; if (ended_by) ended_by[q] = kEndedByFinal; continue; }
         const int take = std::min(n_out[(size_t)q], max_tokens - total);
         std::memcpy(row + total, gen.data() + (size_t)q * max_new, (size_t)take * sizeof(int32_t));
         n_total[q] = total + take;
+        if (ended_by && take < std::min(room[(size_t)q], max_ctx - total + 1)) ended_by[q] = kEndedByEos;
+        if constexpr ((M & kFsm) != 0)
+            if (ended_by && reqs[q].fsm_start >= 0 && take > 0 && fh.final(fsm_state_at(dec, q, total + take))) ended_by[q] = kEndedByFinal;
         if constexpr ((M & kLogprobs) != 0)
             if (const int n_top = reqs[q].n_top; n_top >= 0)
                 if (const int rc = rows.from((size_t)q * max_tokens).store_decoded(dec, q, total, take, n_top)) return rc;
@@ -418,13 +548,25 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
 template <unsigned M>
 struct ServePolicy {
     static constexpr bool kLogprobs = (M & gten::kLogprobs) != 0;
+    static constexpr bool kFsm = (M & gten::kFsm) != 0;
+    // (kFsm) per prompt: the state its next id is chosen in, as the host last read it (-1: not bound), and whether it entered a final one
+    std::vector<int32_t> fsm_state;
+    std::vector<char> fsm_ended;
+    std::vector<int32_t> fsm_buf;
+    FsmHost fh;                          // the pool's flags and the operator's next-state word
+    bool final_state(int state) { return fh.final(state); }
     Requests reqs;
     RecordRows rows;
     int row_len;
     SlotRequests<M> slots;
     FirstRecords rec;
-    ServePolicy(gten_hip_decoder* dec, int n_slots, const Requests& reqs_, const RecordRows& rows_ = {}, int row_len_ = 0)
-        : reqs{reqs_}, rows{rows_}, row_len{row_len_}, slots(dec, n_slots) {}
+    int reqs_n = 0;                      // (kFsm) the number of prompts
+    ServePolicy(gten_hip_decoder* dec, int n_slots, const Requests& reqs_, const RecordRows& rows_ = {}, int row_len_ = 0, int n_prompts = 0)
+        : reqs{reqs_}, rows{rows_}, row_len{row_len_}, slots(dec, n_slots), reqs_n{n_prompts}
+    {
+        fh.dec = dec;
+        if constexpr (kFsm) { fsm_state.assign((size_t)n_prompts, -1); fsm_ended.assign((size_t)n_prompts, 0); }
+    }
     RecordRows rows_of(int j) const { return rows.from((size_t)j * (size_t)row_len); }
     FirstRecord* rec_of(int k) const { return kLogprobs ? rec.dev + k : nullptr; }
     void store_first(int k, int j, int pos)
@@ -434,9 +576,40 @@ struct ServePolicy {
     int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
     {
         if constexpr (kLogprobs) rec.ensure(1);
-        const int id = first_id<M>(b, c, row, reqs[j], rec.dev);
+        const int id = first_id<M>(b, c, row, reqs[j], rec.dev, &fh);
         if constexpr (kLogprobs) store_first(0, j, (int)row.size());
+        if constexpr (kFsm) note_first(j, fh.after);
         return id;
+    }
+    // (kFsm) prompt j's first id entered state `after`
+    void note_first(int j, int32_t after)
+    {
+        if (fsm_state.empty()) { fsm_state.assign((size_t)reqs_n, -1); fsm_ended.assign((size_t)reqs_n, 0); }
+        fsm_state[(size_t)j] = reqs.fsm_start[j] >= 0 ? after : -1;
+    }
+    // (kFsm) whether the id just stored for prompt j -- its first -- entered a final state: the prompt ends there and keeps the id
+    bool ended_first(int j)
+    {
+        if (reqs.fsm_start[j] < 0 || !final_state(fsm_state[(size_t)j])) return false;
+        fsm_ended[(size_t)j] = 1;
+        return true;
+    }
+    // (kFsm) prompt j goes on in slot q with its next id at position pos: the binding travels with the prompt, at the state the host read
+    void bind_state(int q, int j, int pos) { GTEN_HIP_OK(slots.fsm(q, reqs.fsm_start[j] >= 0 ? fsm_state[(size_t)j] : -1, pos)); }
+    // (kFsm) the states that slot q's `count` ids from position `from` on entered (null: prompt j is not bound)
+    const int32_t* states(int q, int j, int from, int count)
+    {
+        if (reqs.fsm_start[j] < 0 || fsm_state[(size_t)j] < 0 || count <= 0) return nullptr;
+        fsm_buf.resize((size_t)count);
+        GTEN_HIP_OK(gten_hip_decoder_slot_states(slots.dec, q, from + 1, count, fsm_buf.data()));
+        fsm_state[(size_t)j] = fsm_buf[(size_t)count - 1];
+        return fsm_buf.data();
+    }
+    bool enters_final(int j, int32_t state)
+    {
+        if (!final_state(state)) return false;
+        fsm_ended[(size_t)j] = 1;
+        return true;
     }
     void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
               std::vector<int>* first)
@@ -448,7 +621,8 @@ struct ServePolicy {
             if constexpr (kLogprobs) rec.ensure((int)sets.size());
             std::vector<float*> lo((size_t)sets.size(), nullptr);
             b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
-                draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data());
+                draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data(), &fh);
+                if constexpr (kFsm) note_first(js[(size_t)k], fh.after);
             });
             if constexpr (kLogprobs)
                 for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
@@ -475,7 +649,7 @@ struct ServePolicy {
 template <unsigned M>
 int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
                 int eos, int slice, int max_new, const int32_t* max_new_each, int32_t* out, int32_t* n_total, double* stats, int n_stats,
-                const Requests& reqs = {}, const RecordRows& rows = {})
+                const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr)
 {
     if (n_prompts <= 0 || max_tokens <= 0 || slice <= 0) return -1;
     for (int j = 0; j < n_prompts; j++)
@@ -508,14 +682,33 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
                 if (const int rc = gten_hip_decoder_set_penalty(dec, 0, reqs[j].rep, reqs[j].freq, reqs[j].pres, 0, reqs[j].last_n)) return rc;
                 if (const int rc = gten_hip_decoder_set_penalty(dec, 0, 1.f, 0.f, 0.f, 0, 0)) return rc;
             }
+    if constexpr ((M & kFsm) != 0) {
+        // (... and every start state is one of the pool's: a refusal comes before the queue starts)
+        int S = 0;
+        if (const int rc = gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr)) return rc;
+        for (int j = 0, bound = 0; j < n_prompts; j++)
+            if (const int start = reqs[j].fsm_start; start >= 0 && (!bound || start >= S)) {
+                if (const int rc = gten_hip_decoder_set_seq_fsm(dec, 0, start, 1)) return rc;
+                if (const int rc = gten_hip_decoder_set_seq_fsm(dec, 0, -1, 0)) return rc;
+                bound = 1;
+            }
+    }
     std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
     for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
-    ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len);
+    ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len, n_prompts);
     const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, pick);
     for (int j = 0; j < n_prompts; j++) {
         const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, n_prompt[j]));
         std::memcpy(out + (size_t)j * row_len, res[(size_t)j].data(), (size_t)take * sizeof(int32_t));
         n_total[j] = take;
+        if (ended_by) {
+            // (shorter than its own limit: an eos, unless the policy saw a final state)
+            const int P = n_prompt[j], mn = Each<int32_t>{max_new_each, max_new}[j];
+            const int limit = std::min(std::min(max_tokens, max_ctx), mn > 0 ? P + mn : max_ctx);
+            ended_by[j] = take < limit && P < limit ? kEndedByEos : kEndedByLength;
+            if constexpr ((M & kFsm) != 0)
+                if (pick.fsm_ended[(size_t)j]) ended_by[j] = kEndedByFinal;
+        }
         // (a first id that was the eos is not stored: neither is its record)
         if constexpr ((M & kLogprobs) != 0) rows.from((size_t)j * row_len + (size_t)take).blank((size_t)(row_len - take));
     }

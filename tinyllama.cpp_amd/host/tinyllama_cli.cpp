@@ -7,7 +7,8 @@
 // (include/gten_host_score.h) instead of generating; --ban / --allow / --min-new constrain the generated ids through bias table 0
 // of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
 // most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h);
-// --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h).
+// --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h);
+// --stop / --choice end the answer at, or hold it to, id sequences through a token automaton on the device (include/gten_hip_fsm.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <string_view>
 #include <vector>
 
+#include "fsm_build.h"
 #include "generate.h"
 #include "tokenizer.h"
 
@@ -59,6 +61,10 @@ Optional args.
 --frequency-penalty F : subtract F from the logit of such an id once per occurrence. |F| must be lte 100. [default=0: off].
 --presence-penalty P : subtract P from the logit of such an id once. |P| must be lte 100. [default=0: off].
 --repeat-last-n N : the penalties look at the last N ids only; N must be gte 0. [default=0: at all of them]
+--stop ID[,ID...] : the answer ends as soon as it ends in this id sequence (which it keeps). Repeatable. Works with -greedy too.
+           Not with --choice, --ban, --allow or --score.
+--choice ID[,ID...] : the answer is exactly one of the id sequences given this way. Repeatable; none may be a prefix of another.
+           Works with -greedy too. Not with --stop, --ban, --allow or --score.
 )";
 
 struct Options {
@@ -79,6 +85,8 @@ struct Options {
     bool pen_given = false;
     bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     bool constrained() const { return !ban.empty() || !allow.empty(); }
+    std::vector<std::vector<int32_t>> stop, choice;      // --stop / --choice, one id sequence per flag
+    bool automaton() const { return !stop.empty() || !choice.empty(); }
 };
 
 static void emit(const Options& o, Tokenizer& tok, int prev, int id)
@@ -88,7 +96,7 @@ static void emit(const Options& o, Tokenizer& tok, int prev, int id)
 }
 
 // "ID[,ID...]" -> ids in [0, n_vocab), none twice; false (with a message) otherwise
-static bool parse_id_list(const char* what, const std::string& text, int n_vocab, std::vector<int32_t>* out)
+static bool parse_id_list(const char* what, const std::string& text, int n_vocab, std::vector<int32_t>* out, bool unique = true)
 {
     out->clear();
     size_t pos = 0;
@@ -100,7 +108,7 @@ static bool parse_id_list(const char* what, const std::string& text, int n_vocab
         try { v = std::stol(item, &used); } catch (...) { used = 0; }
         if (item.empty() || used != item.size()) { std::cerr << "Invalid " << what << " value: ids are integers separated by commas.\n"; return false; }
         if (v < 0 || v >= n_vocab) { std::cerr << what << " ids must be gte 0 and lt " << n_vocab << ".\n"; return false; }
-        if (std::find(out->begin(), out->end(), (int32_t)v) != out->end()) { std::cerr << what << " lists id " << v << " twice.\n"; return false; }
+        if (unique && std::find(out->begin(), out->end(), (int32_t)v) != out->end()) { std::cerr << what << " lists id " << v << " twice.\n"; return false; }
         out->push_back((int32_t)v);
         pos = comma + 1;
     }
@@ -124,12 +132,34 @@ static void set_constraint(const Options& o, TinyLlama& model)
     }
 }
 
+// --stop / --choice as the pool of the model's decoder (host/fsm_build.h); the start state the answers are bound to
+static int set_automaton(const Options& o, TinyLlama& model, int n_vocab)
+{
+    const std::vector<std::vector<int32_t>>& lists = o.stop.empty() ? o.choice : o.stop;
+    std::vector<int32_t> ids, offsets{0};
+    for (const auto& l : lists) {
+        ids.insert(ids.end(), l.begin(), l.end());
+        offsets.push_back((int32_t)ids.size());
+    }
+    FsmPool pool(n_vocab);
+    const int start = o.stop.empty() ? pool.add_choices(ids.data(), offsets.data(), (int)lists.size()) : pool.add_stop(ids.data(), offsets.data(), (int)lists.size());
+    if (start < 0) {
+        std::cerr << (start == FsmPool::kPrefix ? "error: a --choice is a prefix of another.\n" : "error: the id sequences do not fit an automaton pool.\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (gten_hip_decoder_set_fsm(model.decoder_handle(), pool.next(), pool.flags(), pool.n_states()) != 0) {
+        std::cerr << "error: " << gten_hip_last_error() << "\n";
+        std::exit(EXIT_FAILURE);
+    }
+    return start;
+}
+
 // One answer (host/generate.h).  Plain greedy: the prompt as in the reference, every later id from the device-side argmax, nothing set
 // on the decoder.  Top-k (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler,
 // keyed by (seed, stream = the chat turn, position).  --ban / --allow: either mode under table 0 (top_k 0: greedy over the biased
 // logits).  --logprobs: after the ids, one record line per generated id.  --top-p / --min-p: the draw under a cut.  The flow names only
 // the stages the options ask for.
-static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t* turn)
+static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t* turn, int fsm_start = -1)
 {
     std::vector<int> enc = tok.encode(prompt);
     std::vector<int32_t> tokens(enc.begin(), enc.end());
@@ -137,12 +167,21 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
     std::vector<float> logprob, top_lp;
     std::vector<int32_t> top_id;
     int rc = 0;
-    if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises()) {
+    if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises() && fsm_start < 0) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
     } else {
         const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p,
-                        o.rep, o.freq, o.pres, o.last_n, true};
-        if (o.penalises()) {
+                        o.rep, o.freq, o.pres, o.last_n, true, fsm_start};
+        if (fsm_start >= 0) {
+            RecordRows rows;
+            if (o.logprobs >= 0) {
+                logprob.resize(width);
+                top_id.resize(width * W);
+                top_lp.resize(width * W);
+                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
+            }
+            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm>(model, tokens, o.n_predict, tok.eos, r, rows);
+        } else if (o.penalises()) {
             RecordRows rows;
             if (o.logprobs >= 0) {
                 logprob.resize(width);
@@ -322,6 +361,11 @@ int main(int argc, char const* argv[])
             if (v < 0) { std::cerr << "repeat-last-n must be gte 0.\n"; return -1; }
             o.last_n = v;
             o.pen_given = true;
+        } else if (arg == "--stop" || arg == "--choice") {
+            const bool is_stop = arg == "--stop";
+            std::vector<int32_t> list;
+            if (!parse_id_list(is_stop ? "stop" : "choice", value(is_stop ? "stop" : "choice"), 32003, &list, false)) return -1;
+            (is_stop ? o.stop : o.choice).push_back(list);
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
@@ -330,6 +374,15 @@ int main(int argc, char const* argv[])
     if (o.cut_given && o.greedy) { std::cerr << "top-p and min-p need top-k sampling: not with -greedy.\n"; return -1; }
     if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
     if (o.pen_given && !o.score_path.empty()) { std::cerr << "the repeat, frequency and presence penalties do not apply to --score.\n"; return -1; }
+    if (!o.stop.empty() && !o.choice.empty()) { std::cerr << "--stop and --choice do not combine: an answer follows one automaton.\n"; return -1; }
+    if (o.automaton() && o.constrained()) { std::cerr << "--stop and --choice do not combine with --ban or --allow.\n"; return -1; }
+    if (o.automaton() && !o.score_path.empty()) { std::cerr << "--stop and --choice do not apply to --score.\n"; return -1; }
+    for (size_t a = 0; a < o.choice.size(); a++)
+        for (size_t b = 0; b < o.choice.size(); b++)
+            if (a != b && o.choice[a].size() <= o.choice[b].size() && std::equal(o.choice[a].begin(), o.choice[a].end(), o.choice[b].begin())) {
+                std::cerr << "a --choice is a prefix of another.\n";
+                return -1;
+            }
     if (o.min_new > 0 && !o.constrained()) { std::cerr << "min-new needs --ban or --allow.\n"; return -1; }
     if (!o.allow.empty() && std::all_of(o.allow.begin(), o.allow.end(), [&](int32_t id) { return std::find(o.ban.begin(), o.ban.end(), id) != o.ban.end(); })) {
         std::cerr << "--ban bans every id of --allow.\n";
@@ -361,8 +414,9 @@ int main(int argc, char const* argv[])
         seed = ((uint64_t)rd() << 32) | (uint64_t)rd();
     }
     if (o.constrained()) set_constraint(o, model);
+    const int fsm_start = o.automaton() ? set_automaton(o, model, 32003) : -1;
     uint32_t turn = 0;
-    auto answer = [&](const std::string& prompt) { run(o, prompt, model, tokenizer, seed, &turn); };
+    auto answer = [&](const std::string& prompt) { run(o, prompt, model, tokenizer, seed, &turn, fsm_start); };
     if (o.prompt.empty()) {
         std::cout << "Chat interface. Write your prompt and press enter to submit. Enter q or press ctrl+c to quit.\n";
         std::string prompt;

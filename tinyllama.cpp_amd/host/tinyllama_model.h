@@ -987,6 +987,8 @@ public:
     struct ServeStats { int64_t prompt_tokens = 0, new_tokens = 0, steps = 0, admissions = 0, lane_steps = 0, moved = 0; int lane_rows = 0; double prefill_s = 0.0, decode_s = 0.0; };
     // How the ids are picked is `pick`'s business (host/generate.h, ServePolicy): the first id of a prompt processed onto a cache
     // set (first / many), the requests of the slot that takes it (apply), its log-prob records (collect), everything off again (clear).
+    // With Pick::kFsm a prompt may be bound to a token automaton (include/gten_hip_fsm.h): the id that enters a final state ends it as
+    // an eos does but is kept (ended_first / states / enters_final), and its binding is set again wherever it goes on (bind_state).
     // (max_new[j] > 0 additionally bounds the new ids of prompt j)
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
@@ -1079,6 +1081,8 @@ public:
                 if (best_i == eos) continue;                               // ended at once: the set takes the next prompt
                 row.push_back(best_i);
                 st.new_tokens++;
+                if constexpr (Pick::kFsm)
+                    if (pick.ended_first(j)) continue;                     // its first id entered a final state: kept, and the set stays free
                 if ((int)row.size() >= limit) continue;
                 pool.pop_back();
                 ready.push_back(Ready{j, c, (int)row.size(), limit - 1});
@@ -1131,7 +1135,9 @@ public:
                 if (first[k] != eos) {                                       // (eos: ended at once, the set stays free)
                     row.push_back(first[k]);
                     st.new_tokens++;
-                    if ((int)row.size() < limits[k]) { ready.push_back(Ready{js[k], sets[k], (int)row.size(), limits[k] - 1}); taken = true; }
+                    bool ended = false;
+                    if constexpr (Pick::kFsm) ended = pick.ended_first(js[k]);
+                    if (!ended && (int)row.size() < limits[k]) { ready.push_back(Ready{js[k], sets[k], (int)row.size(), limits[k] - 1}); taken = true; }
                 }
                 if (!taken) unused.push_back(sets[k]);
             }
@@ -1189,6 +1195,7 @@ public:
                     // (all joining slots in one call below: their ids, step words and cache-table rows go up behind each other, one wait)
                     ap_seq.push_back(q); ap_first.push_back(r.cur); ap_last.push_back(r.last); ap_tok.push_back(row.data());
                     pick.apply(q, r.j, (int)prompts[(size_t)r.j].size());                                  // (travels with the prompt: also when a sequence moves in the tail)
+                    if constexpr (Pick::kFsm) pick.bind_state(q, r.j, r.cur);                              // (... at its current position, with the state the host read)
                     lp_from[(size_t)q] = r.cur;
                     live[(size_t)q] = 1; n_live++;
                 }
@@ -1227,9 +1234,15 @@ public:
                 const int32_t* ids = all_ids.data() + (size_t)q * (size_t)cnt;
                 std::vector<int32_t>& row = (*out)[(size_t)job[(size_t)q]];
                 bool stop = false;
+                const int32_t* entered = nullptr;                                                      // (Pick::kFsm) the state each id entered
+                if constexpr (Pick::kFsm) entered = pick.states(q, job[(size_t)q], cur[(size_t)q], got);
                 for (int i = 0; i < got && !stop; i++) {
                     if (ids[(size_t)i] == eos) stop = true;
-                    else { row.push_back(ids[(size_t)i]); st.new_tokens++; }
+                    else {
+                        row.push_back(ids[(size_t)i]); st.new_tokens++;
+                        if constexpr (Pick::kFsm)
+                            if (entered && pick.enters_final(job[(size_t)q], entered[(size_t)i])) stop = true;
+                    }
                 }
                 cur[(size_t)q] += got;
                 if (stop || cur[(size_t)q] > last[(size_t)q]) {

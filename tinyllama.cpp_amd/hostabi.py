@@ -64,6 +64,11 @@ class GtenHost:
     # include/gten_host_penalty.h (repetition / frequency / presence penalties, host/capi_penalty.cpp)
     PENALTY_SYMBOLS = ["gten_host_model_set_penalty", "gten_host_batch_set_penalty", "gten_host_model_penalty_info", "gten_host_batch_penalty_info",
                        "gten_host_model_generate_penalized", "gten_host_batch_generate_penalized", "gten_host_batch_serve_penalized"]
+    # include/gten_host_fsm.h (token automata: builders, pools and bound generation, host/capi_fsm.cpp)
+    FSM_SYMBOLS = ["gten_host_fsm_create", "gten_host_fsm_free", "gten_host_fsm_add_stop", "gten_host_fsm_add_choices", "gten_host_fsm_add_table",
+                   "gten_host_fsm_n_states", "gten_host_fsm_tables", "gten_host_model_set_fsm", "gten_host_batch_set_fsm", "gten_host_model_fsm_info",
+                   "gten_host_batch_fsm_info", "gten_host_model_set_seq_fsm", "gten_host_batch_set_seq_fsm", "gten_host_model_fsm_states",
+                   "gten_host_batch_fsm_states", "gten_host_batch_fsm_decoder", "gten_host_model_generate_fsm", "gten_host_batch_generate_fsm", "gten_host_batch_serve_fsm"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -134,6 +139,29 @@ class GtenHost:
                                                                             vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen])
         self._bserve_pen = _sig(L, "gten_host_batch_serve_penalized", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                            C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen])
+        self._fsm_create = _sig(L, "gten_host_fsm_create", vp, [ci])
+        self._fsm_free = _sig(L, "gten_host_fsm_free", None, [vp])
+        self._fsm_add_stop = _sig(L, "gten_host_fsm_add_stop", ci, [vp, vp, vp, ci])
+        self._fsm_add_choices = _sig(L, "gten_host_fsm_add_choices", ci, [vp, vp, vp, ci])
+        self._fsm_add_table = _sig(L, "gten_host_fsm_add_table", ci, [vp, vp, vp, ci])
+        self._fsm_n_states = _sig(L, "gten_host_fsm_n_states", ci, [vp])
+        self._fsm_tables = _sig(L, "gten_host_fsm_tables", ci, [vp, C.POINTER(vp), C.POINTER(vp)])
+        self._m_set_fsm = _sig(L, "gten_host_model_set_fsm", ci, [vp, vp])
+        self._b_set_fsm = _sig(L, "gten_host_batch_set_fsm", ci, [vp, vp])
+        self._m_fsm_info = _sig(L, "gten_host_model_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
+        self._b_fsm_info = _sig(L, "gten_host_batch_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
+        self._m_set_seq_fsm = _sig(L, "gten_host_model_set_seq_fsm", ci, [vp, ci, ci])
+        self._b_set_seq_fsm = _sig(L, "gten_host_batch_set_seq_fsm", ci, [vp, ci, ci, ci])
+        self._m_fsm_states = _sig(L, "gten_host_model_fsm_states", ci, [vp, ci, ci, vp])
+        self._b_fsm_states = _sig(L, "gten_host_batch_fsm_states", ci, [vp, ci, ci, ci, vp])
+        self._b_fsm_decoder = _sig(L, "gten_host_batch_fsm_decoder", vp, [vp])
+        self._generate_fsm = _sig(L, "gten_host_model_generate_fsm", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
+                                                                          C.c_float, C.c_float, vp, vp, vp, pen, ci, vp])
+        self._bgen_fsm = _sig(L, "gten_host_batch_generate_fsm", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
+                                                                      vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen, vp, vp])
+        self._bserve_fsm = _sig(L, "gten_host_batch_serve_fsm", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                     C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
+                                                                     vp, vp])
         self._score_top = _sig(L, "gten_host_model_score_top", ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
@@ -306,6 +334,79 @@ def _penalty_arg(n, rep, freq, pres, last_n, count_prompt):
                       0.0 if p is not None else float(p1), 0 if l is not None else int(l1), 1 if c is not None else int(c1))
     s._keep = (r, f, p, l, c)
     return s
+
+
+class Fsm:
+    """An automaton pool under construction (include/gten_host_fsm.h, host/fsm_build.h): no device needed.  add_stop / add_choices /
+    add_table append an automaton and return its start state; a refusal raises ValueError with the builder's code and leaves the
+    pool as it was."""
+
+    def __init__(self, host, n_vocab):
+        self.host, self.n_vocab = host, int(n_vocab)
+        self.h = host._fsm_create(self.n_vocab)
+        if not self.h:
+            raise ValueError(f"Fsm: n_vocab {n_vocab} outside [1, 65535]")
+
+    @staticmethod
+    def _lists(seqs):
+        off = np.zeros(len(seqs) + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in seqs])
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32).reshape(-1) for s in seqs]) if len(seqs) else [], dtype=np.int32)
+        return ids, off
+
+    def _add(self, fn, what, seqs):
+        ids, off = self._lists(seqs)
+        rc = fn(self.h, _ptr(ids) if len(ids) else None, _ptr(off), len(seqs))
+        if rc < 0:
+            raise ValueError(f"{what} refused: {rc}")
+        return rc
+
+    def add_stop(self, seqs):
+        """Aho-Corasick over the id sequences: nothing banned, final wherever one of them ends; the start state"""
+        return self._add(self.host._fsm_add_stop, "add_stop", seqs)
+
+    def add_choices(self, seqs):
+        """a trie: only its edges allowed, a choice's last id enters a final state; the start state"""
+        return self._add(self.host._fsm_add_choices, "add_choices", seqs)
+
+    def add_table(self, nxt, flags):
+        """the caller's own automaton (u16 [S][n_vocab], u8 [S]) relocated into the pool; the start state (its state 0)"""
+        nxt, flags = np.ascontiguousarray(nxt, dtype=np.uint16), np.ascontiguousarray(flags, dtype=np.uint8)
+        assert nxt.shape == (len(flags), self.n_vocab)
+        rc = self.host._fsm_add_table(self.h, _ptr(nxt), _ptr(flags), len(flags))
+        if rc < 0:
+            raise ValueError(f"add_table refused: {rc}")
+        return rc
+
+    @property
+    def n_states(self):
+        return self.host._fsm_n_states(self.h)
+
+    def tables(self):
+        """copies of the pool: (next u16 [S][n_vocab], flags u8 [S])"""
+        n, f = C.c_void_p(), C.c_void_p()
+        S = self.host._fsm_tables(self.h, C.byref(n), C.byref(f))
+        if S <= 0:
+            return np.zeros((0, self.n_vocab), np.uint16), np.zeros(0, np.uint8)
+        nxt = np.ctypeslib.as_array(C.cast(n, C.POINTER(C.c_uint16)), shape=(S, self.n_vocab)).copy()
+        flags = np.ctypeslib.as_array(C.cast(f, C.POINTER(C.c_uint8)), shape=(S,)).copy()
+        return nxt, flags
+
+    def close(self):
+        if self.h:
+            self.host._fsm_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def _fsm_info(fn, h, n):
+    st, ps, S = np.zeros(n, np.int32), np.zeros(n, np.int32), C.c_int(0)
+    on = fn(h, C.byref(S), _ptr(st), _ptr(ps))
+    if on < 0:
+        raise GtenHipError(f"fsm_info rc={on}")
+    return S.value, st, ps, bool(on)
 
 
 class HostTokenizer:
@@ -656,6 +757,57 @@ class HostModel:
         ids = buf[:total].copy()
         return (ids, lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else ids
 
+    def set_fsm_rc(self, fsm):
+        return self.host._m_set_fsm(self.h, fsm.h if fsm is not None else None)
+
+    def set_fsm(self, fsm):
+        """the decoder's automaton pool becomes `fsm` (an Fsm; None drops it; include/gten_host_fsm.h)"""
+        rc = self.set_fsm_rc(fsm)
+        if rc:
+            raise GtenHipError(f"set_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def fsm_info(self):
+        """(states of the decoder's pool, binding state int32[1], binding position int32[1], whether a sequence was ever bound)"""
+        return _fsm_info(self.host._m_fsm_info, self.h, 1)
+
+    def set_seq_fsm_rc(self, state, pos=0):
+        return self.host._m_set_seq_fsm(self.h, int(state), int(pos))
+
+    def set_seq_fsm(self, state, pos=0):
+        """the id at position pos is chosen in `state` of the decoder's pool from now on (-1: unbound)"""
+        rc = self.set_seq_fsm_rc(state, pos)
+        if rc:
+            raise GtenHipError(f"set_seq_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def fsm_states(self, n_from, count):
+        """entries [n_from, n_from + count) of the sequence's state row"""
+        out = np.zeros(max(count, 1), np.int32)
+        rc = self.host._m_fsm_states(self.h, int(n_from), int(count), _ptr(out))
+        if rc:
+            raise GtenHipError(f"fsm_states rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return out[:count].copy()
+
+    def generate_fsm(self, prompt, max_tokens, fsm_start, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                     count_prompt=True, top_p=1.0, min_p=0.0, n_top=None):
+        """generate_penalized() with the first new id chosen in state fsm_start of the decoder's pool (-1: not bound): (ids, ended_by)
+        -- ended_by 0 length or context, 1 eos, 2 a final state -- or with n_top (ids, ended_by, lp, top ids, top lps)"""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        ask = n_top is not None and n_top >= 0
+        w = int(n_top) if ask else 0
+        lp, ti, tl = np.zeros(width, np.float32), np.full((width, w), -1, np.int32), np.zeros((width, w), np.float32)
+        pen = _penalty_arg(1, float(rep), float(freq), float(pres), int(last_n), bool(count_prompt))
+        ended = np.zeros(1, np.int32)
+        total = self.host._generate_fsm(self.h, _ptr(buf), len(prompt), max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)),
+                                        C.c_uint32(int(stream)), -1, 0, w if ask else -1, C.c_float(top_p), C.c_float(min_p),
+                                        _ptr(lp) if ask else None, _ptr(ti) if ask else None, _ptr(tl) if ask else None, C.byref(pen), int(fsm_start),
+                                        _ptr(ended))
+        if total < 0:
+            raise GtenHipError(f"generate_fsm rc={total}: {self.host.hip._err().decode(errors='replace')}")
+        ids = buf[:total].copy()
+        return (ids, int(ended[0]), lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else (ids, int(ended[0]))
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -942,6 +1094,62 @@ class HostBatch:
                               *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)), *args,
                               *_cut_args(n, top_p, min_p), C.byref(pen))
         return (ids, st) if n_top is None else (ids, st, *rec)
+
+    def set_fsm_rc(self, fsm):
+        return self.host._b_set_fsm(self.h, fsm.h if fsm is not None else None)
+
+    def set_fsm(self, fsm):
+        """the shared decoder's automaton pool becomes `fsm` (an Fsm; None drops it; include/gten_host_fsm.h)"""
+        rc = self.set_fsm_rc(fsm)
+        if rc:
+            raise GtenHipError(f"batch_set_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def fsm_info(self):
+        """(states of the shared decoder's pool, binding state int32[n_seq], binding position int32[n_seq], whether one was ever bound)"""
+        return _fsm_info(self.host._b_fsm_info, self.h, self.n_seq)
+
+    def set_seq_fsm_rc(self, seq, state, pos=0):
+        return self.host._b_set_seq_fsm(self.h, int(seq), int(state), int(pos))
+
+    def set_seq_fsm(self, seq, state, pos=0):
+        """the id at position pos of sequence seq is chosen in `state` of the shared decoder's pool from now on (-1: unbound)"""
+        rc = self.set_seq_fsm_rc(seq, state, pos)
+        if rc:
+            raise GtenHipError(f"batch_set_seq_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def fsm_states(self, seq, n_from, count):
+        """entries [n_from, n_from + count) of sequence seq's state row"""
+        out = np.zeros(max(count, 1), np.int32)
+        rc = self.host._b_fsm_states(self.h, int(seq), int(n_from), int(count), _ptr(out))
+        if rc:
+            raise GtenHipError(f"batch_fsm_states rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return out[:count].copy()
+
+    def fsm_decoder(self):
+        """the shared decoder's raw handle, for hipabi's decoder_slot_* calls"""
+        return self.host._b_fsm_decoder(self.h)
+
+    def generate_fsm(self, prompts, max_tokens, fsm_start, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                     count_prompt=True, top_p=1.0, min_p=0.0, tables=None, min_new=None):
+        """generate_penalized() with a start state per sequence (a scalar for all; -1: not bound): (ids per sequence, ended_by int32[n_seq])"""
+        n = self.n_seq
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
+        ids = self._generate(self.host._bgen_fsm, "batch_generate_fsm", prompts, max_tokens, eos,
+                             _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)),
+                             [None, 0, None, None, None] + _cut_args(n, top_p, min_p) + [C.byref(pen), _ptr(st), _ptr(ended)])
+        return ids, ended
+
+    def serve_fsm(self, prompts, max_tokens, eos, top_k, temp, seed, fsm_start, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True, top_p=1.0,
+                  min_p=0.0, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None):
+        """serve_penalized() with a start state per prompt (a scalar for all; -1: not bound): (ids per prompt, stats, ended_by int32[prompts])"""
+        n = len(prompts)
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
+        ids, stats = self._serve(self.host._bserve_fsm, "batch_serve_fsm", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                                 *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
+                                 None, 0, None, None, None, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
+        return ids, stats, ended
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""

@@ -41,12 +41,12 @@ def main():
         for e in re.split(r"\n\s+- \.agpr_count", notes)[1:]:
             g = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, e) or [None, "0"])[1]
             rows.append((g("name"), int(g("vgpr_count")), int(g("sgpr_count")), int(g("vgpr_spill_count")),
-                         int(g("private_segment_fixed_size")), int(g("group_segment_fixed_size"))))
+                         int(g("private_segment_fixed_size")), int(g("group_segment_fixed_size")), int(g("sgpr_spill_count"))))
     names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows), capture_output=True, text=True).stdout.splitlines()
-    print("vgpr sgpr spill scratchB ldsB  kernel")
+    print("vgpr sgpr vspill sspill scratchB ldsB  kernel")
     for r, nm in sorted(zip(rows, names), key=lambda x: x[1]):
         if flt in nm:
-            print("%4d %4d %5d %8d %5d  %s" % (r[1], r[2], r[3], r[4], r[5], nm[:170]))
+            print("%4d %4d %6d %6d %8d %5d  %s" % (r[1], r[2], r[3], r[6], r[4], r[5], nm[:170]))
 
 
 if __name__ == "__main__":
