@@ -32,6 +32,7 @@
 #include "gten_hip_fsm.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
+#include "gten_hip_prefixes.h"
 
 #include <cmath>
 #include <vector>
@@ -222,22 +223,32 @@ struct gten_hip_decoder {
     size_t hm_seq_stride = 0, hm_cache_bytes = 0, hm_chunk_bytes = 0;
     std::vector<char> hm_dirty;
     unsigned long long hm_imports = 0, hm_import_launches = 0;
-    // ---- a shared prefix (gten_hip_decoder_prefix_set, include/gten_hip_prefix_decode.h; decoders with shadows only).  pfx_hm: ONE more
-    // shadow, laid out as a sequence's, imported from the prefix set's rows [0, pfx_len) (pfx_stale: before the next sharing step);
-    // allocated by the first prefix_set, which also drops the captured graphs: from then on the step launches the _pfx kernels.
-    // share_rows[q]: the caller's promise for sequence q (gten_hip_decoder_slot_share; 0: none); share_cur[q]: the leading chunks
-    // q reads from pfx_hm = the value of share_dev[q] after the queued work -- its own shadow need not hold them.
+    // ---- shared prefixes (gten_hip_decoder_prefix_set, include/gten_hip_prefix_decode.h; decoders with shadows only).  Pfx::hm: ONE more
+    // shadow per prefix, laid out as a sequence's, imported from the prefix set's rows [0, len) (stale: before the next sharing step);
+    // allocated by the first set of its index; the first set at all drops the captured graphs: from then on the step launches the
+    // _pfx kernels.  share_rows[q]: the caller's promise for sequence q (gten_hip_decoder_slot_share; 0: none); share_cur[q]: the
+    // leading chunks q reads from a prefix shadow = the value of share_dev[q] after the queued work -- its own shadow need not hold them.
     // hm_dirty[q] & 1: somebody wrote q's rows (or bound others) -- that ends a promise; & 2: q was (re)started -- that does not.
-    uint8_t* pfx_hm = nullptr;
-    int* share_dev = nullptr;           // [n_seq] on the device, beside `step`
-    const void** pfx_tab = nullptr;     // device: [n_layers][k | v] of the prefix set
-    DecStep* pfx_step = nullptr;        // device: {pfx_len + 1} (the import kernels read a sequence's rows as step.n - 1)
-    std::vector<const void*> pfx_kv;    // the same on the host (watched: pfx_dirty)
-    int pfx_len = 0;
-    char pfx_dirty = 0;
-    bool pfx_stale = false;
-    std::vector<int> share_rows, share_cur;
-    unsigned long long pfx_imports = 0, hm_skip_imports = 0;
+    // SEVERAL prefixes (include/gten_hip_prefixes.h): pfx[w] is prefix w, each with its own shadow, watch flag, stale flag and import
+    // count; a sequence shares at most one (share_which[q], on the device which_dev[q] / which_cur[q]).  pfx_hm_tab: the shadows'
+    // base pointers on the device, at a fixed address (captured graphs hold it).  pfxn: an index above 0 was set once -- the step
+    // launches the _pfxn attention; until then a decoder with a prefix launches _pfx on pfx[0].hm, as before.
+    struct Pfx {
+        uint8_t* hm = nullptr;
+        const void** tab = nullptr;     // device: [n_layers][k | v] of the prefix set
+        DecStep* step = nullptr;        // device: {len + 1} (the import kernels read a sequence's rows as step.n - 1)
+        std::vector<const void*> kv;    // the same on the host (watched: dirty)
+        int len = 0;
+        char dirty = 0;
+        bool stale = false;
+        unsigned long long imports = 0;
+    } pfx[GTEN_PREFIXES_MAX];
+    int* share_dev = nullptr;           // [n_seq] on the device, beside `step`; allocated by the first prefix set at any index
+    int* which_dev = nullptr;           // [n_seq] beside it: the prefix index of the sequence's shared chunks
+    uint8_t** pfx_hm_tab = nullptr;     // device: [GTEN_PREFIXES_MAX]
+    bool pfxn = false;
+    std::vector<int> share_rows, share_cur, share_which, which_cur;
+    unsigned long long hm_skip_imports = 0;
     // every decoder: do the caches it appends to overlap a watch of ANOTHER decoder (cached per registry epoch)
     unsigned long long watch_epoch = 0;
     bool watch_foreign = false;
@@ -356,7 +367,8 @@ static bool g_kv_head_major = true;
 static bool g_pfx_shared = PFX_SHARED_DEFAULT;
 // host side, beside AttnArgs: the prefix shadow of the layer (K; V follows it) and the lane's shared counts -- k null: the decoder
 // holds no prefix shadow and launches the kernels it always did
-struct PfxArgs { const uint8_t* k = nullptr; const int* share = nullptr; };
+// (tab: the decoder holds several prefix shadows -- k is then unused, the kernels take shadow which[seq] from the table)
+struct PfxArgs { const uint8_t* k = nullptr; const int* share = nullptr; const uint8_t* const* tab = nullptr; size_t layer_off = 0; const int* which = nullptr; };
 extern "C" int gten_hip_set_kv_head_major(int on)
 {
     g_kv_head_major = on != 0;
@@ -433,6 +445,13 @@ static int launch_attention_g(const AttnArgs& t, int n_seq, const PfxArgs& pfx)
     if constexpr (ADT == GTEN_Q8) if (grouped_mm(t, n_seq) && t.hm_k) {
         // head-major shadows: one wave per (sequence, kv head, chunk), HM_WAVES consecutive chunks per workgroup
         const int n_cq = (t.n_chunks + HM_WAVES - 1) / HM_WAVES;
+        if (pfx.tab) {
+            if (n_seq >= 128)
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_pfxn<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+            else
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_pfxn<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+            return 0;
+        }
         if (pfx.k) {
             if (n_seq >= 128)
                 DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_pfx<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
@@ -468,6 +487,13 @@ static int launch_attention_g(const AttnArgs& t, int n_seq, const PfxArgs& pfx)
     }
     if constexpr (ADT == GTEN_F16) if (grouped_hm_f16(t, n_seq)) {
         const int n_cq = (t.n_chunks + HM_WAVES - 1) / HM_WAVES;
+        if (pfx.tab) {
+            if (n_seq >= 128)
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfxn<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+            else
+                DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfxn<GRP, false>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+            return 0;
+        }
         if (pfx.k) {
             if (n_seq >= 128)
                 DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfx<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.k, pfx.share);
@@ -1278,7 +1304,10 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
             t.hm_seq_stride = dc->hm_seq_stride; t.hm_cache_bytes = dc->hm_cache_bytes;
         }
         PfxArgs pfx;
-        if (dc->pfx_hm) { pfx.k = dc->pfx_hm + (size_t)l * 2 * dc->hm_cache_bytes; pfx.share = dc->share_dev + (size_t)lane * S; }
+        if (dc->pfxn) {
+            pfx.tab = (const uint8_t* const*)dc->pfx_hm_tab; pfx.layer_off = (size_t)l * 2 * dc->hm_cache_bytes;
+            pfx.share = dc->share_dev + (size_t)lane * S; pfx.which = dc->which_dev + (size_t)lane * S;
+        } else if (dc->pfx[0].hm) { pfx.k = dc->pfx[0].hm + (size_t)l * 2 * dc->hm_cache_bytes; pfx.share = dc->share_dev + (size_t)lane * S; }
         const dim3 agrid(d.n_heads, dc->n_chunks, S);
         const size_t smem1 = (size_t)(16 + 3 * dh + 16) * 4 + 32 + (size_t)3 * dh + 64;
         if (!grouped_known) { grouped = attention_grouped_ok(t, S); grouped_known = true; }
@@ -1729,8 +1758,10 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
                     dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm_next, dc->smp.fsm_flags, dc->smp.fsm, dc->smp.fsm_state,
-                    dc->pfx_hm, dc->share_dev, (void*)dc->pfx_tab, dc->pfx_step};
+                    dc->share_dev, dc->which_dev, (void*)dc->pfx_hm_tab};
     for (void* b : bufs) if (b) rel(hipFree(b));
+    for (gten_hip_decoder::Pfx& x : dc->pfx)
+        for (void* b : {(void*)x.hm, (void*)x.tab, (void*)x.step}) if (b) rel(hipFree(b));
     rel(persist_free(dc));
     for (int g = 1; g < DEC_MAX_LANES; g++) {
         if (dc->lane_stream[g]) { rel(hipStreamSynchronize(dc->lane_stream[g])); rel(hipStreamDestroy(dc->lane_stream[g])); }
@@ -1789,6 +1820,12 @@ static void share_end(gten_hip_decoder* dc, int q)
 {
     if (!dc->share_rows.empty()) dc->share_rows[(size_t)q] = 0;
 }
+// every sequence that shares prefix w comes off it (the others keep their promises)
+static void share_end_prefix(gten_hip_decoder* dc, int w)
+{
+    for (size_t q = 0; q < dc->share_rows.size(); q++)
+        if (dc->share_which[q] == w) dc->share_rows[q] = 0;
+}
 static int pre_run(gten_hip_decoder* dc)
 {
     const gten_hip_decoder_desc& d = dc->d;
@@ -1826,43 +1863,50 @@ static int pre_run(gten_hip_decoder* dc)
                        d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
         return 0;
     };
-    if (dc->pfx_hm) {
-        if (dc->pfx_dirty) {                           // somebody wrote into the prefix set's rows: nobody shares what the shadow holds
-            dc->pfx_dirty = 0;
-            dc->pfx_stale = true;
-            std::fill(dc->share_rows.begin(), dc->share_rows.end(), 0);
+    if (dc->share_dev) {
+        for (int w = 0; w < GTEN_PREFIXES_MAX; w++) {
+            gten_hip_decoder::Pfx& x = dc->pfx[w];
+            if (!x.dirty) continue;                    // somebody wrote into prefix w's rows: nobody shares what ITS shadow holds
+            x.dirty = 0;
+            x.stale = true;
+            share_end_prefix(dc, w);
         }
         HmShareList sl{};
         auto flush_sl = [&]() -> int {
             if (sl.n == 0) return 0;
-            GTR_LAUNCH(KT_PACK, k_hm_share_set, dim3(1), dim3(64), 0, sl, dc->share_dev);
+            GTR_LAUNCH(KT_PACK, k_hm_share_set, dim3(1), dim3(64), 0, sl, dc->share_dev, dc->which_dev);
             sl.n = 0;
             return 0;
         };
-        bool any = false;
+        bool any[GTEN_PREFIXES_MAX] = {};
         for (int q = 0; q < dc->n_seq; q++) {
             if (dc->share_rows[(size_t)q] && (dc->hm_dirty[(size_t)q] & 1)) dc->share_rows[(size_t)q] = 0;      // written since the promise
-            const int want = dc->pfx_len > 0 ? dc->share_rows[(size_t)q] / DEC_CHUNK : 0;
-            any = any || want > 0;
-            if (want == dc->share_cur[(size_t)q]) continue;
+            const int w = dc->share_which[(size_t)q];
+            const int want = dc->pfx[w].len > 0 ? dc->share_rows[(size_t)q] / DEC_CHUNK : 0;
+            if (want > 0) any[w] = true;
+            // (a sequence without shared chunks keeps whatever index it had: nothing reads it)
+            if (want == dc->share_cur[(size_t)q] && (want == 0 || w == dc->which_cur[(size_t)q])) continue;
             if (want < dc->share_cur[(size_t)q]) dc->hm_dirty[(size_t)q] |= 2;                              // its own shadow lacks those chunks
             dc->share_cur[(size_t)q] = want;
-            sl.item[sl.n++] = (unsigned short)((unsigned)q | ((unsigned)want << 10));
+            dc->which_cur[(size_t)q] = w;
+            sl.item[sl.n++] = (unsigned)q | ((unsigned)want << 10) | ((unsigned)w << 16);
             if (sl.n == (int)(sizeof(sl.item) / sizeof(sl.item[0])))
                 if (int rc = flush_sl()) return rc;
         }
         if (int rc = flush_sl()) return rc;
-        if (any && dc->pfx_stale) {
+        for (int w = 0; w < GTEN_PREFIXES_MAX; w++) {
+            gten_hip_decoder::Pfx& x = dc->pfx[w];
+            if (!any[w] || !x.stale) continue;
             HmImportList one{};
             one.n = 1;
-            if (int rc = import_launch(one, dc->pfx_step, (const void* const*)dc->pfx_tab, dc->pfx_hm, nullptr)) return rc;
-            dc->pfx_stale = false;
-            dc->pfx_imports++;
+            if (int rc = import_launch(one, x.step, (const void* const*)x.tab, x.hm, nullptr)) return rc;
+            x.stale = false;
+            x.imports++;
         }
     }
     auto flush = [&]() -> int {
         if (items.n == 0) return 0;
-        if (dc->pfx_hm) {
+        if (dc->share_dev) {
             if (int rc = import_launch(items, (const DecStep*)dc->step, (const void* const*)dc->kv_tab, dc->hm, dc->share_dev)) return rc;
         } else if (d.adtype == GTEN_Q8)
             GTR_LAUNCH(KT_PACK, k_kv_import_hm, dim3(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, items.n), dim3(256), (size_t)DEC_CHUNK * 68, items,
@@ -1881,7 +1925,7 @@ static int pre_run(gten_hip_decoder* dc)
         if (!dc->hm_dirty[(size_t)q]) continue;
         dc->hm_dirty[(size_t)q] = 0;
         items.seq[items.n++] = q;
-        if (dc->pfx_hm && dc->share_cur[(size_t)q] > 0) dc->hm_skip_imports++;
+        if (dc->share_dev && dc->share_cur[(size_t)q] > 0) dc->hm_skip_imports++;
         if (items.n == (int)(sizeof(items.seq) / sizeof(items.seq[0])))
             if (int rc = flush()) return rc;
     }
@@ -2480,70 +2524,133 @@ int gten_hip_set_prefix_decode_shared(int on)
     return 0;
 }
 
-int gten_hip_decoder_prefix_set(gten_hip_decoder* dc, const gten_hip_kv_ptrs* kv, int prefix_len)
+/* ---- several prefixes (include/gten_hip_prefixes.h): the calls of one prefix are these with which = 0 */
+int gten_hip_decoder_prefixes_set(gten_hip_decoder* dc, int which, const gten_hip_kv_ptrs* kv, int prefix_len)
 {
     GTR_NEED_INIT();
-    GTR_REQUIRE(dc && prefix_len >= 0, "decoder_prefix_set: bad arguments");
+    GTR_REQUIRE(dc && prefix_len >= 0, "decoder_prefixes_set: bad arguments");
+    GTR_REQUIRE(which >= 0 && which < GTEN_PREFIXES_MAX, "decoder_prefixes_set: prefix index %d outside [0, %d)", which, GTEN_PREFIXES_MAX);
     if (!dc->hm) return 0;                             // no shadows (<= 8 sequences, exact forms, set_kv_head_major(0)): nothing to share
     const gten_hip_decoder_desc& d = dc->d;
     if (kv && prefix_len > 0) {
-        GTR_REQUIRE(prefix_len <= d.max_ctx, "decoder_prefix_set: prefix of %d rows, context %d", prefix_len, d.max_ctx);
-        for (int l = 0; l < d.n_layers; l++) GTR_REQUIRE(kv[l].kcache && kv[l].vcache, "decoder_prefix_set: null cache pointer (layer %d)", l);
+        GTR_REQUIRE(prefix_len <= d.max_ctx, "decoder_prefixes_set: prefix of %d rows, context %d", prefix_len, d.max_ctx);
+        for (int l = 0; l < d.n_layers; l++) GTR_REQUIRE(kv[l].kcache && kv[l].vcache, "decoder_prefixes_set: null cache pointer (layer %d)", l);
     }
-    // every sequence comes off the shadow first: the next pre_run zeroes its count and imports its own rows in full, ahead of
-    // any import of the prefix shadow
-    std::fill(dc->share_rows.begin(), dc->share_rows.end(), 0);
-    kv_watch_remove(dc, &dc->pfx_dirty);
-    dc->pfx_dirty = 0;
-    dc->pfx_len = 0;
-    dc->pfx_kv.clear();
+    gten_hip_decoder::Pfx& x = dc->pfx[which];
+    // every sequence that shares THIS prefix comes off its shadow first: the next pre_run zeroes its count and imports its own
+    // rows in full, ahead of any import of the shadow.  Sequences behind other prefixes are not touched.
+    share_end_prefix(dc, which);
+    kv_watch_remove(dc, &x.dirty);
+    x.dirty = 0;
+    x.len = 0;
+    x.kv.clear();
     if (!kv || prefix_len == 0) return 0;
-    // (k_hm_share_set's entries are sequence | chunks << 10 in 16 bits)
-    GTR_REQUIRE(dc->n_seq <= 1024 && dc->n_chunks < 64, "decoder_prefix_set: %d sequences (at most 1024) x %d chunks (at most 63)", dc->n_seq, dc->n_chunks);
+    // (k_hm_share_set's entries are sequence | chunks << 10 | index << 16)
+    GTR_REQUIRE(dc->n_seq <= 1024 && dc->n_chunks < 64, "decoder_prefixes_set: %d sequences (at most 1024) x %d chunks (at most 63)", dc->n_seq, dc->n_chunks);
     const size_t L2 = (size_t)d.n_layers * 2;
-    if (!dc->pfx_hm) {
-        // first use: the prefix shadow, the shared counts -- and the step's attention becomes the _pfx instantiation, so the graphs
-        // captured so far go
+    const bool first_any = !dc->share_dev, first_n = which > 0 && !dc->pfxn;
+    if (first_any || first_n) {
+        // first use of a prefix: the step's attention becomes the _pfx instantiation; first use of an index above 0: the _pfxn
+        // instantiation.  Either way the graphs captured so far go, once.
         GTR_CHECK(hipStreamSynchronize(stream()));
         GTR_CHECK(drop_graphs(dc));
+    }
+    if (first_any) {
         GTR_CHECK(hipMalloc((void**)&dc->share_dev, (size_t)dc->n_seq * sizeof(int)));
         GTR_CHECK(hipMemset(dc->share_dev, 0, (size_t)dc->n_seq * sizeof(int)));
-        GTR_CHECK(hipMalloc((void**)&dc->pfx_tab, L2 * sizeof(void*)));
-        GTR_CHECK(hipMalloc((void**)&dc->pfx_step, sizeof(DecStep)));
+        GTR_CHECK(hipMalloc((void**)&dc->which_dev, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMemset(dc->which_dev, 0, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMalloc((void**)&dc->pfx_hm_tab, GTEN_PREFIXES_MAX * sizeof(uint8_t*)));
+        GTR_CHECK(hipMemset(dc->pfx_hm_tab, 0, GTEN_PREFIXES_MAX * sizeof(uint8_t*)));
         dc->share_rows.assign((size_t)dc->n_seq, 0);
         dc->share_cur.assign((size_t)dc->n_seq, 0);
-        GTR_CHECK(hipMalloc((void**)&dc->pfx_hm, dc->hm_seq_stride));
-        GTR_CHECK(hipMemset(dc->pfx_hm, 0, dc->hm_seq_stride));
+        dc->share_which.assign((size_t)dc->n_seq, 0);
+        dc->which_cur.assign((size_t)dc->n_seq, 0);
     }
-    for (int l = 0; l < d.n_layers; l++) { dc->pfx_kv.push_back(kv[l].kcache); dc->pfx_kv.push_back(kv[l].vcache); }
+    if (first_n) dc->pfxn = true;
+    if (!x.hm) {
+        // first use of this index: its shadow, and its entry of the table (nobody reads the entry before a count names it)
+        GTR_CHECK(hipMalloc((void**)&x.tab, L2 * sizeof(void*)));
+        GTR_CHECK(hipMalloc((void**)&x.step, sizeof(DecStep)));
+        GTR_CHECK(hipMalloc((void**)&x.hm, dc->hm_seq_stride));
+        GTR_CHECK(hipMemset(x.hm, 0, dc->hm_seq_stride));
+        GTR_CHECK(hipMemcpy(dc->pfx_hm_tab + which, &x.hm, sizeof(uint8_t*), hipMemcpyHostToDevice));
+    }
+    for (int l = 0; l < d.n_layers; l++) { x.kv.push_back(kv[l].kcache); x.kv.push_back(kv[l].vcache); }
     const DecStep st{prefix_len + 1, 0, 0};
-    GTR_CHECK(hipMemcpyAsync(dc->pfx_tab, dc->pfx_kv.data(), L2 * sizeof(void*), hipMemcpyHostToDevice, stream()));
-    GTR_CHECK(hipMemcpyAsync(dc->pfx_step, &st, sizeof(DecStep), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(x.tab, x.kv.data(), L2 * sizeof(void*), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(x.step, &st, sizeof(DecStep), hipMemcpyHostToDevice, stream()));
     GTR_CHECK(hipStreamSynchronize(stream()));         // (`st` lives on this stack frame)
     const size_t cache_bytes = (size_t)d.max_ctx * gten_hip_row_bytes(d.adtype, (d.n_embd / d.n_heads) * d.n_kv_heads);
-    for (const void* c : dc->pfx_kv) kv_watch_add(c, cache_bytes, dc, &dc->pfx_dirty);
-    dc->pfx_len = prefix_len;
-    dc->pfx_stale = true;
+    for (const void* c : x.kv) kv_watch_add(c, cache_bytes, dc, &x.dirty);
+    x.len = prefix_len;
+    x.stale = true;
     return 0;
 }
 
-int gten_hip_decoder_slot_share(gten_hip_decoder* dc, int seq, int rows)
+int gten_hip_decoder_prefixes_share(gten_hip_decoder* dc, int seq, int which, int rows)
 {
     GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_slot_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_prefixes_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
+    GTR_REQUIRE(which >= 0 && which < GTEN_PREFIXES_MAX, "decoder_prefixes_share: prefix index %d outside [0, %d)", which, GTEN_PREFIXES_MAX);
     if (!dc->hm) return 0;
     if (rows == 0) { share_end(dc, seq); return 0; }
-    GTR_REQUIRE(dc->pfx_len > 0 && rows <= dc->pfx_len, "decoder_slot_share: %d rows, the prefix has %d", rows, dc->pfx_len);
+    const gten_hip_decoder::Pfx& x = dc->pfx[which];
+    GTR_REQUIRE(x.len > 0 && rows <= x.len, "decoder_prefixes_share: %d rows, prefix %d has %d", rows, which, x.len);
     // the sequence's next step, where the decoder knows it: a started slot, or -- outside the slot view -- a sequence that was
     // stepped and whose rows nobody wrote since
     int n_next = 0;
     if (!dc->slots.empty()) { if (dc->slots[(size_t)seq].advance & 1) n_next = dc->slots[(size_t)seq].n; }
     else if (!dc->hm_dirty[(size_t)seq]) n_next = !dc->dev_ns.empty() ? dc->dev_ns[(size_t)seq] : std::max(dc->dev_n, 0);
-    GTR_REQUIRE(n_next == 0 || rows <= n_next - 1, "decoder_slot_share: %d rows, sequence %d is at position %d", rows, seq, n_next - 1);
+    GTR_REQUIRE(n_next == 0 || rows <= n_next - 1, "decoder_prefixes_share: %d rows, sequence %d is at position %d", rows, seq, n_next - 1);
     if (!g_pfx_shared) return 0;                       // (switched off: nothing is recorded)
     dc->share_rows[(size_t)seq] = rows;
+    dc->share_which[(size_t)seq] = which;
     if (dc->hm_dirty[(size_t)seq]) dc->hm_dirty[(size_t)seq] = 2;       // what was written BEFORE the promise is what it speaks about
     return 0;
+}
+
+// (the chunks a step enqueued NOW would read from a prefix shadow: the promise as pre_run would take it)
+static int share_chunks_now(const gten_hip_decoder* dc, int seq, int* which)
+{
+    *which = -1;
+    if (!dc->share_dev || !dc->share_rows[(size_t)seq] || (dc->hm_dirty[(size_t)seq] & 1)) return 0;
+    const int w = dc->share_which[(size_t)seq];
+    if (dc->pfx[w].len <= 0 || dc->pfx[w].dirty) return 0;
+    const int chunks = dc->share_rows[(size_t)seq] / DEC_CHUNK;
+    if (chunks > 0) *which = w;
+    return chunks;
+}
+
+int gten_hip_decoder_prefixes_info(gten_hip_decoder* dc, int seq, int which, int* seq_which, int* seq_chunks, int* prefix_len,
+                                   unsigned long long* prefix_imports, int* sharers)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_prefixes_info: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(which >= 0 && which < GTEN_PREFIXES_MAX, "decoder_prefixes_info: prefix index %d outside [0, %d)", which, GTEN_PREFIXES_MAX);
+    int w = -1;
+    const int chunks = share_chunks_now(dc, seq, &w);
+    int n = 0;
+    for (int q = 0; q < dc->n_seq; q++) {
+        int wq = -1;
+        if (share_chunks_now(dc, q, &wq) > 0 && wq == which) n++;
+    }
+    if (seq_which) *seq_which = w;
+    if (seq_chunks) *seq_chunks = chunks;
+    if (prefix_len) *prefix_len = dc->pfx[which].len;
+    if (prefix_imports) *prefix_imports = dc->pfx[which].imports;
+    if (sharers) *sharers = n;
+    return 0;
+}
+
+int gten_hip_decoder_prefix_set(gten_hip_decoder* dc, const gten_hip_kv_ptrs* kv, int prefix_len)
+{
+    return gten_hip_decoder_prefixes_set(dc, 0, kv, prefix_len);
+}
+
+int gten_hip_decoder_slot_share(gten_hip_decoder* dc, int seq, int rows)
+{
+    return gten_hip_decoder_prefixes_share(dc, seq, 0, rows);
 }
 
 int gten_hip_decoder_prefix_info(gten_hip_decoder* dc, int seq, int* prefix_len, int* seq_chunks, unsigned long long* prefix_imports,
@@ -2551,13 +2658,11 @@ int gten_hip_decoder_prefix_info(gten_hip_decoder* dc, int seq, int* prefix_len,
 {
     GTR_NEED_INIT();
     GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_prefix_info: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
-    // (the chunks a step enqueued NOW would read from the prefix shadow: the promise as pre_run would take it)
-    int chunks = 0;
-    if (dc->pfx_hm && dc->pfx_len > 0 && !dc->pfx_dirty && dc->share_rows[(size_t)seq] && !(dc->hm_dirty[(size_t)seq] & 1))
-        chunks = dc->share_rows[(size_t)seq] / DEC_CHUNK;
-    if (prefix_len) *prefix_len = dc->pfx_len;
-    if (seq_chunks) *seq_chunks = chunks;
-    if (prefix_imports) *prefix_imports = dc->pfx_imports;
+    int w = -1;
+    const int chunks = share_chunks_now(dc, seq, &w);
+    if (prefix_len) *prefix_len = dc->pfx[0].len;
+    if (seq_chunks) *seq_chunks = w == 0 ? chunks : 0;               // (this call speaks of prefix 0)
+    if (prefix_imports) *prefix_imports = dc->pfx[0].imports;
     if (imports_skipping) *imports_skipping = dc->hm_skip_imports;
     return 0;
 }

@@ -162,11 +162,23 @@ __host__ __device__ __forceinline__ unsigned hmf_v_off(unsigned p, unsigned e)
 #undef HM_KERNEL
 #undef HM_IMPORT_PFX_PARAMS
 #undef HM_ATTN_PFX_PARAMS
+// ... and once with a TABLE of prefix shadows (the attention kernels only; gten_hip_decoder_prefixes_set with an index above 0)
+#define HM_PFX 2
+#define HM_KERNEL(name) name##_pfxn
+#define HM_ATTN_PFX_PARAMS , const uint8_t* const* __restrict__ pfx_tab, const size_t pfx_layer, const int* __restrict__ share, const int* __restrict__ which
+#include "gten_decode_attn_hm_kernels.h"
+#undef HM_PFX
+#undef HM_KERNEL
+#undef HM_ATTN_PFX_PARAMS
 
-// the per-sequence shared counts (gten_hip_decoder_slot_share): entry = sequence | chunks << 10, written on the stream ahead of
-// the imports and the steps that read them
-struct HmShareList { int n; unsigned short item[512]; };
-__global__ __launch_bounds__(64) void k_hm_share_set(const HmShareList items, int* __restrict__ share)
+// the per-sequence shared counts and prefix indices (gten_hip_decoder_slot_share, gten_hip_decoder_prefixes_share): entry =
+// sequence | chunks << 10 | prefix index << 16, written on the stream ahead of the imports and the steps that read them
+struct HmShareList { int n; unsigned item[256]; };
+__global__ __launch_bounds__(64) void k_hm_share_set(const HmShareList items, int* __restrict__ share, int* __restrict__ which)
 {
-    for (int i = threadIdx.x; i < items.n; i += 64) share[items.item[i] & 1023u] = (int)(items.item[i] >> 10);
+    for (int i = threadIdx.x; i < items.n; i += 64) {
+        const unsigned e = items.item[i];
+        share[e & 1023u] = (int)((e >> 10) & 63u);
+        which[e & 1023u] = (int)(e >> 16);
+    }
 }

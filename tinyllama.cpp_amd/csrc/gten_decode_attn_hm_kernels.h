@@ -1,4 +1,4 @@
-// gten_decode_attn_hm_kernels.h: the four kernels of gten_decode_attn_hm.h -- included TWICE by it, not a header of its own (no guard).
+// gten_decode_attn_hm_kernels.h: the four kernels of gten_decode_attn_hm.h -- included THREE times by it, not a header of its own (no guard).
 //
 //   HM_PFX 0  k_kv_import_hm, k_dec_attn_hm<GRP, NT>, k_kv_import_hm_f16, k_dec_attn_hm_f16<GRP, NT>: the kernels of every decoder on
 //             which no shared prefix was ever set.  What the preprocessor leaves of this file is then, token for token, the
@@ -12,11 +12,17 @@
 //             the appends -- which go to the sequence's own rows and own shadow only -- never meet it.  Shared chunks are
 //             requested with the default cache policy also where a sequence's own are nontemporal (NT): they are meant to stay.
 //             The imports return at once for the chunks a listed sequence reads from the prefix shadow.
+//   HM_PFX 2  the two attention kernels only, with the suffix _pfxn (a decoder on which a prefix index above 0 was ever set,
+//             gten_hip_decoder_prefixes_set): up to GTEN_PREFIXES_MAX prefix shadows.  pfx_tab[w] is the base of shadow w (a table at a
+//             fixed address: a captured graph stays valid when an entry is filled), pfx_layer the layer's offset inside a shadow,
+//             which[seq] the shadow sequence seq's shared chunks come from.  Otherwise HM_PFX 1, word for word.  The imports need no
+//             such instantiation: they skip chunk < share[seq] whatever the index.
 //
 // Why an include and not `template <..., bool PFX>`: a template parameter cannot take the two extra ARGUMENTS away.  The kernels of a
 // decoder without a prefix must keep their argument list (the kernarg segment, the SGPRs it is loaded into) and with it their
 // instruction stream and register count exactly; two kernels per name with different parameter lists it is, and the text of the
 // body exists once.  Edit the body here; `#if HM_PFX` marks every place where the two differ.
+#if HM_PFX < 2
 __global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm)(const HmImportList items, const DecStep* __restrict__ step, const void* const* __restrict__ kv_tab,
                                                       uint8_t* __restrict__ hm_base, size_t hm_seq_stride, size_t hm_cache_bytes, int n_layers, int n_kv,
                                                       int n_chunks, int max_ctx, size_t kv_pitch HM_IMPORT_PFX_PARAMS)
@@ -69,6 +75,7 @@ __global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm)(const HmImportL
         else { *(uint16_t*)(dst + hm_v_d_off(p, 0)) = d0; *(uint16_t*)(dst + hm_v_d_off(p, 1)) = d1; }
     }
 }
+#endif
 
 
 template <int GRP, bool NT>
@@ -114,6 +121,9 @@ __global__ __launch_bounds__(64 * HM_WAVES) HM_OCC void HM_KERNEL(k_dec_attn_hm)
     const float2 rot = a.rope_now[t & 31];
 #if HM_PFX
     const bool shared = alive && chunk < share[seq];              // (uniform per wave) this chunk comes from the prefix shadow
+#if HM_PFX == 2
+    const uint8_t* pfx_k = shared ? pfx_tab[which[seq]] + pfx_layer : a.hm_k;                  // (uniform per wave) ... of its prefix
+#endif
     const uint8_t* kc = shared ? pfx_k + (size_t)(g * a.n_chunks + chunk) * HM_CHUNK_BYTES
                                : a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HM_CHUNK_BYTES;
 #else
@@ -343,6 +353,7 @@ __global__ __launch_bounds__(64 * HM_WAVES) HM_OCC void HM_KERNEL(k_dec_attn_hm)
     }
 }
 
+#if HM_PFX < 2
 __global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm_f16)(const HmImportList items, const DecStep* __restrict__ step, const void* const* __restrict__ kv_tab,
                                                           uint8_t* __restrict__ hm_base, size_t hm_seq_stride, size_t hm_cache_bytes, int n_layers,
                                                           int n_kv, int n_chunks, int max_ctx, size_t kv_pitch HM_IMPORT_PFX_PARAMS)
@@ -386,6 +397,7 @@ __global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm_f16)(const HmImp
         *(uint4*)(dst + (size_t)q * 16) = make_uint4(w[0], w[1], w[2], w[3]);
     }
 }
+#endif
 
 template <int GRP, bool NT>
 __global__ __launch_bounds__(64 * HM_WAVES) void HM_KERNEL(k_dec_attn_hm_f16)(const AttnArgs a0, const int n_seq, const int n_cq HM_ATTN_PFX_PARAMS)
@@ -442,6 +454,9 @@ __global__ __launch_bounds__(64 * HM_WAVES) void HM_KERNEL(k_dec_attn_hm_f16)(co
     const float2 rot = a.rope_now[t & 31];
 #if HM_PFX
     const bool shared = alive && chunk < share[seq];              // (uniform per wave) this chunk comes from the prefix shadow
+#if HM_PFX == 2
+    const uint8_t* pfx_k = shared ? pfx_tab[which[seq]] + pfx_layer : a.hm_k;                  // (uniform per wave) ... of its prefix
+#endif
     const uint8_t* kc = shared ? pfx_k + (size_t)(g * a.n_chunks + chunk) * HMF_CHUNK_BYTES
                                : a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HMF_CHUNK_BYTES;
 #else

@@ -119,6 +119,8 @@ class GtenHip:
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_hip_decoder_prefix_set", "gten_hip_decoder_slot_share", "gten_hip_decoder_prefix_info",
                              "gten_hip_set_prefix_decode_shared"]          # include/gten_hip_prefix_decode.h
+    PREFIXES_SYMBOLS = ["gten_hip_decoder_prefixes_set", "gten_hip_decoder_prefixes_share",
+                        "gten_hip_decoder_prefixes_info"]                  # include/gten_hip_prefixes.h
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB

@@ -27,6 +27,7 @@
 #include "../gten/gten.h"
 #include "../../include/gten_hip_score.h"
 #include "synth.h"
+#include "prefix_match.h"
 
 namespace gten {
 
@@ -608,6 +609,19 @@ inline PrefixDecode& prefix_decode()
     static PrefixDecode p;
     return p;
 }
+// ... and the entry points of SEVERAL prefixes (include/gten_hip_prefixes.h), installed by host/capi_prefixes.cpp in the same way.
+// Without them only prefix index 0 exists, through the hooks above.
+struct PrefixesDecode {
+    int (*set)(gten_hip_decoder* dec, int which, const gten_hip_kv_ptrs* kv, int prefix_len) = nullptr;
+    int (*share)(gten_hip_decoder* dec, int seq, int which, int rows) = nullptr;
+    int (*info)(gten_hip_decoder* dec, int seq, int which, int* seq_which, int* seq_chunks, int* prefix_len, unsigned long long* prefix_imports,
+                int* sharers) = nullptr;
+};
+inline PrefixesDecode& prefixes_decode()
+{
+    static PrefixesDecode p;
+    return p;
+}
 } // namespace detail
 
 // an array with one value per item, or one value for all of them
@@ -658,14 +672,14 @@ public:
         for (size_t i = 1; i < seqs_.size(); i++)
             for (int w = 0; w < seqs_[0]->n_weights(); w++) seqs_[i]->weight(w) = seqs_[0]->weight(w);
         pre_.reset();                                        // (the shared prompt matrix aliases the weights too: rebuilt on next use)
-        prefix_set_.reset();                                 // (... and the prefix set, whose rows were computed with the old weights)
-        prefix_ids_.clear();
+        for (Prefix& x : pfx_) { x.set.reset(); x.ids.clear(); }     // (... and the prefix sets, whose rows were computed with the old weights)
         // the shared decoder holds device pointers to the weights and to every cache set it was ever bound to (the spares among
         // them): it goes before they do and is rebuilt on next use
         if (dec_) { GTEN_HIP_OK(gten_hip_decoder_destroy(dec_)); dec_ = nullptr; }
         spares_.clear();                                     // (... and so do the spare cache sets)
         set_kv_.clear();
         set_share_.clear();
+        set_which_.clear();
     }
     void load_synthetic(uint64_t seed)
     {
@@ -710,12 +724,13 @@ public:
         // waits and K host loops over the vocabulary (round 4); a caller that wants a prompt's logits gets them as before
         if (!first_ids_) first_ids_.reset(new Tensor({kPreMax}, kInt32));
         int32_t* ids_dev = (int32_t*)first_ids_->device_ptr_mut();
-        // the prompts that begin with the shared prefix (set_prefix) are one row matrix of what follows it, the others one of
-        // whole prompts: two calls at most
-        std::vector<int> shared, plain;
-        for (int k = 0; k < K; k++) (shares_prefix(*prompts[(size_t)k]) ? shared : plain).push_back(k);
-        if (!shared.empty()) prefill_group(shared, (int)prefix_ids_.size(), slots, prompts, logits_out, ids_dev, pick);
-        if (!plain.empty()) prefill_group(plain, 0, slots, prompts, logits_out, ids_dev, pick);
+        // the prompts that begin with a registered prefix (set_prefix_at; the longest one, prefix_of) are one row matrix per prefix
+        // of what follows it, the others one of whole prompts: one call per group
+        std::vector<int> group[kPrefixesMax + 1];
+        for (int k = 0; k < K; k++) group[prefix_of(*prompts[(size_t)k]) + 1].push_back(k);
+        for (int w = 0; w < kPrefixesMax; w++)
+            if (!group[w + 1].empty()) prefill_group(group[w + 1], w, slots, prompts, logits_out, ids_dev, pick);
+        if (!group[0].empty()) prefill_group(group[0], -1, slots, prompts, logits_out, ids_dev, pick);
         std::vector<int32_t> got((size_t)K);
         GTEN_HIP_OK(gten_hip_memcpy_d2h(got.data(), ids_dev, (size_t)K * sizeof(int32_t)));
         for (int k = 0; k < K; k++) (*first)[(size_t)k] = got[(size_t)k];
@@ -726,39 +741,83 @@ public:
     // way in prefill_many_with: only its own rows are computed (hidden_rows_prefixed), its slot's caches get a copy of the
     // prefix set's K / V rows in front of them.  Same bytes as the whole prompt: rows are independent in segmented calls.
     // 0; -1: bad arguments (16 <= n, n + 17 <= context); -2: this batch does not process prompts as segments
-    int set_prefix(const int32_t* tokens, int n)
+    int set_prefix(const int32_t* tokens, int n) { return set_prefix_at(0, tokens, n); }
+    // ... at index `which` of kPrefixesMax (include/gten_host_prefixes.h): every index is a prefix of its own, on a cache set of its
+    // own.  Setting, replacing or clearing one leaves the others, the cache sets marked with them and the slots that decode behind
+    // them alone.  -1 as well: which outside [0, kPrefixesMax); -2 as well: an index above 0 without the entry points of several
+    // prefixes installed.
+    int set_prefix_at(int which, const int32_t* tokens, int n)
     {
-        if (n == 0) { prefix_ids_.clear(); decoder_prefix(false); return 0; }
+        if (which < 0 || which >= kPrefixesMax) return -1;
+        Prefix& x = pfx_[which];
+        if (n == 0) { x.ids.clear(); decoder_prefix(which, false); return 0; }
         if (!tokens || n < 16 || n + 17 > n_ctx_ || n > kPreRows) return -1;
         if (!batched_prompts() || !detail::prefixed_rows().call) return -2;
+        if (which > 0 && !detail::prefixes_decode().set) return -2;
         ensure_pre();
-        if (!prefix_set_) {
-            prefix_set_.reset(new TinyLlama(n_ctx_, dtype_, params_));
-            for (int w = 0; w < seqs_[0]->n_weights(); w++) prefix_set_->weight(w) = seqs_[0]->weight(w);
+        if (!x.set) {
+            x.set.reset(new TinyLlama(n_ctx_, dtype_, params_));
+            for (int w = 0; w < seqs_[0]->n_weights(); w++) x.set->weight(w) = seqs_[0]->weight(w);
         }
-        prefix_ids_.clear();                                   // (nothing shares a half-written set)
-        // ... and no decode slot goes on reading the shadow of rows that are about to be replaced: every sharing sequence is
-        // back on its own copy before the set is overwritten (the same set is reused in place)
-        decoder_prefix(false);
+        x.ids.clear();                                         // (nothing shares a half-written set)
+        // ... and no decode slot goes on reading the shadow of rows that are about to be replaced: every sequence sharing THIS
+        // prefix is back on its own copy before the set is overwritten (the same set is reused in place)
+        decoder_prefix(which, false);
         std::vector<int32_t> ids(tokens, tokens + n);
         Tensor tk(ids.data(), {n}, kInt32);
         (void)pre_->hidden_rows(tk, {0, n});
         for (int l = 0; l < params_.n_layers; l++) {
             AttentionBlock& src = pre_->block(l);
-            AttentionBlock& dst = prefix_set_->block(l);
+            AttentionBlock& dst = x.set->block(l);
             const size_t bytes = (size_t)n * (size_t)src.attn.key.acv.bstride(0);
             const gten_hip_copy_range r[2] = {{dst.attn.key.acv.device_ptr_mut(), src.attn.key.acv.device_ptr(), bytes},
                                               {dst.attn.value.acv.device_ptr_mut(), src.attn.value.acv.device_ptr(), bytes}};
             GTEN_HIP_OK(gten_hip_copy_ranges(r, 2));
         }
         GTEN_HIP_OK(gten_hip_sync());                          // (the set is read from either stream afterwards)
-        prefix_ids_ = std::move(ids);
+        x.ids = std::move(ids);
         // the decode side: the shared decoder exists from here on, so that every mark made below reaches it at once and whatever
         // writes a marked set's rows afterwards is seen by its watch
         ensure_decoder();
-        decoder_prefix(true);
+        decoder_prefix(which, true);
         return 0;
     }
+    // prefix `which`'s own single-sequence decoder re-decodes rows of its set (tests: a write into a prefix set's rows that the
+    // shared decoder hears of through its watch only).  The set no longer holds the registered ids from row n_first - 1 on, so
+    // the registration ends on this side: no later prompt takes the short way behind it.  -1: nothing registered there.
+    int prefix_set_steps(int which, const int32_t* tokens, int count, int n_first, int steps)
+    {
+        if (which < 0 || which >= kPrefixesMax || pfx_[which].ids.empty() || !pfx_[which].set) return -1;
+        Prefix& x = pfx_[which];
+        x.ids.clear();
+        forget_prefix_marks(which);
+        x.set->decode_set_tokens(tokens, 0, count);
+        x.set->decode_steps(n_first, steps, true);
+        return 0;
+    }
+    // the shared decoder's view of several prefixes (gten_hip_decoder_prefixes_info): the prefix sequence seq_i shares (-1: none)
+    // and its chunks; prefix `which`'s length there, the imports of its shadow, its sharers.  Without the entry points: -1 / 0.
+    void prefixes_decode_info(int seq_i, int which, int* seq_which, int* seq_chunks, int* n_prefix, unsigned long long* prefix_imports, int* sharers)
+    {
+        if (seq_which) *seq_which = -1;
+        if (seq_chunks) *seq_chunks = 0;
+        if (n_prefix) *n_prefix = 0;
+        if (prefix_imports) *prefix_imports = 0;
+        if (sharers) *sharers = 0;
+        if (!detail::prefixes_decode().info) return;
+        ensure_decoder();
+        GTEN_HIP_OK(detail::prefixes_decode().info(dec_, seq_i, which, seq_which, seq_chunks, n_prefix, prefix_imports, sharers));
+    }
+    // gten_hip_decoder_prefixes_share on the shared decoder, return code and all (tests: the refusals)
+    int prefixes_share_rc(int seq_i, int which, int rows)
+    {
+        if (!detail::prefixes_decode().share) return 0;
+        ensure_decoder();
+        return detail::prefixes_decode().share(dec_, seq_i, which, rows);
+    }
+    int prefix_len_at(int which) const { return (int)pfx_[which].ids.size(); }
+    unsigned long long prompts_shared_at(int which) const { return pfx_[which].prompts_shared; }
+    unsigned long long rows_computed_at(int which) const { return pfx_[which].rows_computed; }
     // the shared decoder's view (gten_hip_decoder_prefix_info): prefix length it holds, chunks sequence seq_i reads from the
     // prefix shadow, imports of that shadow, sequence imports that skipped shared chunks.  All 0 where nothing is installed.
     void prefix_decode_info(int seq_i, int* n_prefix, int* seq_chunks, unsigned long long* prefix_imports, unsigned long long* imports_skipping)
@@ -780,16 +839,25 @@ public:
     }
     // cache set c's rows were written by somebody else than a prompt of this class (gten_host_batch_seq_steps): its mark goes
     void forget_share(int c) { if (c >= 0 && c < (int)set_share_.size()) set_share_[(size_t)c] = 0; }
-    int prefix_len() const { return (int)prefix_ids_.size(); }
-    unsigned long long prompts_shared() const { return prompts_shared_; }
+    int prefix_len() const { return (int)pfx_[0].ids.size(); }
+    unsigned long long prompts_shared() const { return pfx_[0].prompts_shared; }
     unsigned long long rows_computed() const { return rows_computed_; }
-    bool shares_prefix(const std::vector<int32_t>& p) const
+    // the registered prefix prompt p takes the short way behind (host/prefix_match.h: the longest it begins with and has 16 ids
+    // behind); -1: none, the prompt is processed whole
+    int prefix_of(const std::vector<int32_t>& p) const
     {
-        const size_t P = prefix_ids_.size();
-        return P > 0 && p.size() >= P + 16 && std::equal(prefix_ids_.begin(), prefix_ids_.end(), p.begin());
+        const int32_t* ids[kPrefixesMax];
+        int lens[kPrefixesMax];
+        for (int w = 0; w < kPrefixesMax; w++) { ids[w] = pfx_[w].ids.data(); lens[w] = (int)pfx_[w].ids.size(); }
+        return prefixes_match_ptrs(ids, lens, kPrefixesMax, p.data(), (int)p.size());
     }
+    bool shares_prefix(const std::vector<int32_t>& p) const { return prefix_of(p) >= 0; }
     // rows of the row matrix that prompt p costs
-    int computed_rows(const std::vector<int32_t>& p) const { return (int)p.size() - (shares_prefix(p) ? (int)prefix_ids_.size() : 0); }
+    int computed_rows(const std::vector<int32_t>& p) const
+    {
+        const int w = prefix_of(p);
+        return (int)p.size() - (w >= 0 ? (int)pfx_[w].ids.size() : 0);
+    }
 
 private:
     void ensure_pre()
@@ -799,11 +867,12 @@ private:
         pre_->set_fast_decode(false);
         for (int w = 0; w < seqs_[0]->n_weights(); w++) pre_->weight(w) = seqs_[0]->weight(w);
     }
-    // prompts[idx[..]] as ONE row matrix: whole (P = 0) or what follows the shared prefix of P ids
+    // prompts[idx[..]] as ONE row matrix: whole (w < 0, P = 0) or what follows prefix w's P ids
     template <class Pick>
-    void prefill_group(const std::vector<int>& idx, int P, const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts,
+    void prefill_group(const std::vector<int>& idx, int w, const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts,
                        std::vector<float*>* logits_out, int32_t* ids_dev, Pick& pick)
     {
+        const int P = w >= 0 ? (int)pfx_[w].ids.size() : 0;
         std::vector<int32_t> ids, starts{0};
         for (int k : idx) {
             const std::vector<int32_t>& p = *prompts[(size_t)k];
@@ -812,9 +881,9 @@ private:
         }
         GTEN_ASSERTM((int)ids.size() <= kPreRows, "prefill_many: %zu rows (at most %d)", ids.size(), kPreRows);
         rows_computed_ += ids.size();
-        if (P > 0) prompts_shared_ += idx.size();
+        if (P > 0) { pfx_[w].prompts_shared += idx.size(); pfx_[w].rows_computed += ids.size(); }
         Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
-        const Tensor hidden = P > 0 ? pre_->hidden_rows_prefixed(tk, starts, *prefix_set_, P) : pre_->hidden_rows(tk, starts);
+        const Tensor hidden = P > 0 ? pre_->hidden_rows_prefixed(tk, starts, *pfx_[w].set, P) : pre_->hidden_rows(tk, starts);
         // every prompt's K / V rows into its own caches (behind a copy of the prefix set's rows when it shares them): one
         // launch per layer, two when the ranges do not fit one
         std::vector<gten_hip_copy_range> ranges;
@@ -832,7 +901,7 @@ private:
                 uint8_t* dk = (uint8_t*)dst.attn.key.acv.device_ptr_mut();
                 uint8_t* dv = (uint8_t*)dst.attn.value.acv.device_ptr_mut();
                 if (P > 0) {
-                    AttentionBlock& pre = prefix_set_->block(l);
+                    AttentionBlock& pre = pfx_[w].set->block(l);
                     ranges.push_back({dk, pre.attn.key.acv.device_ptr(), (size_t)P * pitch});
                     ranges.push_back({dv, pre.attn.value.acv.device_ptr(), (size_t)P * pitch});
                 }
@@ -849,8 +918,8 @@ private:
         for (size_t i = 0; i < idx.size(); i++) {
             const int c = slots[(size_t)idx[i]];
             share_mark(c) = P;
-            if (P > 0 && !in_serve_ && c < n_seq() && dec_ && detail::prefix_decode().slot_share)
-                (void)detail::prefix_decode().slot_share(dec_, c, P);     // (refused -- the sequence is mid-run at a position inside the prefix --: it decodes on its own copy)
+            which_mark(c) = P > 0 ? w : 0;
+            if (P > 0 && !in_serve_ && c < n_seq() && dec_) (void)decoder_share(c, w, P);     // (refused -- the sequence is mid-run at a position inside the prefix --: it decodes on its own copy)
         }
         for (size_t i = 0; i < idx.size(); i++) {
             const int k = idx[i];
@@ -1203,9 +1272,8 @@ public:
             if (!ap_seq.empty())
                 GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), ap_tok.data()));
             // the joining slots whose sets begin with the shared prefix's rows read them from the decoder's one copy
-            if (detail::prefix_decode().slot_share)
-                for (const int q : ap_seq)
-                    if (const int P = share_mark(set_of[(size_t)q]); P > 0) (void)detail::prefix_decode().slot_share(dec_, q, P);     // (refused: the slot decodes on its own copy, as in prefill_group)
+            for (const int q : ap_seq)
+                if (const int P = share_mark(set_of[(size_t)q]); P > 0) (void)decoder_share(q, which_mark(set_of[(size_t)q]), P);     // (refused: the slot decodes on its own copy, as in prefill_group)
             if (n_live == 0) return;
             // (a slot whose run ends inside the slice repeats its last step until the slice is over, slot_start_until: the slice
             //  is cut only when EVERY live slot ends earlier)
@@ -1315,9 +1383,12 @@ private:
     std::vector<std::unique_ptr<TinyLlama>> spares_;   // spare cache sets of serve()
     std::vector<std::vector<gten_hip_kv_ptrs>> set_kv_;      // per cache set: its layers' cache pointers (gten_hip_decoder_slot_bind)
     std::unique_ptr<TinyLlama> pre_;         // the shared row matrix of batched prompt processing (prefill_many), made on first use
-    std::unique_ptr<TinyLlama> prefix_set_;  // the cache set that holds the shared prefix's K / V rows (set_prefix)
-    std::vector<int32_t> prefix_ids_;        // the shared prefix (empty: none)
-    unsigned long long prompts_shared_ = 0;  // prompts that took the short way
+    struct Prefix {
+        std::unique_ptr<TinyLlama> set;      // the cache set that holds this prefix's K / V rows (set_prefix_at)
+        std::vector<int32_t> ids;            // the prefix (empty: none registered at this index)
+        unsigned long long prompts_shared = 0;   // prompts that took the short way behind it
+        unsigned long long rows_computed = 0;    // ... and the rows computed for them
+    } pfx_[kPrefixesMax];
     unsigned long long rows_computed_ = 0;   // prompt rows computed in segmented calls (the prefix's own rows not counted)
     std::unique_ptr<Tensor> first_ids_;      // [kPreMax] int32 on the device: the prompts' first ids (gten_hip_argmax_row)
     gten_hip_decoder* dec_ = nullptr;
@@ -1327,7 +1398,8 @@ private:
     int serve_schedule_ = 0;
     int serve_spares_ = -1;
     int serve_ramp_ = 100;
-    std::vector<int> set_share_;             // per cache set: its rows [0, P) are a copy of the prefix set's (0: no such mark)
+    std::vector<int> set_share_;             // per cache set: its rows [0, P) are a copy of a prefix set's (0: no such mark)
+    std::vector<int> set_which_;             // ... of which prefix (where the mark is not 0)
     bool in_serve_ = false;                  // serve() is running: sets are bound to slots by the scheduler
 
     int& share_mark(int c)
@@ -1335,19 +1407,43 @@ private:
         if ((int)set_share_.size() < n_sets()) set_share_.resize((size_t)n_sets(), 0);
         return set_share_[(size_t)c];
     }
-    // the prefix set's caches to the shared decoder (on) or "no prefix" (off): either way every slot is taken off the shared
-    // copy first and every mark is void -- they spoke of the previous prefix
-    void decoder_prefix(bool on)
+    int& which_mark(int c)
     {
-        std::fill(set_share_.begin(), set_share_.end(), 0);
-        if (!dec_ || !detail::prefix_decode().prefix_set) return;
-        if (!on || prefix_ids_.empty() || !prefix_set_) { GTEN_HIP_OK(detail::prefix_decode().prefix_set(dec_, nullptr, 0)); return; }
-        gten_hip_decoder_desc di;
-        std::vector<gten_hip_layer_ptrs> Li;
-        prefix_set_->describe(&di, &Li);
+        if ((int)set_which_.size() < n_sets()) set_which_.resize((size_t)n_sets(), 0);
+        return set_which_[(size_t)c];
+    }
+    // every mark that speaks of prefix w is void
+    void forget_prefix_marks(int w)
+    {
+        for (size_t c = 0; c < set_share_.size(); c++)
+            if (set_share_[c] > 0 && which_mark((int)c) == w) set_share_[c] = 0;
+    }
+    // the decoder's entry points: those of several prefixes where installed, else those of one prefix for index 0
+    int decoder_share(int q, int w, int rows)
+    {
+        if (detail::prefixes_decode().share) return detail::prefixes_decode().share(dec_, q, w, rows);
+        if (w == 0 && detail::prefix_decode().slot_share) return detail::prefix_decode().slot_share(dec_, q, rows);
+        return 0;
+    }
+    // prefix w's set's caches to the shared decoder (on) or "no prefix at index w" (off): either way every slot that shares w is
+    // taken off the shared copy first and every mark that speaks of w is void -- they spoke of the previous prefix
+    void decoder_prefix(int w, bool on)
+    {
+        forget_prefix_marks(w);
+        if (!dec_) return;
+        const gten_hip_kv_ptrs* kvp = nullptr;
         std::vector<gten_hip_kv_ptrs> kv;
-        for (auto& p : Li) kv.push_back(gten_hip_kv_ptrs{p.kcache, p.vcache});
-        GTEN_HIP_OK(detail::prefix_decode().prefix_set(dec_, kv.data(), (int)prefix_ids_.size()));
+        int len = 0;
+        if (on && !pfx_[w].ids.empty() && pfx_[w].set) {
+            gten_hip_decoder_desc di;
+            std::vector<gten_hip_layer_ptrs> Li;
+            pfx_[w].set->describe(&di, &Li);
+            for (auto& p : Li) kv.push_back(gten_hip_kv_ptrs{p.kcache, p.vcache});
+            kvp = kv.data();
+            len = (int)pfx_[w].ids.size();
+        }
+        if (detail::prefixes_decode().set) GTEN_HIP_OK(detail::prefixes_decode().set(dec_, w, kvp, len));
+        else if (w == 0 && detail::prefix_decode().prefix_set) GTEN_HIP_OK(detail::prefix_decode().prefix_set(dec_, kvp, len));
     }
 
     const gten_hip_kv_ptrs* set_kv(int c)
@@ -1376,7 +1472,8 @@ private:
             for (auto& p : Li) kv.push_back(gten_hip_kv_ptrs{p.kcache, p.vcache});
         }
         GTEN_HIP_OK(gten_hip_decoder_create_multi(&d, L.data(), kv.data(), (int)seqs_.size(), &dec_));
-        decoder_prefix(true);                                  // (a prefix set before the decoder existed)
+        for (int w = 0; w < kPrefixesMax; w++)
+            if (!pfx_[w].ids.empty()) decoder_prefix(w, true);     // (a prefix set before the decoder existed)
     }
 };
 

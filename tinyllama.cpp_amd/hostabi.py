@@ -73,6 +73,9 @@ class GtenHost:
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
                              "gten_host_set_prefix_decode_shared"]                                          # include/gten_host_prefix_decode.h
+    PREFIXES_SYMBOLS = ["gten_host_batch_prefixes_set", "gten_host_batch_prefixes_info", "gten_host_batch_prefixes_decode_info",
+                        "gten_host_batch_prefixes_decode_share", "gten_host_batch_prefixes_steps",
+                        "gten_host_prefixes_match"]                                                         # include/gten_host_prefixes.h
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -202,6 +205,14 @@ class GtenHost:
                              [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self._bpdshare = _sig(L, "gten_host_batch_prefix_decode_share", ci, [vp, ci, ci])
         self._pdshared = _sig(L, "gten_host_set_prefix_decode_shared", ci, [ci])
+        ull = C.c_ulonglong
+        self._bpsset = _sig(L, "gten_host_batch_prefixes_set", ci, [vp, ci, vp, ci])
+        self._bpsinfo = _sig(L, "gten_host_batch_prefixes_info", ci, [vp, ci, C.POINTER(ci), C.POINTER(ull), C.POINTER(ull)])
+        self._bpsdinfo = _sig(L, "gten_host_batch_prefixes_decode_info", ci,
+                              [vp, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(ci), C.POINTER(ull), C.POINTER(ci)])
+        self._bpsdshare = _sig(L, "gten_host_batch_prefixes_decode_share", ci, [vp, ci, ci, ci])
+        self._bpssteps = _sig(L, "gten_host_batch_prefixes_steps", ci, [vp, ci, vp, ci, ci, ci])
+        self._psmatch = _sig(L, "gten_host_prefixes_match", ci, [vp, vp, ci, ci, vp, ci])
         self._synthw = _sig(L, "gten_host_synth_weight", ci, [cfgp, C.c_uint64, ci, vp, sz])
         self._writeg = _sig(L, "gten_host_write_gten", ci, [cfgp, C.c_uint64, C.c_char_p])
         self._stoks = _sig(L, "gten_host_synthetic_tokens", None, [vp, ci, C.c_uint32, ci])
@@ -229,6 +240,19 @@ class GtenHost:
         rc = self._pdshared(-1 if on is None else 1 if on else 0)    # (None: the default again)
         if rc:
             raise GtenHipError(f"gten_host_set_prefix_decode_shared rc={rc}")
+
+    def prefixes_match(self, prefixes, prompt):
+        """gten_host_prefixes_match (include/gten_host_prefixes.h): the index of the longest of `prefixes` (id lists; empty or None: not
+        registered) that `prompt` begins with and has at least 16 ids behind, the lower index among equal lengths; -1: none"""
+        prefixes = [[] if p is None else list(p) for p in prefixes]
+        lens = np.ascontiguousarray([len(p) for p in prefixes], dtype=np.int32)
+        max_len = int(lens.max()) if len(prefixes) else 0
+        flat = np.zeros((max(len(prefixes), 1), max(max_len, 1)), np.int32)
+        for i, p in enumerate(prefixes):
+            flat[i, :len(p)] = p
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        return self._psmatch(flat.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), len(prefixes), max(max_len, 1),
+                             prompt.ctypes.data_as(C.c_void_p), len(prompt))
 
     def synthetic_tokens(self, count, seed=12345, n_vocab=32003):
         out = np.zeros(count, np.int32)
@@ -1177,6 +1201,40 @@ class HostBatch:
     def prefix_decode_share_rc(self, seq, rows):
         """gten_hip_decoder_slot_share(seq, rows) on the shared decoder: 0, or the refusal's code"""
         return self.host._bpdshare(self.h, seq, rows)
+
+    def set_prefix_at_rc(self, which, tokens):
+        """gten_host_batch_prefixes_set's return code (0; -2: this batch does not process prompts as segments; -1: bad arguments)"""
+        tokens = np.ascontiguousarray([] if tokens is None else tokens, dtype=np.int32)
+        return self.host._bpsset(self.h, which, tokens.ctypes.data_as(C.c_void_p) if len(tokens) else None, len(tokens))
+
+    def set_prefix_at(self, which, tokens):
+        """set_prefix at index `which` of 8 (None / []: clear it): a later prompt takes the LONGEST registered prefix it begins with and
+        has 16 ids behind; the other indices, and what decodes behind them, are left alone (include/gten_host_prefixes.h)"""
+        self._ck(self.set_prefix_at_rc(which, tokens), "batch_prefixes_set")
+
+    def prefixes_info(self, which):
+        """(length of prefix `which`, prompts that took the short way behind it so far, rows computed for them)"""
+        n, sh, rows = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._ck(self.host._bpsinfo(self.h, which, C.byref(n), C.byref(sh), C.byref(rows)), "batch_prefixes_info")
+        return n.value, sh.value, rows.value
+
+    def prefix_decode_info_at(self, seq, which=None):
+        """the shared decoder's view of several prefixes: (prefix index sequence `seq` shares or -1, leading chunks of 256 positions it
+        reads from that one copy); with `which` also (length of prefix `which` there, imports of its copy so far, its sharers now)"""
+        w, ch, n, pi, sh = C.c_int(-1), C.c_int(0), C.c_int(0), C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.host._bpsdinfo(self.h, seq, C.byref(w), C.byref(ch), 0 if which is None else which, C.byref(n), C.byref(pi), C.byref(sh)),
+                 "batch_prefixes_decode_info")
+        return (w.value, ch.value) if which is None else (w.value, ch.value, n.value, pi.value, sh.value)
+
+    def prefixes_decode_share_rc(self, seq, which, rows):
+        """gten_hip_decoder_prefixes_share(seq, which, rows) on the shared decoder: 0, or the refusal's code"""
+        return self.host._bpsdshare(self.h, seq, which, rows)
+
+    def prefix_set_steps(self, which, tokens, n_first, steps):
+        """tests: prefix `which`'s own single-sequence decoder rewrites rows n_first - 1 .. of the prefix's cache set; the
+        registration at `which` ends (include/gten_host_prefixes.h, gten_host_batch_prefixes_steps)"""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        self._ck(self.host._bpssteps(self.h, which, tokens.ctypes.data_as(C.c_void_p), len(tokens), n_first, steps), "batch_prefixes_steps")
 
     def decode_result(self, seq, n):
         out = C.c_int32(-1)

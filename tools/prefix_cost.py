@@ -20,6 +20,13 @@ Without --step this is a driver: it runs the steps below one after the other, ea
   --step serve_decode   (c) the serving queue of --step serve behind the 1024-id prefix, the switch off / on, three runs each in
                    alternation: new tok/s, and the ids of both ways compared.
   (--decode: the driver runs these two instead of kernels and serve; results go to profiles/prefix_decode_cost.json)
+  --step prefixes  SEVERAL prefixes (include/gten_host_prefixes.h; --prefixes K, default 4): full-size synthetic q4, 256 slots, K
+                   prefixes of 1024 ids with 256 / K slots behind each: the shared ragged step and the attention family's launch
+                   with gten_hip_set_prefix_decode_shared off / on, three runs each in alternation -- and, on the same build and
+                   in the same alternation, today's best case: ONE 1024-id prefix behind all 256 slots.
+  --step serve_prefixes   the serving queue of 1024 prompts split over the K prefixes, all K registered against only index 0
+                   registered (what a build with one prefix can do), three runs each in alternation; the ids compared.
+  (--prefixes K: the driver runs these two; results go to profiles/prefixes_cost.json)
 """
 import argparse
 import json
@@ -35,8 +42,9 @@ sys.path.insert(0, ROOT)
 from __graft_entry__ import load_package  # noqa: E402
 
 PREFIX, SLOTS, QUEUE, CTX, REPS = 256, 256, 1024, 2048, 3
-STEP_LIMIT_S = {"kernels": 240, "serve": 600, "decode": 420, "serve_decode": 600}
+STEP_LIMIT_S = {"kernels": 240, "serve": 600, "decode": 420, "serve_decode": 600, "prefixes": 540, "serve_prefixes": 600}
 DEC_PREFIX = 1024
+N_PREFIXES = 4
 
 
 def queue(host, cfg, n_prefix=PREFIX):
@@ -178,6 +186,99 @@ def step_serve_decode():
     return res
 
 
+def queue_over(host, cfg, k):
+    """queue()'s own ids and budgets behind K different 1024-id prefixes, prompt j behind prefix j % K"""
+    rng = np.random.default_rng(2025)
+    own = rng.integers(64, 257, QUEUE)
+    budgets = rng.integers(32, 225, QUEUE).astype(np.int32)
+    prefixes = [[int(t) for t in host.synthetic_tokens(DEC_PREFIX, seed=424242 + 1000 * w, n_vocab=cfg.n_vocab)] for w in range(k)]
+    prompts = [prefixes[j % k] + [int(t) for t in host.synthetic_tokens(int(n), seed=9000 + j, n_vocab=cfg.n_vocab)] for j, n in enumerate(own)]
+    return prefixes, prompts, budgets
+
+
+def step_prefixes():
+    hip, host, cfg, b = full_size_batch()
+    k = N_PREFIXES
+    prefixes, prompts_k, _ = queue_over(host, cfg, k)
+    _, prompts_1, _ = queue_over(host, cfg, 1)                            # (the same own ids, all behind prefix 0)
+    steps = 32
+    fam = hip.prof_family_index("decode_attn_score")
+    res = {"slots": SLOTS, "prefixes": k, "prefix_ids": DEC_PREFIX, "own_ids": "64..256", "steps_timed": steps, "runs": []}
+    cases = (("off", k, False), ("one_prefix", 1, True), ("on", k, True))
+    last = {}
+    for rep in range(REPS + 1):                                            # (rep 0: warm-up -- graphs, first-use allocations)
+        for name, n_reg, shared in cases:
+            prompts = (prompts_k if n_reg == k else prompts_1)[:SLOTS]
+            n_long = max(len(p) for p in prompts) + 1
+            for w in range(k):
+                b.set_prefix_at(w, prefixes[w] if w < n_reg else None)
+            host.set_prefix_decode_shared(shared)
+            for i in range(0, SLOTS, 3):                                   # (a call takes 4096 ids: three prompts of at most 1280)
+                b.prefill_many(list(range(i, min(i + 3, SLOTS))), prompts[i:i + 3], want=False)
+            streams = [p + [int(t) for t in host.synthetic_tokens(steps + 8, seed=7000 + q, n_vocab=cfg.n_vocab)] for q, p in enumerate(prompts)]
+            for q, s_ in enumerate(streams):
+                b.decode_begin(q, s_)
+            sharing = [sum(1 for q in range(SLOTS) if b.prefix_decode_info_at(q) == (w, DEC_PREFIX // 256)) for w in range(k)]
+            for t in (1, 2):                                               # (imports, graph capture)
+                b.decode_step_ragged([len(p) + t for p in prompts], use_graph=True)
+            hip.sync()
+            t0 = time.perf_counter()
+            for t in range(3, 3 + steps):
+                b.decode_step_ragged([len(p) + t for p in prompts], use_graph=True)
+            hip.sync()
+            ms = 1e3 * (time.perf_counter() - t0) / steps
+            if n_reg == k:
+                last[name] = np.stack([b.logits(q) for q in (0, 1, SLOTS // 2, SLOTS - 1)])
+            us, launches = b.time_family(fam, n_long, 20)
+            if rep:
+                res["runs"].append({"case": name, "rep": rep, "ms_per_step": round(ms, 4), "attn_launch_us": round(us, 2),
+                                    "attn_launches_per_step": launches, "sequences_sharing_per_prefix": sharing})
+    host.set_prefix_decode_shared(None)
+    res["same_logits_on_and_off"] = bool(np.array_equal(last["off"], last["on"]))
+    for name, _, _ in cases:
+        r = [x for x in res["runs"] if x["case"] == name]
+        res[name] = {"ms_per_step": spread([x["ms_per_step"] for x in r]), "attn_launch_us": spread([x["attn_launch_us"] for x in r]),
+                     "sequences_sharing_per_prefix": r[0]["sequences_sharing_per_prefix"]}
+    b.close()
+    return res
+
+
+def step_serve_prefixes():
+    hip, host, cfg, b = full_size_batch()
+    k = N_PREFIXES
+    prefixes, prompts, budgets = queue_over(host, cfg, k)
+    res = {"slots": SLOTS, "prompts": QUEUE, "prefixes": k, "prefix_ids": DEC_PREFIX, "own_ids": "64..256", "runs": []}
+
+    def register(n_reg):
+        for w in range(k):
+            b.set_prefix_at(w, prefixes[w] if w < n_reg else None)
+
+    for n_reg in (1, k):                                                   # warm-up
+        register(n_reg)
+        b.serve(prompts[:SLOTS], CTX, -1, 8, max_new=4)
+    ids = {}
+    for rep in range(REPS):
+        for name, n_reg in (("index_0_only", 1), ("all", k)):
+            register(n_reg)
+            sh0 = [b.prefixes_info(w)[1] for w in range(k)]
+            rows0 = b.prefix_info()[2]
+            t0 = time.perf_counter()
+            got, st = b.serve(prompts, CTX, -1, 8, max_new_each=budgets)
+            wall = time.perf_counter() - t0
+            res["runs"].append({"registered": name, "rep": rep, "new_tok_s": round(st["new_tokens"] / wall, 1), "wall_s": round(wall, 4),
+                                "prefill_s": round(st["prefill_s"], 4), "decode_s": round(st["decode_s"], 4), "new_tokens": int(st["new_tokens"]),
+                                "rows_computed": int(b.prefix_info()[2] - rows0),
+                                "prompts_shared_per_prefix": [int(b.prefixes_info(w)[1] - sh0[w]) for w in range(k)]})
+            ids.setdefault(name, got)
+    register(0)
+    res["same_ids_both_ways"] = bool(all(np.array_equal(x, y) for x, y in zip(ids["index_0_only"], ids["all"])))
+    for name in ids:
+        r = [x for x in res["runs"] if x["registered"] == name]
+        res[name] = {"new_tok_s": spread([x["new_tok_s"] for x in r]), "rows_computed": r[0]["rows_computed"]}
+    b.close()
+    return res
+
+
 def step_kernels():
     pkg = load_package()
     hip = pkg.hipabi.load(0)
@@ -268,17 +369,28 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", choices=sorted(STEP_LIMIT_S), default=None)
     ap.add_argument("--decode", action="store_true", help="the decode side: steps decode and serve_decode")
+    ap.add_argument("--prefixes", type=int, default=0, metavar="K", help="several prefixes (2..8): steps prefixes and serve_prefixes")
     ap.add_argument("--merge", nargs="*", default=[], help="name=file.json: results measured elsewhere (the parent commit's runs) recorded beside these")
     a = ap.parse_args()
+    global N_PREFIXES
+    if a.prefixes:
+        if not 2 <= a.prefixes <= 8 or SLOTS % a.prefixes:
+            ap.error("--prefixes: 2, 4 or 8")
+        N_PREFIXES = a.prefixes
     if a.step:
-        res = {"serve": step_serve, "kernels": step_kernels, "decode": step_decode, "serve_decode": step_serve_decode}[a.step]()
+        res = {"serve": step_serve, "kernels": step_kernels, "decode": step_decode, "serve_decode": step_serve_decode,
+               "prefixes": step_prefixes, "serve_prefixes": step_serve_prefixes}[a.step]()
         print(json.dumps(res))
         return 0
     res = {"what": "shared prompt prefix, TinyLlama-1.1B q4 synthetic, %d slots, %d prompts = %d shared ids + 64..256 of their own" % (SLOTS, QUEUE, PREFIX)}
     if a.decode:
         res["what"] = "decode slots behind a shared prefix read one copy of its K / V, TinyLlama-1.1B q4 synthetic, %d slots, %d shared ids + 64..256 of their own" % (SLOTS, DEC_PREFIX)
-    for step in (("decode", "serve_decode") if a.decode else ("kernels", "serve")):
-        p = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[step]), sys.executable, os.path.abspath(__file__), "--step", step],
+    if a.prefixes:
+        res["what"] = "%d shared prefixes at once, TinyLlama-1.1B q4 synthetic, %d slots, %d shared ids + 64..256 of their own, %d slots behind each" % (
+            N_PREFIXES, SLOTS, DEC_PREFIX, SLOTS // N_PREFIXES)
+    for step in (("prefixes", "serve_prefixes") if a.prefixes else ("decode", "serve_decode") if a.decode else ("kernels", "serve")):
+        cmd = [sys.executable, os.path.abspath(__file__), "--step", step] + (["--prefixes", str(N_PREFIXES)] if a.prefixes else [])
+        p = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT_S[step])] + cmd,
                            capture_output=True, text=True)
         if p.returncode != 0:
             sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
