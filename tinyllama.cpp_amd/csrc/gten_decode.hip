@@ -33,10 +33,14 @@
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 #include "gten_hip_prefixes.h"
+#include "gten_hip_groups.h"
 
 #include <cmath>
 #include <vector>
 #include <algorithm>
+
+// records a sequence may read its leading chunks from: the prefixes, then the group records (include/gten_hip_groups.h)
+#define DEC_SHARE_RECORDS (GTEN_PREFIXES_MAX + GTEN_GROUPS_MAX)
 
 using namespace gtd;
 
@@ -233,6 +237,8 @@ struct gten_hip_decoder {
     // count; a sequence shares at most one (share_which[q], on the device which_dev[q] / which_cur[q]).  pfx_hm_tab: the shadows'
     // base pointers on the device, at a fixed address (captured graphs hold it).  pfxn: an index above 0 was set once -- the step
     // launches the _pfxn attention; until then a decoder with a prefix launches _pfx on pfx[0].hm, as before.
+    // GROUP RECORDS (include/gten_hip_groups.h): pfx[GTEN_PREFIXES_MAX + g] is group record g -- the same record, in the same table,
+    // but a snapshot: no watch (kv stays empty, dirty stays 0), imported when it is set.  The first one set switches to _pfxn too.
     struct Pfx {
         uint8_t* hm = nullptr;
         const void** tab = nullptr;     // device: [n_layers][k | v] of the prefix set
@@ -242,10 +248,10 @@ struct gten_hip_decoder {
         char dirty = 0;
         bool stale = false;
         unsigned long long imports = 0;
-    } pfx[GTEN_PREFIXES_MAX];
+    } pfx[DEC_SHARE_RECORDS];
     int* share_dev = nullptr;           // [n_seq] on the device, beside `step`; allocated by the first prefix set at any index
     int* which_dev = nullptr;           // [n_seq] beside it: the prefix index of the sequence's shared chunks
-    uint8_t** pfx_hm_tab = nullptr;     // device: [GTEN_PREFIXES_MAX]
+    uint8_t** pfx_hm_tab = nullptr;     // device: [DEC_SHARE_RECORDS]
     bool pfxn = false;
     std::vector<int> share_rows, share_cur, share_which, which_cur;
     unsigned long long hm_skip_imports = 0;
@@ -1826,6 +1832,21 @@ static void share_end_prefix(gten_hip_decoder* dc, int w)
     for (size_t q = 0; q < dc->share_rows.size(); q++)
         if (dc->share_which[q] == w) dc->share_rows[q] = 0;
 }
+// the import launch of a decoder with share counts: the sequences of `it` from the caches of `tab` into the shadows at `base`, the
+// chunks below share[seq] left out (share null: a prefix or group record's own import, every chunk of its rows)
+static int hm_import_pfx_launch(gten_hip_decoder* dc, const HmImportList& it, const DecStep* step, const void* const* tab, uint8_t* base, const int* share)
+{
+    const gten_hip_decoder_desc& d = dc->d;
+    const size_t kv_pitch = gten_hip_row_bytes(d.adtype, (d.n_embd / d.n_heads) * d.n_kv_heads);
+    const dim3 grid(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, it.n);
+    if (d.adtype == GTEN_Q8)
+        GTR_LAUNCH(KT_PACK, k_kv_import_hm_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 68, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
+                   d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
+    else
+        GTR_LAUNCH(KT_PACK, k_kv_import_hm_f16_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 33 * 4, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
+                   d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
+    return 0;
+}
 static int pre_run(gten_hip_decoder* dc)
 {
     const gten_hip_decoder_desc& d = dc->d;
@@ -1854,17 +1875,10 @@ static int pre_run(gten_hip_decoder* dc)
     //    steps), whoever loses chunks is imported in full, and the prefix shadow is (re)imported before anybody reads it --
     //    after every sharing sequence was taken off it, since the counts above are written first
     auto import_launch = [&](const HmImportList& it, const DecStep* step, const void* const* tab, uint8_t* base, const int* share) -> int {
-        const dim3 grid(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, it.n);
-        if (d.adtype == GTEN_Q8)
-            GTR_LAUNCH(KT_PACK, k_kv_import_hm_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 68, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
-                       d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
-        else
-            GTR_LAUNCH(KT_PACK, k_kv_import_hm_f16_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 33 * 4, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
-                       d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
-        return 0;
+        return hm_import_pfx_launch(dc, it, step, tab, base, share);
     };
     if (dc->share_dev) {
-        for (int w = 0; w < GTEN_PREFIXES_MAX; w++) {
+        for (int w = 0; w < GTEN_PREFIXES_MAX; w++) {           // (a group record keeps no watch: never dirty)
             gten_hip_decoder::Pfx& x = dc->pfx[w];
             if (!x.dirty) continue;                    // somebody wrote into prefix w's rows: nobody shares what ITS shadow holds
             x.dirty = 0;
@@ -1878,7 +1892,7 @@ static int pre_run(gten_hip_decoder* dc)
             sl.n = 0;
             return 0;
         };
-        bool any[GTEN_PREFIXES_MAX] = {};
+        bool any[DEC_SHARE_RECORDS] = {};
         for (int q = 0; q < dc->n_seq; q++) {
             if (dc->share_rows[(size_t)q] && (dc->hm_dirty[(size_t)q] & 1)) dc->share_rows[(size_t)q] = 0;      // written since the promise
             const int w = dc->share_which[(size_t)q];
@@ -2524,6 +2538,45 @@ int gten_hip_set_prefix_decode_shared(int on)
     return 0;
 }
 
+// record w (a prefix index, or GTEN_PREFIXES_MAX + a group record) is about to be set: what its first use, and the first use of any
+// record, allocate -- and the switch of the step's attention that goes with it
+static int share_record_ready(gten_hip_decoder* dc, int w)
+{
+    const gten_hip_decoder_desc& d = dc->d;
+    gten_hip_decoder::Pfx& x = dc->pfx[w];
+    const size_t L2 = (size_t)d.n_layers * 2;
+    const bool first_any = !dc->share_dev, first_n = w > 0 && !dc->pfxn;
+    if (first_any || first_n) {
+        // first use of a prefix: the step's attention becomes the _pfx instantiation; first use of an index above 0 or of a group
+        // record: the _pfxn instantiation.  Either way the graphs captured so far go, once.
+        GTR_CHECK(hipStreamSynchronize(stream()));
+        GTR_CHECK(drop_graphs(dc));
+    }
+    if (first_any) {
+        GTR_CHECK(hipMalloc((void**)&dc->share_dev, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMemset(dc->share_dev, 0, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMalloc((void**)&dc->which_dev, (size_t)dc->n_seq * sizeof(int)));
+        GTR_CHECK(hipMemset(dc->which_dev, 0, (size_t)dc->n_seq * sizeof(int)));
+        // (allocated once, with the group records' entries behind the prefixes': captured graphs hold its address)
+        GTR_CHECK(hipMalloc((void**)&dc->pfx_hm_tab, DEC_SHARE_RECORDS * sizeof(uint8_t*)));
+        GTR_CHECK(hipMemset(dc->pfx_hm_tab, 0, DEC_SHARE_RECORDS * sizeof(uint8_t*)));
+        dc->share_rows.assign((size_t)dc->n_seq, 0);
+        dc->share_cur.assign((size_t)dc->n_seq, 0);
+        dc->share_which.assign((size_t)dc->n_seq, 0);
+        dc->which_cur.assign((size_t)dc->n_seq, 0);
+    }
+    if (first_n) dc->pfxn = true;
+    if (!x.hm) {
+        // first use of this index: its shadow, and its entry of the table (nobody reads the entry before a count names it)
+        GTR_CHECK(hipMalloc((void**)&x.tab, L2 * sizeof(void*)));
+        GTR_CHECK(hipMalloc((void**)&x.step, sizeof(DecStep)));
+        GTR_CHECK(hipMalloc((void**)&x.hm, dc->hm_seq_stride));
+        GTR_CHECK(hipMemset(x.hm, 0, dc->hm_seq_stride));
+        GTR_CHECK(hipMemcpy(dc->pfx_hm_tab + w, &x.hm, sizeof(uint8_t*), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
 /* ---- several prefixes (include/gten_hip_prefixes.h): the calls of one prefix are these with which = 0 */
 int gten_hip_decoder_prefixes_set(gten_hip_decoder* dc, int which, const gten_hip_kv_ptrs* kv, int prefix_len)
 {
@@ -2548,34 +2601,7 @@ int gten_hip_decoder_prefixes_set(gten_hip_decoder* dc, int which, const gten_hi
     // (k_hm_share_set's entries are sequence | chunks << 10 | index << 16)
     GTR_REQUIRE(dc->n_seq <= 1024 && dc->n_chunks < 64, "decoder_prefixes_set: %d sequences (at most 1024) x %d chunks (at most 63)", dc->n_seq, dc->n_chunks);
     const size_t L2 = (size_t)d.n_layers * 2;
-    const bool first_any = !dc->share_dev, first_n = which > 0 && !dc->pfxn;
-    if (first_any || first_n) {
-        // first use of a prefix: the step's attention becomes the _pfx instantiation; first use of an index above 0: the _pfxn
-        // instantiation.  Either way the graphs captured so far go, once.
-        GTR_CHECK(hipStreamSynchronize(stream()));
-        GTR_CHECK(drop_graphs(dc));
-    }
-    if (first_any) {
-        GTR_CHECK(hipMalloc((void**)&dc->share_dev, (size_t)dc->n_seq * sizeof(int)));
-        GTR_CHECK(hipMemset(dc->share_dev, 0, (size_t)dc->n_seq * sizeof(int)));
-        GTR_CHECK(hipMalloc((void**)&dc->which_dev, (size_t)dc->n_seq * sizeof(int)));
-        GTR_CHECK(hipMemset(dc->which_dev, 0, (size_t)dc->n_seq * sizeof(int)));
-        GTR_CHECK(hipMalloc((void**)&dc->pfx_hm_tab, GTEN_PREFIXES_MAX * sizeof(uint8_t*)));
-        GTR_CHECK(hipMemset(dc->pfx_hm_tab, 0, GTEN_PREFIXES_MAX * sizeof(uint8_t*)));
-        dc->share_rows.assign((size_t)dc->n_seq, 0);
-        dc->share_cur.assign((size_t)dc->n_seq, 0);
-        dc->share_which.assign((size_t)dc->n_seq, 0);
-        dc->which_cur.assign((size_t)dc->n_seq, 0);
-    }
-    if (first_n) dc->pfxn = true;
-    if (!x.hm) {
-        // first use of this index: its shadow, and its entry of the table (nobody reads the entry before a count names it)
-        GTR_CHECK(hipMalloc((void**)&x.tab, L2 * sizeof(void*)));
-        GTR_CHECK(hipMalloc((void**)&x.step, sizeof(DecStep)));
-        GTR_CHECK(hipMalloc((void**)&x.hm, dc->hm_seq_stride));
-        GTR_CHECK(hipMemset(x.hm, 0, dc->hm_seq_stride));
-        GTR_CHECK(hipMemcpy(dc->pfx_hm_tab + which, &x.hm, sizeof(uint8_t*), hipMemcpyHostToDevice));
-    }
+    if (int rc = share_record_ready(dc, which)) return rc;
     for (int l = 0; l < d.n_layers; l++) { x.kv.push_back(kv[l].kcache); x.kv.push_back(kv[l].vcache); }
     const DecStep st{prefix_len + 1, 0, 0};
     GTR_CHECK(hipMemcpyAsync(x.tab, x.kv.data(), L2 * sizeof(void*), hipMemcpyHostToDevice, stream()));
@@ -2588,26 +2614,33 @@ int gten_hip_decoder_prefixes_set(gten_hip_decoder* dc, int which, const gten_hi
     return 0;
 }
 
-int gten_hip_decoder_prefixes_share(gten_hip_decoder* dc, int seq, int which, int rows)
+// the promise "rows [0, rows) of sequence seq's own caches equal record w's" (a prefix's or a group record's: `kind` / `index` are
+// how the caller's refusals name it); the arguments' ranges were checked by the caller
+static int share_promise(gten_hip_decoder* dc, int seq, int w, int rows, const char* call, const char* kind, int index)
 {
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_prefixes_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
-    GTR_REQUIRE(which >= 0 && which < GTEN_PREFIXES_MAX, "decoder_prefixes_share: prefix index %d outside [0, %d)", which, GTEN_PREFIXES_MAX);
     if (!dc->hm) return 0;
     if (rows == 0) { share_end(dc, seq); return 0; }
-    const gten_hip_decoder::Pfx& x = dc->pfx[which];
-    GTR_REQUIRE(x.len > 0 && rows <= x.len, "decoder_prefixes_share: %d rows, prefix %d has %d", rows, which, x.len);
+    const gten_hip_decoder::Pfx& x = dc->pfx[w];
+    GTR_REQUIRE(x.len > 0 && rows <= x.len, "%s: %d rows, %s %d has %d", call, rows, kind, index, x.len);
     // the sequence's next step, where the decoder knows it: a started slot, or -- outside the slot view -- a sequence that was
     // stepped and whose rows nobody wrote since
     int n_next = 0;
     if (!dc->slots.empty()) { if (dc->slots[(size_t)seq].advance & 1) n_next = dc->slots[(size_t)seq].n; }
     else if (!dc->hm_dirty[(size_t)seq]) n_next = !dc->dev_ns.empty() ? dc->dev_ns[(size_t)seq] : std::max(dc->dev_n, 0);
-    GTR_REQUIRE(n_next == 0 || rows <= n_next - 1, "decoder_prefixes_share: %d rows, sequence %d is at position %d", rows, seq, n_next - 1);
+    GTR_REQUIRE(n_next == 0 || rows <= n_next - 1, "%s: %d rows, sequence %d is at position %d", call, rows, seq, n_next - 1);
     if (!g_pfx_shared) return 0;                       // (switched off: nothing is recorded)
     dc->share_rows[(size_t)seq] = rows;
-    dc->share_which[(size_t)seq] = which;
+    dc->share_which[(size_t)seq] = w;
     if (dc->hm_dirty[(size_t)seq]) dc->hm_dirty[(size_t)seq] = 2;       // what was written BEFORE the promise is what it speaks about
     return 0;
+}
+
+int gten_hip_decoder_prefixes_share(gten_hip_decoder* dc, int seq, int which, int rows)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_prefixes_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
+    GTR_REQUIRE(which >= 0 && which < GTEN_PREFIXES_MAX, "decoder_prefixes_share: prefix index %d outside [0, %d)", which, GTEN_PREFIXES_MAX);
+    return share_promise(dc, seq, which, rows, "decoder_prefixes_share", "prefix", which);
 }
 
 // (the chunks a step enqueued NOW would read from a prefix shadow: the promise as pre_run would take it)
@@ -2635,8 +2668,9 @@ int gten_hip_decoder_prefixes_info(gten_hip_decoder* dc, int seq, int which, int
         int wq = -1;
         if (share_chunks_now(dc, q, &wq) > 0 && wq == which) n++;
     }
-    if (seq_which) *seq_which = w;
-    if (seq_chunks) *seq_chunks = chunks;
+    // (a sequence that reads from a group record shares no prefix: include/gten_hip_groups.h)
+    if (seq_which) *seq_which = w < GTEN_PREFIXES_MAX ? w : -1;
+    if (seq_chunks) *seq_chunks = w < GTEN_PREFIXES_MAX ? chunks : 0;
     if (prefix_len) *prefix_len = dc->pfx[which].len;
     if (prefix_imports) *prefix_imports = dc->pfx[which].imports;
     if (sharers) *sharers = n;
@@ -2664,6 +2698,72 @@ int gten_hip_decoder_prefix_info(gten_hip_decoder* dc, int seq, int* prefix_len,
     if (seq_chunks) *seq_chunks = w == 0 ? chunks : 0;               // (this call speaks of prefix 0)
     if (prefix_imports) *prefix_imports = dc->pfx[0].imports;
     if (imports_skipping) *imports_skipping = dc->hm_skip_imports;
+    return 0;
+}
+
+/* ---- group records (include/gten_hip_groups.h): record g is dc->pfx[GTEN_PREFIXES_MAX + g], a snapshot without a watch */
+int gten_hip_decoder_group_set(gten_hip_decoder* dc, int g, const gten_hip_kv_ptrs* kv, int rows)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && rows >= 0, "decoder_group_set: bad arguments");
+    GTR_REQUIRE(g >= 0 && g < GTEN_GROUPS_MAX, "decoder_group_set: group record %d outside [0, %d)", g, GTEN_GROUPS_MAX);
+    if (!dc->hm) return 0;
+    const gten_hip_decoder_desc& d = dc->d;
+    if (kv && rows > 0) {
+        GTR_REQUIRE(rows <= d.max_ctx, "decoder_group_set: %d rows, context %d", rows, d.max_ctx);
+        for (int l = 0; l < d.n_layers; l++) GTR_REQUIRE(kv[l].kcache && kv[l].vcache, "decoder_group_set: null cache pointer (layer %d)", l);
+    }
+    const int w = GTEN_PREFIXES_MAX + g;
+    gten_hip_decoder::Pfx& x = dc->pfx[w];
+    // the sequences that share THIS record come off it first (the next pre_run zeroes their counts and imports their own rows in
+    // full); every step queued so far read the old snapshot in stream order, every later one follows that pre_run
+    share_end_prefix(dc, w);
+    x.len = 0;
+    if (!kv || rows == 0) return 0;
+    GTR_REQUIRE(dc->n_seq <= 1024 && dc->n_chunks < 64, "decoder_group_set: %d sequences (at most 1024) x %d chunks (at most 63)", dc->n_seq, dc->n_chunks);
+    if (int rc = share_record_ready(dc, w)) return rc;
+    const size_t L2 = (size_t)d.n_layers * 2;
+    std::vector<const void*> ptrs;
+    for (int l = 0; l < d.n_layers; l++) { ptrs.push_back(kv[l].kcache); ptrs.push_back(kv[l].vcache); }
+    const DecStep st{rows + 1, 0, 0};
+    GTR_CHECK(hipMemcpyAsync(x.tab, ptrs.data(), L2 * sizeof(void*), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(x.step, &st, sizeof(DecStep), hipMemcpyHostToDevice, stream()));
+    // the snapshot itself, now: behind it the record does not depend on the source rows (no watch is kept on them)
+    HmImportList one{};
+    one.n = 1;
+    if (int rc = hm_import_pfx_launch(dc, one, x.step, (const void* const*)x.tab, x.hm, nullptr)) return rc;
+    GTR_CHECK(hipStreamSynchronize(stream()));         // (`st` and `ptrs` live on this stack frame)
+    x.len = rows;
+    x.stale = false;
+    x.imports++;
+    return 0;
+}
+
+int gten_hip_decoder_group_share(gten_hip_decoder* dc, int seq, int g, int rows)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq && rows >= 0, "decoder_group_share: sequence %d outside [0, %d) or rows %d < 0", seq, dc ? dc->n_seq : 0, rows);
+    GTR_REQUIRE(g >= 0 && g < GTEN_GROUPS_MAX, "decoder_group_share: group record %d outside [0, %d)", g, GTEN_GROUPS_MAX);
+    return share_promise(dc, seq, GTEN_PREFIXES_MAX + g, rows, "decoder_group_share", "group record", g);
+}
+
+int gten_hip_decoder_groups_info(gten_hip_decoder* dc, int seq, int g, int* seq_group, int* seq_chunks, int* rows, unsigned long long* imports, int* sharers)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_groups_info: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    GTR_REQUIRE(g >= 0 && g < GTEN_GROUPS_MAX, "decoder_groups_info: group record %d outside [0, %d)", g, GTEN_GROUPS_MAX);
+    int w = -1;
+    const int chunks = share_chunks_now(dc, seq, &w);
+    int n = 0;
+    for (int q = 0; q < dc->n_seq; q++) {
+        int wq = -1;
+        if (share_chunks_now(dc, q, &wq) > 0 && wq == GTEN_PREFIXES_MAX + g) n++;
+    }
+    if (seq_group) *seq_group = w >= GTEN_PREFIXES_MAX ? w - GTEN_PREFIXES_MAX : -1;
+    if (seq_chunks) *seq_chunks = w >= GTEN_PREFIXES_MAX ? chunks : 0;
+    if (rows) *rows = dc->pfx[GTEN_PREFIXES_MAX + g].len;
+    if (imports) *imports = dc->pfx[GTEN_PREFIXES_MAX + g].imports;
+    if (sharers) *sharers = n;
     return 0;
 }
 

@@ -121,6 +121,10 @@ class GtenHip:
                              "gten_hip_set_prefix_decode_shared"]          # include/gten_hip_prefix_decode.h
     PREFIXES_SYMBOLS = ["gten_hip_decoder_prefixes_set", "gten_hip_decoder_prefixes_share",
                         "gten_hip_decoder_prefixes_info"]                  # include/gten_hip_prefixes.h
+    GROUPS_SYMBOLS = ["gten_hip_decoder_group_set", "gten_hip_decoder_group_share",
+                      "gten_hip_decoder_groups_info"]                      # include/gten_hip_groups.h
+    GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
+    PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -159,6 +163,10 @@ class GtenHip:
         self._block_rows_prefixed = _sig(L, "gten_hip_block_rows_prefixed", ci, [C.POINTER(BlockDesc), ci, vp, vp, ci])
         self._set_block_rows = _sig(L, "gten_hip_set_block_rows", ci, [ci])
         self._prefix_decode_shared = _sig(L, "gten_hip_set_prefix_decode_shared", ci, [ci])
+        self._group_set = _sig(L, "gten_hip_decoder_group_set", ci, [vp, ci, vp, ci])
+        self._group_share = _sig(L, "gten_hip_decoder_group_share", ci, [vp, ci, ci, ci])
+        self._groups_info = _sig(L, "gten_hip_decoder_groups_info", ci, [vp, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
+                                                                         C.POINTER(C.c_ulonglong), C.POINTER(ci)])
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
         self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
         self._decode_persistent = _sig(L, "gten_hip_set_decode_persistent", ci, [ci])
@@ -548,6 +556,25 @@ class GtenHip:
         """decoders created from now on: the single-sequence attention as k_dec_attn_one64w (0 / False, the default), as
         k_dec_attn_one64 (1 / True, the A/B control) or as k_dec_attn_one64v (2) -- the same bytes (include/gten_hip_ab.h)"""
         self._check(self._decode_attn_classic(int(on)))
+
+    def decoder_group_set(self, dec, g, kv, rows):
+        """gten_hip_decoder_group_set on a raw decoder handle (include/gten_hip_groups.h): group record g becomes a snapshot of rows
+        [0, rows) of the caches kv -- device addresses [n_layers][k, v] -- or is released (kv None); the return code"""
+        if kv is None:
+            return self._group_set(dec, int(g), None, 0)
+        kv = np.ascontiguousarray(kv, dtype=np.uint64).reshape(-1, 2)
+        return self._group_set(dec, int(g), kv.ctypes.data_as(C.c_void_p), int(rows))
+
+    def decoder_group_share(self, dec, seq, g, rows):
+        """gten_hip_decoder_group_share: "rows [0, rows) of sequence seq's own caches equal record g"; 0, or the refusal's code"""
+        return self._group_share(dec, int(seq), int(g), int(rows))
+
+    def decoder_groups_info(self, dec, seq, g=0):
+        """gten_hip_decoder_groups_info: (record sequence seq reads from or -1, chunks it reads there, rows of record g, imports of
+        record g's shadow so far, its sharers now)"""
+        sg, ch, rows, imp, sh = C.c_int(-1), C.c_int(0), C.c_int(0), C.c_ulonglong(0), C.c_int(0)
+        self._check(self._groups_info(dec, int(seq), int(g), C.byref(sg), C.byref(ch), C.byref(rows), C.byref(imp), C.byref(sh)))
+        return sg.value, ch.value, rows.value, imp.value, sh.value
 
     def set_prefix_decode_shared(self, on):
         """decode slots behind a shared prefix read ONE copy of its K / V (default) or each its own (include/gten_hip_prefix_decode.h)"""

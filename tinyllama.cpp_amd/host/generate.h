@@ -611,19 +611,20 @@ struct ServePolicy {
         fsm_ended[(size_t)j] = 1;
         return true;
     }
+    // (copy_of: the items that are copies of another item's prompt pass, TinyLlamaBatch::prefill_many_with; null: none)
     void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
-              std::vector<int>* first)
+              std::vector<int>* first, const std::vector<int>* copy_of = nullptr)
     {
         if constexpr (M == 0) {
             (void)js;
-            b.prefill_many(sets, ps, first);
+            b.prefill_many(sets, ps, first, nullptr, copy_of);
         } else {
             if constexpr (kLogprobs) rec.ensure((int)sets.size());
             std::vector<float*> lo((size_t)sets.size(), nullptr);
             b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
                 draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data(), &fh);
                 if constexpr (kFsm) note_first(js[(size_t)k], fh.after);
-            });
+            }, copy_of);
             if constexpr (kLogprobs)
                 for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
         }
@@ -645,11 +646,12 @@ struct ServePolicy {
 
 // ---- gten_host_batch_serve2's packing around a queue (and its _topk / _biased / _lp forms): the prompts in, a decoder that
 // refuses tables or records heard before the queue starts, the rows and the stats list out.  out and rows are
+// (group_of, include/gten_host_samples.h: per item the sample group it belongs to, -1 none; null: no groups)
 // max(max_tokens, max_prompt) positions per prompt.  0; -1: bad arguments; otherwise the code of the decoder's refusal.
 template <unsigned M>
 int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
                 int eos, int slice, int max_new, const int32_t* max_new_each, int32_t* out, int32_t* n_total, double* stats, int n_stats,
-                const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr)
+                const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr, const int32_t* group_of = nullptr)
 {
     if (n_prompts <= 0 || max_tokens <= 0 || slice <= 0) return -1;
     for (int j = 0; j < n_prompts; j++)
@@ -696,7 +698,7 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
     std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
     for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
     ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len, n_prompts);
-    const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, pick);
+    const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, {group_of, -1}, pick);
     for (int j = 0; j < n_prompts; j++) {
         const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, n_prompt[j]));
         std::memcpy(out + (size_t)j * row_len, res[(size_t)j].data(), (size_t)take * sizeof(int32_t));

@@ -622,7 +622,21 @@ inline PrefixesDecode& prefixes_decode()
     static PrefixesDecode p;
     return p;
 }
+// ... and the entry points of the GROUP RECORDS (include/gten_hip_groups.h), installed by host/capi_samples.cpp in the same way.
+// Without them the members of a sample group decode on their own copies of the prompt's rows.
+struct GroupsDecode {
+    int (*set)(gten_hip_decoder* dec, int g, const gten_hip_kv_ptrs* kv, int rows) = nullptr;
+    int (*share)(gten_hip_decoder* dec, int seq, int g, int rows) = nullptr;
+    int (*info)(gten_hip_decoder* dec, int seq, int g, int* seq_group, int* seq_chunks, int* rows, unsigned long long* imports, int* sharers) = nullptr;
+};
+inline GroupsDecode& groups_decode()
+{
+    static GroupsDecode p;
+    return p;
+}
 } // namespace detail
+
+constexpr int kGroupsMax = 64;           // group records of a decoder (GTEN_GROUPS_MAX; host/capi_samples.cpp checks that they agree)
 
 // an array with one value per item, or one value for all of them
 template <class T>
@@ -703,34 +717,51 @@ public:
     // prompts[k] (>= 16 ids each, kPreRows in all, at most kPreMax) onto the caches of sequence slots[k]; first[k] = argmax of
     // prompt k's logits (strict >, first maximum: tinyllama.cpp:416-424); logits_out[k], when given, receives them
     void prefill_many(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
-                      std::vector<float*>* logits_out = nullptr)
+                      std::vector<float*>* logits_out = nullptr, const std::vector<int>* copy_of = nullptr)
     {
         prefill_many_with(slots, prompts, first, logits_out, [](int, const float* lg, int n, int32_t* out) {
             GTEN_HIP_OK(gten_hip_argmax_row(lg, n, out));
-        });
+        }, copy_of);
     }
     // ... with the first id of prompt k (its logits row lg on the device) written to out by pick(k, lg, n_vocab, out)
+    // COPIES (sample groups): (*copy_of)[k] = -1: item k is computed, as all are without the list; = c: item k has
+    // THE SAME IDS as item c of this call, which is computed (the caller's word: nothing is compared).  A copy adds no rows to the
+    // matrix: its set is one more destination of the very ranges item c's set receives -- the prefix rows in front where c takes
+    // a registered prefix's short way, then c's own rows out of the matrix -- and carries the same marks; its first id is drawn
+    // by pick(k, ...) from c's logits row while that row is alive.  kPreMax and kPreRows count computed prompts only.
     template <class Pick>
     void prefill_many_with(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
-                           std::vector<float*>* logits_out, Pick pick)
+                           std::vector<float*>* logits_out, Pick pick, const std::vector<int>* copy_of = nullptr)
     {
         const int K = (int)slots.size();
-        GTEN_ASSERTM(K >= 1 && K <= kPreMax && prompts.size() == slots.size(), "prefill_many: %d prompts", K);
+        GTEN_ASSERTM(K >= 1 && prompts.size() == slots.size() && (!copy_of || copy_of->size() == slots.size()), "prefill_many: %d prompts", K);
+        int computed = 0;
+        std::vector<std::vector<int>> copies((size_t)K);               // per computed item: the items that copy it
+        for (int k = 0; k < K; k++) {
+            const int c = copy_of ? (*copy_of)[(size_t)k] : -1;
+            if (c < 0) { computed++; continue; }
+            GTEN_ASSERTM(c < K && c != k && (*copy_of)[(size_t)c] < 0 && prompts[(size_t)c]->size() == prompts[(size_t)k]->size(),
+                         "prefill_many: item %d copies item %d", k, c);
+            copies[(size_t)c].push_back(k);
+        }
+        GTEN_ASSERTM(computed >= 1 && computed <= kPreMax, "prefill_many: %d prompts to compute (at most %d)", computed, kPreMax);
         ensure_pre();
         for (const auto* p : prompts) GTEN_ASSERTM((int)p->size() >= 16 && (int)p->size() <= n_ctx_, "prefill_many: a prompt of %zu ids", p->size());
         first->assign((size_t)K, 0);
         // a prompt's first id: its logits row stays on the device and so does the sampler (gten_hip_argmax_row, the greedy rule
         // of tinyllama.cpp:416-424) -- the K ids come back in ONE 4 K-byte copy and one wait instead of K copies of 128 KB, K
         // waits and K host loops over the vocabulary (round 4); a caller that wants a prompt's logits gets them as before
-        if (!first_ids_) first_ids_.reset(new Tensor({kPreMax}, kInt32));
+        // (one word per ITEM of the call, copies included)
+        if (!first_ids_ || first_ids_->numel() < K) first_ids_.reset(new Tensor({std::max(K, kPreMax)}, kInt32));
         int32_t* ids_dev = (int32_t*)first_ids_->device_ptr_mut();
         // the prompts that begin with a registered prefix (set_prefix_at; the longest one, prefix_of) are one row matrix per prefix
         // of what follows it, the others one of whole prompts: one call per group
         std::vector<int> group[kPrefixesMax + 1];
-        for (int k = 0; k < K; k++) group[prefix_of(*prompts[(size_t)k]) + 1].push_back(k);
+        for (int k = 0; k < K; k++)
+            if (!copy_of || (*copy_of)[(size_t)k] < 0) group[prefix_of(*prompts[(size_t)k]) + 1].push_back(k);
         for (int w = 0; w < kPrefixesMax; w++)
-            if (!group[w + 1].empty()) prefill_group(group[w + 1], w, slots, prompts, logits_out, ids_dev, pick);
-        if (!group[0].empty()) prefill_group(group[0], -1, slots, prompts, logits_out, ids_dev, pick);
+            if (!group[w + 1].empty()) prefill_group(group[w + 1], w, slots, prompts, logits_out, ids_dev, pick, copies);
+        if (!group[0].empty()) prefill_group(group[0], -1, slots, prompts, logits_out, ids_dev, pick, copies);
         std::vector<int32_t> got((size_t)K);
         GTEN_HIP_OK(gten_hip_memcpy_d2h(got.data(), ids_dev, (size_t)K * sizeof(int32_t)));
         for (int k = 0; k < K; k++) (*first)[(size_t)k] = got[(size_t)k];
@@ -870,9 +901,13 @@ private:
     // prompts[idx[..]] as ONE row matrix: whole (w < 0, P = 0) or what follows prefix w's P ids
     template <class Pick>
     void prefill_group(const std::vector<int>& idx, int w, const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts,
-                       std::vector<float*>* logits_out, int32_t* ids_dev, Pick& pick)
+                       std::vector<float*>* logits_out, int32_t* ids_dev, Pick& pick, const std::vector<std::vector<int>>& copies)
     {
         const int P = w >= 0 ? (int)pfx_[w].ids.size() : 0;
+        for (int k : idx) {                                    // (sample groups: what the copies of these prompts did not cost)
+            samples_copies_ += copies[(size_t)k].size();
+            samples_rows_saved_ += copies[(size_t)k].size() * (prompts[(size_t)k]->size() - (size_t)P);
+        }
         std::vector<int32_t> ids, starts{0};
         for (int k : idx) {
             const std::vector<int32_t>& p = *prompts[(size_t)k];
@@ -895,19 +930,23 @@ private:
             AttentionBlock& src = pre_->block(l);
             const size_t pitch = (size_t)src.attn.key.acv.bstride(0);
             for (size_t i = 0; i < idx.size(); i++) {
-                const int k = idx[i];
-                if (ranges.size() + (P > 0 ? 4 : 2) > (size_t)GTEN_HIP_MAX_COPY_RANGES) flush();
-                AttentionBlock& dst = cset(slots[(size_t)k]).block(l);
-                uint8_t* dk = (uint8_t*)dst.attn.key.acv.device_ptr_mut();
-                uint8_t* dv = (uint8_t*)dst.attn.value.acv.device_ptr_mut();
-                if (P > 0) {
-                    AttentionBlock& pre = pfx_[w].set->block(l);
-                    ranges.push_back({dk, pre.attn.key.acv.device_ptr(), (size_t)P * pitch});
-                    ranges.push_back({dv, pre.attn.value.acv.device_ptr(), (size_t)P * pitch});
+                const std::vector<int>& cp = copies[(size_t)idx[i]];
+                // (the prompt's own set, then the sets of its copies: further destinations of the same sources)
+                for (size_t t = 0; t <= cp.size(); t++) {
+                    const int k = t == 0 ? idx[i] : cp[t - 1];
+                    if (ranges.size() + (P > 0 ? 4 : 2) > (size_t)GTEN_HIP_MAX_COPY_RANGES) flush();
+                    AttentionBlock& dst = cset(slots[(size_t)k]).block(l);
+                    uint8_t* dk = (uint8_t*)dst.attn.key.acv.device_ptr_mut();
+                    uint8_t* dv = (uint8_t*)dst.attn.value.acv.device_ptr_mut();
+                    if (P > 0) {
+                        AttentionBlock& pre = pfx_[w].set->block(l);
+                        ranges.push_back({dk, pre.attn.key.acv.device_ptr(), (size_t)P * pitch});
+                        ranges.push_back({dv, pre.attn.value.acv.device_ptr(), (size_t)P * pitch});
+                    }
+                    const size_t off = (size_t)starts[i] * pitch, bytes = (size_t)(starts[i + 1] - starts[i]) * pitch;
+                    ranges.push_back({dk + (size_t)P * pitch, (const uint8_t*)src.attn.key.acv.device_ptr() + off, bytes});
+                    ranges.push_back({dv + (size_t)P * pitch, (const uint8_t*)src.attn.value.acv.device_ptr() + off, bytes});
                 }
-                const size_t off = (size_t)starts[i] * pitch, bytes = (size_t)(starts[i + 1] - starts[i]) * pitch;
-                ranges.push_back({dk + (size_t)P * pitch, (const uint8_t*)src.attn.key.acv.device_ptr() + off, bytes});
-                ranges.push_back({dv + (size_t)P * pitch, (const uint8_t*)src.attn.value.acv.device_ptr() + off, bytes});
             }
             flush();
         }
@@ -916,17 +955,24 @@ private:
         // were announced: a later write into the set ends the promise on the decoder's side).  Inside serve() the mark travels
         // with the set and becomes gten_hip_decoder_slot_share when a slot is started on it.
         for (size_t i = 0; i < idx.size(); i++) {
-            const int c = slots[(size_t)idx[i]];
-            share_mark(c) = P;
-            which_mark(c) = P > 0 ? w : 0;
-            if (P > 0 && !in_serve_ && c < n_seq() && dec_) (void)decoder_share(c, w, P);     // (refused -- the sequence is mid-run at a position inside the prefix --: it decodes on its own copy)
+            const std::vector<int>& cp = copies[(size_t)idx[i]];
+            for (size_t t = 0; t <= cp.size(); t++) {
+                const int c = slots[(size_t)(t == 0 ? idx[i] : cp[t - 1])];
+                share_mark(c) = P;
+                which_mark(c) = P > 0 ? w : 0;
+                if (P > 0 && !in_serve_ && c < n_seq() && dec_) (void)decoder_share(c, w, P);     // (refused -- the sequence is mid-run at a position inside the prefix --: it decodes on its own copy)
+            }
         }
         for (size_t i = 0; i < idx.size(); i++) {
-            const int k = idx[i];
+            const std::vector<int>& cp = copies[(size_t)idx[i]];
             const Tensor lg = pre_->logits_of_row(hidden, starts[i + 1] - 1);
-            pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
-            if (logits_out && (*logits_out)[(size_t)k])
-                std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
+            // (the copies draw from this row before the next prompt's logits replace it: each with its own request, through pick)
+            for (size_t t = 0; t <= cp.size(); t++) {
+                const int k = t == 0 ? idx[i] : cp[t - 1];
+                pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
+                if (logits_out && (*logits_out)[(size_t)k])
+                    std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
+            }
         }
     }
 
@@ -1059,9 +1105,15 @@ public:
     // With Pick::kFsm a prompt may be bound to a token automaton (include/gten_hip_fsm.h): the id that enters a final state ends it as
     // an eos does but is kept (ended_first / states / enters_final), and its binding is set again wherever it goes on (bind_state).
     // (max_new[j] > 0 additionally bounds the new ids of prompt j)
+    // SAMPLE GROUPS (include/gten_host_samples.h): group_of[j] >= 0 names the group of queue item j; consecutive items
+    // of one group hold THE SAME PROMPT -- the caller's word, no prompt is compared.  prepare_many takes whole groups while free
+    // sets and rows allow: the first member taken is computed, the others are copies of it (prefill_many_with's copy_of); a group
+    // that does not fit is cut, and what is left is a later group with a prompt pass of its own.  Ids and records are those of
+    // the same items without groups.  Sets written for a group of at least two readied members behind at least one full chunk carry
+    // a group mark; a slot started on such a set reads the prompt's full chunks from a group record of the decoder (GroupRecords).
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
-                          std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Pick& pick)
+                          std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Each<int32_t> group_of, Pick& pick)
     {
         using clock = std::chrono::steady_clock;
         ensure_decoder();
@@ -1130,6 +1182,66 @@ public:
             }
             ~Rebind() { run(); }
         } rebind{this, S};
+        // GROUP RECORDS.  One Group per prompt pass whose sets carry a mark: the members that are ready or live, the decoder's
+        // record they read from (-1: none yet, or none was free) and the prompt's rows.  The mark travels with the cache set
+        // (set_group), as share_mark does; the first member that starts takes a free record and snapshots ITS set's rows into it
+        // (the rows are the truth: every member's set holds the same ones), every member then promises its own rows equal it.
+        // When the last member has ended the record is released and goes back to the free list.  No mark and no record outlives
+        // the call, however it is left.
+        struct Group { int members = 0, rec = -1, rows = 0; bool counted = false; };
+        struct GroupRecords {
+            TinyLlamaBatch* b;
+            std::vector<Group> groups;
+            std::vector<int> set_group;                                    // per cache set: its group (-1: no mark)
+            std::vector<int> free_rec;
+            explicit GroupRecords(TinyLlamaBatch* b_) : b{b_}, set_group((size_t)b_->n_sets(), -1)
+            {
+                const detail::GroupsDecode& h = detail::groups_decode();
+                const int cap = (h.set && h.share) ? (b->groups_cap_ < 0 ? kGroupsCapDefault : std::min(b->groups_cap_, kGroupsMax)) : 0;
+                for (int g = cap - 1; g >= 0; g--) free_rec.push_back(g);
+            }
+            void mark(int c, int gi) { set_group[(size_t)c] = gi; }
+            // slot q was started on set c (kv: its caches): true when it now reads the prompt's chunks from its group's record
+            bool start(int q, int c, const gten_hip_kv_ptrs* kv)
+            {
+                const int gi = set_group[(size_t)c];
+                if (gi < 0) return false;
+                Group& g = groups[(size_t)gi];
+                if (g.rec < 0 && !free_rec.empty()) {
+                    g.rec = free_rec.back();
+                    free_rec.pop_back();
+                    GTEN_HIP_OK(detail::groups_decode().set(b->dec_, g.rec, kv, g.rows));
+                    b->group_records_now_++;
+                    if (!g.counted) b->groups_recorded_++;
+                    g.counted = true;
+                }
+                if (g.rec < 0) {
+                    if (!g.counted) b->groups_unrecorded_++;
+                    g.counted = true;
+                    return false;
+                }
+                (void)detail::groups_decode().share(b->dec_, q, g.rec, g.rows);      // (refused, or switched off: the slot decodes on its own copy)
+                return true;
+            }
+            void release(Group& g)
+            {
+                if (g.rec < 0) return;
+                detail::groups_decode().set(b->dec_, g.rec, nullptr, 0);
+                free_rec.push_back(g.rec);
+                g.rec = -1;
+                b->group_records_now_--;
+            }
+            // the member on set c has ended: the set's mark goes, and with the last member the record
+            void leave(int c)
+            {
+                const int gi = set_group[(size_t)c];
+                if (gi < 0) return;
+                set_group[(size_t)c] = -1;
+                Group& g = groups[(size_t)gi];
+                if (--g.members <= 0) release(g);
+            }
+            ~GroupRecords() { for (Group& g : groups) release(g); }
+        } group_records{this};
         // the next prompt of the queue onto a free cache set (stream 1); false when the queue is empty
         auto prepare = [&]() {
             while (next < prompts.size() && !pool.empty()) {
@@ -1163,25 +1275,33 @@ public:
         // all, `cap` when the schedule is fixed -- as ONE row matrix (prefill_many) on stream 1.  Prompts under 16 ids (and
         // configurations the segmented call does not compute) go one by one through prepare().
         const bool batched = batched_prompts();
+        int copies_taken = 0;                                              // items that were copies: a fixed schedule counts prompt passes
         auto prepare_many = [&](int cap) -> bool {
             if (pool.empty()) return next < prompts.size();
-            const size_t room = std::min<size_t>({pool.size(), (size_t)kPreMax, cap > 0 ? (size_t)cap : (size_t)kPreMax});
-            std::vector<int> js, limits;
-            int rows = 0;
+            // (ITEMS: as many as there are free sets; COMPUTED prompts: kPreMax -- `cap` under a fixed schedule -- and kPreRows rows.
+            //  A group's copies cost neither; without sample groups every item is computed and the bounds are the former ones)
+            const size_t room = pool.size();
+            const int max_computed = std::min(kPreMax, cap > 0 ? cap : kPreMax);
+            std::vector<int> js, limits, copy_of;
+            int rows = 0, computed = 0;
+            int lead_k = -1, lead_group = -1;                                // this call's computed member of the group being taken
             while (next < prompts.size() && js.size() < room) {
                 const int j = (int)next;
                 const int P = (int)prompts[(size_t)j].size();
                 GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
                 if (!batched || P < 16) break;                               // (short prompt: one by one below)
-                const int cost = computed_rows(prompts[(size_t)j]);          // (a prompt behind the shared prefix: its own rows only)
-                if (rows + cost > kPreRows) break;
+                const int gid = group_of[j];
+                const bool copy = gid >= 0 && gid == lead_group && lead_k >= 0;
+                const int cost = copy ? 0 : computed_rows(prompts[(size_t)j]);   // (a prompt behind the shared prefix: its own rows only)
+                if (!copy && (rows + cost > kPreRows || computed == max_computed)) break;
                 next++;
                 (*out)[(size_t)j] = prompts[(size_t)j];
                 st.prompt_tokens += P;
                 const int mn = max_new[j];
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);
                 if (P >= limit) continue;                                    // no room to generate: returned as is
-                js.push_back(j); limits.push_back(limit); rows += cost;
+                if (!copy) { lead_group = gid; lead_k = (int)js.size(); computed++; }
+                js.push_back(j); limits.push_back(limit); rows += cost; copy_of.push_back(copy ? lead_k : -1);
             }
             if (js.empty()) {
                 if (next >= prompts.size()) return false;
@@ -1189,14 +1309,16 @@ public:
                 if (batched && P >= 16 && P <= kPreRows) return true;        // (only prompts without room were taken: look again)
                 return prepare();
             }
+            copies_taken += (int)js.size() - computed;
             const auto t0 = clock::now();
             std::vector<int> sets(pool.end() - (long)js.size(), pool.end()), first;
             std::reverse(sets.begin(), sets.end());                          // (the order they would be popped in)
             std::vector<const std::vector<int32_t>*> ps;
             for (int j : js) ps.push_back(&prompts[(size_t)j]);
-            pick.many(*this, sets, ps, js, &first);
+            pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr);
             st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
             std::vector<int> unused;
+            std::vector<int> readied(js.size(), 0);                          // per computed item: the readied members of its prompt pass
             for (size_t k = 0; k < js.size(); k++) {
                 std::vector<int32_t>& row = (*out)[(size_t)js[k]];
                 st.admissions++;
@@ -1209,6 +1331,21 @@ public:
                     if (!ended && (int)row.size() < limits[k]) { ready.push_back(Ready{js[k], sets[k], (int)row.size(), limits[k] - 1}); taken = true; }
                 }
                 if (!taken) unused.push_back(sets[k]);
+                else readied[copy_of[k] < 0 ? k : (size_t)copy_of[k]]++;
+            }
+            // the group mark: at least two readied members behind a prompt of at least one full chunk
+            for (size_t k = 0; k < js.size(); k++) {
+                if (copy_of[k] >= 0 || readied[k] < 2 || (int)ps[k]->size() < kGroupMinRows) continue;
+                const int gi = (int)group_records.groups.size();
+                Group g;
+                g.members = readied[k];
+                g.rows = (int)ps[k]->size();
+                group_records.groups.push_back(g);
+                for (size_t m = k; m < js.size(); m++) {
+                    if (m != k && copy_of[m] != (int)k) continue;
+                    for (const Ready& r : ready)
+                        if (r.j == js[m]) group_records.mark(r.set, gi);     // (readied members only: the others' sets stay free)
+                }
             }
             pool.resize(pool.size() - js.size());
             for (size_t k = unused.size(); k-- > 0;) pool.push_back(unused[k]);
@@ -1272,8 +1409,12 @@ public:
             if (!ap_seq.empty())
                 GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), ap_tok.data()));
             // the joining slots whose sets begin with the shared prefix's rows read them from the decoder's one copy
-            for (const int q : ap_seq)
+            // (a group mark wins over a prefix mark on the same set: the whole prompt covers at least as many chunks; also set again
+            //  for a sequence that moved in the tail)
+            for (const int q : ap_seq) {
+                if (group_records.start(q, set_of[(size_t)q], set_kv(set_of[(size_t)q]))) continue;
                 if (const int P = share_mark(set_of[(size_t)q]); P > 0) (void)decoder_share(q, which_mark(set_of[(size_t)q]), P);     // (refused: the slot decodes on its own copy, as in prefill_group)
+            }
             if (n_live == 0) return;
             // (a slot whose run ends inside the slice repeats its last step until the slice is over, slot_start_until: the slice
             //  is cut only when EVERY live slot ends earlier)
@@ -1317,6 +1458,7 @@ public:
                     // (the records of the ids kept: an eos and what follows it are not stored)
                     if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], (int)row.size() - lp_from[(size_t)q]);
                     ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);                  // parked, all of them at once below
+                    group_records.leave(set_of[(size_t)q]);                                            // (its group's last member: the record goes back)
                     pool.push_back(set_of[(size_t)q]);
                     set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
                 }
@@ -1336,10 +1478,10 @@ public:
                 else GTEN_HIP_OK(gten_hip_stream_idle(0, &idle));
                 if (!idle && queue_left && !pool.empty()) {                 // slice still running: more prompts beside it
                     GTEN_HIP_OK(gten_hip_select_stream(1));
-                    const int before = (int)st.admissions;
+                    const int before = (int)st.admissions - copies_taken;
                     queue_left = batched ? prepare_many(serve_schedule_ > 0 ? serve_schedule_ - prepared_this_slice : 0) : prepare();
                     GTEN_HIP_OK(gten_hip_select_stream(0));
-                    prepared_this_slice += batched ? std::max(1, (int)st.admissions - before) : 1;
+                    prepared_this_slice += batched ? std::max(1, (int)st.admissions - copies_taken - before) : 1;
                     continue;
                 }
                 harvest();                                                  // (waits when nothing is left to prepare)
@@ -1378,7 +1520,56 @@ public:
     // queue allow) instead of "as many as fit while the slice runs", so that a run is repeatable slice by slice.
     void set_serve_schedule(int k) { serve_schedule_ = k; }
 
+    // ---- sample groups (include/gten_host_samples.h).  A prompt behind fewer rows than one full chunk of the decoder's shadows
+    // (DEC_CHUNK) has nothing to read from a record.
+    static constexpr int kGroupMinRows = 256;
+    // group records a queue may hold at a time: -1: the default; 0: never take one (the members decode on their own copies); at most
+    // kGroupsMax.  THE DEFAULT IS 0: measured (profiles/samples_cost.json), the records make the shared step 1 %
+    // faster, but the queue's new tok/s with them lies inside the spread of the runs without -- the rule PFX_SHARED_DEFAULT was
+    // decided by leaves them off.
+    static constexpr int kGroupsCapDefault = 0;
+    void set_groups_cap(int cap) { groups_cap_ = cap < 0 ? -1 : std::min(cap, kGroupsMax); }
+    // items that were copies of another item's prompt pass, the prompt rows not computed for them, the groups that got a record
+    // and those that did not (all since this batch was made), the records in use now
+    // the group records of the shared decoder, for callers that drive the steps themselves (tests): gten_hip_decoder_group_set with
+    // the caches of cache set c (c < 0: release), gten_hip_decoder_group_share, return codes and all; 0 without the entry points
+    int group_set_rc(int g, int c, int rows)
+    {
+        if (!detail::groups_decode().set) return 0;
+        ensure_decoder();
+        return detail::groups_decode().set(dec_, g, c >= 0 ? set_kv(c) : nullptr, c >= 0 ? rows : 0);
+    }
+    int group_share_rc(int seq_i, int g, int rows)
+    {
+        if (!detail::groups_decode().share) return 0;
+        ensure_decoder();
+        return detail::groups_decode().share(dec_, seq_i, g, rows);
+    }
+    // gten_hip_decoder_groups_info on the shared decoder (-1 / 0 without the entry points)
+    void groups_decode_info(int seq_i, int g, int* seq_group, int* seq_chunks, int* rows, unsigned long long* imports, int* sharers)
+    {
+        if (seq_group) *seq_group = -1;
+        if (seq_chunks) *seq_chunks = 0;
+        if (rows) *rows = 0;
+        if (imports) *imports = 0;
+        if (sharers) *sharers = 0;
+        if (!detail::groups_decode().info) return;
+        ensure_decoder();
+        GTEN_HIP_OK(detail::groups_decode().info(dec_, seq_i, g, seq_group, seq_chunks, rows, imports, sharers));
+    }
+    void samples_info(unsigned long long* copies, unsigned long long* rows_saved, unsigned long long* recorded, unsigned long long* unrecorded, int* records_now) const
+    {
+        if (copies) *copies = samples_copies_;
+        if (rows_saved) *rows_saved = samples_rows_saved_;
+        if (recorded) *recorded = groups_recorded_;
+        if (unrecorded) *unrecorded = groups_unrecorded_;
+        if (records_now) *records_now = group_records_now_;
+    }
+
 private:
+    unsigned long long samples_copies_ = 0, samples_rows_saved_ = 0, groups_recorded_ = 0, groups_unrecorded_ = 0;
+    int group_records_now_ = 0;
+    int groups_cap_ = -1;
     std::vector<std::unique_ptr<TinyLlama>> seqs_;
     std::vector<std::unique_ptr<TinyLlama>> spares_;   // spare cache sets of serve()
     std::vector<std::vector<gten_hip_kv_ptrs>> set_kv_;      // per cache set: its layers' cache pointers (gten_hip_decoder_slot_bind)

@@ -76,6 +76,11 @@ class GtenHost:
     PREFIXES_SYMBOLS = ["gten_host_batch_prefixes_set", "gten_host_batch_prefixes_info", "gten_host_batch_prefixes_decode_info",
                         "gten_host_batch_prefixes_decode_share", "gten_host_batch_prefixes_steps",
                         "gten_host_prefixes_match"]                                                         # include/gten_host_prefixes.h
+    SAMPLES_SYMBOLS = ["gten_host_batch_serve_samples", "gten_host_batch_samples_info", "gten_host_batch_set_groups_cap",
+                       "gten_host_batch_group_decode_set", "gten_host_batch_group_decode_share", "gten_host_batch_groups_decode_info",
+                       "gten_host_samples_rank", "gten_host_samples_rank_records"]                          # include/gten_host_samples.h
+    GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
+    SAMPLES_MAX = 64                                             # GTEN_HOST_SAMPLES_MAX
 
     def __init__(self, path=None):
         path = path or _build.HOST_LIB
@@ -213,6 +218,16 @@ class GtenHost:
         self._bpsdshare = _sig(L, "gten_host_batch_prefixes_decode_share", ci, [vp, ci, ci, ci])
         self._bpssteps = _sig(L, "gten_host_batch_prefixes_steps", ci, [vp, ci, vp, ci, ci, ci])
         self._psmatch = _sig(L, "gten_host_prefixes_match", ci, [vp, vp, ci, ci, vp, ci])
+        self._bserve_samples = _sig(L, "gten_host_batch_serve_samples", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                             C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
+                                                                             vp, vp, vp, ci])
+        self._bsamples_info = _sig(L, "gten_host_batch_samples_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ci)])
+        self._bgroups_cap = _sig(L, "gten_host_batch_set_groups_cap", ci, [vp, ci])
+        self._bgdset = _sig(L, "gten_host_batch_group_decode_set", ci, [vp, ci, ci, ci])
+        self._bgdshare = _sig(L, "gten_host_batch_group_decode_share", ci, [vp, ci, ci, ci])
+        self._bgdinfo = _sig(L, "gten_host_batch_groups_decode_info", ci, [vp, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ull), C.POINTER(ci)])
+        self._samples_rank = _sig(L, "gten_host_samples_rank", ci, [vp, vp, ci, vp])
+        self._samples_rank_records = _sig(L, "gten_host_samples_rank_records", ci, [vp, ci, ci, vp, ci, vp])
         self._synthw = _sig(L, "gten_host_synth_weight", ci, [cfgp, C.c_uint64, ci, vp, sz])
         self._writeg = _sig(L, "gten_host_write_gten", ci, [cfgp, C.c_uint64, C.c_char_p])
         self._stoks = _sig(L, "gten_host_synthetic_tokens", None, [vp, ci, C.c_uint32, ci])
@@ -240,6 +255,27 @@ class GtenHost:
         rc = self._pdshared(-1 if on is None else 1 if on else 0)    # (None: the default again)
         if rc:
             raise GtenHipError(f"gten_host_set_prefix_decode_shared rc={rc}")
+
+    def samples_rank(self, logprob_sum, n_new):
+        """gten_host_samples_rank (include/gten_host_samples.h; no device): the samples' indices, best first -- descending mean
+        log-prob per new id (logprob_sum[i] / n_new[i] in double), ties to the lower sample, samples without new ids last"""
+        sums, nn = np.ascontiguousarray(logprob_sum, dtype=np.float64), np.ascontiguousarray(n_new, dtype=np.int32)
+        assert len(sums) == len(nn)
+        order = np.zeros(max(len(nn), 1), np.int32)
+        rc = self._samples_rank(_ptr(sums), _ptr(nn), len(nn), _ptr(order))
+        if rc:
+            raise ValueError(f"samples_rank rc={rc}")
+        return order[: len(nn)].copy()
+
+    def samples_rank_records(self, records, n_prompt, n_new):
+        """... with the sums formed from the samples' f32 log-prob rows (records [n][width]; new ids from position n_prompt on)"""
+        rec, nn = np.ascontiguousarray(records, dtype=np.float32), np.ascontiguousarray(n_new, dtype=np.int32)
+        assert rec.ndim == 2 and rec.shape[0] == len(nn)
+        order = np.zeros(max(len(nn), 1), np.int32)
+        rc = self._samples_rank_records(_ptr(rec), rec.shape[1], int(n_prompt), _ptr(nn), len(nn), _ptr(order))
+        if rc:
+            raise ValueError(f"samples_rank_records rc={rc}")
+        return order[: len(nn)].copy()
 
     def prefixes_match(self, prefixes, prompt):
         """gten_host_prefixes_match (include/gten_host_prefixes.h): the index of the longest of `prefixes` (id lists; empty or None: not
@@ -342,6 +378,13 @@ def _records(n_top, n, width):
     nt, tw = _n_tops(n_top, n)
     lp, ti, tl = np.zeros((n, width), np.float32), np.full((n, width, tw), -1, np.int32), np.zeros((n, width, tw), np.float32)
     return [_ptr(nt), tw, _ptr(lp), _ptr(ti), _ptr(tl)], (lp, ti, tl)
+
+
+def _samples_counts(n, n_prompts):
+    """int32[n_prompts] samples per prompt of a scalar for all or one value per prompt"""
+    ns = np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int32), (n_prompts,)))
+    assert ns.min() >= 1 and ns.max() <= GtenHost.SAMPLES_MAX, "samples per prompt in [1, 64]"
+    return ns
 
 
 def _cut_args(n, top_p, min_p):
@@ -1165,15 +1208,100 @@ class HostBatch:
         return ids, ended
 
     def serve_fsm(self, prompts, max_tokens, eos, top_k, temp, seed, fsm_start, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True, top_p=1.0,
-                  min_p=0.0, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None):
-        """serve_penalized() with a start state per prompt (a scalar for all; -1: not bound): (ids per prompt, stats, ended_by int32[prompts])"""
+                  min_p=0.0, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None, n_top=None):
+        """serve_penalized() with a start state per prompt (a scalar for all; -1: not bound): (ids per prompt, stats, ended_by int32[prompts]);
+        with n_top also serve_logprobs()'s records (log-probs, top ids, top log-probs) behind them"""
         n = len(prompts)
+        args, rec = _records(n_top, n, max(max_tokens, max(len(p) for p in prompts)))
+        if n_top is None:
+            args = [None, 0, None, None, None]
         pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
         st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
         ids, stats = self._serve(self.host._bserve_fsm, "batch_serve_fsm", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
                                  *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
-                                 None, 0, None, None, None, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
-        return ids, stats, ended
+                                 *args, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
+        return (ids, stats, ended) if n_top is None else (ids, stats, ended, *rec)
+
+    # ---- n samples per prompt (include/gten_host_samples.h, DESIGN.md 3.16)
+    def serve_samples_items(self, prompts, n, max_tokens, eos, top_k, temp, seed, fsm_start=-1, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True,
+                            top_p=1.0, min_p=0.0, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None, n_top=None):
+        """gten_host_batch_serve_samples in the EXPANDED queue's order: prompt j is generated n[j] times (n: a scalar for all), sample i
+        of prompt j is item sum(n[:j]) + i and draws with stream = its item number.  Every request -- top_k, temp, fsm_start, the
+        penalties, the cut, tables, min_new, max_new_each, n_top -- is a scalar for everybody, one value per PROMPT (its samples
+        share it) or one value per item.  Returns (ids per item, stats, ended_by int32[items]) and, with n_top, the items' records behind them."""
+        ns = _samples_counts(n, len(prompts))
+        items = int(ns.sum())
+
+        def ex(v):                                                   # a per-prompt list becomes a per-item list; a per-item one stays
+            if v is None or np.isscalar(v):
+                return v
+            assert len(v) in (len(prompts), items), "one value per prompt, or one per item of the expanded queue"
+            return np.repeat(np.asarray(v), ns) if len(v) == len(prompts) else np.asarray(v)
+        width = max(max_tokens, max(len(p) for p in prompts))
+        nt = n_top if n_top is None or np.isscalar(n_top) else [-1 if v is None else v for v in n_top]
+        args, rec = _records(ex(nt), items, width)
+        if n_top is None:
+            args = [None, 0, None, None, None]
+        pen = _penalty_arg(items, ex(rep), ex(freq), ex(pres), ex(last_n), ex(count_prompt))
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(ex(fsm_start), np.int32), (items,))), np.zeros(items, np.int32)
+        pr, npr, mp = _pack(prompts)
+        out, tot, stats = np.zeros((items, width), np.int32), np.zeros(items, np.int32), np.zeros(len(SERVE_STATS), np.float64)
+        each, _ = _each(ex(max_new_each), items, np.int32)
+        self._ck(self.host._bserve_samples(self.h, _ptr(pr), _ptr(npr), len(prompts), mp, max_tokens, eos, slice_steps, max_new, _ptr(each), _ptr(out),
+                                           _ptr(tot), _ptr(stats), len(stats), *_request_args(items, ex(top_k), ex(temp), seed),
+                                           *_full_args(items, (ex(tables), np.int32), (ex(min_new), np.int32)), *args,
+                                           *_cut_args(items, ex(top_p), ex(min_p)), C.byref(pen), _ptr(st), _ptr(ended), _ptr(ns), 0), "batch_serve_samples")
+        ids = [out[e, : tot[e]].copy() for e in range(items)]
+        stats = dict(zip(SERVE_STATS, stats.tolist()))
+        return (ids, stats, ended) if n_top is None else (ids, stats, ended, *rec)
+
+    def serve_samples(self, prompts, n, max_tokens, eos, top_k, temp, seed, n_top=None, best_of=None, **requests):
+        """n samples per prompt: (samples, stats, ended_by) with samples[j] the list of prompt j's id arrays (prompt + new ids) and
+        ended_by[j] their int32 reasons; with n_top also (log-probs, top ids, top log-probs), each a list of per-prompt arrays
+        [samples][positions(, n_top)].  best_of=k keeps, per prompt, the first k samples in samples_rank's order (best first); if
+        nobody asked for records it asks with n_top 0 itself and does not return them.  **requests: serve_samples_items' others."""
+        ns = _samples_counts(n, len(prompts))
+        asked = n_top is not None
+        got = self.serve_samples_items(prompts, ns, max_tokens, eos, top_k, temp, seed, n_top=n_top if asked or best_of is None else 0, **requests)
+        ids, stats, ended = got[:3]
+        first = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        keep = []
+        for j, p in enumerate(prompts):
+            idx = np.arange(first[j], first[j + 1])
+            if best_of is not None:
+                order = self.host.samples_rank_records(got[3][idx], len(p), [len(ids[e]) - len(p) for e in idx])
+                idx = idx[order[: int(best_of)]]
+            keep.append(idx)
+        res = ([[ids[e] for e in idx] for idx in keep], stats, [ended[idx].copy() for idx in keep])
+        return res + tuple([r[idx].copy() for idx in keep] for r in got[3:]) if asked else res
+
+    def samples_info(self):
+        """(items that were copies of another item's prompt pass, prompt rows not computed for them, groups that read from a group
+        record, marked groups that got none -- all counted since the batch was made --, group records in use now)"""
+        a, b, c, d, e = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.host._bsamples_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)), "batch_samples_info")
+        return a.value, b.value, c.value, d.value, e.value
+
+    def group_decode_set_rc(self, g, seq, rows=0):
+        """group record g of the shared decoder becomes a snapshot of rows [0, rows) of sequence seq's own caches (seq None: released):
+        gten_hip_decoder_group_set's return code"""
+        return self.host._bgdset(self.h, int(g), -1 if seq is None else int(seq), int(rows))
+
+    def group_decode_share_rc(self, seq, g, rows):
+        """gten_hip_decoder_group_share(seq, g, rows) on the shared decoder: 0, or the refusal's code"""
+        return self.host._bgdshare(self.h, int(seq), int(g), int(rows))
+
+    def groups_decode_info(self, seq, g=None):
+        """the shared decoder's group records: (record sequence `seq` reads from or -1, leading chunks of 256 positions it reads there);
+        with `g` also (rows of record g, imports of its copy so far, its sharers now)"""
+        sg, ch, rows, imp, sh = C.c_int(-1), C.c_int(0), C.c_int(0), C.c_ulonglong(0), C.c_int(0)
+        self._ck(self.host._bgdinfo(self.h, int(seq), 0 if g is None else int(g), C.byref(sg), C.byref(ch), C.byref(rows), C.byref(imp), C.byref(sh)),
+                 "batch_groups_decode_info")
+        return (sg.value, ch.value) if g is None else (sg.value, ch.value, rows.value, imp.value, sh.value)
+
+    def set_groups_cap(self, cap):
+        """group records a queue may hold at a time (0: never take one; up to GROUPS_MAX; -1: the default, which is 0 -- as measured)"""
+        self._ck(self.host._bgroups_cap(self.h, int(cap)), "batch_set_groups_cap")
 
     def set_prefix_rc(self, tokens):
         """gten_host_batch_set_prefix's return code (0; -2: this batch does not process prompts as segments; < 0: bad arguments)"""
