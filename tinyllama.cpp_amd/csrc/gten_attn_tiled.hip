@@ -21,6 +21,7 @@
 //   * p.V: four accumulators per output for positions = 0,1,2,3 (mod 4), summed in that order.
 #include "gten_rt.h"
 #include "gten_dev.h"
+#include "gten_hip_continue.h"
 
 using namespace gtd;
 using namespace gtr;
@@ -834,7 +835,70 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
                                     q_pitch, kv_pitch, out_pitch, n_heads, n_kv, prefix_len + t.y, prefix_len, t.z, kpre, vpre);
 }
 
+// ---- the rows of SEVERAL prompts that each continue a context of their own (gten_hip_block_rows_continued):
+// k_attn_prefix_* with start position, context rows and the shift of the base pointers taken PER WORKGROUP from the record
+// of the tile's segment (tiles[].w; ctx = this layer's records).  All of it is uniform: scalar loads in front of the same body.
+// (gten_hip_row_ctx as the kernels read it: the pointers typed GLOBAL where they are loaded.  A generic pointer that comes out of
+//  memory stays generic to the compiler, and the body's loads through it would be flat loads; behind this view they are the
+//  global loads they are behind a kernel argument)
+struct RowCtxDev {
+    const __attribute__((address_space(1))) uint8_t* k;
+    const __attribute__((address_space(1))) uint8_t* v;
+    int32_t len;
+};
+static_assert(sizeof(RowCtxDev) == sizeof(gten_hip_row_ctx), "the device view of gten_hip_row_ctx");
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_ctx_q8(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                       const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                       size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                       int n_heads, int n_kv, const int4* __restrict__ tiles,
+                                                       const gten_hip_row_ctx* __restrict__ ctx, _Float16* __restrict__ a16)
+{
+    const int4 t = tiles[blockIdx.y];
+    const RowCtxDev c = ((const RowCtxDev*)ctx)[t.w];
+    const ptrdiff_t mv = (ptrdiff_t)t.x - c.len;
+    attn_tiled_q8_body<FAST, true>(q + mv * (ptrdiff_t)q_pitch, k + mv * (ptrdiff_t)kv_pitch, v + mv * (ptrdiff_t)kv_pitch, out + mv * (ptrdiff_t)out_pitch,
+                                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv, c.len + t.y, c.len,
+                                   a16 ? a16 + (size_t)t.x * (n_heads * 64) : nullptr, t.z, (const uint8_t*)c.k, (const uint8_t*)c.v);
+}
+template <bool FAST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_ctx_f16(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k,
+                                                        const uint8_t* __restrict__ v, uint8_t* __restrict__ out,
+                                                        size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                                                        int n_heads, int n_kv, const int4* __restrict__ tiles,
+                                                        const gten_hip_row_ctx* __restrict__ ctx)
+{
+    const int4 t = tiles[blockIdx.y];
+    const RowCtxDev c = ((const RowCtxDev*)ctx)[t.w];
+    const ptrdiff_t mv = (ptrdiff_t)t.x - c.len;
+    attn_tiled_f16_body<FAST, true>(q + mv * (ptrdiff_t)q_pitch, k + mv * (ptrdiff_t)kv_pitch, v + mv * (ptrdiff_t)kv_pitch, out + mv * (ptrdiff_t)out_pitch,
+                                    q_pitch, kv_pitch, out_pitch, n_heads, n_kv, c.len + t.y, c.len, t.z, (const uint8_t*)c.k, (const uint8_t*)c.v);
+}
+
 } // namespace
+
+int gten_launch_attn_ctx(int f16, const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                         int n_heads, int n_kv_heads, const void* tiles, int n_tiles, const void* ctx, void* a16)
+{
+    const dim3 grid(n_heads, n_tiles);
+    const bool exact = gtr::prefill_exact();
+    if (f16) {
+        if (exact)
+            GTR_LAUNCH(KT_ATTN_TILED, k_attn_ctx_f16<false>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                       q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, (const int4*)tiles, (const gten_hip_row_ctx*)ctx);
+        else
+            GTR_LAUNCH(KT_ATTN_TILED, k_attn_ctx_f16<true>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                       q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, (const int4*)tiles, (const gten_hip_row_ctx*)ctx);
+        return 0;
+    }
+    if (exact)
+        GTR_LAUNCH(KT_ATTN_TILED, k_attn_ctx_q8<false>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, (const int4*)tiles, (const gten_hip_row_ctx*)ctx, (_Float16*)nullptr);
+    else
+        GTR_LAUNCH(KT_ATTN_TILED, k_attn_ctx_q8<true>, grid, dim3(256), 0, (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out,
+                   q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, (const int4*)tiles, (const gten_hip_row_ctx*)ctx, (_Float16*)a16);
+    return 0;
+}
 
 int gten_launch_attn_tiled_f16(const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch,
                                size_t out_pitch, int n, int n_heads, int n_kv_heads, int start_pos)

@@ -12,10 +12,12 @@
 #include <algorithm>
 #include "gten_rt.h"
 #include "gten_hip_prefix.h"
+#include "gten_hip_continue.h"
 #include "gten_hip_score.h"
 #include "gten_row_logprobs.h"
 
 #include <cstdlib>
+#include <cstring>
 
 using namespace gtd;
 
@@ -333,6 +335,16 @@ __global__ __launch_bounds__(256) void k_rope2_rows(uint8_t* __restrict__ x0, si
     const bool second = blockIdx.y != 0;
     rope2_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? d1 : d0, dtype, d_head, prefix_len + row_pos[r], table);
 }
+// ... and for prompts that each continue a context of their own (gten_hip_block_rows_continued): matrix row r sits at position
+// ctx[seg_of_row[r]].len + row_pos[r] (ctx: one layer's records -- a segment's len is the same on every layer)
+__global__ __launch_bounds__(256) void k_rope2_rows_ctx(uint8_t* __restrict__ x0, size_t pitch0, int d0, uint8_t* __restrict__ x1, size_t pitch1, int d1,
+                                                        int dtype, int d_head, const gten_hip_row_ctx* __restrict__ ctx, const int* __restrict__ seg_of_row,
+                                                        const int* __restrict__ row_pos, const float2* __restrict__ table)
+{
+    const int r = blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? d1 : d0, dtype, d_head, ctx[seg_of_row[r]].len + row_pos[r], table);
+}
 
 // ... and for Q8 rows with 64-wide heads, ONE WAVE per (row, matrix): lane L owns block L -- the first (even L) or second
 // (odd L) half of head L / 2 -- and takes its partner's 32 values from the neighbouring lane; k_rope's arithmetic per
@@ -390,6 +402,15 @@ __global__ __launch_bounds__(64) void k_rope2_q8w_rows(uint8_t* __restrict__ x0,
     const int r = blockIdx.x;
     const bool second = blockIdx.y != 0;
     rope2_q8w_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? nblk1 : nblk0, prefix_len + row_pos[r], table);
+}
+// (the rows of several prompts behind contexts of their own: k_rope2_rows_ctx)
+__global__ __launch_bounds__(64) void k_rope2_q8w_rows_ctx(uint8_t* __restrict__ x0, size_t pitch0, int nblk0, uint8_t* __restrict__ x1, size_t pitch1, int nblk1,
+                                                           const gten_hip_row_ctx* __restrict__ ctx, const int* __restrict__ seg_of_row,
+                                                           const int* __restrict__ row_pos, const float2* __restrict__ table)
+{
+    const int r = blockIdx.x;
+    const bool second = blockIdx.y != 0;
+    rope2_q8w_row(second ? x1 + (size_t)r * pitch1 : x0 + (size_t)r * pitch0, second ? nblk1 : nblk0, ctx[seg_of_row[r]].len + row_pos[r], table);
 }
 static bool rope_q8w_ok(const void* x, size_t pitch, int dtype, int d, int d_head)
 {
@@ -1064,8 +1085,10 @@ int gten_hip_set_block_rows(int on)
 // each, q and k are rotated in one launch, silu and the product are one pass, and the two residual sums ride in the
 // epilogues of the o and down projections.  Every buffer ends with the bytes the module sequence leaves in it.
 // (pfx, gten_hip_block_rows_prefixed: the segments' rows continue a shared prefix -- RoPE and attention are one launch each
-//  for all of them; every other launch is the segmented call's)
-struct PrefixRows { const void* k; const void* v; int len; const int* tiles; int n_tiles; const int* row_pos; };
+//  for all of them; every other launch is the segmented call's.  ctx != null, gten_hip_block_rows_continued: the same two
+//  launches with a context per segment -- this layer's device records -- instead of k / v / len)
+struct PrefixRows { const void* k; const void* v; int len; const int* tiles; int n_tiles; const int* row_pos;
+                    const gten_hip_row_ctx* ctx = nullptr; const int* seg_of_row = nullptr; };
 static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, const PrefixRows* pfx)
 {
     GTR_NEED_INIT();
@@ -1114,7 +1137,10 @@ static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, c
             const float2* table = nullptr;
             if ((rc = rope_table(dh, &table))) return rc;
             // (row segments: every prompt from position 0 -- base pointers moved to its first row, start_pos 0)
-            if (pfx)
+            if (pfx && pfx->ctx)
+                GTR_LAUNCH(KT_ROPE, k_rope2_rows_ctx, dim3(n, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q, hE, E, (uint8_t*)b->k, hKV, KV, GTEN_F16, dh, pfx->ctx,
+                           pfx->seg_of_row, pfx->row_pos, table);
+            else if (pfx)
                 GTR_LAUNCH(KT_ROPE, k_rope2_rows, dim3(n, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q, hE, E, (uint8_t*)b->k, hKV, KV, GTEN_F16, dh, pfx->len,
                            pfx->row_pos, table);
             else for (const auto& sg : segs) {
@@ -1123,7 +1149,9 @@ static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, c
                            GTEN_F16, dh, seg ? 0 : start_pos, table);
             }
         }
-        if (pfx) {
+        if (pfx && pfx->ctx) {
+            if ((rc = gten_launch_attn_ctx(1, b->q, b->k, b->v, b->attn_out, hE, hKV, hE, b->n_heads, b->n_kv_heads, pfx->tiles, pfx->n_tiles, pfx->ctx, nullptr))) return rc;
+        } else if (pfx) {
             if ((rc = gten_launch_attn_prefix(1, b->q, b->k, b->v, b->attn_out, hE, hKV, hE, b->n_heads, b->n_kv_heads, pfx->len, pfx->tiles, pfx->n_tiles,
                                               pfx->k, pfx->v, nullptr))) return rc;
         } else
@@ -1193,7 +1221,14 @@ static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, c
         if ((rc = rope_table(dh, &table))) return rc;
         const bool wave_rows = rope_q8w_ok(b->q, pE, GTEN_Q8, E, dh) && rope_q8w_ok(b->k, pKV, GTEN_Q8, KV, dh);
         // (row segments: every prompt from position 0 -- base pointers moved to its first row, start_pos 0)
-        if (pfx) {
+        if (pfx && pfx->ctx) {
+            if (wave_rows)
+                GTR_LAUNCH(KT_ROPE, k_rope2_q8w_rows_ctx, dim3(n, 2), dim3(64), 0, (uint8_t*)b->q, pE, E / 32, (uint8_t*)b->k, pKV, KV / 32, pfx->ctx, pfx->seg_of_row,
+                           pfx->row_pos, table);
+            else
+                GTR_LAUNCH(KT_ROPE, k_rope2_rows_ctx, dim3(n, 2), dim3(256), (size_t)E * 4, (uint8_t*)b->q, pE, E, (uint8_t*)b->k, pKV, KV, GTEN_Q8, dh, pfx->ctx,
+                           pfx->seg_of_row, pfx->row_pos, table);
+        } else if (pfx) {
             if (wave_rows)
                 GTR_LAUNCH(KT_ROPE, k_rope2_q8w_rows, dim3(n, 2), dim3(64), 0, (uint8_t*)b->q, pE, E / 32, (uint8_t*)b->k, pKV, KV / 32, pfx->len, pfx->row_pos, table);
             else
@@ -1210,7 +1245,10 @@ static int block_rows_impl(const gten_hip_block_desc* b, int n, int start_pos, c
                 GTR_LAUNCH(KT_ROPE, k_rope2, dim3(sg.second, 2), dim3(256), (size_t)E * 4, qs, pE, E, ks, pKV, KV, GTEN_Q8, dh, seg ? 0 : start_pos, table);
         }
     }
-    if (pfx) {
+    if (pfx && pfx->ctx) {
+        if ((rc = gten_launch_attn_ctx(0, b->q, b->k, b->v, b->attn_out, pE, pKV, pE, b->n_heads, b->n_kv_heads, pfx->tiles, pfx->n_tiles, pfx->ctx,
+                                       fold ? (void*)a16 : nullptr))) return rc;
+    } else if (pfx) {
         if ((rc = gten_launch_attn_prefix(0, b->q, b->k, b->v, b->attn_out, pE, pKV, pE, b->n_heads, b->n_kv_heads, pfx->len, pfx->tiles, pfx->n_tiles,
                                           pfx->k, pfx->v, fold ? (void*)a16 : nullptr))) return rc;
     } else
@@ -1305,6 +1343,84 @@ int gten_hip_block_rows_prefixed(const gten_hip_block_desc* b, int n, const void
     return block_rows_impl(b, n, 0, &pfx);
 }
 
+// The continued call's device tables, one per library stream and ONE upload per prompt batch (gten_hip_set_row_contexts):
+// [records: n_layers x n_segments][row tiles: int4 (first matrix row of the segment, its rows, tile index, segment)]
+// [row_pos per matrix row][seg_of_row per matrix row].  A block call offsets into the records by its layer.
+struct ContextTables {
+    std::vector<int32_t> seg;      // the segments the device copy was made for (empty: nothing set)
+    uint8_t* dev = nullptr;
+    size_t cap = 0;
+    int n_layers = 0, n_segments = 0, n_tiles = 0;
+    size_t tiles_off = 0, pos_off = 0, segof_off = 0;
+};
+static ContextTables g_ctx_tab[2];
+
+int gten_hip_set_row_contexts(const gten_hip_row_ctx* ctx, int n_layers, int n_segments)
+{
+    GTR_NEED_INIT();
+    ContextTables& t = g_ctx_tab[stream_index() & 1];
+    t.seg.clear();
+    if (!ctx || n_layers <= 0 || n_segments <= 0) return 0;
+    GTR_REQUIRE(!g_seg.empty(), "set_row_contexts: no row segments are set (gten_hip_set_row_segments)");
+    const int S = (int)g_seg.size() - 1;
+    GTR_REQUIRE(n_segments == S, "set_row_contexts: %d contexts for %d row segments", n_segments, S);
+    GTR_REQUIRE(n_layers <= 1024, "set_row_contexts: %d layers", n_layers);
+    for (int l = 0; l < n_layers; l++)
+        for (int s = 0; s < S; s++) {
+            const gten_hip_row_ctx& c = ctx[(size_t)l * S + s];
+            GTR_REQUIRE(c.k && c.v && ((uintptr_t)c.k & 15) == 0 && ((uintptr_t)c.v & 15) == 0, "set_row_contexts: null or unaligned context rows (layer %d, segment %d)", l, s);
+            GTR_REQUIRE(c.len >= 1, "set_row_contexts: a context of %d rows (segment %d)", c.len, s);
+            GTR_REQUIRE(c.len == ctx[s].len, "set_row_contexts: segment %d has %d context rows on layer %d, %d on layer 0", s, c.len, l, ctx[s].len);
+            GTR_REQUIRE(c.len + (g_seg[s + 1] - g_seg[s]) <= GTEN_ROPE_MAX_POS, "set_row_contexts: context %d + a segment of %d rows (at most %d positions)", c.len,
+                        g_seg[s + 1] - g_seg[s], GTEN_ROPE_MAX_POS);
+        }
+    // row tiles in the order of their real walk: context + last row of the tile, longest first
+    struct Tile { int first, rows, ti, s, walk; };
+    std::vector<Tile> tiles;
+    for (int s = 0; s < S; s++) {
+        const int rows = g_seg[s + 1] - g_seg[s];
+        for (int ti = 0; ti * 32 < rows; ti++) tiles.push_back({g_seg[s], rows, ti, s, ctx[s].len + std::min(rows, (ti + 1) * 32)});
+    }
+    std::stable_sort(tiles.begin(), tiles.end(), [](const Tile& a, const Tile& b) { return a.walk > b.walk; });
+    const int n = g_seg.back();
+    const size_t rec_bytes = ((size_t)n_layers * S * sizeof(gten_hip_row_ctx) + 15) & ~(size_t)15;
+    const size_t tile_bytes = tiles.size() * 4 * sizeof(int32_t);
+    const size_t total = rec_bytes + tile_bytes + 2 * (size_t)n * sizeof(int32_t);
+    std::vector<uint8_t> host(total, 0);
+    std::memcpy(host.data(), ctx, (size_t)n_layers * S * sizeof(gten_hip_row_ctx));
+    int32_t* ht = (int32_t*)(host.data() + rec_bytes);
+    for (size_t i = 0; i < tiles.size(); i++) { ht[4 * i] = tiles[i].first; ht[4 * i + 1] = tiles[i].rows; ht[4 * i + 2] = tiles[i].ti; ht[4 * i + 3] = tiles[i].s; }
+    int32_t* hp = (int32_t*)(host.data() + rec_bytes + tile_bytes);
+    for (int s = 0; s < S; s++)
+        for (int r = g_seg[s]; r < g_seg[s + 1]; r++) { hp[r] = r - g_seg[s]; hp[(size_t)n + r] = s; }
+    if (t.cap < total) {
+        if (t.dev) { GTR_CHECK(hipStreamSynchronize(stream())); GTR_CHECK(hipFree(t.dev)); t.dev = nullptr; t.cap = 0; }
+        const size_t want = std::max<size_t>(total, (size_t)64 << 10);
+        GTR_CHECK(hipMalloc((void**)&t.dev, want));
+        t.cap = want;
+    }
+    GTR_CHECK(hipMemcpyAsync(t.dev, host.data(), total, hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));      // (once per prompt batch: the host vector is free again; no block call waits)
+    t.seg = g_seg;
+    t.n_layers = n_layers; t.n_segments = S; t.n_tiles = (int)tiles.size();
+    t.tiles_off = rec_bytes; t.pos_off = rec_bytes + tile_bytes; t.segof_off = t.pos_off + (size_t)n * sizeof(int32_t);
+    return 0;
+}
+
+int gten_hip_block_rows_continued(const gten_hip_block_desc* b, int n, int layer)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(b, "block_rows_continued: null descriptor");
+    GTR_REQUIRE(!g_seg.empty(), "block_rows_continued: no row segments are set (gten_hip_set_row_segments)");
+    const ContextTables& t = g_ctx_tab[stream_index() & 1];
+    GTR_REQUIRE(!t.seg.empty() && t.seg == g_seg, "block_rows_continued: no row contexts are set for these row segments (gten_hip_set_row_contexts)");
+    GTR_REQUIRE(layer >= 0 && layer < t.n_layers, "block_rows_continued: layer %d of %d", layer, t.n_layers);
+    PrefixRows pfx{nullptr, nullptr, 0, (const int*)(t.dev + t.tiles_off), t.n_tiles, (const int*)(t.dev + t.pos_off)};
+    pfx.ctx = (const gten_hip_row_ctx*)t.dev + (size_t)layer * t.n_segments;
+    pfx.seg_of_row = (const int*)(t.dev + t.segof_off);
+    return block_rows_impl(b, n, 0, &pfx);
+}
+
 int gten_hip_row_segments_ok(int n_embd, int n_ffn, int n_heads, int n_kv_heads, int wdtype, int adtype)
 {
     if (!g_block_rows || n_heads <= 0 || n_kv_heads <= 0) return 0;
@@ -1317,6 +1433,8 @@ int gten_hip_row_segments_ok(int n_embd, int n_ffn, int n_heads, int n_kv_heads,
 int gten_hip_set_row_segments(const int32_t* starts, int n_segments)
 {
     GTR_NEED_INIT();
+    // (row contexts speak of the segments they were set for: any new word about the segments, equal values included, ends them)
+    for (ContextTables& t : g_ctx_tab) t.seg.clear();
     if (n_segments <= 0) { g_seg.clear(); return 0; }
     GTR_REQUIRE(starts && starts[0] == 0, "set_row_segments: starts[0] must be 0");
     for (int k = 0; k < n_segments; k++)

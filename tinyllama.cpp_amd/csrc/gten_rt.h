@@ -109,6 +109,10 @@ int gten_launch_attn_tiled_f16(const void* q, const void* k, const void* v, void
 int gten_launch_attn_prefix(int f16, const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch, size_t out_pitch,
                             int n_heads, int n_kv_heads, int prefix_len, const void* tiles, int n_tiles, const void* k_prefix, const void* v_prefix,
                             void* a16);
+// ... and for prompts that each continue a context of their own (include/gten_hip_continue.h): tiles[].w = the tile's segment,
+// `ctx` = this layer's device records (gten_hip_row_ctx per segment), tiles ordered by context + last row, longest first
+int gten_launch_attn_ctx(int f16, const void* q, const void* k, const void* v, void* out, size_t q_pitch, size_t kv_pitch, size_t out_pitch,
+                         int n_heads, int n_kv_heads, const void* tiles, int n_tiles, const void* ctx, void* a16);
 
 namespace gtr {
 const int* row_segments(int* n_segments);   // gten_hip_set_row_segments: starts[0 .. n] or null

@@ -36,6 +36,7 @@
 #include <map>
 #include <vector>
 
+#include "../../include/gten_hip_continue.h"
 #include "ops.h"
 #include "tensor.h"
 
@@ -110,6 +111,24 @@ inline PrefixedRows& prefixed_rows()
 {
     static PrefixedRows p;
     return p;
+}
+
+// Rows that continue contexts of their own (include/gten_hip_continue.h; TinyLlama::hidden_rows_continued).  While `on`, the
+// first AttentionBlock::forward_rows of a pass hands every layer's records to `set` (the row segments are set by then: one
+// upload for the pass) and every block hands its descriptor to `call` with its layer.  Both are installed by the translation
+// unit that links the entry points (host/capi_sessions.cpp), as with PrefixedRows.
+struct ContinuedRows {
+    int (*set)(const gten_hip_row_ctx* ctx, int n_layers, int n_segments) = nullptr;
+    int (*call)(const gten_hip_block_desc* b, int n, int layer) = nullptr;
+    std::vector<gten_hip_row_ctx> ctx;                        // [layer][segment]
+    int n_layers = 0, n_segments = 0;
+    int layer = 0;                                            // the next block's layer
+    bool on = false;
+};
+inline ContinuedRows& continued_rows()
+{
+    static ContinuedRows c;
+    return c;
 }
 
 inline bool& fused_rows_enabled()
@@ -557,6 +576,13 @@ private:
             GTEN_ASSERTM(pr.call && pr.layer < pr.kv.size() && start_pos == 0, "prefixed rows: layer %zu of %zu", pr.layer, pr.kv.size());
             const auto& kv = pr.kv[pr.layer++];
             GTEN_HIP_OK(pr.call(&b, n, kv.first, kv.second, pr.len));      // (not handled: an error too -- the modules know no prefix)
+            return true;
+        }
+        detail::ContinuedRows& cr = detail::continued_rows();
+        if (cr.on) {
+            GTEN_ASSERTM(cr.set && cr.call && cr.layer < cr.n_layers && start_pos == 0, "continued rows: layer %d of %d", cr.layer, cr.n_layers);
+            if (cr.layer == 0) GTEN_HIP_OK(cr.set(cr.ctx.data(), cr.n_layers, cr.n_segments));
+            GTEN_HIP_OK(cr.call(&b, n, cr.layer++));                       // (not handled: an error too, as above)
             return true;
         }
         const int rc = gten_hip_block_rows(&b, n, start_pos);

@@ -76,6 +76,11 @@ class BlockDesc(C.Structure):
                                            "attn_norm_out", "q", "k", "v", "attn_out", "o", "h", "ffn_norm_out", "gate", "up", "down", "out")])
 
 
+class RowCtx(C.Structure):
+    """gten_hip_row_ctx (include/gten_hip_continue.h)"""
+    _fields_ = [("k", C.c_void_p), ("v", C.c_void_p), ("len", C.c_int32)]
+
+
 class GtenHip:
     """Loaded libgten_hip.so with every symbol of include/gten_hip.h bound."""
 
@@ -117,6 +122,7 @@ class GtenHip:
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
+    CONTINUE_SYMBOLS = ["gten_hip_block_rows_continued", "gten_hip_set_row_contexts"]       # include/gten_hip_continue.h
     PREFIX_DECODE_SYMBOLS = ["gten_hip_decoder_prefix_set", "gten_hip_decoder_slot_share", "gten_hip_decoder_prefix_info",
                              "gten_hip_set_prefix_decode_shared"]          # include/gten_hip_prefix_decode.h
     PREFIXES_SYMBOLS = ["gten_hip_decoder_prefixes_set", "gten_hip_decoder_prefixes_share",
@@ -161,6 +167,8 @@ class GtenHip:
         self._prefill_exact = _sig(L, "gten_hip_set_prefill_exact", ci, [ci])
         self._block_rows = _sig(L, "gten_hip_block_rows", ci, [C.POINTER(BlockDesc), ci, ci])
         self._block_rows_prefixed = _sig(L, "gten_hip_block_rows_prefixed", ci, [C.POINTER(BlockDesc), ci, vp, vp, ci])
+        self._set_row_contexts = _sig(L, "gten_hip_set_row_contexts", ci, [vp, ci, ci])
+        self._block_rows_continued = _sig(L, "gten_hip_block_rows_continued", ci, [C.POINTER(BlockDesc), ci, ci])
         self._set_block_rows = _sig(L, "gten_hip_set_block_rows", ci, [ci])
         self._prefix_decode_shared = _sig(L, "gten_hip_set_prefix_decode_shared", ci, [ci])
         self._group_set = _sig(L, "gten_hip_decoder_group_set", ci, [vp, ci, vp, ci])
@@ -647,6 +655,35 @@ class GtenHip:
         for k, v in bufs.items():
             setattr(d, k, v.ptr)
         rc = self._block_rows_prefixed(C.byref(d), n, getattr(k_prefix, "ptr", k_prefix), getattr(v_prefix, "ptr", v_prefix), int(prefix_len))
+        if rc == 1:
+            return False
+        self._check(rc)
+        return True
+
+    def set_row_contexts(self, contexts):
+        """gten_hip_set_row_contexts (include/gten_hip_continue.h): contexts[layer][s] = (k, v, len) of segment s of the row
+        segments that are set -- k / v DeviceBuffers or device addresses of that segment's K / V rows [0, len) on the layer.
+        None / []: clears."""
+        if not contexts:
+            self._check(self._set_row_contexts(None, 0, 0))
+            return
+        n_layers, n_seg = len(contexts), len(contexts[0])
+        arr = (RowCtx * (n_layers * n_seg))()
+        for l, row in enumerate(contexts):
+            if len(row) != n_seg:
+                raise ValueError("set_row_contexts: every layer lists the same segments")
+            for s, (k, v, n) in enumerate(row):
+                arr[l * n_seg + s] = RowCtx(getattr(k, "ptr", k), getattr(v, "ptr", v), int(n))
+        self._check(self._set_row_contexts(C.cast(arr, C.c_void_p), n_layers, n_seg))
+
+    def block_rows_continued(self, n, ints, bufs, layer=0):
+        """gten_hip_block_rows_continued: block_rows for segments whose rows continue the contexts set for `layer`"""
+        d = BlockDesc()
+        for k, v in ints.items():
+            setattr(d, k, int(v))
+        for k, v in bufs.items():
+            setattr(d, k, v.ptr)
+        rc = self._block_rows_continued(C.byref(d), n, int(layer))
         if rc == 1:
             return False
         self._check(rc)

@@ -613,18 +613,27 @@ struct ServePolicy {
     }
     // (copy_of: the items that are copies of another item's prompt pass, TinyLlamaBatch::prefill_many_with; null: none)
     void many(TinyLlamaBatch& b, const std::vector<int>& sets, const std::vector<const std::vector<int32_t>*>& ps, const std::vector<int>& js,
-              std::vector<int>* first, const std::vector<int>* copy_of = nullptr)
+              std::vector<int>* first, const std::vector<int>* copy_of = nullptr, const std::vector<int>* ctx_of = nullptr)
     {
+        // (ctx_of, session items: item k keeps rows [0, ctx) of its set and only what follows them in ps[k] goes through the model --
+        //  the draw below still speaks of the whole of ps[k]: its position, its ids)
+        std::vector<std::vector<int32_t>> tails;
+        std::vector<const std::vector<int32_t>*> cps = ps;
+        if (ctx_of) {
+            tails.resize(ps.size());
+            for (size_t k = 0; k < ps.size(); k++)
+                if ((*ctx_of)[k] > 0) { tails[k].assign(ps[k]->begin() + (*ctx_of)[k], ps[k]->end()); cps[k] = &tails[k]; }
+        }
         if constexpr (M == 0) {
             (void)js;
-            b.prefill_many(sets, ps, first, nullptr, copy_of);
+            b.prefill_many(sets, cps, first, nullptr, copy_of, ctx_of);
         } else {
             if constexpr (kLogprobs) rec.ensure((int)sets.size());
             std::vector<float*> lo((size_t)sets.size(), nullptr);
-            b.prefill_many_with(sets, ps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
+            b.prefill_many_with(sets, cps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
                 draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data(), &fh);
                 if constexpr (kFsm) note_first(js[(size_t)k], fh.after);
-            }, copy_of);
+            }, copy_of, ctx_of);
             if constexpr (kLogprobs)
                 for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
         }
@@ -651,13 +660,26 @@ struct ServePolicy {
 template <unsigned M>
 int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
                 int eos, int slice, int max_new, const int32_t* max_new_each, int32_t* out, int32_t* n_total, double* stats, int n_stats,
-                const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr, const int32_t* group_of = nullptr)
+                const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr, const int32_t* group_of = nullptr,
+                const int32_t* session = nullptr)
 {
     if (n_prompts <= 0 || max_tokens <= 0 || slice <= 0) return -1;
-    for (int j = 0; j < n_prompts; j++)
-        if (n_prompt[j] <= 0 || n_prompt[j] > max_prompt || n_prompt[j] > max_ctx) return -1;
-    if (!reqs.ok(n_prompts, rows.n_top_max)) return -1;
     const int row_len = std::max(max_tokens, max_prompt);
+    // (session, include/gten_host_sessions.h: item j continues session[j] >= 0 -- prompts[j] holds the turn's new ids, possibly
+    //  none; the item is the prompt ids(s) + prompts[j], which `out`'s stride and the context must hold)
+    std::vector<int> full((size_t)n_prompts);
+    {
+        std::vector<char> seen((size_t)TinyLlamaBatch::kSessionsMax, 0);
+        for (int j = 0; j < n_prompts; j++) {
+            const int s = session ? session[j] : -1;
+            if (s < -1 || (s >= 0 && (!batch.session_is_open(s) || seen[(size_t)s]))) return -1;
+            if (s >= 0) seen[(size_t)s] = 1;
+            if (n_prompt[j] < (s >= 0 ? 0 : 1) || n_prompt[j] > max_prompt) return -1;
+            full[(size_t)j] = n_prompt[j] + (s >= 0 ? (int)batch.session_ids(s).size() : 0);
+            if (full[(size_t)j] < 1 || full[(size_t)j] > max_ctx || full[(size_t)j] > row_len) return -1;
+        }
+    }
+    if (!reqs.ok(n_prompts, rows.n_top_max)) return -1;
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = batch.decoder_handle();
     if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)n_prompts * (size_t)row_len);
@@ -696,16 +718,19 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
             }
     }
     std::vector<std::vector<int32_t>> ps((size_t)n_prompts), res;
-    for (int j = 0; j < n_prompts; j++) ps[(size_t)j].assign(prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
-    ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len, n_prompts);
-    const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, {group_of, -1}, pick);
     for (int j = 0; j < n_prompts; j++) {
-        const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, n_prompt[j]));
+        if (session && session[j] >= 0) ps[(size_t)j] = batch.session_ids(session[j]);
+        ps[(size_t)j].insert(ps[(size_t)j].end(), prompts + (size_t)j * max_prompt, prompts + (size_t)j * max_prompt + n_prompt[j]);
+    }
+    ServePolicy<M> pick(dec, batch.n_seq(), reqs, rows, row_len, n_prompts);
+    const TinyLlamaBatch::ServeStats st = batch.serve_with(ps, max_tokens, eos, slice, &res, {max_new_each, max_new}, {group_of, -1}, pick, {session, -1});
+    for (int j = 0; j < n_prompts; j++) {
+        const int take = std::min((int)res[(size_t)j].size(), std::max(max_tokens, full[(size_t)j]));
         std::memcpy(out + (size_t)j * row_len, res[(size_t)j].data(), (size_t)take * sizeof(int32_t));
         n_total[j] = take;
         if (ended_by) {
             // (shorter than its own limit: an eos, unless the policy saw a final state)
-            const int P = n_prompt[j], mn = Each<int32_t>{max_new_each, max_new}[j];
+            const int P = full[(size_t)j], mn = Each<int32_t>{max_new_each, max_new}[j];
             const int limit = std::min(std::min(max_tokens, max_ctx), mn > 0 ? P + mn : max_ctx);
             ended_by[j] = take < limit && P < limit ? kEndedByEos : kEndedByLength;
             if constexpr ((M & kFsm) != 0)

@@ -26,6 +26,7 @@
 
 #include "../gten/gten.h"
 #include "../../include/gten_hip_score.h"
+#include "session_plan.h"
 #include "synth.h"
 #include "prefix_match.h"
 
@@ -134,6 +135,37 @@ public:
             }
             ~Scope() { pr.len = 0; pr.kv.clear(); }
         } scope(prefix, prefix_len);
+        return hidden_rows(tokens, starts);
+    }
+    // hidden_rows for prompts that each CONTINUE A CONTEXT OF THEIR OWN (include/gten_hip_continue.h): segment s of
+    // `tokens` holds the ids of positions ctx_len[s] .., `ctx[s]` is the model object whose K / V tensors hold that segment's rows
+    // [0, ctx_len[s]).  This object's K / V tensors then hold the new rows, at their rows of the matrix.
+    Tensor hidden_rows_continued(const Tensor& tokens, const std::vector<int32_t>& starts, const std::vector<TinyLlama*>& ctx, const std::vector<int>& ctx_len)
+    {
+        struct Scope {
+            detail::ContinuedRows& cr = detail::continued_rows();
+            Scope(const std::vector<TinyLlama*>& ctx, const std::vector<int>& len, int n_layers)
+            {
+                GTEN_ASSERTM(cr.set && cr.call && !ctx.empty() && ctx.size() == len.size(), "hidden_rows_continued: no device entry point installed (%zu contexts)", ctx.size());
+                cr.n_layers = n_layers;
+                cr.n_segments = (int)ctx.size();
+                cr.ctx.clear();
+                for (int l = 0; l < n_layers; l++)
+                    for (size_t s = 0; s < ctx.size(); s++) {
+                        AttentionBlock& blk = ctx[s]->blocks_[(size_t)l];
+                        cr.ctx.push_back(gten_hip_row_ctx{blk.attn.key.acv.device_ptr(), blk.attn.value.acv.device_ptr(), len[s]});
+                    }
+                cr.layer = 0;
+                cr.on = true;
+            }
+            ~Scope()
+            {
+                cr.on = false;
+                cr.ctx.clear();
+                cr.set(nullptr, 0, 0);
+            }
+        } scope(ctx, ctx_len, params.n_layers);
+        GTEN_ASSERTM(starts.size() == ctx.size() + 1, "hidden_rows_continued: %zu segments, %zu contexts", starts.size() - 1, ctx.size());
         return hidden_rows(tokens, starts);
     }
     Tensor logits_of_row(const Tensor& hidden, int row)
@@ -669,10 +701,20 @@ public:
     TinyLlama& seq(int i) { return *seqs_[(size_t)i]; }
     // cache sets: 0 .. n_seq - 1 are the sequences' own K / V caches, n_seq .. n_seq + spares - 1 the spare ones that serve()
     // fills ahead of the slots that will take them (ensure_spares); prefill / prefill_many take a cache set
-    TinyLlama& cset(int c) { return c < n_seq() ? *seqs_[(size_t)c] : *spares_[(size_t)(c - n_seq())]; }
+    // (sessions, DESIGN.md 3.17: a session's own set has index sess_base() + id, behind room for kSpareCap spares, so that it does
+    //  not move when spares grow; n_sets() counts the sets serve() may hand out -- a session's set is never one of them)
+    static constexpr int kSpareCap = 512;
+    int sess_base() const { return n_seq() + kSpareCap; }
+    TinyLlama& cset(int c)
+    {
+        if (c >= sess_base()) return *sessions_[(size_t)(c - sess_base())].set;
+        return c < n_seq() ? *seqs_[(size_t)c] : *spares_[(size_t)(c - n_seq())];
+    }
     int n_sets() const { return n_seq() + (int)spares_.size(); }
+    int index_space() const { return sessions_.empty() ? n_sets() : sess_base() + (int)sessions_.size(); }
     void ensure_spares(int count)
     {
+        GTEN_ASSERTM(count <= kSpareCap, "serve: %d spare cache sets (at most %d)", count, kSpareCap);
         while ((int)spares_.size() < count) {
             spares_.emplace_back(new TinyLlama(n_ctx_, dtype_, params_));
             TinyLlama& m = *spares_.back();
@@ -691,6 +733,7 @@ public:
         // them): it goes before they do and is rebuilt on next use
         if (dec_) { GTEN_HIP_OK(gten_hip_decoder_destroy(dec_)); dec_ = nullptr; }
         spares_.clear();                                     // (... and so do the spare cache sets)
+        sessions_.clear();                                   // (... and the sessions: their rows were computed with the old weights)
         set_kv_.clear();
         set_share_.clear();
         set_which_.clear();
@@ -717,11 +760,11 @@ public:
     // prompts[k] (>= 16 ids each, kPreRows in all, at most kPreMax) onto the caches of sequence slots[k]; first[k] = argmax of
     // prompt k's logits (strict >, first maximum: tinyllama.cpp:416-424); logits_out[k], when given, receives them
     void prefill_many(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
-                      std::vector<float*>* logits_out = nullptr, const std::vector<int>* copy_of = nullptr)
+                      std::vector<float*>* logits_out = nullptr, const std::vector<int>* copy_of = nullptr, const std::vector<int>* ctx_of = nullptr)
     {
         prefill_many_with(slots, prompts, first, logits_out, [](int, const float* lg, int n, int32_t* out) {
             GTEN_HIP_OK(gten_hip_argmax_row(lg, n, out));
-        }, copy_of);
+        }, copy_of, ctx_of);
     }
     // ... with the first id of prompt k (its logits row lg on the device) written to out by pick(k, lg, n_vocab, out)
     // COPIES (sample groups): (*copy_of)[k] = -1: item k is computed, as all are without the list; = c: item k has
@@ -729,24 +772,33 @@ public:
     // matrix: its set is one more destination of the very ranges item c's set receives -- the prefix rows in front where c takes
     // a registered prefix's short way, then c's own rows out of the matrix -- and carries the same marks; its first id is drawn
     // by pick(k, ...) from c's logits row while that row is alive.  kPreMax and kPreRows count computed prompts only.
+    // CONTINUED ITEMS (extend_many): (*ctx_of)[k] = 0: item k is a whole prompt, as all are without the list; = n > 0:
+    // set slots[k] keeps its rows [0, n) and prompts[k] holds the ids of positions n ..: the continued items are one row matrix
+    // of their new rows behind contexts of their own (hidden_rows_continued), the new K / V rows go into the sets at [n, n + rows).
+    // A continued item may hold fewer than 16 ids (at least 1): its segment is filled up to 16 rows behind them (extend_group).
+    // A continued item is never a copy and never copied.
     template <class Pick>
     void prefill_many_with(const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts, std::vector<int>* first,
-                           std::vector<float*>* logits_out, Pick pick, const std::vector<int>* copy_of = nullptr)
+                           std::vector<float*>* logits_out, Pick pick, const std::vector<int>* copy_of = nullptr, const std::vector<int>* ctx_of = nullptr)
     {
         const int K = (int)slots.size();
-        GTEN_ASSERTM(K >= 1 && prompts.size() == slots.size() && (!copy_of || copy_of->size() == slots.size()), "prefill_many: %d prompts", K);
+        GTEN_ASSERTM(K >= 1 && prompts.size() == slots.size() && (!copy_of || copy_of->size() == slots.size()) && (!ctx_of || ctx_of->size() == slots.size()),
+                     "prefill_many: %d prompts", K);
+        auto ctx_at = [&](int k) { return ctx_of ? (*ctx_of)[(size_t)k] : 0; };
         int computed = 0;
         std::vector<std::vector<int>> copies((size_t)K);               // per computed item: the items that copy it
         for (int k = 0; k < K; k++) {
             const int c = copy_of ? (*copy_of)[(size_t)k] : -1;
             if (c < 0) { computed++; continue; }
-            GTEN_ASSERTM(c < K && c != k && (*copy_of)[(size_t)c] < 0 && prompts[(size_t)c]->size() == prompts[(size_t)k]->size(),
+            GTEN_ASSERTM(c < K && c != k && (*copy_of)[(size_t)c] < 0 && prompts[(size_t)c]->size() == prompts[(size_t)k]->size() && ctx_at(k) == 0 && ctx_at(c) == 0,
                          "prefill_many: item %d copies item %d", k, c);
             copies[(size_t)c].push_back(k);
         }
         GTEN_ASSERTM(computed >= 1 && computed <= kPreMax, "prefill_many: %d prompts to compute (at most %d)", computed, kPreMax);
         ensure_pre();
-        for (const auto* p : prompts) GTEN_ASSERTM((int)p->size() >= 16 && (int)p->size() <= n_ctx_, "prefill_many: a prompt of %zu ids", p->size());
+        for (int k = 0; k < K; k++)
+            GTEN_ASSERTM((int)prompts[(size_t)k]->size() >= (ctx_at(k) > 0 ? 1 : 16) && ctx_at(k) >= 0 && ctx_at(k) + (int)prompts[(size_t)k]->size() <= n_ctx_,
+                         "prefill_many: a prompt of %zu ids behind %d rows", prompts[(size_t)k]->size(), ctx_at(k));
         first->assign((size_t)K, 0);
         // a prompt's first id: its logits row stays on the device and so does the sampler (gten_hip_argmax_row, the greedy rule
         // of tinyllama.cpp:416-424) -- the K ids come back in ONE 4 K-byte copy and one wait instead of K copies of 128 KB, K
@@ -756,9 +808,12 @@ public:
         int32_t* ids_dev = (int32_t*)first_ids_->device_ptr_mut();
         // the prompts that begin with a registered prefix (set_prefix_at; the longest one, prefix_of) are one row matrix per prefix
         // of what follows it, the others one of whole prompts: one call per group
-        std::vector<int> group[kPrefixesMax + 1];
-        for (int k = 0; k < K; k++)
-            if (!copy_of || (*copy_of)[(size_t)k] < 0) group[prefix_of(*prompts[(size_t)k]) + 1].push_back(k);
+        std::vector<int> group[kPrefixesMax + 1], continued;
+        for (int k = 0; k < K; k++) {
+            if (ctx_at(k) > 0) continued.push_back(k);
+            else if (!copy_of || (*copy_of)[(size_t)k] < 0) group[prefix_of(*prompts[(size_t)k]) + 1].push_back(k);
+        }
+        if (!continued.empty()) extend_group(continued, slots, prompts, *ctx_of, logits_out, ids_dev, pick);
         for (int w = 0; w < kPrefixesMax; w++)
             if (!group[w + 1].empty()) prefill_group(group[w + 1], w, slots, prompts, logits_out, ids_dev, pick, copies);
         if (!group[0].empty()) prefill_group(group[0], -1, slots, prompts, logits_out, ids_dev, pick, copies);
@@ -976,7 +1031,206 @@ private:
         }
     }
 
+    // prompts[idx[..]] as ONE row matrix of new rows, item k behind rows [0, ctx_of[k]) of its own set slots[k].
+    // A segment has at least 16 rows (the matrix kernels' shortest): an item of fewer ids is FILLED UP behind its last id with
+    // copies of that id.  Rows do not depend on the rows behind them (causal attention; every other kernel works row by row in
+    // segmented calls), so the item's own rows hold the bytes of the whole prompt's rows; the fill rows are computed and
+    // dropped -- neither copied into the set nor asked for logits.
+    static constexpr int kSegMinRows = 16;
+    template <class Pick>
+    void extend_group(const std::vector<int>& idx, const std::vector<int>& slots, const std::vector<const std::vector<int32_t>*>& prompts,
+                      const std::vector<int>& ctx_of, std::vector<float*>* logits_out, int32_t* ids_dev, Pick& pick)
+    {
+        std::vector<int32_t> ids, starts{0};
+        std::vector<TinyLlama*> ctx;
+        std::vector<int> len, own;                                  // per item: rows kept, rows of its own in the segment
+        for (int k : idx) {
+            const std::vector<int32_t>& p = *prompts[(size_t)k];
+            ids.insert(ids.end(), p.begin(), p.end());
+            if ((int)p.size() < kSegMinRows) ids.insert(ids.end(), (size_t)kSegMinRows - p.size(), p.back());
+            starts.push_back((int32_t)ids.size());
+            ctx.push_back(&cset(slots[(size_t)k]));
+            len.push_back(ctx_of[(size_t)k]);
+            own.push_back((int)p.size());
+            rows_kept_ += (unsigned long long)ctx_of[(size_t)k];
+            rows_computed_ += p.size();
+            rows_extended_ += p.size();
+        }
+        GTEN_ASSERTM((int)ids.size() <= kPreRows, "extend_many: %zu rows (at most %d)", ids.size(), kPreRows);
+        turns_continued_ += idx.size();
+        Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
+        const Tensor hidden = pre_->hidden_rows_continued(tk, starts, ctx, len);
+        // the new K / V rows into the sets, behind the rows they continued (announced: a decoder's shadows of these sets re-import)
+        std::vector<gten_hip_copy_range> ranges;
+        auto flush = [&]() {
+            if (!ranges.empty()) GTEN_HIP_OK(gten_hip_copy_ranges(ranges.data(), (int)ranges.size()));
+            ranges.clear();
+        };
+        for (int l = 0; l < params_.n_layers; l++) {
+            AttentionBlock& src = pre_->block(l);
+            const size_t pitch = (size_t)src.attn.key.acv.bstride(0);
+            for (size_t i = 0; i < idx.size(); i++) {
+                if (ranges.size() + 2 > (size_t)GTEN_HIP_MAX_COPY_RANGES) flush();
+                AttentionBlock& dst = ctx[i]->block(l);
+                const size_t at = (size_t)len[i] * pitch, off = (size_t)starts[i] * pitch, bytes = (size_t)own[i] * pitch;
+                ranges.push_back({(uint8_t*)dst.attn.key.acv.device_ptr_mut() + at, (const uint8_t*)src.attn.key.acv.device_ptr() + off, bytes});
+                ranges.push_back({(uint8_t*)dst.attn.value.acv.device_ptr_mut() + at, (const uint8_t*)src.attn.value.acv.device_ptr() + off, bytes});
+            }
+            flush();
+        }
+        // a "shares P rows" mark stays true while the rows written lie behind the prefix's; otherwise it goes
+        for (size_t i = 0; i < idx.size(); i++)
+            if (int& P = share_mark(slots[(size_t)idx[i]]); P > len[i]) P = 0;
+        for (size_t i = 0; i < idx.size(); i++) {
+            const int k = idx[i];
+            const Tensor lg = pre_->logits_of_row(hidden, starts[i] + own[i] - 1);
+            pick(k, (const float*)lg.device_ptr(), lg.numel(), ids_dev + k);
+            if (logits_out && (*logits_out)[(size_t)k])
+                std::memcpy((*logits_out)[(size_t)k], lg.data_ptr<float>(), (size_t)lg.numel() * sizeof(float));   // (waits for the stream)
+        }
+    }
+
 public:
+    // ---- extend sequences (include/gten_host_sessions.h): set seqs[k] keeps its rows [0, ctx_len[k]) and segment k
+    // of the ids becomes positions ctx_len[k] ..; first[k] = argmax of the last new row's logits, logits_out[k] (may be null
+    // pointers) receives them.  Where the batch processes prompts as segments and the continued entry points are installed, the
+    // segments go as ONE row matrix (several, where they do not fit one) -- those of fewer than 16 ids filled up (extend_group)
+    // -- provided history + turn is a prompt the segmented path would take (at least 16 ids in all) and the filled segment
+    // ends inside the RoPE table.  The others go one by one through the set's own model object, the way a prompt of fewer
+    // than 16 ids goes.  The caller has checked the arguments (host/capi_sessions.cpp).
+    // (The fill rows of a short segment sit at positions ctx + n .. ctx + 15, which may lie PAST max_ctx -- prefill_many_with's
+    //  assertion speaks of the item's own ids only.  They exist in the row matrix alone, which has kPreRows rows whatever
+    //  max_ctx is: they are rotated from the RoPE table, hence the bound kMaxPos, and never written into a cache set.)
+    static constexpr int kMaxPos = 2048;       // GTEN_ROPE_MAX_POS
+    bool continued_prompts() const { return batched_prompts() && detail::continued_rows().call && detail::continued_rows().set; }
+    void extend_many(const std::vector<int>& seqs, const std::vector<int>& ctx_len, const std::vector<std::vector<int32_t>>& tails, std::vector<int>* first,
+                     std::vector<float*>* logits_out)
+    {
+        const int K = (int)seqs.size();
+        first->assign((size_t)K, 0);
+        const bool many = continued_prompts();
+        std::vector<int> slots, ctx, back;
+        std::vector<const std::vector<int32_t>*> ps;
+        std::vector<float*> lo;
+        int rows = 0;
+        auto flush = [&]() {
+            if (slots.empty()) return;
+            std::vector<int> got;
+            prefill_many(slots, ps, &got, &lo, nullptr, &ctx);
+            for (size_t i = 0; i < back.size(); i++) (*first)[(size_t)back[i]] = got[i];
+            slots.clear(); ctx.clear(); back.clear(); ps.clear(); lo.clear();
+            rows = 0;
+        };
+        for (int k = 0; k < K; k++) {
+            const int n = (int)tails[(size_t)k].size();
+            float* out = logits_out ? (*logits_out)[(size_t)k] : nullptr;
+            const int seg = std::max(n, kSegMinRows);
+            if (many && ctx_len[(size_t)k] + n >= kSegMinRows && ctx_len[(size_t)k] + seg <= kMaxPos) {
+                if ((int)slots.size() == kPreMax || rows + seg > kPreRows) flush();
+                slots.push_back(seqs[(size_t)k]); ctx.push_back(ctx_len[(size_t)k]); back.push_back(k); ps.push_back(&tails[(size_t)k]); lo.push_back(out);
+                rows += seg;
+                continue;
+            }
+            (*first)[(size_t)k] = extend_one(seqs[(size_t)k], ctx_len[(size_t)k], tails[(size_t)k], out);
+        }
+        flush();
+    }
+    // one sequence, operator path on the set's own model object (rows [ctx, ctx + n) are computed, rows [0, ctx) read)
+    int extend_one(int c, int ctx, const std::vector<int32_t>& tail, float* logits_out)
+    {
+        if (int& P = share_mark(c); P > ctx) P = 0;
+        std::vector<int32_t> ids((size_t)ctx, 0);                   // (rows [ctx, n) alone are embedded: the earlier ids are not read)
+        ids.insert(ids.end(), tail.begin(), tail.end());
+        rows_computed_one_ += tail.size();
+        Tensor tk(ids.data(), {(int)ids.size()}, kInt32);
+        const Tensor lg = cset(c).logits(tk, ctx);
+        const float* p = lg.data_ptr<float>();
+        int best_i = 0;
+        float best = -std::numeric_limits<float>::infinity();
+        for (int j = 0; j < lg.numel(); j++)
+            if (p[j] > best) { best = p[j]; best_i = j; }
+        if (logits_out) std::memcpy(logits_out, p, (size_t)lg.numel() * sizeof(float));
+        return best_i;
+    }
+    // segments that went as continued row matrices, the rows computed for them, the context rows they kept (not recomputed), and
+    // the rows of the segments that went one by one -- all since this batch was made
+    void extend_info(unsigned long long* turns, unsigned long long* rows, unsigned long long* kept, unsigned long long* rows_one) const
+    {
+        if (turns) *turns = turns_continued_;
+        if (rows) *rows = rows_extended_;
+        if (kept) *kept = rows_kept_;
+        if (rows_one) *rows_one = rows_computed_one_;
+    }
+    int max_ctx() const { return n_ctx_; }
+
+    // ---- sessions (include/gten_host_sessions.h): a cache set of its own plus `ids`, the history, and `rows`, the
+    // leading positions that have valid K / V.  serve_with's session items decode on it and leave it to the next queue.
+    static constexpr int kSessionsMax = 256;
+    int sessions_reserve(int n)
+    {
+        if (n < 0 || n > kSessionsMax) return -1;
+        if ((int)sessions_.size() < n) sessions_.resize((size_t)n);
+        return 0;
+    }
+    int session_open()
+    {
+        for (size_t s = 0; s < sessions_.size(); s++) {
+            Session& ss = sessions_[s];
+            if (ss.open) continue;
+            if (!ss.set) {
+                ss.set.reset(new TinyLlama(n_ctx_, dtype_, params_));
+                ss.set->set_fast_decode(false);
+                for (int w = 0; w < seqs_[0]->n_weights(); w++) ss.set->weight(w) = seqs_[0]->weight(w);
+            }
+            ss.open = true;
+            ss.ids.clear();
+            ss.rows = 0;
+            share_mark(sess_base() + (int)s) = 0;
+            return (int)s;
+        }
+        return -1;
+    }
+    bool session_is_open(int s) const { return s >= 0 && s < (int)sessions_.size() && sessions_[(size_t)s].open; }
+    int session_close(int s)
+    {
+        if (!session_is_open(s)) return -1;
+        sessions_[(size_t)s].open = false;
+        sessions_[(size_t)s].ids.clear();
+        sessions_[(size_t)s].rows = 0;
+        share_mark(sess_base() + s) = 0;
+        return 0;
+    }
+    const std::vector<int32_t>& session_ids(int s) const { return sessions_[(size_t)s].ids; }
+    int session_rows(int s) const { return sessions_[(size_t)s].rows; }
+    // the prefix mark the session's set carries: (which, rows), (-1, 0) without one
+    void session_prefix(int s, int* which, int* rows)
+    {
+        const int P = share_mark(sess_base() + s);
+        *which = P > 0 ? which_mark(sess_base() + s) : -1;
+        *rows = P;
+    }
+    // the history is cut to n_ids ids; nothing moves on the device (how a caller regenerates or edits the last turn)
+    int session_truncate(int s, int n_ids)
+    {
+        if (!session_is_open(s) || n_ids < 0 || n_ids > (int)sessions_[(size_t)s].ids.size()) return -1;
+        sessions_[(size_t)s].ids.resize((size_t)n_ids);
+        sessions_[(size_t)s].rows = std::min(sessions_[(size_t)s].rows, n_ids);
+        return 0;
+    }
+    void sessions_info(int* open, unsigned long long* kv_bytes, unsigned long long* turns, unsigned long long* turns_continued,
+                       unsigned long long* rows_computed, unsigned long long* rows_kept) const
+    {
+        int n = 0;
+        for (const Session& ss : sessions_) n += ss.open ? 1 : 0;
+        const int KV = params_.n_embd / params_.n_heads * params_.n_query_groups;
+        if (open) *open = n;
+        if (kv_bytes) *kv_bytes = 2ull * (unsigned long long)params_.n_layers * (unsigned long long)n_ctx_ * gten_hip_row_bytes(dtype_code(dtype_.adtype), KV);
+        if (turns) *turns = sess_turns_;
+        if (turns_continued) *turns_continued = sess_turns_continued_;
+        if (rows_computed) *rows_computed = sess_rows_computed_;
+        if (rows_kept) *rows_kept = sess_rows_kept_;
+    }
+
     // one prompt onto sequence seq_i's caches; returns the argmax of its logits (logits_out may be null)
     int prefill(int seq_i, const std::vector<int32_t>& prompt, float* logits_out = nullptr)
     {
@@ -1113,8 +1367,22 @@ public:
     // a group mark; a slot started on such a set reads the prompt's full chunks from a group record of the decoder (GroupRecords).
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
-                          std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Each<int32_t> group_of, Pick& pick)
+                          std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Each<int32_t> group_of, Pick& pick,
+                          Each<int32_t> session = Each<int32_t>{nullptr, -1})
     {
+        // SESSION ITEMS (session[j] = s >= 0; the caller has checked that s is open and named once): prompts[j] is
+        // the session's ids + the turn's, and the item is that prompt in every respect but two -- its cache set is the session's own
+        // (never out of `pool`, never back into it) and only the rows the plan asks for are computed (prepare_many's continued
+        // items).  When the item ends the session takes the out row as its ids.
+        auto session_done = [&](int j) {
+            const int s = session[j];
+            if (s < 0) return;
+            Session& ss = sessions_[(size_t)s];
+            const std::vector<int32_t>& row = (*out)[(size_t)j];
+            const int generated = (int)row.size() - (int)prompts[(size_t)j].size();
+            ss.ids = row;
+            ss.rows = session_rows_after((int)row.size(), generated);
+        };
         using clock = std::chrono::steady_clock;
         ensure_decoder();
         const int S = n_seq();
@@ -1165,7 +1433,10 @@ public:
             ~ServeMarks()
             {
                 b->in_serve_ = false;
-                std::fill(b->set_share_.begin(), b->set_share_.end(), 0);
+                // (a SESSION's set keeps its mark between queues: its rows stay what they are until a turn writes them -- rows >= ctx
+                //  only, extend_group drops the mark where ctx lies inside the prefix -- and a prefix that is replaced or cleared
+                //  takes every mark that speaks of it along, forget_prefix_marks)
+                std::fill(b->set_share_.begin(), b->set_share_.begin() + (long)std::min(b->set_share_.size(), (size_t)b->sess_base()), 0);
             }
         } serve_marks{this};
         struct Rebind {
@@ -1194,7 +1465,7 @@ public:
             std::vector<Group> groups;
             std::vector<int> set_group;                                    // per cache set: its group (-1: no mark)
             std::vector<int> free_rec;
-            explicit GroupRecords(TinyLlamaBatch* b_) : b{b_}, set_group((size_t)b_->n_sets(), -1)
+            explicit GroupRecords(TinyLlamaBatch* b_) : b{b_}, set_group((size_t)b_->index_space(), -1)
             {
                 const detail::GroupsDecode& h = detail::groups_decode();
                 const int cap = (h.set && h.share) ? (b->groups_cap_ < 0 ? kGroupsCapDefault : std::min(b->groups_cap_, kGroupsMax)) : 0;
@@ -1244,8 +1515,9 @@ public:
         } group_records{this};
         // the next prompt of the queue onto a free cache set (stream 1); false when the queue is empty
         auto prepare = [&]() {
-            while (next < prompts.size() && !pool.empty()) {
+            while (next < prompts.size() && (session[(int)next] >= 0 || !pool.empty())) {
                 const int j = (int)next++;
+                const bool sess = session[j] >= 0;
                 std::vector<int32_t>& row = (*out)[(size_t)j];
                 row = prompts[(size_t)j];
                 const int P = (int)row.size();
@@ -1255,17 +1527,19 @@ public:
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);   // ids in all
                 if (P >= limit) continue;                                  // no room to generate: returned as is
                 const auto t0 = clock::now();
-                const int c = pool.back();
+                // (a session item on this path -- a conversation under 16 ids, a narrow batch -- is processed whole onto its own set)
+                const int c = sess ? sess_base() + session[j] : pool.back();
+                if (sess) { sess_turns_++; sess_rows_computed_ += (unsigned long long)P; }
                 const int best_i = pick.first(*this, c, row, j);           // this set's caches now hold rows [0, P) (waits for stream 1 only)
                 st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
                 st.admissions++;
-                if (best_i == eos) continue;                               // ended at once: the set takes the next prompt
+                if (best_i == eos) { session_done(j); continue; }          // ended at once: the set takes the next prompt
                 row.push_back(best_i);
                 st.new_tokens++;
                 if constexpr (Pick::kFsm)
-                    if (pick.ended_first(j)) continue;                     // its first id entered a final state: kept, and the set stays free
-                if ((int)row.size() >= limit) continue;
-                pool.pop_back();
+                    if (pick.ended_first(j)) { session_done(j); continue; }   // its first id entered a final state: kept, and the set stays free
+                if ((int)row.size() >= limit) { session_done(j); continue; }
+                if (!sess) pool.pop_back();
                 ready.push_back(Ready{j, c, (int)row.size(), limit - 1});
                 return true;
             }
@@ -1277,31 +1551,46 @@ public:
         const bool batched = batched_prompts();
         int copies_taken = 0;                                              // items that were copies: a fixed schedule counts prompt passes
         auto prepare_many = [&](int cap) -> bool {
-            if (pool.empty()) return next < prompts.size();
+            if (pool.empty() && !(next < prompts.size() && session[(int)next] >= 0)) return next < prompts.size();
             // (ITEMS: as many as there are free sets; COMPUTED prompts: kPreMax -- `cap` under a fixed schedule -- and kPreRows rows.
             //  A group's copies cost neither; without sample groups every item is computed and the bounds are the former ones)
             const size_t room = pool.size();
             const int max_computed = std::min(kPreMax, cap > 0 ? cap : kPreMax);
-            std::vector<int> js, limits, copy_of;
-            int rows = 0, computed = 0;
+            std::vector<int> js, limits, copy_of, ctx_of;
+            int rows = 0, computed = 0, continued = 0;
+            size_t plain = 0;                                                // items that take a set out of the pool
             int lead_k = -1, lead_group = -1;                                // this call's computed member of the group being taken
-            while (next < prompts.size() && js.size() < room) {
+            while (next < prompts.size()) {
                 const int j = (int)next;
+                const bool sess = session[j] >= 0;
+                if (!sess && plain == room) break;                           // (a session item needs no free set)
                 const int P = (int)prompts[(size_t)j].size();
                 GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
                 if (!batched || P < 16) break;                               // (short prompt: one by one below)
-                const int gid = group_of[j];
+                const int gid = sess ? -1 : group_of[j];
                 const bool copy = gid >= 0 && gid == lead_group && lead_k >= 0;
-                const int cost = copy ? 0 : computed_rows(prompts[(size_t)j]);   // (a prompt behind the shared prefix: its own rows only)
+                // a session item: the rows its plan keeps stay, the others are a continued segment (filled up to 16 rows); where
+                // the plan keeps nothing -- a first turn -- or the segment would end past the RoPE table it is a whole prompt
+                int ctx = 0, seg_rows = 0;
+                if (sess && continued_prompts()) {
+                    const Session& ss = sessions_[(size_t)session[j]];
+                    SessionPlan pl;
+                    if (session_plan((int)ss.ids.size(), ss.rows, P - (int)ss.ids.size(), true, &pl) && pl.path == kSessionContinued &&
+                        pl.ctx + pl.seg_rows <= kMaxPos) { ctx = pl.ctx; seg_rows = pl.seg_rows; }
+                }
+                const int cost = copy ? 0 : ctx > 0 ? seg_rows : computed_rows(prompts[(size_t)j]);   // (a prompt behind the shared prefix: its own rows only)
                 if (!copy && (rows + cost > kPreRows || computed == max_computed)) break;
                 next++;
                 (*out)[(size_t)j] = prompts[(size_t)j];
                 st.prompt_tokens += P;
                 const int mn = max_new[j];
                 const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);
-                if (P >= limit) continue;                                    // no room to generate: returned as is
+                if (P >= limit) continue;                                    // no room to generate: returned as is (a session stays as it is)
                 if (!copy) { lead_group = gid; lead_k = (int)js.size(); computed++; }
-                js.push_back(j); limits.push_back(limit); rows += cost; copy_of.push_back(copy ? lead_k : -1);
+                js.push_back(j); limits.push_back(limit); rows += cost; copy_of.push_back(copy ? lead_k : -1); ctx_of.push_back(ctx);
+                if (!sess) plain++;
+                if (sess) { sess_turns_++; sess_rows_computed_ += (unsigned long long)(P - ctx); sess_rows_kept_ += (unsigned long long)ctx; }
+                if (ctx > 0) { continued++; sess_turns_continued_++; }
             }
             if (js.empty()) {
                 if (next >= prompts.size()) return false;
@@ -1311,11 +1600,13 @@ public:
             }
             copies_taken += (int)js.size() - computed;
             const auto t0 = clock::now();
-            std::vector<int> sets(pool.end() - (long)js.size(), pool.end()), first;
-            std::reverse(sets.begin(), sets.end());                          // (the order they would be popped in)
+            std::vector<int> sets, first;
+            for (size_t k = 0, taken = 0; k < js.size(); k++)               // (plain items: the order the sets would be popped in)
+                sets.push_back(session[js[k]] >= 0 ? sess_base() + session[js[k]] : pool[pool.size() - 1 - taken++]);
             std::vector<const std::vector<int32_t>*> ps;
             for (int j : js) ps.push_back(&prompts[(size_t)j]);
-            pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr);
+            if (continued) pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr, &ctx_of);
+            else pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr);
             st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
             std::vector<int> unused;
             std::vector<int> readied(js.size(), 0);                          // per computed item: the readied members of its prompt pass
@@ -1330,7 +1621,7 @@ public:
                     if constexpr (Pick::kFsm) ended = pick.ended_first(js[k]);
                     if (!ended && (int)row.size() < limits[k]) { ready.push_back(Ready{js[k], sets[k], (int)row.size(), limits[k] - 1}); taken = true; }
                 }
-                if (!taken) unused.push_back(sets[k]);
+                if (!taken) { if (session[js[k]] >= 0) session_done(js[k]); else unused.push_back(sets[k]); }
                 else readied[copy_of[k] < 0 ? k : (size_t)copy_of[k]]++;
             }
             // the group mark: at least two readied members behind a prompt of at least one full chunk
@@ -1347,7 +1638,7 @@ public:
                         if (r.j == js[m]) group_records.mark(r.set, gi);     // (readied members only: the others' sets stay free)
                 }
             }
-            pool.resize(pool.size() - js.size());
+            pool.resize(pool.size() - plain);
             for (size_t k = unused.size(); k-- > 0;) pool.push_back(unused[k]);
             return true;
         };
@@ -1459,7 +1750,8 @@ public:
                     if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], (int)row.size() - lp_from[(size_t)q]);
                     ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);                  // parked, all of them at once below
                     group_records.leave(set_of[(size_t)q]);                                            // (its group's last member: the record goes back)
-                    pool.push_back(set_of[(size_t)q]);
+                    if (set_of[(size_t)q] >= sess_base()) session_done(job[(size_t)q]);                  // (a session keeps its set)
+                    else pool.push_back(set_of[(size_t)q]);
                     set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
                 }
             }
@@ -1476,7 +1768,11 @@ public:
                 int idle = 0;
                 if (serve_schedule_ > 0) idle = prepared_this_slice >= serve_schedule_;   // fixed schedule (tests): k prompts per slice
                 else GTEN_HIP_OK(gten_hip_stream_idle(0, &idle));
-                if (!idle && queue_left && !pool.empty()) {                 // slice still running: more prompts beside it
+                // (a session item at the head of the queue needs no free set: it is prepared beside the slice even when every set
+                //  is taken.  The other way round, while any set is free prepare_many may take session items far ahead of the slots
+                //  that will run them -- they wait in `ready` on their own sets and hold nothing a plain prompt could use)
+                const bool head_is_session = next < prompts.size() && session[(int)next] >= 0;
+                if (!idle && queue_left && (!pool.empty() || head_is_session)) {   // slice still running: more prompts beside it
                     GTEN_HIP_OK(gten_hip_select_stream(1));
                     const int before = (int)st.admissions - copies_taken;
                     queue_left = batched ? prepare_many(serve_schedule_ > 0 ? serve_schedule_ - prepared_this_slice : 0) : prepare();
@@ -1580,6 +1876,15 @@ private:
         unsigned long long prompts_shared = 0;   // prompts that took the short way behind it
         unsigned long long rows_computed = 0;    // ... and the rows computed for them
     } pfx_[kPrefixesMax];
+    struct Session {
+        bool open = false;
+        std::unique_ptr<TinyLlama> set;      // its own cache set (made on first open, kept for the next session at this index)
+        std::vector<int32_t> ids;            // the history
+        int rows = 0;                        // leading positions with valid K / V rows
+    };
+    std::vector<Session> sessions_;
+    unsigned long long sess_turns_ = 0, sess_turns_continued_ = 0, sess_rows_computed_ = 0, sess_rows_kept_ = 0;
+    unsigned long long turns_continued_ = 0, rows_extended_ = 0, rows_kept_ = 0, rows_computed_one_ = 0;    // extend_many (extend_info)
     unsigned long long rows_computed_ = 0;   // prompt rows computed in segmented calls (the prefix's own rows not counted)
     std::unique_ptr<Tensor> first_ids_;      // [kPreMax] int32 on the device: the prompts' first ids (gten_hip_argmax_row)
     gten_hip_decoder* dec_ = nullptr;
@@ -1595,12 +1900,12 @@ private:
 
     int& share_mark(int c)
     {
-        if ((int)set_share_.size() < n_sets()) set_share_.resize((size_t)n_sets(), 0);
+        if ((int)set_share_.size() < index_space()) set_share_.resize((size_t)index_space(), 0);
         return set_share_[(size_t)c];
     }
     int& which_mark(int c)
     {
-        if ((int)set_which_.size() < n_sets()) set_which_.resize((size_t)n_sets(), 0);
+        if ((int)set_which_.size() < index_space()) set_which_.resize((size_t)index_space(), 0);
         return set_which_[(size_t)c];
     }
     // every mark that speaks of prefix w is void
@@ -1639,7 +1944,7 @@ private:
 
     const gten_hip_kv_ptrs* set_kv(int c)
     {
-        if ((int)set_kv_.size() < n_sets()) set_kv_.resize((size_t)n_sets());
+        if ((int)set_kv_.size() < index_space()) set_kv_.resize((size_t)index_space());
         std::vector<gten_hip_kv_ptrs>& kv = set_kv_[(size_t)c];
         if (kv.empty()) {
             gten_hip_decoder_desc di;

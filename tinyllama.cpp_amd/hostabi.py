@@ -80,6 +80,11 @@ class GtenHost:
                        "gten_host_batch_group_decode_set", "gten_host_batch_group_decode_share", "gten_host_batch_groups_decode_info",
                        "gten_host_samples_rank", "gten_host_samples_rank_records"]                          # include/gten_host_samples.h
     GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
+    # include/gten_host_sessions.h (continued sequences, host/capi_sessions.cpp)
+    SESSIONS_SYMBOLS = ["gten_host_batch_extend_info", "gten_host_batch_extend_many", "gten_host_session_plan", "gten_host_batch_sessions_reserve",
+                        "gten_host_batch_session_open", "gten_host_batch_session_close", "gten_host_batch_session_info", "gten_host_batch_session_ids",
+                        "gten_host_batch_session_truncate", "gten_host_batch_sessions_info", "gten_host_batch_serve_sessions"]
+    SESSIONS_MAX = 256                                           # GTEN_HOST_SESSIONS_MAX
     SAMPLES_MAX = 64                                             # GTEN_HOST_SAMPLES_MAX
 
     def __init__(self, path=None):
@@ -170,6 +175,18 @@ class GtenHost:
         self._bserve_fsm = _sig(L, "gten_host_batch_serve_fsm", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                      C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
                                                                      vp, vp])
+        self._bserve_sessions = _sig(L, "gten_host_batch_serve_sessions", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                               C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
+                                                                               vp, vp, vp])
+        self._bsess_reserve = _sig(L, "gten_host_batch_sessions_reserve", ci, [vp, ci])
+        self._bsess_open = _sig(L, "gten_host_batch_session_open", ci, [vp])
+        self._bsess_close = _sig(L, "gten_host_batch_session_close", ci, [vp, ci])
+        self._bsess_info = _sig(L, "gten_host_batch_session_info", ci, [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)])
+        self._bsess_ids = _sig(L, "gten_host_batch_session_ids", ci, [vp, ci, vp, ci])
+        self._bsess_truncate = _sig(L, "gten_host_batch_session_truncate", ci, [vp, ci, ci])
+        _ull = C.c_ulonglong
+        self._bsessions_info = _sig(L, "gten_host_batch_sessions_info", ci, [vp, C.POINTER(ci), C.POINTER(_ull), C.POINTER(_ull), C.POINTER(_ull),
+                                                                             C.POINTER(_ull), C.POINTER(_ull)])
         self._score_top = _sig(L, "gten_host_model_score_top", ci, [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp])
         self._score = _sig(L, "gten_host_model_score", ci, [vp, vp, ci, ci, vp, vp, vp])
         self._logits_all = _sig(L, "gten_host_model_logits_all", ci, [vp, vp, ci, ci, vp])
@@ -223,6 +240,9 @@ class GtenHost:
                                                                              vp, vp, vp, ci])
         self._bsamples_info = _sig(L, "gten_host_batch_samples_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ci)])
         self._bgroups_cap = _sig(L, "gten_host_batch_set_groups_cap", ci, [vp, ci])
+        self._bextend_many = _sig(L, "gten_host_batch_extend_many", ci, [vp, vp, vp, vp, vp, ci, vp, vp])
+        self._bextend_info = _sig(L, "gten_host_batch_extend_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ull)])
+        self._session_plan = _sig(L, "gten_host_session_plan", ci, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)])
         self._bgdset = _sig(L, "gten_host_batch_group_decode_set", ci, [vp, ci, ci, ci])
         self._bgdshare = _sig(L, "gten_host_batch_group_decode_share", ci, [vp, ci, ci, ci])
         self._bgdinfo = _sig(L, "gten_host_batch_groups_decode_info", ci, [vp, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ull), C.POINTER(ci)])
@@ -289,6 +309,14 @@ class GtenHost:
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         return self._psmatch(flat.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), len(prefixes), max(max_len, 1),
                              prompt.ctypes.data_as(C.c_void_p), len(prompt))
+
+    def session_plan(self, n_ids, rows, n_new, segmented=True):
+        """gten_host_session_plan (include/gten_host_sessions.h): (rows kept, rows computed, path 0 whole / 1 continued / 2 one by
+        one) of a turn of n_new ids behind n_ids ids with `rows` valid K / V rows; None where there is no such turn"""
+        ctx, k, path = C.c_int(0), C.c_int(0), C.c_int(0)
+        if self._session_plan(int(n_ids), int(rows), int(n_new), 1 if segmented else 0, C.byref(ctx), C.byref(k), C.byref(path)) != 0:
+            return None
+        return ctx.value, k.value, path.value
 
     def synthetic_tokens(self, count, seed=12345, n_vocab=32003):
         out = np.zeros(count, np.int32)
@@ -928,6 +956,31 @@ class HostBatch:
                                           len(prompts), out.ctypes.data_as(C.c_void_p) if want else None), "batch_prefill_many")
         return out
 
+    def extend_many_rc(self, seqs, ctx_len, tails, out=None, first=None):
+        """gten_host_batch_extend_many's return code (tests: the refusals)"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        ctx_len = np.ascontiguousarray(ctx_len, dtype=np.int32)
+        starts = np.zeros(len(tails) + 1, np.int32)
+        starts[1:] = np.cumsum([len(t) for t in tails])
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for t in tails] + [np.zeros(1, np.int32)]), dtype=np.int32)
+        return self.host._bextend_many(self.h, seqs.ctypes.data_as(C.c_void_p), ctx_len.ctypes.data_as(C.c_void_p), toks.ctypes.data_as(C.c_void_p),
+                                       starts.ctypes.data_as(C.c_void_p), len(tails), out.ctypes.data_as(C.c_void_p) if out is not None else None,
+                                       first.ctypes.data_as(C.c_void_p) if first is not None else None)
+
+    def extend_many(self, seqs, ctx_len, tails, want=True):
+        """sequence seqs[k] keeps rows [0, ctx_len[k]) of its caches, tails[k] become positions ctx_len[k] .. (include/gten_host_sessions.h):
+        only the new rows are computed.  Returns ([n][n_vocab] logits of the segments' last rows or None, their argmax ids)"""
+        out = np.zeros((len(tails), self.cfg.n_vocab), np.float32) if want else None
+        first = np.zeros(len(tails), np.int32)
+        self._ck(self.extend_many_rc(seqs, ctx_len, tails, out, first), "batch_extend_many")
+        return out, first
+
+    def extend_info(self):
+        """(segments that went as continued row matrices, rows computed for them, context rows kept, rows of one-by-one segments)"""
+        a, b, c, d = (C.c_ulonglong(0) for _ in range(4))
+        self._ck(self.host._bextend_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "batch_extend_info")
+        return a.value, b.value, c.value, d.value
+
     def decode_begin(self, seq, tokens):
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         self._ck(self.host._bbegin(self.h, seq, tokens.ctypes.data_as(C.c_void_p), len(tokens)), "batch_decode_begin")
@@ -1221,6 +1274,80 @@ class HostBatch:
                                  *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
                                  *args, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
         return (ids, stats, ended) if n_top is None else (ids, stats, ended, *rec)
+
+    # ---- sessions (include/gten_host_sessions.h)
+    def sessions_reserve(self, n):
+        """room for n sessions in all (at most SESSIONS_MAX); each costs a cache set when it is first opened"""
+        self._ck(self.host._bsess_reserve(self.h, int(n)), "batch_sessions_reserve")
+
+    def session_open(self):
+        """a new, empty session: its id (raises when every reserved one is open)"""
+        s = self.host._bsess_open(self.h)
+        if s < 0:
+            raise GtenHipError("batch_session_open: no free session (sessions_reserve)")
+        return s
+
+    def session_close(self, s):
+        self._ck(self.host._bsess_close(self.h, int(s)), "batch_session_close")
+
+    def session_info(self, s):
+        """(ids held, valid rows, prefix the set is marked with or -1, rows of that mark)"""
+        a, b, c, d = (C.c_int(0) for _ in range(4))
+        self._ck(self.host._bsess_info(self.h, int(s), C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "batch_session_info")
+        return a.value, b.value, c.value, d.value
+
+    def session_ids(self, s):
+        n = self.host._bsess_ids(self.h, int(s), None, 0)
+        if n < 0:
+            raise GtenHipError("batch_session_ids rc=%d" % n)
+        out = np.zeros(max(n, 1), np.int32)
+        self.host._bsess_ids(self.h, int(s), _ptr(out), n)
+        return out[:n].copy()
+
+    def session_truncate_rc(self, s, n_ids):
+        return self.host._bsess_truncate(self.h, int(s), int(n_ids))
+
+    def session_truncate(self, s, n_ids):
+        """the history is cut to n_ids ids (rows = min(rows, n_ids)); nothing moves on the device"""
+        self._ck(self.session_truncate_rc(s, n_ids), "batch_session_truncate")
+
+    def sessions_info(self):
+        """(open sessions, K / V bytes per session, session items served, of them continued segments, rows computed, rows kept)"""
+        a = C.c_int(0)
+        u = [C.c_ulonglong(0) for _ in range(5)]
+        self._ck(self.host._bsessions_info(self.h, C.byref(a), *[C.byref(x) for x in u]), "batch_sessions_info")
+        return (a.value,) + tuple(x.value for x in u)
+
+    def serve_sessions_rc(self, items, max_tokens, eos, top_k, temp, seed, fsm_start=-1, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True, top_p=1.0,
+                          min_p=0.0, tables=None, min_new=None, slice_steps=16, max_new=0, max_new_each=None, stride=None):
+        """gten_host_batch_serve_sessions: items = [(session or None, ids)] -- a plain prompt, or the NEW ids of a session's turn (may be
+        empty).  Returns (rc, ids per item -- history included --, stats, ended_by).  stride: the width of the out rows (default: what
+        holds max_tokens and every history + turn)."""
+        n = len(items)
+        sess = np.ascontiguousarray([-1 if s is None else int(s) for s, _ in items], dtype=np.int32)
+        turns = [list(p) for _, p in items]
+        if stride is None:
+            stride = max([max_tokens] + [len(p) + (self.session_info(s)[0] if s is not None else 0) for s, p in items])
+        mp = max([1] + [len(p) for p in turns])
+        width = max(stride, mp) if stride > max_tokens else mp
+        pr, npr = np.zeros((n, width), np.int32), np.zeros(n, np.int32)
+        for j, p in enumerate(turns):
+            pr[j, : len(p)] = p
+            npr[j] = len(p)
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
+        out, tot, stats = np.zeros((n, max(max_tokens, width)), np.int32), np.zeros(n, np.int32), np.zeros(len(SERVE_STATS), np.float64)
+        each, _ = _each(max_new_each, n, np.int32)
+        rc = self.host._bserve_sessions(self.h, _ptr(pr), _ptr(npr), n, width, max_tokens, eos, slice_steps, max_new, _ptr(each), _ptr(out), _ptr(tot),
+                                        _ptr(stats), len(stats), *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
+                                        None, 0, None, None, None, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended), _ptr(sess))
+        return rc, [out[j, : tot[j]].copy() for j in range(n)], dict(zip(SERVE_STATS, stats.tolist())), ended
+
+    def serve_sessions(self, items, max_tokens, eos, top_k, temp, seed, **requests):
+        """serve_fsm() with a session per item (serve_sessions_rc): (ids per item, stats, ended_by)"""
+        rc, ids, stats, ended = self.serve_sessions_rc(items, max_tokens, eos, top_k, temp, seed, **requests)
+        self._ck(rc, "batch_serve_sessions")
+        return ids, stats, ended
 
     # ---- n samples per prompt (include/gten_host_samples.h, DESIGN.md 3.16)
     def serve_samples_items(self, prompts, n, max_tokens, eos, top_k, temp, seed, fsm_start=-1, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True,
