@@ -30,6 +30,7 @@
 #include "gten_hip_nucleus.h"
 #include "gten_hip_penalty.h"
 #include "gten_hip_fsm.h"
+#include "gten_hip_regex.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 #include "gten_hip_prefixes.h"
@@ -163,6 +164,10 @@ struct SamplerState {
     int32_t* fsm_state = nullptr;       // [n_seq][max_ctx + 2] the state per position, laid out like `result`
     int n_fsm = 0;                      // sequences that are bound
     bool fsm_on = false;
+    // the vocabulary as byte strings (include/gten_hip_regex.h): what a byte automaton is expanded over
+    uint8_t* vocab_bytes = nullptr;     // [vocab_n_bytes]
+    int32_t* vocab_offsets = nullptr;   // [n_vocab + 1]
+    long long vocab_n_bytes = 0;
 };
 
 struct gten_hip_decoder {
@@ -1764,7 +1769,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
                     dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm_next, dc->smp.fsm_flags, dc->smp.fsm, dc->smp.fsm_state,
-                    dc->share_dev, dc->which_dev, (void*)dc->pfx_hm_tab};
+                    dc->smp.vocab_bytes, dc->smp.vocab_offsets, dc->share_dev, dc->which_dev, (void*)dc->pfx_hm_tab};
     for (void* b : bufs) if (b) rel(hipFree(b));
     for (gten_hip_decoder::Pfx& x : dc->pfx)
         for (void* b : {(void*)x.hm, (void*)x.tab, (void*)x.step}) if (b) rel(hipFree(b));
@@ -2796,3 +2801,6 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
 #include "gten_decode_sampler_api.h"
 
 } // extern "C"
+
+// byte automata expanded over the vocabulary into the pool, and the pool's check on the device (include/gten_hip_regex.h)
+#include "gten_fsm_expand.h"

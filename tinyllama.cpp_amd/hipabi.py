@@ -117,6 +117,9 @@ class GtenHip:
     # include/gten_hip_fsm.h (token automata: stop sequences and masked grammars)
     FSM_SYMBOLS = ["gten_hip_fsm_check", "gten_hip_decoder_set_fsm", "gten_hip_decoder_set_seq_fsm", "gten_hip_decoder_fsm_info",
                    "gten_hip_decoder_slot_states", "gten_hip_mask_rows_fsm", "gten_hip_sample_rows_fsm"]
+    # include/gten_hip_regex.h (byte automata expanded over the vocabulary on the device)
+    REGEX_SYMBOLS = ["gten_hip_fsm_expand", "gten_hip_fsm_check_dev", "gten_hip_decoder_set_vocab_bytes", "gten_hip_decoder_set_fsm_parts"]
+    FSM_EXPAND_CHUNK, FSM_EXPAND_PASS, FSM_EXPAND_STATES = 4096, 8, 64      # GTEN_HIP_FSM_EXPAND_*
     FSM_DEAD = 0xFFFF                                            # GTEN_HIP_FSM_DEAD
     FSM_MAX_BYTES = 1 << 30                                      # GTEN_HIP_FSM_MAX_BYTES
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
@@ -213,6 +216,10 @@ class GtenHip:
         self._slot_park = _sig(L, "gten_hip_decoder_slot_park", ci, [vp, ci])
         self._decoder_run = _sig(L, "gten_hip_decoder_run", ci, [vp, ci])
         self._slot_ids = _sig(L, "gten_hip_decoder_slot_ids", ci, [vp, ci, ci, ci, vp])
+        self._fsm_expand = _sig(L, "gten_hip_fsm_expand", ci, [vp, vp, ci, ci, ci, vp, C.c_longlong, vp, vp, vp, ci, ci])
+        self._fsm_check_dev = _sig(L, "gten_hip_fsm_check_dev", ci, [vp, vp, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong)])
+        self._set_vocab_bytes = _sig(L, "gten_hip_decoder_set_vocab_bytes", ci, [vp, vp, vp])
+        self._set_fsm_parts = _sig(L, "gten_hip_decoder_set_fsm_parts", ci, [vp, ci, vp, vp, ci])
         self._mask_rows_fsm = _sig(L, "gten_hip_mask_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, C.c_longlong])
         self._sample_rows_fsm = _sig(L, "gten_hip_sample_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
                                                                          vp, vp, vp, vp, vp, vp, vp, vp])
@@ -413,6 +420,75 @@ class GtenHip:
         dn.upload(nxt)
         df.upload(flags)
         return dn, df, len(flags)
+
+    # ---- include/gten_hip_regex.h
+    def fsm_expand(self, pool, n_vocab, base, vocab, next256, accept, eos=-1):
+        """gten_hip_fsm_expand into `pool` (fsm_upload()'s tuple: next, flags, n_states): rows [base, base + Sb (+ 1 with eos >= 0)) from the
+        vocabulary `vocab` = (bytes u8[], offsets int32[n_vocab + 1]) and the byte automaton (next256 u16 [Sb][256], accept u8 [Sb]).
+        Asynchronous on the library's stream; everything it reads is uploaded here and freed after a sync."""
+        vb, vo = np.ascontiguousarray(vocab[0], dtype=np.uint8), np.ascontiguousarray(vocab[1], dtype=np.int32)
+        n256, acc = np.ascontiguousarray(next256, dtype=np.uint16), np.ascontiguousarray(accept, dtype=np.uint8)
+        assert n256.shape == (len(acc), 256) and len(vo) == n_vocab + 1
+        pad = np.zeros(4, np.uint8)
+        bufs = [self.upload(np.concatenate([vb, pad])), self.upload(vo), self.upload(n256), self.upload(acc)]
+        try:
+            self._check(self._fsm_expand(pool[0].ptr, pool[1].ptr, int(pool[2]), int(n_vocab), int(base), bufs[0].ptr, len(vb), bufs[1].ptr, bufs[2].ptr,
+                                         bufs[3].ptr, len(acc), int(eos)))
+            self.sync()
+        finally:
+            for b in bufs:
+                b.free()
+
+    def fsm_check_dev(self, pool, n_vocab, n_states=None):
+        """gten_hip_fsm_check_dev on a device pool (fsm_upload()'s tuple): (code, offending state or -1), as fsm_check gives on the host"""
+        where = C.c_longlong(-1)
+        code = self._fsm_check_dev(pool[0].ptr, pool[1].ptr, int(pool[2] if n_states is None else n_states), int(n_vocab), C.byref(where))
+        return code, int(where.value)
+
+    def decoder_set_vocab_bytes(self, dec, vocab):
+        """gten_hip_decoder_set_vocab_bytes: vocab = (bytes u8[], offsets int32[n_vocab + 1]); None drops it"""
+        if vocab is None:
+            return self._check(self._set_vocab_bytes(dec, None, None))
+        vb, vo = np.ascontiguousarray(vocab[0], dtype=np.uint8), np.ascontiguousarray(vocab[1], dtype=np.int32)
+        self._check(self._set_vocab_bytes(dec, vb.ctypes.data_as(C.c_void_p) if len(vb) else None, vo.ctypes.data_as(C.c_void_p)))
+
+    class FsmPart(C.Structure):
+        _fields_ = [("first", C.c_int), ("count", C.c_int), ("rows_host", C.c_void_p), ("next256_host", C.c_void_p), ("accept_host", C.c_void_p),
+                    ("n_byte_states", C.c_int), ("eos", C.c_int)]
+
+    def decoder_set_fsm_parts_rc(self, dec, n_states, flags, parts):
+        """the return code of gten_hip_decoder_set_fsm_parts.  parts: in order, ("rows", u16 [count][n_vocab]) or
+        ("regex", next256 u16 [Sb][256], accept u8 [Sb], eos); flags u8 [n_states] (read for the row parts)."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        keep, arr, at = [], (self.FsmPart * max(len(parts), 1))(), 0
+        for k, p in enumerate(parts):
+            if p[0] == "rows":
+                rows = np.ascontiguousarray(p[1], dtype=np.uint16)
+                keep.append(rows)
+                arr[k] = self.FsmPart(at, len(rows), rows.ctypes.data, None, None, 0, -1)
+                at += len(rows)
+            else:
+                n256, acc, eos = np.ascontiguousarray(p[1], dtype=np.uint16), np.ascontiguousarray(p[2], dtype=np.uint8), int(p[3])
+                keep += [n256, acc]
+                count = len(acc) + (1 if eos >= 0 else 0)
+                arr[k] = self.FsmPart(at, count, None, n256.ctypes.data, acc.ctypes.data, len(acc), eos)
+                at += count
+        return self._set_fsm_parts(dec, int(n_states), flags.ctypes.data_as(C.c_void_p), C.cast(arr, C.c_void_p), len(parts))
+
+    def decoder_set_fsm_parts(self, dec, n_states, flags, parts):
+        self._check(self.decoder_set_fsm_parts_rc(dec, n_states, flags, parts))
+
+    def decoder_fsm_pool(self, dec, n_vocab):
+        """the decoder's pool read back from the device through gten_hip_decoder_fsm_info's pointers: (next u16 [S][n_vocab], flags u8 [S])"""
+        S, on, nd, fd = C.c_int(0), C.c_int(0), C.c_void_p(), C.c_void_p()
+        self._check(self._fsm_info(dec, C.byref(S), None, None, C.byref(on), 0, 0, 0, None, C.byref(nd), C.byref(fd)))
+        if S.value == 0:
+            return np.zeros((0, n_vocab), np.uint16), np.zeros(0, np.uint8)
+        nxt, flags = np.empty((S.value, n_vocab), np.uint16), np.empty(S.value, np.uint8)
+        self.sync()
+        self._check(self._d2h(nxt.ctypes.data_as(C.c_void_p), nd.value, nxt.nbytes))
+        self._check(self._d2h(flags.ctypes.data_as(C.c_void_p), fd.value, flags.nbytes))
+        return nxt, flags
 
     def mask_rows_fsm(self, logits, n_rows, n_vocab, row_stride, pool, states, hist=None, r=1.0, freq=0.0, pres=0.0):
         """gten_hip_mask_rows_fsm: the rows the draw would be made from, f32[n_rows][n_vocab].  pool: fsm_upload()'s tuple; states: one

@@ -108,8 +108,6 @@ int gten_host_model_generate(gten_host_model* m, int32_t* tokens, int n_prompt, 
 }
 
 // ---- tokenizer (host/tokenizer.h): ids and pieces of the reference's tokenizer.h on the same vocabulary file
-struct gten_host_tokenizer { Tokenizer tok; gten_host_tokenizer(const char* path, int vocab) : tok(path, vocab) {} };
-
 gten_host_tokenizer* gten_host_tokenizer_create(const char* path, int vocab_size)
 {
     if (!path || vocab_size <= 0) return nullptr;

@@ -4,14 +4,11 @@
 
 #include <vector>
 
+#include "../../include/gten_hip_regex.h"
 #include "capi_handles.h"
 #include "fsm_build.h"
 
 using namespace gten;
-
-struct gten_host_fsm {
-    FsmPool pool;
-};
 
 namespace {
 
@@ -35,6 +32,21 @@ int set_pool(gten_hip_decoder* dec, int n_vocab, const gten_host_fsm* f)
 {
     if (!f) return gten_hip_decoder_set_fsm(dec, nullptr, nullptr, 0);
     if (f->pool.n_vocab() != n_vocab || f->pool.n_states() < 1) return -1;
+    if (f->pool.has_regex()) {
+        // regex ranges never cross the bus as tables: the decoder gets the vocabulary's bytes and expands them itself
+        // (include/gten_hip_regex.h); the ranges of host rows are uploaded as they always were
+        if (const int rc = gten_hip_decoder_set_vocab_bytes(dec, f->pool.vocab_bytes(), f->pool.vocab_offsets())) return rc;
+        std::vector<gten_hip_fsm_part> parts;
+        for (const FsmPool::Part& p : f->pool.parts()) {
+            if (p.regex < 0) {
+                parts.push_back(gten_hip_fsm_part{p.first, p.count, f->pool.host_rows(p), nullptr, nullptr, 0, -1});
+            } else {
+                const FsmPool::Regex& r = f->pool.regex(p.regex);
+                parts.push_back(gten_hip_fsm_part{p.first, p.count, nullptr, r.dfa.next.data(), r.dfa.accept.data(), r.dfa.n_states(), r.eos});
+            }
+        }
+        return gten_hip_decoder_set_fsm_parts(dec, f->pool.n_states(), f->pool.flags(), parts.data(), (int)parts.size());
+    }
     return gten_hip_decoder_set_fsm(dec, f->pool.next(), f->pool.flags(), f->pool.n_states());
 }
 

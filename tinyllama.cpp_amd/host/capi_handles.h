@@ -4,7 +4,9 @@
 #include <memory>
 
 #include "../../include/gten_host.h"
+#include "fsm_build.h"
 #include "generate.h"
+#include "tokenizer.h"
 
 struct gten_host_model {
     gten_host_config cfg;
@@ -14,4 +16,13 @@ struct gten_host_model {
 struct gten_host_batch {
     gten_host_config cfg;
     std::unique_ptr<gten::TinyLlamaBatch> batch;
+};
+
+struct gten_host_fsm {
+    gten::FsmPool pool;
+};
+
+struct gten_host_tokenizer {
+    Tokenizer tok;
+    gten_host_tokenizer(const char* path, int vocab) : tok(path, vocab) {}
 };

@@ -2,26 +2,94 @@
 // of [states][n_vocab] entries and a u8 `flags` row.  Host C++ with no device call, shared by the command line program and -- through
 // the flat gten_host_fsm_* exports of host/capi_fsm.cpp -- by Python.  Every builder appends its automaton to the pool as a new range
 // of states and returns its start state; a refusal (< 0) leaves the pool as it was.
+//
+// A regular expression (add_regex; host/regex_build.h) is kept as its byte automaton only -- a few KB instead of
+// 2 * n_vocab bytes per state.  The pool is then a list of PARTS: ranges of host rows (packed in next_) and ranges that are byte
+// automata.  next() materialises the latter with the host expansion (regex_expand: the definition the device's expansion is held to);
+// a pool with no such range is one part, and next() is the table it always was.
 #pragma once
 
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/gten_hip_fsm.h"
+#include "regex_build.h"
 
 namespace gten {
 
 class FsmPool {
 public:
-    enum : int { kBadArgument = -1, kTooLarge = -2, kPrefix = -3 };
+    enum : int { kBadArgument = -1, kTooLarge = -2, kPrefix = -3, kUnsupported = -4 };
+
+    // states [first, first + count): host rows at next_[rows_at ...] (regex < 0), or byte automaton number `regex`
+    struct Part { int first, count; size_t rows_at; int regex; };
+    struct Regex { ByteDfa dfa; int eos; };
 
     explicit FsmPool(int n_vocab) : V_{n_vocab} {}
     int n_vocab() const { return V_; }
     int n_states() const { return (int)flags_.size(); }
-    const uint16_t* next() const { return next_.data(); }
+    // the whole pool as one table (valid until the next add): with regex ranges, the host expansion of each beside the host rows
+    const uint16_t* next() const
+    {
+        if (regexes_.empty()) return next_.data();
+        if (view_.empty()) {
+            view_.resize((size_t)n_states() * (size_t)V_);
+            for (const Part& p : parts_) {
+                uint16_t* to = view_.data() + (size_t)p.first * (size_t)V_;
+                if (p.regex < 0) std::memcpy(to, next_.data() + p.rows_at, (size_t)p.count * (size_t)V_ * sizeof(uint16_t));
+                else regex_expand(regexes_[(size_t)p.regex].dfa, bytes_.data(), offsets_.data(), V_, regexes_[(size_t)p.regex].eos, p.first, to);
+            }
+        }
+        return view_.data();
+    }
     const uint8_t* flags() const { return flags_.data(); }
+    bool has_regex() const { return !regexes_.empty(); }
+    const std::vector<Part>& parts() const { return parts_; }
+    const Regex& regex(int i) const { return regexes_[(size_t)i]; }
+    const uint16_t* host_rows(const Part& p) const { return next_.data() + p.rows_at; }
+    bool has_vocab() const { return !offsets_.empty(); }
+    const uint8_t* vocab_bytes() const { return bytes_.data(); }
+    const int32_t* vocab_offsets() const { return offsets_.data(); }
+
+    // The vocabulary as byte strings: id i spells bytes[offsets[i], offsets[i + 1]).  Refused once a regex range exists.
+    int set_vocab(const uint8_t* bytes, const int32_t* offsets)
+    {
+        if (!offsets || offsets[0] != 0 || !regexes_.empty()) return kBadArgument;
+        for (int i = 0; i < V_; i++)
+            if (offsets[i + 1] < offsets[i]) return kBadArgument;
+        if (offsets[V_] > 0 && !bytes) return kBadArgument;
+        offsets_.assign(offsets, offsets + V_ + 1);
+        bytes_.assign(bytes, bytes + offsets[V_]);
+        bytes_.push_back(0);                 // (never empty: data() is a pointer)
+        return 0;
+    }
+
+    // The pattern's byte automaton (regex_compile) as a range of Sb states, and the END state behind them when eos >= 0; the start
+    // state.  An identical (pattern, eos) of this pool gives the range it already has.  *error_offset (may be NULL): where a refused
+    // pattern offends, or -1.
+    int add_regex(const char* pattern, size_t n, int eos, int* error_offset)
+    {
+        if (error_offset) *error_offset = -1;
+        if (!pattern || !has_vocab() || eos < -1 || eos >= V_) return kBadArgument;
+        const std::pair<std::string, int> key{std::string(pattern, n), eos};
+        const auto it = regex_start_.find(key);
+        if (it != regex_start_.end()) return it->second;
+        Regex r{ByteDfa{}, eos};
+        if (const int rc = regex_compile(pattern, n, r.dfa, error_offset)) return rc;
+        const int count = regex_pool_states(r.dfa, eos), base = n_states();
+        if (!fits(count)) return kTooLarge;
+        flags_.resize((size_t)(base + count));
+        regex_flags(r.dfa, eos, flags_.data() + base);
+        parts_.push_back(Part{base, count, 0, (int)regexes_.size()});
+        regexes_.push_back(std::move(r));
+        regex_start_.emplace(key, base);
+        view_.clear();
+        return base;
+    }
 
     // Aho-Corasick over the n id sequences ids[offsets[k], offsets[k + 1]): nothing is banned, a state is final where any sequence
     // ends (so walking any id string from the start state is final exactly after the first position at which a sequence ends).
@@ -117,6 +185,9 @@ private:
     int append(const std::vector<uint16_t>& rows, const std::vector<uint8_t>& fin, int S)
     {
         const int base = n_states();
+        if (!parts_.empty() && parts_.back().regex < 0) parts_.back().count += S;        // (host rows behind host rows: one part)
+        else parts_.push_back(Part{base, S, next_.size(), -1});
+        view_.clear();
         next_.reserve(next_.size() + rows.size());
         for (const uint16_t e : rows) next_.push_back(e == GTEN_HIP_FSM_DEAD ? e : (uint16_t)(e + base));
         static_assert(GTEN_HIP_FSM_FINAL == 1, "the builders mark a final state with 1");
@@ -125,8 +196,14 @@ private:
     }
 
     int V_;
-    std::vector<uint16_t> next_;
-    std::vector<uint8_t> flags_;
+    std::vector<uint16_t> next_;            // the rows of the host parts, packed
+    std::vector<uint8_t> flags_;            // of every state
+    std::vector<Part> parts_;
+    std::vector<Regex> regexes_;
+    std::map<std::pair<std::string, int>, int> regex_start_;
+    std::vector<uint8_t> bytes_;
+    std::vector<int32_t> offsets_;
+    mutable std::vector<uint16_t> view_;    // next()'s table while regex ranges exist
 };
 
 } // namespace gten

@@ -8,7 +8,8 @@
 // of the model's decoder (include/gten_hip_bias.h), in both generation modes; --logprobs N prints every generated id's log-prob and its N
 // most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h);
 // --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h);
-// --stop / --choice end the answer at, or hold it to, id sequences through a token automaton on the device (include/gten_hip_fsm.h).
+// --stop / --choice end the answer at, or hold it to, id sequences through a token automaton on the device (include/gten_hip_fsm.h);
+// --regex holds it to a regular expression over its text, expanded over the vocabulary on the device (include/gten_hip_regex.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <string_view>
 #include <vector>
 
+#include "../../include/gten_hip_regex.h"
 #include "fsm_build.h"
 #include "generate.h"
 #include "tokenizer.h"
@@ -65,6 +67,10 @@ Optional args.
            Not with --choice, --ban, --allow or --score.
 --choice ID[,ID...] : the answer is exactly one of the id sequences given this way. Repeatable; none may be a prefix of another.
            Works with -greedy too. Not with --stop, --ban, --allow or --score.
+--regex PATTERN : the text of the answer matches PATTERN as a whole (the dialect of host/regex_build.h: literals, classes, groups,
+           | ? * + {m,n}, ASCII \d \w \s; no anchors, look-around or back-references). Where the pattern could stop or go on the
+           model decides by drawing the end-of-turn id. Works with -greedy too. Not with --choice, --stop, --ban, --allow or
+           --score: an answer is bound to one start state of one automaton.
 )";
 
 struct Options {
@@ -86,7 +92,9 @@ struct Options {
     bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     bool constrained() const { return !ban.empty() || !allow.empty(); }
     std::vector<std::vector<int32_t>> stop, choice;      // --stop / --choice, one id sequence per flag
-    bool automaton() const { return !stop.empty() || !choice.empty(); }
+    std::string regex;                                   // --regex
+    bool regex_given = false;
+    bool automaton() const { return !stop.empty() || !choice.empty() || regex_given; }
 };
 
 static void emit(const Options& o, Tokenizer& tok, int prev, int id)
@@ -133,8 +141,39 @@ static void set_constraint(const Options& o, TinyLlama& model)
 }
 
 // --stop / --choice as the pool of the model's decoder (host/fsm_build.h); the start state the answers are bound to
-static int set_automaton(const Options& o, TinyLlama& model, int n_vocab)
+static int set_automaton(const Options& o, TinyLlama& model, const Tokenizer& tok, int n_vocab)
 {
+    if (o.regex_given) {
+        // the vocabulary's byte strings as decode prints them (control pieces and the ids past the tokenizer: empty), the pattern as a
+        // byte automaton, and the expansion of the one over the other on the device
+        std::vector<uint8_t> bytes;
+        std::vector<int32_t> offsets{0};
+        for (int i = 0; i < n_vocab; i++) {
+            if (i > 2 && i < tok.vocab_size()) {
+                const std::string piece = tok.piece_bytes(i);
+                bytes.insert(bytes.end(), piece.begin(), piece.end());
+            }
+            offsets.push_back((int32_t)bytes.size());
+        }
+        FsmPool pool(n_vocab);
+        int at = -1;
+        pool.set_vocab(bytes.data(), offsets.data());
+        const int start = pool.add_regex(o.regex.c_str(), o.regex.size(), tok.eos, &at);
+        if (start < 0) {
+            std::cerr << "error: --regex: " << (start == kRegexUnsupported ? "unsupported construct" : start == kRegexTooLarge ? "too many states" : "bad syntax");
+            if (at >= 0) std::cerr << " at byte " << at;
+            std::cerr << ".\n";
+            std::exit(EXIT_FAILURE);
+        }
+        const FsmPool::Regex& r = pool.regex(0);
+        const gten_hip_fsm_part part{0, pool.n_states(), nullptr, r.dfa.next.data(), r.dfa.accept.data(), r.dfa.n_states(), r.eos};
+        if (gten_hip_decoder_set_vocab_bytes(model.decoder_handle(), pool.vocab_bytes(), pool.vocab_offsets()) != 0 ||
+            gten_hip_decoder_set_fsm_parts(model.decoder_handle(), pool.n_states(), pool.flags(), &part, 1) != 0) {
+            std::cerr << "error: " << gten_hip_last_error() << "\n";
+            std::exit(EXIT_FAILURE);
+        }
+        return start;
+    }
     const std::vector<std::vector<int32_t>>& lists = o.stop.empty() ? o.choice : o.stop;
     std::vector<int32_t> ids, offsets{0};
     for (const auto& l : lists) {
@@ -366,6 +405,17 @@ int main(int argc, char const* argv[])
             std::vector<int32_t> list;
             if (!parse_id_list(is_stop ? "stop" : "choice", value(is_stop ? "stop" : "choice"), 32003, &list, false)) return -1;
             (is_stop ? o.stop : o.choice).push_back(list);
+        } else if (arg == "--regex") {
+            o.regex = value("regex");
+            o.regex_given = true;
+            int at = -1;
+            ByteDfa dfa;
+            if (const int rc = regex_compile(o.regex.c_str(), o.regex.size(), dfa, &at)) {
+                std::cerr << "--regex: " << (rc == kRegexUnsupported ? "unsupported construct" : rc == kRegexTooLarge ? "too many states" : "bad syntax");
+                if (at >= 0) std::cerr << " at byte " << at;
+                std::cerr << ".\n";
+                return -1;
+            }
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
@@ -375,8 +425,10 @@ int main(int argc, char const* argv[])
     if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
     if (o.pen_given && !o.score_path.empty()) { std::cerr << "the repeat, frequency and presence penalties do not apply to --score.\n"; return -1; }
     if (!o.stop.empty() && !o.choice.empty()) { std::cerr << "--stop and --choice do not combine: an answer follows one automaton.\n"; return -1; }
-    if (o.automaton() && o.constrained()) { std::cerr << "--stop and --choice do not combine with --ban or --allow.\n"; return -1; }
-    if (o.automaton() && !o.score_path.empty()) { std::cerr << "--stop and --choice do not apply to --score.\n"; return -1; }
+    if (o.regex_given && !o.choice.empty()) { std::cerr << "--regex and --choice do not combine: an answer follows one automaton.\n"; return -1; }
+    if (o.regex_given && !o.stop.empty()) { std::cerr << "--regex and --stop do not combine: an answer is bound to one start state.\n"; return -1; }
+    if (o.automaton() && o.constrained()) { std::cerr << "--stop, --choice and --regex do not combine with --ban or --allow.\n"; return -1; }
+    if (o.automaton() && !o.score_path.empty()) { std::cerr << "--stop, --choice and --regex do not apply to --score.\n"; return -1; }
     for (size_t a = 0; a < o.choice.size(); a++)
         for (size_t b = 0; b < o.choice.size(); b++)
             if (a != b && o.choice[a].size() <= o.choice[b].size() && std::equal(o.choice[a].begin(), o.choice[a].end(), o.choice[b].begin())) {
@@ -414,7 +466,7 @@ int main(int argc, char const* argv[])
         seed = ((uint64_t)rd() << 32) | (uint64_t)rd();
     }
     if (o.constrained()) set_constraint(o, model);
-    const int fsm_start = o.automaton() ? set_automaton(o, model, 32003) : -1;
+    const int fsm_start = o.automaton() ? set_automaton(o, model, tokenizer, 32003) : -1;
     uint32_t turn = 0;
     auto answer = [&](const std::string& prompt) { run(o, prompt, model, tokenizer, seed, &turn, fsm_start); };
     if (o.prompt.empty()) {

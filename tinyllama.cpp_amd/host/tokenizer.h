@@ -89,6 +89,16 @@ public:
 
     int vocab_size() const { return (int)vocab_.size(); }
 
+    // The bytes decode() prints for `token` behind any id but BOS (no dropped leading space): "<0xHH>" as the single byte HH -- the
+    // NUL byte too, which decode()'s C string cannot carry.  "" past the vocabulary.
+    std::string piece_bytes(int token) const
+    {
+        const char* piece = decode(0, token);
+        const char* lo = &byte_pieces_[0][0];
+        if (piece >= lo && piece < lo + sizeof(byte_pieces_)) return std::string(piece, 1);
+        return std::string(piece);
+    }
+
 private:
     struct Cand {
         float score;

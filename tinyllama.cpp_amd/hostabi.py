@@ -69,6 +69,9 @@ class GtenHost:
                    "gten_host_fsm_n_states", "gten_host_fsm_tables", "gten_host_model_set_fsm", "gten_host_batch_set_fsm", "gten_host_model_fsm_info",
                    "gten_host_batch_fsm_info", "gten_host_model_set_seq_fsm", "gten_host_batch_set_seq_fsm", "gten_host_model_fsm_states",
                    "gten_host_batch_fsm_states", "gten_host_batch_fsm_decoder", "gten_host_model_generate_fsm", "gten_host_batch_generate_fsm", "gten_host_batch_serve_fsm"]
+    # include/gten_host_regex.h (regular expressions as ranges of an automaton pool, host/capi_regex.cpp)
+    REGEX_SYMBOLS = ["gten_host_fsm_set_vocab", "gten_host_tokenizer_vocab_bytes", "gten_host_fsm_add_regex", "gten_host_regex_byte_dfa",
+                     "gten_host_fsm_n_regex"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -159,6 +162,11 @@ class GtenHost:
         self._fsm_add_table = _sig(L, "gten_host_fsm_add_table", ci, [vp, vp, vp, ci])
         self._fsm_n_states = _sig(L, "gten_host_fsm_n_states", ci, [vp])
         self._fsm_tables = _sig(L, "gten_host_fsm_tables", ci, [vp, C.POINTER(vp), C.POINTER(vp)])
+        self._fsm_set_vocab = _sig(L, "gten_host_fsm_set_vocab", ci, [vp, vp, vp])
+        self._tok_vocab_bytes = _sig(L, "gten_host_tokenizer_vocab_bytes", C.c_longlong, [vp, ci, vp, ci, vp, C.c_longlong, vp])
+        self._fsm_add_regex = _sig(L, "gten_host_fsm_add_regex", ci, [vp, C.c_char_p, ci, C.POINTER(ci)])
+        self._regex_byte_dfa = _sig(L, "gten_host_regex_byte_dfa", ci, [C.c_char_p, vp, vp, ci, C.POINTER(ci)])
+        self._fsm_n_regex = _sig(L, "gten_host_fsm_n_regex", ci, [vp])
         self._m_set_fsm = _sig(L, "gten_host_model_set_fsm", ci, [vp, vp])
         self._b_set_fsm = _sig(L, "gten_host_batch_set_fsm", ci, [vp, vp])
         self._m_fsm_info = _sig(L, "gten_host_model_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
@@ -431,6 +439,32 @@ def _penalty_arg(n, rep, freq, pres, last_n, count_prompt):
     return s
 
 
+class RegexError(ValueError):
+    def __init__(self, code, offset, pattern):
+        super().__init__(f"regex {pattern!r} refused: {code} at byte {offset}")
+        self.code, self.offset = code, offset
+
+
+def vocab_arrays(pieces):
+    """a list of bytes objects as (bytes u8[], offsets int32[n + 1])"""
+    off = np.zeros(len(pieces) + 1, np.int32)
+    off[1:] = np.cumsum([len(p) for p in pieces])
+    return np.frombuffer(b"".join(bytes(p) for p in pieces), np.uint8).copy(), off
+
+
+def byte_dfa(host, pattern):
+    """the pattern's canonical minimal byte automaton (host/regex_build.h): (next256 u16 [Sb][256] with 0xFFFF for no edge, accept u8 [Sb]);
+    a refusal raises RegexError"""
+    data = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+    off = C.c_int(-1)
+    n = host._regex_byte_dfa(data, None, None, 0, C.byref(off))
+    if n < 0:
+        raise RegexError(n, off.value, pattern)
+    n256, acc = np.zeros((n, 256), np.uint16), np.zeros(n, np.uint8)
+    host._regex_byte_dfa(data, _ptr(n256), _ptr(acc), n, C.byref(off))
+    return n256, acc
+
+
 class Fsm:
     """An automaton pool under construction (include/gten_host_fsm.h, host/fsm_build.h): no device needed.  add_stop / add_choices /
     add_table append an automaton and return its start state; a refusal raises ValueError with the builder's code and leaves the
@@ -472,6 +506,38 @@ class Fsm:
         if rc < 0:
             raise ValueError(f"add_table refused: {rc}")
         return rc
+
+    # ---- regular expressions (include/gten_host_regex.h)
+    def set_vocab(self, vocab):
+        """the pool's vocabulary as byte strings: a HostTokenizer (its vocab_bytes(n_vocab)), a list of n_vocab bytes objects, or a
+        (bytes u8[], offsets int32[n_vocab + 1]) pair.  Needed before add_regex."""
+        if isinstance(vocab, HostTokenizer):
+            vocab = vocab.vocab_bytes(self.n_vocab)
+        elif not (isinstance(vocab, tuple) and len(vocab) == 2):
+            vocab = vocab_arrays(vocab)
+        vb, vo = np.ascontiguousarray(vocab[0], dtype=np.uint8), np.ascontiguousarray(vocab[1], dtype=np.int32)
+        if len(vo) != self.n_vocab + 1:
+            raise ValueError(f"set_vocab: {len(vo) - 1} pieces for {self.n_vocab} ids")
+        rc = self.host._fsm_set_vocab(self.h, _ptr(vb) if len(vb) else None, _ptr(vo))
+        if rc < 0:
+            raise ValueError(f"set_vocab refused: {rc}")
+        self.vocab = (vb, vo)
+
+    def add_regex(self, pattern, eos=-1):
+        """the pattern (str) as a range of the pool: its start state.  A refusal raises RegexError (a ValueError) with .code (-1 syntax,
+        -2 too many states, -4 an unsupported construct) and .offset, the byte offset of the offence."""
+        off = C.c_int(-1)
+        rc = self.host._fsm_add_regex(self.h, pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern), int(eos), C.byref(off))
+        if rc < 0:
+            raise RegexError(rc, off.value, pattern)
+        return rc
+
+    @property
+    def n_regex(self):
+        return self.host._fsm_n_regex(self.h)
+
+    def byte_dfa(self, pattern):
+        return byte_dfa(self.host, pattern)
 
     @property
     def n_states(self):
@@ -522,6 +588,22 @@ class HostTokenizer:
 
     def decode(self, prev_token, token):
         return self.host._tok_decode(self.h, prev_token, token)        # bytes
+
+    def vocab_bytes(self, n_vocab, empty=None):
+        """the byte strings of ids [0, n_vocab) as decode prints them ("<0xHH>" as the byte, no dropped space): (bytes u8[], offsets
+        int32[n_vocab + 1]); ids past the tokenizer and the ids of `empty` (None: 0, 1, 2) are empty (include/gten_host_regex.h)"""
+        off = np.zeros(n_vocab + 1, np.int32)
+        e = np.ascontiguousarray(empty, dtype=np.int32) if empty is not None else None
+        args = (self.h, int(n_vocab), _ptr(e) if e is not None and len(e) else None, len(e) if e is not None else 0)
+        if e is not None and len(e) == 0:                                # "nothing is empty": an id outside the vocabulary
+            e = np.array([-1], np.int32)
+            args = (self.h, int(n_vocab), _ptr(e), 1)
+        n = self.host._tok_vocab_bytes(*args, None, 0, _ptr(off))
+        if n < 0:
+            raise GtenHipError(f"tokenizer_vocab_bytes rc={n}")
+        buf = np.zeros(max(n, 1), np.uint8)
+        self.host._tok_vocab_bytes(*args, _ptr(buf), n, _ptr(off))
+        return buf[:n], off
 
     def close(self):
         if self.h:
@@ -903,6 +985,20 @@ class HostModel:
         ids = buf[:total].copy()
         return (ids, int(ended[0]), lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else (ids, int(ended[0]))
 
+    def generate_regex(self, prompt, max_tokens, pattern, vocab, eos=-1, **kw):
+        """generate_fsm() bound to `pattern` (None: not bound): a pool of that one pattern over `vocab` (what Fsm.set_vocab takes) becomes
+        the decoder's pool -- expanded on the device -- and the first new id is chosen in its start state.  kw: generate_fsm's."""
+        if pattern is None:
+            return self.generate_fsm(prompt, max_tokens, -1, eos, **kw)
+        f = Fsm(self.host, self.cfg.n_vocab)
+        try:
+            f.set_vocab(vocab)
+            start = f.add_regex(pattern, eos)
+            self.set_fsm(f)
+            return self.generate_fsm(prompt, max_tokens, start, eos, **kw)
+        finally:
+            f.close()
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -1274,6 +1370,20 @@ class HostBatch:
                                  *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
                                  *args, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
         return (ids, stats, ended) if n_top is None else (ids, stats, ended, *rec)
+
+    def serve_regex(self, prompts, patterns, eos, vocab, max_tokens, top_k=0, temp=1.0, seed=0, **kw):
+        """serve_fsm() with one pattern (or None: not bound) per prompt: a pool of the DISTINCT patterns over `vocab` (what Fsm.set_vocab
+        takes) becomes the shared decoder's pool -- expanded on the device -- and every prompt starts in its pattern's start state.
+        Returns serve_fsm()'s tuple with the list of start states behind it.  kw: serve_fsm's."""
+        f = Fsm(self.host, self.cfg.n_vocab)
+        try:
+            f.set_vocab(vocab)
+            starts = [-1 if p is None else f.add_regex(p, eos) for p in patterns]
+            if f.n_states > 0:
+                self.set_fsm(f)
+            return (*self.serve_fsm(prompts, max_tokens, eos, top_k, temp, seed, starts, **kw), starts)
+        finally:
+            f.close()
 
     # ---- sessions (include/gten_host_sessions.h, DESIGN.md 3.17)
     def sessions_reserve(self, n):
