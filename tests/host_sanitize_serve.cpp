@@ -3,7 +3,8 @@
 // stand-in for libgten_hip.so whose "model" is a fixed next-id rule) in a binary built with -fsanitize=address,undefined
 // (tests/test_host_sanitize_cpu.py).  What is checked besides the sanitizers: every way of generating -- the reference's
 // loop through logits(), the device sampler, the fixed batch, the queue through the slots under several admission schedules
-// and slice lengths, one by one or (16 slots) several prompts per row matrix -- returns the same ids.  Exits 0 when every check holds.
+// and slice lengths, one by one or (16 slots) several prompts per row matrix -- returns the same ids, and the 16-slot queue takes
+// the same number of steps, admissions and lane-steps as it always did (kStats16).  Exits 0 when every check holds.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,15 @@
     do {                                                                      \
         if (!(c)) { std::fprintf(stderr, "host_sanitize_serve: %s failed (line %d)\n", #c, __LINE__); return 1; } \
     } while (0)
+
+// The 16-slot queue below per (schedule k, slice) in the order of its loops: prompt tokens, new ids, steps, admissions, lane_steps,
+// lane_rows, moved -- as the scheduler gave them before it became host/serve.h (this program built from that commit printed them).
+static const long kStats16[12][7] = {
+    {720, 649, 80, 19, 80, 16, 0},  {720, 649, 78, 19, 78, 16, 0},   {720, 649, 78, 19, 78, 16, 0},     // k 0: slice 16, 5, 3
+    {720, 649, 297, 19, 297, 16, 0}, {720, 649, 127, 19, 127, 16, 0}, {720, 649, 95, 19, 95, 16, 0},    // k 1
+    {720, 649, 176, 19, 176, 16, 0}, {720, 649, 90, 19, 90, 16, 0},   {720, 649, 84, 19, 84, 16, 0},    // k 2
+    {720, 649, 96, 19, 96, 16, 0},   {720, 649, 83, 19, 83, 16, 0},   {720, 649, 81, 19, 81, 16, 0},    // k 8
+};
 
 int main()
 {
@@ -101,11 +111,20 @@ int main()
             npr[(size_t)j] = lengths[j];
             std::memcpy(pr.data() + (size_t)j * total, prompts[(size_t)j].data(), (size_t)lengths[j] * 4);
         }
+        int run = 0;
         for (int k : {0, 1, 2, 8})
             for (int slice : {16, 5, 3}) {
                 CHECK(gten_host_batch_set_serve_schedule(b, k) == 0);
-                double stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                CHECK(gten_host_batch_serve2(b, pr.data(), npr.data(), NP, total, total, eos, slice, 0, nullptr, out.data(), tot.data(), stats, 8) == 0);
+                double stats[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                CHECK(gten_host_batch_serve2(b, pr.data(), npr.data(), NP, total, total, eos, slice, 0, nullptr, out.data(), tot.data(), stats, 9) == 0);
+                // (16 slots: what the scheduler DID, not only what it returned -- the stub's stream_idle is a counter, so schedule 0
+                //  repeats too in this fixed order of calls; the two timing entries are left out)
+                if (n_seq == 16) {
+                    const long got[7] = {(long)stats[0], (long)stats[1], (long)stats[2], (long)stats[3], (long)stats[6], (long)stats[7], (long)stats[8]};
+                    std::printf("stats k %d slice %2d: {%ld, %ld, %ld, %ld, %ld, %ld, %ld}\n", k, slice, got[0], got[1], got[2], got[3], got[4], got[5], got[6]);
+                    for (int i = 0; i < 7; i++) CHECK(got[i] == kStats16[run][i]);
+                }
+                run++;
                 long new_ids = 0;
                 for (int j = 0; j < NP; j++) {
                     CHECK(tot[(size_t)j] == (int)alone_eos[(size_t)j].size());

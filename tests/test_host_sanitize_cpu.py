@@ -35,7 +35,8 @@ def test_modules_and_scheduler_under_sanitizers_against_a_stub_device(tmp_path):
     TinyLlamaBatch, the continuous-batching scheduler, capi.cpp -- under ASan + UBSan, linked against tests/hip_stub.cpp (a
     test-only stand-in for libgten_hip.so on host memory whose 'model' is a fixed next-id rule).  tests/host_sanitize_serve.cpp
     checks that the reference's loop, the device sampler, the fixed batch and the queue through the slots (4 admission
-    schedules x 3 slice lengths, per-prompt budgets, 2 and 8 slots) all return the same ids."""
+    schedules x 3 slice lengths, per-prompt budgets, 2 and 8 slots) all return the same ids, and that the 16-slot queue's stats
+    (prompt tokens, new ids, steps, admissions, lane_steps, lane_rows, moved) per schedule and slice are the pinned ones."""
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     exe = str(tmp_path / "host_sanitize_serve")
@@ -49,6 +50,29 @@ def test_modules_and_scheduler_under_sanitizers_against_a_stub_device(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
     assert "host_sanitize_serve ok" in r.stdout
+
+
+def test_serving_decisions_under_sanitizers(tmp_path):
+    """host/serve_plan.h -- which queue items a batch of prompts takes (free sets, kPreMax, kPreRows, the fixed schedule's cap, group
+    copies and session items that cost neither), the order free slots fill in, when the tail's emptiest lane moves, the length of
+    a slice -- on hand-written queues (tests/host_serve_plan.cpp), under ASan + UBSan.  The program includes that header alone:
+    the decisions need no device and no model."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    src = os.path.join(ROOT, "tests", "host_serve_plan.cpp")
+    includes = [line for line in open(src) if line.startswith("#include \"")]
+    assert includes == ['#include "../tinyllama.cpp_amd/host/serve_plan.h"\n'], includes
+    plan = open(os.path.join(ROOT, "tinyllama.cpp_amd", "host", "serve_plan.h")).read()
+    assert "#include \"" not in plan and "gten_hip" not in plan          # device-free: the standard library only
+    exe = str(tmp_path / "host_serve_plan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           src, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:protect_shadow_gap=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    assert "host_serve_plan ok" in r.stdout
 
 
 def test_stub_device_covers_the_whole_header(tmp_path):

@@ -1,6 +1,7 @@
 """-m gpu: continuous batching (round-1 verdict "slot admission/eviction").  A queue of prompts is
 served through the slots of a multi-sequence decoder: a slot whose sequence ended takes the next prompt while the
-others go on (TinyLlamaBatch::serve_with; gten_hip_decoder_slot_start / _slot_park / _run / _slot_ids).  Up to 8 slots every
+others go on (TinyLlamaBatch::serve_with, whose scheduler is ServeQueue in host/serve.h and whose decisions are
+host/serve_plan.h; gten_hip_decoder_slot_start / _slot_park / _run / _slot_ids).  Up to 8 slots every
 sequence's ids must be EXACTLY those of generating it alone on the single-sequence decoder."""
 import numpy as np
 import pytest
@@ -161,6 +162,41 @@ def test_lanes_without_a_live_slot_sit_the_run_out(hip):
     assert stats[0]["lane_rows"] == 128 and stats[0]["lane_steps"] <= stats[1]["lane_steps"] < 2 * stats[1]["steps"]
     assert stats[0]["lane_steps"] < 2 * stats[0]["steps"], stats[0]
     print("lane-steps with / without skipping:", stats[0]["lane_steps"], stats[1]["lane_steps"], "steps", stats[0]["steps"], stats[1]["steps"])
+
+
+def test_fixed_schedule_stats_are_those_of_the_scheduler_before_it_moved(hip):
+    """What the scheduler DOES, not only the ids it returns: the queue and the two lanes of the test above under
+    set_serve_schedule(2) with slices of 4 steps.  Under a fixed schedule the idle poll is not consulted, so shared steps,
+    admissions, lane-steps and moved sequences are deterministic: they must be what serve_with gave while the scheduler stood
+    inside it (host/tinyllama_model.h, before host/serve.h) -- measured once with that commit's host library on this call.
+    A fixed schedule never enters the tail (compact_tail asks for schedule 0, then as now), so `moved` is 0 there; that the
+    tail is really taken is asserted on the same queue under the free schedule, whose ids must be the same."""
+    pkg = load_package()
+    host = pkg.load_host()
+    cfg = host_cfg(tiny_config(Q4, Q8, n_heads=4, n_kv_heads=2, max_ctx=320, n_layers=2))
+    weights = [host.synth_weight(cfg, 1414, i) for i in range(len(cfg.weight_shapes()))]
+    lengths = [16 + (23 * i) % 140 for i in range(330)]
+    prompts = make_prompts(host, cfg, lengths, 17)
+    budgets = np.array([4 + (11 * i) % 70 for i in range(330)], np.int32)
+    b = host.batch(cfg, 256)
+    for i, w in enumerate(weights):
+        b.set_weight(i, w)
+    try:
+        b.set_serve_schedule(2)
+        fixed, st = b.serve(prompts, 300, -1, 4, max_new_each=budgets)
+    finally:
+        b.set_serve_schedule(0)
+    print("fixed schedule 2, slice 4:", {k: st[k] for k in ("steps", "admissions", "lane_steps", "lane_rows", "moved")})
+    # the parent commit's values for this call (its libgten_host.so beside this tree's kernels, run twice: identical)
+    assert st["lane_rows"] == 128
+    assert (st["steps"], st["admissions"], st["lane_steps"], st["moved"]) == (715, 330, 1430, 0)
+    free, st = b.serve(prompts, 300, -1, 4, max_new_each=budgets)
+    b.close()
+    print("free schedule, slice 4:", {k: st[k] for k in ("steps", "admissions", "lane_steps", "moved")})
+    assert st["moved"] > 0 and st["admissions"] == 330
+    assert st["lane_steps"] < 2 * st["steps"]                # (the tail's runs left the emptied lane out)
+    for j in range(330):
+        assert fixed[j].tolist() == free[j].tolist(), j
 
 
 def test_slot_api_errors_are_reported(hip):

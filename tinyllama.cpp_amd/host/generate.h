@@ -730,8 +730,8 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
         n_total[j] = take;
         if (ended_by) {
             // (shorter than its own limit: an eos, unless the policy saw a final state)
-            const int P = full[(size_t)j], mn = Each<int32_t>{max_new_each, max_new}[j];
-            const int limit = std::min(std::min(max_tokens, max_ctx), mn > 0 ? P + mn : max_ctx);
+            const int P = full[(size_t)j];
+            const int limit = serve_limit(P, max_tokens, max_ctx, Each<int32_t>{max_new_each, max_new}[j]);
             ended_by[j] = take < limit && P < limit ? kEndedByEos : kEndedByLength;
             if constexpr ((M & kFsm) != 0)
                 if (pick.fsm_ended[(size_t)j]) ended_by[j] = kEndedByFinal;

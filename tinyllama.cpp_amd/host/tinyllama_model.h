@@ -678,7 +678,13 @@ struct Each {
     T operator[](int j) const { return each ? each[j] : all; }
 };
 
+template <class Pick>
+class ServeQueue;                        // host/serve.h: the scheduler of TinyLlamaBatch::serve_with
+
 class TinyLlamaBatch {
+    template <class Pick>
+    friend class ServeQueue;
+
 public:
     TinyLlamaBatch(int n_seq, int n_ctx, ModuleDtype dtype, TinyLLamaParams p = TinyLLamaParams{}) : n_ctx_{n_ctx}, dtype_{dtype}, params_{p}
     {
@@ -1335,475 +1341,17 @@ public:
         return us;
     }
 
-    // ---- continuous batching: a queue of prompts served through the n_seq slots ------------------------------
-    // Every prompt is generated greedily to `max_tokens` ids in all (prompt included) or until `eos` (not stored,
-    // tinyllama.cpp:425), as greedy_sample does for one sequence; max_new > 0 additionally bounds the new ids per prompt.
-    // One host thread keeps two things going that OVERLAP on the GPU:
-    //   * a slice of `slice` shared free-running steps of the live slots, queued on stream 0 (gten_hip_decoder_run);
-    //   * while it runs: the prompts of the next sequences, one after the other, each on a free slot's own caches on stream 1
-    //     (operator path: iteration 0 of the reference's loop incl. the host argmax of its logits).  A parked slot idles on
-    //     the decoder's dummy caches (gten_hip_decoder_slot_park), so nothing the shared steps do touches the caches being
-    //     filled.  Prompt processing is host-bound (~500 short launches) and the shared steps are GPU-bound: side by side
-    //     they hide each other.
-    // Between two prompts the slice is polled (gten_hip_stream_idle): once done its ids are read (eos / length -> the slot is
-    // parked and becomes free) and the next slice starts at once with the slots whose prompts became ready meanwhile.  Nobody
-    // runs past its last step: a slot that ends inside a slice repeats that step until the slice is over
-    // (gten_hip_decoder_slot_start_until; cutting the slice to the shortest remaining run instead left 128 slots with
-    // slices of one to three steps and prompt batches of two).  Per sequence the ids are those of
-    // generating it alone (bit for bit up to 8 slots; tests/test_serving_gpu.py).
-    // (lane_steps: shared steps x the lanes each of them ran -- a lane whose slots are all parked is left out of a run; lane_rows:
-    //  slots per lane; new ids / (lane_steps x lane_rows) is the share of COMPUTED slot-steps that produced an id)
+    // ---- continuous batching: a queue of prompts served through the n_seq slots.  The scheduler is ServeQueue (host/serve.h, where
+    // the stats, sample groups and session items are explained; its decisions: host/serve_plan.h); `pick` chooses the ids
+    // (host/generate.h, ServePolicy).
     struct ServeStats { int64_t prompt_tokens = 0, new_tokens = 0, steps = 0, admissions = 0, lane_steps = 0, moved = 0; int lane_rows = 0; double prefill_s = 0.0, decode_s = 0.0; };
-    // How the ids are picked is `pick`'s business (host/generate.h, ServePolicy): the first id of a prompt processed onto a cache
-    // set (first / many), the requests of the slot that takes it (apply), its log-prob records (collect), everything off again (clear).
-    // With Pick::kFsm a prompt may be bound to a token automaton (include/gten_hip_fsm.h): the id that enters a final state ends it as
-    // an eos does but is kept (ended_first / states / enters_final), and its binding is set again wherever it goes on (bind_state).
-    // (max_new[j] > 0 additionally bounds the new ids of prompt j)
-    // SAMPLE GROUPS (include/gten_host_samples.h): group_of[j] >= 0 names the group of queue item j; consecutive items
-    // of one group hold THE SAME PROMPT -- the caller's word, no prompt is compared.  prepare_many takes whole groups while free
-    // sets and rows allow: the first member taken is computed, the others are copies of it (prefill_many_with's copy_of); a group
-    // that does not fit is cut, and what is left is a later group with a prompt pass of its own.  Ids and records are those of
-    // the same items without groups.  Sets written for a group of at least two readied members behind at least one full chunk carry
-    // a group mark; a slot started on such a set reads the prompt's full chunks from a group record of the decoder (GroupRecords).
     template <class Pick>
     ServeStats serve_with(const std::vector<std::vector<int32_t>>& prompts, int max_tokens, int eos, int slice,
                           std::vector<std::vector<int32_t>>* out, Each<int32_t> max_new, Each<int32_t> group_of, Pick& pick,
                           Each<int32_t> session = Each<int32_t>{nullptr, -1})
     {
-        // SESSION ITEMS (session[j] = s >= 0; the caller has checked that s is open and named once): prompts[j] is
-        // the session's ids + the turn's, and the item is that prompt in every respect but two -- its cache set is the session's own
-        // (never out of `pool`, never back into it) and only the rows the plan asks for are computed (prepare_many's continued
-        // items).  When the item ends the session takes the out row as its ids.
-        auto session_done = [&](int j) {
-            const int s = session[j];
-            if (s < 0) return;
-            Session& ss = sessions_[(size_t)s];
-            const std::vector<int32_t>& row = (*out)[(size_t)j];
-            const int generated = (int)row.size() - (int)prompts[(size_t)j].size();
-            ss.ids = row;
-            ss.rows = session_rows_after((int)row.size(), generated);
-        };
-        using clock = std::chrono::steady_clock;
-        ensure_decoder();
-        const int S = n_seq();
-        ServeStats st;
-        out->assign(prompts.size(), {});
-        // per slot: prompt index (-1: free), next step, last step, the cache set it decodes on (-1: none)
-        std::vector<int> job((size_t)S, -1), cur((size_t)S, 0), last((size_t)S, 0), set_of((size_t)S, -1);
-        std::vector<char> live((size_t)S, 0);
-        std::vector<int> lp_from((size_t)S, 0);                            // (Pick::kLogprobs) the first position whose record slot q has not handed over
-        // CACHE SETS (round 4).  A prompt is processed onto a free cache set, not onto a free slot: besides the S sets the
-        // sequences own there are `spare` more, so that prompts are ready BEFORE the slots that will take them end -- a slot
-        // that ends in a harvest gets a ready prompt's set bound (gten_hip_decoder_slot_bind) and joins the very next slice
-        // instead of sitting one or two slices out while its replacement is processed.  pool: the free sets; ready: processed
-        // prompts waiting for a slot, in queue order.
-        struct Ready { int j, set, cur, last; };
-        std::deque<Ready> ready;
-        const int spare = serve_spares_ >= 0 ? serve_spares_ : (batched_prompts() ? std::min(S / 4, 64) : 0);
-        ensure_spares(spare);
-        std::vector<int> pool;
-        for (int c = n_sets() - 1; c >= 0; c--) pool.push_back(c);           // (taken from the back: the sequences' own sets first)
-        size_t next = 0;
-        int n_live = 0;
-        slice = std::min(std::max(slice, 1), 64);                          // (gten_hip_decoder_slot_ids_all reads up to 64 steps at once)
-        int lane_rows = S, n_lanes = 1;
-        GTEN_HIP_OK(gten_hip_decoder_lane_info(dec_, &lane_rows, &n_lanes, nullptr));
-        st.lane_rows = lane_rows;
-        // free slots in the order they are filled: slots of lanes that already run first (a lane without a live slot sits a
-        // run out, so a half-empty queue should occupy as few lanes as possible), then by index
-        auto free_slots = [&]() {
-            std::vector<int> busy((size_t)n_lanes, 0), fq;
-            for (int q = 0; q < S; q++)
-                if (job[(size_t)q] >= 0) busy[(size_t)(q / lane_rows)]++;
-            for (int pass = 0; pass < 2; pass++)
-                for (int q = 0; q < S; q++)
-                    if (job[(size_t)q] < 0 && (busy[(size_t)(q / lane_rows)] > 0) == (pass == 0)) fq.push_back(q);
-            return fq;
-        };
-        GTEN_HIP_OK(gten_hip_select_stream(0));
-        for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_slot_park(dec_, q));
-        // Whatever way this function is left (a failed check ends the process, but an allocation may throw), every slot goes back
-        // to its own sequence's caches: a decoder left bound to spare or foreign sets would read and write the wrong rows in the
-        // decode_step / generate that follows -- and dangle once share_weights() drops the spares.
-        // (while the queue runs, cache sets are bound to slots by the scheduler and carry their "shares P rows" marks with them; the
-        //  slots go back to their own sets afterwards, so no mark outlives the queue -- however this function is left)
-        struct ServeMarks {
-            TinyLlamaBatch* b;
-            explicit ServeMarks(TinyLlamaBatch* b_) : b{b_} { b->in_serve_ = true; }
-            ~ServeMarks()
-            {
-                b->in_serve_ = false;
-                // (a SESSION's set keeps its mark between queues: its rows stay what they are until a turn writes them -- rows >= ctx
-                //  only, extend_group drops the mark where ctx lies inside the prefix -- and a prefix that is replaced or cleared
-                //  takes every mark that speaks of it along, forget_prefix_marks)
-                std::fill(b->set_share_.begin(), b->set_share_.begin() + (long)std::min(b->set_share_.size(), (size_t)b->sess_base()), 0);
-            }
-        } serve_marks{this};
-        struct Rebind {
-            TinyLlamaBatch* b; int S; bool done = false;
-            void run()
-            {
-                if (done) return;
-                done = true;
-                gten_hip_select_stream(0);
-                for (int q = 0; q < S; q++) {
-                    gten_hip_decoder_slot_park(b->dec_, q);
-                    gten_hip_decoder_slot_bind(b->dec_, q, b->set_kv(q));
-                }
-            }
-            ~Rebind() { run(); }
-        } rebind{this, S};
-        // GROUP RECORDS.  One Group per prompt pass whose sets carry a mark: the members that are ready or live, the decoder's
-        // record they read from (-1: none yet, or none was free) and the prompt's rows.  The mark travels with the cache set
-        // (set_group), as share_mark does; the first member that starts takes a free record and snapshots ITS set's rows into it
-        // (the rows are the truth: every member's set holds the same ones), every member then promises its own rows equal it.
-        // When the last member has ended the record is released and goes back to the free list.  No mark and no record outlives
-        // the call, however it is left.
-        struct Group { int members = 0, rec = -1, rows = 0; bool counted = false; };
-        struct GroupRecords {
-            TinyLlamaBatch* b;
-            std::vector<Group> groups;
-            std::vector<int> set_group;                                    // per cache set: its group (-1: no mark)
-            std::vector<int> free_rec;
-            explicit GroupRecords(TinyLlamaBatch* b_) : b{b_}, set_group((size_t)b_->index_space(), -1)
-            {
-                const detail::GroupsDecode& h = detail::groups_decode();
-                const int cap = (h.set && h.share) ? (b->groups_cap_ < 0 ? kGroupsCapDefault : std::min(b->groups_cap_, kGroupsMax)) : 0;
-                for (int g = cap - 1; g >= 0; g--) free_rec.push_back(g);
-            }
-            void mark(int c, int gi) { set_group[(size_t)c] = gi; }
-            // slot q was started on set c (kv: its caches): true when it now reads the prompt's chunks from its group's record
-            bool start(int q, int c, const gten_hip_kv_ptrs* kv)
-            {
-                const int gi = set_group[(size_t)c];
-                if (gi < 0) return false;
-                Group& g = groups[(size_t)gi];
-                if (g.rec < 0 && !free_rec.empty()) {
-                    g.rec = free_rec.back();
-                    free_rec.pop_back();
-                    GTEN_HIP_OK(detail::groups_decode().set(b->dec_, g.rec, kv, g.rows));
-                    b->group_records_now_++;
-                    if (!g.counted) b->groups_recorded_++;
-                    g.counted = true;
-                }
-                if (g.rec < 0) {
-                    if (!g.counted) b->groups_unrecorded_++;
-                    g.counted = true;
-                    return false;
-                }
-                (void)detail::groups_decode().share(b->dec_, q, g.rec, g.rows);      // (refused, or switched off: the slot decodes on its own copy)
-                return true;
-            }
-            void release(Group& g)
-            {
-                if (g.rec < 0) return;
-                detail::groups_decode().set(b->dec_, g.rec, nullptr, 0);
-                free_rec.push_back(g.rec);
-                g.rec = -1;
-                b->group_records_now_--;
-            }
-            // the member on set c has ended: the set's mark goes, and with the last member the record
-            void leave(int c)
-            {
-                const int gi = set_group[(size_t)c];
-                if (gi < 0) return;
-                set_group[(size_t)c] = -1;
-                Group& g = groups[(size_t)gi];
-                if (--g.members <= 0) release(g);
-            }
-            ~GroupRecords() { for (Group& g : groups) release(g); }
-        } group_records{this};
-        // the next prompt of the queue onto a free cache set (stream 1); false when the queue is empty
-        auto prepare = [&]() {
-            while (next < prompts.size() && (session[(int)next] >= 0 || !pool.empty())) {
-                const int j = (int)next++;
-                const bool sess = session[j] >= 0;
-                std::vector<int32_t>& row = (*out)[(size_t)j];
-                row = prompts[(size_t)j];
-                const int P = (int)row.size();
-                GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
-                st.prompt_tokens += P;
-                const int mn = max_new[j];
-                const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);   // ids in all
-                if (P >= limit) continue;                                  // no room to generate: returned as is
-                const auto t0 = clock::now();
-                // (a session item on this path -- a conversation under 16 ids, a narrow batch -- is processed whole onto its own set)
-                const int c = sess ? sess_base() + session[j] : pool.back();
-                if (sess) { sess_turns_++; sess_rows_computed_ += (unsigned long long)P; }
-                const int best_i = pick.first(*this, c, row, j);           // this set's caches now hold rows [0, P) (waits for stream 1 only)
-                st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
-                st.admissions++;
-                if (best_i == eos) { session_done(j); continue; }          // ended at once: the set takes the next prompt
-                row.push_back(best_i);
-                st.new_tokens++;
-                if constexpr (Pick::kFsm)
-                    if (pick.ended_first(j)) { session_done(j); continue; }   // its first id entered a final state: kept, and the set stays free
-                if ((int)row.size() >= limit) { session_done(j); continue; }
-                if (!sess) pool.pop_back();
-                ready.push_back(Ready{j, c, (int)row.size(), limit - 1});
-                return true;
-            }
-            return next < prompts.size();
-        };
-        // Wide batches: the next prompts of the queue -- as many as there are free cache sets, kPreMax at most, kPreRows rows in
-        // all, `cap` when the schedule is fixed -- as ONE row matrix (prefill_many) on stream 1.  Prompts under 16 ids (and
-        // configurations the segmented call does not compute) go one by one through prepare().
-        const bool batched = batched_prompts();
-        int copies_taken = 0;                                              // items that were copies: a fixed schedule counts prompt passes
-        auto prepare_many = [&](int cap) -> bool {
-            if (pool.empty() && !(next < prompts.size() && session[(int)next] >= 0)) return next < prompts.size();
-            // (ITEMS: as many as there are free sets; COMPUTED prompts: kPreMax -- `cap` under a fixed schedule -- and kPreRows rows.
-            //  A group's copies cost neither; without sample groups every item is computed and the bounds are the former ones)
-            const size_t room = pool.size();
-            const int max_computed = std::min(kPreMax, cap > 0 ? cap : kPreMax);
-            std::vector<int> js, limits, copy_of, ctx_of;
-            int rows = 0, computed = 0, continued = 0;
-            size_t plain = 0;                                                // items that take a set out of the pool
-            int lead_k = -1, lead_group = -1;                                // this call's computed member of the group being taken
-            while (next < prompts.size()) {
-                const int j = (int)next;
-                const bool sess = session[j] >= 0;
-                if (!sess && plain == room) break;                           // (a session item needs no free set)
-                const int P = (int)prompts[(size_t)j].size();
-                GTEN_ASSERTM(P >= 1 && P <= n_ctx_, "serve: prompt %d has %d ids (context %d)", j, P, n_ctx_);
-                if (!batched || P < 16) break;                               // (short prompt: one by one below)
-                const int gid = sess ? -1 : group_of[j];
-                const bool copy = gid >= 0 && gid == lead_group && lead_k >= 0;
-                // a session item: the rows its plan keeps stay, the others are a continued segment (filled up to 16 rows); where
-                // the plan keeps nothing -- a first turn -- or the segment would end past the RoPE table it is a whole prompt
-                int ctx = 0, seg_rows = 0;
-                if (sess && continued_prompts()) {
-                    const Session& ss = sessions_[(size_t)session[j]];
-                    SessionPlan pl;
-                    if (session_plan((int)ss.ids.size(), ss.rows, P - (int)ss.ids.size(), true, &pl) && pl.path == kSessionContinued &&
-                        pl.ctx + pl.seg_rows <= kMaxPos) { ctx = pl.ctx; seg_rows = pl.seg_rows; }
-                }
-                const int cost = copy ? 0 : ctx > 0 ? seg_rows : computed_rows(prompts[(size_t)j]);   // (a prompt behind the shared prefix: its own rows only)
-                if (!copy && (rows + cost > kPreRows || computed == max_computed)) break;
-                next++;
-                (*out)[(size_t)j] = prompts[(size_t)j];
-                st.prompt_tokens += P;
-                const int mn = max_new[j];
-                const int limit = std::min(std::min(max_tokens, n_ctx_), mn > 0 ? P + mn : n_ctx_);
-                if (P >= limit) continue;                                    // no room to generate: returned as is (a session stays as it is)
-                if (!copy) { lead_group = gid; lead_k = (int)js.size(); computed++; }
-                js.push_back(j); limits.push_back(limit); rows += cost; copy_of.push_back(copy ? lead_k : -1); ctx_of.push_back(ctx);
-                if (!sess) plain++;
-                if (sess) { sess_turns_++; sess_rows_computed_ += (unsigned long long)(P - ctx); sess_rows_kept_ += (unsigned long long)ctx; }
-                if (ctx > 0) { continued++; sess_turns_continued_++; }
-            }
-            if (js.empty()) {
-                if (next >= prompts.size()) return false;
-                const int P = (int)prompts[next].size();
-                if (batched && P >= 16 && P <= kPreRows) return true;        // (only prompts without room were taken: look again)
-                return prepare();
-            }
-            copies_taken += (int)js.size() - computed;
-            const auto t0 = clock::now();
-            std::vector<int> sets, first;
-            for (size_t k = 0, taken = 0; k < js.size(); k++)               // (plain items: the order the sets would be popped in)
-                sets.push_back(session[js[k]] >= 0 ? sess_base() + session[js[k]] : pool[pool.size() - 1 - taken++]);
-            std::vector<const std::vector<int32_t>*> ps;
-            for (int j : js) ps.push_back(&prompts[(size_t)j]);
-            if (continued) pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr, &ctx_of);
-            else pick.many(*this, sets, ps, js, &first, computed < (int)js.size() ? &copy_of : nullptr);
-            st.prefill_s += std::chrono::duration<double>(clock::now() - t0).count();
-            std::vector<int> unused;
-            std::vector<int> readied(js.size(), 0);                          // per computed item: the readied members of its prompt pass
-            for (size_t k = 0; k < js.size(); k++) {
-                std::vector<int32_t>& row = (*out)[(size_t)js[k]];
-                st.admissions++;
-                bool taken = false;
-                if (first[k] != eos) {                                       // (eos: ended at once, the set stays free)
-                    row.push_back(first[k]);
-                    st.new_tokens++;
-                    bool ended = false;
-                    if constexpr (Pick::kFsm) ended = pick.ended_first(js[k]);
-                    if (!ended && (int)row.size() < limits[k]) { ready.push_back(Ready{js[k], sets[k], (int)row.size(), limits[k] - 1}); taken = true; }
-                }
-                if (!taken) { if (session[js[k]] >= 0) session_done(js[k]); else unused.push_back(sets[k]); }
-                else readied[copy_of[k] < 0 ? k : (size_t)copy_of[k]]++;
-            }
-            // the group mark: at least two readied members behind a prompt of at least one full chunk
-            for (size_t k = 0; k < js.size(); k++) {
-                if (copy_of[k] >= 0 || readied[k] < 2 || (int)ps[k]->size() < kGroupMinRows) continue;
-                const int gi = (int)group_records.groups.size();
-                Group g;
-                g.members = readied[k];
-                g.rows = (int)ps[k]->size();
-                group_records.groups.push_back(g);
-                for (size_t m = k; m < js.size(); m++) {
-                    if (m != k && copy_of[m] != (int)k) continue;
-                    for (const Ready& r : ready)
-                        if (r.j == js[m]) group_records.mark(r.set, gi);     // (readied members only: the others' sets stay free)
-                }
-            }
-            pool.resize(pool.size() - plain);
-            for (size_t k = unused.size(); k-- > 0;) pool.push_back(unused[k]);
-            return true;
-        };
-        int cnt = 0;                                                       // steps of the slice in flight (0: none)
-        bool queue_left = true;
-        bool tail = false;                                                 // the queue is empty: the last sequences are kept in as few lanes as they fit
-        auto t_slice = clock::now();
-        std::vector<int> ap_seq, ap_first, ap_last;                        // gten_hip_decoder_slots_apply's arguments
-        std::vector<const int32_t*> ap_tok;
-        // ready prompts take the free slots, then the next slice starts (stream 0, asynchronous)
-        auto launch_slice = [&]() {
-            // THE TAIL.  Once the queue is empty and nothing waits, the live sequences thin out in every lane alike, and a lane
-            // costs a full lane's launches however few of its slots are live.  Whenever they would fit into fewer lanes than they
-            // occupy, the sequences of the emptiest lane move: parked here, handed over as ready prompts (their cache sets go
-            // with them), started again in the free slots of the lanes that stay -- and the runs of the tail leave empty lanes
-            // out (gten_hip_decoder_run_lanes).  Same rows, same ids: a sequence does not know its slot.
-            if (n_lanes > 1 && serve_schedule_ == 0 && !queue_left && ready.empty() && n_live > 0) {
-                std::vector<int> per((size_t)n_lanes, 0);
-                for (int q = 0; q < S; q++) per[(size_t)(q / lane_rows)] += live[(size_t)q] ? 1 : 0;
-                int occupied = 0, emptiest = -1;
-                for (int g = 0; g < n_lanes; g++)
-                    if (per[(size_t)g] > 0) { occupied++; if (emptiest < 0 || per[(size_t)g] < per[(size_t)emptiest]) emptiest = g; }
-                if (occupied > (n_live + lane_rows - 1) / lane_rows) {
-                    ap_seq.clear(); ap_first.clear(); ap_last.clear();
-                    for (int q = emptiest * lane_rows; q < (emptiest + 1) * lane_rows; q++) {
-                        if (!live[(size_t)q]) continue;
-                        if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], cur[(size_t)q] - lp_from[(size_t)q]);
-                        ready.push_back(Ready{job[(size_t)q], set_of[(size_t)q], cur[(size_t)q], last[(size_t)q]});
-                        ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);
-                        set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
-                    }
-                    GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), nullptr));
-                    st.moved += (int64_t)ap_seq.size();
-                }
-                tail = true;
-            }
-            ap_seq.clear(); ap_first.clear(); ap_last.clear(); ap_tok.clear();
-            if (!ready.empty()) {
-                const std::vector<int> fq = free_slots();
-                // (the caches of the joining slots were filled on stream 1: the host has waited for that, and the explicit
-                //  stream-to-stream dependency makes the next launch on stream 0 acquire what another queue has written)
-                if (!fq.empty()) GTEN_HIP_OK(gten_hip_stream_wait(0, 1));
-                for (size_t i = 0; i < fq.size() && !ready.empty(); i++) {
-                    const int q = fq[i];
-                    const Ready r = ready.front();
-                    ready.pop_front();
-                    const std::vector<int32_t>& row = (*out)[(size_t)r.j];
-                    GTEN_ASSERTM((int)row.size() == r.cur, "serve: prompt %d holds %zu ids at step %d", r.j, row.size(), r.cur);
-                    GTEN_HIP_OK(gten_hip_decoder_slot_bind(dec_, q, set_kv(r.set)));
-                    set_of[(size_t)q] = r.set; job[(size_t)q] = r.j; cur[(size_t)q] = r.cur; last[(size_t)q] = r.last;
-                    // (all joining slots in one call below: their ids, step words and cache-table rows go up behind each other, one wait)
-                    ap_seq.push_back(q); ap_first.push_back(r.cur); ap_last.push_back(r.last); ap_tok.push_back(row.data());
-                    pick.apply(q, r.j, (int)prompts[(size_t)r.j].size());                                  // (travels with the prompt: also when a sequence moves in the tail)
-                    if constexpr (Pick::kFsm) pick.bind_state(q, r.j, r.cur);                              // (... at its current position, with the state the host read)
-                    lp_from[(size_t)q] = r.cur;
-                    live[(size_t)q] = 1; n_live++;
-                }
-            }
-            if (!ap_seq.empty())
-                GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), ap_tok.data()));
-            // the joining slots whose sets begin with the shared prefix's rows read them from the decoder's one copy
-            // (a group mark wins over a prefix mark on the same set: the whole prompt covers at least as many chunks; also set again
-            //  for a sequence that moved in the tail)
-            for (const int q : ap_seq) {
-                if (group_records.start(q, set_of[(size_t)q], set_kv(set_of[(size_t)q]))) continue;
-                if (const int P = share_mark(set_of[(size_t)q]); P > 0) (void)decoder_share(q, which_mark(set_of[(size_t)q]), P);     // (refused: the slot decodes on its own copy, as in prefill_group)
-            }
-            if (n_live == 0) return;
-            // (a slot whose run ends inside the slice repeats its last step until the slice is over, slot_start_until: the slice
-            //  is cut only when EVERY live slot ends earlier)
-            int longest = 0;
-            for (int q = 0; q < S; q++)
-                if (live[(size_t)q]) longest = std::max(longest, last[(size_t)q] - cur[(size_t)q] + 1);
-            cnt = std::min(std::max(slice, 1), longest);
-            t_slice = clock::now();
-            GTEN_HIP_OK(gten_hip_decoder_run_lanes(dec_, cnt, tail ? 1 : 0));
-            st.steps += cnt;
-            int ran = n_lanes;
-            GTEN_HIP_OK(gten_hip_decoder_lane_info(dec_, nullptr, nullptr, &ran));
-            st.lane_steps += (int64_t)cnt * ran;
-        };
-        // the ids of the finished slice; slots that ended are parked (their cache sets are free for the next prompts)
-        std::vector<int> from((size_t)S, 0);
-        std::vector<int32_t> all_ids((size_t)S * (size_t)std::max(slice, 1));
-        auto harvest = [&]() {
-            // every live slot's ids of the slice in ONE gather + copy (waits for stream 0)
-            for (int q = 0; q < S; q++) from[(size_t)q] = live[(size_t)q] ? cur[(size_t)q] : 0;
-            GTEN_HIP_OK(gten_hip_decoder_slot_ids_all(dec_, from.data(), cnt, all_ids.data()));
-            ap_seq.clear(); ap_first.clear(); ap_last.clear();
-            for (int q = 0; q < S; q++) {
-                if (!live[(size_t)q]) continue;
-                const int got = std::min(cnt, last[(size_t)q] - cur[(size_t)q] + 1);                  // (its steps of this slice)
-                const int32_t* ids = all_ids.data() + (size_t)q * (size_t)cnt;
-                std::vector<int32_t>& row = (*out)[(size_t)job[(size_t)q]];
-                bool stop = false;
-                const int32_t* entered = nullptr;                                                      // (Pick::kFsm) the state each id entered
-                if constexpr (Pick::kFsm) entered = pick.states(q, job[(size_t)q], cur[(size_t)q], got);
-                for (int i = 0; i < got && !stop; i++) {
-                    if (ids[(size_t)i] == eos) stop = true;
-                    else {
-                        row.push_back(ids[(size_t)i]); st.new_tokens++;
-                        if constexpr (Pick::kFsm)
-                            if (entered && pick.enters_final(job[(size_t)q], entered[(size_t)i])) stop = true;
-                    }
-                }
-                cur[(size_t)q] += got;
-                if (stop || cur[(size_t)q] > last[(size_t)q]) {
-                    // (the records of the ids kept: an eos and what follows it are not stored)
-                    if constexpr (Pick::kLogprobs) pick.collect(q, job[(size_t)q], lp_from[(size_t)q], (int)row.size() - lp_from[(size_t)q]);
-                    ap_seq.push_back(q); ap_first.push_back(0); ap_last.push_back(0);                  // parked, all of them at once below
-                    group_records.leave(set_of[(size_t)q]);                                            // (its group's last member: the record goes back)
-                    if (set_of[(size_t)q] >= sess_base()) session_done(job[(size_t)q]);                  // (a session keeps its set)
-                    else pool.push_back(set_of[(size_t)q]);
-                    set_of[(size_t)q] = -1; job[(size_t)q] = -1; live[(size_t)q] = 0; n_live--;
-                }
-            }
-            if (!ap_seq.empty()) GTEN_HIP_OK(gten_hip_decoder_slots_apply(dec_, (int)ap_seq.size(), ap_seq.data(), ap_first.data(), ap_last.data(), nullptr));
-            st.decode_s += std::chrono::duration<double>(clock::now() - t_slice).count();
-            cnt = 0;
-            GTEN_HIP_OK(gten_hip_stream_wait(1, 0));            // (... and the other way round for the cache sets the parked slots leave)
-        };
-        // One host thread: prompts are processed back to back on stream 1; between two prompt calls the slice on stream 0 is
-        // polled, and when it has finished its ids are read and the next slice (with the prompts that became ready) starts.
-        int prepared_this_slice = 0;
-        for (;;) {
-            if (cnt > 0) {
-                int idle = 0;
-                if (serve_schedule_ > 0) idle = prepared_this_slice >= serve_schedule_;   // fixed schedule (tests): k prompts per slice
-                else GTEN_HIP_OK(gten_hip_stream_idle(0, &idle));
-                // (a session item at the head of the queue needs no free set: it is prepared beside the slice even when every set
-                //  is taken.  The other way round, while any set is free prepare_many may take session items far ahead of the slots
-                //  that will run them -- they wait in `ready` on their own sets and hold nothing a plain prompt could use)
-                const bool head_is_session = next < prompts.size() && session[(int)next] >= 0;
-                if (!idle && queue_left && (!pool.empty() || head_is_session)) {   // slice still running: more prompts beside it
-                    GTEN_HIP_OK(gten_hip_select_stream(1));
-                    const int before = (int)st.admissions - copies_taken;
-                    queue_left = batched ? prepare_many(serve_schedule_ > 0 ? serve_schedule_ - prepared_this_slice : 0) : prepare();
-                    GTEN_HIP_OK(gten_hip_select_stream(0));
-                    prepared_this_slice += batched ? std::max(1, (int)st.admissions - copies_taken - before) : 1;
-                    continue;
-                }
-                harvest();                                                  // (waits when nothing is left to prepare)
-                prepared_this_slice = 0;
-            }
-            if (n_live == 0 && ready.empty()) {                             // nothing to decode: a prompt first
-                if (!queue_left || pool.empty()) break;                     // queue empty, nothing in flight
-                GTEN_HIP_OK(gten_hip_select_stream(1));
-                queue_left = batched ? prepare_many(serve_schedule_) : prepare();
-                // (with nothing live there is nothing to run beside: prompts are processed -- at the prompt kernels' full rate --
-                //  until serve_ramp_ percent of the slots have one, and only then does the first slice start: 669 instead of 709
-                //  shared steps on the bench's queue, its first 256 prompts 31.3 k instead of 28.6 k new ids/s; the price is the
-                //  first ids' latency, ~0.4 s at full size.  0: the first slice starts with the first batch of prompts)
-                while (serve_schedule_ == 0 && batched && queue_left && !pool.empty() && (int)ready.size() * 100 < S * serve_ramp_)
-                    queue_left = prepare_many(0);
-                GTEN_HIP_OK(gten_hip_select_stream(0));
-                if (ready.empty()) { if (!queue_left) break; continue; }
-            }
-            launch_slice();
-        }
-        // every slot back on its own sequence's caches (all of them are parked now): what follows a serve() -- decode_step,
-        // generate -- addresses slot q as sequence q
-        for (int q = 0; q < S; q++) GTEN_HIP_OK(gten_hip_decoder_slot_bind(dec_, q, set_kv(q)));
-        rebind.done = true;
-        pick.clear();                                                      // every slot greedy again, unbound, and nobody asks
-        return st;
+        ServeQueue<Pick> queue(*this, prompts, max_tokens, eos, slice, out, max_new, group_of, pick, session);
+        return queue.run();
     }
 
     // Cache sets beyond the sequences' own that serve() fills ahead (-1: a quarter of the slots, at most 64, for wide batches; 0:
@@ -1997,3 +1545,5 @@ inline int greedy_sample(TinyLlama& model, std::vector<int32_t>& tokens, const i
 }
 
 } // namespace gten
+
+#include "serve.h"                       // ServeQueue, which serve_with instantiates
