@@ -266,7 +266,9 @@ struct gten_hip_decoder {
     int lanes = 1;
     hipStream_t lane_stream[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};    // capture / eager side streams of lanes 1..
     hipEvent_t lane_fork = nullptr, lane_join[DEC_MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    struct BeamSearch* beam = nullptr;  // a beam search between begin and end (gten_decode_beam.h); made by the first begin
 };
+static hipError_t beam_destroy(gten_hip_decoder* dc);
 
 // the step ends in the sampler launch (not in k_dec_argmax) once a sequence samples, has a bias table, asks for log-probs or is penalised
 static inline bool sampler_on(const gten_hip_decoder* dc) { return dc->smp.n_sampling + dc->smp.n_bound + dc->smp.n_asking + dc->smp.n_penalised + dc->smp.n_fsm > 0; }
@@ -1774,6 +1776,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     for (gten_hip_decoder::Pfx& x : dc->pfx)
         for (void* b : {(void*)x.hm, (void*)x.tab, (void*)x.step}) if (b) rel(hipFree(b));
     rel(persist_free(dc));
+    rel(beam_destroy(dc));
     for (int g = 1; g < DEC_MAX_LANES; g++) {
         if (dc->lane_stream[g]) { rel(hipStreamSynchronize(dc->lane_stream[g])); rel(hipStreamDestroy(dc->lane_stream[g])); }
         if (dc->lane_join[g]) rel(hipEventDestroy(dc->lane_join[g]));
@@ -2804,3 +2807,6 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
 
 // byte automata expanded over the vocabulary into the pool, and the pool's check on the device (include/gten_hip_regex.h)
 #include "gten_fsm_expand.h"
+
+// beam search: the round, the in-place gather of the beams' K / V rows and their decoder form (include/gten_hip_beam.h)
+#include "gten_decode_beam.h"

@@ -132,6 +132,10 @@ class GtenHip:
                         "gten_hip_decoder_prefixes_info"]                  # include/gten_hip_prefixes.h
     GROUPS_SYMBOLS = ["gten_hip_decoder_group_set", "gten_hip_decoder_group_share",
                       "gten_hip_decoder_groups_info"]                      # include/gten_hip_groups.h
+    # include/gten_hip_beam.h (beam search: the round, the in-place gather of the beams' K / V rows, their decoder form)
+    BEAM_SYMBOLS = ["gten_hip_beam_round", "gten_hip_permute_sets", "gten_hip_decoder_beam_begin", "gten_hip_decoder_beam_round",
+                    "gten_hip_decoder_beam_live", "gten_hip_decoder_beam_read", "gten_hip_decoder_beam_end", "gten_hip_decoder_beam_info"]
+    BEAM_MAX = 8                                                 # GTEN_HIP_BEAM_MAX
     GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -225,6 +229,14 @@ class GtenHip:
                                                                          vp, vp, vp, vp, vp, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
+        self._beam_round = _sig(L, "gten_hip_beam_round", ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, vp, ci, vp])
+        self._permute_sets = _sig(L, "gten_hip_permute_sets", ci, [vp, ci, sz, sz, vp, ci, vp, vp, ci])
+        self._beam_begin = _sig(L, "gten_hip_decoder_beam_begin", ci, [vp, vp, ci, vp, ci])
+        self._dec_beam_round = _sig(L, "gten_hip_decoder_beam_round", ci, [vp])
+        self._beam_live = _sig(L, "gten_hip_decoder_beam_live", ci, [vp, C.POINTER(ci)])
+        self._beam_read = _sig(L, "gten_hip_decoder_beam_read", ci, [vp, ci, vp, vp, vp])
+        self._beam_end = _sig(L, "gten_hip_decoder_beam_end", ci, [vp])
+        self._beam_info = _sig(L, "gten_hip_decoder_beam_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self.initialised = False
 
     # -- runtime
@@ -631,6 +643,64 @@ class GtenHip:
         out = DeviceBuffer(self, 4)
         self._check(self._argmax_row(logits.ptr + offset, n, out.ptr))
         return int(out.download(np.int32)[0])
+
+    # -- beam search (include/gten_hip_beam.h).  BEAM_GROUP: one gten_hip_beam_group; BEAM_STATE: one gten_hip_beam_state (176 bytes)
+    BEAM_GROUP = np.dtype([("row0", np.int32), ("n_beams", np.int32), ("prompt_len", np.int32), ("max_new", np.int32), ("eos", np.int32)])
+    BEAM_STATE = np.dtype([("cum", np.float32, 8), ("fin_final", np.float32, 8), ("fin_cum", np.float32, 8), ("fin_t", np.int32, 8),
+                           ("fin_beam", np.int32, 8), ("n_fin", np.int32), ("done", np.int32), ("t", np.int32), ("stepped", np.int32)])
+
+    def beam_round(self, groups, state, top_id, top_lp, row_stride, w, n_w, parent, ids, trellis_rows, next_id):
+        """gten_hip_beam_round on DeviceBuffers (groups: BEAM_GROUP records, state: BEAM_STATE records, in place); asynchronous"""
+        self._check(self._beam_round(groups.ptr, groups.nbytes // self.BEAM_GROUP.itemsize, state.ptr, top_id.ptr, top_lp.ptr, int(row_stride), w.ptr,
+                                     int(n_w), parent.ptr, ids.ptr, int(trellis_rows), next_id.ptr))
+
+    def permute_sets_rc(self, ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows=1):
+        """gten_hip_permute_sets: ranges = [(group, [base address of set 0, 1, ...])] (host), groups / state / parent device addresses
+        (state 0 or None: parent is [n_groups][8]); the return code"""
+        rec = np.zeros(len(ranges), np.dtype([("base", np.uint64, 8), ("group", np.int32), ("pad", np.int32)]))
+        for i, (g, bases) in enumerate(ranges):
+            rec["group"][i] = g
+            rec["base"][i, : len(bases)] = bases
+        return self._permute_sets(rec.ctypes.data_as(C.c_void_p), len(ranges), int(offset), int(nbytes), int(groups), int(n_groups),
+                                  int(state) if state else None, int(parent), int(trellis_rows))
+
+    def permute_sets(self, ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows=1):
+        self._check(self.permute_sets_rc(ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows))
+
+    def decoder_beam_begin(self, dec, groups, w):
+        """gten_hip_decoder_beam_begin on a raw decoder handle: groups = [(first_seq, n_beams, prompt_len, max_new, eos)], w the f32
+        length weights; the return code (0, or a refusal: last_error())"""
+        g = np.array([tuple(int(v) for v in x) for x in groups], dtype=self.BEAM_GROUP)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        return self._beam_begin(dec, g.ctypes.data_as(C.c_void_p), len(g), w.ctypes.data_as(C.c_void_p), len(w))
+
+    def decoder_beam_round(self, dec):
+        self._check(self._dec_beam_round(dec))
+
+    def decoder_beam_live(self, dec):
+        n = C.c_int(-1)
+        self._check(self._beam_live(dec, C.byref(n)))
+        return n.value
+
+    def decoder_beam_read(self, dec, g, max_new):
+        """(state as a BEAM_STATE record, parent int32[t][8], ids int32[t][8]) of group g"""
+        st = np.zeros(1, self.BEAM_STATE)
+        par, ids = np.zeros((max_new, 8), np.int32), np.zeros((max_new, 8), np.int32)
+        self._check(self._beam_read(dec, int(g), st.ctypes.data_as(C.c_void_p), par.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p)))
+        t = int(st["t"][0])
+        return st[0], par[:t].copy(), ids[:t].copy()
+
+    def decoder_beam_end(self, dec):
+        return self._beam_end(dec)
+
+    def decoder_beam_info(self, dec):
+        """(rounds since begin, bytes the last gather launch covered, gather launches so far)"""
+        r, b, n = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._beam_info(dec, C.byref(r), C.byref(b), C.byref(n)))
+        return r.value, b.value, n.value
+
+    def last_error(self):
+        return self._err().decode(errors="replace")
 
     def set_decode_exact(self, on):
         """exact forms of the decode step for decoders created from now on (include/gten_hip.h)"""

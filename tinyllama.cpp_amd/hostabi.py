@@ -88,6 +88,10 @@ class GtenHost:
                         "gten_host_batch_session_open", "gten_host_batch_session_close", "gten_host_batch_session_info", "gten_host_batch_session_ids",
                         "gten_host_batch_session_truncate", "gten_host_batch_sessions_info", "gten_host_batch_serve_sessions"]
     SESSIONS_MAX = 256                                           # GTEN_HOST_SESSIONS_MAX
+    # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
+    BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
+    BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
+    BEAM_ENDED = ("eos", "length")                               # GTEN_HOST_BEAM_ENDED_*
     SAMPLES_MAX = 64                                             # GTEN_HOST_SAMPLES_MAX
 
     def __init__(self, path=None):
@@ -251,6 +255,10 @@ class GtenHost:
         self._bextend_many = _sig(L, "gten_host_batch_extend_many", ci, [vp, vp, vp, vp, vp, ci, vp, vp])
         self._bextend_info = _sig(L, "gten_host_batch_extend_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull), C.POINTER(ull)])
         self._session_plan = _sig(L, "gten_host_session_plan", ci, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)])
+        self._bbeam = _sig(L, "gten_host_batch_beam_search", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, vp, vp, vp, vp, vp, vp, C.POINTER(ci)])
+        self._beam_weights = _sig(L, "gten_host_beam_weights", ci, [ci, C.c_float, vp])
+        self._beam_backtrack = _sig(L, "gten_host_beam_backtrack", ci, [vp, vp, ci, ci, ci, vp])
+        self._beam_finalize = _sig(L, "gten_host_beam_finalize", ci, [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp])
         self._bgdset = _sig(L, "gten_host_batch_group_decode_set", ci, [vp, ci, ci, ci])
         self._bgdshare = _sig(L, "gten_host_batch_group_decode_share", ci, [vp, ci, ci, ci])
         self._bgdinfo = _sig(L, "gten_host_batch_groups_decode_info", ci, [vp, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ull), C.POINTER(ci)])
@@ -317,6 +325,34 @@ class GtenHost:
         prompt = np.ascontiguousarray(prompt, dtype=np.int32)
         return self._psmatch(flat.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), len(prefixes), max(max_len, 1),
                              prompt.ctypes.data_as(C.c_void_p), len(prompt))
+
+    # -- beam search's plan (host/beam_plan.h): no device needed
+    def beam_weights(self, max_new, length_penalty):
+        """f32[max_new + 1]: w[0] = 0, w[t] = (float)(1 / t^length_penalty)"""
+        w = np.zeros(max_new + 1, np.float32)
+        if self._beam_weights(int(max_new), float(length_penalty), _ptr(w)):
+            raise GtenHipError("beam_weights: bad arguments")
+        return w
+
+    def beam_backtrack(self, parent, ids, t, b):
+        """the ids of beam b after round t; parent / ids int32[rows][8], round r at row r - 1.  None where the walk leaves the trellis"""
+        parent, ids = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1, 8), np.ascontiguousarray(ids, dtype=np.int32).reshape(-1, 8)
+        out = np.zeros(max(int(t), 1), np.int32)
+        n = self._beam_backtrack(_ptr(parent), _ptr(ids), len(parent), int(t), int(b), _ptr(out))
+        return None if n < 0 else out[:n].copy()
+
+    def beam_finalize(self, state, parent, ids, n_beams, w, max_new):
+        """state: one 176-byte record (hipabi.GtenHip.BEAM_STATE); returns [(ids, final, cum, ended_by)], best first"""
+        parent, ids = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1, 8), np.ascontiguousarray(ids, dtype=np.int32).reshape(-1, 8)
+        st = np.frombuffer(np.asarray(state).tobytes(), np.uint8).copy()
+        assert st.size == 176
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        oi, on = np.zeros((n_beams, max_new), np.int32), np.zeros(n_beams, np.int32)
+        of, oc, oe = np.zeros(n_beams, np.float32), np.zeros(n_beams, np.float32), np.zeros(n_beams, np.int32)
+        n = self._beam_finalize(_ptr(st), _ptr(parent), _ptr(ids), len(parent), int(n_beams), _ptr(w), int(max_new), _ptr(oi), _ptr(on), _ptr(of), _ptr(oc), _ptr(oe))
+        if n < 0:
+            raise GtenHipError("beam_finalize: bad arguments")
+        return [(oi[i, : on[i]].copy(), of[i], oc[i], self.BEAM_ENDED[oe[i]]) for i in range(n)]
 
     def session_plan(self, n_ids, rows, n_new, segmented=True):
         """gten_host_session_plan (include/gten_host_sessions.h): (rows kept, rows computed, path 0 whole / 1 continued / 2 one by
@@ -1344,6 +1380,29 @@ class HostBatch:
     def fsm_decoder(self):
         """the shared decoder's raw handle, for hipabi's decoder_slot_* calls"""
         return self.host._b_fsm_decoder(self.h)
+
+    def beam_search_rc(self, prompts, n_beams, max_new, eos=-1, length_penalty=1.0):
+        """gten_host_batch_beam_search: (return code, hypotheses per prompt or None, rounds run)"""
+        G = len(prompts)
+        starts = np.zeros(G + 1, np.int32)
+        starts[1:] = np.cumsum([len(p) for p in prompts])
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]), dtype=np.int32)
+        nb = max(int(n_beams), 1)
+        oi, on = np.zeros((G, nb, max(max_new, 1)), np.int32), np.zeros((G, nb), np.int32)
+        of, oc, oe = np.zeros((G, nb), np.float32), np.zeros((G, nb), np.float32), np.zeros((G, nb), np.int32)
+        nh, rounds = np.zeros(G, np.int32), C.c_int(0)
+        rc = self.host._bbeam(self.h, _ptr(toks), _ptr(starts), G, int(n_beams), int(max_new), int(eos), float(length_penalty), _ptr(oi), _ptr(on), _ptr(of),
+                              _ptr(oc), _ptr(oe), _ptr(nh), C.byref(rounds))
+        if rc:
+            return rc, None, rounds.value
+        return 0, [[(oi[g, i, : on[g, i]].copy(), of[g, i], oc[g, i], GtenHost.BEAM_ENDED[oe[g, i]]) for i in range(nh[g])] for g in range(G)], rounds.value
+
+    def beam_search(self, prompts, n_beams, max_new, eos=-1, length_penalty=1.0):
+        """beam search (include/gten_host_beam.h): prompt g x n_beams beams on sequences g * n_beams + b.  Per prompt a list of
+        (new ids, final, cum, ended_by 'eos' | 'length'), best first"""
+        rc, out, _ = self.beam_search_rc(prompts, n_beams, max_new, eos, length_penalty)
+        self._ck(rc, "batch_beam_search")
+        return out
 
     def generate_fsm(self, prompts, max_tokens, fsm_start, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, rep=1.0, freq=0.0, pres=0.0, last_n=0,
                      count_prompt=True, top_p=1.0, min_p=0.0, tables=None, min_new=None):
