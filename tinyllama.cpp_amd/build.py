@@ -73,7 +73,8 @@ def build_hip(force=False):
     """one object per .hip file (only stale ones are recompiled, up to 4 at a time), then one link"""
     from concurrent.futures import ThreadPoolExecutor
     srcs = _sources(CSRC, (".hip",))
-    hdrs = _sources(CSRC, (".h",)) + _sources(INCLUDE, (".h",)) + [os.path.abspath(__file__)]
+    # (host/resident_plan.h: the one device-free plan header the decoder itself includes)
+    hdrs = _sources(CSRC, (".h",)) + _sources(INCLUDE, (".h",)) + [os.path.join(HOST, "resident_plan.h"), os.path.abspath(__file__)]
     os.makedirs(HIP_OBJ, exist_ok=True)
     compile_flags = [f for f in HIP_FLAGS if f != "-shared"]
     stamp = " ".join(_EXTRA)

@@ -35,8 +35,10 @@
 #include "gten_hip_prefix_decode.h"
 #include "gten_hip_prefixes.h"
 #include "gten_hip_groups.h"
+#include "../host/resident_plan.h"      // device-free: which W.x launches keep their weights in the memory-side cache
 
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 #include <algorithm>
 
@@ -224,6 +226,12 @@ struct gten_hip_decoder {
     int attn_classic = 0;             // gten_hip_set_decode_attn_classic at creation (0 / 1 / 2)
     bool persist_on = false;          // gten_hip_set_decode_persistent at creation: the step as ONE persistent launch (gten_decode_persist.h)
     struct PersistState* persist = nullptr;
+    // the W.x launches whose weights are requested with the default cache policy (host/resident_plan.h), in step order: per layer
+    // q|k|v, o, gate|up, down, then lm_head.  Computed once at creation from gten_hip_set_weight_resident_mb's value at that time
+    // (captured graphs stay valid); empty unless this is a single-sequence decoder on the fast forms.
+    gten::ResidentPlan resident;
+    long long resident_overhead = 0;  // what came off the setting: this decoder's K / V rows at max_ctx and its scratch, bytes
+    long long resident_budget = 0;    // what was left for the weights
     // ---- head-major shadows of the K / V caches (gten_decode_attn_hm.h): decoders of 16+ sequences, Q8 activations, fast forms.
     // [sequence][layer][K | V][kv head][chunk][HM_CHUNK_BYTES]; hm_dirty[q] != 0: sequence q's shadow must be re-imported from
     // its cache rows before the next step (set at creation, by every (re)start of the sequence, and -- through the watch
@@ -402,6 +410,53 @@ extern "C" int gten_hip_set_decode_attn_classic(int v)
 {
     GTR_REQUIRE(v >= 0 && v <= 2, "gten_hip_set_decode_attn_classic: %d is not 0, 1 or 2", v);
     g_attn_classic = v;
+    return 0;
+}
+
+// The byte budget, in MiB, of everything a single-sequence decoder created AFTERWARDS loads with the default cache policy in a
+// step (include/gten_hip_ab.h): gten_hip_set_weight_resident_mb's value, else the environment's GTEN_HIP_RESIDENT_MB, else the
+// compiled-in default -- chosen by the sweep of DESIGN.md §4 (profiles/resident_sweep.json).  0: every weight request nontemporal.
+// 160: TinyLlama q4 at ctx 2048 holds all of o, all of q|k|v and three layers of down (47 of its 112 launches, 136 MB); the step is
+// at its best from 128 to 192 MiB and falls off past 192 (the cache is 256 MiB), so 160 is the plateau's end less one sweep step.
+#ifndef GTEN_RESIDENT_MB_DEFAULT
+#define GTEN_RESIDENT_MB_DEFAULT 160
+#endif
+static long long g_resident_bytes = -1;  // < 0: not set by a call
+static long long resident_setting_bytes()
+{
+    if (g_resident_bytes >= 0) return g_resident_bytes;
+    if (const char* e = getenv("GTEN_HIP_RESIDENT_MB"); e && e[0]) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 0 && v <= (1 << 20)) return (long long)v << 20;
+    }
+    return (long long)GTEN_RESIDENT_MB_DEFAULT << 20;
+}
+extern "C" int gten_hip_set_weight_resident_mb(int mb)
+{
+    GTR_REQUIRE(mb >= 0 && mb <= (1 << 20), "gten_hip_set_weight_resident_mb: %d MiB is not in [0, 2^20]", mb);
+    g_resident_bytes = (long long)mb << 20;
+    return 0;
+}
+extern "C" int gten_hip_set_weight_resident_bytes(long long bytes)
+{
+    GTR_REQUIRE(bytes >= 0 && bytes <= (1ll << 40), "gten_hip_set_weight_resident_bytes: %lld is not in [0, 2^40]", bytes);
+    g_resident_bytes = bytes;
+    return 0;
+}
+extern "C" long long gten_hip_weight_resident_bytes(void) { return resident_setting_bytes(); }
+extern "C" int gten_hip_decoder_resident(gten_hip_decoder* dc, int* launches, long long* bytes)
+{
+    GTR_REQUIRE(dc, "decoder_resident: null decoder");
+    if (launches) *launches = dc->resident.launches;
+    if (bytes) *bytes = dc->resident.bytes;
+    return 0;
+}
+extern "C" int gten_hip_decoder_resident_budget(gten_hip_decoder* dc, long long* budget, long long* overhead)
+{
+    GTR_REQUIRE(dc, "decoder_resident_budget: null decoder");
+    if (budget) *budget = dc->resident_budget;
+    if (overhead) *overhead = dc->resident_overhead;
     return 0;
 }
 
@@ -667,25 +722,30 @@ static GemvHotWords hot_of_gemv8(const Gemv8Args& a)
     return hw;
 }
 
+// keep: the decoder's plan holds this launch's weights resident -- the WLD_KEEP instantiation, the same kernel with the default
+// cache policy on its weight requests (chosen here, on the host: the kernel takes no argument and no branch for it)
 template <int WT, int PRO, int NCH, int R, int NT, int NM = 0>
-static int launch_gemv8(int tag, const Gemv8Args& a, int total_rows)
+static int launch_gemv8(int tag, const Gemv8Args& a, int total_rows, bool keep)
 {
     const int rows_per_wg = (NT / 64) * R;
     const dim3 grid((total_rows + rows_per_wg - 1) / rows_per_wg), block(NT);
     for (int k = 0; k + 1 < a.n_mats; k++) GTR_REQUIRE(a.rows[k] % R == 0, "decoder: concatenated matrices must hold a multiple of %d rows", R);
     const GemvHotWords hw = hot_of_gemv8<WT, PRO>(a);
-    DEC_LAUNCH_HOT(tag, (k_dec_gemv8<WT, PRO, NCH, R, EPI_RAW, NT, NM>), grid, block, stage_bytes((PRO == PRO_ACTQ8 && WT != GTEN_F16) ? 32 : a.d_in), hw, a);
+    const size_t lds = stage_bytes((PRO == PRO_ACTQ8 && WT != GTEN_F16) ? 32 : a.d_in);
+    if (keep) DEC_LAUNCH_HOT(tag, (k_dec_gemv8<WT, PRO, NCH, R, EPI_RAW, NT, NM, WLD_KEEP>), grid, block, lds, hw, a);
+    else DEC_LAUNCH_HOT(tag, (k_dec_gemv8<WT, PRO, NCH, R, EPI_RAW, NT, NM>), grid, block, lds, hw, a);
     return 0;
 }
 
 // gate + up projections with the silu*up chain in the epilogue: one workgroup per 32-wide FFN slice
 template <int WT>
-static int launch_gateup8(const Gemv8Args& a, int n_ffn)
+static int launch_gateup8(const Gemv8Args& a, int n_ffn, bool keep)
 {
     const dim3 grid(n_ffn / 32), block(512);
     GTR_REQUIRE(n_ffn % 32 == 0, "decoder: n_ffn %d is not a multiple of 32", n_ffn);
     const GemvHotWords hw = hot_of_gemv8<WT, PRO_RESID>(a);
-    DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, (WT == GTEN_F16 ? 4 : 1), 8, EPI_SILUMUL, 512>), grid, block, stage_bytes(a.d_in), hw, a);
+    if (keep) DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, (WT == GTEN_F16 ? 4 : 1), 8, EPI_SILUMUL, 512, 0, WLD_KEEP>), grid, block, stage_bytes(a.d_in), hw, a);
+    else DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, (WT == GTEN_F16 ? 4 : 1), 8, EPI_SILUMUL, 512>), grid, block, stage_bytes(a.d_in), hw, a);
     return 0;
 }
 
@@ -714,18 +774,21 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     float* xbuf = (float*)dc->xbuf;
     float* hbuf = (float*)dc->hbuf;
     int rc;
+    // launch i of the step's W.x launches (per layer q|k|v, o, gate|up, down; then lm_head): resident in the decoder's plan
+    const auto keep = [&](size_t i) { return i < dc->resident.resident.size() && dc->resident.resident[i] != 0; };
     for (int l = 0; l < d.n_layers; l++) {
         const gten_hip_layer_ptrs& L = dc->layers[l];
+        const size_t l4 = (size_t)l * 4;
         Gemv8Args a{};
         a.step = dc->step; a.d_in = E; a.n_mats = 3;
         set_mat(a, 0, L.wq, WT, E, E); set_mat(a, 1, L.wk, WT, KV, E); set_mat(a, 2, L.wv, WT, KV, E);
         a.out = dc->qkv_raw; a.norm_w = (const uint16_t*)L.attn_norm; a.x_out = xbuf;
         if (l == 0) {
             a.table = d.embed; a.rope = dc->rope; a.rope_now = dc->rope_now; a.rope_half = dh / 2; a.n_vocab = d.n_vocab; a.tokens = dc->tokens;
-            rc = launch_gemv8<WT, PRO_EMBED, NE, 2, 512>(KT_DEC_GEMV_QKV, a, E + 2 * KV);
+            rc = launch_gemv8<WT, PRO_EMBED, NE, 2, 512>(KT_DEC_GEMV_QKV, a, E + 2 * KV, keep(l4));
         } else {
             a.res_a = hbuf; a.res_raw = dc->down_raw;
-            rc = launch_gemv8<WT, PRO_RESID, NE, 2, 512>(KT_DEC_GEMV_QKV, a, E + 2 * KV);
+            rc = launch_gemv8<WT, PRO_RESID, NE, 2, 512>(KT_DEC_GEMV_QKV, a, E + 2 * KV, keep(l4));
         }
         if (rc) return rc;
         AttnArgs t{};
@@ -744,28 +807,28 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
         // 256): q|k|v 1 row 0.510, on 256 threads 0.500; o 1 row 0.4845 (3.90 against 4.22 us per launch: every CU gets a workgroup),
         // 4 rows 0.512, 1 row on 256 threads 0.504, 2 rows on 256 threads 0.489; down 1 row 0.494, 1 row on 512 threads 0.496;
         // lm_head 4 / 8 / 16 rows per wave 0.486 / 0.488 / 0.487 (then, with o at 1 row)
-        rc = attention_one_pass(dh) ? launch_gemv8<WT, PRO_ATTW, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E)
-                                    : launch_gemv8<WT, PRO_ATT, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E);
+        rc = attention_one_pass(dh) ? launch_gemv8<WT, PRO_ATTW, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1))
+                                    : launch_gemv8<WT, PRO_ATT, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1));
         if (rc) return rc;
         Gemv8Args gu{};
         gu.step = dc->step; gu.d_in = E; gu.n_mats = 2; set_mat(gu, 0, L.wgate, WT, F, E); set_mat(gu, 1, L.wup, WT, F, E);
         gu.res_a = xbuf; gu.res_raw = dc->proj_raw; gu.x_out = hbuf; gu.norm_w = (const uint16_t*)L.ffn_norm;
         gu.act_q = dc->act_q; gu.act_d = dc->act_d; gu.act_sum = dc->act_sum; gu.act_f = dc->act_f;
-        if ((rc = launch_gateup8<WT>(gu, F))) return rc;
+        if ((rc = launch_gateup8<WT>(gu, F, keep(l4 + 2)))) return rc;
         Gemv8Args dn{};
         dn.step = dc->step; dn.d_in = F; dn.n_mats = 1; set_mat(dn, 0, L.wdown, WT, E, F); dn.out = dc->down_raw;
         dn.act_q = dc->act_q; dn.act_d = dc->act_d; dn.act_sum = dc->act_sum;
         dn.act_f = dc->act_f;
-        rc = widerF ? launch_gemv8<WT, PRO_ACTQ8, NF12, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E)
-             : wideF ? launch_gemv8<WT, PRO_ACTQ8, NF, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E)
-                     : launch_gemv8<WT, PRO_ACTQ8, NE, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E);
+        rc = widerF ? launch_gemv8<WT, PRO_ACTQ8, NF12, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E, keep(l4 + 3))
+             : wideF ? launch_gemv8<WT, PRO_ACTQ8, NF, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E, keep(l4 + 3))
+                     : launch_gemv8<WT, PRO_ACTQ8, NE, 2, 256, 1>(KT_DEC_GEMV_DOWN, dn, E, keep(l4 + 3));
         if (rc) return rc;
     }
     Gemv8Args hd{};
     hd.step = dc->step; hd.d_in = E; hd.n_mats = 1; set_mat(hd, 0, d.lm_head, WT, d.n_vocab, E); hd.out = d.logits;
     hd.res_a = hbuf; hd.res_raw = dc->down_raw; hd.x_out = nullptr; hd.norm_w = (const uint16_t*)d.final_norm;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
-    if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab))) return rc;
+    if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab, keep((size_t)d.n_layers * 4)))) return rc;
     // (one sequence: no strides; the argmax joins lm_head's per-wave winners)
     return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state,
                                        dc->best_val, dc->best_idx, dc->n_best, 0});
@@ -1647,6 +1710,20 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     // the persistent step's state is allocated now: the first step may already be a stream capture
     if (dc->persist_on && n_seq == 1 && !dc->exact)
         if (int rc = persist_prepare(dc)) return rc;
+    // which W.x launches keep their weights resident (host/resident_plan.h): single-sequence decoders on the fast forms only.  The
+    // setting bounds EVERYTHING this decoder loads with the default policy in a step, so its K / V rows at max_ctx and its scratch
+    // (every buffer allocated above, and the logits row) come off it first.
+    {
+        const int block_bytes = d.wdtype == GTEN_F16 ? gten::kResidentBlockF16 : d.wdtype == GTEN_Q8 ? gten::kResidentBlockQ8 : gten::kResidentBlockQ4;
+        const long long kv_bytes = 2ll * d.n_layers * d.max_ctx * (long long)gten_hip_row_bytes(d.adtype, KV);
+        const long long scratch = 4ll * ((E + 2 * KV) + 2 * E + (long long)d.n_heads * d.max_ctx + 2ll * d.n_heads * dc->n_chunks + 16 +
+                                         (long long)d.n_heads * dc->n_chunks * dh + 2 * E + 2 * (F / 32) + F + 2 * dc->n_best + d.n_vocab) + F;
+        dc->resident_overhead = kv_bytes + scratch;
+        if (n_seq == 1 && !dc->exact && !dc->persist_on) {
+            dc->resident_budget = gten::resident_budget(resident_setting_bytes(), kv_bytes, scratch);
+            dc->resident = gten::resident_plan(gten::resident_step_launches(d.n_layers, E, F, KV, d.n_vocab, block_bytes), dc->resident_budget);
+        }
+    }
     return 0;
 }
 

@@ -238,7 +238,8 @@ union GemvHotWords {
 
 // NM: matrices concatenated along the output rows -- 1 (o, down, lm_head: the weight requests are formed from the
 // preloaded words alone), or 0 = a.n_mats at run time (q|k|v, gate|up)
-template <int WT, int PRO, int NCH, int R, int EPI, int NT, int NM = 0>
+// WLD: the cache policy of the weight requests (gten_dev.h) -- WLD_NT, or WLD_KEEP for a launch the decoder's plan keeps resident
+template <int WT, int PRO, int NCH, int R, int EPI, int NT, int NM = 0, int WLD = WLD_NT>
 __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, const unsigned long long h1, const unsigned long long h2,
                                                   const unsigned long long h3, const unsigned long long h4, const unsigned long long h5,
                                                   const unsigned long long h6, const Gemv8Args a)
@@ -394,19 +395,19 @@ __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, c
             if (F16W) {
                 // f16 rows: NCH counts 512-element segments, lane takes 8 halves of each
                 const int e = (c * 512 + lane * 8 < d) ? c * 512 + lane * 8 : 0;
-                wq[j][c] = ld_w16((const uint16_t*)qbase + (size_t)lr * d + e);
+                wq[j][c] = ld_w16<WLD>((const uint16_t*)qbase + (size_t)lr * d + e);
                 wq1[j][c] = make_uint4(0, 0, 0, 0);
                 wd[j][c] = 0;
                 continue;
             }
             if (WT == GTEN_Q4) {
-                wq[j][c] = ld_w16((const uint4*)(qbase + (size_t)lr * nb * 16) + b);
+                wq[j][c] = ld_w16<WLD>((const uint4*)(qbase + (size_t)lr * nb * 16) + b);
             } else {
                 const uint4* q0 = (const uint4*)(qbase + (size_t)lr * nb * 32);
-                wq[j][c] = ld_w16(q0 + b);
-                wq1[j][c] = ld_w16(q0 + nb + b);
+                wq[j][c] = ld_w16<WLD>(q0 + b);
+                wq1[j][c] = ld_w16<WLD>(q0 + nb + b);
             }
-            wd[j][c] = ld_w2(drow + b);
+            wd[j][c] = ld_w2<WLD>(drow + b);
         }
     }
     __builtin_amdgcn_sched_barrier(0);            // keep every request above ahead of the prologue's arithmetic

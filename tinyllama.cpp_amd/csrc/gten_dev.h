@@ -47,26 +47,30 @@ __device__ __forceinline__ uint16_t f2h(float f)
 // A decode step reads every weight byte exactly once and each byte by ONE workgroup; with the default policy the
 // stream displaces what the step DOES re-read from the caches (residual rows, attention partials, K/V).  Measured on
 // the fused q4 step (profiles/README.md, round 3).  Activations, K/V and anything re-read keep the default policy.
+// That holds for the SUM of the weights (582 MB in q4 through a 256 MiB memory-side cache); it does not hold for a part of
+// them: the weights are the one input of a step that is identical from token to token, and a nontemporal request does not
+// leave its line in that cache.  So the policy is a compile-time parameter of the load (WLD_*), chosen per LAUNCH by the
+// decoder's plan (host/resident_plan.h): the smallest matrices, up to a byte budget, are requested with the
+// default policy and stay on the die; everything else, and every launch of a decoder without a budget, keeps WLD_NT -- the
+// same instructions as before.  -DGTEN_NT_WEIGHTS=0 still forces the default policy everywhere.
 #ifndef GTEN_NT_WEIGHTS
 #define GTEN_NT_WEIGHTS 1
 #endif
+enum { WLD_NT = 0, WLD_KEEP = 1 };
 typedef unsigned gt_u4v __attribute__((ext_vector_type(4)));
+template <int WLD = WLD_NT>
 __device__ __forceinline__ uint4 ld_w16(const void* p)
 {
-#if GTEN_NT_WEIGHTS
-    const gt_u4v v = __builtin_nontemporal_load((const gt_u4v*)p);
-#else
-    const gt_u4v v = *(const gt_u4v*)p;
-#endif
+    gt_u4v v;
+    if constexpr (GTEN_NT_WEIGHTS && WLD == WLD_NT) v = __builtin_nontemporal_load((const gt_u4v*)p);
+    else v = *(const gt_u4v*)p;
     return make_uint4(v.x, v.y, v.z, v.w);
 }
+template <int WLD = WLD_NT>
 __device__ __forceinline__ uint16_t ld_w2(const uint16_t* p)
 {
-#if GTEN_NT_WEIGHTS
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
+    if constexpr (GTEN_NT_WEIGHTS && WLD == WLD_NT) return __builtin_nontemporal_load(p);
+    else return *p;
 }
 
 // ---- cross-lane moves on the DPP path (no LDS crossbar round trip) ----

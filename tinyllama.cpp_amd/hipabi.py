@@ -122,7 +122,8 @@ class GtenHip:
     FSM_EXPAND_CHUNK, FSM_EXPAND_PASS, FSM_EXPAND_STATES = 4096, 8, 64      # GTEN_HIP_FSM_EXPAND_*
     FSM_DEAD = 0xFFFF                                            # GTEN_HIP_FSM_DEAD
     FSM_MAX_BYTES = 1 << 30                                      # GTEN_HIP_FSM_MAX_BYTES
-    AB_SYMBOLS = ["gten_hip_set_decode_attn_classic"]           # include/gten_hip_ab.h
+    AB_SYMBOLS = ["gten_hip_set_decode_attn_classic", "gten_hip_set_weight_resident_mb", "gten_hip_set_weight_resident_bytes", "gten_hip_weight_resident_bytes",
+                  "gten_hip_decoder_resident", "gten_hip_decoder_resident_budget"]         # include/gten_hip_ab.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
     CONTINUE_SYMBOLS = ["gten_hip_block_rows_continued", "gten_hip_set_row_contexts"]       # include/gten_hip_continue.h
@@ -185,6 +186,11 @@ class GtenHip:
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
         self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
         self._decode_persistent = _sig(L, "gten_hip_set_decode_persistent", ci, [ci])
+        self._weight_resident_mb = _sig(L, "gten_hip_set_weight_resident_mb", ci, [ci])
+        self._weight_resident_bytes = _sig(L, "gten_hip_set_weight_resident_bytes", ci, [C.c_longlong])
+        self._weight_resident_get = _sig(L, "gten_hip_weight_resident_bytes", C.c_longlong, [])
+        self._decoder_resident = _sig(L, "gten_hip_decoder_resident", ci, [vp, C.POINTER(ci), C.POINTER(C.c_longlong)])
+        self._decoder_resident_budget = _sig(L, "gten_hip_decoder_resident_budget", ci, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)])
         self._kv_head_major = _sig(L, "gten_hip_set_kv_head_major", ci, [ci])
         self._kv_watch_selftest = _sig(L, "gten_hip_kv_watch_selftest", ci, [])
         self._ffn_streamed = _sig(L, "gten_hip_set_ffn_streamed", ci, [ci])
@@ -710,6 +716,27 @@ class GtenHip:
         """decoders created from now on: the single-sequence attention as k_dec_attn_one64w (0 / False, the default), as
         k_dec_attn_one64 (1 / True, the A/B control) or as k_dec_attn_one64v (2) -- the same bytes (include/gten_hip_ab.h)"""
         self._check(self._decode_attn_classic(int(on)))
+
+    def set_weight_resident_mb(self, mb):
+        """single-sequence decoders created from now on keep the weights of their smallest W.x launches in the memory-side cache, up
+        to `mb` MiB less their own K / V rows and scratch (0: every weight request nontemporal; include/gten_hip_ab.h)"""
+        self._check(self._weight_resident_mb(int(mb)))
+
+    def set_weight_resident_bytes(self, n):
+        """set_weight_resident_mb to the byte"""
+        self._check(self._weight_resident_bytes(int(n)))
+
+    def weight_resident_bytes(self):
+        """the setting a decoder created now would take, in bytes"""
+        return int(self._weight_resident_get())
+
+    def decoder_resident(self, dec):
+        """(resident W.x launches, their weight bytes, the bytes the decoder had left for them, what it took off the setting first) of
+        a raw decoder handle"""
+        n, b, budget, over = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self._check(self._decoder_resident(dec, C.byref(n), C.byref(b)))
+        self._check(self._decoder_resident_budget(dec, C.byref(budget), C.byref(over)))
+        return n.value, b.value, budget.value, over.value
 
     def decoder_group_set(self, dec, g, kv, rows):
         """gten_hip_decoder_group_set on a raw decoder handle (include/gten_hip_groups.h): group record g becomes a snapshot of rows

@@ -91,6 +91,9 @@ class GtenHost:
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
     BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
+    # include/gten_host_resident.h (resident weights: what a decoder decided, and the plan: host/resident_plan.h)
+    RESIDENT_SYMBOLS = ["gten_host_model_resident", "gten_host_batch_resident", "gten_host_resident_plan"]
+    RESIDENT_BLOCK_BYTES = {"f16": 64, "q8": 34, "q4": 18}       # bytes of a 32-element weight block, deltas included
     BEAM_ENDED = ("eos", "length")                               # GTEN_HOST_BEAM_ENDED_*
     SAMPLES_MAX = 64                                             # GTEN_HOST_SAMPLES_MAX
 
@@ -180,6 +183,10 @@ class GtenHost:
         self._m_fsm_states = _sig(L, "gten_host_model_fsm_states", ci, [vp, ci, ci, vp])
         self._b_fsm_states = _sig(L, "gten_host_batch_fsm_states", ci, [vp, ci, ci, ci, vp])
         self._b_fsm_decoder = _sig(L, "gten_host_batch_fsm_decoder", vp, [vp])
+        ll, llp = C.c_longlong, C.POINTER(C.c_longlong)
+        self._m_resident = _sig(L, "gten_host_model_resident", ci, [vp, C.POINTER(ci), llp, llp, llp])
+        self._b_resident = _sig(L, "gten_host_batch_resident", ci, [vp, C.POINTER(ci), llp, llp, llp])
+        self._resident_plan = _sig(L, "gten_host_resident_plan", ci, [ci, ci, ci, ci, ci, ci, ll, vp, vp, llp])
         self._generate_fsm = _sig(L, "gten_host_model_generate_fsm", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
                                                                           C.c_float, C.c_float, vp, vp, vp, pen, ci, vp])
         self._bgen_fsm = _sig(L, "gten_host_batch_generate_fsm", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
@@ -366,6 +373,23 @@ class GtenHost:
         out = np.zeros(count, np.int32)
         self._stoks(out.ctypes.data_as(C.c_void_p), count, seed, n_vocab)
         return out
+
+    def resident_plan(self, n_layers, n_embd, n_ffn, kv_width, n_vocab, block_bytes, budget):
+        """host/resident_plan.h on the W.x launches of one step (per layer q|k|v, o, gate|up, down; then lm_head) against `budget`
+        bytes: (resident u8[4 * n_layers + 1], every launch's weight bytes i64[...], resident launches, their byte sum)"""
+        n = 4 * n_layers + 1
+        res, each, total = np.zeros(n, np.uint8), np.zeros(n, np.int64), C.c_longlong(0)
+        got = self._resident_plan(n_layers, n_embd, n_ffn, kv_width, n_vocab, block_bytes, int(budget), _ptr(res), _ptr(each), C.byref(total))
+        if got < 0:
+            raise GtenHipError(f"resident_plan rc={got}")
+        return res, each, got, total.value
+
+    def _resident_of(self, fn, h):
+        n, b, budget, over = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        rc = fn(h, C.byref(n), C.byref(b), C.byref(budget), C.byref(over))
+        if rc:
+            raise GtenHipError(f"resident rc={rc}: {self.hip._err().decode(errors='replace')}")
+        return n.value, b.value, budget.value, over.value
 
     def model(self, cfg):
         return HostModel(self, cfg)
@@ -906,6 +930,11 @@ class HostModel:
         if rc:
             raise GtenHipError(f"set_cut rc={rc}: {self.host.hip._err().decode(errors='replace')}")
 
+    def resident(self):
+        """(resident W.x launches, their weight bytes, the bytes the decoder had left for them, what it took off the setting first)
+        of this model's decoder (include/gten_host_resident.h)"""
+        return self.host._resident_of(self.host._m_resident, self.h)
+
     def cut_info(self):
         """(top_p, min_p, t = f32(log(min_p)), whether the decoder has ever had a cut set)"""
         a, b, t = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32)
@@ -1268,6 +1297,10 @@ class HostBatch:
         rc = self.set_cut_rc(seq, top_p, min_p)
         if rc:
             raise GtenHipError(f"batch_set_cut rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def resident(self):
+        """HostModel.resident() of the shared decoder: a decoder of 2+ sequences keeps no weights resident"""
+        return self.host._resident_of(self.host._b_resident, self.h)
 
     def cut_info(self):
         """(top_p f32[n_seq], min_p f32[n_seq], t f32[n_seq] = f32(log(min_p)), whether the shared decoder has ever had a cut set)"""
