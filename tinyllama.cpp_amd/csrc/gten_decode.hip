@@ -2887,3 +2887,6 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
 
 // beam search: the round, the in-place gather of the beams' K / V rows and their decoder form (include/gten_hip_beam.h)
 #include "gten_decode_beam.h"
+
+// context shift: K / V rows slid down in place, K rotated back (include/gten_hip_shift.h)
+#include "gten_kv_shift.h"

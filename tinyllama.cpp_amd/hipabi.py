@@ -137,6 +137,8 @@ class GtenHip:
     BEAM_SYMBOLS = ["gten_hip_beam_round", "gten_hip_permute_sets", "gten_hip_decoder_beam_begin", "gten_hip_decoder_beam_round",
                     "gten_hip_decoder_beam_live", "gten_hip_decoder_beam_read", "gten_hip_decoder_beam_end", "gten_hip_decoder_beam_info"]
     BEAM_MAX = 8                                                 # GTEN_HIP_BEAM_MAX
+    SHIFT_SYMBOLS = ["gten_hip_kv_shift"]                        # include/gten_hip_shift.h (context shift of K / V caches in place)
+    SHIFT_ITEM = np.dtype([("k", np.uint64), ("v", np.uint64), ("n", np.int32), ("keep", np.int32), ("drop", np.int32), ("pad", np.int32)])
     GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -243,6 +245,7 @@ class GtenHip:
         self._beam_read = _sig(L, "gten_hip_decoder_beam_read", ci, [vp, ci, vp, vp, vp])
         self._beam_end = _sig(L, "gten_hip_decoder_beam_end", ci, [vp])
         self._beam_info = _sig(L, "gten_hip_decoder_beam_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
+        self._kv_shift = _sig(L, "gten_hip_kv_shift", ci, [vp, ci, ci, sz, ci, ci])
         self.initialised = False
 
     # -- runtime
@@ -672,6 +675,18 @@ class GtenHip:
 
     def permute_sets(self, ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows=1):
         self._check(self.permute_sets_rc(ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows))
+
+    # -- context shift (include/gten_hip_shift.h)
+    def kv_shift_rc(self, items, dtype, pitch, kv_dim, d_head):
+        """the return code of one gten_hip_kv_shift call.  items: [(k_ptr, v_ptr, n, keep, drop)] -- device addresses (ints)"""
+        a = np.zeros(len(items), self.SHIFT_ITEM)
+        for i, (k, v, n, keep, drop) in enumerate(items):
+            a[i] = (int(k), int(v), int(n), int(keep), int(drop), 0)
+        return self._kv_shift(a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a), int(dtype), int(pitch), int(kv_dim), int(d_head))
+
+    def kv_shift(self, items, dtype, pitch, kv_dim, d_head):
+        """gten_hip_kv_shift: every item's K / V rows [keep + drop, n) slide down to keep, K rotated back by drop; asynchronous"""
+        self._check(self.kv_shift_rc(items, dtype, pitch, kv_dim, d_head))
 
     def decoder_beam_begin(self, dec, groups, w):
         """gten_hip_decoder_beam_begin on a raw decoder handle: groups = [(first_seq, n_beams, prompt_len, max_new, eos)], w the f32

@@ -46,6 +46,7 @@ struct Request {
     int last_n = 0;                      // ... counted over the last last_n positions (0: all of them) ...
     bool count_prompt = true;            // ... the prompt's included, or only what was generated
     int fsm_start = -1;                  // the state of the decoder's automaton pool the first new id is chosen in (-1: no automaton)
+    int shift_keep = -1, shift_drop = 0; // context shift when the window fills (host/generate_shift.h; keep < 0: off, the sequence ends there)
     bool cuts() const { return top_k > 0 && !(top_p == 1.f && min_p == 0.f); }
     bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     int start(int n_prompt) const { return count_prompt ? 0 : n_prompt; }

@@ -9,7 +9,9 @@
 // most likely alternatives (include/gten_hip_logprobs.h) after the text; --top-p / --min-p cut the top-k draw (include/gten_hip_nucleus.h);
 // --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h);
 // --stop / --choice end the answer at, or hold it to, id sequences through a token automaton on the device (include/gten_hip_fsm.h);
-// --regex holds it to a regular expression over its text, expanded over the vocabulary on the device (include/gten_hip_regex.h).
+// --regex holds it to a regular expression over its text, expanded over the vocabulary on the device (include/gten_hip_regex.h);
+// --ctx-shift lets an answer go on past the window: when it is full the oldest rows behind KEEP are dropped from the K / V caches on the
+// device and the rest re-rotated in place (include/gten_hip_shift.h, host/generate_shift.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -24,6 +26,7 @@
 #include "../../include/gten_hip_regex.h"
 #include "fsm_build.h"
 #include "generate.h"
+#include "generate_shift.h"
 #include "tokenizer.h"
 
 using namespace gten;
@@ -71,6 +74,10 @@ Optional args.
            | ? * + {m,n}, ASCII \d \w \s; no anchors, look-around or back-references). Where the pattern could stop or go on the
            model decides by drawing the end-of-turn id. Works with -greedy too. Not with --choice, --stop, --ban, --allow or
            --score: an answer is bound to one start state of one automaton.
+--ctx-shift KEEP[,DROP] : go on past the window instead of stopping when it is full: the window is then --ctx positions and --npred may
+           exceed it (up to 1048576). Whenever the window is full the first KEEP positions stay, the next DROP are dropped [default:
+           half of what lies behind KEEP] and the rest slide down. Works with -greedy, top-k, --top-p / --min-p and the penalties.
+           Not with --ban, --allow, --logprobs, --stop, --choice, --regex or --score.
 )";
 
 struct Options {
@@ -95,6 +102,8 @@ struct Options {
     std::string regex;                                   // --regex
     bool regex_given = false;
     bool automaton() const { return !stop.empty() || !choice.empty() || regex_given; }
+    int shift_keep = -1, shift_drop = 0;                 // --ctx-shift KEEP[,DROP] (keep < 0: off)
+    bool shifting() const { return shift_keep >= 0; }
 };
 
 static void emit(const Options& o, Tokenizer& tok, int prev, int id)
@@ -206,7 +215,14 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
     std::vector<float> logprob, top_lp;
     std::vector<int32_t> top_id;
     int rc = 0;
-    if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises() && fsm_start < 0) {
+    if (o.shifting()) {
+        Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, -1, 0, -1, o.top_p, o.min_p, o.rep, o.freq, o.pres, o.last_n, true};
+        r.shift_keep = o.shift_keep;
+        r.shift_drop = o.shift_drop;
+        const char* why = nullptr;
+        rc = generate_shifting<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm>(model, tokens, o.n_predict, tok.eos, r, model.n_ctx_, nullptr, &why);
+        if (rc < 0 && why) { std::cerr << "error: " << why << "\n"; std::exit(EXIT_FAILURE); }
+    } else if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises() && fsm_start < 0) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
     } else {
         const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p,
@@ -331,7 +347,7 @@ int main(int argc, char const* argv[])
         else if (arg == "--npred") {
             int v = 0;
             try { v = std::stoi(value("npred")); } catch (...) { std::cerr << "Invalid npred value.\n"; return -1; }
-            if (v < 1 || v > 2048) { std::cerr << "npred must be greater than 1 and less than 2048.\n"; return -1; }
+            if (v < 1 || v > (1 << 20)) { std::cerr << "npred must be greater than 1 and less than 2048.\n"; return -1; }
             o.n_predict = v;
         } else if (arg == "--temp") {
             float v = 0.f;
@@ -405,6 +421,12 @@ int main(int argc, char const* argv[])
             std::vector<int32_t> list;
             if (!parse_id_list(is_stop ? "stop" : "choice", value(is_stop ? "stop" : "choice"), 32003, &list, false)) return -1;
             (is_stop ? o.stop : o.choice).push_back(list);
+        } else if (arg == "--ctx-shift") {
+            std::vector<int32_t> pair;
+            if (!parse_id_list("ctx-shift", value("ctx-shift"), 2048, &pair, false)) return -1;
+            if (pair.size() > 2 || (pair.size() == 2 && pair[1] < 1)) { std::cerr << "ctx-shift takes KEEP or KEEP,DROP with DROP gte 1.\n"; return -1; }
+            o.shift_keep = pair[0];
+            o.shift_drop = pair.size() == 2 ? pair[1] : 0;
         } else if (arg == "--regex") {
             o.regex = value("regex");
             o.regex_given = true;
@@ -421,6 +443,12 @@ int main(int argc, char const* argv[])
             return EXIT_FAILURE;
         }
     }
+    if (!o.shifting() && o.n_predict > 2048) { std::cerr << "npred must be greater than 1 and less than 2048.\n"; return -1; }
+    if (o.shifting() && (o.constrained() || o.logprobs >= 0 || o.automaton() || !o.score_path.empty())) {
+        std::cerr << "--ctx-shift does not combine with --ban, --allow, --logprobs, --stop, --choice, --regex or --score: what they bind by position is not carried through a shift.\n";
+        return -1;
+    }
+    if (o.shifting() && !shift_ok(o.ctx, o.shift_keep, o.shift_drop)) { std::cerr << "ctx-shift: KEEP + DROP do not fit the window of " << o.ctx << " positions.\n"; return -1; }
     if (o.cut_given && o.greedy) { std::cerr << "top-p and min-p need top-k sampling: not with -greedy.\n"; return -1; }
     if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
     if (o.pen_given && !o.score_path.empty()) { std::cerr << "the repeat, frequency and presence penalties do not apply to --score.\n"; return -1; }
@@ -455,7 +483,7 @@ int main(int argc, char const* argv[])
     dtype.wdtype = o.model_dtype;
     dtype.adtype = (o.model_dtype == kFloat16) ? kFloat16 : kQint8;          // tinyllama.cpp:258-265
 
-    TinyLlama model{o.score_path.empty() ? o.n_predict : o.ctx, dtype};
+    TinyLlama model{o.score_path.empty() && !o.shifting() ? o.n_predict : o.ctx, dtype};
     model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
     if (!o.score_path.empty()) return run_score(o, model, tokenizer);

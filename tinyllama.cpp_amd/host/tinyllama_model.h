@@ -1223,6 +1223,15 @@ public:
         sessions_[(size_t)s].rows = std::min(sessions_[(size_t)s].rows, n_ids);
         return 0;
     }
+    // the session's set was shifted by (keep, drop) on the device (include/gten_host_shift.h; keep + drop <= rows):
+    // the history loses ids [keep, keep + drop), `drop` fewer rows are valid, and a prefix mark stays only where keep covers it
+    void session_shifted(int s, int keep, int drop)
+    {
+        Session& ss = sessions_[(size_t)s];
+        ss.ids.erase(ss.ids.begin() + keep, ss.ids.begin() + keep + drop);
+        ss.rows -= drop;
+        if (int& P = share_mark(sess_base() + s); keep < P) P = 0;
+    }
     void sessions_info(int* open, unsigned long long* kv_bytes, unsigned long long* turns, unsigned long long* turns_continued,
                        unsigned long long* rows_computed, unsigned long long* rows_kept) const
     {

@@ -88,6 +88,12 @@ class GtenHost:
                         "gten_host_batch_session_open", "gten_host_batch_session_close", "gten_host_batch_session_info", "gten_host_batch_session_ids",
                         "gten_host_batch_session_truncate", "gten_host_batch_sessions_info", "gten_host_batch_serve_sessions"]
     SESSIONS_MAX = 256                                           # GTEN_HOST_SESSIONS_MAX
+    # include/gten_host_shift.h (context shift: the plan, the cache primitives, generation past the window, host/capi_shift.cpp)
+    SHIFT_SYMBOLS = ["gten_host_shift_last_error", "gten_host_shift_plan", "gten_host_shift_drop", "gten_host_shift_phi", "gten_host_model_shift",
+                     "gten_host_batch_shift", "gten_host_batch_kv_read", "gten_host_batch_kv_row_bytes", "gten_host_batch_shift_info",
+                     "gten_host_model_shift_info", "gten_host_model_generate_shifting", "gten_host_batch_generate_shifting",
+                     "gten_host_batch_session_shift"]
+    SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
     BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
@@ -274,6 +280,40 @@ class GtenHost:
         self._synthw = _sig(L, "gten_host_synth_weight", ci, [cfgp, C.c_uint64, ci, vp, sz])
         self._writeg = _sig(L, "gten_host_write_gten", ci, [cfgp, C.c_uint64, C.c_char_p])
         self._stoks = _sig(L, "gten_host_synthetic_tokens", None, [vp, ci, C.c_uint32, ci])
+        self._shift_err = _sig(L, "gten_host_shift_last_error", C.c_char_p, [])
+        self._shift_plan = _sig(L, "gten_host_shift_plan", ci, [ci, ci, ci, ci, ci] + [C.POINTER(ci)] * 5)
+        self._shift_drop = _sig(L, "gten_host_shift_drop", ci, [ci, ci, ci])
+        self._shift_phi = _sig(L, "gten_host_shift_phi", ci, [ci, ci, ci])
+        self._mshift = _sig(L, "gten_host_model_shift", ci, [vp, ci, ci, ci])
+        self._bshift = _sig(L, "gten_host_batch_shift", ci, [vp, vp, vp, ci, ci, ci])
+        self._bkv_read = _sig(L, "gten_host_batch_kv_read", ci, [vp, ci, ci, ci, ci, vp, vp])
+        self._bkv_row_bytes = _sig(L, "gten_host_batch_kv_row_bytes", ci, [vp])
+        self._bshift_info = _sig(L, "gten_host_batch_shift_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull)])
+        self._mshift_info = _sig(L, "gten_host_model_shift_info", ci, [vp, C.POINTER(ull), C.POINTER(ull), C.POINTER(ull)])
+        self._generate_shift = _sig(L, "gten_host_model_generate_shifting", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, C.c_float,
+                                                                                C.c_float, pen, ci, ci])
+        self._bgen_shift = _sig(L, "gten_host_batch_generate_shifting", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, vp, ci, ci, C.c_float, C.c_float,
+                                                                             pen, ci, ci, vp, vp])
+        self._bsess_shift = _sig(L, "gten_host_batch_session_shift", ci, [vp, ci, ci, ci])
+
+    def shift_error(self):
+        """the text of the last refusal by an entry point of include/gten_host_shift.h"""
+        return self._shift_err().decode(errors="replace")
+
+    # -- the context shift's plan (host/shift_plan.h): no device needed
+    def shift_plan(self, n_ids, rows, max_ctx, keep, drop=0):
+        """(due, keep, drop, ids after, rows after) for a sequence of n_ids ids, `rows` of them with valid K / V rows; None: no such plan"""
+        o = [C.c_int(0) for _ in range(5)]
+        if self._shift_plan(int(n_ids), int(rows), int(max_ctx), int(keep), int(drop), *[C.byref(x) for x in o]):
+            return None
+        return tuple(x.value for x in o)
+
+    def shift_drop(self, rows, keep, drop=0):
+        """the drop that applies to `rows` valid rows, or -1 where shift(keep, drop) is not possible on them"""
+        return self._shift_drop(int(rows), int(keep), int(drop))
+
+    def shift_phi(self, p, keep, drop):
+        return self._shift_phi(int(p), int(keep), int(drop))
 
     def default_config(self, wdtype, adtype):
         cfg = HostConfig()
@@ -999,6 +1039,40 @@ class HostModel:
         ids = buf[:total].copy()
         return (ids, lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else ids
 
+    # ---- context shift (include/gten_host_shift.h)
+    def generate_shifting_rc(self, prompt, max_tokens, keep, drop=0, eos=-1, top_k=0, temp=1.0, seed=0, stream=0, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                             count_prompt=True, top_p=1.0, min_p=0.0, table=-1, n_top=None):
+        """gten_host_model_generate_shifting: (total or a negative code, ids)"""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        pen = _penalty_arg(1, float(rep), float(freq), float(pres), int(last_n), bool(count_prompt))
+        total = self.host._generate_shift(self.h, _ptr(buf), len(prompt), max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)),
+                                          C.c_uint32(int(stream)), int(table), -1 if n_top is None else int(n_top), C.c_float(top_p), C.c_float(min_p),
+                                          C.byref(pen), int(keep), int(drop))
+        return total, buf[: max(total, 0)].copy()
+
+    def generate_shifting(self, prompt, max_tokens, keep, drop=0, **requests):
+        """generate_penalized() that goes on past the window: whenever it is full the caches are shifted by (keep, drop) -- drop 0: half
+        of what lies behind keep -- and generation continues; max_tokens may exceed max_ctx, the ids come back in generation order.
+        keep < 0: generate_penalized() itself."""
+        total, ids = self.generate_shifting_rc(prompt, max_tokens, keep, drop, **requests)
+        if total < 0:
+            raise GtenHipError(f"generate_shifting rc={total}: {self.host.shift_error() or self.host.hip._err().decode(errors='replace')}")
+        return ids
+
+    def shift(self, n_rows, keep, drop=0):
+        """gten_host_model_shift: this model's caches, n_rows of them valid, shifted by (keep, drop)"""
+        rc = self.host._mshift(self.h, int(n_rows), int(keep), int(drop))
+        if rc:
+            raise GtenHipError(f"model_shift rc={rc}: {self.host.shift_error() or self.host.hip._err().decode(errors='replace')}")
+
+    def shift_info(self):
+        """(shifts done, rows moved, rows dropped)"""
+        u = [C.c_ulonglong(0) for _ in range(3)]
+        self.host._mshift_info(self.h, *[C.byref(x) for x in u])
+        return tuple(x.value for x in u)
+
     def set_fsm_rc(self, fsm):
         return self.host._m_set_fsm(self.h, fsm.h if fsm is not None else None)
 
@@ -1478,6 +1552,62 @@ class HostBatch:
             f.close()
 
     # ---- sessions (include/gten_host_sessions.h)
+    # ---- context shift (include/gten_host_shift.h)
+    def _shift_ck(self, rc, what):
+        if rc:
+            raise GtenHipError(f"{what} rc={rc}: {self.host.shift_error() or self.host.hip._err().decode(errors='replace')}")
+
+    def shift_rc(self, seqs, n_rows, keep, drop=0):
+        seqs, n_rows = np.ascontiguousarray(seqs, dtype=np.int32), np.ascontiguousarray(n_rows, dtype=np.int32)
+        assert len(seqs) == len(n_rows)
+        return self.host._bshift(self.h, _ptr(seqs), _ptr(n_rows), int(keep), int(drop), len(seqs))
+
+    def shift(self, seqs, n_rows, keep, drop=0):
+        """gten_host_batch_shift: the caches of sequences seqs[i], n_rows[i] of their rows valid, shifted by (keep, drop) in one device call.
+        Only the caches change: the ids and positions of the steps that follow are the caller's."""
+        self._shift_ck(self.shift_rc(seqs, n_rows, keep, drop), "batch_shift")
+
+    def kv_row_bytes(self):
+        return self.host._bkv_row_bytes(self.h)
+
+    def kv_read(self, seq, layer, row_from, rows):
+        """(K, V) storage bytes of rows [row_from, row_from + rows) of sequence seq's caches on `layer`: uint8 [rows][row_bytes] each"""
+        rb = self.kv_row_bytes()
+        k, v = np.zeros((rows, rb), np.uint8), np.zeros((rows, rb), np.uint8)
+        self._shift_ck(self.host._bkv_read(self.h, int(seq), int(layer), int(row_from), int(rows), _ptr(k), _ptr(v)), "batch_kv_read")
+        return k, v
+
+    def shift_info(self):
+        """(sequence-shifts done, rows moved, rows dropped) through this batch"""
+        u = [C.c_ulonglong(0) for _ in range(3)]
+        self._ck(self.host._bshift_info(self.h, *[C.byref(x) for x in u]), "batch_shift_info")
+        return tuple(x.value for x in u)
+
+    def generate_shifting_rc(self, prompts, max_tokens, keep, drop=0, eos=-1, top_k=0, temp=1.0, seed=0, streams=None, rep=1.0, freq=0.0, pres=0.0,
+                             last_n=0, count_prompt=True, top_p=1.0, min_p=0.0, table=-1, n_top=None):
+        """gten_host_batch_generate_shifting: (rc, ids per sequence)"""
+        assert len(prompts) == self.n_seq
+        pr, npr, mp = _pack(prompts)
+        out, tot = np.zeros((self.n_seq, max_tokens), np.int32), np.zeros(self.n_seq, np.int32)
+        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
+        pen = _penalty_arg(self.n_seq, rep, freq, pres, last_n, count_prompt)
+        rc = self.host._bgen_shift(self.h, _ptr(pr), _ptr(npr), mp, max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)), _ptr(st), int(table),
+                                   -1 if n_top is None else int(n_top), C.c_float(top_p), C.c_float(min_p), C.byref(pen), int(keep), int(drop), _ptr(out), _ptr(tot))
+        return rc, [out[q, : tot[q]].copy() for q in range(self.n_seq)]
+
+    def generate_shifting(self, prompts, max_tokens, keep, drop=0, **requests):
+        """generate_penalized() of every sequence past the window (HostModel.generate_shifting): list of id arrays, prompt included"""
+        rc, ids = self.generate_shifting_rc(prompts, max_tokens, keep, drop, **requests)
+        self._shift_ck(rc, "batch_generate_shifting")
+        return ids
+
+    def session_shift_rc(self, s, keep, drop=0):
+        return self.host._bsess_shift(self.h, int(s), int(keep), int(drop))
+
+    def session_shift(self, s, keep, drop=0):
+        """the session's set is shifted by (keep, drop) on the device; its ids become ids[:keep] + ids[keep + drop:], its rows rows - drop"""
+        self._shift_ck(self.session_shift_rc(s, keep, drop), "batch_session_shift")
+
     def sessions_reserve(self, n):
         """room for n sessions in all (at most SESSIONS_MAX); each costs a cache set when it is first opened"""
         self._ck(self.host._bsess_reserve(self.h, int(n)), "batch_sessions_reserve")
