@@ -31,6 +31,7 @@
 #include "gten_hip_penalty.h"
 #include "gten_hip_fsm.h"
 #include "gten_hip_regex.h"
+#include "gten_hip_stoptext.h"
 #include "gten_hip_ab.h"
 #include "gten_hip_prefix_decode.h"
 #include "gten_hip_prefixes.h"
@@ -2884,6 +2885,8 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
 
 // byte automata expanded over the vocabulary into the pool, and the pool's check on the device (include/gten_hip_regex.h)
 #include "gten_fsm_expand.h"
+// search automata (stop strings given as text) expanded the same way by their own rule (include/gten_hip_stoptext.h)
+#include "gten_fsm_search.h"
 
 // beam search: the round, the in-place gather of the beams' K / V rows and their decoder form (include/gten_hip_beam.h)
 #include "gten_decode_beam.h"

@@ -220,69 +220,15 @@ int gten_hip_decoder_set_vocab_bytes(gten_hip_decoder* dc, const uint8_t* bytes_
     return 0;
 }
 
+// (the body is gten_hip_decoder_set_fsm_parts_ex's, csrc/gten_fsm_search.h: parts that name the rule their automaton is expanded by)
 int gten_hip_decoder_set_fsm_parts(gten_hip_decoder* dc, int n_states, const uint8_t* flags_host, const gten_hip_fsm_part* parts, int n_parts)
 {
-    GTR_NEED_INIT();
-    GTR_REQUIRE(dc, "decoder_set_fsm_parts: null decoder");
-    GTR_REQUIRE(!dc->persist_on, "decoder_set_fsm_parts: the persistent step (gten_hip_set_decode_persistent) has no sampler");
-    SamplerState& s = dc->smp;
-    GTR_REQUIRE(s.n_fsm == 0, "decoder_set_fsm_parts: %d sequences are bound to the present pool (gten_hip_decoder_set_seq_fsm(.., -1, 0) first)", s.n_fsm);
-    const int V = dc->d.n_vocab;
-    GTR_REQUIRE(flags_host && parts && n_parts >= 1 && n_states >= 1 && n_states <= GTEN_HIP_FSM_MAX_STATES, "decoder_set_fsm_parts: %d states (1 .. %d), or a null table",
-                n_states, GTEN_HIP_FSM_MAX_STATES);
-    GTR_REQUIRE((unsigned long long)n_states * (unsigned long long)V * 2ull <= GTEN_HIP_FSM_MAX_BYTES, "decoder_set_fsm_parts: %d states of %d ids are more than %llu bytes",
-                n_states, V, (unsigned long long)GTEN_HIP_FSM_MAX_BYTES);
-    long long at = 0;
-    for (int k = 0; k < n_parts; k++) {
+    std::vector<gten_hip_fsm_part_ex> ex;
+    for (int k = 0; parts && k < n_parts; k++) {
         const gten_hip_fsm_part& p = parts[k];
-        GTR_REQUIRE(p.first == at && p.count >= 1 && at + p.count <= n_states, "decoder_set_fsm_parts: part %d covers [%d, %d + %d), expected to start at %lld of %d",
-                    k, p.first, p.first, p.count, at, n_states);
-        if (!p.rows_host) {
-            GTR_REQUIRE(p.next256_host && p.accept_host && p.n_byte_states >= 1 && p.eos >= -1 && p.eos < V && p.count == p.n_byte_states + (p.eos >= 0 ? 1 : 0),
-                        "decoder_set_fsm_parts: part %d: a byte automaton of %d states with eos %d does not make %d states", k, p.n_byte_states, p.eos, p.count);
-            GTR_REQUIRE(s.vocab_offsets, "decoder_set_fsm_parts: part %d is a byte automaton and the decoder has no vocabulary (gten_hip_decoder_set_vocab_bytes)", k);
-        }
-        at += p.count;
+        ex.push_back(gten_hip_fsm_part_ex{p.first, p.count, p.rows_host, p.next256_host, p.accept_host, p.n_byte_states, p.eos, GTEN_HIP_FSM_PART_MATCH});
     }
-    GTR_REQUIRE(at == n_states, "decoder_set_fsm_parts: the parts cover %lld of %d states", at, n_states);
-    GTR_CHECK(hipStreamSynchronize(stream()));             // (no step in flight reads the pool that goes)
-    // the new pool is complete and checked on the device before the old one goes: a refusal or a failed allocation leaves the previous pool
-    FxScratch tmp;
-    uint16_t* next = nullptr;
-    uint8_t* flags = nullptr;
-    GTR_CHECK(tmp.take((void**)&next, (size_t)n_states * (size_t)V * sizeof(uint16_t)));
-    GTR_CHECK(tmp.take((void**)&flags, (size_t)n_states));
-    GTR_CHECK(hipMemcpyAsync(flags, flags_host, (size_t)n_states, hipMemcpyHostToDevice, stream()));
-    for (int k = 0; k < n_parts; k++) {
-        const gten_hip_fsm_part& p = parts[k];
-        if (p.rows_host) {
-            GTR_CHECK(hipMemcpyAsync(next + (size_t)p.first * (size_t)V, p.rows_host, (size_t)p.count * (size_t)V * sizeof(uint16_t), hipMemcpyHostToDevice, stream()));
-            continue;
-        }
-        uint16_t* n256 = nullptr;
-        uint8_t* acc = nullptr;
-        GTR_CHECK(tmp.take((void**)&n256, (size_t)p.n_byte_states * 256 * sizeof(uint16_t)));
-        GTR_CHECK(tmp.take((void**)&acc, (size_t)p.n_byte_states));
-        GTR_CHECK(hipMemcpyAsync(n256, p.next256_host, (size_t)p.n_byte_states * 256 * sizeof(uint16_t), hipMemcpyHostToDevice, stream()));
-        GTR_CHECK(hipMemcpyAsync(acc, p.accept_host, (size_t)p.n_byte_states, hipMemcpyHostToDevice, stream()));
-        if (const int rc = fx_launch(next, flags, V, p.first, s.vocab_bytes, s.vocab_n_bytes, s.vocab_offsets, n256, acc, p.n_byte_states, p.eos)) return rc;
-    }
-    int bad = 0;
-    long long where = -1;
-    if (const int rc = fx_check(next, flags, n_states, V, &bad, &where)) return rc;
-    GTR_REQUIRE(bad != GTEN_HIP_FSM_BAD_ENTRY, "decoder_set_fsm_parts: state %lld has an entry that is neither a state nor DEAD", where);
-    GTR_REQUIRE(bad != GTEN_HIP_FSM_STUCK, "decoder_set_fsm_parts: state %lld is not final and allows no id", where);
-    std::vector<uint8_t> flags_now((size_t)n_states);
-    GTR_CHECK(hipMemcpy(flags_now.data(), flags, (size_t)n_states, hipMemcpyDeviceToHost));      // (the expanded ranges' flags were made on the device)
-    // (the pool's pointers and size are arguments of the captured step-end launch: graphs that hold the old ones go)
-    if (s.fsm_on) GTR_CHECK(drop_graphs(dc));
-    if (s.fsm_next) GTR_CHECK(hipFree(s.fsm_next));
-    if (s.fsm_flags) GTR_CHECK(hipFree(s.fsm_flags));
-    tmp.release(next);
-    tmp.release(flags);
-    s.fsm_next = next; s.fsm_flags = flags; s.fsm_states = n_states;
-    s.fsm_flags_host.swap(flags_now);
-    return 0;
+    return gten_hip_decoder_set_fsm_parts_ex(dc, n_states, flags_host, parts ? ex.data() : nullptr, n_parts);
 }
 
 } // extern "C"

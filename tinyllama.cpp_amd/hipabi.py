@@ -119,6 +119,8 @@ class GtenHip:
                    "gten_hip_decoder_slot_states", "gten_hip_mask_rows_fsm", "gten_hip_sample_rows_fsm"]
     # include/gten_hip_regex.h (byte automata expanded over the vocabulary on the device)
     REGEX_SYMBOLS = ["gten_hip_fsm_expand", "gten_hip_fsm_check_dev", "gten_hip_decoder_set_vocab_bytes", "gten_hip_decoder_set_fsm_parts"]
+    # include/gten_hip_stoptext.h (search automata -- stop strings given as text -- expanded over the vocabulary on the device)
+    STOPTEXT_SYMBOLS = ["gten_hip_fsm_expand_search", "gten_hip_decoder_set_fsm_parts_ex"]
     FSM_EXPAND_CHUNK, FSM_EXPAND_PASS, FSM_EXPAND_STATES = 4096, 8, 64      # GTEN_HIP_FSM_EXPAND_*
     FSM_DEAD = 0xFFFF                                            # GTEN_HIP_FSM_DEAD
     FSM_MAX_BYTES = 1 << 30                                      # GTEN_HIP_FSM_MAX_BYTES
@@ -231,6 +233,8 @@ class GtenHip:
         self._fsm_expand = _sig(L, "gten_hip_fsm_expand", ci, [vp, vp, ci, ci, ci, vp, C.c_longlong, vp, vp, vp, ci, ci])
         self._fsm_check_dev = _sig(L, "gten_hip_fsm_check_dev", ci, [vp, vp, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong)])
         self._set_vocab_bytes = _sig(L, "gten_hip_decoder_set_vocab_bytes", ci, [vp, vp, vp])
+        self._fsm_expand_search = _sig(L, "gten_hip_fsm_expand_search", ci, [vp, vp, ci, ci, ci, vp, C.c_longlong, vp, vp, vp, ci])
+        self._set_fsm_parts_ex = _sig(L, "gten_hip_decoder_set_fsm_parts_ex", ci, [vp, ci, vp, vp, ci])
         self._set_fsm_parts = _sig(L, "gten_hip_decoder_set_fsm_parts", ci, [vp, ci, vp, vp, ci])
         self._mask_rows_fsm = _sig(L, "gten_hip_mask_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, C.c_longlong])
         self._sample_rows_fsm = _sig(L, "gten_hip_sample_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
@@ -498,6 +502,53 @@ class GtenHip:
 
     def decoder_set_fsm_parts(self, dec, n_states, flags, parts):
         self._check(self.decoder_set_fsm_parts_rc(dec, n_states, flags, parts))
+
+    # ---- include/gten_hip_stoptext.h
+    def fsm_expand_search(self, pool, n_vocab, base, vocab, next256, accept, n_bytes=None):
+        """gten_hip_fsm_expand_search into `pool` (fsm_upload()'s tuple): rows [base, base + Sb] -- the last one the HIT state -- from the
+        vocabulary `vocab` = (bytes u8[], offsets int32[n_vocab + 1]) and the search automaton (next256 u16 [Sb][256], accept u8 [Sb]).
+        n_bytes: what the call is told the bytes' length is (None: len(bytes)).  Everything it reads is uploaded here and freed after a sync."""
+        vb, vo = np.ascontiguousarray(vocab[0], dtype=np.uint8), np.ascontiguousarray(vocab[1], dtype=np.int32)
+        n256, acc = np.ascontiguousarray(next256, dtype=np.uint16), np.ascontiguousarray(accept, dtype=np.uint8)
+        assert n256.shape == (len(acc), 256) and len(vo) == n_vocab + 1
+        assert n_bytes is None or 0 <= n_bytes <= len(vb)
+        pad = np.zeros(4, np.uint8)
+        bufs = [self.upload(np.concatenate([vb, pad])), self.upload(vo), self.upload(n256), self.upload(acc)]
+        try:
+            self._check(self._fsm_expand_search(pool[0].ptr, pool[1].ptr, int(pool[2]), int(n_vocab), int(base), bufs[0].ptr,
+                                                len(vb) if n_bytes is None else int(n_bytes), bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, len(acc)))
+            self.sync()
+        finally:
+            for b in bufs:
+                b.free()
+
+    class FsmPartEx(C.Structure):
+        _fields_ = [("first", C.c_int), ("count", C.c_int), ("rows_host", C.c_void_p), ("next256_host", C.c_void_p), ("accept_host", C.c_void_p),
+                    ("n_byte_states", C.c_int), ("eos", C.c_int), ("mode", C.c_int)]
+
+    def decoder_set_fsm_parts_ex_rc(self, dec, n_states, flags, parts):
+        """the return code of gten_hip_decoder_set_fsm_parts_ex.  parts: decoder_set_fsm_parts_rc's, or ("search", next256 u16 [Sb][256],
+        accept u8 [Sb]): Sb + 1 states by the search rule."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        keep, arr, at = [], (self.FsmPartEx * max(len(parts), 1))(), 0
+        for k, p in enumerate(parts):
+            if p[0] == "rows":
+                rows = np.ascontiguousarray(p[1], dtype=np.uint16)
+                keep.append(rows)
+                arr[k] = self.FsmPartEx(at, len(rows), rows.ctypes.data, None, None, 0, -1, 0)
+                at += len(rows)
+            else:
+                n256, acc = np.ascontiguousarray(p[1], dtype=np.uint16), np.ascontiguousarray(p[2], dtype=np.uint8)
+                search = p[0] == "search"
+                eos = -1 if search else int(p[3])
+                keep += [n256, acc]
+                count = len(acc) + (1 if (search or eos >= 0) else 0)
+                arr[k] = self.FsmPartEx(at, count, None, n256.ctypes.data, acc.ctypes.data, len(acc), eos, 1 if search else 0)
+                at += count
+        return self._set_fsm_parts_ex(dec, int(n_states), flags.ctypes.data_as(C.c_void_p), C.cast(arr, C.c_void_p), len(parts))
+
+    def decoder_set_fsm_parts_ex(self, dec, n_states, flags, parts):
+        self._check(self.decoder_set_fsm_parts_ex_rc(dec, n_states, flags, parts))
 
     def decoder_fsm_pool(self, dec, n_vocab):
         """the decoder's pool read back from the device through gten_hip_decoder_fsm_info's pointers: (next u16 [S][n_vocab], flags u8 [S])"""

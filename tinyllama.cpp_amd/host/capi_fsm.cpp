@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/gten_hip_regex.h"
+#include "../../include/gten_hip_stoptext.h"
 #include "capi_handles.h"
 #include "fsm_build.h"
 
@@ -36,16 +37,18 @@ int set_pool(gten_hip_decoder* dec, int n_vocab, const gten_host_fsm* f)
         // regex ranges never cross the bus as tables: the decoder gets the vocabulary's bytes and expands them itself
         // (include/gten_hip_regex.h); the ranges of host rows are uploaded as they always were
         if (const int rc = gten_hip_decoder_set_vocab_bytes(dec, f->pool.vocab_bytes(), f->pool.vocab_offsets())) return rc;
-        std::vector<gten_hip_fsm_part> parts;
+        // (a search range -- stop strings as text, include/gten_hip_stoptext.h -- goes the same way under its own mode)
+        std::vector<gten_hip_fsm_part_ex> parts;
         for (const FsmPool::Part& p : f->pool.parts()) {
             if (p.regex < 0) {
-                parts.push_back(gten_hip_fsm_part{p.first, p.count, f->pool.host_rows(p), nullptr, nullptr, 0, -1});
+                parts.push_back(gten_hip_fsm_part_ex{p.first, p.count, f->pool.host_rows(p), nullptr, nullptr, 0, -1, GTEN_HIP_FSM_PART_MATCH});
             } else {
                 const FsmPool::Regex& r = f->pool.regex(p.regex);
-                parts.push_back(gten_hip_fsm_part{p.first, p.count, nullptr, r.dfa.next.data(), r.dfa.accept.data(), r.dfa.n_states(), r.eos});
+                parts.push_back(gten_hip_fsm_part_ex{p.first, p.count, nullptr, r.dfa.next.data(), r.dfa.accept.data(), r.dfa.n_states(), r.eos,
+                                                     r.mode == FsmPool::kSearch ? GTEN_HIP_FSM_PART_SEARCH : GTEN_HIP_FSM_PART_MATCH});
             }
         }
-        return gten_hip_decoder_set_fsm_parts(dec, f->pool.n_states(), f->pool.flags(), parts.data(), (int)parts.size());
+        return gten_hip_decoder_set_fsm_parts_ex(dec, f->pool.n_states(), f->pool.flags(), parts.data(), (int)parts.size());
     }
     return gten_hip_decoder_set_fsm(dec, f->pool.next(), f->pool.flags(), f->pool.n_states());
 }

@@ -59,7 +59,7 @@ int gten_host_fsm_n_regex(const gten_host_fsm* f)
 {
     if (!f) return -1;
     int n = 0;
-    for (const FsmPool::Part& p : f->pool.parts()) n += p.regex >= 0 ? 1 : 0;
+    for (const FsmPool::Part& p : f->pool.parts()) n += (p.regex >= 0 && f->pool.regex(p.regex).mode == FsmPool::kMatch) ? 1 : 0;
     return n;
 }
 

@@ -7,6 +7,9 @@
 // 2 * n_vocab bytes per state.  The pool is then a list of PARTS: ranges of host rows (packed in next_) and ranges that are byte
 // automata.  next() materialises the latter with the host expansion (regex_expand: the definition the device's expansion is held to);
 // a pool with no such range is one part, and next() is the table it always was.
+//
+// Stop strings given as text (add_stop_text; host/stop_text_build.h) are kept the same way, as a byte automaton in
+// SEARCH mode: its token-level meaning is search_expand(), not regex_expand().
 #pragma once
 
 #include <cstdint>
@@ -18,6 +21,7 @@
 
 #include "../../include/gten_hip_fsm.h"
 #include "regex_build.h"
+#include "stop_text_build.h"
 
 namespace gten {
 
@@ -27,7 +31,9 @@ public:
 
     // states [first, first + count): host rows at next_[rows_at ...] (regex < 0), or byte automaton number `regex`
     struct Part { int first, count; size_t rows_at; int regex; };
-    struct Regex { ByteDfa dfa; int eos; };
+    // a byte automaton and the rule that expands it: kMatch (regex_expand, with eos) or kSearch (search_expand, no eos)
+    enum : int { kMatch = 0, kSearch = 1 };
+    struct Regex { ByteDfa dfa; int eos; int mode = kMatch; };
 
     explicit FsmPool(int n_vocab) : V_{n_vocab} {}
     int n_vocab() const { return V_; }
@@ -41,6 +47,7 @@ public:
             for (const Part& p : parts_) {
                 uint16_t* to = view_.data() + (size_t)p.first * (size_t)V_;
                 if (p.regex < 0) std::memcpy(to, next_.data() + p.rows_at, (size_t)p.count * (size_t)V_ * sizeof(uint16_t));
+                else if (regexes_[(size_t)p.regex].mode == kSearch) search_expand(regexes_[(size_t)p.regex].dfa, bytes_.data(), offsets_.data(), V_, p.first, to);
                 else regex_expand(regexes_[(size_t)p.regex].dfa, bytes_.data(), offsets_.data(), V_, regexes_[(size_t)p.regex].eos, p.first, to);
             }
         }
@@ -55,7 +62,7 @@ public:
     const uint8_t* vocab_bytes() const { return bytes_.data(); }
     const int32_t* vocab_offsets() const { return offsets_.data(); }
 
-    // The vocabulary as byte strings: id i spells bytes[offsets[i], offsets[i + 1]).  Refused once a regex range exists.
+    // The vocabulary as byte strings: id i spells bytes[offsets[i], offsets[i + 1]).  Refused once a regex or search range exists.
     int set_vocab(const uint8_t* bytes, const int32_t* offsets)
     {
         if (!offsets || offsets[0] != 0 || !regexes_.empty()) return kBadArgument;
@@ -87,6 +94,24 @@ public:
         parts_.push_back(Part{base, count, 0, (int)regexes_.size()});
         regexes_.push_back(std::move(r));
         regex_start_.emplace(key, base);
+        view_.clear();
+        return base;
+    }
+
+    // Stop strings as TEXT: the Aho-Corasick automaton of the n byte strings (stop_text_build) as a SEARCH range of Sb + 1 states, the
+    // last one the HIT state; the start state.  Nothing is banned: up to the hit the ids are the unbound generation's, and the id
+    // whose bytes complete a string -- wherever in its piece -- enters the HIT state, which is FINAL.
+    int add_stop_text(const StopText* strings, int n)
+    {
+        if (!has_vocab()) return kBadArgument;
+        Regex r{ByteDfa{}, -1, kSearch};
+        if (const int rc = stop_text_build(strings, n, r.dfa)) return rc;
+        const int count = search_pool_states(r.dfa), base = n_states();
+        if (!fits(count)) return kTooLarge;
+        flags_.resize((size_t)(base + count));
+        search_flags(r.dfa, flags_.data() + base);
+        parts_.push_back(Part{base, count, 0, (int)regexes_.size()});
+        regexes_.push_back(std::move(r));
         view_.clear();
         return base;
     }

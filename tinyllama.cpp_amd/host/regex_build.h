@@ -729,4 +729,39 @@ inline void regex_expand(const ByteDfa& d, const uint8_t* bytes, const int32_t* 
     if (eos >= 0) std::fill(rows + (size_t)Sb * (size_t)n_vocab, rows + (size_t)(Sb + 1) * (size_t)n_vocab, (uint16_t)0xFFFF);
 }
 
+// The token-level meaning of a SEARCH automaton (host/stop_text_build.h): one that looks for something in the text
+// and bans nothing on the way.  Sb byte states become pool states [base, base + Sb], always Sb + 1 of them: base + Sb is the HIT
+// state, FINAL, whose row is all DEAD; the flags of the others are 0.  For s < Sb and id i:
+//   an empty piece stays: next[base + s][i] = base + s (ids beyond the tokenizer, control ids, eos: nothing is banned);
+//   a non-empty piece walks its bytes from s: base + Sb if the state after ANY byte is accepting, else base + the last state;
+//   an entry >= Sb of the automaton reads as "no edge" and makes the entry DEAD (a built automaton has none).
+// The rows of accepting byte states are written by the same rule and are unreachable.  rows: u16 [Sb + 1][n_vocab].  The reference the
+// device kernel (csrc/gten_fsm_search.h) is held to, byte for byte.
+inline int search_pool_states(const ByteDfa& d) { return d.n_states() + 1; }
+
+inline void search_flags(const ByteDfa& d, uint8_t* flags)
+{
+    std::fill(flags, flags + d.n_states(), (uint8_t)0);
+    flags[d.n_states()] = 1;
+}
+
+inline void search_expand(const ByteDfa& d, const uint8_t* bytes, const int32_t* offsets, int n_vocab, int base, uint16_t* rows)
+{
+    const int Sb = d.n_states();
+    for (int s = 0; s < Sb; s++) {
+        uint16_t* row = rows + (size_t)s * (size_t)n_vocab;
+        for (int i = 0; i < n_vocab; i++) {
+            int cur = s;
+            bool hit = false;
+            for (int j = offsets[i]; j < offsets[i + 1] && cur >= 0; j++) {
+                const uint16_t t = d.next[(size_t)cur * 256 + bytes[j]];
+                cur = (int)t < Sb ? (int)t : -1;
+                if (cur >= 0 && d.accept[(size_t)cur]) hit = true;
+            }
+            row[i] = cur < 0 ? (uint16_t)0xFFFF : (uint16_t)(base + (hit ? Sb : cur));
+        }
+    }
+    std::fill(rows + (size_t)Sb * (size_t)n_vocab, rows + (size_t)(Sb + 1) * (size_t)n_vocab, (uint16_t)0xFFFF);
+}
+
 } // namespace gten

@@ -10,6 +10,8 @@
 // --repeat-penalty / --frequency-penalty / --presence-penalty / --repeat-last-n penalise the ids already there, in both modes (include/gten_hip_penalty.h);
 // --stop / --choice end the answer at, or hold it to, id sequences through a token automaton on the device (include/gten_hip_fsm.h);
 // --regex holds it to a regular expression over its text, expanded over the vocabulary on the device (include/gten_hip_regex.h);
+// --stop-text ends it at a stop string given as text, a search automaton expanded the same way (include/gten_hip_stoptext.h);
+// --json-schema holds it to a JSON schema, compiled to a pattern of --regex's dialect (host/json_schema.h);
 // --ctx-shift lets an answer go on past the window: when it is full the oldest rows behind KEEP are dropped from the K / V caches on the
 // device and the rest re-rotated in place (include/gten_hip_shift.h, host/generate_shift.h).
 #include <algorithm>
@@ -24,7 +26,9 @@
 #include <vector>
 
 #include "../../include/gten_hip_regex.h"
+#include "../../include/gten_hip_stoptext.h"
 #include "fsm_build.h"
+#include "json_schema.h"
 #include "generate.h"
 #include "generate_shift.h"
 #include "tokenizer.h"
@@ -74,6 +78,13 @@ Optional args.
            | ? * + {m,n}, ASCII \d \w \s; no anchors, look-around or back-references). Where the pattern could stop or go on the
            model decides by drawing the end-of-turn id. Works with -greedy too. Not with --choice, --stop, --ban, --allow or
            --score: an answer is bound to one start state of one automaton.
+--stop-text STRING : the answer ends as soon as its text holds STRING, wherever in a token it begins or ends; the printed text ends
+           before it (--ids prints every id, the one that completes STRING included). Nothing is banned on the way. Repeatable.
+           Works with -greedy too. Not with --stop, --choice, --regex, --json-schema, --ban, --allow or --score.
+--json-schema FILE : the text of the answer is a JSON document that fits the schema in FILE (types, enum / const, properties /
+           required in their order, items with minItems / maxItems, minLength / maxLength, anyOf / oneOf, $ref into $defs; anything
+           else that would constrain is refused), compact. The tokenizer's end-of-turn id ends it where it could go on. Works with
+           -greedy too. Not with the other automaton flags, --ban, --allow or --score.
 --ctx-shift KEEP[,DROP] : go on past the window instead of stopping when it is full: the window is then --ctx positions and --npred may
            exceed it (up to 1048576). Whenever the window is full the first KEEP positions stay, the next DROP are dropped [default:
            half of what lies behind KEEP] and the rest slide down. Works with -greedy, top-k, --top-p / --min-p and the penalties.
@@ -101,7 +112,9 @@ struct Options {
     std::vector<std::vector<int32_t>> stop, choice;      // --stop / --choice, one id sequence per flag
     std::string regex;                                   // --regex
     bool regex_given = false;
-    bool automaton() const { return !stop.empty() || !choice.empty() || regex_given; }
+    std::vector<std::string> stop_text;                  // --stop-text, one string per flag
+    bool json_given = false;                             // --json-schema: `regex` holds the schema's pattern
+    bool automaton() const { return !stop.empty() || !choice.empty() || regex_given || json_given || !stop_text.empty(); }
     int shift_keep = -1, shift_drop = 0;                 // --ctx-shift KEEP[,DROP] (keep < 0: off)
     bool shifting() const { return shift_keep >= 0; }
 };
@@ -152,7 +165,7 @@ static void set_constraint(const Options& o, TinyLlama& model)
 // --stop / --choice as the pool of the model's decoder (host/fsm_build.h); the start state the answers are bound to
 static int set_automaton(const Options& o, TinyLlama& model, const Tokenizer& tok, int n_vocab)
 {
-    if (o.regex_given) {
+    if (o.regex_given || o.json_given || !o.stop_text.empty()) {
         // the vocabulary's byte strings as decode prints them (control pieces and the ids past the tokenizer: empty), the pattern as a
         // byte automaton, and the expansion of the one over the other on the device
         std::vector<uint8_t> bytes;
@@ -167,9 +180,27 @@ static int set_automaton(const Options& o, TinyLlama& model, const Tokenizer& to
         FsmPool pool(n_vocab);
         int at = -1;
         pool.set_vocab(bytes.data(), offsets.data());
+        if (!o.stop_text.empty()) {
+            // the strings' Aho-Corasick automaton over bytes as a search range: nothing banned, the id that completes one is final
+            std::vector<StopText> strings;
+            for (const std::string& t : o.stop_text) strings.push_back(StopText{(const uint8_t*)t.data(), t.size()});
+            const int start = pool.add_stop_text(strings.data(), (int)strings.size());
+            if (start < 0) {
+                std::cerr << "error: --stop-text: the strings do not fit an automaton pool.\n";
+                std::exit(EXIT_FAILURE);
+            }
+            const FsmPool::Regex& r = pool.regex(0);
+            const gten_hip_fsm_part_ex part{0, pool.n_states(), nullptr, r.dfa.next.data(), r.dfa.accept.data(), r.dfa.n_states(), -1, GTEN_HIP_FSM_PART_SEARCH};
+            if (gten_hip_decoder_set_vocab_bytes(model.decoder_handle(), pool.vocab_bytes(), pool.vocab_offsets()) != 0 ||
+                gten_hip_decoder_set_fsm_parts_ex(model.decoder_handle(), pool.n_states(), pool.flags(), &part, 1) != 0) {
+                std::cerr << "error: " << gten_hip_last_error() << "\n";
+                std::exit(EXIT_FAILURE);
+            }
+            return start;
+        }
         const int start = pool.add_regex(o.regex.c_str(), o.regex.size(), tok.eos, &at);
         if (start < 0) {
-            std::cerr << "error: --regex: " << (start == kRegexUnsupported ? "unsupported construct" : start == kRegexTooLarge ? "too many states" : "bad syntax");
+            std::cerr << "error: " << (o.json_given ? "--json-schema: " : "--regex: ") << (start == kRegexUnsupported ? "unsupported construct" : start == kRegexTooLarge ? "too many states" : "bad syntax");
             if (at >= 0) std::cerr << " at byte " << at;
             std::cerr << ".\n";
             std::exit(EXIT_FAILURE);
@@ -269,7 +300,18 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
         std::cerr << "error: " << gten_hip_last_error() << "\n";
         std::exit(EXIT_FAILURE);
     }
-    for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
+    if (!o.stop_text.empty() && !o.ids) {
+        // the new text as the search automaton read it (the pieces' bytes), cut before the first stop string
+        std::string text;
+        for (size_t i = n_prompt; i < tokens.size(); i++)
+            if (tokens[i] > 2 && tokens[i] < tok.vocab_size()) text += tok.piece_bytes(tokens[i]);
+        std::vector<StopText> strings;
+        for (const std::string& t : o.stop_text) strings.push_back(StopText{(const uint8_t*)t.data(), t.size()});
+        const StopTextHit hit = stop_text_find(strings.data(), (int)strings.size(), (const uint8_t*)text.data(), (long long)text.size());
+        std::cerr << text.substr(0, (size_t)hit.begin);
+    } else {
+        for (size_t i = n_prompt; i < tokens.size(); i++) emit(o, tok, i == n_prompt ? 1 : tokens[i - 1], tokens[i]);
+    }
     (o.ids ? std::cout : std::cerr) << '\n';
     if (o.logprobs < 0) return;
     std::cout.flush();
@@ -438,6 +480,27 @@ int main(int argc, char const* argv[])
                 std::cerr << ".\n";
                 return -1;
             }
+        } else if (arg == "--stop-text") {
+            const std::string text = value("stop-text");
+            if (text.empty()) { std::cerr << "--stop-text: an empty string.\n"; return -1; }
+            o.stop_text.push_back(text);
+        } else if (arg == "--json-schema") {
+            const std::string path = value("json-schema");
+            std::ifstream sf{path, std::ios::binary};
+            if (!sf.is_open()) { std::cerr << "--json-schema: cannot read " << path << ".\n"; return -1; }
+            const std::string schema((std::istreambuf_iterator<char>(sf)), std::istreambuf_iterator<char>());
+            std::string error;
+            if (const int rc = json_schema_regex(schema.data(), schema.size(), 0, 2, o.regex, error)) {
+                if (rc == kJsonUnsupported) std::cerr << "--json-schema: unsupported: " << error << ".\n";
+                else std::cerr << "--json-schema: malformed JSON at byte " << error << ".\n";
+                return -1;
+            }
+            ByteDfa dfa;
+            if (const int rc = regex_compile(o.regex.c_str(), o.regex.size(), dfa, nullptr)) {
+                std::cerr << "--json-schema: " << (rc == kRegexTooLarge ? "too many states" : "the schema's pattern is refused") << ".\n";
+                return -1;
+            }
+            o.json_given = true;
         } else {
             std::cerr << "error: Unknown argument: " << arg << "\n" << usage_message;
             return EXIT_FAILURE;
@@ -455,6 +518,15 @@ int main(int argc, char const* argv[])
     if (!o.stop.empty() && !o.choice.empty()) { std::cerr << "--stop and --choice do not combine: an answer follows one automaton.\n"; return -1; }
     if (o.regex_given && !o.choice.empty()) { std::cerr << "--regex and --choice do not combine: an answer follows one automaton.\n"; return -1; }
     if (o.regex_given && !o.stop.empty()) { std::cerr << "--regex and --stop do not combine: an answer is bound to one start state.\n"; return -1; }
+    for (const char* other : {"--stop", "--choice", "--regex", "--stop-text"}) {
+        const std::string name = other;
+        const bool given = name == "--stop" ? !o.stop.empty() : name == "--choice" ? !o.choice.empty() : name == "--regex" ? o.regex_given : !o.stop_text.empty();
+        if (o.json_given && given) { std::cerr << "--json-schema and " << name << " do not combine: an answer is bound to one start state of one automaton.\n"; return -1; }
+        if (!o.stop_text.empty() && given && name != "--stop-text") {
+            std::cerr << "--stop-text and " << name << " do not combine: an answer is bound to one start state of one automaton.\n";
+            return -1;
+        }
+    }
     if (o.automaton() && o.constrained()) { std::cerr << "--stop, --choice and --regex do not combine with --ban or --allow.\n"; return -1; }
     if (o.automaton() && !o.score_path.empty()) { std::cerr << "--stop, --choice and --regex do not apply to --score.\n"; return -1; }
     for (size_t a = 0; a < o.choice.size(); a++)

@@ -72,6 +72,9 @@ class GtenHost:
     # include/gten_host_regex.h (regular expressions as ranges of an automaton pool, host/capi_regex.cpp)
     REGEX_SYMBOLS = ["gten_host_fsm_set_vocab", "gten_host_tokenizer_vocab_bytes", "gten_host_fsm_add_regex", "gten_host_regex_byte_dfa",
                      "gten_host_fsm_n_regex"]
+    # include/gten_host_stoptext.h (stop strings given as text) and include/gten_host_json.h (JSON schemas as patterns), host/capi_text.cpp
+    STOPTEXT_SYMBOLS = ["gten_host_fsm_add_stop_text", "gten_host_fsm_n_search", "gten_host_stop_text_dfa", "gten_host_stop_text_find"]
+    JSON_SYMBOLS = ["gten_host_json_schema_regex"]
     SCORE_SYMBOLS = ["gten_host_model_score", "gten_host_model_logits_all", "gten_host_model_score_many"]   # include/gten_host_score.h
     PREFIX_SYMBOLS = ["gten_host_batch_set_prefix", "gten_host_batch_prefix_info"]                          # include/gten_host_prefix.h
     PREFIX_DECODE_SYMBOLS = ["gten_host_batch_prefix_decode_info", "gten_host_batch_prefix_decode_share",
@@ -180,6 +183,11 @@ class GtenHost:
         self._fsm_add_regex = _sig(L, "gten_host_fsm_add_regex", ci, [vp, C.c_char_p, ci, C.POINTER(ci)])
         self._regex_byte_dfa = _sig(L, "gten_host_regex_byte_dfa", ci, [C.c_char_p, vp, vp, ci, C.POINTER(ci)])
         self._fsm_n_regex = _sig(L, "gten_host_fsm_n_regex", ci, [vp])
+        self._fsm_add_stop_text = _sig(L, "gten_host_fsm_add_stop_text", ci, [vp, vp, vp, ci])
+        self._fsm_n_search = _sig(L, "gten_host_fsm_n_search", ci, [vp])
+        self._stop_text_dfa = _sig(L, "gten_host_stop_text_dfa", ci, [vp, vp, ci, vp, vp, ci])
+        self._stop_text_find = _sig(L, "gten_host_stop_text_find", ci, [vp, vp, ci, vp, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)])
+        self._json_schema_regex = _sig(L, "gten_host_json_schema_regex", C.c_longlong, [C.c_char_p, ci, ci, vp, C.c_longlong, vp, C.c_longlong])
         self._m_set_fsm = _sig(L, "gten_host_model_set_fsm", ci, [vp, vp])
         self._b_set_fsm = _sig(L, "gten_host_batch_set_fsm", ci, [vp, vp])
         self._m_fsm_info = _sig(L, "gten_host_model_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
@@ -441,6 +449,20 @@ class GtenHost:
         """host/tokenizer.h on a vocabulary file (host only: no GPU needed)"""
         return HostTokenizer(self, path, vocab_size)
 
+    # ---- stop strings as text and JSON schemas (include/gten_host_stoptext.h, include/gten_host_json.h, DESIGN.md 3.21): device-free
+    def stop_text_dfa(self, strings):
+        """the strings' Aho-Corasick automaton over bytes (host/stop_text_build.h): (next256 u16 [Sb][256], total; accept u8 [Sb]); a
+        refusal raises ValueError with the code"""
+        return stop_text_dfa(self, strings)
+
+    def stop_text_find(self, strings, text):
+        """(index, begin, end) of the match that ends first in `text` (then the longest, then the lowest index); (-1, n, n) for none"""
+        return stop_text_find(self, strings, text)
+
+    def json_schema_regex(self, schema, ws=0, depth=2):
+        """the schema (a dict, or its JSON text) as a pattern of the regex dialect; a refusal raises JsonSchemaError"""
+        return json_schema_regex(self, schema, ws, depth)
+
 
 def bias_pairs(pairs=(), fill=0.0, allow=None):
     """(ids int32[], values f32[], fill) of a bias table request (include/gten_hip_bias.h): `pairs` = [(id, value)] over `fill` for every
@@ -565,6 +587,71 @@ def byte_dfa(host, pattern):
     return n256, acc
 
 
+def _as_bytes(s):
+    return s.encode("utf-8") if isinstance(s, str) else bytes(s)
+
+
+def _byte_strings(strings):
+    """a list of str / bytes as the C interface's (pointers, lengths): (ptrs, lens, n); the tuple keeps the buffers alive"""
+    data = [np.frombuffer(_as_bytes(s) + b"\0", np.uint8).copy() for s in strings]          # (never empty: the pointer is real)
+    ptrs = (C.c_void_p * max(len(data), 1))(*[d.ctypes.data for d in data])
+    lens = np.ascontiguousarray([len(d) - 1 for d in data], dtype=np.int32)
+    ptrs._keep = data
+    return ptrs, lens, len(data)
+
+
+def stop_text_dfa(host, strings):
+    ptrs, lens, n = _byte_strings(strings)
+    S = host._stop_text_dfa(ptrs, _ptr(lens), n, None, None, 0)
+    if S < 0:
+        raise ValueError(f"stop_text_dfa refused: {S}")
+    n256, acc = np.zeros((S, 256), np.uint16), np.zeros(S, np.uint8)
+    host._stop_text_dfa(ptrs, _ptr(lens), n, _ptr(n256), _ptr(acc), S)
+    return n256, acc
+
+
+def stop_text_find(host, strings, text):
+    ptrs, lens, n = _byte_strings(strings)
+    raw = _as_bytes(text)
+    buf = np.frombuffer(raw + b"\0", np.uint8).copy()
+    b, e = C.c_longlong(0), C.c_longlong(0)
+    k = host._stop_text_find(ptrs, _ptr(lens), n, _ptr(buf), len(raw), C.byref(b), C.byref(e))
+    if k < -1:
+        raise ValueError(f"stop_text_find refused: {k}")
+    return k, int(b.value), int(e.value)
+
+
+def _cut_text(host, vocab, new_ids, strings):
+    """the bytes the new ids spell over `vocab` (Fsm.vocab), cut before the first stop string (stop_text_find)"""
+    vb, vo = vocab
+    raw = b"".join(bytes(vb[vo[i]:vo[i + 1]]) for i in new_ids)
+    return raw[:stop_text_find(host, strings, raw)[1]] if strings else raw
+
+
+class JsonSchemaError(ValueError):
+    """.code -1: malformed JSON, .where the byte offset (int, or None); .code -4: outside the subset, .where the offending key's path"""
+
+    def __init__(self, code, where):
+        super().__init__(f"JSON schema refused: {code} at {where!r}")
+        self.code, self.where = code, where
+
+
+def json_schema_regex(host, schema, ws=0, depth=2):
+    import json
+    text = schema if isinstance(schema, (str, bytes)) else json.dumps(schema, ensure_ascii=False)
+    data = _as_bytes(text)
+    if b"\0" in data:
+        raise JsonSchemaError(-1, data.index(b"\0"))
+    err = C.create_string_buffer(1024)
+    n = host._json_schema_regex(data, int(ws), int(depth), None, 0, err, len(err))
+    if n < 0:
+        where = err.value.decode("utf-8", errors="replace")
+        raise JsonSchemaError(int(n), (int(where) if where else None) if n == -1 else where)
+    out = C.create_string_buffer(n + 1)
+    host._json_schema_regex(data, int(ws), int(depth), out, n + 1, err, len(err))
+    return out.value.decode("utf-8")
+
+
 class Fsm:
     """An automaton pool under construction (include/gten_host_fsm.h, host/fsm_build.h): no device needed.  add_stop / add_choices /
     add_table append an automaton and return its start state; a refusal raises ValueError with the builder's code and leaves the
@@ -638,6 +725,25 @@ class Fsm:
 
     def byte_dfa(self, pattern):
         return byte_dfa(self.host, pattern)
+
+    # ---- stop strings as text, JSON schemas (include/gten_host_stoptext.h, include/gten_host_json.h)
+    def add_stop_text(self, strings):
+        """the strings (str as UTF-8, or bytes) as a SEARCH range of the pool: nothing is banned, the id whose bytes complete one of them
+        enters the range's HIT state, which is final; the start state.  Needs set_vocab.  A refusal raises ValueError with the code."""
+        ptrs, lens, n = _byte_strings(strings)
+        rc = self.host._fsm_add_stop_text(self.h, ptrs, _ptr(lens), n)
+        if rc < 0:
+            raise ValueError(f"add_stop_text refused: {rc}")
+        return rc
+
+    @property
+    def n_search(self):
+        return self.host._fsm_n_search(self.h)
+
+    def add_json_schema(self, schema, eos, ws=0, depth=2):
+        """add_regex of json_schema_regex(schema, ws, depth): the start state.  Refusals: JsonSchemaError from the schema, RegexError (-2:
+        too many states) from the pattern."""
+        return self.add_regex(json_schema_regex(self.host, schema, ws, depth), eos)
 
     @property
     def n_states(self):
@@ -1138,6 +1244,27 @@ class HostModel:
         finally:
             f.close()
 
+    def generate_stop_text(self, prompt, max_tokens, strings, vocab, eos=-1, **kw):
+        """generate_fsm() that ends at the first of `strings` (str / bytes; None or empty: not bound) in the NEW text: a pool of that one
+        search range over `vocab` (what Fsm.set_vocab takes) becomes the decoder's pool, expanded on the device.  Nothing is banned; the
+        id that completes a string is kept.  Returns (ids, ended_by, new text as bytes, cut before the string).  kw: generate_fsm's."""
+        f = Fsm(self.host, self.cfg.n_vocab)
+        try:
+            f.set_vocab(vocab)
+            start = -1
+            if strings:
+                start = f.add_stop_text(strings)
+                self.set_fsm(f)
+            ids, ended = self.generate_fsm(prompt, max_tokens, start, eos, **kw)[:2]
+            return ids, ended, _cut_text(self.host, f.vocab, ids[len(prompt):], strings)
+        finally:
+            f.close()
+
+    def generate_json(self, prompt, max_tokens, schema, vocab, eos, ws=0, depth=2, **kw):
+        """generate_regex() of json_schema_regex(schema, ws, depth): the new text is a JSON document that fits the schema, ended by its
+        last byte where nothing can follow (ended_by 2), else by eos"""
+        return self.generate_regex(prompt, max_tokens, json_schema_regex(self.host, schema, ws, depth), vocab, eos, **kw)
+
     def close(self):
         if self.h:
             self.host._free(self.h)
@@ -1550,6 +1677,32 @@ class HostBatch:
             return (*self.serve_fsm(prompts, max_tokens, eos, top_k, temp, seed, starts, **kw), starts)
         finally:
             f.close()
+
+    def serve_stop_text(self, prompts, strings_per_prompt, eos, vocab, max_tokens, top_k=0, temp=1.0, seed=0, **kw):
+        """serve_fsm() with a list of stop strings (or None: not bound) per prompt: a pool of the DISTINCT lists as search ranges over `vocab`
+        becomes the shared decoder's pool, expanded on the device.  Returns serve_fsm()'s tuple with, behind it, each prompt's new text
+        (bytes) cut before its stop string.  kw: serve_fsm's."""
+        f = Fsm(self.host, self.cfg.n_vocab)
+        try:
+            f.set_vocab(vocab)
+            seen, starts = {}, []
+            for strings in strings_per_prompt:
+                key = tuple(_as_bytes(s) for s in strings) if strings else None
+                if key is not None and key not in seen:
+                    seen[key] = f.add_stop_text(strings)
+                starts.append(-1 if key is None else seen[key])
+            if f.n_states > 0:
+                self.set_fsm(f)
+            out = self.serve_fsm(prompts, max_tokens, eos, top_k, temp, seed, starts, **kw)
+            texts = [_cut_text(self.host, f.vocab, ids[len(p):], s) for p, ids, s in zip(prompts, out[0], strings_per_prompt)]
+            return (*out, texts)
+        finally:
+            f.close()
+
+    def serve_json(self, prompts, schemas, eos, vocab, max_tokens, ws=0, depth=2, **kw):
+        """serve_regex() with one schema (or None: not bound) per prompt, each as json_schema_regex(schema, ws, depth)"""
+        patterns = [None if s is None else json_schema_regex(self.host, s, ws, depth) for s in schemas]
+        return self.serve_regex(prompts, patterns, eos, vocab, max_tokens, **kw)
 
     # ---- sessions (include/gten_host_sessions.h, DESIGN.md 3.17)
     # ---- context shift (include/gten_host_shift.h, DESIGN.md 3.20)
