@@ -15,6 +15,8 @@
 #include "gten_hip_continue.h"
 #include "gten_hip_score.h"
 #include "gten_row_logprobs.h"
+#include "gten_hip_embed.h"
+#include "gten_pool_rows.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -1037,6 +1039,72 @@ int gten_hip_row_logprobs(const float* logits, int n_rows, int n_vocab, long lon
     else
         GTR_LAUNCH(KT_ROW_LOGPROBS, k_row_logprobs<false>, dim3(n_rows), dim3(LP_THREADS), 0, logits, n_vocab, row_stride, targets,
                    logprob_out, rank_out, argmax_out);
+    return 0;
+}
+
+// ---- pooling the rows of several texts into one vector per text (include/gten_hip_embed.h; kernels: gten_pool_rows.h)
+// the chunk sums of mean pooling: library-owned, grown on demand, one per stream (as the prompt GEMM's scratch, gten_mfma.hip)
+static int pool_scratch(size_t bytes, float** out)
+{
+    static float* bufs[2] = {nullptr, nullptr};
+    static size_t caps[2] = {0, 0};
+    float*& buf = bufs[stream_index()];
+    size_t& cap = caps[stream_index()];
+    if (bytes > cap) {
+        if (buf) { GTR_CHECK(hipStreamSynchronize(stream())); GTR_CHECK(hipFree(buf)); }
+        buf = nullptr; cap = 0;
+        GTR_CHECK(hipMalloc((void**)&buf, bytes + bytes / 2));
+        cap = bytes + bytes / 2;
+    }
+    *out = buf;
+    return 0;
+}
+
+int gten_hip_pool_rows(const void* x, int dtype, size_t pitch, int n_embd, const int32_t* starts, int n_segments, int pooling,
+                       int normalize, float* out)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(x && starts && out, "pool_rows: null pointer");
+    GTR_REQUIRE(act_dtype_ok(dtype), "pool_rows: bad activation dtype %d", dtype);
+    GTR_REQUIRE(n_embd >= 32 && n_embd <= GTEN_HIP_POOL_MAX_EMBD && n_embd % 32 == 0, "pool_rows: unsupported width %d", n_embd);
+    GTR_REQUIRE(pitch >= gten_hip_row_bytes(dtype, n_embd) && pitch % 2 == 0 && (uintptr_t)x % 2 == 0, "pool_rows: bad pitch %zu or base", pitch);
+    GTR_REQUIRE(n_segments >= 1 && n_segments <= GTEN_HIP_POOL_MAX_SEGMENTS, "pool_rows: bad segment count %d", n_segments);
+    GTR_REQUIRE(pooling == GTEN_HIP_POOL_MEAN || pooling == GTEN_HIP_POOL_LAST, "pool_rows: unknown pooling %d", pooling);
+    GTR_REQUIRE(starts[0] >= 0, "pool_rows: negative first row %d", starts[0]);
+    PoolSegs segs{};
+    segs.n = n_segments;
+    segs.start[0] = starts[0];
+    for (int k = 0; k < n_segments; k++) {
+        const long long len = (long long)starts[k + 1] - starts[k];
+        GTR_REQUIRE(len >= 1 && len <= GTEN_HIP_POOL_MAX_ROWS, "pool_rows: segment %d holds %lld rows", k, len);
+        segs.start[k + 1] = starts[k + 1];
+        segs.chunk0[k + 1] = segs.chunk0[k] + ((int)len + POOL_CHUNK - 1) / POOL_CHUNK;
+    }
+    for (int k = n_segments + 1; k <= GTEN_HIP_POOL_MAX_SEGMENTS; k++) {
+        segs.start[k] = segs.start[n_segments];
+        segs.chunk0[k] = segs.chunk0[n_segments];
+    }
+    const uint8_t* xb = (const uint8_t*)x;
+    float* part = nullptr;
+    size_t smem = (size_t)n_embd * 4;
+    if (pooling == GTEN_HIP_POOL_MEAN) {
+        const int chunks = segs.chunk0[n_segments];
+        if (int rc = pool_scratch((size_t)chunks * n_embd * sizeof(float), &part)) return rc;
+        const dim3 grid(chunks, (n_embd + POOL_TILE - 1) / POOL_TILE);
+        if (dtype == GTEN_Q8)
+            GTR_LAUNCH(KT_ELEMWISE, k_pool_partials<GTEN_Q8>, grid, dim3(GTEN_WAVE), 0, xb, pitch, n_embd, segs, part);
+        else
+            GTR_LAUNCH(KT_ELEMWISE, k_pool_partials<GTEN_F16>, grid, dim3(GTEN_WAVE), 0, xb, pitch, n_embd, segs, part);
+    } else {
+        smem += gten_hip_row_bytes(dtype, n_embd) + 32;                 // the staged last row, misaligned at worst
+    }
+    kv_watch_touch(out, (size_t)n_segments * n_embd * sizeof(float));
+    if (dtype == GTEN_Q8)
+        GTR_LAUNCH(KT_ELEMWISE, k_pool_finish<GTEN_Q8>, dim3(n_segments), dim3(POOL_FIN_THREADS), smem, xb, pitch, n_embd, segs, (const float*)part,
+                   pooling, normalize, out);
+    else
+        GTR_LAUNCH(KT_ELEMWISE, k_pool_finish<GTEN_F16>, dim3(n_segments), dim3(POOL_FIN_THREADS), smem, xb, pitch, n_embd, segs, (const float*)part,
+                   pooling, normalize, out);
     return 0;
 }
 

@@ -141,6 +141,8 @@ class GtenHip:
     BEAM_MAX = 8                                                 # GTEN_HIP_BEAM_MAX
     SHIFT_SYMBOLS = ["gten_hip_kv_shift"]                        # include/gten_hip_shift.h (context shift of K / V caches in place)
     SHIFT_ITEM = np.dtype([("k", np.uint64), ("v", np.uint64), ("n", np.int32), ("keep", np.int32), ("drop", np.int32), ("pad", np.int32)])
+    EMBED_SYMBOLS = ["gten_hip_pool_rows"]                       # include/gten_hip_embed.h (rows of several texts pooled into one vector each)
+    POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HIP_POOL_*
     GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -250,6 +252,7 @@ class GtenHip:
         self._beam_end = _sig(L, "gten_hip_decoder_beam_end", ci, [vp])
         self._beam_info = _sig(L, "gten_hip_decoder_beam_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self._kv_shift = _sig(L, "gten_hip_kv_shift", ci, [vp, ci, ci, sz, ci, ci])
+        self._pool_rows = _sig(L, "gten_hip_pool_rows", ci, [vp, ci, sz, ci, vp, ci, ci, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -726,6 +729,27 @@ class GtenHip:
 
     def permute_sets(self, ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows=1):
         self._check(self.permute_sets_rc(ranges, offset, nbytes, groups, n_groups, state, parent, trellis_rows))
+
+    # -- embeddings: rows pooled into one vector per segment (include/gten_hip_embed.h)
+    def pool_rows_rc(self, dev, dtype, pitch, n_embd, starts, pooling="mean", normalize=True, out=None):
+        """the return code of one gten_hip_pool_rows call (include/gten_hip_embed.h); `starts` holds the segment table, one more
+        entry than there are segments.  out: a DeviceBuffer, by default a scratch with room for whatever an accepted call writes"""
+        a = np.ascontiguousarray(starts, dtype=np.int32)
+        if out is None:
+            if getattr(self, "_pool_out", None) is None:
+                self._pool_out = DeviceBuffer(self, 4 * 32 * 8192)
+            out = self._pool_out
+        code = self.POOLINGS.get(pooling, pooling)
+        return self._pool_rows(dev.ptr if isinstance(dev, DeviceBuffer) else dev, int(dtype), int(pitch), int(n_embd), a.ctypes.data_as(C.c_void_p),
+                               len(a) - 1, int(code), 1 if normalize else 0, out.ptr)
+
+    def pool_rows(self, dev, dtype, pitch, n_embd, starts, pooling="mean", normalize=True):
+        """gten_hip_pool_rows: segment k = rows [starts[k], starts[k + 1]) of the matrix at `dev` (a DeviceBuffer or a device address;
+        dtype Q8 or F16, `pitch` bytes per row) pooled into one vector.  Returns f32 [len(starts) - 1][n_embd]."""
+        T = len(starts) - 1
+        out = DeviceBuffer(self, max(4 * T * n_embd, 64))
+        self._check(self.pool_rows_rc(dev, dtype, pitch, n_embd, starts, pooling, normalize, out))
+        return out.download(np.float32)[: T * n_embd].reshape(T, n_embd).copy()
 
     # -- context shift (include/gten_hip_shift.h)
     def kv_shift_rc(self, items, dtype, pitch, kv_dim, d_head):

@@ -12,6 +12,7 @@
 // --regex holds it to a regular expression over its text, expanded over the vocabulary on the device (include/gten_hip_regex.h);
 // --stop-text ends it at a stop string given as text, a search automaton expanded the same way (include/gten_hip_stoptext.h);
 // --json-schema holds it to a JSON schema, compiled to a pattern of --regex's dialect (host/json_schema.h);
+// --embed FILE prints one pooled, normalised vector per line of FILE (include/gten_host_embed.h, host/embed.h) instead of generating.
 // --ctx-shift lets an answer go on past the window: when it is full the oldest rows behind KEEP are dropped from the K / V caches on the
 // device and the rest re-rotated in place (include/gten_hip_shift.h, host/generate_shift.h).
 #include <algorithm>
@@ -27,6 +28,7 @@
 
 #include "../../include/gten_hip_regex.h"
 #include "../../include/gten_hip_stoptext.h"
+#include "embed.h"
 #include "fsm_build.h"
 #include "json_schema.h"
 #include "generate.h"
@@ -89,6 +91,12 @@ Optional args.
            exceed it (up to 1048576). Whenever the window is full the first KEEP positions stay, the next DROP are dropped [default:
            half of what lies behind KEEP] and the rest slide down. Works with -greedy, top-k, --top-p / --min-p and the penalties.
            Not with --ban, --allow, --logprobs, --stop, --choice, --regex or --score.
+--embed FILE : embed the texts of FILE instead of generating: one text per line (BOS + plain BPE, as --score tokenises; at most --ctx
+           ids each), one output line per text: the vector's values as %.9g, separated by blanks. Not with any generation flag
+           (-greedy, --temp, --topk, --npred, --seed, -p, --ids and everything above that constrains or samples) or --score.
+--pooling mean|last : with --embed: the mean of a text's final-norm rows, or its last row. [default=mean]
+--no-normalize : with --embed: print the pooled vector as it is instead of scaling it to length 1.
+--layer N : with --embed: the final norm applied to the output of block N (1 .. 22) instead of the last block's. [default=0: the last]
 )";
 
 struct Options {
@@ -117,6 +125,10 @@ struct Options {
     bool automaton() const { return !stop.empty() || !choice.empty() || regex_given || json_given || !stop_text.empty(); }
     int shift_keep = -1, shift_drop = 0;                 // --ctx-shift KEEP[,DROP] (keep < 0: off)
     bool shifting() const { return shift_keep >= 0; }
+    std::string embed_path;                              // --embed FILE
+    int pooling = GTEN_HIP_POOL_MEAN, layer = 0;         // --pooling / --layer
+    bool normalize = true, embed_flag = false;           // --no-normalize; one of the three given
+    bool generation_flag = false;                        // any flag that only generation reads
 };
 
 static void emit(const Options& o, Tokenizer& tok, int prev, int id)
@@ -359,6 +371,37 @@ static int run_score(const Options& o, TinyLlama& model, Tokenizer& tok)
     return 0;
 }
 
+// --embed: one text per line as [1] + its plain BPE ids, all of them through embed_many (host/embed.h), one line of values per text
+static int run_embed(const Options& o, TinyLlama& model, Tokenizer& tok)
+{
+    std::ifstream f{o.embed_path, std::ios::binary};
+    if (!f.is_open()) { std::cerr << "error: cannot open " << o.embed_path << ".\n"; return EXIT_FAILURE; }
+    std::vector<int32_t> tokens, starts{0};
+    std::string line;
+    while (std::getline(f, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        const std::vector<int> ids = tok.encode_plain(line);
+        tokens.push_back(1);
+        tokens.insert(tokens.end(), ids.begin(), ids.end());
+        starts.push_back((int32_t)tokens.size());
+    }
+    const int n_texts = (int)starts.size() - 1;
+    std::vector<int> lengths;
+    if (const char* why = embed_texts_ok(model, tokens.data(), starts.data(), n_texts, o.layer, &lengths)) {
+        std::cerr << "--embed: " << why << " (--ctx " << o.ctx << ").\n";
+        return EXIT_FAILURE;
+    }
+    const size_t E = (size_t)model.params.n_embd;
+    std::vector<float> out((size_t)n_texts * E);
+    embed_many(model, tokens.data(), starts.data(), lengths, o.pooling, o.normalize, o.layer, out.data());
+    for (int k = 0; k < n_texts; k++) {
+        for (size_t c = 0; c < E; c++) std::printf(c ? " %.9g" : "%.9g", out[(size_t)k * E + c]);
+        std::printf("\n");
+    }
+    std::fflush(stdout);
+    return 0;
+}
+
 int main(int argc, char const* argv[])
 {
     Options o;
@@ -379,6 +422,21 @@ int main(int argc, char const* argv[])
         else if (arg == "--model") o.model_path = value("model");
         else if (arg == "--tokenizer") o.tokenizer_path = value("tokenizer");
         else if (arg == "--score") o.score_path = value("score");
+        else if (arg == "--embed") o.embed_path = value("embed");
+        else if (arg == "--pooling") {
+            const std::string v = value("pooling");
+            if (v != "mean" && v != "last") { std::cerr << "pooling must be mean or last.\n"; return -1; }
+            o.pooling = v == "mean" ? GTEN_HIP_POOL_MEAN : GTEN_HIP_POOL_LAST;
+            o.embed_flag = true;
+        }
+        else if (arg == "--no-normalize") { o.normalize = false; o.embed_flag = true; }
+        else if (arg == "--layer") {
+            int v = -1;
+            try { v = std::stoi(value("layer")); } catch (...) { std::cerr << "Invalid layer value.\n"; return -1; }
+            if (v < 0 || v > 22) { std::cerr << "layer must be gte 0 and lte 22.\n"; return -1; }
+            o.layer = v;
+            o.embed_flag = true;
+        }
         else if (arg == "--ctx") {
             int v = 0;
             try { v = std::stoi(value("ctx")); } catch (...) { std::cerr << "Invalid ctx value.\n"; return -1; }
@@ -391,16 +449,19 @@ int main(int argc, char const* argv[])
             try { v = std::stoi(value("npred")); } catch (...) { std::cerr << "Invalid npred value.\n"; return -1; }
             if (v < 1 || v > (1 << 20)) { std::cerr << "npred must be greater than 1 and less than 2048.\n"; return -1; }
             o.n_predict = v;
+            o.generation_flag = true;
         } else if (arg == "--temp") {
             float v = 0.f;
             try { v = std::stof(value("temp")); } catch (...) { std::cerr << "Invalid temp value \n"; return -1; }
             if (v <= 0.0f) { std::cerr << "temp value must be greater than zero.\n"; return -1; }
             o.temp = v;
+            o.generation_flag = true;
         } else if (arg == "--topk") {
             int v = 0;
             try { v = std::stoi(value("topk")); } catch (...) { std::cerr << "Invalid topk value.\n"; return -1; }
             if (v < 1 || v > 32003) { std::cerr << "topk must be gte 1 and lte " << 32003 << ".\n"; return -1; }
             o.topk = v;
+            o.generation_flag = true;
         } else if (arg == "--ban") {
             if (!parse_id_list("ban", value("ban"), 32003, &o.ban)) return -1;
         } else if (arg == "--allow") {
@@ -506,6 +567,12 @@ int main(int argc, char const* argv[])
             return EXIT_FAILURE;
         }
     }
+    if (o.embed_flag && o.embed_path.empty()) { std::cerr << "--pooling, --no-normalize and --layer need --embed.\n"; return -1; }
+    if (!o.embed_path.empty() && (o.generation_flag || o.greedy || o.ids || o.seeded || !o.prompt.empty() || o.constrained() || o.min_new > 0 || o.logprobs >= 0 ||
+                                  o.cut_given || o.pen_given || o.last_n > 0 || o.automaton() || o.shifting() || !o.score_path.empty())) {
+        std::cerr << "--embed does not generate: it does not combine with -p, --score, --ids, -greedy or any flag that samples, constrains or extends generation.\n";
+        return -1;
+    }
     if (!o.shifting() && o.n_predict > 2048) { std::cerr << "npred must be greater than 1 and less than 2048.\n"; return -1; }
     if (o.shifting() && (o.constrained() || o.logprobs >= 0 || o.automaton() || !o.score_path.empty())) {
         std::cerr << "--ctx-shift does not combine with --ban, --allow, --logprobs, --stop, --choice, --regex or --score: what they bind by position is not carried through a shift.\n";
@@ -555,10 +622,11 @@ int main(int argc, char const* argv[])
     dtype.wdtype = o.model_dtype;
     dtype.adtype = (o.model_dtype == kFloat16) ? kFloat16 : kQint8;          // tinyllama.cpp:258-265
 
-    TinyLlama model{o.score_path.empty() && !o.shifting() ? o.n_predict : o.ctx, dtype};
+    TinyLlama model{o.score_path.empty() && o.embed_path.empty() && !o.shifting() ? o.n_predict : o.ctx, dtype};
     model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
     if (!o.score_path.empty()) return run_score(o, model, tokenizer);
+    if (!o.embed_path.empty()) return run_embed(o, model, tokenizer);
 
     uint64_t seed = o.seed;
     if (!o.seeded) {

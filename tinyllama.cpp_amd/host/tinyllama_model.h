@@ -86,7 +86,8 @@ public:
 
     // rows [start_pos, n) through the blocks and the final norm, operator by operator (this class drives its own decoder
     // above; with the fast path switched off the modules must not record the row for theirs either -- gten/modules.h)
-    Tensor final_rows(const Tensor& tokens, const int start_pos)
+    // (n_blocks >= 0: only the first n_blocks blocks run, the final norm behind them -- include/gten_host_embed.h, `layer`)
+    Tensor final_rows(const Tensor& tokens, const int start_pos, const int n_blocks = -1)
     {
         struct OpsOnly {
             bool was = detail::fused_rows_enabled();
@@ -94,14 +95,14 @@ public:
             ~OpsOnly() { detail::fused_rows_enabled() = was; }
         } ops_only;
         Tensor x = tok_emb_.forward(tokens, start_pos);
-        for (auto& block : blocks_) x = block.forward(x, start_pos);
+        for (size_t i = 0; i < blocks_in(n_blocks); i++) x = blocks_[i].forward(x, start_pos);
         return norm_.forward(x, start_pos);
     }
 
     // ---- several prompts as ONE row matrix (TinyLlamaBatch::prefill_many; include/gten_hip.h, gten_hip_set_row_segments):
     // rows [starts[k], starts[k + 1]) of `tokens` are prompt k.  Returns the final-norm rows; logits_of_row gives the
     // logits of one of them.  This object's K / V tensors then hold every prompt's rows, at the prompt's rows.
-    Tensor hidden_rows(const Tensor& tokens, const std::vector<int32_t>& starts)
+    Tensor hidden_rows(const Tensor& tokens, const std::vector<int32_t>& starts, const int n_blocks = -1)
     {
         GTEN_ASSERTM(tokens.numel() <= n_ctx_ && (int)starts.size() >= 2 && starts.back() == tokens.numel(), "hidden_rows: %d rows, context %d",
                      tokens.numel(), n_ctx_);
@@ -115,7 +116,7 @@ public:
             ~Segments() { gten_hip_set_row_segments(nullptr, 0); }
         } segments(starts);
         Tensor x = tok_emb_.forward(tokens, 0);
-        for (auto& block : blocks_) x = block.forward(x, 0);
+        for (size_t i = 0; i < blocks_in(n_blocks); i++) x = blocks_[i].forward(x, 0);
         return norm_.forward(x, 0);
     }
     // hidden_rows for prompts that all begin with the SAME prefix_len ids (include/gten_hip_prefix.h): `tokens`
@@ -175,6 +176,18 @@ public:
         return lm_head_.forward(v);                           // EmbeddingLinear computes the last row of what it is given
     }
     AttentionBlock& block(int i) { return blocks_[(size_t)i]; }
+    size_t blocks_in(int n_blocks) const { return n_blocks < 0 ? blocks_.size() : std::min(blocks_.size(), (size_t)n_blocks); }
+    // the second TinyLlama of kScoreRows rows that aliases these weights: the segmented-prompt model of score_many, which
+    // creates it in the same way on first use (host/capi_embed.cpp runs its grouped texts on it)
+    TinyLlama& segment_model()
+    {
+        if (!pre_) {
+            pre_.reset(new TinyLlama(kScoreRows, dtype_, params));
+            pre_->set_fast_decode(false);
+            for (int w = 0; w < n_weights(); w++) pre_->weight(w) = weight(w);
+        }
+        return *pre_;
+    }
 
     // ---- scoring given ids (include/gten_host_score.h): the lm_head over EVERY computed row, in chunks of
     // at most kScoreChunk rows into an f32 scratch this object owns (row pitch padded to 16 bytes), each chunk read by

@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import build as _build
-from .hipabi import GtenHipError, load as _load_hip
+from .hipabi import F16, Q8, GtenHipError, load as _load_hip
 
 
 class HostConfig(C.Structure):
@@ -96,6 +96,9 @@ class GtenHost:
                      "gten_host_batch_shift", "gten_host_batch_kv_read", "gten_host_batch_kv_row_bytes", "gten_host_batch_shift_info",
                      "gten_host_model_shift_info", "gten_host_model_generate_shifting", "gten_host_batch_generate_shifting",
                      "gten_host_batch_session_shift"]
+    # include/gten_host_embed.h (hidden rows of texts and one pooled vector per text, host/capi_embed.cpp; the plan: host/embed_plan.h)
+    EMBED_SYMBOLS = ["gten_host_embed_last_error", "gten_host_embed_plan", "gten_host_model_hidden_many", "gten_host_model_embed_many"]
+    POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HOST_POOL_*
     SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -303,6 +306,10 @@ class GtenHost:
         self._bgen_shift = _sig(L, "gten_host_batch_generate_shifting", ci, [vp, vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, vp, ci, ci, C.c_float, C.c_float,
                                                                              pen, ci, ci, vp, vp])
         self._bsess_shift = _sig(L, "gten_host_batch_session_shift", ci, [vp, ci, ci, ci])
+        self._embed_err = _sig(L, "gten_host_embed_last_error", C.c_char_p, [])
+        self._embed_plan = _sig(L, "gten_host_embed_plan", ci, [vp, ci, ci, vp, vp])
+        self._hidden_many = _sig(L, "gten_host_model_hidden_many", ci, [vp, vp, vp, ci, ci, vp, C.POINTER(ci)])
+        self._embed_many = _sig(L, "gten_host_model_embed_many", ci, [vp, vp, vp, ci, ci, ci, ci, vp])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -322,6 +329,20 @@ class GtenHost:
 
     def shift_phi(self, p, keep, drop):
         return self._shift_phi(int(p), int(keep), int(drop))
+
+    def embed_error(self):
+        """the text of the last refusal by an entry point of include/gten_host_embed.h"""
+        return self._embed_err().decode(errors="replace")
+
+    # -- the embedding calls' plan (host/embed_plan.h): no device needed
+    def embed_plan(self, lengths, seg_ok=True):
+        """(group of every text, [1 where the group is a text that goes alone]) for texts of these lengths; None: no such plan"""
+        a = np.ascontiguousarray(lengths, dtype=np.int32)
+        group_of, alone = np.zeros(max(len(a), 1), np.int32), np.zeros(max(len(a), 1), np.int32)
+        n = self._embed_plan(a.ctypes.data_as(C.c_void_p), len(a), 1 if seg_ok else 0, group_of.ctypes.data_as(C.c_void_p), alone.ctypes.data_as(C.c_void_p))
+        if n < 0:
+            return None
+        return [int(g) for g in group_of[: len(a)]], [int(x) for x in alone[:n]]
 
     def default_config(self, wdtype, adtype):
         cfg = HostConfig()
@@ -937,6 +958,68 @@ class HostModel:
         if rc:
             raise GtenHipError(f"score_many rc={rc}")
         return lp, rk
+
+    @staticmethod
+    def _texts(texts):
+        texts = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in texts]
+        starts = np.zeros(len(texts) + 1, np.int32)
+        starts[1:] = np.cumsum([len(t) for t in texts])
+        toks = np.ascontiguousarray(np.concatenate(texts) if texts else np.zeros(0, np.int32), dtype=np.int32)
+        return (toks if len(toks) else np.zeros(1, np.int32)), starts
+
+    def hidden_many_rc(self, texts, layer=None):
+        """(return code, [(row bytes uint8[len][row bytes], dtype code) per text]) of gten_host_model_hidden_many (include/gten_host_embed.h):
+        every text's rows behind the final norm, in storage form.  layer None: the model's own output."""
+        toks, starts = self._texts(texts)
+        rb = max(self.host.hip.row_bytes(Q8, self.cfg.n_embd), self.host.hip.row_bytes(F16, self.cfg.n_embd))
+        rows = np.zeros((max(int(starts[-1]), 1), rb), np.uint8)
+        dt = C.c_int(-1)
+        rc = self.host._hidden_many(self.h, toks.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), len(texts), 0 if layer is None else int(layer),
+                                    rows.ctypes.data_as(C.c_void_p), C.byref(dt))
+        if rc:
+            return rc, []
+        rb = self.host.hip.row_bytes(dt.value, self.cfg.n_embd)
+        flat = rows.reshape(-1)[: int(starts[-1]) * rb].reshape(-1, rb)
+        return 0, [(flat[starts[k]:starts[k + 1]].copy(), dt.value) for k in range(len(texts))]
+
+    def hidden_many(self, texts, layer=None):
+        """[(row bytes, dtype code) per text]: see hidden_many_rc; rows_to_f32 gives the values"""
+        rc, rows = self.hidden_many_rc(texts, layer)
+        if rc:
+            raise GtenHipError(f"hidden_many rc={rc}: {self.host.embed_error()}")
+        return rows
+
+    @staticmethod
+    def rows_to_f32(rows, dtype):
+        """the f32 values of rows in storage form (uint8 [n][row bytes]): Q8 (float)q * f16_to_f32(delta), one f32 multiply; f16 the conversion"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if dtype == F16:
+            return rows.view(np.float16).astype(np.float32)
+        assert dtype == Q8
+        blk = rows.reshape(rows.shape[0], -1, 34)
+        d = np.ascontiguousarray(blk[:, :, :2]).view(np.float16).astype(np.float32)
+        q = np.ascontiguousarray(blk[:, :, 2:]).view(np.int8).astype(np.float32)
+        return (q * d).astype(np.float32).reshape(rows.shape[0], -1)
+
+    def embed_many_rc(self, texts, pooling="mean", normalize=True, layer=None):
+        """(return code, f32 [len(texts)][n_embd]) of gten_host_model_embed_many: one vector per text, pooled (and normalised) on the device"""
+        toks, starts = self._texts(texts)
+        out = np.zeros((max(len(texts), 1), self.cfg.n_embd), np.float32)
+        code = self.host.POOLINGS.get(pooling, pooling)
+        rc = self.host._embed_many(self.h, toks.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), len(texts), int(code), 1 if normalize else 0,
+                                   0 if layer is None else int(layer), out.ctypes.data_as(C.c_void_p))
+        return rc, out[: len(texts)]
+
+    def embed_many(self, texts, pooling="mean", normalize=True, layer=None):
+        """f32 [len(texts)][n_embd]: see embed_many_rc"""
+        rc, out = self.embed_many_rc(texts, pooling, normalize, layer)
+        if rc:
+            raise GtenHipError(f"embed_many rc={rc}: {self.host.embed_error()}")
+        return out
+
+    def embed(self, ids, pooling="mean", normalize=True, layer=None):
+        """the vector of one text: embed_many([ids])[0]"""
+        return self.embed_many([ids], pooling, normalize, layer)[0]
 
     def set_fast_decode(self, on):
         self.host._setfast(self.h, 1 if on else 0)
