@@ -100,6 +100,19 @@ size_t gten_hip_row_bytes(int dtype, int cols);
 int gten_hip_pack_weight(const void* src_blocks, int dtype, int rows, int cols, void* dst_packed);
 
 /* ---- the ten operators ------------------------------------------------ */
+/* Row views.  Every row matrix below is a bare device pointer and a pitch: row r starts at base + r * pitch, and only its
+ * first gten_hip_row_bytes(dtype, d) bytes belong to the operator -- the bytes up to the pitch may be someone else's columns
+ * (q | k | v and gate | up are column ranges of one wider matrix) and are neither read for a result nor written.  One
+ * alignment contract holds for token_embed, matmul_2d, rms_norm, rotary_emb, silu, mul, add and qkv_attn:
+ *   - Q8 and f16 rows, inputs and outputs alike (a Q8 block begins with an f16 delta, f16 rows are half-words), and the f16
+ *     weights of rms_norm: base and pitch are multiples of 2;
+ *   - f32 outputs of matmul_2d: base and pitch are multiples of 4;  `tokens` (int32): the pointer is a multiple of 4;
+ *   - the weight matrices of matmul_2d and token_embed (whole allocations, read in 16-byte pieces): a multiple of 16.
+ * A call that breaks it is refused (non-zero return, gten_hip_last_error() names the operator) before anything is launched
+ * or written.  Inside the contract every view computes the same rows: the faster forms of an operator (dword and 16-byte
+ * accesses) are taken only when base and pitch are multiples of 4 or 16 as the form needs, and any other view runs the form
+ * written for 2-byte alignment (DESIGN.md lists which).  Dense rows at the start of an allocation always get the fast forms.
+ * gten_hip_copy_ranges takes any alignment (it picks 16-, 4- or 1-byte copies per range). */
 /* ops::token_embed, gten/ops.h:514-564.  tokens: int32[n] on the device. */
 int gten_hip_token_embed(const void* w, int w_dtype, int n_vocab,
                          const int32_t* tokens,

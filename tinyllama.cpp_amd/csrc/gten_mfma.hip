@@ -910,14 +910,16 @@ static int convert_rows(const void* x, size_t x_pitch, int n, int d_in, int star
     uint8_t* buf = nullptr;
     float* da = nullptr;
     if (int rc = act_scratch((size_t)rows * d_in * 2, (size_t)rows * nb * 4, &buf, &da)) return rc;
+    // (the pair kernel reads 17 dwords per pair: it needs 4-byte aligned rows; every other view takes the half-word kernel, which
+    //  writes the same f16 copy -- recorded as KT_VIEW_NARROW, since d_in % 128 == 0 leaves alignment as the only way there)
     const bool x2 = nb % 2 == 0 && x_pitch % 4 == 0 && ((uintptr_t)x % 4) == 0;
     const dim3 grid(x2 ? (rows * (nb / 2) + 255) / 256 : (rows * nb + 255) / 256);
     if (fast) {
         if (x2) GTR_LAUNCH(KT_MATMUL_MFMA, k_act_to_f16_x2<true>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
-        else GTR_LAUNCH(KT_MATMUL_MFMA, k_act_to_f16<true>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
+        else GTR_LAUNCH(KT_VIEW_NARROW, k_act_to_f16<true>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
     } else {
         if (x2) GTR_LAUNCH(KT_MATMUL_MFMA, k_act_to_f16_x2<false>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
-        else GTR_LAUNCH(KT_MATMUL_MFMA, k_act_to_f16<false>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
+        else GTR_LAUNCH(KT_VIEW_NARROW, k_act_to_f16<false>, grid, dim3(256), 0, (const uint8_t*)x, x_pitch, rows, nb, start_pos, (uint4*)buf, da);
     }
     *buf_out = buf; *da_out = da;
     return 0;

@@ -785,6 +785,16 @@ const int* gtr::row_segments(int* n_segments)
 
 static bool act_dtype_ok(int dt) { return dt == GTEN_F16 || dt == GTEN_Q8; }
 
+// ---- the alignment contract of the operators (include/gten_hip.h, "Row views"): a matrix is a base pointer and a pitch, and
+// every row starts at base + r * pitch -- so "every access of width a is aligned" is (base % a == 0 && pitch % a == 0) plus
+// what the kernel adds inside a row.  The entry points REQUIRE 2 (Q8 / f16 rows: the f16 delta of a block and the f16
+// elements are half-words) or 4 (f32 / int32) and refuse the rest; the wider forms are chosen by the same test at 4 or 16,
+// and a view that fails it takes the form written for 2-byte alignment, recorded under KT_VIEW_NARROW.
+static bool rows_al(const void* p, size_t pitch, unsigned a) { return (uintptr_t)p % a == 0 && pitch % a == 0; }
+#define GTR_REQUIRE_ROWS(op, what, p, pitch, a)                                                                                      \
+    GTR_REQUIRE(rows_al(p, pitch, a), "%s: %s needs a base and a pitch that are multiples of %d (base %p, pitch %zu)", op, what, a, \
+                (const void*)(p), (size_t)(pitch))
+
 // ---- self-test of the quantizer's scale arithmetic (see include/gten_hip.h)
 __global__ __launch_bounds__(256) void k_selftest_q8scale(unsigned long long* __restrict__ bad)
 {
@@ -853,6 +863,10 @@ int gten_hip_token_embed(const void* w, int w_dtype, int n_vocab, const int32_t*
     GTR_REQUIRE(d > 0 && d % 32 == 0 && d <= 8192, "token_embed: unsupported width %d", d);
     GTR_REQUIRE(act_dtype_ok(out_dtype), "token_embed: bad output dtype %d", out_dtype);
     GTR_REQUIRE(out_pitch >= gten_hip_row_bytes(out_dtype, d), "token_embed: output pitch too small");
+    // k_embed: int32 ids, bytes and half-words of the table, bytes and half-words of the output rows
+    GTR_REQUIRE((uintptr_t)tokens % 4 == 0, "token_embed: tokens must be 4-byte aligned (%p)", (const void*)tokens);
+    GTR_REQUIRE((uintptr_t)w % 16 == 0, "token_embed: the table must be 16-byte aligned (%p)", w);
+    GTR_REQUIRE_ROWS("token_embed", "the output", out, out_pitch, 2);
     kv_watch_touch(out, (size_t)n * out_pitch);
     const dim3 grid(n - start_pos), block(256);
     if (w_dtype == GTEN_F16) {
@@ -885,20 +899,30 @@ int gten_hip_matmul_2d(const void* x, int x_dtype, size_t x_pitch, const void* w
     GTR_REQUIRE(x_pitch >= gten_hip_row_bytes(x_dtype, d_in), "matmul_2d: input pitch too small");
     GTR_REQUIRE(out_pitch >= gten_hip_row_bytes(out_dtype, d_out), "matmul_2d: output pitch too small");
     GTR_REQUIRE(n - start_pos <= 65535, "matmul_2d: too many new rows");
+    // every kernel below reads the weights in 16-byte pieces, the input rows as half-words at least, and writes bytes and
+    // half-words (Q8), half-words (f16) or dwords (f32)
+    GTR_REQUIRE((uintptr_t)w % 16 == 0, "matmul_2d: the weights must be 16-byte aligned (%p)", w);
+    GTR_REQUIRE_ROWS("matmul_2d", "the input", x, x_pitch, 2);
+    GTR_REQUIRE_ROWS("matmul_2d", out_dtype == GTEN_F32 ? "an f32 output" : "the output", out, out_pitch, out_dtype == GTEN_F32 ? 4 : 2);
     kv_watch_touch(out, (size_t)n * out_pitch);       // (the key / value projections write the K / V caches: gten/modules.cpp:188-201)
     // prefill-sized calls go to the matrix cores (gten_mfma.hip); the row-per-workgroup
     // kernel below streams the weights once per row and is meant for a handful of rows
-    if (n - start_pos >= GTEN_MFMA_MIN_ROWS && d_in % 128 == 0)   // the MFMA kernel stages 4 quant blocks at a time
+    const bool mfma_shape = n - start_pos >= GTEN_MFMA_MIN_ROWS && d_in % 128 == 0;   // the MFMA kernel stages 4 quant blocks at a time
+    // f16 weights: the MFMA kernel reads the caller's rows themselves, in 16-byte pieces at row * pitch + 16 c (quantized
+    // weights read a copy the library makes: gten_mfma.hip picks the conversion kernel by the same test at 4)
+    const bool mfma_al = x_dtype != GTEN_F16 || rows_al(x, x_pitch, 16);
+    if (mfma_shape && mfma_al)
         return gten_launch_matmul_mfma(x, x_dtype, x_pitch, w, w_dtype, out, out_dtype, out_pitch, n, d_in, d_out, start_pos);
+    const int tag = mfma_shape ? KT_VIEW_NARROW : KT_MATMUL;
     const dim3 grid((d_out + 31) / 32, n - start_pos), block(256);
     const size_t act = (w_dtype == GTEN_F16) ? (size_t)d_in * 4 : (size_t)(d_in / 32) * 40;
     const size_t smem = 128 + act;
     if (w_dtype == GTEN_F16)
-        GTR_LAUNCH(KT_MATMUL, (k_matmul<GTEN_F16>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
+        GTR_LAUNCH(tag, (k_matmul<GTEN_F16>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
     else if (w_dtype == GTEN_Q8)
-        GTR_LAUNCH(KT_MATMUL, (k_matmul<GTEN_Q8>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
+        GTR_LAUNCH(tag, (k_matmul<GTEN_Q8>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
     else
-        GTR_LAUNCH(KT_MATMUL, (k_matmul<GTEN_Q4>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
+        GTR_LAUNCH(tag, (k_matmul<GTEN_Q4>), grid, block, smem, (const uint8_t*)x, x_pitch, w, (uint8_t*)out, out_dtype, out_pitch, d_in, d_out, start_pos);
     return 0;
 }
 
@@ -909,7 +933,13 @@ static int check_rowwise(const char* op, const void* a, const void* out, int dty
     GTR_REQUIRE(n > 0 && start_pos >= 0 && start_pos < n, "%s: bad rows n=%d start_pos=%d", op, n, start_pos);
     GTR_REQUIRE(d > 0 && d % 32 == 0 && d <= 12288, "%s: unsupported width %d", op, d);
     GTR_REQUIRE(pitch >= gten_hip_row_bytes(dtype, d), "%s: pitch too small", op);
+    GTR_REQUIRE_ROWS(op, "the input", a, pitch, 2);
     return 0;
+}
+// silu / mul / add with n - start_pos rows of d elements: big enough for the block-pair / eight-element kernels
+static bool elementwise_wide_shape(int dtype, int rows, int d)
+{
+    return (size_t)rows * d >= 32768 && (dtype == GTEN_Q8 ? (d / 32) % 2 == 0 : d % 8 == 0);
 }
 
 int gten_hip_rms_norm(const void* x, int dtype, size_t x_pitch, const void* w_f16,
@@ -918,13 +948,16 @@ int gten_hip_rms_norm(const void* x, int dtype, size_t x_pitch, const void* w_f1
     GTR_NEED_INIT();
     if (int rc = check_rowwise("rms_norm", x, out, dtype, x_pitch, n, d, start_pos)) return rc;
     GTR_REQUIRE(w_f16 && out_pitch >= gten_hip_row_bytes(dtype, d), "rms_norm: bad weight/output");
+    GTR_REQUIRE((uintptr_t)w_f16 % 2 == 0, "rms_norm: the weights must be 2-byte aligned (%p)", w_f16);
+    GTR_REQUIRE_ROWS("rms_norm", "the output", out, out_pitch, 2);
     kv_watch_touch(out, (size_t)n * out_pitch);
-    if (n - start_pos >= 4 && rms_norm_q8w_ok(x, x_pitch, w_f16, out, out_pitch, dtype, d)) {
+    const bool wave_shape = n - start_pos >= 4 && dtype == GTEN_Q8 && d == 2048;
+    if (wave_shape && rms_norm_q8w_ok(x, x_pitch, w_f16, out, out_pitch, dtype, d)) {
         GTR_LAUNCH(KT_RMSNORM, k_rms_norm_q8w, dim3(n - start_pos), dim3(64), 0, (const uint8_t*)x, x_pitch, (const uint16_t*)w_f16, (uint8_t*)out, out_pitch,
                    start_pos, (uint4*)nullptr);
         return 0;
     }
-    GTR_LAUNCH(KT_RMSNORM, k_rms_norm, dim3(n - start_pos), dim3(256), 64 + (size_t)d * 4,
+    GTR_LAUNCH(wave_shape ? KT_VIEW_NARROW : KT_RMSNORM, k_rms_norm, dim3(n - start_pos), dim3(256), 64 + (size_t)d * 4,
                        (const uint8_t*)x, dtype, x_pitch, (const uint16_t*)w_f16, (uint8_t*)out, out_pitch, d, start_pos, (_Float16*)nullptr);
     return 0;
 }
@@ -939,11 +972,12 @@ int gten_hip_rotary_emb(void* x, int dtype, size_t pitch, int n, int d, int d_he
     kv_watch_touch(x, (size_t)n * pitch);             // (K is rotated in place in its cache: gten/modules.cpp:199)
     const float2* table = nullptr;
     if (int rc = rope_table(d_head, &table)) return rc;
-    if (n - start_pos >= 4 && rope_q8w_ok(x, pitch, dtype, d, d_head)) {
+    const bool wave_shape = n - start_pos >= 4 && dtype == GTEN_Q8 && d_head == 64 && d % 64 == 0 && d <= 2048;
+    if (wave_shape && rope_q8w_ok(x, pitch, dtype, d, d_head)) {
         GTR_LAUNCH(KT_ROPE, k_rope2_q8w, dim3(n - start_pos, 1), dim3(64), 0, (uint8_t*)x, pitch, d / 32, (uint8_t*)x, pitch, 0, start_pos, table);
         return 0;
     }
-    GTR_LAUNCH(KT_ROPE, k_rope, dim3(n - start_pos), dim3(256), (size_t)d * 4, (uint8_t*)x, dtype, pitch, d, d_head, start_pos, table);
+    GTR_LAUNCH(wave_shape ? KT_VIEW_NARROW : KT_ROPE, k_rope, dim3(n - start_pos), dim3(256), (size_t)d * 4, (uint8_t*)x, dtype, pitch, d, d_head, start_pos, table);
     return 0;
 }
 
@@ -951,10 +985,11 @@ int gten_hip_silu(const void* x, void* out, int dtype, size_t pitch, int n, int 
 {
     GTR_NEED_INIT();
     if (int rc = check_rowwise("silu", x, out, dtype, pitch, n, d, start_pos)) return rc;
+    GTR_REQUIRE_ROWS("silu", "the output", out, pitch, 2);
     kv_watch_touch(out, (size_t)n * pitch);
     if (elementwise_q8x2_ok(x, nullptr, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_q8x2<EW_SILU>(x, nullptr, out, pitch, n, d, start_pos);
     if (elementwise_f16x8_ok(x, nullptr, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_f16x8<EW_SILU>(x, nullptr, out, pitch, n, d, start_pos);
-    GTR_LAUNCH(KT_ELEMWISE, (k_elementwise<EW_SILU>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
+    GTR_LAUNCH(elementwise_wide_shape(dtype, n - start_pos, d) ? KT_VIEW_NARROW : KT_ELEMWISE, (k_elementwise<EW_SILU>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
                        (const uint8_t*)x, (const uint8_t*)nullptr, (uint8_t*)out, dtype, pitch, d, start_pos);
     return 0;
 }
@@ -964,10 +999,12 @@ int gten_hip_mul(const void* a, const void* b, void* out, int dtype, size_t pitc
     GTR_NEED_INIT();
     if (int rc = check_rowwise("mul", a, out, dtype, pitch, n, d, start_pos)) return rc;
     GTR_REQUIRE(b, "mul: null pointer");
+    GTR_REQUIRE_ROWS("mul", "the second input", b, pitch, 2);
+    GTR_REQUIRE_ROWS("mul", "the output", out, pitch, 2);
     kv_watch_touch(out, (size_t)n * pitch);
     if (elementwise_q8x2_ok(a, b, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_q8x2<EW_MUL>(a, b, out, pitch, n, d, start_pos);
     if (elementwise_f16x8_ok(a, b, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_f16x8<EW_MUL>(a, b, out, pitch, n, d, start_pos);
-    GTR_LAUNCH(KT_ELEMWISE, (k_elementwise<EW_MUL>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
+    GTR_LAUNCH(elementwise_wide_shape(dtype, n - start_pos, d) ? KT_VIEW_NARROW : KT_ELEMWISE, (k_elementwise<EW_MUL>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
                        (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, dtype, pitch, d, start_pos);
     return 0;
 }
@@ -977,10 +1014,12 @@ int gten_hip_add(const void* a, const void* b, void* out, int dtype, size_t pitc
     GTR_NEED_INIT();
     if (int rc = check_rowwise("add", a, out, dtype, pitch, n, d, start_pos)) return rc;
     GTR_REQUIRE(b, "add: null pointer");
+    GTR_REQUIRE_ROWS("add", "the second input", b, pitch, 2);
+    GTR_REQUIRE_ROWS("add", "the output", out, pitch, 2);
     kv_watch_touch(out, (size_t)n * pitch);
     if (elementwise_q8x2_ok(a, b, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_q8x2<EW_ADD>(a, b, out, pitch, n, d, start_pos);
     if (elementwise_f16x8_ok(a, b, out, dtype, pitch, n - start_pos, d)) return launch_elementwise_f16x8<EW_ADD>(a, b, out, pitch, n, d, start_pos);
-    GTR_LAUNCH(KT_ELEMWISE, (k_elementwise<EW_ADD>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
+    GTR_LAUNCH(elementwise_wide_shape(dtype, n - start_pos, d) ? KT_VIEW_NARROW : KT_ELEMWISE, (k_elementwise<EW_ADD>), dim3(n - start_pos), dim3(256), (size_t)d * 4,
                        (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, dtype, pitch, d, start_pos);
     return 0;
 }
@@ -1122,19 +1161,27 @@ int gten_hip_qkv_attn(const void* q, const void* k, const void* v, void* out, in
     GTR_REQUIRE(q_pitch >= gten_hip_row_bytes(dtype, n_heads * d_head) && out_pitch >= gten_hip_row_bytes(dtype, n_heads * d_head) &&
                 kv_pitch >= gten_hip_row_bytes(dtype, n_kv_heads * d_head), "qkv_attn: pitch too small");
     GTR_REQUIRE(n - start_pos <= 65535 && n <= 12288, "qkv_attn: context %d too long for this kernel", n);
+    GTR_REQUIRE_ROWS("qkv_attn", "q", q, q_pitch, 2);
+    GTR_REQUIRE_ROWS("qkv_attn", "k", k, kv_pitch, 2);
+    GTR_REQUIRE_ROWS("qkv_attn", "v", v, kv_pitch, 2);
+    GTR_REQUIRE_ROWS("qkv_attn", "the output", out, out_pitch, 2);
     kv_watch_touch(out, (size_t)n * out_pitch);
-    if (dtype == GTEN_Q8 && d_head == 64 && n - start_pos >= GTEN_ATTN_TILED_MIN_ROWS) {
+    const bool tiled_shape = d_head == 64 && n - start_pos >= GTEN_ATTN_TILED_MIN_ROWS;
+    // Q8: the tiled kernel is written for 2-byte alignment -- its 8- and 16-byte loads of quants are declared align 2 (a
+    // block's quants start 2 bytes into its 34: dense rows already put them at every even residue of 16), its stores are
+    // bytes and half-words: the contract above is its whole requirement
+    if (dtype == GTEN_Q8 && tiled_shape) {
         // prompt processing: 32 rows of a head per workgroup, int8 MFMA scores (same bytes as k_attn below)
         // (fewer than 16 new rows take the row kernel: tests reach it for long inputs by calling in 15-row pieces)
         return gten_launch_attn_tiled(q, k, v, out, q_pitch, kv_pitch, out_pitch, n, n_heads, n_kv_heads, start_pos);
     }
-    if (dtype == GTEN_F16 && d_head == 64 && n - start_pos >= GTEN_ATTN_TILED_MIN_ROWS && q_pitch % 16 == 0 && kv_pitch % 16 == 0 &&
-        ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)out % 4 == 0) && out_pitch % 4 == 0) {
+    // f16: 16-byte loads of q, k and v rows, dword stores of the output
+    if (dtype == GTEN_F16 && tiled_shape && rows_al(q, q_pitch, 16) && rows_al(k, kv_pitch, 16) && rows_al(v, kv_pitch, 16) && rows_al(out, out_pitch, 4)) {
         return gten_launch_attn_tiled_f16(q, k, v, out, q_pitch, kv_pitch, out_pitch, n, n_heads, n_kv_heads, start_pos);
     }
     const int p_cap = (n + 31) & ~31;
     const size_t smem = (size_t)(16 + d_head + 8 + d_head + 256 + p_cap) * 4;
-    GTR_LAUNCH(KT_ATTN, k_attn, dim3(n_heads, n - start_pos), dim3(256), smem,
+    GTR_LAUNCH(tiled_shape ? KT_VIEW_NARROW : KT_ATTN, k_attn, dim3(n_heads, n - start_pos), dim3(256), smem,
                        (const uint8_t*)q, (const uint8_t*)k, (const uint8_t*)v, (uint8_t*)out, dtype,
                        q_pitch, kv_pitch, out_pitch, n_heads, n_kv_heads, d_head, start_pos, p_cap);
     return 0;

@@ -60,7 +60,9 @@ bool kv_watch_overlaps(const void* p, size_t bytes, const void* except);
 enum {
     KT_PACK = 0, KT_EMBED, KT_MATMUL, KT_RMSNORM, KT_ROPE, KT_ELEMWISE, KT_ATTN,
     KT_DEC_GEMV_QKV, KT_DEC_ATTN_SCORE, KT_DEC_ATTN_PV, KT_DEC_GEMV_O, KT_DEC_GEMV_GATEUP, KT_DEC_GEMV_DOWN,
-    KT_DEC_GEMV_HEAD, KT_DEC_ARGMAX, KT_MATMUL_MFMA, KT_DEC_STAGE, KT_ATTN_TILED, KT_DEC_PERSIST, KT_DEC_SAMPLE, KT_ROW_LOGPROBS, KT_COUNT
+    KT_DEC_GEMV_HEAD, KT_DEC_ARGMAX, KT_MATMUL_MFMA, KT_DEC_STAGE, KT_ATTN_TILED, KT_DEC_PERSIST, KT_DEC_SAMPLE, KT_ROW_LOGPROBS,
+    KT_VIEW_NARROW,    // a call whose SHAPE picks a wide form (dword / 16-byte accesses) but whose view lacks the alignment: the 2-byte form ran
+    KT_COUNT
 };
 
 // gten_mfma.hip: ops::matmul_2d for >= GTEN_MFMA_MIN_ROWS new rows

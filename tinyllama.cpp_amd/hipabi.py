@@ -57,6 +57,10 @@ class DeviceBuffer:
     def zero(self, byte=0):
         self.api._check(self.api._memset(self.ptr, byte, self.nbytes))
 
+    def view(self, offset):
+        """the bytes from `offset` on as an operand: every operator method takes it where it takes a buffer"""
+        return DeviceView(self, offset)
+
     def free(self):
         if self.ptr:
             self.api._check(self.api._free(self.ptr))
@@ -67,6 +71,26 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceView:
+    """An address inside a DeviceBuffer: `.ptr` is parent.ptr + offset.  Owns nothing; holds its parent so that the
+    allocation outlives every view of it."""
+
+    def __init__(self, parent, offset):
+        offset = int(offset)
+        if not 0 <= offset <= parent.nbytes:
+            raise ValueError(f"view at {offset} of a buffer of {parent.nbytes} bytes")
+        self.parent = parent
+        self.offset = offset
+        self.nbytes = parent.nbytes - offset
+
+    @property
+    def ptr(self):
+        return self.parent.ptr + self.offset
+
+    def view(self, offset):
+        return DeviceView(self.parent, self.offset + int(offset))
 
 
 class BlockDesc(C.Structure):
@@ -293,10 +317,14 @@ class GtenHip:
 
     def copy_ranges(self, ranges):
         """ranges: [(dst_ptr, src_ptr, nbytes)] device-to-device, one launch"""
+        self._check(self.copy_ranges_rc(ranges))
+
+    def copy_ranges_rc(self, ranges):
+        """the return code of one gten_hip_copy_ranges call (a null address is passed as it is: the library refuses it)"""
         class R(C.Structure):
             _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("bytes", C.c_size_t)]
-        arr = (R * len(ranges))(*[R(int(d), int(s), int(b)) for d, s, b in ranges])
-        self._check(self._copy_ranges(C.cast(arr, C.c_void_p), len(ranges)))
+        arr = (R * max(len(ranges), 1))(*[R(int(d) or None, int(s) or None, int(b)) for d, s, b in ranges])
+        return self._copy_ranges(C.cast(arr, C.c_void_p), len(ranges))
 
     def sample_rows(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed, stream, position):
         """ids of gten_hip_sample_rows (include/gten_hip_sample.h): `logits` a DeviceBuffer of f32 rows, row r at r * row_stride
@@ -998,37 +1026,65 @@ class GtenHip:
         src.free()
         return dst
 
-    # -- operators (DeviceBuffers; pitches default to dense rows)
-    def token_embed(self, w, w_dtype, n_vocab, tokens, out, out_dtype, n, d, start_pos=0, out_pitch=None):
-        self._check(self._embed(w.ptr, w_dtype, n_vocab, tokens.ptr, out.ptr, out_dtype,
-                                out_pitch or self.row_bytes(out_dtype, d), n, d, start_pos))
+    # -- operators (DeviceBuffers or views of them; pitches default to dense rows).  The `_rc` forms return the code of the
+    #    call instead of raising (0 = done; otherwise last_error() names the operator): what a refusal test reads
+    def token_embed_rc(self, w, w_dtype, n_vocab, tokens, out, out_dtype, n, d, start_pos=0, out_pitch=None):
+        return self._embed(w.ptr, w_dtype, n_vocab, tokens.ptr, out.ptr, out_dtype,
+                           self.row_bytes(out_dtype, d) if out_pitch is None else out_pitch, n, d, start_pos)
 
-    def matmul_2d(self, x, x_dtype, w, w_dtype, out, out_dtype, n, d_in, d_out, start_pos=0,
-                  x_pitch=None, out_pitch=None):
-        self._check(self._matmul(x.ptr, x_dtype, x_pitch or self.row_bytes(x_dtype, d_in), w.ptr, w_dtype,
-                                 out.ptr, out_dtype, out_pitch or self.row_bytes(out_dtype, d_out),
-                                 n, d_in, d_out, start_pos))
+    def token_embed(self, *a, **kw):
+        self._check(self.token_embed_rc(*a, **kw))
 
-    def rms_norm(self, x, dtype, w, out, n, d, start_pos=0):
+    def matmul_2d_rc(self, x, x_dtype, w, w_dtype, out, out_dtype, n, d_in, d_out, start_pos=0,
+                     x_pitch=None, out_pitch=None):
+        return self._matmul(x.ptr, x_dtype, self.row_bytes(x_dtype, d_in) if x_pitch is None else x_pitch, w.ptr, w_dtype,
+                            out.ptr, out_dtype, self.row_bytes(out_dtype, d_out) if out_pitch is None else out_pitch,
+                            n, d_in, d_out, start_pos)
+
+    def matmul_2d(self, *a, **kw):
+        self._check(self.matmul_2d_rc(*a, **kw))
+
+    def rms_norm_rc(self, x, dtype, w, out, n, d, start_pos=0, x_pitch=None, out_pitch=None):
         p = self.row_bytes(dtype, d)
-        self._check(self._rms(x.ptr, dtype, p, w.ptr, out.ptr, p, n, d, start_pos))
+        return self._rms(x.ptr, dtype, p if x_pitch is None else x_pitch, w.ptr, out.ptr, p if out_pitch is None else out_pitch,
+                         n, d, start_pos)
 
-    def rotary_emb(self, x, dtype, n, d, d_head, start_pos=0):
-        self._check(self._rope(x.ptr, dtype, self.row_bytes(dtype, d), n, d, d_head, start_pos))
+    def rms_norm(self, *a, **kw):
+        self._check(self.rms_norm_rc(*a, **kw))
 
-    def silu(self, x, out, dtype, n, d, start_pos=0):
-        self._check(self._silu(x.ptr, out.ptr, dtype, self.row_bytes(dtype, d), n, d, start_pos))
+    def rotary_emb_rc(self, x, dtype, n, d, d_head, start_pos=0, pitch=None):
+        return self._rope(x.ptr, dtype, self.row_bytes(dtype, d) if pitch is None else pitch, n, d, d_head, start_pos)
 
-    def mul(self, a, b, out, dtype, n, d, start_pos=0):
-        self._check(self._mul(a.ptr, b.ptr, out.ptr, dtype, self.row_bytes(dtype, d), n, d, start_pos))
+    def rotary_emb(self, *a, **kw):
+        self._check(self.rotary_emb_rc(*a, **kw))
 
-    def add(self, a, b, out, dtype, n, d, start_pos=0):
-        self._check(self._add(a.ptr, b.ptr, out.ptr, dtype, self.row_bytes(dtype, d), n, d, start_pos))
+    def silu_rc(self, x, out, dtype, n, d, start_pos=0, pitch=None):
+        return self._silu(x.ptr, out.ptr, dtype, self.row_bytes(dtype, d) if pitch is None else pitch, n, d, start_pos)
 
-    def qkv_attn(self, q, k, v, out, dtype, n, n_heads, n_kv_heads, d_head, start_pos=0):
+    def silu(self, *a, **kw):
+        self._check(self.silu_rc(*a, **kw))
+
+    def mul_rc(self, a, b, out, dtype, n, d, start_pos=0, pitch=None):
+        return self._mul(a.ptr, b.ptr, out.ptr, dtype, self.row_bytes(dtype, d) if pitch is None else pitch, n, d, start_pos)
+
+    def mul(self, *a, **kw):
+        self._check(self.mul_rc(*a, **kw))
+
+    def add_rc(self, a, b, out, dtype, n, d, start_pos=0, pitch=None):
+        return self._add(a.ptr, b.ptr, out.ptr, dtype, self.row_bytes(dtype, d) if pitch is None else pitch, n, d, start_pos)
+
+    def add(self, *a, **kw):
+        self._check(self.add_rc(*a, **kw))
+
+    def qkv_attn_rc(self, q, k, v, out, dtype, n, n_heads, n_kv_heads, d_head, start_pos=0, q_pitch=None, kv_pitch=None,
+                    out_pitch=None):
         qp = self.row_bytes(dtype, n_heads * d_head)
         kp = self.row_bytes(dtype, n_kv_heads * d_head)
-        self._check(self._attn(q.ptr, k.ptr, v.ptr, out.ptr, dtype, qp, kp, qp, n, n_heads, n_kv_heads, d_head, start_pos))
+        return self._attn(q.ptr, k.ptr, v.ptr, out.ptr, dtype, qp if q_pitch is None else q_pitch, kp if kv_pitch is None else kv_pitch,
+                          qp if out_pitch is None else out_pitch, n, n_heads, n_kv_heads, d_head, start_pos)
+
+    def qkv_attn(self, *a, **kw):
+        self._check(self.qkv_attn_rc(*a, **kw))
 
 
 _api = None
