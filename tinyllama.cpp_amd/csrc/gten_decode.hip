@@ -33,6 +33,7 @@
 #include "gten_hip_regex.h"
 #include "gten_hip_stoptext.h"
 #include "gten_hip_ab.h"
+#include "gten_hip_oplanes.h"
 #include "gten_hip_prefix_decode.h"
 #include "gten_hip_prefixes.h"
 #include "gten_hip_groups.h"
@@ -105,6 +106,7 @@ enum { EPI_RAW = 0, EPI_SILUMUL = 1, EPI_STAGE = 2, EPI_STAGE_FRAG = 3 };
 
 #define WXP_PLANES 8             // K planes of k_dec_wxp_f16 (gten_decode_wxp.h), added by the staging launches
 #include "gten_decode_wx.h"
+#include "gten_decode_oplanes.h"
 #include "gten_decode_wide_wx.h"
 #include "gten_decode_ffn.h"
 #include "gten_decode_wxp.h"
@@ -225,6 +227,7 @@ struct gten_hip_decoder {
     // kernels, their arguments and therefore the results are those of a 64-sequence decoder.
     bool exact = false;               // gten_hip_set_decode_exact at creation
     int attn_classic = 0;             // gten_hip_set_decode_attn_classic at creation (0 / 1 / 2)
+    bool o_planes = false;            // the o launch as K-quarter planes (gten_decode_oplanes.h); chosen at creation (decoder_build)
     bool persist_on = false;          // gten_hip_set_decode_persistent at creation: the step as ONE persistent launch (gten_decode_persist.h)
     struct PersistState* persist = nullptr;
     // the W.x launches whose weights are requested with the default cache policy (host/resident_plan.h), in step order: per layer
@@ -411,6 +414,25 @@ extern "C" int gten_hip_set_decode_attn_classic(int v)
 {
     GTR_REQUIRE(v >= 0 && v <= 2, "gten_hip_set_decode_attn_classic: %d is not 0, 1 or 2", v);
     g_attn_classic = v;
+    return 0;
+}
+// decoders created AFTERWARDS run the o launch of the single-sequence fast step as k_dec_o_planes (1) or as k_dec_gemv8<.., PRO_ATTW, ..>
+// (0, the A/B control) -- the same bytes (include/gten_hip_oplanes.h); where the planes do not apply a decoder keeps 0 whatever this says
+#ifndef GTEN_O_PLANES_DEFAULT
+#define GTEN_O_PLANES_DEFAULT 1
+#endif
+static int g_o_planes = GTEN_O_PLANES_DEFAULT;
+extern "C" int gten_hip_set_decode_o_planes(int v)
+{
+    GTR_REQUIRE(v == 0 || v == 1, "gten_hip_set_decode_o_planes: %d is not 0 or 1", v);
+    g_o_planes = v;
+    return 0;
+}
+extern "C" int gten_hip_decode_o_planes(void) { return g_o_planes; }
+extern "C" int gten_hip_decoder_o_planes(gten_hip_decoder* dc, int* planes)
+{
+    GTR_REQUIRE(dc, "decoder_o_planes: null decoder");
+    if (planes) *planes = dc->o_planes ? 1 : 0;
     return 0;
 }
 
@@ -739,15 +761,38 @@ static int launch_gemv8(int tag, const Gemv8Args& a, int total_rows, bool keep)
 }
 
 // gate + up projections with the silu*up chain in the epilogue: one workgroup per 32-wide FFN slice
+// planes: res_raw holds OPL_PLANES K planes (the o launch was k_dec_o_planes)
 template <int WT>
-static int launch_gateup8(const Gemv8Args& a, int n_ffn, bool keep)
+static int launch_gateup8(const Gemv8Args& a, int n_ffn, bool keep, bool planes)
 {
     const dim3 grid(n_ffn / 32), block(512);
     GTR_REQUIRE(n_ffn % 32 == 0, "decoder: n_ffn %d is not a multiple of 32", n_ffn);
     const GemvHotWords hw = hot_of_gemv8<WT, PRO_RESID>(a);
+    if constexpr (WT != GTEN_F16) if (planes) {
+        if (keep) DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, 1, 8, EPI_SILUMUL, 512, 0, WLD_KEEP, OPL_PLANES>), grid, block, stage_bytes(a.d_in), hw, a);
+        else DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, 1, 8, EPI_SILUMUL, 512, 0, WLD_NT, OPL_PLANES>), grid, block, stage_bytes(a.d_in), hw, a);
+        return 0;
+    }
     if (keep) DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, (WT == GTEN_F16 ? 4 : 1), 8, EPI_SILUMUL, 512, 0, WLD_KEEP>), grid, block, stage_bytes(a.d_in), hw, a);
     else DEC_LAUNCH_HOT(KT_DEC_GEMV_GATEUP, (k_dec_gemv8<WT, PRO_RESID, (WT == GTEN_F16 ? 4 : 1), 8, EPI_SILUMUL, 512>), grid, block, stage_bytes(a.d_in), hw, a);
     return 0;
+}
+
+// the o projection as four K-quarter planes (gten_decode_oplanes.h): one workgroup per (32 rows, quarter)
+template <int WT>
+static int launch_o_planes(const Gemv8Args& a, bool keep)
+{
+    if constexpr (WT == GTEN_F16) return fail(-4, "decoder: the o planes want quantized weights");
+    else {
+        GTR_REQUIRE(a.d_in == OPL_E && a.rows[0] == OPL_E && a.d_head == 64 && a.n_chunks >= 1 && a.n_chunks <= DEC_ATT_MAXCH,
+                    "decoder: the o planes want n_embd %d and d_head 64 (got %d, %d)", OPL_E, a.d_in, a.d_head);
+        const dim3 grid(OPL_E / 32 * OPL_PLANES), block(512);
+        const unsigned long long w[6] = {(unsigned long long)(uintptr_t)a.att_part, (unsigned long long)(uintptr_t)a.att_stats, (unsigned long long)(uintptr_t)a.qs[0],
+                                         (unsigned long long)(uintptr_t)a.step, (unsigned long long)(uintptr_t)a.out, (unsigned long long)(unsigned)a.n_chunks};
+        if (keep) DEC_LAUNCH(KT_DEC_GEMV_O, (k_dec_o_planes<WT, WLD_KEEP>), grid, block, OPL_LDS, w[0], w[1], w[2], w[3], w[4], w[5]);
+        else DEC_LAUNCH(KT_DEC_GEMV_O, (k_dec_o_planes<WT, WLD_NT>), grid, block, OPL_LDS, w[0], w[1], w[2], w[3], w[4], w[5]);
+        return 0;
+    }
 }
 
 static void set_mat(Gemv8Args& a, int k, const void* w, int wdtype, int rows, int cols)
@@ -808,14 +853,16 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
         // 256): q|k|v 1 row 0.510, on 256 threads 0.500; o 1 row 0.4845 (3.90 against 4.22 us per launch: every CU gets a workgroup),
         // 4 rows 0.512, 1 row on 256 threads 0.504, 2 rows on 256 threads 0.489; down 1 row 0.494, 1 row on 512 threads 0.496;
         // lm_head 4 / 8 / 16 rows per wave 0.486 / 0.488 / 0.487 (then, with o at 1 row)
-        rc = attention_one_pass(dh) ? launch_gemv8<WT, PRO_ATTW, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1))
-                                    : launch_gemv8<WT, PRO_ATT, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1));
+        // (o as four K-quarter planes where the decoder chose them at creation: 3.51 us per launch as one plane)
+        rc = dc->o_planes           ? launch_o_planes<WT>(o, keep(l4 + 1))
+             : attention_one_pass(dh) ? launch_gemv8<WT, PRO_ATTW, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1))
+                                      : launch_gemv8<WT, PRO_ATT, NE, 1, 512, 1>(KT_DEC_GEMV_O, o, E, keep(l4 + 1));
         if (rc) return rc;
         Gemv8Args gu{};
         gu.step = dc->step; gu.d_in = E; gu.n_mats = 2; set_mat(gu, 0, L.wgate, WT, F, E); set_mat(gu, 1, L.wup, WT, F, E);
         gu.res_a = xbuf; gu.res_raw = dc->proj_raw; gu.x_out = hbuf; gu.norm_w = (const uint16_t*)L.ffn_norm;
         gu.act_q = dc->act_q; gu.act_d = dc->act_d; gu.act_sum = dc->act_sum; gu.act_f = dc->act_f;
-        if ((rc = launch_gateup8<WT>(gu, F, keep(l4 + 2)))) return rc;
+        if ((rc = launch_gateup8<WT>(gu, F, keep(l4 + 2), dc->o_planes))) return rc;
         Gemv8Args dn{};
         dn.step = dc->step; dn.d_in = F; dn.n_mats = 1; set_mat(dn, 0, L.wdown, WT, E, F); dn.out = dc->down_raw;
         dn.act_q = dc->act_q; dn.act_d = dc->act_d; dn.act_sum = dc->act_sum;
@@ -1602,6 +1649,10 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     dc->exact = g_decode_exact;
     dc->attn_classic = g_attn_classic;
     dc->persist_on = g_persist_on;
+    // the o launch as K-quarter planes: the single-sequence fast step with one-pass attention (d_head 64, not the exact forms), Q8
+    // activations (q4 or q8 weights) and the width k_dec_o_planes is written for; everything else keeps k_dec_gemv8
+    dc->o_planes = g_o_planes != 0 && n_seq == 1 && !dc->exact && !dc->persist_on && dh == 64 && d.adtype == GTEN_Q8 &&
+                   (d.wdtype == GTEN_Q4 || d.wdtype == GTEN_Q8) && d.n_embd == OPL_E;
     {
         // Rows per lane: 128 where the folded W.x form runs eight row tiles per workgroup (k_dec_mmvh<.., 8, ..>: every expanded
         // weight fragment feeds eight matrix instructions and the weights are read once per 128 sequences), else 64 (the exact forms,
@@ -1639,7 +1690,7 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
     dc->smp.samp_host.assign(S, SampleParam{});
     const size_t planes = wide ? 2 : 1;                       // k_dec_mmv may split K over two workgroups: one output plane each
     GTR_CHECK(hipMalloc((void**)&dc->qkv_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)(E + 2 * KV) * 4));
-    GTR_CHECK(hipMalloc((void**)&dc->proj_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)E * 4));      // (k_dec_wxp_f16: eight K planes)
+    GTR_CHECK(hipMalloc((void**)&dc->proj_raw, (wide ? (size_t)WXP_PLANES : dc->o_planes ? (size_t)OPL_PLANES : 1) * S * (size_t)E * 4));      // (k_dec_wxp_f16: eight K planes; k_dec_o_planes: four)
     GTR_CHECK(hipMalloc((void**)&dc->down_raw, (wide ? (size_t)WXP_PLANES : 1) * S * (size_t)E * 4));
     GTR_CHECK(hipMalloc((void**)&dc->scores, S * (size_t)d.n_heads * d.max_ctx * 4));
     GTR_CHECK(hipMalloc((void**)&dc->stats, (S * (size_t)d.n_heads * dc->n_chunks * 2 + 16) * 4));   // + 8 chunks of slack: the one-launch kernel reads 8 per head
@@ -1718,7 +1769,8 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
         const int block_bytes = d.wdtype == GTEN_F16 ? gten::kResidentBlockF16 : d.wdtype == GTEN_Q8 ? gten::kResidentBlockQ8 : gten::kResidentBlockQ4;
         const long long kv_bytes = 2ll * d.n_layers * d.max_ctx * (long long)gten_hip_row_bytes(d.adtype, KV);
         const long long scratch = 4ll * ((E + 2 * KV) + 2 * E + (long long)d.n_heads * d.max_ctx + 2ll * d.n_heads * dc->n_chunks + 16 +
-                                         (long long)d.n_heads * dc->n_chunks * dh + 2 * E + 2 * (F / 32) + F + 2 * dc->n_best + d.n_vocab) + F;
+                                         (long long)d.n_heads * dc->n_chunks * dh + 2 * E + 2 * (F / 32) + F + 2 * dc->n_best + d.n_vocab) + F +
+                                  (dc->o_planes ? 4ll * (OPL_PLANES - 1) * E : 0);
         dc->resident_overhead = kv_bytes + scratch;
         if (n_seq == 1 && !dc->exact && !dc->persist_on) {
             dc->resident_budget = gten::resident_budget(resident_setting_bytes(), kv_bytes, scratch);

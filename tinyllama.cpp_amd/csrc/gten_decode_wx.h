@@ -239,7 +239,9 @@ union GemvHotWords {
 // NM: matrices concatenated along the output rows -- 1 (o, down, lm_head: the weight requests are formed from the
 // preloaded words alone), or 0 = a.n_mats at run time (q|k|v, gate|up)
 // WLD: the cache policy of the weight requests (gten_dev.h) -- WLD_NT, or WLD_KEEP for a launch the decoder's plan keeps resident
-template <int WT, int PRO, int NCH, int R, int EPI, int NT, int NM = 0, int WLD = WLD_NT>
+// NPL: K planes of res_raw, d_in floats apart -- 1, or OPL_PLANES (gate|up behind k_dec_o_planes, gten_decode_oplanes.h): the planes
+//      are requested at entry and the row starts from (p0 + p1) + (p2 + p3), wave_sum's own order over the K quarters
+template <int WT, int PRO, int NCH, int R, int EPI, int NT, int NM = 0, int WLD = WLD_NT, int NPL = 1>
 __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, const unsigned long long h1, const unsigned long long h2,
                                                   const unsigned long long h3, const unsigned long long h4, const unsigned long long h5,
                                                   const unsigned long long h6, const Gemv8Args a)
@@ -267,6 +269,7 @@ __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, c
     // (round 3, built and measured: the FFN slice launch on 1024 threads -- sixteen waves of four rows, the prologue on the
     //  first 512 threads, the same bits -- 6.23 against 5.86 us per launch: not kept)
     static_assert(EPI != EPI_SILUMUL || NT == 512, "the FFN slice epilogue wants 8 waves");
+    static_assert(NPL == 1 || (NPL == 4 && PRO == PRO_RESID && EPI == EPI_SILUMUL), "K planes of res_raw: the gate|up launch only");
     constexpr bool F16W = (WT == GTEN_F16);        // f16 weights <=> f16 activations (tinyllama.cpp:258-265)
     const int d = hot.d_in, nb = d >> 5;
     ActStage s = carve_stage((PRO == PRO_ACTQ8 && !F16W) ? 32 : d);
@@ -300,7 +303,15 @@ __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, c
     float pin0[EPT], pin1[EPT];
 #pragma unroll
     for (int i = 0; i < EPT; i++) { pin0[i] = 0.f; pin1[i] = 0.f; }
-    if (PRO == PRO_RESID) { ldN<EPT>(res_raw + sbase, pin0); ldN<EPT>(res_a + sbase, pin1); }
+    float pinp[NPL > 1 ? NPL - 1 : 1][EPT];
+    if (PRO == PRO_RESID) {
+        ldN<EPT>(res_raw + sbase, pin0);
+        if constexpr (NPL > 1) {
+#pragma unroll
+            for (int q = 1; q < NPL; q++) ldN<EPT>(res_raw + q * d + sbase, pinp[q - 1]);
+        }
+        ldN<EPT>(res_a + sbase, pin1);
+    }
     // staging launches of the wide path: the producer (k_dec_mmv) may have split K over two workgroups -- the second
     // plane of partial sums is requested unconditionally (plane 0: the same row again) and added below
     float pin0b[(STG && PRO == PRO_RESID) ? EPT : 1];
@@ -432,6 +443,10 @@ __global__ __launch_bounds__(NT) void k_dec_gemv8(const unsigned long long h0, c
         } else if (PRO == PRO_RESID) {
 #pragma unroll
             for (int i = 0; i < EPT; i++) v[i] = pin0[i];
+            if constexpr (NPL == 4) {
+#pragma unroll
+                for (int i = 0; i < EPT; i++) v[i] = (pin0[i] + pinp[0][i]) + (pinp[1][i] + pinp[2][i]);
+            }
             if constexpr (STG && PRO == PRO_RESID) {
 #pragma unroll
                 for (int i = 0; i < EPT; i++) v[i] += a.raw_plane ? pin0b[i] : 0.f;

@@ -150,6 +150,7 @@ class GtenHip:
     FSM_MAX_BYTES = 1 << 30                                      # GTEN_HIP_FSM_MAX_BYTES
     AB_SYMBOLS = ["gten_hip_set_decode_attn_classic", "gten_hip_set_weight_resident_mb", "gten_hip_set_weight_resident_bytes", "gten_hip_weight_resident_bytes",
                   "gten_hip_decoder_resident", "gten_hip_decoder_resident_budget"]         # include/gten_hip_ab.h
+    O_PLANES_SYMBOLS = ["gten_hip_set_decode_o_planes", "gten_hip_decode_o_planes", "gten_hip_decoder_o_planes"]    # include/gten_hip_oplanes.h
     SCORE_SYMBOLS = ["gten_hip_row_logprobs"]                    # include/gten_hip_score.h
     PREFIX_SYMBOLS = ["gten_hip_block_rows_prefixed"]            # include/gten_hip_prefix.h
     CONTINUE_SYMBOLS = ["gten_hip_block_rows_continued", "gten_hip_set_row_contexts"]       # include/gten_hip_continue.h
@@ -215,6 +216,9 @@ class GtenHip:
                                                                          C.POINTER(C.c_ulonglong), C.POINTER(ci)])
         self._decode_exact = _sig(L, "gten_hip_set_decode_exact", ci, [ci])
         self._decode_attn_classic = _sig(L, "gten_hip_set_decode_attn_classic", ci, [ci])
+        self._decode_o_planes = _sig(L, "gten_hip_set_decode_o_planes", ci, [ci])
+        self._decode_o_planes_get = _sig(L, "gten_hip_decode_o_planes", ci, [])
+        self._decoder_o_planes = _sig(L, "gten_hip_decoder_o_planes", ci, [vp, C.POINTER(ci)])
         self._decode_persistent = _sig(L, "gten_hip_set_decode_persistent", ci, [ci])
         self._weight_resident_mb = _sig(L, "gten_hip_set_weight_resident_mb", ci, [ci])
         self._weight_resident_bytes = _sig(L, "gten_hip_set_weight_resident_bytes", ci, [C.c_longlong])
@@ -834,6 +838,21 @@ class GtenHip:
         """decoders created from now on: the single-sequence attention as k_dec_attn_one64w (0 / False, the default), as
         k_dec_attn_one64 (1 / True, the A/B control) or as k_dec_attn_one64v (2) -- the same bytes (include/gten_hip_ab.h)"""
         self._check(self._decode_attn_classic(int(on)))
+
+    def set_decode_o_planes(self, on):
+        """single-sequence decoders created from now on run their o launch as four K-quarter planes (1 / True, the default) or as
+        one plane (0 / False, the A/B control) -- the same bytes (include/gten_hip_oplanes.h)"""
+        self._check(self._decode_o_planes(int(on)))
+
+    def decode_o_planes(self):
+        """the setting a decoder created now would read: 1 or 0"""
+        return int(self._decode_o_planes_get())
+
+    def decoder_o_planes(self, dec):
+        """what a raw decoder handle chose: 1 (k_dec_o_planes) or 0"""
+        p = C.c_int(-1)
+        self._check(self._decoder_o_planes(dec, C.byref(p)))
+        return p.value
 
     def set_weight_resident_mb(self, mb):
         """single-sequence decoders created from now on keep the weights of their smallest W.x launches in the memory-side cache, up

@@ -1,8 +1,10 @@
 // capi_resident.cpp -- flat C exports of include/gten_host_resident.h: what a model's or a batch's decoder decided about resident
 // weights, and host/resident_plan.h itself for callers without a device.  The one host unit that names include/gten_hip_ab.h.
 #include "../../include/gten_host_resident.h"
+#include "../../include/gten_host_ab.h"
 
 #include "../../include/gten_hip_ab.h"
+#include "../../include/gten_hip_oplanes.h"
 #include "capi_handles.h"
 #include "resident_plan.h"
 
@@ -32,6 +34,20 @@ int gten_host_batch_resident(gten_host_batch* b, int* launches, long long* bytes
 {
     if (!b) return -1;
     return info(b->batch->decoder_handle(), launches, bytes, budget, overhead);
+}
+
+int gten_host_model_o_planes(gten_host_model* m, int* planes)
+{
+    if (!m) return -1;
+    gten_hip_decoder* dec = m->model->decoder_handle();
+    return (dec && !gten_hip_decoder_o_planes(dec, planes)) ? 0 : -1;
+}
+
+int gten_host_batch_o_planes(gten_host_batch* b, int* planes)
+{
+    if (!b) return -1;
+    gten_hip_decoder* dec = b->batch->decoder_handle();
+    return (dec && !gten_hip_decoder_o_planes(dec, planes)) ? 0 : -1;
 }
 
 int gten_host_resident_plan(int n_layers, int n_embd, int n_ffn, int kv_width, int n_vocab, int block_bytes, long long budget,

@@ -105,6 +105,8 @@ class GtenHost:
     BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
     # include/gten_host_resident.h (resident weights: what a decoder decided, and the plan: host/resident_plan.h)
     RESIDENT_SYMBOLS = ["gten_host_model_resident", "gten_host_batch_resident", "gten_host_resident_plan"]
+    # include/gten_host_ab.h (what a decoder chose among the A/B forms of include/gten_hip_oplanes.h)
+    AB_SYMBOLS = ["gten_host_model_o_planes", "gten_host_batch_o_planes"]
     RESIDENT_BLOCK_BYTES = {"f16": 64, "q8": 34, "q4": 18}       # bytes of a 32-element weight block, deltas included
     BEAM_ENDED = ("eos", "length")                               # GTEN_HOST_BEAM_ENDED_*
     SAMPLES_MAX = 64                                             # GTEN_HOST_SAMPLES_MAX
@@ -203,6 +205,8 @@ class GtenHost:
         ll, llp = C.c_longlong, C.POINTER(C.c_longlong)
         self._m_resident = _sig(L, "gten_host_model_resident", ci, [vp, C.POINTER(ci), llp, llp, llp])
         self._b_resident = _sig(L, "gten_host_batch_resident", ci, [vp, C.POINTER(ci), llp, llp, llp])
+        self._m_o_planes = _sig(L, "gten_host_model_o_planes", ci, [vp, C.POINTER(ci)])
+        self._b_o_planes = _sig(L, "gten_host_batch_o_planes", ci, [vp, C.POINTER(ci)])
         self._resident_plan = _sig(L, "gten_host_resident_plan", ci, [ci, ci, ci, ci, ci, ci, ll, vp, vp, llp])
         self._generate_fsm = _sig(L, "gten_host_model_generate_fsm", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
                                                                           C.c_float, C.c_float, vp, vp, vp, pen, ci, vp])
@@ -459,6 +463,13 @@ class GtenHost:
         if rc:
             raise GtenHipError(f"resident rc={rc}: {self.hip._err().decode(errors='replace')}")
         return n.value, b.value, budget.value, over.value
+
+    def _o_planes_of(self, fn, h):
+        p = C.c_int(-1)
+        rc = fn(h, C.byref(p))
+        if rc:
+            raise GtenHipError(f"o_planes rc={rc}: {self.hip._err().decode(errors='replace')}")
+        return p.value
 
     def model(self, cfg):
         return HostModel(self, cfg)
@@ -1164,6 +1175,10 @@ class HostModel:
         of this model's decoder (include/gten_host_resident.h)"""
         return self.host._resident_of(self.host._m_resident, self.h)
 
+    def o_planes(self):
+        """1 where this model's decoder runs its o launch as four K-quarter planes, else 0 (include/gten_host_resident.h)"""
+        return self.host._o_planes_of(self.host._m_o_planes, self.h)
+
     def cut_info(self):
         """(top_p, min_p, t = f32(log(min_p)), whether the decoder has ever had a cut set)"""
         a, b, t = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32)
@@ -1585,6 +1600,10 @@ class HostBatch:
     def resident(self):
         """HostModel.resident() of the shared decoder: a decoder of 2+ sequences keeps no weights resident"""
         return self.host._resident_of(self.host._b_resident, self.h)
+
+    def o_planes(self):
+        """HostModel.o_planes() of the shared decoder: a decoder of 2+ sequences keeps the one-plane launch"""
+        return self.host._o_planes_of(self.host._b_o_planes, self.h)
 
     def cut_info(self):
         """(top_p f32[n_seq], min_p f32[n_seq], t f32[n_seq] = f32(log(min_p)), whether the shared decoder has ever had a cut set)"""
