@@ -30,6 +30,7 @@
 #include "gten_hip_nucleus.h"
 #include "gten_hip_penalty.h"
 #include "gten_hip_fsm.h"
+#include "gten_hip_mirostat.h"
 #include "gten_hip_regex.h"
 #include "gten_hip_stoptext.h"
 #include "gten_hip_ab.h"
@@ -123,6 +124,9 @@ static_assert(CUT_MASS_BITS == GTEN_HIP_NUCLEUS_MASS_BITS && sizeof(CutInfo) == 
               "gten_decode_nucleus.h and include/gten_hip_nucleus.h disagree");
 #include "gten_decode_penalty.h"
 #include "gten_decode_fsm.h"
+#include "gten_decode_mirostat.h"
+static_assert(sizeof(MiroInfo) == GTEN_HIP_MIRO_INFO_BYTES && sizeof(MiroInfo) == sizeof(gten_hip_miro_info) && MIRO_MU_MAX == GTEN_HIP_MIRO_MU_MAX,
+              "gten_decode_mirostat.h and include/gten_hip_mirostat.h disagree");
 
 // --------------------------------------------------------------- host side
 
@@ -169,6 +173,12 @@ struct SamplerState {
     int32_t* fsm_state = nullptr;       // [n_seq][max_ctx + 2] the state per position, laid out like `result`
     int n_fsm = 0;                      // sequences that are bound
     bool fsm_on = false;
+    // Mirostat v2 (include/gten_hip_mirostat.h): the sequences' bindings and mu per position.  It only acts on a
+    // sampling sequence, so it does not enter sampler_on (as a cut does not)
+    MiroParam* miro = nullptr;          // [n_seq] bindings beside `samp`
+    std::vector<MiroParam> miro_host;
+    int32_t* miro_mu = nullptr;         // [n_seq][max_ctx + 2] mu per position (Q16), laid out like `fsm_state`
+    bool miro_on = false;
     // the vocabulary as byte strings (include/gten_hip_regex.h): what a byte automaton is expanded over
     uint8_t* vocab_bytes = nullptr;     // [vocab_n_bytes]
     int32_t* vocab_offsets = nullptr;   // [n_vocab + 1]
@@ -298,6 +308,7 @@ struct StepEnd {
     const CutParam* cut;
     const PenParam* pen;
     const FsmParam* fsm; int32_t* fsm_state;
+    const MiroParam* miro; int32_t* miro_mu;
     const float* best_val; const int* best_idx; int n_best, best_stride;      // k_dec_argmax: candidates per sequence
 };
 
@@ -308,7 +319,11 @@ static int launch_step_end(gten_hip_decoder* dc, const StepEnd& e)
     const int V = dc->d.n_vocab, tok_stride = dc->d.max_ctx + 1, rec_stride = dc->d.max_ctx + 2;
     const dim3 grid(e.rows), block(SMP_THREADS);
     const bool on = sampler_on(dc);
-    if (on && s.fsm_on)
+    if (on && s.miro_on)
+        DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_miro, grid, block, s.pen_lds, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens,
+                   tok_stride, (const float*)s.bias, e.lp, rec_stride, e.cut, e.pen, (const uint16_t*)s.fsm_next, (const uint8_t*)s.fsm_flags, s.fsm_states,
+                   e.fsm, e.fsm_state, e.miro, e.miro_mu);
+    else if (on && s.fsm_on)
         DEC_LAUNCH(KT_DEC_SAMPLE, k_dec_sample_fsm, grid, block, s.pen_lds, e.logits, V, e.row_stride, e.samp, e.step, e.result, e.result_stride, e.tokens,
                    tok_stride, (const float*)s.bias, e.lp, rec_stride, e.cut, e.pen, (const uint16_t*)s.fsm_next, (const uint8_t*)s.fsm_flags, s.fsm_states,
                    e.fsm, e.fsm_state);
@@ -337,6 +352,7 @@ struct LaneBufs {
     int n_seq;
     DecStep* step; int32_t* tokens; int32_t* result; const SampleParam* samp; LpRecord* lp; const CutParam* cut; const PenParam* pen;
     const FsmParam* fsm; int32_t* fsm_state;
+    const MiroParam* miro; int32_t* miro_mu;
     float *qkv_raw, *proj_raw, *down_raw, *scores, *stats, *att_part;
     uint8_t *xbuf, *hbuf;
     float* act_f; int8_t* act_q; float* act_d; int* act_sum;
@@ -358,6 +374,8 @@ static LaneBufs lane_bufs(const gten_hip_decoder* dc, int lane)
     b.pen = dc->smp.pen ? dc->smp.pen + o : nullptr;
     b.fsm = dc->smp.fsm ? dc->smp.fsm + o : nullptr;
     b.fsm_state = dc->smp.fsm_state ? dc->smp.fsm_state + o * (d.max_ctx + 2) : nullptr;
+    b.miro = dc->smp.miro ? dc->smp.miro + o : nullptr;
+    b.miro_mu = dc->smp.miro_mu ? dc->smp.miro_mu + o * (d.max_ctx + 2) : nullptr;
     const size_t rplanes = dc->n_seq >= 16 ? (size_t)WXP_PLANES : 1;        // (k_dec_wxp_f16: eight K planes)
     b.qkv_raw = dc->qkv_raw + o * rplanes * (E + 2 * KV);
     b.proj_raw = dc->proj_raw + o * rplanes * E; b.down_raw = dc->down_raw + o * rplanes * E;
@@ -878,7 +896,7 @@ static int enqueue_step_q8act(gten_hip_decoder* dc)
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemv8<WT, PRO_RESID, NE, F16W ? 4 : 8, 512, 1>(KT_DEC_GEMV_HEAD, hd, d.n_vocab, keep((size_t)d.n_layers * 4)))) return rc;
     // (one sequence: no strides; the argmax joins lm_head's per-wave winners)
-    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state,
+    return launch_step_end(dc, StepEnd{1, d.logits, 0, dc->smp.samp, dc->step, dc->result, 0, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state, dc->smp.miro, dc->smp.miro_mu,
                                        dc->best_val, dc->best_idx, dc->n_best, 0});
 }
 
@@ -1017,7 +1035,7 @@ static int enqueue_step_multi(gten_hip_decoder* dc)
     hd.act_q = dc->stg_q; hd.act_d = dc->stg_d; hd.act_sum = dc->stg_sum; hd.act_f = dc->stg_f;
     hd.best_val = dc->best_val; hd.best_idx = dc->best_idx;
     if ((rc = launch_gemvm<WT, NE, RH, S, 512>(KT_DEC_GEMV_HEAD, hd, V))) return rc;
-    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state,
+    return launch_step_end(dc, StepEnd{S, dc->logits_m, V, dc->smp.samp, dc->step, dc->result, d.max_ctx + 2, dc->tokens, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm, dc->smp.fsm_state, dc->smp.miro, dc->smp.miro_mu,
                                        dc->best_val, dc->best_idx, dc->n_best, dc->n_best});
 }
 
@@ -1493,7 +1511,7 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
     if ((rc = launch_stage_frag<WT, PRO_RESID>(KT_DEC_STAGE, sf, S))) return rc;
     if ((rc = mm(KT_DEC_GEMV_HEAD, b.stg_q, b.stg_d, b.stg_sum, b.logits_m, V, E, d.lm_head, V))) return rc;
     // (the matrix-core lm_head keeps no winners: the argmax reads the logits rows; the bias tables are the decoder's, not a lane's)
-    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.pen, b.fsm, b.fsm_state, b.logits_m, nullptr, V, V});
+    return launch_step_end(dc, StepEnd{S, b.logits_m, V, b.samp, b.step, b.result, d.max_ctx + 2, b.tokens, b.lp, b.cut, b.pen, b.fsm, b.fsm_state, b.miro, b.miro_mu, b.logits_m, nullptr, V, V});
 }
 
 template <int WT>
@@ -1900,7 +1918,7 @@ int gten_hip_decoder_destroy(gten_hip_decoder* dc)
     void* bufs[] = {dc->hm, dc->ids_stage, dc->step, dc->tokens, dc->result, dc->qkv_raw, dc->proj_raw, dc->down_raw,
                     dc->scores, dc->stats, dc->att_part, dc->xbuf, dc->hbuf, dc->best_val, dc->best_idx,
                     dc->act_q, dc->act_d, dc->act_sum, dc->act_f, dc->stg_q, dc->stg_d, dc->stg_sum, dc->stg_f,
-                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm_next, dc->smp.fsm_flags, dc->smp.fsm, dc->smp.fsm_state,
+                    dc->logits_m, (void*)dc->kv_tab, dc->gu_raw, dc->rope_now, dc->dummy_kv, dc->smp.samp, dc->smp.bias, dc->smp.lp, dc->smp.cut, dc->smp.pen, dc->smp.fsm_next, dc->smp.fsm_flags, dc->smp.fsm, dc->smp.fsm_state, dc->smp.miro, dc->smp.miro_mu,
                     dc->smp.vocab_bytes, dc->smp.vocab_offsets, dc->share_dev, dc->which_dev, (void*)dc->pfx_hm_tab};
     for (void* b : bufs) if (b) rel(hipFree(b));
     for (gten_hip_decoder::Pfx& x : dc->pfx)

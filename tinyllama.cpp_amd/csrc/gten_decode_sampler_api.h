@@ -242,6 +242,8 @@ int gten_hip_decoder_set_cut(gten_hip_decoder* dc, int seq, float top_p, float m
     if (int rc = cut_check(top_p, min_p, "decoder_set_cut")) return rc;
     const CutParam c = cut_param(top_p, min_p);
     GTR_REQUIRE(c.on == 0u || !dc->persist_on, "decoder_set_cut: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+    GTR_REQUIRE(c.on == 0u || !dc->smp.miro_on || dc->smp.miro_host[(size_t)seq].on == 0u,
+                "decoder_set_cut: sequence %d is bound to mirostat (gten_hip_decoder_set_seq_mirostat): a cut and mirostat do not compose", seq);
     if (c.on == 0u && !dc->smp.cut_on) return 0;       // nobody has ever cut: nothing to clear
     if (!dc->smp.cut_on)
         if (int rc = first_use(dc, dc->smp.cut_on, cut_make)) return rc;
@@ -356,7 +358,9 @@ static int pen_rows_upload(const char* who, const PenRows& pen, int n_rows)
 // accepts (null: none), ROWS_PEN those and every row's window and penalty (`pen`; with pen->y_out the rows are written out and nothing
 // is drawn: no request is looked at).  `who` names the operator in every message.
 // ROWS_FSM (include/gten_hip_fsm.h, §3.15): ROWS_PEN without a bias, every row in a state of the caller's pool (`fsm`).
-enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT, ROWS_PEN, ROWS_FSM };
+// ROWS_MIRO (include/gten_hip_mirostat.h, §3.23): ROWS_FSM without cuts, with a bias it accepts and a pool it accepts (null: no row is
+// in a state), every row under its own Mirostat request (`miro`).
+enum RowsLevel { ROWS_PLAIN, ROWS_BIASED, ROWS_CUT, ROWS_PEN, ROWS_FSM, ROWS_MIRO };
 struct FsmRows {
     const uint16_t* next; const uint8_t* flags;      // the pool, on the device
     int n_states;
@@ -372,10 +376,49 @@ static int fsm_rows_upload(const char* who, const FsmRows& f, int n_rows)
         GTR_REQUIRE(f.state_host[r] >= -1 && f.state_host[r] < f.n_states, "%s: state %d of row %d outside [-1, %d)", who, f.state_host[r], r, f.n_states);
     return grow_upload(g_state_dev, f.state_host, (size_t)n_rows * sizeof(int32_t));
 }
+struct MiroRows {
+    const int32_t* mu_host;                          // [n_rows] Q16
+    const float *tau_host, *eta_host;                // [n_rows]; tau 0: the row draws by the routine below
+    gten_hip_miro_info* info_out;                    // device [n_rows] or null
+};
+static GrowBuf g_miro_dev;                           // the rows' Mirostat requests of one ROWS_MIRO call
+// a Mirostat request checked and converted to Q16 (the setters and the operator share the refusals)
+static int miro_check(float tau, float eta, long long mu, const char* who, int* tau_q, int* eta_q)
+{
+    const int bad = miro_q16(tau, eta, tau_q, eta_q);
+    GTR_REQUIRE(bad != MIRO_BAD_TAU, "%s: mirostat tau %g outside (0, 32]", who, (double)tau);
+    GTR_REQUIRE(bad != MIRO_BAD_ETA, "%s: mirostat eta %g outside (0, 1]", who, (double)eta);
+    GTR_REQUIRE(mu >= -(long long)MIRO_MU_MAX && mu <= (long long)MIRO_MU_MAX, "%s: mirostat mu %lld outside [-%d, %d] (Q16)", who, mu, MIRO_MU_MAX, MIRO_MU_MAX);
+    return 0;
+}
+static int miro_rows_upload(const char* who, const MiroRows& m, const FsmRows& f, const float* bias, int n_rows)
+{
+    GTR_REQUIRE(m.mu_host && m.tau_host && m.eta_host, "%s: null argument", who);
+    const bool pool = f.next || f.flags || f.state_host || f.n_states != 0;
+    if (pool) {
+        if (int rc = fsm_rows_upload(who, f, n_rows)) return rc;
+    } else {
+        const std::vector<int32_t> none((size_t)n_rows, -1);
+        if (int rc = grow_upload(g_state_dev, none.data(), none.size() * sizeof(int32_t))) return rc;
+        GTR_CHECK(hipStreamSynchronize(stream()));    // `none` lives on this stack frame
+    }
+    std::vector<MiroRowParam> rows((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        GTR_REQUIRE(!(bias && pool && f.state_host[r] >= 0), "%s: row %d has a bias and a state: a table and an automaton do not compose", who, r);
+        MiroRowParam& q = rows[(size_t)r];
+        q = MiroRowParam{m.mu_host[r], 0, 0, 0u};
+        if (m.tau_host[r] == 0.f) continue;
+        if (int rc = miro_check(m.tau_host[r], m.eta_host[r], m.mu_host[r], who, &q.tau_q, &q.eta_q)) return rc;
+        q.on = 1u;
+    }
+    if (int rc = grow_upload(g_miro_dev, rows.data(), rows.size() * sizeof(MiroRowParam))) return rc;
+    GTR_CHECK(hipStreamSynchronize(stream()));        // `rows` lives on this stack frame
+    return 0;
+}
 static int sample_rows_common(const char* who, RowsLevel level, const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias,
                               long long bias_stride, const int32_t* top_k_host, const float* temp_host, uint64_t seed, const uint32_t* stream_host,
                               const int32_t* position_host, const float* top_p_host, const float* min_p_host, int32_t* out, gten_hip_cut_info* info_out,
-                              const PenRows* pen = nullptr, const FsmRows* fsm = nullptr)
+                              const PenRows* pen = nullptr, const FsmRows* fsm = nullptr, const MiroRows* miro = nullptr)
 {
     GTR_NEED_INIT();
     const bool shape_ok = n_rows >= 0 && n_vocab >= 1 && n_vocab <= 65535 && row_stride >= 0;
@@ -420,14 +463,22 @@ static int sample_rows_common(const char* who, RowsLevel level, const float* log
         rows[(size_t)r] = SampleRowParam{top_k_host[r], temp_host[r], stream_host[r], (unsigned)position_host[r]};
         if (cutting) cuts[(size_t)r] = cut_param(top_p_host[r], min_p_host[r]);
     }
-    if (level == ROWS_PEN || level == ROWS_FSM)
+    if (level == ROWS_PEN || level == ROWS_FSM || level == ROWS_MIRO)
         if (int rc = pen_rows_upload(who, *pen, n_rows)) return rc;
     if (level == ROWS_FSM)
         if (int rc = fsm_rows_upload(who, *fsm, n_rows)) return rc;
+    if (level == ROWS_MIRO)
+        if (int rc = miro_rows_upload(who, *miro, *fsm, bias, n_rows)) return rc;
     if (int rc = grow_upload(g_rows_dev, rows.data(), rows.size() * sizeof(SampleRowParam))) return rc;
     const SampleRowParam* par = (const SampleRowParam*)g_rows_dev.dev;
     const unsigned seed_lo = (unsigned)(seed & 0xffffffffu), seed_hi = (unsigned)(seed >> 32);
-    if (level == ROWS_FSM) {
+    if (level == ROWS_MIRO) {
+        size_t lds = 0;
+        if (int rc = pen_fit((const void*)k_sample_rows_miro, n_vocab, who, &lds)) return rc;
+        GTR_LAUNCH(KT_DEC_SAMPLE, k_sample_rows_miro, grid, block, lds, logits, n_vocab, row_stride, bias, bias_stride, par, (const PenParam*)g_pen_dev.dev,
+                   (const int32_t*)g_hist_dev.dev, (const int32_t*)g_off_dev.dev, fsm->next, fsm->flags, fsm->next ? fsm->n_states : 0,
+                   (const int32_t*)g_state_dev.dev, (const MiroRowParam*)g_miro_dev.dev, seed_lo, seed_hi, out, fsm->next_out, (MiroInfo*)miro->info_out);
+    } else if (level == ROWS_FSM) {
         size_t lds = 0;
         if (int rc = pen_fit((const void*)k_sample_rows_fsm, n_vocab, who, &lds)) return rc;
         if (int rc = grow_upload(g_cut_dev, cuts.data(), cuts.size() * sizeof(CutParam))) return rc;
@@ -695,4 +746,115 @@ int gten_hip_sample_rows_fsm(const float* logits, int n_rows, int n_vocab, long 
     const FsmRows fsm{next, flags, n_states, state_host, next_state_out};
     return sample_rows_common("sample_rows_fsm", ROWS_FSM, logits, n_rows, n_vocab, row_stride, nullptr, 0, top_k_host, temp_host, seed, stream_host,
                               position_host, top_p_host, min_p_host, out, info_out, &pen, &fsm);
+}
+
+// ---- Mirostat v2 (include/gten_hip_mirostat.h)
+// the shared arithmetic, device-free: no GTR_NEED_INIT
+int32_t gten_hip_miro_lg16_host(uint64_t x) { return (int32_t)miro_lg16((unsigned long long)x); }
+int32_t gten_hip_miro_update_host(int32_t mu, int32_t s, int32_t tau_q, int32_t eta_q) { return (int32_t)miro_update(mu, s, tau_q, eta_q); }
+int gten_hip_miro_q16_host(float tau, float eta, int32_t* tau_q, int32_t* eta_q)
+{
+    int t = 0, e = 0;
+    const int bad = miro_q16(tau, eta, &t, &e);
+    if (bad != MIRO_OK) return bad;
+    if (tau_q) *tau_q = t;
+    if (eta_q) *eta_q = e;
+    return GTEN_HIP_MIRO_OK;
+}
+static_assert(MIRO_OK == GTEN_HIP_MIRO_OK && MIRO_BAD_TAU == GTEN_HIP_MIRO_BAD_TAU && MIRO_BAD_ETA == GTEN_HIP_MIRO_BAD_ETA,
+              "gten_miro_math.h and include/gten_hip_mirostat.h disagree");
+
+static int miro_make(gten_hip_decoder* dc)          // every sequence: unbound; the mu rows zeroed
+{
+    SamplerState& s = dc->smp;
+    // (this rung counts a penalised sequence's window too: its dynamic LDS limit is raised here, before any capture, as fsm_make does)
+    size_t lds = 0;
+    if (int rc = pen_fit((const void*)k_dec_sample_miro, dc->d.n_vocab, "decoder_set_seq_mirostat", &lds)) return rc;
+    s.miro_host.assign((size_t)dc->n_seq, MiroParam{0, 0, 0, 0u});
+    const size_t rows = (size_t)dc->n_seq * (size_t)(dc->d.max_ctx + 2) * sizeof(int32_t);
+    if (!s.miro) GTR_CHECK(hipMalloc((void**)&s.miro, (size_t)dc->n_seq * sizeof(MiroParam)));
+    if (!s.miro_mu) GTR_CHECK(hipMalloc((void**)&s.miro_mu, rows));
+    GTR_CHECK(hipMemcpyAsync(s.miro, s.miro_host.data(), s.miro_host.size() * sizeof(MiroParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemsetAsync(s.miro_mu, 0, rows, stream()));
+    return 0;
+}
+
+int gten_hip_decoder_set_seq_mirostat(gten_hip_decoder* dc, int seq, float tau, float eta, int32_t mu_q16, int pos)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && seq >= 0 && seq < dc->n_seq, "decoder_set_seq_mirostat: sequence %d outside [0, %d)", seq, dc ? dc->n_seq : 0);
+    SamplerState& s = dc->smp;
+    MiroParam h{0, 0, 0, 0u};
+    int32_t mu = 0;
+    if (tau == 0.f) {
+        if (!s.miro_on) return 0;                        // nobody has ever been bound: nothing to clear
+    } else {
+        if (int rc = miro_check(tau, eta, mu_q16 == GTEN_HIP_MIRO_MU_DEFAULT ? 0 : (long long)mu_q16, "decoder_set_seq_mirostat", &h.tau_q, &h.eta_q)) return rc;
+        mu = mu_q16 == GTEN_HIP_MIRO_MU_DEFAULT ? 2 * h.tau_q : mu_q16;
+        GTR_REQUIRE(!dc->persist_on, "decoder_set_seq_mirostat: the persistent step (gten_hip_set_decode_persistent) has no sampler");
+        GTR_REQUIRE(pos >= 1 && pos <= dc->d.max_ctx, "decoder_set_seq_mirostat: position %d outside [1, %d]", pos, dc->d.max_ctx);
+        GTR_REQUIRE(!s.cut_on || s.cut_host[(size_t)seq].on == 0u,
+                    "decoder_set_seq_mirostat: sequence %d draws under a cut (gten_hip_decoder_set_cut): a cut and mirostat do not compose", seq);
+        if (!s.miro_on)
+            if (int rc = first_use(dc, s.miro_on, miro_make)) return rc;
+        h.pos = pos; h.on = 1u;
+    }
+    s.miro_host[(size_t)seq] = h;
+    if (h.on)
+        GTR_CHECK(hipMemcpyAsync(s.miro_mu + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + pos, &mu, sizeof(mu), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipMemcpyAsync(s.miro + seq, &s.miro_host[(size_t)seq], sizeof(MiroParam), hipMemcpyHostToDevice, stream()));
+    GTR_CHECK(hipStreamSynchronize(stream()));           // `mu` lives on this stack frame
+    return 0;
+}
+
+// entries [from, from + count) of sequence seq's mu row to the host (zeros while nobody has ever been bound)
+static int miro_row_read(gten_hip_decoder* dc, const char* who, int seq, int from, int count, int32_t* out_host)
+{
+    GTR_REQUIRE(seq >= 0 && seq < dc->n_seq && from >= 0 && count >= 0 && from + count <= dc->d.max_ctx + 2,
+                "%s: entries [%d, %d + %d) of sequence %d's mu row (%d entries, %d sequences)", who, from, from, count, seq, dc->d.max_ctx + 2, dc->n_seq);
+    if (count == 0) return 0;
+    GTR_REQUIRE(out_host, "%s: null output", who);
+    if (!dc->smp.miro_mu) { std::fill(out_host, out_host + count, 0); return 0; }
+    GTR_CHECK(hipStreamSynchronize(stream()));
+    GTR_CHECK(hipMemcpy(out_host, dc->smp.miro_mu + (size_t)seq * (size_t)(dc->d.max_ctx + 2) + from, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int gten_hip_decoder_mirostat_info(gten_hip_decoder* dc, int32_t* tau_q_host, int32_t* eta_q_host, int32_t* pos_host, int* on, int row_seq,
+                                   int row_from, int row_count, int32_t* row_host)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc, "decoder_mirostat_info: null decoder");
+    const SamplerState& s = dc->smp;
+    for (int q = 0; q < dc->n_seq; q++) {
+        const MiroParam m = s.miro_on ? s.miro_host[(size_t)q] : MiroParam{0, 0, 0, 0u};
+        if (tau_q_host) tau_q_host[q] = m.on ? m.tau_q : 0;
+        if (eta_q_host) eta_q_host[q] = m.on ? m.eta_q : 0;
+        if (pos_host) pos_host[q] = m.on ? m.pos : 0;
+    }
+    if (on) *on = s.miro_on ? 1 : 0;
+    if (row_host) return miro_row_read(dc, "decoder_mirostat_info", row_seq, row_from, row_count, row_host);
+    return 0;
+}
+
+int gten_hip_decoder_slot_mus(gten_hip_decoder* dc, int seq, int n_from, int count, int32_t* out_host)
+{
+    GTR_NEED_INIT();
+    GTR_REQUIRE(dc && out_host, "decoder_slot_mus: null argument");
+    return miro_row_read(dc, "decoder_slot_mus", seq, n_from, count, out_host);
+}
+
+int gten_hip_sample_rows_miro(const float* logits, int n_rows, int n_vocab, long long row_stride, const float* bias, long long bias_stride,
+                              const uint16_t* next, const uint8_t* flags, int n_states, const int32_t* state_host, const int32_t* top_k_host,
+                              const float* temp_host, uint64_t seed, const uint32_t* stream_host, const int32_t* position_host,
+                              const int32_t* hist_host, const int32_t* hist_offset_host, const float* r_host, const float* freq_host,
+                              const float* pres_host, const int32_t* mu_host, const float* tau_host, const float* eta_host, int32_t* out,
+                              int32_t* next_state_out, gten_hip_miro_info* info_out)
+{
+    FsmPenDefaults d;
+    const PenRows pen = d.rows(n_rows, hist_host, hist_offset_host, r_host, freq_host, pres_host, nullptr, 0);
+    const FsmRows fsm{next, flags, n_states, state_host, next_state_out};
+    const MiroRows miro{mu_host, tau_host, eta_host, info_out};
+    return sample_rows_common("sample_rows_miro", ROWS_MIRO, logits, n_rows, n_vocab, row_stride, bias, bias_stride, top_k_host, temp_host, seed, stream_host,
+                              position_host, nullptr, nullptr, out, nullptr, &pen, &fsm, &miro);
 }

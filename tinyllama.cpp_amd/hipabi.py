@@ -141,6 +141,13 @@ class GtenHip:
     # include/gten_hip_fsm.h (token automata: stop sequences and masked grammars)
     FSM_SYMBOLS = ["gten_hip_fsm_check", "gten_hip_decoder_set_fsm", "gten_hip_decoder_set_seq_fsm", "gten_hip_decoder_fsm_info",
                    "gten_hip_decoder_slot_states", "gten_hip_mask_rows_fsm", "gten_hip_sample_rows_fsm"]
+    # include/gten_hip_mirostat.h (Mirostat v2: integer surprise, mu per position)
+    MIROSTAT_SYMBOLS = ["gten_hip_miro_lg16_host", "gten_hip_miro_update_host", "gten_hip_miro_q16_host", "gten_hip_decoder_set_seq_mirostat",
+                        "gten_hip_decoder_mirostat_info", "gten_hip_decoder_slot_mus", "gten_hip_sample_rows_miro"]
+    MIRO_INFO = np.dtype([("Z", np.uint64), ("Zk", np.uint64), ("q_id", np.uint64), ("n_cand", np.int32), ("n_keep", np.int32), ("s", np.int32),
+                          ("mu_next", np.int32), ("pad", np.int32, (2,))])                          # gten_hip_miro_info
+    MIRO_MU_MAX = 64 << 16                                       # GTEN_HIP_MIRO_MU_MAX
+    MIRO_MU_DEFAULT = -(1 << 31)                                 # GTEN_HIP_MIRO_MU_DEFAULT: start at 2 * tau_q
     # include/gten_hip_regex.h (byte automata expanded over the vocabulary on the device)
     REGEX_SYMBOLS = ["gten_hip_fsm_expand", "gten_hip_fsm_check_dev", "gten_hip_decoder_set_vocab_bytes", "gten_hip_decoder_set_fsm_parts"]
     # include/gten_hip_stoptext.h (search automata -- stop strings given as text -- expanded over the vocabulary on the device)
@@ -269,6 +276,14 @@ class GtenHip:
         self._mask_rows_fsm = _sig(L, "gten_hip_mask_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, C.c_longlong])
         self._sample_rows_fsm = _sig(L, "gten_hip_sample_rows_fsm", ci, [vp, ci, ci, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_uint64, vp, vp, vp, vp,
                                                                          vp, vp, vp, vp, vp, vp, vp, vp])
+        self._miro_lg16 = _sig(L, "gten_hip_miro_lg16_host", C.c_int32, [C.c_uint64])
+        self._miro_update = _sig(L, "gten_hip_miro_update_host", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32])
+        self._miro_q16 = _sig(L, "gten_hip_miro_q16_host", ci, [C.c_float, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32)])
+        self._set_seq_mirostat = _sig(L, "gten_hip_decoder_set_seq_mirostat", ci, [vp, ci, C.c_float, C.c_float, C.c_int32, ci])
+        self._mirostat_info = _sig(L, "gten_hip_decoder_mirostat_info", ci, [vp, vp, vp, vp, C.POINTER(ci), ci, ci, ci, vp])
+        self._slot_mus = _sig(L, "gten_hip_decoder_slot_mus", ci, [vp, ci, ci, ci, vp])
+        self._sample_rows_miro = _sig(L, "gten_hip_sample_rows_miro", ci, [vp, ci, ci, C.c_longlong, vp, C.c_longlong, vp, vp, ci, vp, vp, vp, C.c_uint64,
+                                                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         self._row_logprobs = _sig(L, "gten_hip_row_logprobs", ci, [vp, ci, ci, C.c_longlong, vp, vp, vp, vp])
         self._argmax_row = _sig(L, "gten_hip_argmax_row", ci, [vp, ci, vp])
         self._beam_round = _sig(L, "gten_hip_beam_round", ci, [vp, ci, vp, vp, vp, C.c_longlong, vp, ci, vp, vp, ci, vp])
@@ -631,6 +646,73 @@ class GtenHip:
                                           inf.ptr if info else None))
         got, after = out.download(np.int32)[:n_rows].copy(), nxt.download(np.int32)[:n_rows].copy()
         return got, after, (inf.download(np.uint8)[: self.CUT_INFO.itemsize * n_rows].view(self.CUT_INFO).copy() if info else None)
+
+    # -- Mirostat v2 (include/gten_hip_mirostat.h)
+    def miro_lg16(self, x):
+        """gten_hip_miro_lg16_host: lg16(x) in Q16; needs no device"""
+        return int(self._miro_lg16(C.c_uint64(int(x))))
+
+    def miro_update(self, mu, s, tau_q, eta_q):
+        """gten_hip_miro_update_host: mu' of the contract's step 5; needs no device"""
+        return int(self._miro_update(int(mu), int(s), int(tau_q), int(eta_q)))
+
+    def miro_q16(self, tau, eta):
+        """gten_hip_miro_q16_host: (code, tau_q, eta_q) -- code 0, or 1 / 2 for a tau / eta outside its range (tau_q, eta_q then None)"""
+        a, b = C.c_int32(0), C.c_int32(0)
+        rc = self._miro_q16(C.c_float(tau), C.c_float(eta), C.byref(a), C.byref(b))
+        return (rc, a.value, b.value) if rc == 0 else (rc, None, None)
+
+    def sample_rows_miro(self, logits, n_rows, n_vocab, row_stride, top_k, temp, seed, stream, position, mu, tau, eta, bias=None, bias_stride=0,
+                         pool=None, states=-1, hist=None, r=1.0, freq=0.0, pres=0.0, info=True, rc=False):
+        """gten_hip_sample_rows_miro: row r drawn under Mirostat (tau[r], eta[r]) with the threshold mu[r] (Q16); tau 0: the routine
+        below.  pool: fsm_upload()'s tuple or None; hist None: no penalties; scalars are broadcast.  Returns (ids int32[n_rows], next
+        states int32[n_rows], info of dtype MIRO_INFO or None); with rc=True the call's return code alone."""
+        m = max(n_rows, 1)
+
+        def per_row(v, dt):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (m,)))
+            return a, a.ctypes.data_as(C.c_void_p)
+        (k, kp), (t, tp), (s, sp), (p, pp) = (per_row(top_k, np.int32), per_row(temp, np.float32), per_row(stream, np.uint32),
+                                              per_row(position, np.int32))
+        (muv, mup), (tav, tap), (etv, etp), (st, stp) = per_row(mu, np.int32), per_row(tau, np.float32), per_row(eta, np.float32), per_row(states, np.int32)
+        (rr, rp), (ff, fp), (pr_, prp) = per_row(r, np.float32), per_row(freq, np.float32), per_row(pres, np.float32)
+        ids, off = self._windows(hist, n_rows) if hist is not None else (np.zeros(0, np.int32), None)
+        out, nxt = DeviceBuffer(self, 4 * m), DeviceBuffer(self, 4 * m)
+        inf = DeviceBuffer(self, self.MIRO_INFO.itemsize * m) if info else None
+        code = self._sample_rows_miro(logits.ptr, n_rows, n_vocab, row_stride, bias.ptr if bias is not None else None, bias_stride,
+                                      pool[0].ptr if pool else None, pool[1].ptr if pool else None, pool[2] if pool else 0, stp if pool else None,
+                                      kp, tp, C.c_uint64(int(seed)), sp, pp, ids.ctypes.data_as(C.c_void_p) if len(ids) else None,
+                                      off.ctypes.data_as(C.c_void_p) if off is not None else None, rp, fp, prp, mup, tap, etp, out.ptr, nxt.ptr,
+                                      inf.ptr if info else None)
+        if rc:
+            return code
+        self._check(code)
+        got, after = out.download(np.int32)[:n_rows].copy(), nxt.download(np.int32)[:n_rows].copy()
+        return got, after, (inf.download(np.uint8)[: self.MIRO_INFO.itemsize * n_rows].view(self.MIRO_INFO).copy() if info else None)
+
+    def decoder_set_seq_mirostat_rc(self, dec, seq, tau, eta=0.1, mu_q16=None, pos=0):
+        return self._set_seq_mirostat(dec, int(seq), C.c_float(tau), C.c_float(eta), int(self.MIRO_MU_DEFAULT if mu_q16 is None else mu_q16), int(pos))
+
+    def decoder_set_seq_mirostat(self, dec, seq, tau, eta=0.1, mu_q16=None, pos=0):
+        """gten_hip_decoder_set_seq_mirostat: the ids of sequence seq from position pos on are drawn under Mirostat (tau, eta), mu starting
+        at mu_q16 (None: 2 * tau_q); tau 0 unbinds"""
+        self._check(self.decoder_set_seq_mirostat_rc(dec, seq, tau, eta, mu_q16, pos))
+
+    def decoder_mirostat_info(self, dec, n_seq, row_seq=None, row_from=0, row_count=0):
+        """gten_hip_decoder_mirostat_info: (tau_q int32[n_seq], eta_q int32[n_seq], pos int32[n_seq], on, mu row int32[row_count] or None)"""
+        tq, eq, ps = np.zeros(n_seq, np.int32), np.zeros(n_seq, np.int32), np.zeros(n_seq, np.int32)
+        on = C.c_int(0)
+        row = np.zeros(max(row_count, 1), np.int32) if row_seq is not None else None
+        v = lambda z: z.ctypes.data_as(C.c_void_p)                                                  # noqa: E731
+        self._check(self._mirostat_info(dec, v(tq), v(eq), v(ps), C.byref(on), int(row_seq or 0), int(row_from), int(row_count),
+                                        v(row) if row is not None else None))
+        return tq, eq, ps, bool(on.value), (row[:row_count].copy() if row is not None else None)
+
+    def decoder_slot_mus(self, dec, seq, n_from, count):
+        """gten_hip_decoder_slot_mus: int32[count], entry i the mu (Q16) the id at position n_from + i is drawn under"""
+        out = np.zeros(max(count, 1), np.int32)
+        self._check(self._slot_mus(dec, int(seq), int(n_from), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:count].copy()
 
     def decoder_set_fsm_rc(self, dec, nxt, flags, n_states=None):
         """the return code of gten_hip_decoder_set_fsm (nxt None: the pool is dropped)"""

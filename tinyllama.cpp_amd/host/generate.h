@@ -21,13 +21,16 @@
 #include "../../include/gten_hip_nucleus.h"
 #include "../../include/gten_hip_penalty.h"
 #include "../../include/gten_hip_fsm.h"
+#include "../../include/gten_hip_mirostat.h"
 
 namespace gten {
 
 // (kPenalty -- include/gten_hip_penalty.h, DESIGN.md §3.14, instantiated in host/capi_penalty.cpp -- requires kSampled: a penalised
 // greedy request takes its first id from the device too)
 // (kFsm -- include/gten_hip_fsm.h, DESIGN.md §3.15, instantiated in host/capi_fsm.cpp -- requires kSampled for the same reason)
-enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u, kFsm = 32u };
+// (kMirostat -- include/gten_hip_mirostat.h, DESIGN.md §3.23, instantiated in host/capi_mirostat.cpp and the command line only -- requires
+// kSampled: Mirostat acts on a sampling request)
+enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u, kFsm = 32u, kMirostat = 64u };
 
 // why a prompt's generation ended (kFsm flows report it per item)
 enum : int { kEndedByLength = 0, kEndedByEos = 1, kEndedByFinal = 2 };
@@ -47,6 +50,8 @@ struct Request {
     bool count_prompt = true;            // ... the prompt's included, or only what was generated
     int fsm_start = -1;                  // the state of the decoder's automaton pool the first new id is chosen in (-1: no automaton)
     int shift_keep = -1, shift_drop = 0; // context shift when the window fills (host/generate_shift.h; keep < 0: off, the sequence ends there)
+    float miro_tau = 0.f, miro_eta = 0.1f;       // Mirostat v2's target surprise in bits and learning rate (tau 0: off; ignored by a greedy request)
+    bool mirostat() const { return top_k > 0 && miro_tau != 0.f; }
     bool cuts() const { return top_k > 0 && !(top_p == 1.f && min_p == 0.f); }
     bool penalises() const { return !(rep == 1.f && freq == 0.f && pres == 0.f); }
     int start(int n_prompt) const { return count_prompt ? 0 : n_prompt; }
@@ -58,6 +63,13 @@ inline bool request_ok(int top_k, float temp) { return top_k >= 0 && (top_k == 0
 inline bool binding_ok(int table, int min_new) { return table >= -1 && table < GTEN_HIP_BIAS_TABLES && min_new >= 0; }
 inline bool asking_ok(int n_top, int n_top_max) { return n_top >= -1 && n_top <= GTEN_HIP_LOGPROBS_TOP && n_top <= n_top_max; }
 inline bool cut_ok(float top_p, float min_p) { return std::isfinite(top_p) && top_p > 0.f && top_p <= 1.f && std::isfinite(min_p) && min_p >= 0.f && min_p <= 1.f; }
+// (tau 0 is "off"; a cut and Mirostat on one request are refused: they do not compose, include/gten_hip_mirostat.h)
+inline bool mirostat_ok(float tau, float eta, int top_k, float top_p, float min_p)
+{
+    if (tau == 0.f) return true;
+    if (!(tau > 0.f && tau <= 32.f && eta > 0.f && eta <= 1.f)) return false;
+    return !(top_k > 0 && !(top_p == 1.f && min_p == 0.f));
+}
 inline bool fsm_ok(int fsm_start, int table) { return fsm_start >= -1 && fsm_start < GTEN_HIP_FSM_MAX_STATES && !(fsm_start >= 0 && table >= 0); }
 inline bool penalty_ok(float rep, float freq, float pres, int last_n)
 {
@@ -76,6 +88,14 @@ struct Requests {
     Each<float> rep{nullptr, 1.f}, freq{nullptr, 0.f}, pres{nullptr, 0.f};
     Each<int32_t> last_n{nullptr, 0}, count_prompt{nullptr, 1};
     Each<int32_t> fsm_start{nullptr, -1};
+    Each<float> miro_tau{nullptr, 0.f}, miro_eta{nullptr, 0.1f};
+    // these requests under Mirostat (each list may be null: the value for all)
+    Requests with_mirostat(const float* tau, float tau_all, const float* eta, float eta_all) const
+    {
+        Requests r = *this;
+        r.miro_tau = {tau, tau_all}; r.miro_eta = {eta, eta_all};
+        return r;
+    }
     // these requests with a start state per item (null: fsm_all for everybody)
     Requests bound_to(const int32_t* starts, int fsm_all = -1) const
     {
@@ -103,14 +123,17 @@ struct Requests {
     }
     Request operator[](int j) const
     {
-        return {top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j],
-                rep[j], freq[j], pres[j], last_n[j], count_prompt[j] != 0, fsm_start[j]};
+        Request r{top_k[j], temp[j], seed, stream ? stream[j] : (uint32_t)j, table[j], min_new[j], n_top[j], top_p[j], min_p[j],
+                  rep[j], freq[j], pres[j], last_n[j], count_prompt[j] != 0, fsm_start[j]};
+        r.miro_tau = miro_tau[j]; r.miro_eta = miro_eta[j];
+        return r;
     }
     bool ok(int n, int n_top_max) const
     {
         for (int j = 0; j < n; j++)
             if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j]) ||
-                !penalty_ok(rep[j], freq[j], pres[j], last_n[j]) || !fsm_ok(fsm_start[j], table[j])) return false;
+                !penalty_ok(rep[j], freq[j], pres[j], last_n[j]) || !fsm_ok(fsm_start[j], table[j]) ||
+                !mirostat_ok(miro_tau[j], miro_eta[j], top_k[j], top_p[j], min_p[j])) return false;
         return true;
     }
 };
@@ -194,9 +217,23 @@ struct FsmHost {
     std::vector<uint8_t> flags;
     int32_t* word = nullptr;             // device
     int32_t after = -1;
+    // (kMirostat) what gten_hip_sample_rows_miro returned with a first id: the mu the decoder is bound with at the next position
+    gten_hip_miro_info* miro_word = nullptr;     // device
+    int32_t mu_next = 0;
+    gten_hip_miro_info* miro_info_dev()
+    {
+        if (!miro_word) GTEN_HIP_OK(gten_hip_malloc((void**)&miro_word, sizeof(gten_hip_miro_info)));
+        return miro_word;
+    }
+    void read_mu_next()
+    {
+        gten_hip_miro_info info;
+        GTEN_HIP_OK(gten_hip_memcpy_d2h(&info, miro_word, sizeof(info)));
+        mu_next = info.mu_next;
+    }
     explicit FsmHost(gten_hip_decoder* dec_ = nullptr) : dec{dec_} {}
     FsmHost(const FsmHost&) = delete;
-    ~FsmHost() { if (word) gten_hip_free(word); }
+    ~FsmHost() { if (word) gten_hip_free(word); if (miro_word) gten_hip_free(miro_word); }
     int32_t* next_state_dev()
     {
         if (!word) GTEN_HIP_OK(gten_hip_malloc((void**)&word, sizeof(int32_t)));
@@ -236,8 +273,31 @@ void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_
     bool drawn = false;
     if constexpr ((M & kBiased) != 0)
         if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
+    // A request under Mirostat (kMirostat) draws through gten_hip_sample_rows_miro with the default start mu = 2 tau -- penalised, then under
+    // its table or in its start state, never under a cut; fsm->mu_next receives the mu of the next position, from the operator itself.
+    if constexpr ((M & kMirostat) != 0)
+        if (r.mirostat() && fsm) {
+            const uint16_t* next = nullptr;
+            const uint8_t* flags = nullptr;
+            int S = 0;
+            const bool bound = (M & kFsm) != 0 && r.fsm_start >= 0;
+            if (bound) GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, &next, &flags));
+            const bool pen = (M & kPenalty) != 0 && r.penalises();
+            const int32_t lo = pen ? std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos) : pos;
+            const int32_t off[2] = {0, pos - lo};
+            int32_t tq = 0, eq = 0;
+            GTEN_ASSERTM(gten_hip_miro_q16_host(r.miro_tau, r.miro_eta, &tq, &eq) == 0, "mirostat tau %g eta %g", (double)r.miro_tau, (double)r.miro_eta);
+            const int32_t mu0 = 2 * tq;
+            GTEN_HIP_OK(gten_hip_sample_rows_miro(lg, 1, n_vocab, 0, bound ? nullptr : row, 0, bound ? next : nullptr, bound ? flags : nullptr, bound ? S : 0,
+                                                  bound ? &r.fsm_start : nullptr, &k, &r.temp, r.seed, &r.stream, &pos, pen ? ids + lo : nullptr,
+                                                  pen ? off : nullptr, &r.rep, &r.freq, &r.pres, &mu0, &r.miro_tau, &r.miro_eta, id_dev,
+                                                  bound ? fsm->next_state_dev() : nullptr, fsm->miro_info_dev()));
+            if (bound) fsm->read_after();
+            fsm->read_mu_next();
+            drawn = true;
+        }
     if constexpr ((M & kFsm) != 0)
-        if (r.fsm_start >= 0) {
+        if (r.fsm_start >= 0 && !drawn) {
             const uint16_t* next = nullptr;
             const uint8_t* flags = nullptr;
             int S = 0;
@@ -287,7 +347,7 @@ template <unsigned M>
 struct SlotRequests {
     gten_hip_decoder* dec;
     int n_slots;
-    bool bound = false, sampling = false, fsm_bound = false;
+    bool bound = false, sampling = false, fsm_bound = false, miro_bound = false;
     SlotRequests(gten_hip_decoder* dec_, int n_slots_) : dec{dec_}, n_slots{n_slots_} {}
     SlotRequests(const SlotRequests&) = delete;
     ~SlotRequests() { clear(); }
@@ -307,6 +367,10 @@ struct SlotRequests {
                 if (r.fsm_start >= S) return gten_hip_decoder_set_seq_fsm(dec, q, r.fsm_start, 1);
             }
         }
+        // (a slot that carried a prompt under Mirostat is unbound before a cut may be set on it: the two do not compose)
+        if constexpr ((M & kMirostat) != 0)
+            if (miro_bound)
+                if (const int rc = gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0)) return rc;
         if constexpr ((M & kBiased) != 0)
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
         if constexpr ((M & kLogprobs) != 0)
@@ -329,6 +393,18 @@ struct SlotRequests {
             if (state < 0) return fsm_bound ? gten_hip_decoder_set_seq_fsm(dec, q, -1, 0) : 0;
             fsm_bound = true;
             return gten_hip_decoder_set_seq_fsm(dec, q, state, pos);
+        }
+        return 0;
+    }
+    // "slot q's ids from position pos on are drawn under the request's Mirostat, from mu" for the decode steps that follow (a request
+    // without Mirostat: the slot is unbound)
+    int mirostat(int q, const Request& r, int32_t mu, int pos)
+    {
+        (void)q; (void)r; (void)mu; (void)pos;
+        if constexpr ((M & kMirostat) != 0) {
+            if (!r.mirostat()) return miro_bound ? gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0) : 0;
+            miro_bound = true;
+            return gten_hip_decoder_set_seq_mirostat(dec, q, r.miro_tau, r.miro_eta, mu, pos);
         }
         return 0;
     }
@@ -364,7 +440,10 @@ struct SlotRequests {
         if constexpr ((M & kFsm) != 0)
             for (int q = 0; fsm_bound && q < n_slots; q++)
                 if (const int r = gten_hip_decoder_set_seq_fsm(dec, q, -1, 0)) rc = r;
-        bound = sampling = fsm_bound = false;
+        if constexpr ((M & kMirostat) != 0)
+            for (int q = 0; miro_bound && q < n_slots; q++)
+                if (const int r = gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0)) rc = r;
+        bound = sampling = fsm_bound = miro_bound = false;
         return rc;
     }
 };
@@ -425,6 +504,8 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
     if (slot.sample(0, r) != 0) return -1;
     if constexpr ((M & kFsm) != 0)
         if (r.fsm_start >= 0 && slot.fsm(0, state, n_first) != 0) return -1;
+    if constexpr ((M & kMirostat) != 0)
+        if (slot.mirostat(0, r, fh.mu_next, n_first) != 0) return -1;
     const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
     // (fewer ids than the steps that could run: an eos.  The context bounds them too; a caller that does not say how long it is
@@ -485,7 +566,7 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
     FsmHost fh(dec);
     for (int q = 0; q < S; q++)
         if (const int rc = slots.bind(q, reqs[q], n_prompt[q])) return rc;
-    std::vector<int32_t> first((size_t)S), state((size_t)S, -1);
+    std::vector<int32_t> first((size_t)S), state((size_t)S, -1), mu_first((size_t)S, 0);
     std::vector<char> final_first((size_t)S, 0);                  // (kFsm) the first id entered a final state: the prompt plus that id
     FirstRecords rec;
     if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
@@ -499,6 +580,7 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
             state[(size_t)q] = fh.after;
             final_first[(size_t)q] = r.fsm_start >= 0 && first[(size_t)q] != eos && fh.final(state[(size_t)q]);
         }
+        if constexpr ((M & kMirostat) != 0) mu_first[(size_t)q] = fh.mu_next;
         if constexpr ((M & kLogprobs) != 0)
             if (r.n_top >= 0 && first[(size_t)q] != eos) rows.from((size_t)q * max_tokens).store_first((size_t)P, r.n_top, rec.dev);
     }
@@ -514,6 +596,8 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
         if constexpr ((M & kFsm) != 0)
             if (reqs[q].fsm_start >= 0 && first[(size_t)q] != eos && !final_first[(size_t)q])
                 if (const int rc = slots.fsm(q, state[(size_t)q], P + 1)) return rc;
+        if constexpr ((M & kMirostat) != 0)
+            if (const int rc = slots.mirostat(q, reqs[q], mu_first[(size_t)q], P + 1)) return rc;
         // this sequence's own room; none when its first id is already eos (the sequence is then parked from the start instead of
         // being decoded for the longest sequence's length)
         room[(size_t)q] = (first[(size_t)q] == eos || final_first[(size_t)q]) ? 0 : max_tokens - (P + 1);
@@ -550,6 +634,25 @@ template <unsigned M>
 struct ServePolicy {
     static constexpr bool kLogprobs = (M & gten::kLogprobs) != 0;
     static constexpr bool kFsm = (M & gten::kFsm) != 0;
+    static constexpr bool kMirostat = (M & gten::kMirostat) != 0;
+    // (kMirostat) per prompt: the mu its next id is drawn under, as the host last read it
+    std::vector<int32_t> miro_mu;
+    void note_mu(int j, int32_t mu)
+    {
+        if (miro_mu.empty()) miro_mu.assign((size_t)std::max(reqs_n, j + 1), 0);
+        miro_mu[(size_t)j] = mu;
+    }
+    // (kMirostat) prompt j goes on in slot q with its next id at position pos: the binding travels with the prompt, at the mu the host read
+    void bind_mu(int q, int j, int pos) { GTEN_HIP_OK(slots.mirostat(q, reqs[j], miro_mu.empty() ? 0 : miro_mu[(size_t)j], pos)); }
+    // (kMirostat) slot q's next id, at position pos, is prompt j's, and the prompt is about to move to another slot (the tail): its mu is
+    // read back to go with it.  A slot that stays keeps its mu row on the device: nothing is read between slices
+    void read_mu(int q, int j, int pos)
+    {
+        if (!reqs[j].mirostat()) return;
+        int32_t mu = 0;
+        GTEN_HIP_OK(gten_hip_decoder_slot_mus(slots.dec, q, pos, 1, &mu));
+        note_mu(j, mu);
+    }
     // (kFsm) per prompt: the state its next id is chosen in, as the host last read it (-1: not bound), and whether it entered a final one
     std::vector<int32_t> fsm_state;
     std::vector<char> fsm_ended;
@@ -580,6 +683,7 @@ struct ServePolicy {
         const int id = first_id<M>(b, c, row, reqs[j], rec.dev, &fh);
         if constexpr (kLogprobs) store_first(0, j, (int)row.size());
         if constexpr (kFsm) note_first(j, fh.after);
+        if constexpr (kMirostat) note_mu(j, fh.mu_next);
         return id;
     }
     // (kFsm) prompt j's first id entered state `after`
@@ -634,6 +738,7 @@ struct ServePolicy {
             b.prefill_many_with(sets, cps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
                 draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data(), &fh);
                 if constexpr (kFsm) note_first(js[(size_t)k], fh.after);
+                if constexpr (kMirostat) note_mu(js[(size_t)k], fh.mu_next);
             }, copy_of, ctx_of);
             if constexpr (kLogprobs)
                 for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());

@@ -46,6 +46,7 @@ inline const char* shift_refusal(const Request& r, int n_prompt, int max_ctx)
     if (r.table >= 0) return "generate_shifting: a bias table is bound by position (its `until`) and is not carried through a shift: refused with keep >= 0";
     if (r.n_top >= 0) return "generate_shifting: log-prob records are kept per position and are not carried through a shift: refused with keep >= 0";
     if (r.fsm_start >= 0) return "generate_shifting: an automaton's states are kept per position and are not carried through a shift: refused with keep >= 0";
+    if (r.miro_tau != 0.f) return "generate_shifting: mirostat's mu is kept per position and is not carried through a shift: refused with keep >= 0";
     if (r.stream >= (1u << 24)) return "generate_shifting: stream >= 2^24 (a shifted sequence draws on stream + (shifts << 24)): refused with keep >= 0";
     if (!shift_ok(max_ctx, r.shift_keep, r.shift_drop)) return "generate_shifting: keep + drop do not fit a full window";
     if (n_prompt >= max_ctx) return "generate_shifting: the prompt fills the window";

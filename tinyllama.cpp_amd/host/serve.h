@@ -386,6 +386,7 @@ class ServeQueue {
                 const Slot s = slots_[(size_t)q];
                 if (s.job < 0) continue;
                 if constexpr (Pick::kLogprobs) pick_.collect(q, s.job, s.lp_from, s.cur - s.lp_from);
+                if constexpr (Pick::kMirostat) pick_.read_mu(q, s.job, s.cur);                          // (the mu its next id is drawn under goes with it)
                 ready_.push_back(Ready{s.job, s.set, s.cur, s.last});
                 release_slot(q);
             }
@@ -416,6 +417,7 @@ class ServeQueue {
                 apply_.join(q, r.cur, r.last, row.data());
                 pick_.apply(q, r.j, (int)prompts_[(size_t)r.j].size());                                // (travels with the prompt: also when a sequence moves in the tail)
                 if constexpr (Pick::kFsm) pick_.bind_state(q, r.j, r.cur);                              // (... at its current position, with the state the host read)
+                if constexpr (Pick::kMirostat) pick_.bind_mu(q, r.j, r.cur);                            // (... and with the mu the host read)
                 n_live_++;
             }
         }

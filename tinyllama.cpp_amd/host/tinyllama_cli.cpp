@@ -67,6 +67,10 @@ Optional args.
            [default=1: off]. With --topk 32003: over the whole vocabulary. Not with -greedy or --score.
 --min-p F : draw only from ids at least F times as likely as the most likely one. F must be gte 0 and lte 1. [default=0: off].
            Not with -greedy or --score.
+--mirostat N : 2: Mirostat v2 sampling (the surprise of the text is held at a target); 0: off; 1 (Mirostat v1) is not implemented. [default=0].
+--mirostat-ent F : Mirostat's target surprise tau in bits. F must be gt 0 and lte 32. [default=5.0].
+--mirostat-lr F : Mirostat's learning rate eta. F must be gt 0 and lte 1. [default=0.1].
+           Not with -greedy, --top-p / --min-p, --score, --embed or the context shift.
 --repeat-penalty R : ids the answer or the prompt already holds are made less likely: a positive logit is divided by R, a negative
            one multiplied. R must be gte 0.125 and lte 8. [default=1: off]. Works with -greedy too. Not with --score.
 --frequency-penalty F : subtract F from the logit of such an id once per occurrence. |F| must be lte 100. [default=0: off].
@@ -110,6 +114,9 @@ struct Options {
     int min_new = 0;
     int logprobs = -1;                       // --logprobs N (-1: off)
     float top_p = 1.f, min_p = 0.f;          // --top-p / --min-p ((1, 0): off)
+    int mirostat = 0;                        // --mirostat (0: off; 2: Mirostat v2)
+    float miro_tau = 5.f, miro_eta = 0.1f;   // --mirostat-ent / --mirostat-lr
+    bool miro_given = false;                 // any of the three flags was given
     bool cut_given = false;
     bool cuts() const { return !(top_p == 1.f && min_p == 0.f); }
     float rep = 1.f, freq = 0.f, pres = 0.f; // --repeat-penalty / --frequency-penalty / --presence-penalty ((1, 0, 0): off)
@@ -268,9 +275,20 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
     } else if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises() && fsm_start < 0) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
     } else {
-        const Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p,
-                        o.rep, o.freq, o.pres, o.last_n, true, fsm_start};
-        if (fsm_start >= 0) {
+        Request r{o.greedy ? 0 : o.topk, o.temp, seed, (*turn)++, o.constrained() ? 0 : -1, o.min_new, o.logprobs, o.top_p, o.min_p,
+                  o.rep, o.freq, o.pres, o.last_n, true, fsm_start};
+        if (o.mirostat == 2) {
+            r.miro_tau = o.miro_tau;
+            r.miro_eta = o.miro_eta;
+            RecordRows rows;
+            if (o.logprobs >= 0) {
+                logprob.resize(width);
+                top_id.resize(width * W);
+                top_lp.resize(width * W);
+                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
+            }
+            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm | kMirostat>(model, tokens, o.n_predict, tok.eos, r, rows);
+        } else if (fsm_start >= 0) {
             RecordRows rows;
             if (o.logprobs >= 0) {
                 logprob.resize(width);
@@ -479,6 +497,32 @@ int main(int argc, char const* argv[])
             if (text.empty() || used != text.size()) { std::cerr << "Invalid logprobs value.\n"; return -1; }
             if (v < 0 || v > GTEN_HIP_LOGPROBS_TOP) { std::cerr << "logprobs must be gte 0 and lte " << GTEN_HIP_LOGPROBS_TOP << ".\n"; return -1; }
             o.logprobs = v;
+        } else if (arg == "--mirostat") {
+            const std::string text = value("mirostat");
+            size_t used = 0;
+            int v = -1;
+            try { v = std::stoi(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size()) { std::cerr << "Invalid mirostat value.\n"; return -1; }
+            if (v == 1) { std::cerr << "mirostat 1 (Mirostat v1) is not implemented: use --mirostat 2.\n"; return -1; }
+            if (v != 0 && v != 2) { std::cerr << "mirostat must be 0 or 2.\n"; return -1; }
+            o.mirostat = v;
+            o.miro_given = true;
+        } else if (arg == "--mirostat-ent" || arg == "--mirostat-lr") {
+            const bool is_ent = arg == "--mirostat-ent";
+            const char* name = is_ent ? "mirostat-ent" : "mirostat-lr";
+            const std::string text = value(name);
+            size_t used = 0;
+            float v = -1.f;
+            try { v = std::stof(text, &used); } catch (...) { used = 0; }
+            if (text.empty() || used != text.size() || !std::isfinite(v)) { std::cerr << "Invalid " << name << " value.\n"; return -1; }
+            if (is_ent) {
+                if (!(v > 0.f && v <= 32.f)) { std::cerr << "mirostat-ent must be gt 0 and lte 32.\n"; return -1; }
+                o.miro_tau = v;
+            } else {
+                if (!(v > 0.f && v <= 1.f)) { std::cerr << "mirostat-lr must be gt 0 and lte 1.\n"; return -1; }
+                o.miro_eta = v;
+            }
+            o.miro_given = true;
         } else if (arg == "--top-p" || arg == "--min-p") {
             const bool is_top = arg == "--top-p";
             const char* name = is_top ? "top-p" : "min-p";
@@ -569,7 +613,7 @@ int main(int argc, char const* argv[])
     }
     if (o.embed_flag && o.embed_path.empty()) { std::cerr << "--pooling, --no-normalize and --layer need --embed.\n"; return -1; }
     if (!o.embed_path.empty() && (o.generation_flag || o.greedy || o.ids || o.seeded || !o.prompt.empty() || o.constrained() || o.min_new > 0 || o.logprobs >= 0 ||
-                                  o.cut_given || o.pen_given || o.last_n > 0 || o.automaton() || o.shifting() || !o.score_path.empty())) {
+                                  o.cut_given || o.miro_given || o.pen_given || o.last_n > 0 || o.automaton() || o.shifting() || !o.score_path.empty())) {
         std::cerr << "--embed does not generate: it does not combine with -p, --score, --ids, -greedy or any flag that samples, constrains or extends generation.\n";
         return -1;
     }
@@ -579,6 +623,10 @@ int main(int argc, char const* argv[])
         return -1;
     }
     if (o.shifting() && !shift_ok(o.ctx, o.shift_keep, o.shift_drop)) { std::cerr << "ctx-shift: KEEP + DROP do not fit the window of " << o.ctx << " positions.\n"; return -1; }
+    if (o.mirostat == 2 && o.greedy) { std::cerr << "mirostat needs top-k sampling: not with -greedy.\n"; return -1; }
+    if (o.mirostat == 2 && o.cut_given) { std::cerr << "mirostat and top-p / min-p do not compose: give one of them.\n"; return -1; }
+    if (o.miro_given && !o.score_path.empty()) { std::cerr << "mirostat does not apply to --score.\n"; return -1; }
+    if (o.mirostat == 2 && o.shifting()) { std::cerr << "mirostat does not work with the context shift yet.\n"; return -1; }
     if (o.cut_given && o.greedy) { std::cerr << "top-p and min-p need top-k sampling: not with -greedy.\n"; return -1; }
     if (o.cut_given && !o.score_path.empty()) { std::cerr << "top-p and min-p do not apply to --score.\n"; return -1; }
     if (o.pen_given && !o.score_path.empty()) { std::cerr << "the repeat, frequency and presence penalties do not apply to --score.\n"; return -1; }

@@ -69,6 +69,10 @@ class GtenHost:
                    "gten_host_fsm_n_states", "gten_host_fsm_tables", "gten_host_model_set_fsm", "gten_host_batch_set_fsm", "gten_host_model_fsm_info",
                    "gten_host_batch_fsm_info", "gten_host_model_set_seq_fsm", "gten_host_batch_set_seq_fsm", "gten_host_model_fsm_states",
                    "gten_host_batch_fsm_states", "gten_host_batch_fsm_decoder", "gten_host_model_generate_fsm", "gten_host_batch_generate_fsm", "gten_host_batch_serve_fsm"]
+    # include/gten_host_mirostat.h (a sequence's Mirostat v2 binding on a model's or a batch's decoder)
+    MIROSTAT_SYMBOLS = ["gten_host_model_set_mirostat", "gten_host_batch_set_mirostat", "gten_host_model_mirostat_info", "gten_host_batch_mirostat_info",
+                        "gten_host_model_mirostat_mus", "gten_host_batch_mirostat_mus", "gten_host_model_generate_mirostat",
+                        "gten_host_batch_generate_mirostat", "gten_host_batch_serve_mirostat"]
     # include/gten_host_regex.h (regular expressions as ranges of an automaton pool, host/capi_regex.cpp)
     REGEX_SYMBOLS = ["gten_host_fsm_set_vocab", "gten_host_tokenizer_vocab_bytes", "gten_host_fsm_add_regex", "gten_host_regex_byte_dfa",
                      "gten_host_fsm_n_regex"]
@@ -195,6 +199,12 @@ class GtenHost:
         self._json_schema_regex = _sig(L, "gten_host_json_schema_regex", C.c_longlong, [C.c_char_p, ci, ci, vp, C.c_longlong, vp, C.c_longlong])
         self._m_set_fsm = _sig(L, "gten_host_model_set_fsm", ci, [vp, vp])
         self._b_set_fsm = _sig(L, "gten_host_batch_set_fsm", ci, [vp, vp])
+        self._m_set_mirostat = _sig(L, "gten_host_model_set_mirostat", ci, [vp, C.c_float, C.c_float, C.c_int32, ci])
+        self._b_set_mirostat = _sig(L, "gten_host_batch_set_mirostat", ci, [vp, ci, C.c_float, C.c_float, C.c_int32, ci])
+        self._m_mirostat_info = _sig(L, "gten_host_model_mirostat_info", ci, [vp, vp, vp, vp])
+        self._b_mirostat_info = _sig(L, "gten_host_batch_mirostat_info", ci, [vp, vp, vp, vp])
+        self._m_mirostat_mus = _sig(L, "gten_host_model_mirostat_mus", ci, [vp, ci, ci, vp])
+        self._b_mirostat_mus = _sig(L, "gten_host_batch_mirostat_mus", ci, [vp, ci, ci, ci, vp])
         self._m_fsm_info = _sig(L, "gten_host_model_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
         self._b_fsm_info = _sig(L, "gten_host_batch_fsm_info", ci, [vp, C.POINTER(ci), vp, vp])
         self._m_set_seq_fsm = _sig(L, "gten_host_model_set_seq_fsm", ci, [vp, ci, ci])
@@ -215,6 +225,14 @@ class GtenHost:
         self._bserve_fsm = _sig(L, "gten_host_batch_serve_fsm", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                      C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
                                                                      vp, vp])
+        self._generate_miro = _sig(L, "gten_host_model_generate_mirostat", ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.c_uint64, C.c_uint32, ci, ci, ci,
+                                                                                C.c_float, C.c_float, vp, vp, vp, pen, ci, vp, C.c_float, C.c_float])
+        self._bgen_miro = _sig(L, "gten_host_batch_generate_mirostat", ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, C.c_float, C.c_uint64, vp, vp, vp, vp, vp,
+                                                                            vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen, vp, vp,
+                                                                            vp, vp, C.c_float, C.c_float])
+        self._bserve_miro = _sig(L, "gten_host_batch_serve_mirostat", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
+                                                                           C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
+                                                                           vp, vp, vp, vp, C.c_float, C.c_float])
         self._bserve_sessions = _sig(L, "gten_host_batch_serve_sessions", ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci,
                                                                                C.c_float, C.c_uint64, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, C.c_float, pen,
                                                                                vp, vp, vp])
@@ -800,6 +818,17 @@ class Fsm:
         self.close()
 
 
+MIRO_MU_DEFAULT = -(1 << 31)                                    # GTEN_HIP_MIRO_MU_DEFAULT: mu starts at 2 * tau_q
+
+
+def _mirostat_info(fn, h, n):
+    tq, eq, ps = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    on = fn(h, _ptr(tq), _ptr(eq), _ptr(ps))
+    if on < 0:
+        raise GtenHipError(f"mirostat_info rc={on}")
+    return tq, eq, ps, bool(on)
+
+
 def _fsm_info(fn, h, n):
     st, ps, S = np.zeros(n, np.int32), np.zeros(n, np.int32), C.c_int(0)
     on = fn(h, C.byref(S), _ptr(st), _ptr(ps))
@@ -1286,6 +1315,27 @@ class HostModel:
         if rc:
             raise GtenHipError(f"set_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
 
+    def set_mirostat_rc(self, tau, eta=0.1, mu_q16=None, pos=0):
+        return self.host._m_set_mirostat(self.h, C.c_float(tau), C.c_float(eta), int(MIRO_MU_DEFAULT if mu_q16 is None else mu_q16), int(pos))
+
+    def set_mirostat(self, tau, eta=0.1, mu_q16=None, pos=0):
+        """the ids from position pos on are drawn under Mirostat v2 (tau, eta), mu starting at mu_q16 (Q16; None: 2 tau); tau 0 unbinds"""
+        rc = self.set_mirostat_rc(tau, eta, mu_q16, pos)
+        if rc:
+            raise GtenHipError(f"set_mirostat rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def mirostat_info(self):
+        """(tau_q int32[1], eta_q int32[1], binding position int32[1], whether a sequence was ever bound)"""
+        return _mirostat_info(self.host._m_mirostat_info, self.h, 1)
+
+    def mirostat_mus(self, n_from, count):
+        """entries [n_from, n_from + count) of the sequence's mu row (Q16)"""
+        out = np.zeros(max(count, 1), np.int32)
+        rc = self.host._m_mirostat_mus(self.h, int(n_from), int(count), _ptr(out))
+        if rc:
+            raise GtenHipError(f"mirostat_mus rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return out[:count].copy()
+
     def fsm_info(self):
         """(states of the decoder's pool, binding state int32[1], binding position int32[1], whether a sequence was ever bound)"""
         return _fsm_info(self.host._m_fsm_info, self.h, 1)
@@ -1327,6 +1377,22 @@ class HostModel:
             raise GtenHipError(f"generate_fsm rc={total}: {self.host.hip._err().decode(errors='replace')}")
         ids = buf[:total].copy()
         return (ids, int(ended[0]), lp[:total].copy(), ti[:total].copy(), tl[:total].copy()) if ask else (ids, int(ended[0]))
+
+    def generate_mirostat(self, prompt, max_tokens, tau, eta=0.1, eos=-1, top_k=40, temp=1.0, seed=0, stream=0, rep=1.0, freq=0.0, pres=0.0, last_n=0,
+                          count_prompt=True, top_p=1.0, min_p=0.0, table=-1, min_new=0, fsm_start=-1):
+        """generate_fsm() under Mirostat v2 (include/gten_host_mirostat.h): the surprise of the new ids is held at tau bits with learning
+        rate eta (tau 0: off).  Returns the ids.  A cut beside Mirostat is refused."""
+        width = max(max_tokens, len(prompt))
+        buf = np.zeros(width, np.int32)
+        buf[: len(prompt)] = prompt
+        pen = _penalty_arg(1, float(rep), float(freq), float(pres), int(last_n), bool(count_prompt))
+        ended = np.zeros(1, np.int32)
+        total = self.host._generate_miro(self.h, _ptr(buf), len(prompt), max_tokens, eos, int(top_k), float(temp), C.c_uint64(int(seed)),
+                                         C.c_uint32(int(stream)), int(table), int(min_new), -1, C.c_float(top_p), C.c_float(min_p), None, None, None,
+                                         C.byref(pen), int(fsm_start), _ptr(ended), C.c_float(tau), C.c_float(eta))
+        if total < 0:
+            raise GtenHipError(f"generate_mirostat rc={total}: {self.host.hip._err().decode(errors='replace')}")
+        return buf[:total].copy()
 
     def generate_regex(self, prompt, max_tokens, pattern, vocab, eos=-1, **kw):
         """generate_fsm() bound to `pattern` (None: not bound): a pool of that one pattern over `vocab` (what Fsm.set_vocab takes) becomes
@@ -1692,6 +1758,27 @@ class HostBatch:
         if rc:
             raise GtenHipError(f"batch_set_fsm rc={rc}: {self.host.hip._err().decode(errors='replace')}")
 
+    def set_mirostat_rc(self, seq, tau, eta=0.1, mu_q16=None, pos=0):
+        return self.host._b_set_mirostat(self.h, int(seq), C.c_float(tau), C.c_float(eta), int(MIRO_MU_DEFAULT if mu_q16 is None else mu_q16), int(pos))
+
+    def set_mirostat(self, seq, tau, eta=0.1, mu_q16=None, pos=0):
+        """sequence seq's ids from position pos on are drawn under Mirostat v2 (tau, eta), mu starting at mu_q16 (Q16; None: 2 tau); tau 0 unbinds"""
+        rc = self.set_mirostat_rc(seq, tau, eta, mu_q16, pos)
+        if rc:
+            raise GtenHipError(f"batch_set_mirostat rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+
+    def mirostat_info(self):
+        """(tau_q int32[n_seq], eta_q int32[n_seq], binding position int32[n_seq], whether one was ever bound)"""
+        return _mirostat_info(self.host._b_mirostat_info, self.h, self.n_seq)
+
+    def mirostat_mus(self, seq, n_from, count):
+        """entries [n_from, n_from + count) of sequence seq's mu row (Q16)"""
+        out = np.zeros(max(count, 1), np.int32)
+        rc = self.host._b_mirostat_mus(self.h, int(seq), int(n_from), int(count), _ptr(out))
+        if rc:
+            raise GtenHipError(f"batch_mirostat_mus rc={rc}: {self.host.hip._err().decode(errors='replace')}")
+        return out[:count].copy()
+
     def fsm_info(self):
         """(states of the shared decoder's pool, binding state int32[n_seq], binding position int32[n_seq], whether one was ever bound)"""
         return _fsm_info(self.host._b_fsm_info, self.h, self.n_seq)
@@ -1765,6 +1852,32 @@ class HostBatch:
                                  *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
                                  *args, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended))
         return (ids, stats, ended) if n_top is None else (ids, stats, ended, *rec)
+
+    def generate_mirostat(self, prompts, max_tokens, tau, eta=0.1, eos=-1, top_k=40, temp=1.0, seed=0, streams=None, rep=1.0, freq=0.0, pres=0.0,
+                          last_n=0, count_prompt=True, top_p=1.0, min_p=0.0, tables=None, min_new=None, fsm_start=-1):
+        """generate_fsm() with a Mirostat request per sequence (tau / eta a scalar or a list; tau 0: off): the ids per sequence"""
+        n = self.n_seq
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
+        ta = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, np.float32), (n,)))
+        et = np.ascontiguousarray(np.broadcast_to(np.asarray(eta, np.float32), (n,)))
+        return self._generate(self.host._bgen_miro, "batch_generate_mirostat", prompts, max_tokens, eos,
+                              _request_args(n, top_k, temp, seed) + _full_args(n, (streams, np.uint32), (tables, np.int32), (min_new, np.int32)),
+                              [None, 0, None, None, None] + _cut_args(n, top_p, min_p) + [C.byref(pen), _ptr(st), _ptr(ended), _ptr(ta), _ptr(et),
+                                                                                        C.c_float(0.0), C.c_float(0.1)])
+
+    def serve_mirostat(self, prompts, max_tokens, eos, top_k, temp, seed, tau, eta=0.1, rep=1.0, freq=0.0, pres=0.0, last_n=0, count_prompt=True,
+                       top_p=1.0, min_p=0.0, tables=None, min_new=None, fsm_start=-1, slice_steps=16, max_new=0, max_new_each=None):
+        """serve_fsm() with a Mirostat request per prompt (tau / eta a scalar or a list; tau 0: off): (ids per prompt, stats)"""
+        n = len(prompts)
+        pen = _penalty_arg(n, rep, freq, pres, last_n, count_prompt)
+        st, ended = np.ascontiguousarray(np.broadcast_to(np.asarray(fsm_start, np.int32), (n,))), np.zeros(n, np.int32)
+        ta = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, np.float32), (n,)))
+        et = np.ascontiguousarray(np.broadcast_to(np.asarray(eta, np.float32), (n,)))
+        return self._serve(self.host._bserve_miro, "batch_serve_mirostat", prompts, max_tokens, eos, slice_steps, max_new, max_new_each,
+                           *_request_args(n, top_k, temp, seed), *_full_args(n, (tables, np.int32), (min_new, np.int32)),
+                           None, 0, None, None, None, *_cut_args(n, top_p, min_p), C.byref(pen), _ptr(st), _ptr(ended), _ptr(ta), _ptr(et),
+                           C.c_float(0.0), C.c_float(0.1))
 
     def serve_regex(self, prompts, patterns, eos, vocab, max_tokens, top_k=0, temp=1.0, seed=0, **kw):
         """serve_fsm() with one pattern (or None: not bound) per prompt: a pool of the DISTINCT patterns over `vocab` (what Fsm.set_vocab
