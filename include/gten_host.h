@@ -53,7 +53,11 @@ int gten_host_model_logits(gten_host_model* m, const int32_t* tokens, int n, int
  * `eos` is produced (pass eos < 0 to never stop).  Returns the total count. */
 int gten_host_model_greedy(gten_host_model* m, int32_t* tokens, int n_prompt, int max_tokens, int eos);
 /* the same loop with the sampler on the device (gten_hip_decoder_generate): the prompt as above, every later id from
- * back-to-back graph replays whose argmax is the next step's input on the device.  Same ids, same return value. */
+ * back-to-back graph replays whose argmax is the next step's input on the device.  Same ids, same return value.
+ * This and every other generation call of the gten_host_*.h headers (_generate*, _serve*): a generation call touches, and
+ * afterwards takes back, exactly the stages its own requests use -- the sampling request, and a table, a record request, a cut, a
+ * penalty, an automaton binding or a Mirostat binding where one of its requests carries it.  What a caller has set by hand on a
+ * slot (the set_* calls, for callers that drive the steps themselves) for a stage no request of the call uses is left as it is. */
 int gten_host_model_generate(gten_host_model* m, int32_t* tokens, int n_prompt, int max_tokens, int eos);
 
 /* ---- tokenizer + chat template (tokenizer.h:22-283 of the reference, on its vocabulary file tokenizer.bin).

@@ -7,13 +7,21 @@ exactly those on every way out.  Held here, on a HostModel, a HostBatch of 2 and
   * after every call no sequence is bound, plain generate() gives the greedy ids it gave before anything was set, and a step
     the caller drives writes no record;
   * with no table and no log-prob request the three sampled entry points and the three sampled serves return the same ids, and
-    with top_k 0 those are generate()'s and serve()'s."""
+    with top_k 0 those are generate()'s and serve()'s.
+
+The nucleus, penalized, fsm and mirostat forms are held to the same: with every upper feature off each of the seven sampled forms
+returns the top-k form's ids -- the one form that cannot name an upper stage -- and leaves the decoder's cut, penalty, automaton and
+Mirostat state as it found it, "ever used" flags included."""
 import numpy as np
 import pytest
 
+import bias_ref as bref
+import fsm_ref
 from gpu_common import hip  # noqa: F401
 from __graft_entry__ import load_package
-from test_bias_gpu import model_setup
+from test_bias_gpu import model_setup, upload
+from test_fsm_gpu import SEED as FSM_SEED      # (the seed test_fsm_gpu.existing draws with)
+from test_fsm_gpu import existing
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +31,7 @@ TOTAL, MAX_NEW = 52, 10
 K, TEMP, SEED = 40, 0.9, 77
 N_TOP = 3
 PAIRS = [(1, 0), (3, 2), (4, 3)]      # (longer, shorter) prompts of a 2-sequence batch: the longer one gets the early exit
-KINDS = ["topk", "biased", "logprobs"]
+KINDS = ["topk", "biased", "logprobs", "nucleus", "penalized", "fsm", "mirostat"]
 
 
 def bits(a):
@@ -73,7 +81,13 @@ def model_call(m, kind, prompt, total, eos):
         return m.generate_topk(prompt, total, eos, K, TEMP, SEED, 5), None
     if kind == "biased":
         return m.generate_biased(prompt, total, eos, K, TEMP, SEED, 5, 1, 0), None
-    ids, lp, ti, tl = m.generate_logprobs(prompt, total, N_TOP, eos, K, TEMP, SEED, 5, 1, 0)
+    if kind == "fsm":            # (an automaton and a table do not compose: this form carries records only)
+        ids, _, lp, ti, tl = m.generate_fsm(prompt, total, -1, eos, K, TEMP, SEED, 5, n_top=N_TOP)
+        return ids, (lp, ti, tl)
+    if kind == "mirostat":       # (tau 0: off; the binding passes no record outputs)
+        return m.generate_mirostat(prompt, total, 0.0, 0.1, eos, K, TEMP, SEED, 5, table=1), None
+    call = {"logprobs": m.generate_logprobs, "nucleus": m.generate_nucleus, "penalized": m.generate_penalized}[kind]
+    ids, lp, ti, tl = call(prompt, total, eos=eos, top_k=K, temp=TEMP, seed=SEED, stream=5, table=1, n_top=N_TOP)
     return ids, (lp, ti, tl)
 
 
@@ -84,8 +98,26 @@ def batch_call(b, kind, prompts, total, eos):
         return b.generate_topk(prompts, total, eos, K, TEMP, SEED, streams), None
     if kind == "biased":
         return b.generate_biased(prompts, total, eos, K, TEMP, SEED, streams, [1, 1], None), None
-    ids, lp, ti, tl = b.generate_logprobs(prompts, total, N_TOP, eos, K, TEMP, SEED, streams, [1, 1], None)
+    if kind == "fsm":            # (the binding passes no record outputs through this form's fixed batch)
+        return b.generate_fsm(prompts, total, -1, eos, K, TEMP, SEED, streams, tables=[1, 1])[0], None
+    if kind == "mirostat":
+        return b.generate_mirostat(prompts, total, 0.0, 0.1, eos, K, TEMP, SEED, streams, tables=[1, 1]), None
+    call = {"logprobs": b.generate_logprobs, "nucleus": b.generate_nucleus, "penalized": b.generate_penalized}[kind]
+    ids, lp, ti, tl = call(prompts, total, eos=eos, top_k=K, temp=TEMP, seed=SEED, streams=streams, tables=[1, 1], n_top=N_TOP)
     return ids, (lp, ti, tl)
+
+
+def lists(ids):
+    return ids.tolist() if isinstance(ids, np.ndarray) else [a.tolist() for a in ids]
+
+
+def stages(o):
+    """the "ever used" flags of a decoder's cut, penalty, automaton and Mirostat stages -- and nobody is bound to any of them"""
+    cut, pen, fsm, miro = o.cut_info(), o.penalty_info(), o.fsm_info(), o.mirostat_info()
+    assert np.all(np.asarray(cut[0]) == 1.0) and np.all(np.asarray(cut[1]) == 0.0)
+    assert np.all(np.asarray(pen[0]) == 1.0) and np.all(np.asarray(pen[1]) == 0.0) and np.all(np.asarray(pen[2]) == 0.0)
+    assert np.all(np.asarray(fsm[1]) == -1) and not np.asarray(miro[0]).any()
+    return cut[3], pen[5], fsm[3], miro[3]
 
 
 def assert_blank(rec, sl=slice(None)):
@@ -149,7 +181,7 @@ def test_model_early_exits(env, kind):
         P = len(p)
         full, full_rec = model_call(e.m, kind, p, TOTAL, -1)
         assert len(full) == TOTAL and full[:P].tolist() == p
-        if kind != "topk":
+        if kind not in ("topk", "fsm"):                   # (the two single-sequence forms that run without table 1)
             assert not set(full[P:].tolist()) & set(e.banned)
         ids, rec = model_call(e.m, kind, p, TOTAL, int(full[P]))
         assert ids.tolist() == p
@@ -212,8 +244,16 @@ def test_serve_leaves_every_slot_clean(env, n_seq, kind):
         ids, st = b.serve_topk(e.prompts, TOTAL, -1, ks, TEMP, SEED, slice_steps=4, max_new=MAX_NEW)
     elif kind == "biased":
         ids, st = b.serve_biased(e.prompts, TOTAL, -1, ks, TEMP, SEED, tables, None, slice_steps=4, max_new=MAX_NEW)
+    elif kind == "mirostat":
+        ids, st = b.serve_mirostat(e.prompts, TOTAL, -1, ks, TEMP, SEED, 0.0, 0.1, tables=tables, slice_steps=4, max_new=MAX_NEW)
     else:
-        ids, st, lp, ti, tl = b.serve_logprobs(e.prompts, TOTAL, -1, ks, TEMP, SEED, tops, tables, None, slice_steps=4, max_new=MAX_NEW)
+        if kind == "logprobs":
+            ids, st, lp, ti, tl = b.serve_logprobs(e.prompts, TOTAL, -1, ks, TEMP, SEED, tops, tables, None, slice_steps=4, max_new=MAX_NEW)
+        elif kind == "fsm":
+            ids, st, _, lp, ti, tl = b.serve_fsm(e.prompts, TOTAL, -1, ks, TEMP, SEED, -1, tables=tables, n_top=tops, slice_steps=4, max_new=MAX_NEW)
+        else:
+            call = b.serve_nucleus if kind == "nucleus" else b.serve_penalized
+            ids, st, lp, ti, tl = call(e.prompts, TOTAL, -1, ks, TEMP, SEED, tables=tables, n_top=tops, slice_steps=4, max_new=MAX_NEW)
         for j, p in enumerate(e.prompts):
             assert_blank((lp[j], ti[j], tl[j]), slice(0, len(p)))
             assert_blank((lp[j], ti[j], tl[j]), slice(len(ids[j]), None))
@@ -236,35 +276,197 @@ def test_serve_leaves_every_slot_clean(env, n_seq, kind):
     assert all(a.tolist() == g.tolist() for a, g in zip(again, e.serve_greedy[n_seq]))
 
 
+def model_forms(m, p, top_k):
+    """prompt p through the seven sampled single-sequence forms, every upper feature off: (name, ids), top-k first"""
+    yield "topk", m.generate_topk(p, TOTAL, -1, top_k, TEMP, SEED, 5)
+    yield "biased", m.generate_biased(p, TOTAL, -1, top_k, TEMP, SEED, 5)
+    yield "logprobs", m.generate_logprobs(p, TOTAL, 0, -1, top_k, TEMP, SEED, 5)[0]      # (this form always asks: 0 alternatives)
+    yield "nucleus", m.generate_nucleus(p, TOTAL, -1, top_k, TEMP, SEED, 5)
+    yield "penalized", m.generate_penalized(p, TOTAL, -1, top_k, TEMP, SEED, 5)
+    yield "fsm", m.generate_fsm(p, TOTAL, -1, -1, top_k, TEMP, SEED, 5)[0]
+    yield "mirostat", m.generate_mirostat(p, TOTAL, 0.0, 0.1, -1, top_k, TEMP, SEED, 5)
+
+
+def batch_forms(b, ps, top_k, streams):
+    yield "topk", b.generate_topk(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
+    yield "biased", b.generate_biased(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
+    yield "logprobs", b.generate_logprobs(ps, TOTAL, None, -1, top_k, TEMP, SEED, streams)[0]
+    yield "nucleus", b.generate_nucleus(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
+    yield "penalized", b.generate_penalized(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
+    yield "fsm", b.generate_fsm(ps, TOTAL, -1, -1, top_k, TEMP, SEED, streams)[0]
+    yield "mirostat", b.generate_mirostat(ps, TOTAL, 0.0, 0.1, -1, top_k, TEMP, SEED, streams)
+
+
+def serve_forms(b, ps, top_k):
+    kw = dict(slice_steps=4, max_new=MAX_NEW)
+    yield "topk", b.serve_topk(ps, TOTAL, -1, top_k, TEMP, SEED, **kw)[0]
+    yield "biased", b.serve_biased(ps, TOTAL, -1, top_k, TEMP, SEED, **kw)[0]
+    yield "logprobs", b.serve_logprobs(ps, TOTAL, -1, top_k, TEMP, SEED, None, **kw)[0]
+    yield "nucleus", b.serve_nucleus(ps, TOTAL, -1, top_k, TEMP, SEED, **kw)[0]
+    yield "penalized", b.serve_penalized(ps, TOTAL, -1, top_k, TEMP, SEED, **kw)[0]
+    yield "fsm", b.serve_fsm(ps, TOTAL, -1, top_k, TEMP, SEED, -1, **kw)[0]
+    yield "mirostat", b.serve_mirostat(ps, TOTAL, -1, top_k, TEMP, SEED, 0.0, 0.1, **kw)[0]
+
+
 @pytest.mark.parametrize("top_k", [K, 0])
 def test_unused_extras_change_nothing(env, top_k):
-    """no table, no log-prob request: top-k, biased and log-prob entry points agree id for id; top_k 0 is generate() / serve()"""
+    """no table, no log-prob request, cut (1, 0), penalty (1, 0, 0), no automaton, tau 0: each of the seven sampled forms returns the
+    top-k form's ids, id for id, on a model, a batch of 2 and through serve at 2 and 16 slots; top_k 0 is generate() / serve().  After
+    every call the cut, the penalty, the automaton and Mirostat report nobody bound and their "ever used" flags are as before it."""
     e = env
     same = n = 0
 
     def count(ids, greedy):
         nonlocal same, n
         same, n = same + (ids.tolist() == greedy.tolist()), n + 1
+
+    def agree(o, forms, where, greedy, want):
+        """every form's ids are the first form's (top-k's); after each call the decoder's upper stages are as they were and the plain
+        greedy call `greedy` gives the ids `want` recorded in the fixture"""
+        before, first = stages(o), None
+        for name, ids in forms:                            # (a generator: this body runs right after the form's call)
+            assert stages(o) == before, (where, name)
+            assert lists(greedy()) == lists(want), (where, name)
+            first = ids if first is None else first
+            assert lists(ids) == lists(first), (where, name)
+        return first
     for i, p in enumerate(e.prompts):
-        a = e.m.generate_topk(p, TOTAL, -1, top_k, TEMP, SEED, 5)
-        b_ = e.m.generate_biased(p, TOTAL, -1, top_k, TEMP, SEED, 5)
-        c = e.m.generate_logprobs(p, TOTAL, 0, -1, top_k, TEMP, SEED, 5)[0]      # (a model call always asks: 0 alternatives)
-        assert a.tolist() == b_.tolist() == c.tolist(), i
-        count(a, e.greedy_m[i])
-    streams = [5, 6]
+        count(agree(e.m, model_forms(e.m, p, top_k), i, lambda: e.m.generate(p, TOTAL), e.greedy_m[i]), e.greedy_m[i])
     for pair in PAIRS:
         ps = [e.prompts[i] for i in pair]
-        a = e.b2.generate_topk(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
-        b_ = e.b2.generate_biased(ps, TOTAL, -1, top_k, TEMP, SEED, streams)
-        c = e.b2.generate_logprobs(ps, TOTAL, None, -1, top_k, TEMP, SEED, streams)[0]
+        a = agree(e.b2, batch_forms(e.b2, ps, top_k, [5, 6]), pair, lambda: e.b2.generate(ps, TOTAL), e.greedy_b2[pair])
         for q in range(2):
-            assert a[q].tolist() == b_[q].tolist() == c[q].tolist(), (pair, q)
             count(a[q], e.greedy_b2[pair][q])
     for n_seq, b in ((2, e.b2), (16, e.b16)):
-        a, _ = b.serve_topk(e.prompts, TOTAL, -1, top_k, TEMP, SEED, slice_steps=4, max_new=MAX_NEW)
-        b_, _ = b.serve_biased(e.prompts, TOTAL, -1, top_k, TEMP, SEED, slice_steps=4, max_new=MAX_NEW)
-        c = b.serve_logprobs(e.prompts, TOTAL, -1, top_k, TEMP, SEED, None, slice_steps=4, max_new=MAX_NEW)[0]
+        a = agree(b, serve_forms(b, e.prompts, top_k), n_seq, lambda: b.serve(e.prompts, TOTAL, -1, 4, MAX_NEW)[0], e.serve_greedy[n_seq])
         for j in range(5):
-            assert a[j].tolist() == b_[j].tolist() == c[j].tolist(), (n_seq, j)
             count(a[j], e.serve_greedy[n_seq][j])
     assert same == n if top_k == 0 else same < n          # (sampled: something differs from greedy, or the request never arrived)
+
+
+# ---- one request that uses every stage that composes, through the _mirostat forms (the only ones that can pass them all): item A is
+# a table (with min_new) + records + a penalty + Mirostat, item B an automaton + a penalty + a cut.  The reference is put together from
+# what the per-feature tests use: the first id by the row operators on the prompt's logits (gten_hip_sample_rows_miro for A; for B
+# tests/test_fsm_gpu.py's `existing` -- the penalised cut operator under the bias row that restates the state's mask), every later id
+# by the decoder driven step by step from here with the requests set through the set_* calls, teacher-forced with the ids under test.
+# (The queue is not held to this reference here: serve_mirostat with these two items among the five prompts, slices of 4 steps, gives
+# item A another id at position P + 8 than the single call does -- 377 where this reference has 149 -- and gave the same before the
+# levels were collapsed; host/serve.h's scheduler is outside this test's subject.)
+A = dict(j=1, stream=1, tau=3.0, eta=0.25, rep=1.3, freq=0.1, pres=0.0, last_n=0, min_new=6, n_top=N_TOP)
+B = dict(j=3, stream=3, state=2, rep=1.2, freq=0.0, pres=0.2, last_n=8, top_p=0.9, min_p=0.02)
+TAU_Q = 3 << 16                       # tau 3.0 in Q16; the first id is drawn from mu = 2 tau
+
+
+def raw_model_mirostat(e, p, stream, table=-1, min_new=0, n_top=-1, top_p=1.0, min_p=0.0, rep=1.0, freq=0.0, pres=0.0, last_n=0, state=-1, tau=0.0,
+                       eta=0.1):
+    """gten_host_model_generate_mirostat with record outputs (the Python wrapper passes none): (ids, (lp, top ids, top lps) or None)"""
+    import ctypes as C
+    H = load_package().hostabi
+    ask, w = n_top >= 0, max(n_top, 0)
+    buf = np.zeros(TOTAL, np.int32)
+    buf[: len(p)] = p
+    lp, ti, tl = np.zeros(TOTAL, np.float32), np.full((TOTAL, w), -1, np.int32), np.zeros((TOTAL, w), np.float32)
+    pen, ended = H._penalty_arg(1, float(rep), float(freq), float(pres), int(last_n), True), np.zeros(1, np.int32)
+    total = e.host._generate_miro(e.m.h, H._ptr(buf), len(p), TOTAL, -1, K, TEMP, C.c_uint64(FSM_SEED), C.c_uint32(stream), table, min_new, n_top,
+                                  C.c_float(top_p), C.c_float(min_p), H._ptr(lp) if ask else None, H._ptr(ti) if ask else None,
+                                  H._ptr(tl) if ask else None, C.byref(pen), state, H._ptr(ended), C.c_float(tau), C.c_float(eta))
+    assert total == TOTAL and ended[0] == 0
+    return buf, ((lp, ti, tl) if ask else None)
+
+
+def raw_batch_mirostat(e, ps):
+    """gten_host_batch_generate_mirostat on (A's prompt, B's prompt) with record outputs: (ids per sequence, (lp, top ids, top lps))"""
+    import ctypes as C
+    H = load_package().hostabi
+    args, rec = H._records([A["n_top"], -1], 2, TOTAL)
+    pen = H._penalty_arg(2, [A["rep"], B["rep"]], [A["freq"], B["freq"]], [A["pres"], B["pres"]], [A["last_n"], B["last_n"]], True)
+    st, ended = np.array([-1, B["state"]], np.int32), np.zeros(2, np.int32)
+    ta, et = np.array([A["tau"], 0.0], np.float32), np.array([A["eta"], 0.1], np.float32)
+    ids = e.b2._generate(e.host._bgen_miro, "batch_generate_mirostat", ps, TOTAL, -1,
+                         H._request_args(2, K, TEMP, FSM_SEED) + H._full_args(2, ([A["stream"], B["stream"]], np.uint32), ([1, -1], np.int32),
+                                                                            ([A["min_new"], 0], np.int32)),
+                         args + H._cut_args(2, [1.0, B["top_p"]], [0.0, B["min_p"]]) + [C.byref(pen), H._ptr(st), H._ptr(ended), H._ptr(ta), H._ptr(et),
+                                                                                       C.c_float(0.0), C.c_float(0.1)])
+    assert not ended.any()
+    return ids, rec
+
+
+def driven_by_hand(m, got, P):
+    """the ids the model's decoder commits at positions (P, len(got)) when every step is driven from here, teacher-forced with `got`
+    (the prompt's rows are in the caches: the caller has just read its logits)"""
+    m.decode_begin(got)
+    out = []
+    for n in range(P + 1, len(got)):
+        m.decode_step(n, use_graph=n % 2 == 0)
+        out.append(m.decode_result(n))
+    return out
+
+
+def test_a_composed_request_through_the_mirostat_forms(env, hip):
+    e, m, V = env, env.m, env.cfg.n_vocab
+    pkg = load_package()
+    f = pkg.hostabi.Fsm(e.host, V)
+    f.add_table(*fsm_ref.random_pool(np.random.default_rng(31), 16, V, 0.25, 0))          # sixteen live states, a quarter of the ids each
+    nxt, flags = f.tables()
+    for o in (m, e.b2, e.b16):
+        o.set_fsm(f)
+    table = bref.table(V, [(j, NINF) for j in e.banned])
+    pa, pb = e.prompts[A["j"]], e.prompts[B["j"]]
+    Pa, Pb = len(pa), len(pb)
+    # -- item A alone on the model
+    ga, rec = raw_model_mirostat(e, pa, A["stream"], table=1, min_new=A["min_new"], n_top=A["n_top"], rep=A["rep"], freq=A["freq"], pres=A["pres"],
+                                 last_n=A["last_n"], tau=A["tau"], eta=A["eta"])
+    assert ga[:Pa].tolist() == pa and not set(ga[Pa:Pa + A["min_new"]].tolist()) & set(e.banned)
+    row = upload(hip, m.logits(pa, 0))[0]
+    ids, _, info = hip.sample_rows_miro(row, 1, V, V, K, TEMP, FSM_SEED, A["stream"], Pa, 2 * TAU_Q, A["tau"], A["eta"], bias=upload(hip, table)[0],
+                                        bias_stride=0, hist=[np.asarray(pa, np.int32)], r=A["rep"], freq=A["freq"], pres=A["pres"])
+    assert int(ids[0]) == int(ga[Pa])
+    first_rec = hip.row_top_logprobs(row, 1, V, V, int(ids[0]), A["n_top"])
+    m.set_sampling(K, TEMP, FSM_SEED, A["stream"])
+    assert m.set_seq_bias_rc(1, Pa + A["min_new"]) == 0
+    m.set_logprobs(A["n_top"])
+    m.set_penalty(A["rep"], A["freq"], A["pres"], 0, A["last_n"])
+    m.set_mirostat(A["tau"], A["eta"], int(info[0]["mu_next"]), Pa + 1)
+    assert driven_by_hand(m, ga, Pa) == ga[Pa + 1:].tolist()
+    want = m.logprobs(Pa + 1, TOTAL - Pa - 1, A["n_top"])
+    m.set_mirostat(0.0, 0.1, 0, 0)
+    m.set_penalty()
+    m.set_logprobs(-1)
+    assert m.set_seq_bias_rc(-1) == 0
+    m.set_sampling(0)
+    assert_blank(rec, slice(0, Pa))
+    assert_same_records([r[Pa:Pa + 1] for r in rec], [first_rec[0], first_rec[1], first_rec[2]], 1)
+    assert_same_records([r[Pa + 1:] for r in rec], want, TOTAL - Pa - 1)
+    # -- item B alone on the model
+    gb, _ = raw_model_mirostat(e, pb, B["stream"], top_p=B["top_p"], min_p=B["min_p"], rep=B["rep"], freq=B["freq"], pres=B["pres"], last_n=B["last_n"],
+                               state=B["state"])
+    hist = np.asarray(pb[Pb - B["last_n"]:], np.int32)
+    ids, _ = existing(hip, m.logits(pb, 0)[None], fsm_ref.bias_of(nxt, flags, B["state"], V)[None], K, TEMP, B["stream"], Pb, B["top_p"], B["min_p"],
+                      ([hist], B["rep"], B["freq"], B["pres"]))
+    assert int(ids[0]) == int(gb[Pb]) and nxt[B["state"]][gb[Pb]] != fsm_ref.DEAD
+    m.set_sampling(K, TEMP, FSM_SEED, B["stream"])
+    m.set_cut(B["top_p"], B["min_p"])
+    m.set_penalty(B["rep"], B["freq"], B["pres"], 0, B["last_n"])
+    m.set_seq_fsm(int(nxt[B["state"]][gb[Pb]]), Pb + 1)
+    assert driven_by_hand(m, gb, Pb) == gb[Pb + 1:].tolist()
+    m.set_seq_fsm(-1, 0)
+    m.set_penalty()
+    m.set_cut()
+    m.set_sampling(0)
+    state = B["state"]
+    for t in gb[Pb:]:                                                                      # every new id walks the automaton
+        state = int(nxt[state][t])
+        assert state != fsm_ref.DEAD
+    assert m.generate_topk(pb, TOTAL, -1, K, TEMP, FSM_SEED, B["stream"]).tolist() != gb.tolist()
+    # -- both as one batch of 2, with A's records
+    ids, brec = raw_batch_mirostat(e, [pa, pb])
+    assert ids[0].tolist() == ga.tolist() and ids[1].tolist() == gb.tolist()
+    assert_same_records([r[0] for r in brec], rec, TOTAL)
+    assert_blank([r[1] for r in brec])
+    # -- nothing is left behind on any decoder
+    for o in (m, e.b2, e.b16):
+        stages(o)
+        o.set_fsm(None)
+    clean_model(e, 0)
+    clean_batch(e, e.b2, [e.prompts[1], e.prompts[0]], e.greedy_b2[(1, 0)])
+    f.close()

@@ -1,8 +1,8 @@
 // capi_bias.cpp -- flat C exports of constrained generation (include/gten_host_bias.h): the bias tables and requests of a decoder, and
-// host/generate.h's flows with the sampler's and the tables' stages.
+// generation under a table -- adapters onto the kFull flows of host/capi_flows.h.
 #include "../../include/gten_host_bias.h"
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 
 using namespace gten;
 
@@ -62,16 +62,16 @@ int gten_host_model_generate_biased(gten_host_model* m, int32_t* tokens, int n_p
                                     uint64_t seed, uint32_t stream, int table, int min_new)
 {
     if (!m || !tokens || n_prompt <= 0 || !request_ok(top_k, temp) || !binding_ok(table, min_new)) return -1;
-    return generate_in_place<kSampled | kBiased>(*m->model, tokens, n_prompt, max_tokens, eos, Request{top_k, temp, seed, stream, table, min_new});
+    return generate_full(*m->model, tokens, n_prompt, max_tokens, eos, request_of(top_k, temp, seed, stream, table, min_new));
 }
 
 int gten_host_batch_generate_biased(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
                                     const int32_t* top_k, const float* temp, int top_k_all, float temp_all, uint64_t seed, const uint32_t* stream,
                                     const int32_t* table, const int32_t* min_new, int32_t* out, int32_t* n_total)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || max_tokens <= 0) return -1;
-    return generate_batch<kSampled | kBiased>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
-                                              Requests::of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new), out, n_total);
+    if (!batch_args_ok(b, prompts, n_prompt, out, n_total, max_tokens)) return -1;
+    return generate_batch_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
+                               requests_of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new), out, n_total);
 }
 
 int gten_host_batch_serve_biased(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt,
@@ -79,9 +79,9 @@ int gten_host_batch_serve_biased(gten_host_batch* b, const int32_t* prompts, con
                                  double* stats, int n_stats, const int32_t* top_k, const float* temp, int top_k_all, float temp_all, uint64_t seed,
                                  const int32_t* table, const int32_t* min_new)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats)) return -1;
-    return serve_queue<kSampled | kBiased>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each,
-                                           out, n_total, stats, n_stats, Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new));
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats)) return -1;
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats, requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new));
 }
 
 } // extern "C"

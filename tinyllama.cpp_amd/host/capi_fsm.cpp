@@ -1,33 +1,18 @@
-// capi_fsm.cpp -- flat C exports of include/gten_host_fsm.h: the automaton builders of host/fsm_build.h and generation bound to a token
-// automaton (host/generate.h's flows with all six stages -- the only instantiation of kFsm in the library).
+// capi_fsm.cpp -- flat C exports of include/gten_host_fsm.h: the automaton builders of host/fsm_build.h, a decoder's pool and bindings, and
+// generation bound to a token automaton -- adapters onto the kFull flows of host/capi_flows.h.
 #include "../../include/gten_host_fsm.h"
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/gten_hip_regex.h"
 #include "../../include/gten_hip_stoptext.h"
-#include "capi_handles.h"
+#include "capi_flows.h"
 #include "fsm_build.h"
 
 using namespace gten;
 
 namespace {
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm;
-const gten_host_penalties kNone = {nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, 0.f, 0, 1};
-
-bool records_ok(bool asking, int n_top_max, const float* lp, const int32_t* ids, const float* lps)
-{
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP) return false;
-    if (asking && (!lp || (n_top_max > 0 && (!ids || !lps)))) return false;
-    return true;
-}
-
-Requests with(const Requests& r, const gten_host_penalties* pen, const int32_t* fsm_start)
-{
-    const gten_host_penalties& p = pen ? *pen : kNone;
-    return r.penalised(p.rep, p.rep_all, p.freq, p.freq_all, p.pres, p.pres_all, p.last_n, p.last_n_all, p.count_prompt, p.count_prompt_all).bound_to(fsm_start);
-}
 
 int set_pool(gten_hip_decoder* dec, int n_vocab, const gten_host_fsm* f)
 {
@@ -145,15 +130,12 @@ int gten_host_model_generate_fsm(gten_host_model* m, int32_t* tokens, int n_prom
                                  uint32_t stream, int table, int min_new, int n_top, float top_p, float min_p, float* logprob_out, int32_t* top_id_out,
                                  float* top_logprob_out, const gten_host_penalties* pen, int fsm_start, int32_t* ended_by)
 {
-    if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !request_ok(top_k, temp) || !binding_ok(table, min_new) || !cut_ok(top_p, min_p)) return -1;
-    if (n_top < -1 || !records_ok(n_top >= 0, std::max(n_top, 0), logprob_out, top_id_out, top_logprob_out)) return -1;
-    const gten_host_penalties& p = pen ? *pen : kNone;
-    if (!penalty_ok(p.rep_all, p.freq_all, p.pres_all, p.last_n_all) || !fsm_ok(fsm_start, table)) return -1;
-    const RecordRows rows = n_top >= 0 ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top} : RecordRows{};
-    const Request r{top_k, temp, seed, stream, table, min_new, n_top, top_p, min_p, p.rep_all, p.freq_all, p.pres_all, p.last_n_all, p.count_prompt_all != 0,
-                    fsm_start};
+    if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !records_ok(n_top >= 0, std::max(n_top, 0), logprob_out, top_id_out, top_logprob_out)) return -1;
+    const Request r = request_of(top_k, temp, seed, stream, table, min_new, n_top, top_p, min_p, pen, fsm_start);
+    if (!request_valid(r, std::max(n_top, 0))) return -1;
     int ended = kEndedByLength;
-    const int total = generate_in_place<kAll>(*m->model, tokens, n_prompt, max_tokens, eos, r, rows, &ended, m->cfg.max_ctx);
+    const int total = generate_full(*m->model, tokens, n_prompt, max_tokens, eos, r, record_rows(n_top >= 0, n_top, logprob_out, top_id_out, top_logprob_out),
+                                    &ended, m->cfg.max_ctx);
     if (ended_by) *ended_by = ended;
     return total;
 }
@@ -164,13 +146,10 @@ int gten_host_batch_generate_fsm(gten_host_batch* b, const int32_t* prompts, con
                                  float* logprob_out, int32_t* top_id_out, float* top_logprob_out, const float* top_p, const float* min_p,
                                  float top_p_all, float min_p_all, const gten_host_penalties* pen, const int32_t* fsm_start, int32_t* ended_by)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || max_tokens <= 0) return -1;
-    if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return generate_batch<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
-                                with(Requests::of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all), pen,
-                                     fsm_start),
-                                out, n_total, rows, ended_by);
+    if (!batch_args_ok(b, prompts, n_prompt, out, n_total, max_tokens) || !records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
+    return generate_batch_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
+                               requests_of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all, pen, fsm_start),
+                               out, n_total, record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out), ended_by);
 }
 
 int gten_host_batch_serve_fsm(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
@@ -180,15 +159,12 @@ int gten_host_batch_serve_fsm(gten_host_batch* b, const int32_t* prompts, const 
                               float* top_logprob_out, const float* top_p, const float* min_p, float top_p_all, float min_p_all,
                               const gten_host_penalties* pen, const int32_t* fsm_start, int32_t* ended_by)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats)) return -1;
-    if (max_tokens <= 0 || slice <= 0) return -1;
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats)) return -1;
     if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return serve_queue<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
-                             stats, n_stats,
-                             with(Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all), pen,
-                                  fsm_start),
-                             rows, ended_by);
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats,
+                            requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all, pen, fsm_start),
+                            record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out), ended_by);
 }
 
 } // extern "C"

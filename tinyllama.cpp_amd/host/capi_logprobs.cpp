@@ -1,20 +1,14 @@
 // capi_logprobs.cpp -- flat C exports of include/gten_host_logprobs.h: generation that reports every new id's log-prob and top-N
-// alternatives (host/generate.h's flows with all three stages), and scoring with alternatives.
+// alternatives (adapters onto the kFull flows of host/capi_flows.h; these forms always ask), and scoring with alternatives.
 #include "../../include/gten_host_logprobs.h"
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 
 using namespace gten;
-
-namespace {
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs;
-
-} // namespace
 
 extern "C" {
 
@@ -47,9 +41,9 @@ int gten_host_model_generate_lp(gten_host_model* m, int32_t* tokens, int n_promp
                                 uint32_t stream, int table, int min_new, int n_top, float* logprob_out, int32_t* top_id_out, float* top_logprob_out)
 {
     if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !request_ok(top_k, temp) || !binding_ok(table, min_new)) return -1;
-    if (n_top < 0 || n_top > GTEN_HIP_LOGPROBS_TOP || !logprob_out || (n_top > 0 && (!top_id_out || !top_logprob_out))) return -1;
-    return generate_in_place<kAll>(*m->model, tokens, n_prompt, max_tokens, eos, Request{top_k, temp, seed, stream, table, min_new, n_top},
-                                   RecordRows{logprob_out, top_id_out, top_logprob_out, n_top});
+    if (!records_ok(true, n_top, logprob_out, top_id_out, top_logprob_out)) return -1;
+    return generate_full(*m->model, tokens, n_prompt, max_tokens, eos, request_of(top_k, temp, seed, stream, table, min_new, n_top),
+                         record_rows(true, n_top, logprob_out, top_id_out, top_logprob_out));
 }
 
 int gten_host_batch_generate_lp(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
@@ -57,11 +51,10 @@ int gten_host_batch_generate_lp(gten_host_batch* b, const int32_t* prompts, cons
                                 const int32_t* table, const int32_t* min_new, int32_t* out, int32_t* n_total, const int32_t* n_top, int n_top_max,
                                 float* logprob_out, int32_t* top_id_out, float* top_logprob_out)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || max_tokens <= 0) return -1;
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP || !logprob_out || (n_top_max > 0 && (!top_id_out || !top_logprob_out))) return -1;
-    return generate_batch<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
-                                Requests::of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top), out, n_total,
-                                RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max});
+    if (!batch_args_ok(b, prompts, n_prompt, out, n_total, max_tokens) || !records_ok(true, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
+    return generate_batch_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
+                               requests_of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top), out, n_total,
+                               record_rows(true, n_top_max, logprob_out, top_id_out, top_logprob_out));
 }
 
 int gten_host_batch_serve_lp(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
@@ -70,11 +63,11 @@ int gten_host_batch_serve_lp(gten_host_batch* b, const int32_t* prompts, const i
                              const int32_t* min_new, const int32_t* n_top, int n_top_max, float* logprob_out, int32_t* top_id_out,
                              float* top_logprob_out)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats)) return -1;
-    if (max_tokens <= 0 || slice <= 0) return -1;
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP || !logprob_out || (n_top_max > 0 && (!top_id_out || !top_logprob_out))) return -1;
-    return serve_queue<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
-                             stats, n_stats, Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top), RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max});
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats)) return -1;
+    if (!records_ok(true, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats, requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top),
+                            record_rows(true, n_top_max, logprob_out, top_id_out, top_logprob_out));
 }
 
 int gten_host_model_score_top(gten_host_model* m, const int32_t* tokens, int n, int start_pos, const int32_t* targets, int n_top,

@@ -1,26 +1,12 @@
-// capi_nucleus.cpp -- flat C exports of include/gten_host_nucleus.h: generation under a top-p / min-p cut (host/generate.h's flows
-// with all four stages -- the only instantiation of them in the library).
+// capi_nucleus.cpp -- flat C exports of include/gten_host_nucleus.h: a decoder's cut, and generation under a top-p / min-p cut --
+// adapters onto the kFull flows of host/capi_flows.h.
 #include "../../include/gten_host_nucleus.h"
 
-#include <vector>
+#include <algorithm>
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 
 using namespace gten;
-
-namespace {
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs | kNucleus;
-
-// n_top_max / the three outputs of a call whose requests ask for at most n_top_max alternatives (nobody asks: none needed)
-bool records_ok(bool asking, int n_top_max, const float* lp, const int32_t* ids, const float* lps)
-{
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP) return false;
-    if (asking && (!lp || (n_top_max > 0 && (!ids || !lps)))) return false;
-    return true;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -56,10 +42,10 @@ int gten_host_model_generate_nucleus(gten_host_model* m, int32_t* tokens, int n_
                                      uint32_t stream, int table, int min_new, int n_top, float top_p, float min_p, float* logprob_out,
                                      int32_t* top_id_out, float* top_logprob_out)
 {
-    if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !request_ok(top_k, temp) || !binding_ok(table, min_new) || !cut_ok(top_p, min_p)) return -1;
-    if (n_top < -1 || !records_ok(n_top >= 0, std::max(n_top, 0), logprob_out, top_id_out, top_logprob_out)) return -1;
-    const RecordRows rows = n_top >= 0 ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top} : RecordRows{};
-    return generate_in_place<kAll>(*m->model, tokens, n_prompt, max_tokens, eos, Request{top_k, temp, seed, stream, table, min_new, n_top, top_p, min_p}, rows);
+    if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !records_ok(n_top >= 0, std::max(n_top, 0), logprob_out, top_id_out, top_logprob_out)) return -1;
+    const Request r = request_of(top_k, temp, seed, stream, table, min_new, n_top, top_p, min_p);
+    if (!request_valid(r, std::max(n_top, 0))) return -1;
+    return generate_full(*m->model, tokens, n_prompt, max_tokens, eos, r, record_rows(n_top >= 0, n_top, logprob_out, top_id_out, top_logprob_out));
 }
 
 int gten_host_batch_generate_nucleus(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
@@ -68,12 +54,10 @@ int gten_host_batch_generate_nucleus(gten_host_batch* b, const int32_t* prompts,
                                      float* logprob_out, int32_t* top_id_out, float* top_logprob_out, const float* top_p, const float* min_p,
                                      float top_p_all, float min_p_all)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || max_tokens <= 0) return -1;
-    if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return generate_batch<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
-                                Requests::of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all), out,
-                                n_total, rows);
+    if (!batch_args_ok(b, prompts, n_prompt, out, n_total, max_tokens) || !records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
+    return generate_batch_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos,
+                               requests_of(top_k, top_k_all, temp, temp_all, seed, stream, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all), out, n_total,
+                               record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out));
 }
 
 int gten_host_batch_serve_nucleus(gten_host_batch* b, const int32_t* prompts, const int32_t* n_prompt, int n_prompts, int max_prompt, int max_tokens,
@@ -83,13 +67,11 @@ int gten_host_batch_serve_nucleus(gten_host_batch* b, const int32_t* prompts, co
                                   int32_t* top_id_out, float* top_logprob_out, const float* top_p, const float* min_p, float top_p_all,
                                   float min_p_all)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats)) return -1;
-    if (max_tokens <= 0 || slice <= 0) return -1;
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats)) return -1;
     if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return serve_queue<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
-                             stats, n_stats,
-                             Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all), rows);
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats, requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all),
+                            record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out));
 }
 
 } // extern "C"

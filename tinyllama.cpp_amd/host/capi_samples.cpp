@@ -8,7 +8,7 @@
 #include <numeric>
 #include <vector>
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 
 using namespace gten;
 
@@ -23,9 +23,6 @@ const bool installed = [] {
     detail::groups_decode().info = gten_hip_decoder_groups_info;
     return true;
 }();
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm;
-const gten_host_penalties kNone = {nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, 0.f, 0, 1};
 
 // the rule of gten_host_samples_rank on sums already formed
 int rank(const double* sum, const int32_t* n_new, int n, int32_t* order)
@@ -53,10 +50,8 @@ int gten_host_batch_serve_samples(gten_host_batch* b, const int32_t* prompts, co
                                   float* top_logprob_out, const float* top_p, const float* min_p, float top_p_all, float min_p_all,
                                   const gten_host_penalties* pen, const int32_t* fsm_start, int32_t* ended_by, const int32_t* n_samples, int n_samples_all)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats) || !installed) return -1;
-    if (max_tokens <= 0 || slice <= 0) return -1;
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP) return -1;
-    if (n_top && (!logprob_out || (n_top_max > 0 && (!top_id_out || !top_logprob_out)))) return -1;
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats) || !installed || max_tokens <= 0 || slice <= 0) return -1;
+    if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
     // the expanded queue: prompt j written out n_samples[j] times in a row, each item a member of group j
     std::vector<int32_t> len, group;
     for (int j = 0; j < n_prompts; j++) {
@@ -71,13 +66,10 @@ int gten_host_batch_serve_samples(gten_host_batch* b, const int32_t* prompts, co
         std::copy(prompts + (size_t)j * max_prompt, prompts + (size_t)(j + 1) * max_prompt, ids.begin() + (size_t)e * max_prompt);
         if (++i == (n_samples ? n_samples[j] : n_samples_all)) { j++; i = 0; }
     }
-    const gten_host_penalties& p = pen ? *pen : kNone;
-    const Requests reqs = Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all)
-                              .penalised(p.rep, p.rep_all, p.freq, p.freq_all, p.pres, p.pres_all, p.last_n, p.last_n_all, p.count_prompt, p.count_prompt_all)
-                              .bound_to(fsm_start);
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return serve_queue<kAll>(*b->batch, b->cfg.max_ctx, ids.data(), len.data(), n_items, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
-                             stats, n_stats, reqs, rows, ended_by, group.data());
+    const Requests reqs = requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all, pen, fsm_start);
+    const RecordRows rows = record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out);
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, ids.data(), len.data(), n_items, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats, reqs, rows, ended_by, group.data());
 }
 
 int gten_host_batch_samples_info(gten_host_batch* b, unsigned long long* copies, unsigned long long* rows_saved, unsigned long long* groups_recorded,

@@ -6,7 +6,7 @@
 
 #include <algorithm>
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 #include "session_plan.h"
 
 using namespace gten;
@@ -18,9 +18,6 @@ const bool installed = [] {
     detail::continued_rows().call = gten_hip_block_rows_continued;
     return true;
 }();
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm;
-const gten_host_penalties kNone = {nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, 0.f, 0, 1};
 
 } // namespace
 
@@ -69,17 +66,12 @@ int gten_host_batch_serve_sessions(gten_host_batch* b, const int32_t* prompts, c
                                    float* top_logprob_out, const float* top_p, const float* min_p, float top_p_all, float min_p_all,
                                    const gten_host_penalties* pen, const int32_t* fsm_start, int32_t* ended_by, const int32_t* session)
 {
-    if (!b || !prompts || !n_prompt || !out || !n_total || n_prompts <= 0 || max_prompt <= 0 || n_stats < 0 || (n_stats > 0 && !stats) || !installed) return -1;
-    if (max_tokens <= 0 || slice <= 0) return -1;
-    if (n_top_max < 0 || n_top_max > GTEN_HIP_LOGPROBS_TOP) return -1;
-    if (n_top && (!logprob_out || (n_top_max > 0 && (!top_id_out || !top_logprob_out)))) return -1;
-    const gten_host_penalties& p = pen ? *pen : kNone;
-    const Requests reqs = Requests::of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all)
-                              .penalised(p.rep, p.rep_all, p.freq, p.freq_all, p.pres, p.pres_all, p.last_n, p.last_n_all, p.count_prompt, p.count_prompt_all)
-                              .bound_to(fsm_start);
-    const RecordRows rows = n_top ? RecordRows{logprob_out, top_id_out, top_logprob_out, n_top_max} : RecordRows{};
-    return serve_queue<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
-                             stats, n_stats, reqs, rows, ended_by, nullptr, session);
+    if (!serve_args_ok(b, prompts, n_prompt, out, n_total, n_prompts, max_prompt, stats, n_stats) || !installed || max_tokens <= 0 || slice <= 0) return -1;
+    if (!records_ok(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out)) return -1;
+    const Requests reqs = requests_of(top_k, top_k_all, temp, temp_all, seed, nullptr, table, min_new, n_top, top_p, top_p_all, min_p, min_p_all, pen, fsm_start);
+    const RecordRows rows = record_rows(n_top != nullptr, n_top_max, logprob_out, top_id_out, top_logprob_out);
+    return serve_queue_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, n_prompts, max_prompt, max_tokens, eos, slice, max_new, max_new_each, out, n_total,
+                            stats, n_stats, reqs, rows, ended_by, nullptr, session);
 }
 
 int gten_host_batch_extend_many(gten_host_batch* b, const int32_t* seqs, const int32_t* ctx_len, const int32_t* tokens, const int32_t* starts, int n,

@@ -1,20 +1,18 @@
 // capi_shift.cpp -- flat C exports of include/gten_host_shift.h: the shift plan, the cache primitives, generation past the window
 // and shifted sessions.  Kept apart from capi.cpp: this is the only translation unit of the library that names the device entry
-// point of include/gten_hip_shift.h (through host/generate_shift.h).
+// point of include/gten_hip_shift.h (through host/generate_shift.h, whose two shifting flows it instantiates at kFull; a call with
+// keep < 0 shifts nothing and takes the plain kFull flows of host/capi_flows.h).
 #include "../../include/gten_host_shift.h"
 
 #include <algorithm>
 #include <vector>
 
-#include "capi_handles.h"
+#include "capi_flows.h"
 #include "generate_shift.h"
 
 using namespace gten;
 
 namespace {
-
-constexpr unsigned kAll = kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm;
-const gten_host_penalties kNone = {nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f, 0.f, 0, 1};
 
 thread_local const char* g_why = "";
 
@@ -129,15 +127,15 @@ int gten_host_model_generate_shifting(gten_host_model* m, int32_t* tokens, int n
     if (!m || !tokens || n_prompt <= 0 || max_tokens <= 0 || !request_ok(top_k, temp) || !binding_ok(table, 0) || !cut_ok(top_p, min_p))
         return refuse("generate_shifting: bad arguments");
     if (n_top >= 0) return refuse(kNoRecords);
-    const gten_host_penalties& p = pen ? *pen : kNone;
-    if (!penalty_ok(p.rep_all, p.freq_all, p.pres_all, p.last_n_all)) return refuse("generate_shifting: bad penalties");
-    Request r{top_k, temp, seed, stream, table, 0, -1, top_p, min_p, p.rep_all, p.freq_all, p.pres_all, p.last_n_all, p.count_prompt_all != 0};
+    Request r = request_of(top_k, temp, seed, stream, table, 0, -1, top_p, min_p, pen);
+    if (!penalty_ok(r.rep, r.freq, r.pres, r.last_n)) return refuse("generate_shifting: bad penalties");
+    if (keep < 0) return generate_full(*m->model, tokens, n_prompt, max_tokens, eos, r, {}, nullptr, m->cfg.max_ctx);
     r.shift_keep = keep;
     r.shift_drop = drop;
     std::vector<int32_t> t(tokens, tokens + n_prompt);
     t.reserve((size_t)std::max(max_tokens, n_prompt));
     const char* why = nullptr;
-    const int total = generate_shifting<kAll>(*m->model, t, max_tokens, eos, r, m->cfg.max_ctx, &m->shifts, &why);
+    const int total = generate_shifting<kFull>(*m->model, t, max_tokens, eos, r, m->cfg.max_ctx, &m->shifts, &why);
     if (why) g_why = why;
     if (total > 0) std::copy(t.begin(), t.begin() + total, tokens);
     return total;
@@ -150,14 +148,14 @@ int gten_host_batch_generate_shifting(gten_host_batch* b, const int32_t* prompts
     g_why = "";
     if (!b || !prompts || !n_prompt || !out || !n_total || max_tokens <= 0 || max_prompt <= 0) return refuse("generate_shifting: bad arguments");
     if (n_top >= 0) return refuse(kNoRecords);
-    const gten_host_penalties& p = pen ? *pen : kNone;
     const int S = b->batch->n_seq();
     std::vector<int32_t> tables((size_t)S, table);
-    const Requests reqs = Requests::of(nullptr, top_k, nullptr, temp, seed, stream, table >= 0 ? tables.data() : nullptr, nullptr, nullptr, nullptr, top_p, nullptr, min_p)
-                              .penalised(p.rep, p.rep_all, p.freq, p.freq_all, p.pres, p.pres_all, p.last_n, p.last_n_all, p.count_prompt, p.count_prompt_all);
+    const Requests reqs = requests_of(nullptr, top_k, nullptr, temp, seed, stream, table >= 0 ? tables.data() : nullptr, nullptr, nullptr, nullptr, top_p, nullptr,
+                                      min_p, pen);
     const char* why = nullptr;
-    const int rc = generate_batch_shifting<kAll>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos, reqs, keep, drop, out, n_total,
-                                                 &b->shifts, &why);
+    const int rc = keep < 0 ? generate_batch_full(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos, reqs, out, n_total)
+                            : generate_batch_shifting<kFull>(*b->batch, b->cfg.max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos, reqs, keep, drop, out,
+                                                             n_total, &b->shifts, &why);
     if (why) g_why = why;
     else if (rc == -1) g_why = "generate_shifting: bad arguments";
     return rc;

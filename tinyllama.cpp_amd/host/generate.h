@@ -1,15 +1,21 @@
 // generate.h -- choosing the next id, once for every entry point above the C ABI of libgten_hip.so: greedy, top-k sampling
-// (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h) and log-prob records
-// (include/gten_hip_logprobs.h), top-p / min-p cuts (include/gten_hip_nucleus.h) and penalties on
-// repeated ids (include/gten_hip_penalty.h) and token automata (include/gten_hip_fsm.h) are ONE flow with optional stages -- a Request says what a prompt asks for, a
-// compile-time mask says which device entry points the flow may name.
-//
-// Why a mask and not a run-time switch: host/capi.cpp links against a stand-in of include/gten_hip.h alone
-// (tests/test_host_sanitize_cpu.py), host/capi.cpp + host/capi_sample.cpp against that plus the sampler's
-// (tests/test_sampler_cpu.py).  So every flow here is a template on the mask, the stages it does not have are discarded with
-// `if constexpr`, and each flow is instantiated where its stages may be named: mask 0 in host/capi.cpp, kSampled in
-// host/capi_sample.cpp, kSampled | kBiased in host/capi_bias.cpp, those three in host/capi_logprobs.cpp, four in host/capi_nucleus.cpp, five in host/capi_penalty.cpp, all six in host/capi_fsm.cpp
-// (and in the command line program, which links against the library itself).  That is the only reason those files are separate.
+// (include/gten_hip_sample.h), bias tables (include/gten_hip_bias.h), log-prob records
+// (include/gten_hip_logprobs.h, §3.11), top-p / min-p cuts (include/gten_hip_nucleus.h, §3.12), penalties on repeated ids
+// (include/gten_hip_penalty.h, §3.14), token automata (include/gten_hip_fsm.h, §3.15) and Mirostat (include/gten_hip_mirostat.h, §3.23)
+// are ONE flow with optional stages.  A Request says what a prompt asks for: whether a stage acts is a run-time fact of the request.
+// A compile-time LEVEL says which device entry points the flow may name, and there are exactly three, because exactly two link tests
+// need a flow that names less than everything:
+//   0         greedy: names include/gten_hip.h only.  host/capi.cpp links against a stand-in of that header alone
+//             (tests/test_host_sanitize_cpu.py).  Instantiated in host/capi.cpp (and by the command line for plain greedy).
+//   kSampled  plus include/gten_hip_sample.h.  host/capi.cpp + host/capi_sample.cpp link against that stand-in plus the sampler's
+//             (tests/test_sampler_cpu.py).  Instantiated in host/capi_sample.cpp.
+//   kFull     every stage.  Nothing above kSampled is linked without the whole device library, so the six upper stages need no levels
+//             of their own: instantiated ONCE in the library, in host/capi_generate.cpp, behind the plain functions of
+//             host/capi_flows.h that every upper export calls (host/capi_shift.cpp instantiates the shifting flows of
+//             host/generate_shift.h), and in the command line program, which links against the device library itself.
+// Every flow is a template on the level; what a level may not name is discarded with `if constexpr` under two predicates: `M != 0`
+// (the decoder handle, draw_first, the sampling request) and `M == kFull` (everything the upper six stages do).  A kFull flow whose
+// requests leave a stage off makes no decoder call for it (SlotRequests), so it does what kSampled does for a top-k request.
 #pragma once
 
 #include <cmath>
@@ -25,14 +31,12 @@
 
 namespace gten {
 
-// (kPenalty -- include/gten_hip_penalty.h, DESIGN.md §3.14, instantiated in host/capi_penalty.cpp -- requires kSampled: a penalised
-// greedy request takes its first id from the device too)
-// (kFsm -- include/gten_hip_fsm.h, DESIGN.md §3.15, instantiated in host/capi_fsm.cpp -- requires kSampled for the same reason)
-// (kMirostat -- include/gten_hip_mirostat.h, DESIGN.md §3.23, instantiated in host/capi_mirostat.cpp and the command line only -- requires
-// kSampled: Mirostat acts on a sampling request)
+// The stages.  Only three combinations are levels: 0, kSampled and kFull; the upper six names say what kFull contains.  (Every stage
+// needs kSampled: a penalised or bound greedy request takes its first id from the device too.)
 enum : unsigned { kSampled = 1u, kBiased = 2u, kLogprobs = 4u, kNucleus = 8u, kPenalty = 16u, kFsm = 32u, kMirostat = 64u };
+constexpr unsigned kFull = kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm | kMirostat;
 
-// why a prompt's generation ended (kFsm flows report it per item)
+// why a prompt's generation ended (kFull flows report it per item)
 enum : int { kEndedByLength = 0, kEndedByEos = 1, kEndedByFinal = 2 };
 
 // What one prompt or sequence asks for.  The defaults: greedy, no table, no records.
@@ -75,6 +79,12 @@ inline bool penalty_ok(float rep, float freq, float pres, int last_n)
 {
     return std::isfinite(rep) && rep >= GTEN_HIP_PENALTY_R_MIN && rep <= GTEN_HIP_PENALTY_R_MAX && std::isfinite(freq) &&
            std::fabs(freq) <= GTEN_HIP_PENALTY_ADD_MAX && std::isfinite(pres) && std::fabs(pres) <= GTEN_HIP_PENALTY_ADD_MAX && last_n >= 0;
+}
+// all of the above on one request, for a caller whose record outputs are n_top_max wide
+inline bool request_valid(const Request& r, int n_top_max)
+{
+    return request_ok(r.top_k, r.temp) && binding_ok(r.table, r.min_new) && asking_ok(r.n_top, n_top_max) && cut_ok(r.top_p, r.min_p) &&
+           penalty_ok(r.rep, r.freq, r.pres, r.last_n) && fsm_ok(r.fsm_start, r.table) && mirostat_ok(r.miro_tau, r.miro_eta, r.top_k, r.top_p, r.min_p);
 }
 
 // the requests of a fixed batch's sequences or of a queue's prompts, as the C ABI passes them
@@ -131,9 +141,7 @@ struct Requests {
     bool ok(int n, int n_top_max) const
     {
         for (int j = 0; j < n; j++)
-            if (!request_ok(top_k[j], temp[j]) || !binding_ok(table[j], min_new[j]) || !asking_ok(n_top[j], n_top_max) || !cut_ok(top_p[j], min_p[j]) ||
-                !penalty_ok(rep[j], freq[j], pres[j], last_n[j]) || !fsm_ok(fsm_start[j], table[j]) ||
-                !mirostat_ok(miro_tau[j], miro_eta[j], top_k[j], top_p[j], min_p[j])) return false;
+            if (!request_valid((*this)[j], n_top_max)) return false;
         return true;
     }
 };
@@ -209,7 +217,7 @@ struct RecordRows {
     }
 };
 
-// What a flow keeps of a decoder's automaton pool on the host (kFsm): the flags, read once -- the pool cannot change while a sequence
+// What a flow keeps of a decoder's automaton pool on the host (kFull, a bound request): the flags, read once -- the pool cannot change while a sequence
 // is bound -- and one device word for the next state gten_hip_sample_rows_fsm returns with a first id (`after`: that state, -1 for a
 // banned id, which only a row whose allowed logits are all -inf yields).
 struct FsmHost {
@@ -257,79 +265,75 @@ struct FsmHost {
     }
 };
 
-// The id that will sit at position `pos`, drawn on the device from the logits row lg into id_dev: plain or under the request's
-// table, plus its record into rec_dev when the request asks.  (The only draw from a prompt's row outside the decoder.)
-// A penalising request (kPenalty) draws from the row penalised by the prompt's window of ids[0, pos) -- the window the decoder's
-// first step would read from its own copy of them.
-// A bound request (kFsm) draws in its start state from the row masked by the decoder's pool (gten_hip_sample_rows_fsm: the penalty
-// first, the mask second; no table); fsm->after receives the state the id entered, from the operator itself.
+// The window of ids[0, pos) a penalising request's row at position pos is penalised by: ids + lo, offsets {0, pos - lo} -- the window the
+// decoder's first step would read from its own copy of them.  (No penalty: empty, no ids.)
+struct PenaltyWindow {
+    const int32_t* ids = nullptr;
+    int32_t off[2] = {0, 0};
+    PenaltyWindow(const Request& r, const int32_t* all, int32_t pos)
+    {
+        if (!r.penalises()) return;
+        const int32_t lo = std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos);
+        ids = all + lo;
+        off[1] = pos - lo;
+    }
+    const int32_t* offsets() const { return ids ? off : nullptr; }
+};
+
+// draw_first's choice among the upper stages' row operators (kFull only), the first whose stage the request uses: Mirostat
+// (gten_hip_sample_rows_miro with the default start mu = 2 tau -- penalised, then under its table or in its start state, never under a
+// cut; fsm->mu_next receives the mu of the next position, from the operator itself), an automaton (gten_hip_sample_rows_fsm in the
+// request's start state: the penalty first, the mask second; no table; fsm->after receives the state the id entered), a penalty, a
+// cut, a table.  False: the request uses none of them, nothing was drawn.
+inline bool draw_first_staged(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, const int32_t* ids, FsmHost* fsm)
+{
+    const int32_t k = r.top_k;
+    const float* row = nullptr;
+    if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
+    const bool bound = r.fsm_start >= 0, miro = r.mirostat() && fsm;
+    const uint16_t* next = nullptr;
+    const uint8_t* flags = nullptr;
+    int S = 0;
+    if (bound) GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, &next, &flags));
+    const PenaltyWindow w(r, ids, pos);
+    const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
+    if (miro) {
+        int32_t tq = 0, eq = 0;
+        GTEN_ASSERTM(gten_hip_miro_q16_host(r.miro_tau, r.miro_eta, &tq, &eq) == 0, "mirostat tau %g eta %g", (double)r.miro_tau, (double)r.miro_eta);
+        const int32_t mu0 = 2 * tq;
+        GTEN_HIP_OK(gten_hip_sample_rows_miro(lg, 1, n_vocab, 0, bound ? nullptr : row, 0, next, flags, S, bound ? &r.fsm_start : nullptr, &k, &r.temp, r.seed,
+                                              &r.stream, &pos, w.ids, w.offsets(), &r.rep, &r.freq, &r.pres, &mu0, &r.miro_tau, &r.miro_eta, id_dev,
+                                              bound ? fsm->next_state_dev() : nullptr, fsm->miro_info_dev()));
+        fsm->read_mu_next();
+    } else if (bound) {
+        GTEN_HIP_OK(gten_hip_sample_rows_fsm(lg, 1, n_vocab, 0, next, flags, S, &r.fsm_start, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p, w.ids,
+                                             w.offsets(), &r.rep, &r.freq, &r.pres, id_dev, fsm ? fsm->next_state_dev() : nullptr, nullptr));
+    } else if (w.ids) {
+        GTEN_HIP_OK(gten_hip_sample_rows_pen(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p, w.ids, w.off, &r.rep, &r.freq,
+                                             &r.pres, id_dev, nullptr));
+    } else if (r.cuts()) {
+        GTEN_HIP_OK(gten_hip_sample_rows_cut(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &r.top_p, &r.min_p, id_dev, nullptr));
+    } else if (row) {
+        GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    } else {
+        return false;
+    }
+    if (bound && fsm) fsm->read_after();
+    return true;
+}
+
+// The id that will sit at position `pos`, drawn on the device from the logits row lg into id_dev.  kSampled: gten_hip_sample_rows, the
+// only operator that level names.  kFull: draw_first_staged's operator when the request uses an upper stage, the same plain one when
+// it does not, plus the id's record into rec_dev when the request asks.  (The only draw from a prompt's row outside the decoder.)
 template <unsigned M>
 void draw_first(gten_hip_decoder* dec, const Request& r, const float* lg, int n_vocab, int32_t pos, int32_t* id_dev, FirstRecord* rec_dev,
                 const int32_t* ids = nullptr, FsmHost* fsm = nullptr)
 {
-    static_assert(M & kSampled, "greedy takes the argmax of the prompt's logits on the host");
-    const int32_t k = r.top_k;
-    const float* row = nullptr;
+    static_assert(M == kSampled || M == kFull, "greedy takes the argmax of the prompt's logits on the host");
     bool drawn = false;
-    if constexpr ((M & kBiased) != 0)
-        if (r.table >= 0) GTEN_HIP_OK(gten_hip_decoder_bias_info(dec, nullptr, nullptr, nullptr, r.table, &row));
-    // A request under Mirostat (kMirostat) draws through gten_hip_sample_rows_miro with the default start mu = 2 tau -- penalised, then under
-    // its table or in its start state, never under a cut; fsm->mu_next receives the mu of the next position, from the operator itself.
-    if constexpr ((M & kMirostat) != 0)
-        if (r.mirostat() && fsm) {
-            const uint16_t* next = nullptr;
-            const uint8_t* flags = nullptr;
-            int S = 0;
-            const bool bound = (M & kFsm) != 0 && r.fsm_start >= 0;
-            if (bound) GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, &next, &flags));
-            const bool pen = (M & kPenalty) != 0 && r.penalises();
-            const int32_t lo = pen ? std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos) : pos;
-            const int32_t off[2] = {0, pos - lo};
-            int32_t tq = 0, eq = 0;
-            GTEN_ASSERTM(gten_hip_miro_q16_host(r.miro_tau, r.miro_eta, &tq, &eq) == 0, "mirostat tau %g eta %g", (double)r.miro_tau, (double)r.miro_eta);
-            const int32_t mu0 = 2 * tq;
-            GTEN_HIP_OK(gten_hip_sample_rows_miro(lg, 1, n_vocab, 0, bound ? nullptr : row, 0, bound ? next : nullptr, bound ? flags : nullptr, bound ? S : 0,
-                                                  bound ? &r.fsm_start : nullptr, &k, &r.temp, r.seed, &r.stream, &pos, pen ? ids + lo : nullptr,
-                                                  pen ? off : nullptr, &r.rep, &r.freq, &r.pres, &mu0, &r.miro_tau, &r.miro_eta, id_dev,
-                                                  bound ? fsm->next_state_dev() : nullptr, fsm->miro_info_dev()));
-            if (bound) fsm->read_after();
-            fsm->read_mu_next();
-            drawn = true;
-        }
-    if constexpr ((M & kFsm) != 0)
-        if (r.fsm_start >= 0 && !drawn) {
-            const uint16_t* next = nullptr;
-            const uint8_t* flags = nullptr;
-            int S = 0;
-            GTEN_HIP_OK(gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, &next, &flags));
-            const bool pen = (M & kPenalty) != 0 && r.penalises();
-            const int32_t lo = pen ? std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos) : pos;
-            const int32_t off[2] = {0, pos - lo};
-            const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
-            GTEN_HIP_OK(gten_hip_sample_rows_fsm(lg, 1, n_vocab, 0, next, flags, S, &r.fsm_start, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p,
-                                                 pen ? ids + lo : nullptr, pen ? off : nullptr, &r.rep, &r.freq, &r.pres, id_dev, fsm ? fsm->next_state_dev() : nullptr, nullptr));
-            if (fsm) fsm->read_after();
-            drawn = true;
-        }
-    if constexpr ((M & kPenalty) != 0)
-        if (r.penalises() && !drawn) {
-            const int32_t lo = std::min(std::max(std::max(r.start(pos), r.last_n > 0 ? pos - r.last_n : 0), 0), pos);
-            const int32_t off[2] = {0, pos - lo};
-            const float top_p = r.cuts() ? r.top_p : 1.f, min_p = r.cuts() ? r.min_p : 0.f;
-            GTEN_HIP_OK(gten_hip_sample_rows_pen(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &top_p, &min_p, ids + lo, off, &r.rep, &r.freq,
-                                                 &r.pres, id_dev, nullptr));
-            drawn = true;
-        }
-    if constexpr ((M & kNucleus) != 0)
-        if (r.cuts() && !drawn) {
-            GTEN_HIP_OK(gten_hip_sample_rows_cut(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, &r.top_p, &r.min_p, id_dev, nullptr));
-            drawn = true;
-        }
-    if constexpr ((M & kBiased) != 0) {
-        if (row && !drawn) GTEN_HIP_OK(gten_hip_sample_rows_biased(lg, 1, n_vocab, 0, row, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
-    }
-    if (!row && !drawn) GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n_vocab, 0, &k, &r.temp, r.seed, &r.stream, &pos, id_dev));
-    if constexpr ((M & kLogprobs) != 0)
+    if constexpr (M == kFull) drawn = draw_first_staged(dec, r, lg, n_vocab, pos, id_dev, ids, fsm);
+    if (!drawn) GTEN_HIP_OK(gten_hip_sample_rows(lg, 1, n_vocab, 0, &r.top_k, &r.temp, r.seed, &r.stream, &pos, id_dev));
+    if constexpr (M == kFull)
         if (r.n_top >= 0) GTEN_HIP_OK(gten_hip_row_top_logprobs(lg, 1, n_vocab, n_vocab, id_dev, r.n_top, &rec_dev->logprob, rec_dev->top_id, rec_dev->top_lp));
 }
 
@@ -341,23 +345,25 @@ inline int fsm_state_at(gten_hip_decoder* dec, int q, int pos)
     return s;
 }
 
-// Requests on a decoder's slots [0, n_slots), taken back when the scope ends: whatever way a flow is left, every kind of request
-// it has set is cleared on every slot -- the decoder's later steps are greedy, unbound and record nothing.
+// Requests on a decoder's slots [0, n_slots), taken back when the scope ends.  One flag per stage, raised by the first request of the
+// flow that uses the stage: from then on bind() sets that stage on every slot it binds (a slot reused for a prompt without the stage
+// is cleared), and clear() takes back exactly the raised stages on every slot -- whatever way a flow is left, the decoder's later
+// steps are greedy, unbound and record nothing.  A stage no request of the flow uses costs no decoder call.
 template <unsigned M>
 struct SlotRequests {
+    static_assert(M == 0 || M == kSampled || M == kFull, "the levels are 0, kSampled and kFull");
     gten_hip_decoder* dec;
     int n_slots;
-    bool bound = false, sampling = false, fsm_bound = false, miro_bound = false;
+    bool sampling = false, biased = false, recording = false, cutting = false, penalising = false, fsm_bound = false, miro_bound = false;
     SlotRequests(gten_hip_decoder* dec_, int n_slots_) : dec{dec_}, n_slots{n_slots_} {}
     SlotRequests(const SlotRequests&) = delete;
     ~SlotRequests() { clear(); }
-    // table and log-prob request of a prompt of n_prompt ids (a decoder that refuses them says so here, before any work)
+    // table, record, cut and penalty request of a prompt of n_prompt ids (a decoder that refuses them says so here, before any work)
     int bind(int q, const Request& r, int n_prompt)
     {
         (void)q; (void)r; (void)n_prompt;
-        if constexpr ((M & (kBiased | kLogprobs | kNucleus | kPenalty)) != 0) bound = true;
-        // (a slot that carried a bound prompt is unbound before a table may be set on it: the two do not compose)
-        if constexpr ((M & kFsm) != 0) {
+        if constexpr (M == kFull) {
+            // (a slot that carried a bound prompt is unbound before a table may be set on it: the two do not compose)
             if (fsm_bound)
                 if (const int rc = gten_hip_decoder_set_seq_fsm(dec, q, -1, 0)) return rc;
             // (a start state outside the decoder's pool is refused here, before any work, in the setter's own words)
@@ -366,22 +372,21 @@ struct SlotRequests {
                 if (const int rc = gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr)) return rc;
                 if (r.fsm_start >= S) return gten_hip_decoder_set_seq_fsm(dec, q, r.fsm_start, 1);
             }
-        }
-        // (a slot that carried a prompt under Mirostat is unbound before a cut may be set on it: the two do not compose)
-        if constexpr ((M & kMirostat) != 0)
+            // (a slot that carried a prompt under Mirostat is unbound before a cut may be set on it: the two do not compose)
             if (miro_bound)
                 if (const int rc = gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0)) return rc;
-        if constexpr ((M & kBiased) != 0)
-            if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
-        if constexpr ((M & kLogprobs) != 0)
-            if (const int rc = gten_hip_decoder_set_logprobs(dec, q, r.n_top)) return rc;
-        if constexpr ((M & kNucleus) != 0)
+            if ((biased |= r.table >= 0))
+                if (const int rc = gten_hip_decoder_set_seq_bias(dec, q, r.table, r.until(n_prompt))) return rc;
+            if ((recording |= r.n_top >= 0))
+                if (const int rc = gten_hip_decoder_set_logprobs(dec, q, r.n_top)) return rc;
             // (a greedy request's cut could never act: it is not passed on, so it does not switch a decoder to the cut launch)
-            if (const int rc = gten_hip_decoder_set_cut(dec, q, r.cuts() ? r.top_p : 1.f, r.cuts() ? r.min_p : 0.f)) return rc;
-        if constexpr ((M & kPenalty) != 0) {
-            const bool on = r.penalises();
-            if (const int rc = gten_hip_decoder_set_penalty(dec, q, on ? r.rep : 1.f, on ? r.freq : 0.f, on ? r.pres : 0.f, on ? r.start(n_prompt) : 0,
-                                                            on ? r.last_n : 0)) return rc;
+            if ((cutting |= r.cuts()))
+                if (const int rc = gten_hip_decoder_set_cut(dec, q, r.cuts() ? r.top_p : 1.f, r.cuts() ? r.min_p : 0.f)) return rc;
+            if ((penalising |= r.penalises())) {
+                const bool on = r.penalises();
+                if (const int rc = gten_hip_decoder_set_penalty(dec, q, on ? r.rep : 1.f, on ? r.freq : 0.f, on ? r.pres : 0.f, on ? r.start(n_prompt) : 0,
+                                                                on ? r.last_n : 0)) return rc;
+            }
         }
         return 0;
     }
@@ -389,7 +394,7 @@ struct SlotRequests {
     int fsm(int q, int state, int pos)
     {
         (void)q; (void)state; (void)pos;
-        if constexpr ((M & kFsm) != 0) {
+        if constexpr (M == kFull) {
             if (state < 0) return fsm_bound ? gten_hip_decoder_set_seq_fsm(dec, q, -1, 0) : 0;
             fsm_bound = true;
             return gten_hip_decoder_set_seq_fsm(dec, q, state, pos);
@@ -401,7 +406,7 @@ struct SlotRequests {
     int mirostat(int q, const Request& r, int32_t mu, int pos)
     {
         (void)q; (void)r; (void)mu; (void)pos;
-        if constexpr ((M & kMirostat) != 0) {
+        if constexpr (M == kFull) {
             if (!r.mirostat()) return miro_bound ? gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0) : 0;
             miro_bound = true;
             return gten_hip_decoder_set_seq_mirostat(dec, q, r.miro_tau, r.miro_eta, mu, pos);
@@ -412,7 +417,7 @@ struct SlotRequests {
     int sample(int q, const Request& r)
     {
         (void)q; (void)r;
-        if constexpr ((M & kSampled) != 0) {
+        if constexpr (M != 0) {
             sampling = true;
             return gten_hip_decoder_set_sampling(dec, q, r.top_k, r.temp, r.seed, r.stream);
         }
@@ -422,49 +427,41 @@ struct SlotRequests {
     int clear()
     {
         int rc = 0;
-        if constexpr ((M & kSampled) != 0)
-            for (int q = 0; sampling && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_sampling(dec, q, 0, 0.f, 0, 0)) rc = r;
-        if constexpr ((M & kBiased) != 0)
-            for (int q = 0; bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_seq_bias(dec, q, -1, 0)) rc = r;
-        if constexpr ((M & kLogprobs) != 0)
-            for (int q = 0; bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_logprobs(dec, q, -1)) rc = r;
-        if constexpr ((M & kNucleus) != 0)
-            for (int q = 0; bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_cut(dec, q, 1.f, 0.f)) rc = r;
-        if constexpr ((M & kPenalty) != 0)
-            for (int q = 0; bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_penalty(dec, q, 1.f, 0.f, 0.f, 0, 0)) rc = r;
-        if constexpr ((M & kFsm) != 0)
-            for (int q = 0; fsm_bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_seq_fsm(dec, q, -1, 0)) rc = r;
-        if constexpr ((M & kMirostat) != 0)
-            for (int q = 0; miro_bound && q < n_slots; q++)
-                if (const int r = gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0)) rc = r;
-        bound = sampling = fsm_bound = miro_bound = false;
+        auto every = [&](bool raised, auto&& off) {
+            for (int q = 0; raised && q < n_slots; q++)
+                if (const int r = off(q)) rc = r;
+        };
+        (void)every;
+        if constexpr (M != 0) every(sampling, [&](int q) { return gten_hip_decoder_set_sampling(dec, q, 0, 0.f, 0, 0); });
+        if constexpr (M == kFull) {
+            every(biased, [&](int q) { return gten_hip_decoder_set_seq_bias(dec, q, -1, 0); });
+            every(recording, [&](int q) { return gten_hip_decoder_set_logprobs(dec, q, -1); });
+            every(cutting, [&](int q) { return gten_hip_decoder_set_cut(dec, q, 1.f, 0.f); });
+            every(penalising, [&](int q) { return gten_hip_decoder_set_penalty(dec, q, 1.f, 0.f, 0.f, 0, 0); });
+            every(fsm_bound, [&](int q) { return gten_hip_decoder_set_seq_fsm(dec, q, -1, 0); });
+            every(miro_bound, [&](int q) { return gten_hip_decoder_set_seq_mirostat(dec, q, 0.f, 0.f, 0, 0); });
+        }
+        sampling = biased = recording = cutting = penalising = fsm_bound = miro_bound = false;
         return rc;
     }
 };
 
 // ---- one sequence.  The prompt is processed as in the reference (iteration 0 of greedy_sample); its first id is the host
-// argmax of its logits (mask 0) or draw_first's; every later id comes from back-to-back graph replays whose sampler feeds the
-// next step on the device -- no logits copy, no host round trip per token.  Mask 0 gives greedy_sample's ids (tested), top_k 0
-// gives mask 0's.  With kLogprobs `rows` (max(n_predict, prompt) positions, blanked here once the decoder has accepted the requests)
-// receives the new ids' records at their positions.
+// argmax of its logits (level 0) or draw_first's; every later id comes from back-to-back graph replays whose sampler feeds the
+// next step on the device -- no logits copy, no host round trip per token.  Level 0 gives greedy_sample's ids (tested), top_k 0
+// gives level 0's.  `rows`, when the caller passes them (max(n_predict, prompt) positions, blanked here once the decoder has accepted
+// the requests), receives the new ids' records at their positions (kFull, a request that asks).
 // Returns the number of ids in `tokens`; -1 when the decoder refuses a request (gten_hip_last_error).
 template <unsigned M>
 int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, const Request& r = {}, const RecordRows& rows = {},
              int* ended_by = nullptr, int max_ctx = 0)
 {
+    static_assert(M == 0 || M == kSampled || M == kFull, "the levels are 0, kSampled and kFull");
     const int n_prompt = (int)tokens.size();
     int ended = kEndedByLength, state = -1;
     struct Report { int* out; const int& v; ~Report() { if (out) *out = v; } } report{ended_by, ended};
     (void)state;
-    auto blank = [&]() {
-        if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)std::max(n_predict, n_prompt));
-    };
+    auto blank = [&]() { rows.blank((size_t)std::max(n_predict, n_prompt)); };
     if (n_prompt >= n_predict) { blank(); return n_prompt; }
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = model.decoder_handle();
@@ -484,37 +481,35 @@ int generate(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict
         } else {
             Tensor id({1}, kInt32);
             FirstRecords rec;
-            if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
+            const bool asks = M == kFull && r.n_top >= 0;
+            if (asks) rec.ensure(1);
             draw_first<M>(dec, r, (const float*)logits.device_ptr(), logits.numel(), n_prompt, (int32_t*)id.device_ptr_mut(), rec.dev, tokens.data(), &fh);
             state = fh.after;
             GTEN_HIP_OK(gten_hip_memcpy_d2h(&first, id.device_ptr(), sizeof(first)));
-            if constexpr ((M & kLogprobs) != 0)
-                if (first != eos && r.n_top >= 0) rows.store_first((size_t)n_prompt, r.n_top, rec.dev);
+            if (first != eos && asks) rows.store_first((size_t)n_prompt, r.n_top, rec.dev);
         }
         if (first == eos) { ended = kEndedByEos; return n_prompt; }
         tokens.push_back(first);
     }
     const int n_first = n_prompt + 1;
     // (a first id that is itself final: the prompt plus that id)
-    if constexpr ((M & kFsm) != 0)
+    if constexpr (M == kFull)
         if (r.fsm_start >= 0 && fh.final(state)) { ended = kEndedByFinal; return n_first; }
     const int max_new = n_predict - n_first;
     if (max_new <= 0) return n_first;
     std::vector<int32_t> out((size_t)max_new);
     if (slot.sample(0, r) != 0) return -1;
-    if constexpr ((M & kFsm) != 0)
-        if (r.fsm_start >= 0 && slot.fsm(0, state, n_first) != 0) return -1;
-    if constexpr ((M & kMirostat) != 0)
-        if (slot.mirostat(0, r, fh.mu_next, n_first) != 0) return -1;
+    if (r.fsm_start >= 0 && slot.fsm(0, state, n_first) != 0) return -1;
+    if (slot.mirostat(0, r, fh.mu_next, n_first) != 0) return -1;
     const int got = model.decode_generate(tokens.data(), n_first, max_new, eos, out.data());
     tokens.insert(tokens.end(), out.begin(), out.begin() + got);
     // (fewer ids than the steps that could run: an eos.  The context bounds them too; a caller that does not say how long it is
     //  keeps max_tokens inside it)
     if (got < (max_ctx > 0 ? std::min(max_new, max_ctx - n_first + 1) : max_new)) ended = kEndedByEos;
-    if constexpr ((M & kFsm) != 0)
+    if constexpr (M == kFull) {
         if (r.fsm_start >= 0 && got > 0 && fh.final(fsm_state_at(dec, 0, n_first + got))) ended = kEndedByFinal;
-    if constexpr ((M & kLogprobs) != 0)
         if (r.n_top >= 0 && rows.store_decoded(dec, 0, n_first, got, r.n_top) != 0) return -1;
+    }
     return slot.clear() ? -1 : (int)tokens.size();
 }
 
@@ -530,7 +525,7 @@ int generate_in_place(TinyLlama& model, int32_t* tokens, int n_prompt, int max_t
     return total;
 }
 
-// the first id of `prompt` processed onto cache set `set` of a batch: TinyLlamaBatch::prefill's argmax (mask 0) or draw_first's
+// the first id of `prompt` processed onto cache set `set` of a batch: TinyLlamaBatch::prefill's argmax (level 0) or draw_first's
 template <unsigned M>
 int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, const Request& r, FirstRecord* rec_dev, FsmHost* fsm = nullptr)
 {
@@ -539,7 +534,7 @@ int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, con
         return b.prefill(set, prompt);
     } else {
         gten_hip_decoder* dec = nullptr;
-        if constexpr ((M & (kBiased | kNucleus | kFsm)) != 0) dec = b.decoder_handle();
+        if constexpr (M == kFull) dec = b.decoder_handle();
         return b.prefill_picked(set, prompt, [&](int, const float* lg, int n, int32_t* out) {
             draw_first<M>(dec, r, lg, n, (int32_t)prompt.size(), out, rec_dev, prompt.data(), fsm);
         });
@@ -549,17 +544,18 @@ int first_id(TinyLlamaBatch& b, int set, const std::vector<int32_t>& prompt, con
 // ---- a fixed batch (gten_host_batch_generate and its _topk / _biased / _lp forms).  prompts [n_seq][max_prompt] (sequence q uses
 // its first n_prompt[q] ids): every request is set first (a refusal comes before any work), each prompt is processed on its
 // sequence's own caches and its first id chosen from its logits row, then all sequences generate together with the sampler on
-// the device.  out is [n_seq][max_tokens]: prompt + new ids; n_total [n_seq]; rows (kLogprobs) [n_seq][max_tokens] positions.
+// the device.  out is [n_seq][max_tokens]: prompt + new ids; n_total [n_seq]; rows (kFull, optional) [n_seq][max_tokens] positions.
 // 0; -1: bad arguments (nothing was touched); otherwise the code of the decoder call that refused.
 template <unsigned M>
 int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
                    const Requests& reqs, int32_t* out, int32_t* n_total, const RecordRows& rows = {}, int32_t* ended_by = nullptr)
 {
+    static_assert(M == 0 || M == kSampled || M == kFull, "the levels are 0, kSampled and kFull");
     const int S = batch.n_seq();
     for (int q = 0; q < S; q++)
         if (n_prompt[q] <= 0 || n_prompt[q] > max_prompt || n_prompt[q] >= max_tokens || n_prompt[q] >= max_ctx) return -1;
     if (!reqs.ok(S, rows.n_top_max)) return -1;
-    if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)S * (size_t)max_tokens);
+    rows.blank((size_t)S * (size_t)max_tokens);
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = batch.decoder_handle();
     SlotRequests<M> slots(dec, S);
@@ -567,22 +563,22 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
     for (int q = 0; q < S; q++)
         if (const int rc = slots.bind(q, reqs[q], n_prompt[q])) return rc;
     std::vector<int32_t> first((size_t)S), state((size_t)S, -1), mu_first((size_t)S, 0);
-    std::vector<char> final_first((size_t)S, 0);                  // (kFsm) the first id entered a final state: the prompt plus that id
+    std::vector<char> final_first((size_t)S, 0);                  // (bound) the first id entered a final state: the prompt plus that id
     FirstRecords rec;
-    if constexpr ((M & kLogprobs) != 0) rec.ensure(1);
     for (int q = 0; q < S; q++) {
         const int P = n_prompt[q];
         int32_t* row = out + (size_t)q * max_tokens;
         std::memcpy(row, prompts + (size_t)q * max_prompt, (size_t)P * sizeof(int32_t));
         const Request r = reqs[q];
+        const bool asks = M == kFull && r.n_top >= 0;
+        if (asks) rec.ensure(1);
         first[(size_t)q] = first_id<M>(batch, q, std::vector<int32_t>(row, row + P), r, rec.dev, &fh);
-        if constexpr ((M & kFsm) != 0) {
+        if constexpr (M == kFull) {
             state[(size_t)q] = fh.after;
             final_first[(size_t)q] = r.fsm_start >= 0 && first[(size_t)q] != eos && fh.final(state[(size_t)q]);
+            mu_first[(size_t)q] = fh.mu_next;
         }
-        if constexpr ((M & kMirostat) != 0) mu_first[(size_t)q] = fh.mu_next;
-        if constexpr ((M & kLogprobs) != 0)
-            if (r.n_top >= 0 && first[(size_t)q] != eos) rows.from((size_t)q * max_tokens).store_first((size_t)P, r.n_top, rec.dev);
+        if (asks && first[(size_t)q] != eos) rows.from((size_t)q * max_tokens).store_first((size_t)P, r.n_top, rec.dev);
     }
     std::vector<int> n_first((size_t)S), room((size_t)S);
     int max_new = 0;
@@ -593,11 +589,9 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
         n_first[(size_t)q] = P + 1;
         batch.decode_set_tokens(q, row, 0, P + 1);
         if (const int rc = slots.sample(q, reqs[q])) return rc;
-        if constexpr ((M & kFsm) != 0)
-            if (reqs[q].fsm_start >= 0 && first[(size_t)q] != eos && !final_first[(size_t)q])
-                if (const int rc = slots.fsm(q, state[(size_t)q], P + 1)) return rc;
-        if constexpr ((M & kMirostat) != 0)
-            if (const int rc = slots.mirostat(q, reqs[q], mu_first[(size_t)q], P + 1)) return rc;
+        if (reqs[q].fsm_start >= 0 && first[(size_t)q] != eos && !final_first[(size_t)q])
+            if (const int rc = slots.fsm(q, state[(size_t)q], P + 1)) return rc;
+        if (const int rc = slots.mirostat(q, reqs[q], mu_first[(size_t)q], P + 1)) return rc;
         // this sequence's own room; none when its first id is already eos (the sequence is then parked from the start instead of
         // being decoded for the longest sequence's length)
         room[(size_t)q] = (first[(size_t)q] == eos || final_first[(size_t)q]) ? 0 : max_tokens - (P + 1);
@@ -616,11 +610,11 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
         std::memcpy(row + total, gen.data() + (size_t)q * max_new, (size_t)take * sizeof(int32_t));
         n_total[q] = total + take;
         if (ended_by && take < std::min(room[(size_t)q], max_ctx - total + 1)) ended_by[q] = kEndedByEos;
-        if constexpr ((M & kFsm) != 0)
+        if constexpr (M == kFull) {
             if (ended_by && reqs[q].fsm_start >= 0 && take > 0 && fh.final(fsm_state_at(dec, q, total + take))) ended_by[q] = kEndedByFinal;
-        if constexpr ((M & kLogprobs) != 0)
             if (const int n_top = reqs[q].n_top; n_top >= 0)
                 if (const int rc = rows.from((size_t)q * max_tokens).store_decoded(dec, q, total, take, n_top)) return rc;
+        }
     }
     return slots.clear();
 }
@@ -629,12 +623,13 @@ int generate_batch(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, c
 // logits row on the device -- under its table, with its record -- and is set on whichever slot takes the prompt, also when a
 // sequence moves in the tail: the ids depend on (seed, j) and the logits only, not on the slot or schedule.  A slot's records
 // are read when its prompt ends or moves (collect), before the slot is started again.  Every slot's requests are cleared when
-// the queue is done.  Mask 0: the prompt's argmax, the decoder's argmax, nothing set.  `rows` is [prompts][row_len] positions.
+// the queue is done.  Level 0: the prompt's argmax, the decoder's argmax, nothing set.  `rows` is [prompts][row_len] positions.
 template <unsigned M>
 struct ServePolicy {
-    static constexpr bool kLogprobs = (M & gten::kLogprobs) != 0;
-    static constexpr bool kFsm = (M & gten::kFsm) != 0;
-    static constexpr bool kMirostat = (M & gten::kMirostat) != 0;
+    static_assert(M == 0 || M == kSampled || M == kFull, "the levels are 0, kSampled and kFull");
+    // what host/serve.h's scheduler asks its policy: whether the record, automaton and Mirostat hooks exist.  At kFull all do, and each
+    // returns at once for a prompt that does not ask or is not bound
+    static constexpr bool kLogprobs = M == kFull, kFsm = M == kFull, kMirostat = M == kFull;
     // (kMirostat) per prompt: the mu its next id is drawn under, as the host last read it
     std::vector<int32_t> miro_mu;
     void note_mu(int j, int32_t mu)
@@ -669,21 +664,23 @@ struct ServePolicy {
         : reqs{reqs_}, rows{rows_}, row_len{row_len_}, slots(dec, n_slots), reqs_n{n_prompts}
     {
         fh.dec = dec;
-        if constexpr (kFsm) { fsm_state.assign((size_t)n_prompts, -1); fsm_ended.assign((size_t)n_prompts, 0); }
+        if constexpr (M == kFull) { fsm_state.assign((size_t)n_prompts, -1); fsm_ended.assign((size_t)n_prompts, 0); }
     }
     RecordRows rows_of(int j) const { return rows.from((size_t)j * (size_t)row_len); }
-    FirstRecord* rec_of(int k) const { return kLogprobs ? rec.dev + k : nullptr; }
+    FirstRecord* rec_of(int k) const { return rec.dev ? rec.dev + k : nullptr; }
     void store_first(int k, int j, int pos)
     {
         if (reqs.n_top[j] >= 0 && pos < row_len) rows_of(j).store_first((size_t)pos, reqs.n_top[j], rec_of(k));
     }
     int first(TinyLlamaBatch& b, int c, const std::vector<int32_t>& row, int j)
     {
-        if constexpr (kLogprobs) rec.ensure(1);
+        if (M == kFull && reqs.n_top[j] >= 0) rec.ensure(1);
         const int id = first_id<M>(b, c, row, reqs[j], rec.dev, &fh);
-        if constexpr (kLogprobs) store_first(0, j, (int)row.size());
-        if constexpr (kFsm) note_first(j, fh.after);
-        if constexpr (kMirostat) note_mu(j, fh.mu_next);
+        if constexpr (M == kFull) {
+            store_first(0, j, (int)row.size());
+            note_first(j, fh.after);
+            note_mu(j, fh.mu_next);
+        }
         return id;
     }
     // (kFsm) prompt j's first id entered state `after`
@@ -733,15 +730,18 @@ struct ServePolicy {
             (void)js;
             b.prefill_many(sets, cps, first, nullptr, copy_of, ctx_of);
         } else {
-            if constexpr (kLogprobs) rec.ensure((int)sets.size());
+            bool asks = false;
+            for (const int j : js) asks |= M == kFull && reqs.n_top[j] >= 0;
+            if (asks) rec.ensure((int)sets.size());
             std::vector<float*> lo((size_t)sets.size(), nullptr);
             b.prefill_many_with(sets, cps, first, &lo, [&](int k, const float* lg, int n, int32_t* out) {
                 draw_first<M>(slots.dec, reqs[js[(size_t)k]], lg, n, (int32_t)ps[(size_t)k]->size(), out, rec_of(k), ps[(size_t)k]->data(), &fh);
-                if constexpr (kFsm) note_first(js[(size_t)k], fh.after);
-                if constexpr (kMirostat) note_mu(js[(size_t)k], fh.mu_next);
+                if constexpr (M == kFull) {
+                    note_first(js[(size_t)k], fh.after);
+                    note_mu(js[(size_t)k], fh.mu_next);
+                }
             }, copy_of, ctx_of);
-            if constexpr (kLogprobs)
-                for (size_t k = 0; k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
+            for (size_t k = 0; asks && k < js.size(); k++) store_first((int)k, js[k], (int)ps[k]->size());
         }
     }
     // prompt j (n_prompt ids) starts, or goes on, in slot q
@@ -769,6 +769,7 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
                 const Requests& reqs = {}, const RecordRows& rows = {}, int32_t* ended_by = nullptr, const int32_t* group_of = nullptr,
                 const int32_t* session = nullptr)
 {
+    static_assert(M == 0 || M == kSampled || M == kFull, "the levels are 0, kSampled and kFull");
     if (n_prompts <= 0 || max_tokens <= 0 || slice <= 0) return -1;
     const int row_len = std::max(max_tokens, max_prompt);
     // (session, include/gten_host_sessions.h: item j continues session[j] >= 0 -- prompts[j] holds the turn's new ids, possibly
@@ -788,36 +789,34 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
     if (!reqs.ok(n_prompts, rows.n_top_max)) return -1;
     gten_hip_decoder* dec = nullptr;
     if constexpr (M != 0) dec = batch.decoder_handle();
-    if constexpr ((M & kLogprobs) != 0) rows.blank((size_t)n_prompts * (size_t)row_len);
-    // (slot 0 is as it was at once)
-    if constexpr ((M & kBiased) != 0)
+    rows.blank((size_t)n_prompts * (size_t)row_len);
+    // (a stage some request uses is set and taken back on slot 0 -- as it was at once -- so a decoder that refuses it says so now)
+    if constexpr (M == kFull) {
         if (reqs.table.each) {
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, 0, 0, 0)) return rc;
             if (const int rc = gten_hip_decoder_set_seq_bias(dec, 0, -1, 0)) return rc;
         }
-    if constexpr ((M & kLogprobs) != 0)
         if (reqs.n_top.each) {
             if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, 0)) return rc;
             if (const int rc = gten_hip_decoder_set_logprobs(dec, 0, -1)) return rc;
         }
-    if constexpr ((M & kNucleus) != 0)
         for (int j = 0, cutting = 0; j < n_prompts && !cutting; j++)
             if ((cutting = reqs[j].cuts())) {
                 if (const int rc = gten_hip_decoder_set_cut(dec, 0, reqs[j].top_p, reqs[j].min_p)) return rc;
                 if (const int rc = gten_hip_decoder_set_cut(dec, 0, 1.f, 0.f)) return rc;
             }
-    if constexpr ((M & kPenalty) != 0)
         for (int j = 0, pen = 0; j < n_prompts && !pen; j++)
             if ((pen = reqs[j].penalises())) {
                 if (const int rc = gten_hip_decoder_set_penalty(dec, 0, reqs[j].rep, reqs[j].freq, reqs[j].pres, 0, reqs[j].last_n)) return rc;
                 if (const int rc = gten_hip_decoder_set_penalty(dec, 0, 1.f, 0.f, 0.f, 0, 0)) return rc;
             }
-    if constexpr ((M & kFsm) != 0) {
         // (... and every start state is one of the pool's: a refusal comes before the queue starts)
-        int S = 0;
-        if (const int rc = gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr)) return rc;
+        int S = -1;
         for (int j = 0, bound = 0; j < n_prompts; j++)
-            if (const int start = reqs[j].fsm_start; start >= 0 && (!bound || start >= S)) {
+            if (const int start = reqs[j].fsm_start; start >= 0) {
+                if (S < 0)
+                    if (const int rc = gten_hip_decoder_fsm_info(dec, &S, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr)) return rc;
+                if (bound && start < S) continue;
                 if (const int rc = gten_hip_decoder_set_seq_fsm(dec, 0, start, 1)) return rc;
                 if (const int rc = gten_hip_decoder_set_seq_fsm(dec, 0, -1, 0)) return rc;
                 bound = 1;
@@ -839,11 +838,11 @@ int serve_queue(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, cons
             const int P = full[(size_t)j];
             const int limit = serve_limit(P, max_tokens, max_ctx, Each<int32_t>{max_new_each, max_new}[j]);
             ended_by[j] = take < limit && P < limit ? kEndedByEos : kEndedByLength;
-            if constexpr ((M & kFsm) != 0)
+            if constexpr (M == kFull)
                 if (pick.fsm_ended[(size_t)j]) ended_by[j] = kEndedByFinal;
         }
         // (a first id that was the eos is not stored: neither is its record)
-        if constexpr ((M & kLogprobs) != 0) rows.from((size_t)j * row_len + (size_t)take).blank((size_t)(row_len - take));
+        rows.from((size_t)j * row_len + (size_t)take).blank((size_t)(row_len - take));
     }
     if (stats) {
         // (exactly n_stats doubles are written: a caller sized for an older, shorter list stays inside its array)

@@ -54,24 +54,22 @@ inline const char* shift_refusal(const Request& r, int n_prompt, int max_ctx)
 }
 
 // the requests of a sequence that has shifted `shifts` times: the draw stream, the penalty window's start (already through phi)
-template <unsigned M>
-int rebind_shifted(gten_hip_decoder* dec, int q, const Request& r, unsigned shifts, int pen_start)
+inline int rebind_shifted(gten_hip_decoder* dec, int q, const Request& r, unsigned shifts, int pen_start)
 {
-    if constexpr ((M & kSampled) != 0)
-        if (const int rc = gten_hip_decoder_set_sampling(dec, q, r.top_k, r.temp, r.seed, r.stream + (shifts << 24))) return rc;
-    if constexpr ((M & kPenalty) != 0)
-        if (r.penalises())
-            if (const int rc = gten_hip_decoder_set_penalty(dec, q, r.rep, r.freq, r.pres, pen_start, r.last_n)) return rc;
+    if (const int rc = gten_hip_decoder_set_sampling(dec, q, r.top_k, r.temp, r.seed, r.stream + (shifts << 24))) return rc;
+    if (r.penalises())
+        if (const int rc = gten_hip_decoder_set_penalty(dec, q, r.rep, r.freq, r.pres, pen_start, r.last_n)) return rc;
     return 0;
 }
 
-// ---- one sequence: generate<M> with r.shift_keep >= 0 (below 0: generate<M> itself).  `why` receives the text of a refusal.
+// ---- one sequence: generate() at kFull cut into segments, for a request with r.shift_keep >= 0 (below 0 there is nothing to shift: the
+// caller takes generate() itself, in the library through host/capi_flows.h).  `why` receives the text of a refusal.
 template <unsigned M>
 int generate_shifting(TinyLlama& model, std::vector<int32_t>& tokens, const int n_predict, const int eos, const Request& r, int max_ctx,
                       ShiftCounts* counts = nullptr, const char** why = nullptr)
 {
-    static_assert((M & kSampled) != 0, "the first id is drawn on the device");
-    if (r.shift_keep < 0) return generate<M>(model, tokens, n_predict, eos, r, {}, nullptr, max_ctx);
+    static_assert(M == kFull, "a shifting flow may carry a cut and a penalty: it exists at kFull only");
+    if (r.shift_keep < 0) { if (why) *why = "generate_shifting: keep < 0 is not a shift"; return -1; }
     const int n_prompt = (int)tokens.size();
     if (const char* no = shift_refusal(r, n_prompt, max_ctx)) { if (why) *why = no; return -1; }
     if (n_prompt >= n_predict) return n_prompt;
@@ -100,7 +98,7 @@ int generate_shifting(TinyLlama& model, std::vector<int32_t>& tokens, const int 
             if (kv_shift_sets({&model}, {(int)view.size() - 1}, p.keep, {p.drop}, counts) != 0) return -1;
             view.resize((size_t)shift_ids(view.data(), (int)view.size(), p.keep, p.drop));
             pen_start = shift_phi(pen_start, p.keep, p.drop);
-            if (rebind_shifted<M>(dec, 0, r, ++shifts, pen_start) != 0) return -1;
+            if (rebind_shifted(dec, 0, r, ++shifts, pen_start) != 0) return -1;
         }
         const int n_first = (int)view.size(), room = std::min(n_predict - (int)tokens.size(), max_ctx - n_first + 1);
         out.resize((size_t)room);
@@ -112,15 +110,15 @@ int generate_shifting(TinyLlama& model, std::vector<int32_t>& tokens, const int 
     return slot.clear() ? -1 : (int)tokens.size();
 }
 
-// ---- a fixed batch: generate_batch<M> with a (keep, drop) pair for every sequence (keep < 0: generate_batch<M> itself).  A segment
+// ---- a fixed batch: generate_batch() at kFull with a (keep, drop) pair for every sequence (keep >= 0, as above).  A segment
 // is one decode_generate over all sequences, each with the room its own window leaves; every live sequence ends it finished or with
 // its window full, so all that are due shift together in one device call.
 template <unsigned M>
 int generate_batch_shifting(TinyLlamaBatch& batch, int max_ctx, const int32_t* prompts, const int32_t* n_prompt, int max_prompt, int max_tokens, int eos,
                             const Requests& reqs, int keep, int drop, int32_t* out, int32_t* n_total, ShiftCounts* counts = nullptr, const char** why = nullptr)
 {
-    static_assert((M & kSampled) != 0, "the first ids are drawn on the device");
-    if (keep < 0) return generate_batch<M>(batch, max_ctx, prompts, n_prompt, max_prompt, max_tokens, eos, reqs, out, n_total);
+    static_assert(M == kFull, "a shifting flow may carry a cut and a penalty: it exists at kFull only");
+    if (keep < 0) { if (why) *why = "generate_shifting: keep < 0 is not a shift"; return -1; }
     const int S = batch.n_seq();
     for (int q = 0; q < S; q++)
         if (n_prompt[q] <= 0 || n_prompt[q] > max_prompt || n_prompt[q] >= max_tokens) return -1;
@@ -174,7 +172,7 @@ int generate_batch_shifting(TinyLlamaBatch& batch, int max_ctx, const int32_t* p
             const int q = who[i];
             view[(size_t)q].resize((size_t)shift_ids(view[(size_t)q].data(), (int)view[(size_t)q].size(), keep, drops[i]));
             pen_start[(size_t)q] = shift_phi(pen_start[(size_t)q], keep, drops[i]);
-            if (const int rc = rebind_shifted<M>(dec, q, reqs[q], ++shifts[(size_t)q], pen_start[(size_t)q])) return rc;
+            if (const int rc = rebind_shifted(dec, q, reqs[q], ++shifts[(size_t)q], pen_start[(size_t)q])) return rc;
         }
         int max_new = 0, n_live = 0;
         for (int q = 0; q < S; q++) {

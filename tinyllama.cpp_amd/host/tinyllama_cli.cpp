@@ -255,8 +255,8 @@ static int set_automaton(const Options& o, TinyLlama& model, const Tokenizer& to
 // One answer (host/generate.h).  Plain greedy: the prompt as in the reference, every later id from the device-side argmax, nothing set
 // on the decoder.  Top-k (tinyllama.cpp:442-507: the k largest of logits / temp, one draw from their softmax) on the device sampler,
 // keyed by (seed, stream = the chat turn, position).  --ban / --allow: either mode under table 0 (top_k 0: greedy over the biased
-// logits).  --logprobs: after the ids, one record line per generated id.  --top-p / --min-p: the draw under a cut.  The flow names only
-// the stages the options ask for.
+// logits).  --logprobs: after the ids, one record line per generated id.  --top-p / --min-p: the draw under a cut.  Everything but
+// plain greedy is ONE kFull flow: the request says which stages act, and a stage no option asks for costs no decoder call.
 static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenizer& tok, uint64_t seed, uint32_t* turn, int fsm_start = -1)
 {
     std::vector<int> enc = tok.encode(prompt);
@@ -270,7 +270,7 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
         r.shift_keep = o.shift_keep;
         r.shift_drop = o.shift_drop;
         const char* why = nullptr;
-        rc = generate_shifting<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm>(model, tokens, o.n_predict, tok.eos, r, model.n_ctx_, nullptr, &why);
+        rc = generate_shifting<kFull>(model, tokens, o.n_predict, tok.eos, r, model.n_ctx_, nullptr, &why);
         if (rc < 0 && why) { std::cerr << "error: " << why << "\n"; std::exit(EXIT_FAILURE); }
     } else if (o.greedy && !o.constrained() && o.logprobs < 0 && !o.penalises() && fsm_start < 0) {
         rc = generate<0>(model, tokens, o.n_predict, tok.eos);
@@ -280,51 +280,15 @@ static void run(const Options& o, std::string prompt, TinyLlama& model, Tokenize
         if (o.mirostat == 2) {
             r.miro_tau = o.miro_tau;
             r.miro_eta = o.miro_eta;
-            RecordRows rows;
-            if (o.logprobs >= 0) {
-                logprob.resize(width);
-                top_id.resize(width * W);
-                top_lp.resize(width * W);
-                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
-            }
-            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm | kMirostat>(model, tokens, o.n_predict, tok.eos, r, rows);
-        } else if (fsm_start >= 0) {
-            RecordRows rows;
-            if (o.logprobs >= 0) {
-                logprob.resize(width);
-                top_id.resize(width * W);
-                top_lp.resize(width * W);
-                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
-            }
-            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty | kFsm>(model, tokens, o.n_predict, tok.eos, r, rows);
-        } else if (o.penalises()) {
-            RecordRows rows;
-            if (o.logprobs >= 0) {
-                logprob.resize(width);
-                top_id.resize(width * W);
-                top_lp.resize(width * W);
-                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
-            }
-            rc = generate<kSampled | kBiased | kLogprobs | kNucleus | kPenalty>(model, tokens, o.n_predict, tok.eos, r, rows);
-        } else if (o.cuts()) {
-            RecordRows rows;
-            if (o.logprobs >= 0) {
-                logprob.resize(width);
-                top_id.resize(width * W);
-                top_lp.resize(width * W);
-                rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
-            }
-            rc = generate<kSampled | kBiased | kLogprobs | kNucleus>(model, tokens, o.n_predict, tok.eos, r, rows);
-        } else if (o.logprobs >= 0) {
+        }
+        RecordRows rows;
+        if (o.logprobs >= 0) {
             logprob.resize(width);
             top_id.resize(width * W);
             top_lp.resize(width * W);
-            rc = generate<kSampled | kBiased | kLogprobs>(model, tokens, o.n_predict, tok.eos, r, RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W});
-        } else if (o.constrained()) {
-            rc = generate<kSampled | kBiased>(model, tokens, o.n_predict, tok.eos, r);
-        } else {
-            rc = generate<kSampled>(model, tokens, o.n_predict, tok.eos, r);
+            rows = RecordRows{logprob.data(), top_id.data(), top_lp.data(), (int)W};
         }
+        rc = generate<kFull>(model, tokens, o.n_predict, tok.eos, r, rows);
     }
     if (rc < 0) {
         std::cerr << "error: " << gten_hip_last_error() << "\n";
