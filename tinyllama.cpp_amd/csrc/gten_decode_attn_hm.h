@@ -43,6 +43,7 @@
 // position) the same operations -- what differs is the order of the f32 additions in a chunk's sum of exponentials and in
 // p.V (the matrix core's order over another assignment of positions to its steps).
 // three waves per SIMD: the kernel fits 160 registers without a spill (hipcc takes 176 when left alone)
+#include "gten_kvq4_math.h"
 #ifndef HM_OCC
 #define HM_OCC __attribute__((amdgpu_waves_per_eu(3)))
 #endif
@@ -62,6 +63,25 @@ __host__ __device__ __forceinline__ unsigned hm_v_d_off(unsigned p, unsigned hal
     const unsigned s = p >> 5, tp = (p >> 4) & 1u, r = p & 15u;
     return HM_Q_BYTES + ((r >> 2) * 2u + ((r >> 1) & 1u)) * 128u + s * 16u + (tp * 4u + (r & 1u) * 2u + half) * 2u;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 4-bit shadows (gten_hip_set_kv_shadow_q4, include/gten_hip_kvq4.h): a chunk holds R(block) of every block of
+// its 256 positions (gten_kvq4_math.h: 15 levels under a delta of its own), the quants as nibbles biased by 8 --
+// 8192 + 1024 = HMQ4_CHUNK_BYTES = 9216 per matrix, 36 instead of 68 bytes per (kv head, position), again ONE contiguous run.
+//   a K chunk   bytes [0, 8192)  8 tile PAIRS x 1 KiB; lane l = 16 lq + lc owns bytes [16 l, 16 l + 16) of a pair: byte i holds
+//               element 16 lq + i of position 32 j + lc (tile 2 j) in its LOW nibble and of position 32 j + 16 + lc (tile 2 j + 1)
+//               in its HIGH nibble -- one coalesced 16-byte-per-lane load is two A operands of v_mfma_i32_16x16x64_i8 after
+//               `w & 0x0f0f0f0f` and `(w >> 4) & 0x0f0f0f0f`.  The bias stays in the operand: the integer dot comes out as
+//               c + 8 sum(q_head block), and -8 sum(...) -- one integer per head column, from one more matrix instruction on the
+//               head vectors -- is the accumulator the tile's instruction starts from.
+//               bytes [8192, 9216)  the block deltas, laid out as the Q8 chunk's
+//   a V chunk   bytes [0, 8192)  8 steps of 32 positions x 1 KiB; lane l owns 16 bytes = four element tiles x 8 position slots
+//               (the Q8 chunk's slot order), dword et = element 16 et + lc.  Slot j sits at bit 4 (j >> 1) + 16 (j & 1) of its
+//               dword, so that `(w >> 4 i) & 0x000f000f | 0x64006400` IS the f16 pair (1024 + n_2i, 1024 + n_2i+1): minus 1032 and
+//               the A operand of v_mfma_f32_16x16x32_f16 is there (hm_bytes_to_h4's trick on nibbles).
+//               bytes [8192, 9216)  the block deltas, laid out as the Q8 chunk's
+// The offset functions hmq4_{k,v}_{q,d}_off and HMQ4_CHUNK_BYTES are in gten_kvq4_math.h (device-free: a host program checks them).
+static_assert(HMQ4_CHUNK_BYTES - HMQ4_Q_BYTES == HM_CHUNK_BYTES - HM_Q_BYTES, "the 4-bit chunk keeps the Q8 chunk's delta runs");
 
 // ---- row caches -> shadows: one workgroup per (kv head, chunk) x (layer, K | V) x listed sequence.  Rows [0, n - 1) of a
 // sequence at step n are its context (the step itself appends row n - 1); chunks without such a row return at once.
@@ -99,6 +119,23 @@ __device__ __forceinline__ void hm_bytes_to_h4(unsigned b4, unsigned& lo, unsign
     const hm_h2 k = {(_Float16)1152.0f, (_Float16)1152.0f};
     lo = __builtin_bit_cast(unsigned, __builtin_bit_cast(hm_h2, x0) - k);
     hi = __builtin_bit_cast(unsigned, __builtin_bit_cast(hm_h2, x1) - k);
+}
+
+// eight nibbles of a Q4 V dword (slot j at bit 4 (j >> 1) + 16 (j & 1), biased by 8) -> pair i = slots (2 i, 2 i + 1) as exact f16 integers
+__device__ __forceinline__ unsigned hmq4_pair_to_h2(unsigned w, int i)
+{
+    const hm_h2 k = {(_Float16)1032.0f, (_Float16)1032.0f};
+    return __builtin_bit_cast(unsigned, __builtin_bit_cast(hm_h2, ((w >> (4 * i)) & 0x000f000fu) | 0x64006400u) - k);
+}
+// R on a wave that holds two Q8 blocks, lane t = element t & 31 of block t >> 5 (an appended K or V slice, two blocks of an operator's
+// row): the block's largest |q| over its 32 lanes, then gten_kvq4_math.h.  Returns the lane's q4; d4 = the block's new delta.
+__device__ __forceinline__ int hmq4_round_lane(int q, uint16_t d, uint16_t& d4)
+{
+    int m = q < 0 ? -q : q;
+#pragma unroll
+    for (int x = 1; x < 32; x <<= 1) m = max(m, __shfl_xor(m, x, 64));
+    d4 = kvq4_delta(m, d);
+    return kvq4_quant(q, d, d4);
 }
 
 // Measured on the 256- / 64-sequence step (ms per step, two runs each, one box): waves per workgroup 4 | 2 and the

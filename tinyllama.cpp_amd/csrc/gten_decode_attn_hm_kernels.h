@@ -18,6 +18,9 @@
 //             which[seq] the shadow sequence seq's shared chunks come from.  Otherwise HM_PFX 1, word for word.  The imports need no
 //             such instantiation: they skip chunk < share[seq] whatever the index.
 //
+// Behind the four: k_kv_import_hm_q4 and k_dec_attn_hm_q4<GRP, NT>, the Q8 pair on 4-bit chunks (gten_hip_set_kv_shadow_q4), in the same three
+// forms by the same three includes.
+//
 // Why an include and not `template <..., bool PFX>`: a template parameter cannot take the two extra ARGUMENTS away.  The kernels of a
 // decoder without a prefix must keep their argument list (the kernarg segment, the SGPRs it is loaded into) and with it their
 // instruction stream and register count exactly; two kernels per name with different parameter lists it is, and the text of the
@@ -597,6 +600,350 @@ __global__ __launch_bounds__(64 * HM_WAVES) void HM_KERNEL(k_dec_attn_hm_f16)(co
     }
     if (lc < GRP) {
         float* o = a.att_part + ((size_t)(g * GRP + lc) * a.n_chunks + chunk) * dh + 4 * lq;
+#pragma unroll
+        for (int et = 0; et < 4; et++) *(float4*)(o + 16 * et) = make_float4(acc[et][0], acc[et][1], acc[et][2], acc[et][3]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 4-bit shadows (gten_decode_attn_hm.h, "4-bit shadows"): the Q8 pair of kernels above on chunks of R(block).
+#if HM_PFX < 2
+// k_kv_import_hm's grid, arguments and skips.  A thread first rounds the two blocks of ITS row where they lie in LDS (R of
+// gten_kvq4_math.h: the delta replaced, every quant as a biased nibble in its byte), then the pieces are gathered as there.
+__global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm_q4)(const HmImportList items, const DecStep* __restrict__ step, const void* const* __restrict__ kv_tab,
+                                                         uint8_t* __restrict__ hm_base, size_t hm_seq_stride, size_t hm_cache_bytes, int n_layers, int n_kv,
+                                                         int n_chunks, int max_ctx, size_t kv_pitch HM_IMPORT_PFX_PARAMS)
+{
+    const int seq = items.seq[blockIdx.z], layer = blockIdx.y >> 1, kv = blockIdx.y & 1;
+    const int g = blockIdx.x % n_kv, chunk = blockIdx.x / n_kv, c0 = chunk * DEC_CHUNK;
+    const int rows = step[seq].n - 1;                             // cached positions of the sequence
+    if (c0 >= rows) return;
+#if HM_PFX
+    if (share && chunk < share[seq]) return;
+#endif
+    const uint8_t* src = (const uint8_t*)kv_tab[((size_t)seq * n_layers + layer) * 2 + kv] + (size_t)g * 68;
+    uint8_t* dst = hm_base + (size_t)seq * hm_seq_stride + (size_t)(layer * 2 + kv) * hm_cache_bytes + (size_t)(g * n_chunks + chunk) * HMQ4_CHUNK_BYTES;
+    unsigned* raw = (unsigned*)g_smem;                            // [256][17]: the slices as they lie in the cache
+    uint8_t* rb = (uint8_t*)raw;
+    {
+        const int p = threadIdx.x, row = min(c0 + p, max_ctx - 1);
+        const gmem_u32 s = as_global(src + (size_t)row * kv_pitch);
+#pragma unroll
+        for (int j = 0; j < 17; j++) raw[p * 17 + j] = s[j];
+        // (a row of 17 dwords: 256 threads on their own rows meet no bank twice)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            uint8_t* blk = rb + p * 68 + b * 34;
+            const uint16_t d = *(const uint16_t*)blk;
+            int m = 0;
+            for (int i = 0; i < 32; i++) { const int q = (int8_t)blk[2 + i]; m = max(m, q < 0 ? -q : q); }
+            const uint16_t d4 = kvq4_delta(m, d);
+            for (int i = 0; i < 32; i++) blk[2 + i] = (uint8_t)(kvq4_quant((int8_t)blk[2 + i], d, d4) + KVQ4_BIAS);
+            *(uint16_t*)blk = d4;
+        }
+    }
+    __syncthreads();
+    auto elem = [&](unsigned p, unsigned e) -> unsigned { return rb[p * 68u + e + (e < 32u ? 2u : 4u)]; };
+    for (unsigned q = threadIdx.x; q < 512u; q += 256u) {
+        unsigned w[4] = {0, 0, 0, 0};
+        const unsigned lq = (q >> 4) & 3u, lc = q & 15u;
+        if (kv == 0) {
+            // K piece q = 64 j + 16 lq + lc: elements 16 lq .. 16 lq + 15 of positions 32 j + lc (low nibbles) and 32 j + 16 + lc (high)
+            const unsigned p = 32u * (q >> 6) + lc;
+#pragma unroll
+            for (unsigned i = 0; i < 16; i++) w[i >> 2] |= (elem(p, 16u * lq + i) | (elem(p + 16u, 16u * lq + i) << 4)) << (8u * (i & 3u));
+        } else {
+            // V piece q = 64 s + 16 lq + lc: dword et = element 16 et + lc at the step's 8 position slots of this lane
+            const unsigned s = q >> 6;
+#pragma unroll
+            for (unsigned et = 0; et < 4; et++)
+#pragma unroll
+                for (unsigned j = 0; j < 8; j++)
+                    w[et] |= elem(32u * s + 16u * (j >> 2) + 4u * lq + (j & 3u), 16u * et + lc) << (4u * (j >> 1) + 16u * (j & 1u));
+        }
+        *(uint4*)(dst + (size_t)q * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    {
+        const unsigned p = threadIdx.x;
+        // (rows the sequence does not have yet: delta 0, as in the Q8 import and for the same reason)
+        const bool known = c0 + (int)p < rows;
+        const uint16_t d0 = known ? *(const uint16_t*)(rb + p * 68u) : (uint16_t)0, d1 = known ? *(const uint16_t*)(rb + p * 68u + 34u) : (uint16_t)0;
+        if (kv == 0) { *(uint16_t*)(dst + hmq4_k_d_off(p, 0)) = d0; *(uint16_t*)(dst + hmq4_k_d_off(p, 1)) = d1; }
+        else { *(uint16_t*)(dst + hmq4_v_d_off(p, 0)) = d0; *(uint16_t*)(dst + hmq4_v_d_off(p, 1)) = d1; }
+    }
+}
+#endif
+
+// k_dec_attn_hm on 4-bit chunks: the same wave per (sequence, kv head, chunk), head vectors, statistics, partials and per
+// (head, position) f32 operations -- and the same ORDER of them: on rows that R leaves unchanged the two kernels see the same
+// integers and deltas in the same places of the same matrix instructions, so they write the same bits.  What differs is where
+// the integers come from: 8 + 8 requests of 16 bytes per lane for K and V instead of 16 + 16, two masks per K tile, a shift and a
+// mask-or per V pair, and the nibbles' bias taken out of the integer dots by the accumulator the score instructions start from.
+// The new position's score and p.V term come from the chip's own Q8 row, unrounded; its append writes that row to the cache
+// rows and R(row) to the shadow (a read-modify-write of the byte its nibble shares with a position 16 (K) or 2 (V) away: this
+// wave is the only writer of the chunk, and the steps of a sequence follow each other on the stream).
+template <int GRP, bool NT>
+__global__ __launch_bounds__(64 * HM_WAVES) HM_OCC void HM_KERNEL(k_dec_attn_hm_q4)(const AttnArgs a0, const int n_seq, const int n_cq HM_ATTN_PFX_PARAMS)
+{
+    constexpr int dh = 64, NWV = HM_WAVES;
+    const int g = blockIdx.x % a0.n_kv, sci = blockIdx.x / a0.n_kv, seq = sci % n_seq, cq = sci / n_seq;
+    const int w = threadIdx.x >> 6, t = threadIdx.x & 63, lc = t & 15, lq = t >> 4, hd = lc & 7, hi = lc >> 3;
+    const int chunk = NWV * cq + w, c0 = chunk * DEC_CHUNK;
+    const AttnArgs a = attn_for_seq(a0, seq);
+    const int n = a.step->n, pos = n - 1;
+    if (NWV * cq * DEC_CHUNK >= n) return;                        // (the whole workgroup)
+    const bool alive = c0 < n;                                    // (uniform per wave)
+    const int len = min(DEC_CHUNK, pos - c0);
+    const bool has_new = alive && pos < c0 + DEC_CHUNK;
+    const int kv_dim = a.n_kv * dh;
+
+    int8_t* qi8 = (int8_t*)g_smem;                                // (k_dec_attn_hm's LDS, item for item)
+    float* qd = (float*)(qi8 + 8 * dh);
+    uint16_t* d16 = (uint16_t*)(qd + 16);
+    int8_t* ki8 = (int8_t*)(d16 + 32) + w * 192;
+    int8_t* vi8 = ki8 + dh;
+    float* kd = (float*)(vi8 + dh);
+    uint16_t* kvd16 = (uint16_t*)(kd + 8);
+
+    // ---- requests: the raw projections, the rotation, then the chunk's 8 K tile pairs and deltas (pairs past the context
+    //      re-read the last live one)
+    constexpr int NJ = (GRP + NWV - 1) / NWV;
+    float qraw[NJ];
+#pragma unroll
+    for (int jj = 0; jj < NJ; jj++) qraw[jj] = a.qkv_raw[(g * GRP + min(w + NWV * jj, GRP - 1)) * dh + t];
+    float kraw = a.qkv_raw[a.n_embd + g * dh + t], vraw = a.qkv_raw[a.n_embd + kv_dim + g * dh + t];
+    if (a.qkv_plane) {
+#pragma unroll
+        for (int jj = 0; jj < NJ; jj++) qraw[jj] += a.qkv_raw[a.qkv_plane + (g * GRP + min(w + NWV * jj, GRP - 1)) * dh + t];
+        kraw += a.qkv_raw[a.qkv_plane + a.n_embd + g * dh + t];
+        vraw += a.qkv_raw[a.qkv_plane + a.n_embd + kv_dim + g * dh + t];
+    }
+    const float2 rot = a.rope_now[t & 31];
+#if HM_PFX
+    const bool shared = alive && chunk < share[seq];
+#if HM_PFX == 2
+    const uint8_t* pfx_k = shared ? pfx_tab[which[seq]] + pfx_layer : a.hm_k;
+#endif
+    const uint8_t* kc = shared ? pfx_k + (size_t)(g * a.n_chunks + chunk) * HMQ4_CHUNK_BYTES
+                               : a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HMQ4_CHUNK_BYTES;
+#else
+    const uint8_t* kc = a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HMQ4_CHUNK_BYTES;
+#endif
+    const uint8_t* vc = kc + a.hm_cache_bytes;
+    const int Tl = max(len - 1, 0) >> 4, Sl = Tl >> 1;
+    typedef int hm_v4i __attribute__((ext_vector_type(4)));
+    typedef const hm_v4i __attribute__((address_space(1)))* gmem_v4i;
+    hm_v4i ka[8], kdw[8];
+    if (alive) {
+        const gmem_v4i kq = (gmem_v4i)(uintptr_t)(kc + t * 16);
+        const gmem_v4i kdp = (gmem_v4i)(uintptr_t)(kc + HMQ4_Q_BYTES + hi * 512 + lq * 128);
+#if HM_PFX
+        if (NT && shared && !HM_PFX_SHARED_NT) {                  // a shared chunk is meant to stay in the caches: default policy
+#pragma unroll
+            for (int j = 0; j < 8; j++) ka[j] = *(kq + min(j, Sl) * 64);
+#pragma unroll
+            for (int j = 0; j < 8; j++) kdw[j] = *(kdp + j);
+        } else {
+#endif
+#pragma unroll
+        for (int j = 0; j < 8; j++) ka[j] = HM_LD(kq + min(j, Sl) * 64);
+#pragma unroll
+        for (int j = 0; j < 8; j++) kdw[j] = HM_LD(kdp + j);
+#if HM_PFX
+        }
+#endif
+    }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- head vectors of the group: this wave's share
+#pragma unroll
+    for (int jj = 0; jj < NJ; jj++) {
+        const int j = w + NWV * jj;
+        if (j < GRP) head_prep_cs(qraw[jj], true, true, rot, dh, GTEN_Q8, qi8 + j * dh, qd + 2 * j, d16 + 4 * j);
+    }
+    if (has_new) {
+        head_prep_cs(kraw, true, true, rot, dh, GTEN_Q8, ki8, kd, kvd16);
+        head_prep_cs(vraw, true, false, rot, dh, GTEN_Q8, vi8, kd + 4, kvd16 + 4);
+    }
+    __syncthreads();
+    if (!alive) return;
+    const bool bsel = ((hi == 0) == (lq < 2)) && hd < GRP;
+    hm_v4i qb = *(const hm_v4i*)(qi8 + hd * dh + 16 * lq);
+    const hm_v4i z = {0, 0, 0, 0};
+    qb = bsel ? qb : z;
+    // the bias of the K nibbles: every row of an all-ones A operand is the column's sum of its head block; the score instructions
+    // start from -8 times it
+    hm_v4i c8;
+    {
+        const hm_v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+        const int nb = -KVQ4_BIAS * __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, qb, z, 0, 0, 0)[0];
+        c8 = hm_v4i{nb, nb, nb, nb};
+    }
+    const float dq = qd[2 * hd + hi];
+    const unsigned pn = (unsigned)(pos - c0);
+    float scn = -INFINITY;
+    if (has_new) {
+        {
+            uint8_t* krow = a.kcache + (size_t)pos * a.kv_pitch + (size_t)g * 68, *vrow = a.vcache + (size_t)pos * a.kv_pitch + (size_t)g * 68;
+            const unsigned kb = (uint8_t)ki8[t], vb = (uint8_t)vi8[t], b = (unsigned)t >> 5;
+            store_global<uint8_t>(krow + b * GTEN_Q8_BYTES + 2 + (t & 31), (uint8_t)kb);
+            store_global<uint8_t>(vrow + b * GTEN_Q8_BYTES + 2 + (t & 31), (uint8_t)vb);
+            // the shadow takes R(row): this lane's nibble beside the one that shares its byte
+            uint16_t kd4, vd4;
+            const unsigned kn4 = (unsigned)(hmq4_round_lane((int8_t)kb, kvd16[b], kd4) + KVQ4_BIAS);
+            const unsigned vn4 = (unsigned)(hmq4_round_lane((int8_t)vb, kvd16[4 + b], vd4) + KVQ4_BIAS);
+            uint8_t* kcw = a.hm_k + (size_t)(g * a.n_chunks + chunk) * HMQ4_CHUNK_BYTES;
+            uint8_t* vcw = kcw + a.hm_cache_bytes;
+            const unsigned ki = hmq4_k_q_off(pn, (unsigned)t), vi = hmq4_v_q_off(pn, (unsigned)t);
+            const unsigned ko = kcw[ki >> 1], vo = vcw[vi >> 1];
+            store_global<uint8_t>(kcw + (ki >> 1), (uint8_t)((ki & 1u) ? (ko & 0x0fu) | (kn4 << 4) : (ko & 0xf0u) | kn4));
+            store_global<uint8_t>(vcw + (vi >> 1), (uint8_t)((vi & 1u) ? (vo & 0x0fu) | (vn4 << 4) : (vo & 0xf0u) | vn4));
+            if ((t & 31) == 0) {
+                store_global<uint16_t>(krow + b * GTEN_Q8_BYTES, kvd16[b]);
+                store_global<uint16_t>(vrow + b * GTEN_Q8_BYTES, kvd16[4 + b]);
+                store_global<uint16_t>(kcw + hmq4_k_d_off(pn, b), kd4);
+                store_global<uint16_t>(vcw + hmq4_v_d_off(pn, b), vd4);
+            }
+        }
+        const hm_v4i kn = *(const hm_v4i*)(ki8 + 16 * lq);
+        const hm_v4i cn = __builtin_amdgcn_mfma_i32_16x16x64_i8(kn, qb, z, 0, 0, 0);
+        const float tn = (float)cn[0] * (dq * kd[hi]);
+        scn = (tn + hm_ror8(tn)) * 0.125f;
+    }
+
+    // ---- scores: lane (lc, lq) keeps positions 16 T + 4 lq + 2 hi + u (u = 0, 1) under head hd
+    float sc[16][2];
+#pragma unroll
+    for (int T = 0; T < 16; T++) {
+        const hm_v4i m4 = {0x0f0f0f0f, 0x0f0f0f0f, 0x0f0f0f0f, 0x0f0f0f0f};
+        const hm_v4i kt = ((T & 1) ? ka[T >> 1] >> 4 : ka[T >> 1]) & m4;
+        const hm_v4i c = __builtin_amdgcn_mfma_i32_16x16x64_i8(kt, qb, c8, 0, 0, 0);
+        const unsigned w0 = (unsigned)kdw[T >> 1][(T & 1) * 2], w1 = (unsigned)kdw[T >> 1][(T & 1) * 2 + 1];
+        float term[4];
+        term[0] = (float)c[0] * (dq * h2f((uint16_t)(w0 & 0xffffu)));
+        term[1] = (float)c[1] * (dq * h2f((uint16_t)(w0 >> 16)));
+        term[2] = (float)c[2] * (dq * h2f((uint16_t)(w1 & 0xffffu)));
+        term[3] = (float)c[3] * (dq * h2f((uint16_t)(w1 >> 16)));
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const float mine = hi ? term[2 + u] : term[u], send = hi ? term[u] : term[2 + u];
+            const float both = mine + hm_ror8(send);
+            const bool live = 16 * T + 4 * lq + 2 * hi + u < len;
+            sc[T][u] = live ? both * 0.125f : -INFINITY;
+        }
+    }
+    // ---- the V chunk and its deltas are requested now
+    hm_v4i va[8], vdw[8];
+    {
+        const gmem_v4i vq = (gmem_v4i)(uintptr_t)(vc + t * 16);
+        const gmem_v4i vdp = (gmem_v4i)(uintptr_t)(vc + HMQ4_Q_BYTES + (lq * 2 + hi) * 128);
+#if HM_PFX
+        if (NT && shared && !HM_PFX_SHARED_NT) {
+#pragma unroll
+            for (int s = 0; s < 8; s++) va[s] = *(vq + min(s, Sl) * 64);
+#pragma unroll
+            for (int s = 0; s < 8; s++) vdw[s] = *(vdp + s);
+        } else {
+#endif
+#pragma unroll
+        for (int s = 0; s < 8; s++) va[s] = HM_LD(vq + min(s, Sl) * 64);
+#pragma unroll
+        for (int s = 0; s < 8; s++) vdw[s] = HM_LD(vdp + s);
+#if HM_PFX
+        }
+#endif
+    }
+    // ---- chunk maximum and sum of exponentials per head
+    float M = scn;
+#pragma unroll
+    for (int T = 0; T < 16; T++) M = fmaxf(M, fmaxf(sc[T][0], sc[T][1]));
+    M = fmaxf(M, hm_ror8(M));
+    M = hm_rows_max(M);
+    float L = 0.f;
+#pragma unroll
+    for (int T = 0; T < 16; T++) {
+        sc[T][0] = __expf(sc[T][0] - M);
+        sc[T][1] = __expf(sc[T][1] - M);
+        L += sc[T][0] + sc[T][1];
+    }
+    L += hm_ror8(L);
+    L = hm_rows_sum(L);
+    float en = 0.f;
+    if (has_new) { en = __expf(scn - M); L += en; }
+    if (lq == 0 && hi == 0 && hd < GRP)
+        *(float2*)(a.stats + ((size_t)(g * GRP + hd) * a.n_chunks + chunk) * 2) = make_float2(M, L);
+    const float rL = recip_rn(L);
+
+    // ---- the probabilities and the Q8 scale of every block of 32 positions
+    const int sn = (int)(pn >> 5);
+    const float pnew = en * rL;
+    float am[8];
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        sc[2 * s][0] *= rL; sc[2 * s][1] *= rL; sc[2 * s + 1][0] *= rL; sc[2 * s + 1][1] *= rL;
+        am[s] = fmaxf(fmaxf(sc[2 * s][0], sc[2 * s][1]), fmaxf(sc[2 * s + 1][0], sc[2 * s + 1][1]));
+    }
+#pragma unroll
+    for (int s = 0; s < 8; s++) am[s] = fmaxf(am[s], hm_ror8(am[s]));
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(am[s]), __float_as_uint(am[s]), false, false);
+        am[s] = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    }
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(am[s]), __float_as_uint(am[s]), false, false);
+        am[s] = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+        if (has_new && s == sn) am[s] = fmaxf(am[s], pnew);
+    }
+    float pnq = 0.f;
+    att_f4 acc[4];
+#pragma unroll
+    for (int et = 0; et < 4; et++) acc[et] = att_f4{0.f, 0.f, 0.f, 0.f};
+    // ---- per block: Q8 rounding, the V deltas folded in (one fp16 rounding), p.V on the nibbles widened to exact f16 integers
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const Q8Scale qs = q8_scale_from_absmax(am[s]);
+        if (has_new && s == sn) pnq = (float)q8_round(pnew, qs.scale) * qs.ddeq;
+        unsigned own[2][2];
+#pragma unroll
+        for (int tp = 0; tp < 2; tp++) {
+            const unsigned d0 = (unsigned)vdw[s][2 * tp], d1 = (unsigned)vdw[s][2 * tp + 1];
+            const float q0 = (float)q8_round(sc[2 * s + tp][0], qs.scale) * qs.ddeq, q1 = (float)q8_round(sc[2 * s + tp][1], qs.scale) * qs.ddeq;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const float dv0 = h2f((uint16_t)(h ? d0 >> 16 : d0 & 0xffffu)), dv1 = h2f((uint16_t)(h ? d1 >> 16 : d1 & 0xffffu));
+                const hm_h2 pr = {f2hv(q0 * dv0), f2hv(q1 * dv1)};
+                own[tp][h] = __builtin_bit_cast(unsigned, pr);
+            }
+        }
+        att_h8 bp[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const unsigned wv[4] = {own[0][h], hm_ror8_u(own[0][h]), own[1][h], hm_ror8_u(own[1][h])};
+            __builtin_memcpy(&bp[h], wv, 16);
+        }
+#pragma unroll
+        for (int et = 0; et < 4; et++) {
+            const unsigned vw = (unsigned)va[s][et];
+            const unsigned wv[4] = {hmq4_pair_to_h2(vw, 0), hmq4_pair_to_h2(vw, 1), hmq4_pair_to_h2(vw, 2), hmq4_pair_to_h2(vw, 3)};
+            att_h8 av;
+            __builtin_memcpy(&av, wv, 16);
+            acc[et] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bp[et >> 1], acc[et], 0, 0, 0);
+        }
+    }
+    // ---- the new position's term from the chip: out[head][e] += f16(p dv[half]) v[e]
+    if (has_new) {
+#pragma unroll
+        for (int et = 0; et < 4; et++) {
+            const float pv = (float)f2hv(pnq * h2f(kvd16[4 + (et >> 1)]));
+            const unsigned vb = *(const unsigned*)(vi8 + 16 * et + 4 * lq);
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[et][i] += pv * (float)(int8_t)((vb >> (8 * i)) & 0xffu);
+        }
+    }
+    if (hi == 0 && hd < GRP) {
+        float* o = a.att_part + ((size_t)(g * GRP + hd) * a.n_chunks + chunk) * dh + 4 * lq;
 #pragma unroll
         for (int et = 0; et < 4; et++) *(float4*)(o + 16 * et) = make_float4(acc[et][0], acc[et][1], acc[et][2], acc[et][3]);
     }

@@ -175,7 +175,9 @@ class GtenHip:
     SHIFT_ITEM = np.dtype([("k", np.uint64), ("v", np.uint64), ("n", np.int32), ("keep", np.int32), ("drop", np.int32), ("pad", np.int32)])
     EMBED_SYMBOLS = ["gten_hip_pool_rows"]                       # include/gten_hip_embed.h (rows of several texts pooled into one vector each)
     POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HIP_POOL_*
-    GROUPS_MAX = 64                                              # GTEN_GROUPS_MAX
+    # include/gten_hip_kvq4.h (4-bit head-major K / V shadows of the wide decoders)
+    KVQ4_SYMBOLS = ["gten_hip_set_kv_shadow_q4", "gten_hip_decoder_kv_shadow_info", "gten_hip_kv_round_q4", "gten_hip_decoder_kv_shadow_read"]
+    GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
     def __init__(self, path=None):
@@ -296,6 +298,10 @@ class GtenHip:
         self._beam_info = _sig(L, "gten_hip_decoder_beam_info", ci, [vp, C.POINTER(ci), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)])
         self._kv_shift = _sig(L, "gten_hip_kv_shift", ci, [vp, ci, ci, sz, ci, ci])
         self._pool_rows = _sig(L, "gten_hip_pool_rows", ci, [vp, ci, sz, ci, vp, ci, ci, ci, vp])
+        self._kv_shadow_q4 = _sig(L, "gten_hip_set_kv_shadow_q4", ci, [ci])
+        self._kv_shadow_info = _sig(L, "gten_hip_decoder_kv_shadow_info", ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong)])
+        self._kv_round_q4 = _sig(L, "gten_hip_kv_round_q4", ci, [vp, ci, sz, sz])
+        self._kv_shadow_read = _sig(L, "gten_hip_decoder_kv_shadow_read", ci, [vp, ci, ci, ci, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -983,6 +989,18 @@ class GtenHip:
     def set_kv_head_major(self, on):
         """decoders of 16+ sequences created from now on: head-major shadows of the K / V caches (default) or the cache rows as they lie"""
         self._check(self._kv_head_major(1 if on else 0))
+
+    def set_kv_shadow_q4(self, on):
+        """decoders created from now on keep their head-major K / V shadows as 4-bit shadows (lossy; only where a Q8 shadow would exist)
+        or as they always did (default)"""
+        self._check(self._kv_shadow_q4(1 if on else 0))
+
+    def kv_round_q4_rc(self, rows, n_rows, row_bytes, pitch=None):
+        return self._kv_round_q4(rows.ptr, int(n_rows), int(row_bytes), int(row_bytes if pitch is None else pitch))
+
+    def kv_round_q4(self, rows, n_rows, row_bytes, pitch=None):
+        """the 4-bit shadows' rounding R in place on every Q8 block of a row view (a buffer or a view of one); asynchronous"""
+        self._check(self.kv_round_q4_rc(rows, n_rows, row_bytes, pitch))
 
     def set_ffn_streamed(self, on):
         """gate | up of full 128-row q4 lanes as the streamed kernel (default) or as k_dec_mmvh: the same bits"""

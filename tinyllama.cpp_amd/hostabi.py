@@ -103,6 +103,8 @@ class GtenHost:
     # include/gten_host_embed.h (hidden rows of texts and one pooled vector per text, host/capi_embed.cpp; the plan: host/embed_plan.h)
     EMBED_SYMBOLS = ["gten_host_embed_last_error", "gten_host_embed_plan", "gten_host_model_hidden_many", "gten_host_model_embed_many"]
     POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HOST_POOL_*
+    # include/gten_host_kvq4.h (4-bit head-major K / V shadows of a batch's shared decoder, host/capi_kvq4.cpp)
+    KVQ4_SYMBOLS = ["gten_host_batch_kv_shadow_info", "gten_host_batch_kv_round_q4", "gten_host_batch_kv_shadow_read", "gten_host_batch_kv_rows"]
     SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -332,6 +334,10 @@ class GtenHost:
         self._embed_plan = _sig(L, "gten_host_embed_plan", ci, [vp, ci, ci, vp, vp])
         self._hidden_many = _sig(L, "gten_host_model_hidden_many", ci, [vp, vp, vp, ci, ci, vp, C.POINTER(ci)])
         self._embed_many = _sig(L, "gten_host_model_embed_many", ci, [vp, vp, vp, ci, ci, ci, ci, vp])
+        self._bkv_shadow_info = _sig(L, "gten_host_batch_kv_shadow_info", ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ull)])
+        self._bkv_round_q4 = _sig(L, "gten_host_batch_kv_round_q4", ci, [vp, ci, ci])
+        self._bkv_shadow_read = _sig(L, "gten_host_batch_kv_shadow_read", ci, [vp, ci, ci, ci, vp, vp])
+        self._bkv_rows = _sig(L, "gten_host_batch_kv_rows", ci, [vp, ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -2211,6 +2217,29 @@ class HostBatch:
         hm, imp, lau = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
         self._ck(self.host._bkvinfo(self.h, C.byref(hm), C.byref(imp), C.byref(lau)), "batch_kv_info")
         return bool(hm.value), imp.value, lau.value
+
+    def kv_shadow_info(self):
+        """(bits per quant of the shared decoder's K / V shadows -- 4, 8, 16 or 0 for none --, bytes of one chunk of one matrix, bytes of all shadows)"""
+        bits, chunk, total = C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+        self._ck(self.host._bkv_shadow_info(self.h, C.byref(bits), C.byref(chunk), C.byref(total)), "batch_kv_shadow_info")
+        return bits.value, chunk.value, total.value
+
+    def kv_round_q4(self, seq, n_rows):
+        """the 4-bit shadows' rounding R in place on cache rows [0, n_rows) of sequence seq: every layer, K and V"""
+        self._ck(self.host._bkv_round_q4(self.h, int(seq), int(n_rows)), "batch_kv_round_q4")
+
+    def kv_rows(self, seq, layer):
+        """(device address of K row 0, of V row 0, pitch in bytes) of sequence seq's cache rows on `layer`"""
+        k, v, p = C.c_void_p(0), C.c_void_p(0), C.c_size_t(0)
+        self._ck(self.host._bkv_rows(self.h, int(seq), int(layer), C.byref(k), C.byref(v), C.byref(p)), "batch_kv_rows")
+        return k.value, v.value, p.value
+
+    def kv_shadow_read(self, seq, layer, n_rows):
+        """(K, V) of positions [0, n_rows) of sequence seq's own shadow on `layer` as dense Q8 rows: uint8 [n_rows][row_bytes] each"""
+        rb = self.kv_row_bytes()
+        k, v = np.zeros((n_rows, rb), np.uint8), np.zeros((n_rows, rb), np.uint8)
+        self._ck(self.host._bkv_shadow_read(self.h, int(seq), int(layer), int(n_rows), _ptr(k), _ptr(v)), "batch_kv_shadow_read")
+        return k, v
 
     def time_family(self, family, n, reps=20):
         us, cnt = C.c_double(0.0), C.c_int(0)
