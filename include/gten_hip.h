@@ -152,7 +152,8 @@ int gten_hip_set_decode_exact(int on);
  * not possible through this interface; a caller that writes cache rows with its own kernels restarts the sequence --
  * slot_start / step at another position / generate_multi -- to the same effect).
  * An opt-in, lossy 4-bit form of these Q8 shadows -- 36 instead of 68 bytes per (kv head, position), the rows themselves
- * unchanged -- with its switch, its rounding operator and a read-back of a shadow is declared in include/gten_hip_kvq4.h. */
+ * unchanged -- with its switch, its rounding operator and a read-back of a shadow is declared in include/gten_hip_kvq4.h; the
+ * like for the f16 shadows, as FP8 (E4M3) codes of 64 instead of 128 bytes, in include/gten_hip_kvfp8.h. */
 int gten_hip_set_kv_head_major(int on);
 /* gate | up (with the silu . mul chain) and the lm_head of lanes of 49-64 or 128 rows as the streamed kernels of
  * csrc/gten_decode_ffn.h (on != 0, the default) or as the launches every other shape takes (0): k_dec_mmvh (+ k_dec_silumul_rows

@@ -24,8 +24,9 @@ extern "C" {
  * prefix shadows and group records of such a decoder are 4-bit shadows too. */
 int gten_hip_set_kv_shadow_q4(int on);
 
-/* What shadows a decoder keeps: bits = 4 (4-bit), 8 (Q8), 16 (f16 activations) or 0 (none); the bytes of one chunk of one
- * matrix (9216 / 17408 / 32768 / 0) and of all shadows of its sequences together.  Any output may be null. */
+/* What shadows a decoder keeps, as the pair (bits, bytes of one chunk of one matrix): (4, 9216) 4-bit, (8, 17408) Q8,
+ * (8, 16384) FP8 shadows of f16 activations (gten_hip_kvfp8.h), (16, 32768) f16, (0, 0) none -- the chunk bytes tell the two
+ * 8-bit forms apart; and the bytes of all shadows of its sequences together.  Any output may be null. */
 int gten_hip_decoder_kv_shadow_info(gten_hip_decoder* dec, int* bits, int* chunk_bytes, unsigned long long* bytes_total);
 
 /* R in place on every block of a view of Q8 rows (device memory): row r is the row_bytes bytes at rows + r * pitch, row_bytes a

@@ -253,6 +253,7 @@ struct gten_hip_decoder {
     uint8_t* hm = nullptr;
     size_t hm_seq_stride = 0, hm_cache_bytes = 0, hm_chunk_bytes = 0;
     bool hm_q4 = false;                 // the shadows are 4-bit shadows (gten_hip_set_kv_shadow_q4 when the decoder was created)
+    bool hm_fp8 = false;                // the shadows of an f16 decoder are FP8 shadows (gten_hip_set_kv_shadow_fp8 when it was created)
     std::vector<char> hm_dirty;
     unsigned long long hm_imports = 0, hm_import_launches = 0;
     // ---- shared prefixes (gten_hip_decoder_prefix_set, include/gten_hip_prefix_decode.h; decoders with shadows only).  Pfx::hm: ONE more
@@ -407,6 +408,8 @@ static bool g_kv_head_major = true;
 // ... and, where such a decoder would keep Q8 shadows, keep them as 4-bit shadows instead (include/gten_hip_kvq4.h):
 // lossy, so off by default
 static bool g_kv_shadow_q4 = false;
+// ... and, where it would keep f16 shadows, keep them as E4M3 codes (include/gten_hip_kvfp8.h): lossy, off by default
+static bool g_kv_shadow_fp8 = false;
 // gten_hip_set_prefix_decode_shared: gten_hip_decoder_slot_share records promises (1) or nothing (0: every sequence decodes on
 // its own shadow, as before -- the tests' and the measurement's other side).  ON by default: tools/prefix_cost.py --decode measures
 // the shared step and the serving queue faster with it on by far more than the off runs' own spread.
@@ -415,8 +418,9 @@ static bool g_pfx_shared = PFX_SHARED_DEFAULT;
 // host side, beside AttnArgs: the prefix shadow of the layer (K; V follows it) and the lane's shared counts -- k null: the decoder
 // holds no prefix shadow and launches the kernels it always did
 // (tab: the decoder holds several prefix shadows -- k is then unused, the kernels take shadow which[seq] from the table)
-// (q4: the shadows, the decoder's own and every prefix's, are 4-bit shadows -- k_dec_attn_hm_q4 in place of k_dec_attn_hm)
-struct PfxArgs { const uint8_t* k = nullptr; const int* share = nullptr; const uint8_t* const* tab = nullptr; size_t layer_off = 0; const int* which = nullptr; bool q4 = false; };
+// (q4: the shadows, the decoder's own and every prefix's, are 4-bit shadows -- k_dec_attn_hm_q4 in place of k_dec_attn_hm;
+//  fp8: they are FP8 shadows -- k_dec_attn_hm_fp8 in place of k_dec_attn_hm_f16)
+struct PfxArgs { const uint8_t* k = nullptr; const int* share = nullptr; const uint8_t* const* tab = nullptr; size_t layer_off = 0; const int* which = nullptr; bool q4 = false, fp8 = false; };
 extern "C" int gten_hip_set_kv_head_major(int on)
 {
     g_kv_head_major = on != 0;
@@ -613,6 +617,18 @@ static int launch_attention_g(const AttnArgs& t, int n_seq, const PfxArgs& pfx)
     }
     if constexpr (ADT == GTEN_F16) if (grouped_hm_f16(t, n_seq)) {
         const int n_cq = (t.n_chunks + HM_WAVES - 1) / HM_WAVES;
+        if (pfx.fp8) {
+            const dim3 fgrid(n_seq * n_cq * t.n_kv), fblock(64 * HM_WAVES);
+            if (pfx.tab) {
+                if (n_seq >= 128) DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8_pfxn<GRP, true>), fgrid, fblock, 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+                else DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8_pfxn<GRP, false>), fgrid, fblock, 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
+            } else if (pfx.k) {
+                if (n_seq >= 128) DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8_pfx<GRP, true>), fgrid, fblock, 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+                else DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8_pfx<GRP, false>), fgrid, fblock, 2048, t, n_seq, n_cq, pfx.k, pfx.share);
+            } else if (n_seq >= 128) DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8<GRP, true>), fgrid, fblock, 2048, t, n_seq, n_cq);
+            else DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_fp8<GRP, false>), fgrid, fblock, 2048, t, n_seq, n_cq);
+            return 0;
+        }
         if (pfx.tab) {
             if (n_seq >= 128)
                 DEC_LAUNCH(KT_DEC_ATTN_SCORE, (k_dec_attn_hm_f16_pfxn<GRP, true>), dim3(n_seq * n_cq * t.n_kv), dim3(64 * HM_WAVES), 2048, t, n_seq, n_cq, pfx.tab, pfx.layer_off, pfx.share, pfx.which);
@@ -1464,6 +1480,7 @@ static int enqueue_step_wide(gten_hip_decoder* dc, int lane)
         }
         PfxArgs pfx;
         pfx.q4 = dc->hm_q4;
+        pfx.fp8 = dc->hm_fp8;
         if (dc->pfxn) {
             pfx.tab = (const uint8_t* const*)dc->pfx_hm_tab; pfx.layer_off = (size_t)l * 2 * dc->hm_cache_bytes;
             pfx.share = dc->share_dev + (size_t)lane * S; pfx.which = dc->which_dev + (size_t)lane * S;
@@ -1782,7 +1799,8 @@ static int decoder_build(gten_hip_decoder* dc, const gten_hip_decoder_desc& d, c
         const int grp = d.n_heads / d.n_kv_heads;
         if (wide && g_kv_head_major && !dc->exact && (d.adtype == GTEN_Q8 || d.adtype == GTEN_F16) && dh == 64 && (grp == 8 || grp == 4 || grp == 2 || grp == 1)) {
             dc->hm_q4 = g_kv_shadow_q4 && d.adtype == GTEN_Q8;
-            dc->hm_chunk_bytes = dc->hm_q4 ? HMQ4_CHUNK_BYTES : d.adtype == GTEN_Q8 ? HM_CHUNK_BYTES : HMF_CHUNK_BYTES;
+            dc->hm_fp8 = g_kv_shadow_fp8 && d.adtype == GTEN_F16;
+            dc->hm_chunk_bytes = dc->hm_q4 ? HMQ4_CHUNK_BYTES : d.adtype == GTEN_Q8 ? HM_CHUNK_BYTES : dc->hm_fp8 ? HMF8_CHUNK_BYTES : HMF_CHUNK_BYTES;
             dc->hm_cache_bytes = (size_t)d.n_kv_heads * dc->n_chunks * dc->hm_chunk_bytes;
             dc->hm_seq_stride = (size_t)d.n_layers * 2 * dc->hm_cache_bytes;
             GTR_CHECK(hipMalloc((void**)&dc->hm, S * dc->hm_seq_stride));
@@ -2020,6 +2038,9 @@ static int hm_import_pfx_launch(gten_hip_decoder* dc, const HmImportList& it, co
     else if (d.adtype == GTEN_Q8)
         GTR_LAUNCH(KT_PACK, k_kv_import_hm_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 68, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
                    d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
+    else if (dc->hm_fp8)
+        GTR_LAUNCH(KT_PACK, k_kv_import_hm_fp8_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 33 * 4, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
+                   d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
     else
         GTR_LAUNCH(KT_PACK, k_kv_import_hm_f16_pfx, grid, dim3(256), (size_t)DEC_CHUNK * 33 * 4, it, step, tab, base, dc->hm_seq_stride, dc->hm_cache_bytes,
                    d.n_layers, d.n_kv_heads, dc->n_chunks, d.max_ctx, kv_pitch, share);
@@ -2106,6 +2127,10 @@ static int pre_run(gten_hip_decoder* dc)
                        dc->n_chunks, d.max_ctx, kv_pitch);
         else if (d.adtype == GTEN_Q8)
             GTR_LAUNCH(KT_PACK, k_kv_import_hm, dim3(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, items.n), dim3(256), (size_t)DEC_CHUNK * 68, items,
+                       (const DecStep*)dc->step, (const void* const*)dc->kv_tab, dc->hm, dc->hm_seq_stride, dc->hm_cache_bytes, d.n_layers, d.n_kv_heads,
+                       dc->n_chunks, d.max_ctx, kv_pitch);
+        else if (dc->hm_fp8)
+            GTR_LAUNCH(KT_PACK, k_kv_import_hm_fp8, dim3(d.n_kv_heads * dc->n_chunks, d.n_layers * 2, items.n), dim3(256), (size_t)DEC_CHUNK * 33 * 4, items,
                        (const DecStep*)dc->step, (const void* const*)dc->kv_tab, dc->hm, dc->hm_seq_stride, dc->hm_cache_bytes, d.n_layers, d.n_kv_heads,
                        dc->n_chunks, d.max_ctx, kv_pitch);
         else
@@ -2992,3 +3017,6 @@ int gten_hip_decoder_logits_seq(gten_hip_decoder* dc, int seq, float* logits_hos
 
 // ---- 4-bit K / V shadows: the switch, the rounding operator and the shadow's read-back (include/gten_hip_kvq4.h)
 #include "gten_decode_kvq4.h"
+
+// ---- FP8 K / V shadows of the f16 configuration: the same three (include/gten_hip_kvfp8.h)
+#include "gten_decode_kvfp8.h"

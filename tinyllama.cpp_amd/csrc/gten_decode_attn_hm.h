@@ -44,6 +44,7 @@
 // p.V (the matrix core's order over another assignment of positions to its steps).
 // three waves per SIMD: the kernel fits 160 registers without a spill (hipcc takes 176 when left alone)
 #include "gten_kvq4_math.h"
+#include "gten_kvfp8_math.h"
 #ifndef HM_OCC
 #define HM_OCC __attribute__((amdgpu_waves_per_eu(3)))
 #endif
@@ -173,6 +174,34 @@ __host__ __device__ __forceinline__ unsigned hmf_k_off(unsigned p, unsigned e)
 __host__ __device__ __forceinline__ unsigned hmf_v_off(unsigned p, unsigned e)
 {
     return (p >> 5) * 4096u + (e >> 4) * 1024u + (((((p & 15u) >> 2) * 16u) + (e & 15u)) * 16u) + (4u * ((p >> 4) & 1u) + (p & 3u)) * 2u;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// FP8 shadows of the f16 configuration (gten_hip_set_kv_shadow_fp8, include/gten_hip_kvfp8.h): a chunk holds the
+// E4M3 code R8(x) of every element of its 256 positions (gten_kvfp8_math.h; no scale, a direct cast) -- HMF8_CHUNK_BYTES = 16 384
+// per matrix, 64 instead of 128 bytes per (kv head, position), ONE contiguous run.  The f16 chunk's operand order, two of its
+// 16-byte pieces in one:
+//   a K chunk   16 tiles of 16 positions x 1 KiB; lane l = 16 lq + lc owns bytes [16 l, 16 l + 16) of a tile: bytes 0 .. 7 are
+//               elements 8 lq .. 8 lq + 7 of position 16 T + lc (the f16 chunk's piece of step 0), bytes 8 .. 15 elements
+//               32 + 8 lq .. + 7 (its piece of step 1) -- one request, expanded, is BOTH A operands of the tile's two
+//               v_mfma_f32_16x16x32_f16
+//   a V chunk   8 steps of 32 positions x 2 KiB = 2 x 1 KiB; lane l owns 16 bytes of (step s, half h): bytes 0 .. 7 are element
+//               16 (2 h) + lc at the 8 position slots of the f16 chunk (slot j < 4: position 32 s + 4 lq + j, j >= 4:
+//               32 s + 16 + 4 lq + j - 4), bytes 8 .. 15 element 16 (2 h + 1) + lc at the same slots -- the A operands of element
+//               tiles 2 h and 2 h + 1
+// A wave issues 16 + 16 requests of 16 bytes per lane where the f16 kernel issues 32 + 32.  The offset functions hmf8_{k,v}_off are
+// in gten_kvfp8_math.h (device-free: a host program checks that they are bijections).
+// Expansion: v_cvt_scalef32_pk_f16_fp8 under the scale 1.0 turns two codes into two halfs, one instruction per dword of operand;
+// it returns E8(c) for all 254 codes R8 produces (k_kv_round_fp8 goes through this function too, and tests/test_kv_fp8_gpu.py holds
+// it to the restatement on every f16 pattern).  Every E4M3 value is an f16 value, so the expanded operands are what the f16 kernel
+// reads from a shadow of rows rounded by R, and the instructions behind them are the f16 kernel's own.
+typedef int hmf8_v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ unsigned hmf8_lo2(unsigned c4) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c4, 1.0f, false)); }
+__device__ __forceinline__ unsigned hmf8_hi2(unsigned c4) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c4, 1.0f, true)); }
+// eight codes (two dwords, in memory order) -> the eight halfs of one matrix operand
+__device__ __forceinline__ hmf8_v4i hmf8_expand8(unsigned c0, unsigned c1)
+{
+    return hmf8_v4i{(int)hmf8_lo2(c0), (int)hmf8_hi2(c0), (int)hmf8_lo2(c1), (int)hmf8_hi2(c1)};
 }
 
 // A/B (GTEN_HIP_EXTRA_FLAGS=-DHM_PFX_SHARED_NT=1): the NT instantiations request SHARED chunks nontemporal too (DESIGN.md 3.9 has

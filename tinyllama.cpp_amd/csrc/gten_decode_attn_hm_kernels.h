@@ -19,7 +19,8 @@
 //             such instantiation: they skip chunk < share[seq] whatever the index.
 //
 // Behind the four: k_kv_import_hm_q4 and k_dec_attn_hm_q4<GRP, NT>, the Q8 pair on 4-bit chunks (gten_hip_set_kv_shadow_q4), in the same three
-// forms by the same three includes.
+// forms by the same three includes; likewise k_kv_import_hm_fp8 and k_dec_attn_hm_fp8<GRP, NT>, the f16 pair on chunks of E4M3 codes
+// (gten_hip_set_kv_shadow_fp8), behind the f16 pair.
 //
 // Why an include and not `template <..., bool PFX>`: a template parameter cannot take the two extra ARGUMENTS away.  The kernels of a
 // decoder without a prefix must keep their argument list (the kernarg segment, the SGPRs it is loaded into) and with it their
@@ -590,6 +591,275 @@ __global__ __launch_bounds__(64 * HM_WAVES) void HM_KERNEL(k_dec_attn_hm_f16)(co
         for (int j = 0; j < 8; j++) bp[j] = f2hv(sc[2 * s + (j >> 2)][j & 3] * rL);
 #pragma unroll
         for (int et = 0; et < 4; et++) acc[et] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(att_h8, va[s][et]), bp, acc[et], 0, 0, 0);
+    }
+    if (has_new) {
+        const float pv = (float)f2hv(en * rL);
+#pragma unroll
+        for (int et = 0; et < 4; et++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[et][i] += pv * h2f(vh[16 * et + 4 * lq + i]);
+    }
+    if (lc < GRP) {
+        float* o = a.att_part + ((size_t)(g * GRP + lc) * a.n_chunks + chunk) * dh + 4 * lq;
+#pragma unroll
+        for (int et = 0; et < 4; et++) *(float4*)(o + 16 * et) = make_float4(acc[et][0], acc[et][1], acc[et][2], acc[et][3]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// FP8 shadows (gten_decode_attn_hm.h, "FP8 shadows"): the f16 pair of kernels above on chunks of E4M3 codes.
+#if HM_PFX < 2
+// k_kv_import_hm_f16's grid, arguments and skips.  A thread stages ITS row as it lies and puts every element through R8 where it
+// lies (the code in the low byte of its half-word); then the pieces are gathered: a 16-byte piece is two of the f16 chunk's.
+__global__ __launch_bounds__(256) void HM_KERNEL(k_kv_import_hm_fp8)(const HmImportList items, const DecStep* __restrict__ step, const void* const* __restrict__ kv_tab,
+                                                          uint8_t* __restrict__ hm_base, size_t hm_seq_stride, size_t hm_cache_bytes, int n_layers,
+                                                          int n_kv, int n_chunks, int max_ctx, size_t kv_pitch HM_IMPORT_PFX_PARAMS)
+{
+    const int seq = items.seq[blockIdx.z], layer = blockIdx.y >> 1, kv = blockIdx.y & 1;
+    const int g = blockIdx.x % n_kv, chunk = blockIdx.x / n_kv, c0 = chunk * DEC_CHUNK;
+    const int rows = step[seq].n - 1;
+    if (c0 >= rows) return;
+#if HM_PFX
+    if (share && chunk < share[seq]) return;
+#endif
+    const uint8_t* src = (const uint8_t*)kv_tab[((size_t)seq * n_layers + layer) * 2 + kv] + (size_t)g * 128;
+    uint8_t* dst = hm_base + (size_t)seq * hm_seq_stride + (size_t)(layer * 2 + kv) * hm_cache_bytes + (size_t)(g * n_chunks + chunk) * HMF8_CHUNK_BYTES;
+    unsigned* raw = (unsigned*)g_smem;                            // [256][33]: the slices (32 dwords), padded; a half-word = its element's code
+    {
+        const int p = threadIdx.x, row = min(c0 + p, max_ctx - 1);
+        const gmem_u32 s = as_global(src + (size_t)row * kv_pitch);
+        const bool known = c0 + p < rows;                         // (rows the sequence does not have yet become zeros: code 0)
+#pragma unroll
+        for (int j = 0; j < 32; j++) {
+            const unsigned v = s[j];
+            raw[p * 33 + j] = known ? (unsigned)kvfp8_r8((uint16_t)(v & 0xffffu)) | ((unsigned)kvfp8_r8((uint16_t)(v >> 16)) << 16) : 0u;
+        }
+    }
+    __syncthreads();
+    const uint16_t* rh = (const uint16_t*)raw;
+    auto code = [&](unsigned p, unsigned e) -> unsigned { return rh[p * 66u + e]; };
+    for (unsigned q = threadIdx.x; q < 1024u; q += 256u) {
+        unsigned w[4] = {0, 0, 0, 0};
+        const unsigned lq = (q >> 4) & 3u, lc = q & 15u;
+        if (kv == 0) {
+            // K piece q = 64 T + 16 lq + lc: elements 8 lq .. + 7 and 32 + 8 lq .. + 7 of position 16 T + lc
+            const unsigned p = 16u * (q >> 6) + lc;
+#pragma unroll
+            for (unsigned i = 0; i < 16; i++) w[i >> 2] |= code(p, 32u * (i >> 3) + 8u * lq + (i & 7u)) << (8u * (i & 3u));
+        } else {
+            // V piece q = 128 s + 64 h + 16 lq + lc: elements 16 (2 h) + lc and 16 (2 h + 1) + lc at 8 positions each
+            const unsigned s = q >> 7, h = (q >> 6) & 1u;
+#pragma unroll
+            for (unsigned i = 0; i < 16; i++) {
+                const unsigned j = i & 7u, p = 32u * s + 16u * (j >> 2) + 4u * lq + (j & 3u);
+                w[i >> 2] |= code(p, 16u * (2u * h + (i >> 3)) + lc) << (8u * (i & 3u));
+            }
+        }
+        *(uint4*)(dst + (size_t)q * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+#endif
+
+// k_dec_attn_hm_f16 with every 16-byte request carrying two of its operands as codes: the same wave per (sequence, kv head, chunk),
+// head preparation, statistics, partials and join; the codes of tile T + 1 (step s + 1) are expanded while tile T (step s) is in
+// the matrix unit -- the expansion hangs on nothing but its request, so it stays off the chain M -> exp -> L -> p.  Behind the
+// expansion the score and p.V instructions are the f16 kernel's, the f32 operations in its order.
+template <int GRP, bool NT>
+__global__ __launch_bounds__(64 * HM_WAVES) void HM_KERNEL(k_dec_attn_hm_fp8)(const AttnArgs a0, const int n_seq, const int n_cq HM_ATTN_PFX_PARAMS)
+{
+    constexpr int dh = 64, NWV = HM_WAVES;
+    const int g = blockIdx.x % a0.n_kv, sci = blockIdx.x / a0.n_kv, seq = sci % n_seq, cq = sci / n_seq;
+    const int w = threadIdx.x >> 6, t = threadIdx.x & 63, lc = t & 15, lq = t >> 4;
+    const int chunk = NWV * cq + w, c0 = chunk * DEC_CHUNK;
+    const AttnArgs a = attn_for_seq(a0, seq);
+    const int n = a.step->n, pos = n - 1;
+    if (NWV * cq * DEC_CHUNK >= n) return;
+    const bool alive = c0 < n;
+    const int len = min(DEC_CHUNK, pos - c0);
+    const bool has_new = alive && pos < c0 + DEC_CHUNK;
+    const int kv_dim = a.n_kv * dh;
+
+    uint16_t* qh = (uint16_t*)g_smem;                             // [8][64] head vectors as f16 (shared)
+    uint16_t* kh = qh + 8 * dh + w * 128;                         // per wave: the new K row [64], the new V row [64]
+    uint16_t* vh = kh + dh;
+    int8_t* nul8 = (int8_t*)(qh + 8 * dh + NWV * 128);            // (head_prep_cs's Q8 outputs: unused for f16, as in k_dec_attn_hm_f16)
+    float* nulf = (float*)(nul8 + 64);
+    uint16_t* nulh = (uint16_t*)(nulf + 2);
+
+    constexpr int NJ = (GRP + NWV - 1) / NWV;
+    float qraw[NJ];
+#pragma unroll
+    for (int jj = 0; jj < NJ; jj++) qraw[jj] = a.qkv_raw[(g * GRP + min(w + NWV * jj, GRP - 1)) * dh + t];
+    float kraw = a.qkv_raw[a.n_embd + g * dh + t], vraw = a.qkv_raw[a.n_embd + kv_dim + g * dh + t];
+    if (a.qkv_plane) {
+#pragma unroll
+        for (int jj = 0; jj < NJ; jj++) qraw[jj] += a.qkv_raw[a.qkv_plane + (g * GRP + min(w + NWV * jj, GRP - 1)) * dh + t];
+        kraw += a.qkv_raw[a.qkv_plane + a.n_embd + g * dh + t];
+        vraw += a.qkv_raw[a.qkv_plane + a.n_embd + kv_dim + g * dh + t];
+        if (a.qkv_nplanes == 4) {                                 // (uniform) four planes of k_dec_wxp_f16: 2 and 3 behind the first two, in order
+            float qx[2][NJ], kx[2], vx[2];
+#pragma unroll
+            for (int q = 2; q < 4; q++) {
+                const float* pl = a.qkv_raw + (size_t)q * a.qkv_plane;
+#pragma unroll
+                for (int jj = 0; jj < NJ; jj++) qx[q - 2][jj] = pl[(g * GRP + min(w + NWV * jj, GRP - 1)) * dh + t];
+                kx[q - 2] = pl[a.n_embd + g * dh + t];
+                vx[q - 2] = pl[a.n_embd + kv_dim + g * dh + t];
+            }
+#pragma unroll
+            for (int q = 2; q < 4; q++) {
+#pragma unroll
+                for (int jj = 0; jj < NJ; jj++) qraw[jj] += qx[q - 2][jj];
+                kraw += kx[q - 2];
+                vraw += vx[q - 2];
+            }
+        }
+    }
+    const float2 rot = a.rope_now[t & 31];
+#if HM_PFX
+    const bool shared = alive && chunk < share[seq];              // (uniform per wave) this chunk comes from the prefix shadow
+#if HM_PFX == 2
+    const uint8_t* pfx_k = shared ? pfx_tab[which[seq]] + pfx_layer : a.hm_k;                  // (uniform per wave) ... of its prefix
+#endif
+    const uint8_t* kc = shared ? pfx_k + (size_t)(g * a.n_chunks + chunk) * HMF8_CHUNK_BYTES
+                               : a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HMF8_CHUNK_BYTES;
+#else
+    const uint8_t* kc = a.hm_k + (size_t)(g * a.n_chunks + (alive ? chunk : 0)) * HMF8_CHUNK_BYTES;
+#endif
+    const uint8_t* vc = kc + a.hm_cache_bytes;
+    const int Tl = max(len - 1, 0) >> 4, Sl = Tl >> 1;
+    typedef const hmf8_v4i __attribute__((address_space(1)))* gmem_v4i;
+    // the whole K chunk: 16 requests, as many registers as the f16 kernel's first eight tiles
+    hmf8_v4i kr[16];
+    const gmem_v4i kq = (gmem_v4i)(uintptr_t)(kc + t * 16);
+    if (alive) {
+#if HM_PFX
+        if (NT && shared && !HM_PFX_SHARED_NT) {
+#pragma unroll
+            for (int T = 0; T < 16; T++) kr[T] = *(kq + min(T, Tl) * 64);
+        } else
+#endif
+#pragma unroll
+        for (int T = 0; T < 16; T++) kr[T] = HM_LD(kq + min(T, Tl) * 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int jj = 0; jj < NJ; jj++) {
+        const int j = w + NWV * jj;
+        if (j < GRP) {
+            const float v = head_prep_cs(qraw[jj], true, true, rot, dh, GTEN_F16, nul8, nulf, nulh);
+            qh[j * dh + t] = f2h(v);
+        }
+    }
+    float vnew = 0.f;
+    if (has_new) {
+        const float kf = head_prep_cs(kraw, true, true, rot, dh, GTEN_F16, nul8, nulf, nulh);
+        vnew = head_prep_cs(vraw, true, false, rot, dh, GTEN_F16, nul8, nulf, nulh);
+        kh[t] = f2h(kf);
+        vh[t] = f2h(vnew);
+    }
+    __syncthreads();
+    if (!alive) return;
+    // B operand: column lc = head lc (lc < GRP), two steps of 32 elements
+    att_h8 qb[2];
+    {
+        const hmf8_v4i z = {0, 0, 0, 0};
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            const hmf8_v4i v = *(const hmf8_v4i*)(qh + min(lc, GRP - 1) * dh + 32 * ks + 8 * lq);
+            qb[ks] = __builtin_bit_cast(att_h8, lc < GRP ? v : z);
+        }
+    }
+    const unsigned pn = (unsigned)(pos - c0);
+    float scn = -INFINITY;
+    if (has_new) {
+        // the append: the f16 row to the cache rows, R8 of it to the shadow -- one byte per lane, this wave the chunk's only writer
+        // (a byte store leaves its neighbours alone: nothing to read back first)
+        uint8_t* krow = a.kcache + (size_t)pos * a.kv_pitch + (size_t)g * 128, *vrow = a.vcache + (size_t)pos * a.kv_pitch + (size_t)g * 128;
+        const uint16_t kb = kh[t], vb = vh[t];
+        store_global<uint16_t>(krow + 2 * t, kb);
+        store_global<uint16_t>(vrow + 2 * t, vb);
+        uint8_t* kcw = a.hm_k + (size_t)(g * a.n_chunks + chunk) * HMF8_CHUNK_BYTES;
+        store_global<uint8_t>(kcw + hmf8_k_off(pn, (unsigned)t), kvfp8_r8(kb));
+        store_global<uint8_t>(kcw + a.hm_cache_bytes + hmf8_v_off(pn, (unsigned)t), kvfp8_r8(vb));
+        att_f4 cn = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            const att_h8 kn = __builtin_bit_cast(att_h8, *(const hmf8_v4i*)(kh + 32 * ks + 8 * lq));     // every row of A is the new K row, unrounded
+            cn = __builtin_amdgcn_mfma_f32_16x16x32_f16(kn, qb[ks], cn, 0, 0, 0);
+        }
+        scn = cn[0] * 0.125f;
+    }
+    // ---- scores: lane (lc, lq) holds positions 16 T + 4 lq + i under head lc
+    float sc[16][4];
+    {
+        hmf8_v4i kx[2] = {hmf8_expand8((unsigned)kr[0][0], (unsigned)kr[0][1]), hmf8_expand8((unsigned)kr[0][2], (unsigned)kr[0][3])};
+#pragma unroll
+        for (int T = 0; T < 16; T++) {
+            const int U = min(T + 1, 15);
+            const hmf8_v4i nx[2] = {hmf8_expand8((unsigned)kr[U][0], (unsigned)kr[U][1]), hmf8_expand8((unsigned)kr[U][2], (unsigned)kr[U][3])};
+            att_f4 c = {0.f, 0.f, 0.f, 0.f};
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(att_h8, kx[0]), qb[0], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(att_h8, kx[1]), qb[1], c, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; i++) sc[T][i] = (16 * T + 4 * lq + i < len) ? c[i] * 0.125f : -INFINITY;
+            kx[0] = nx[0]; kx[1] = nx[1];
+        }
+    }
+    // ---- the V chunk (the K registers are free)
+    hmf8_v4i vr[8][2];
+    {
+        const gmem_v4i vq = (gmem_v4i)(uintptr_t)(vc + t * 16);
+#if HM_PFX
+        if (NT && shared && !HM_PFX_SHARED_NT) {
+#pragma unroll
+            for (int s = 0; s < 8; s++)
+#pragma unroll
+                for (int h = 0; h < 2; h++) vr[s][h] = *(vq + min(s, Sl) * 128 + h * 64);
+        } else
+#endif
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) vr[s][h] = HM_LD(vq + min(s, Sl) * 128 + h * 64);
+    }
+    float M = scn;
+#pragma unroll
+    for (int T = 0; T < 16; T++) M = fmaxf(M, fmaxf(fmaxf(sc[T][0], sc[T][1]), fmaxf(sc[T][2], sc[T][3])));
+    M = hm_rows_max(M);
+    float L = 0.f;
+#pragma unroll
+    for (int T = 0; T < 16; T++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) { sc[T][i] = __expf(sc[T][i] - M); L += sc[T][i]; }
+    L = hm_rows_sum(L);
+    float en = 0.f;
+    if (has_new) { en = __expf(scn - M); L += en; }
+    if (lq == 0 && lc < GRP)
+        *(float2*)(a.stats + ((size_t)(g * GRP + lc) * a.n_chunks + chunk) * 2) = make_float2(M, L);
+    const float rL = recip_rn(L);
+    // ---- p.V: the probabilities rounded to f16 (as the reference stores them) are the B operand as they stand
+    att_f4 acc[4];
+#pragma unroll
+    for (int et = 0; et < 4; et++) acc[et] = att_f4{0.f, 0.f, 0.f, 0.f};
+    {
+        hmf8_v4i vx[4];
+#pragma unroll
+        for (int et = 0; et < 4; et++) vx[et] = hmf8_expand8((unsigned)vr[0][et >> 1][2 * (et & 1)], (unsigned)vr[0][et >> 1][2 * (et & 1) + 1]);
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            const int u = min(s + 1, 7);
+            hmf8_v4i nx[4];
+#pragma unroll
+            for (int et = 0; et < 4; et++) nx[et] = hmf8_expand8((unsigned)vr[u][et >> 1][2 * (et & 1)], (unsigned)vr[u][et >> 1][2 * (et & 1) + 1]);
+            att_h8 bp;
+#pragma unroll
+            for (int j = 0; j < 8; j++) bp[j] = f2hv(sc[2 * s + (j >> 2)][j & 3] * rL);
+#pragma unroll
+            for (int et = 0; et < 4; et++) acc[et] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(att_h8, vx[et]), bp, acc[et], 0, 0, 0);
+#pragma unroll
+            for (int et = 0; et < 4; et++) vx[et] = nx[et];
+        }
     }
     if (has_new) {
         const float pv = (float)f2hv(en * rL);

@@ -50,7 +50,7 @@ int gten_hip_decoder_kv_shadow_info(gten_hip_decoder* dc, int* bits, int* chunk_
 {
     GTR_NEED_INIT();
     GTR_REQUIRE(dc, "decoder_kv_shadow_info: null decoder");
-    if (bits) *bits = !dc->hm ? 0 : dc->hm_q4 ? 4 : dc->d.adtype == GTEN_Q8 ? 8 : 16;
+    if (bits) *bits = !dc->hm ? 0 : dc->hm_q4 ? 4 : (dc->d.adtype == GTEN_Q8 || dc->hm_fp8) ? 8 : 16;
     if (chunk_bytes) *chunk_bytes = dc->hm ? (int)dc->hm_chunk_bytes : 0;
     if (bytes_total) *bytes_total = dc->hm ? (unsigned long long)dc->n_seq * dc->hm_seq_stride : 0ull;
     return 0;

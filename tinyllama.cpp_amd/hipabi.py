@@ -177,6 +177,8 @@ class GtenHip:
     POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HIP_POOL_*
     # include/gten_hip_kvq4.h (4-bit head-major K / V shadows of the wide decoders)
     KVQ4_SYMBOLS = ["gten_hip_set_kv_shadow_q4", "gten_hip_decoder_kv_shadow_info", "gten_hip_kv_round_q4", "gten_hip_decoder_kv_shadow_read"]
+    # include/gten_hip_kvfp8.h (FP8 head-major K / V shadows of the f16 wide decoders)
+    KVFP8_SYMBOLS = ["gten_hip_set_kv_shadow_fp8", "gten_hip_kv_round_fp8", "gten_hip_decoder_kv_shadow_read_fp8"]
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -302,6 +304,9 @@ class GtenHip:
         self._kv_shadow_info = _sig(L, "gten_hip_decoder_kv_shadow_info", ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_ulonglong)])
         self._kv_round_q4 = _sig(L, "gten_hip_kv_round_q4", ci, [vp, ci, sz, sz])
         self._kv_shadow_read = _sig(L, "gten_hip_decoder_kv_shadow_read", ci, [vp, ci, ci, ci, ci, vp])
+        self._kv_shadow_fp8 = _sig(L, "gten_hip_set_kv_shadow_fp8", ci, [ci])
+        self._kv_round_fp8 = _sig(L, "gten_hip_kv_round_fp8", ci, [vp, ci, sz, sz])
+        self._kv_shadow_read_fp8 = _sig(L, "gten_hip_decoder_kv_shadow_read_fp8", ci, [vp, ci, ci, ci, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -1001,6 +1006,18 @@ class GtenHip:
     def kv_round_q4(self, rows, n_rows, row_bytes, pitch=None):
         """the 4-bit shadows' rounding R in place on every Q8 block of a row view (a buffer or a view of one); asynchronous"""
         self._check(self.kv_round_q4_rc(rows, n_rows, row_bytes, pitch))
+
+    def set_kv_shadow_fp8(self, on):
+        """decoders created from now on keep their head-major K / V shadows as FP8 (E4M3) codes (lossy; only where an f16 shadow would
+        exist) or as they always did (default)"""
+        self._check(self._kv_shadow_fp8(1 if on else 0))
+
+    def kv_round_fp8_rc(self, rows, n_rows, row_bytes, pitch=None):
+        return self._kv_round_fp8(rows.ptr, int(n_rows), int(row_bytes), int(row_bytes if pitch is None else pitch))
+
+    def kv_round_fp8(self, rows, n_rows, row_bytes, pitch=None):
+        """the FP8 shadows' rounding R in place on every f16 element of a row view (a buffer or a view of one); asynchronous"""
+        self._check(self.kv_round_fp8_rc(rows, n_rows, row_bytes, pitch))
 
     def set_ffn_streamed(self, on):
         """gate | up of full 128-row q4 lanes as the streamed kernel (default) or as k_dec_mmvh: the same bits"""

@@ -105,6 +105,8 @@ class GtenHost:
     POOLINGS = {"mean": 0, "last": 1}                            # GTEN_HOST_POOL_*
     # include/gten_host_kvq4.h (4-bit head-major K / V shadows of a batch's shared decoder, host/capi_kvq4.cpp)
     KVQ4_SYMBOLS = ["gten_host_batch_kv_shadow_info", "gten_host_batch_kv_round_q4", "gten_host_batch_kv_shadow_read", "gten_host_batch_kv_rows"]
+    # include/gten_host_kvfp8.h (FP8 head-major K / V shadows of an f16 batch's shared decoder, host/capi_kvfp8.cpp)
+    KVFP8_SYMBOLS = ["gten_host_batch_kv_round_fp8", "gten_host_batch_kv_shadow_read_fp8"]
     SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -338,6 +340,8 @@ class GtenHost:
         self._bkv_round_q4 = _sig(L, "gten_host_batch_kv_round_q4", ci, [vp, ci, ci])
         self._bkv_shadow_read = _sig(L, "gten_host_batch_kv_shadow_read", ci, [vp, ci, ci, ci, vp, vp])
         self._bkv_rows = _sig(L, "gten_host_batch_kv_rows", ci, [vp, ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)])
+        self._bkv_round_fp8 = _sig(L, "gten_host_batch_kv_round_fp8", ci, [vp, ci, ci])
+        self._bkv_shadow_read_fp8 = _sig(L, "gten_host_batch_kv_shadow_read_fp8", ci, [vp, ci, ci, ci, vp, vp])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -2239,6 +2243,18 @@ class HostBatch:
         rb = self.kv_row_bytes()
         k, v = np.zeros((n_rows, rb), np.uint8), np.zeros((n_rows, rb), np.uint8)
         self._ck(self.host._bkv_shadow_read(self.h, int(seq), int(layer), int(n_rows), _ptr(k), _ptr(v)), "batch_kv_shadow_read")
+        return k, v
+
+    def kv_round_fp8(self, seq, n_rows):
+        """the FP8 shadows' rounding R in place on f16 cache rows [0, n_rows) of sequence seq: every layer, K and V"""
+        self._ck(self.host._bkv_round_fp8(self.h, int(seq), int(n_rows)), "batch_kv_round_fp8")
+
+    def kv_shadow_read_fp8(self, seq, layer, n_rows):
+        """(K, V) of positions [0, n_rows) of sequence seq's own FP8 shadow on `layer` as dense f16 rows, as the attention kernel
+        expands them: uint8 [n_rows][row_bytes] each (kv_read's shape)"""
+        rb = self.kv_row_bytes()
+        k, v = np.zeros((n_rows, rb), np.uint8), np.zeros((n_rows, rb), np.uint8)
+        self._ck(self.host._bkv_shadow_read_fp8(self.h, int(seq), int(layer), int(n_rows), _ptr(k), _ptr(v)), "batch_kv_shadow_read_fp8")
         return k, v
 
     def time_family(self, family, n, reps=20):
