@@ -17,6 +17,7 @@
 #include "gten_row_logprobs.h"
 #include "gten_hip_embed.h"
 #include "gten_pool_rows.h"
+#include "gten_quant.h"
 
 #include <cstdlib>
 #include <cstring>

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/gten_hip.h"
+#include "../../include/gten_hip_quant.h"
 #include "gten_types.h"
 #include "log.h"
 #include "quants.h"
@@ -138,6 +139,20 @@ struct Storage {
         if (!external) { std::free(host); host = nullptr; }
         return dev;
     }
+    // The same tensor filled from UNQUANTISED rows that already lie in HBM: rows x cols elements in a source dtype of
+    // include/gten_hip_quant.h, quantised and packed (Q8/Q4) or rounded to f16 by one launch.  Returns the library's code
+    // instead of asserting: a non-finite source is the caller's to report.
+    int dev_weight_from(const void* src_dev, int src_dtype, int dtype_code_, int rows, int cols)
+    {
+        settle_pending();
+        need_dev();
+        if (const int rc = gten_hip_quantize_weight(src_dev, src_dtype, rows, cols, dtype_code_, dev)) return rc;
+        host_newer = false;
+        if (dtype_code_ == GTEN_Q8 || dtype_code_ == GTEN_Q4) packed = true;
+        else dev_newer = true;
+        if (host && !external) { std::free(host); host = nullptr; }
+        return 0;
+    }
 };
 
 } // namespace detail
@@ -210,6 +225,13 @@ public:
             return store_->dev_weight(dtype_code(dtype_), shape_[0], shape_[1]);
         }
         return store_->dev_view(false);
+    }
+    // a weight matrix (any weight dtype) or an f16 norm vector from its unquantised elements in HBM; 0 or the library's code
+    int device_weight_from(const void* src_dev, int src_dtype)
+    {
+        GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
+        GTEN_ASSERT(is_2d() || is_1d());
+        return store_->dev_weight_from(src_dev, src_dtype, dtype_code(dtype_), is_2d() ? shape_[0] : 1, shape_.back());
     }
     bool is_host_external() const { return store_ && store_->external; }
     // identity of the storage this handle aliases (shallow copies share it, gten/tensor.h:24-29)

@@ -179,6 +179,9 @@ class GtenHip:
     KVQ4_SYMBOLS = ["gten_hip_set_kv_shadow_q4", "gten_hip_decoder_kv_shadow_info", "gten_hip_kv_round_q4", "gten_hip_decoder_kv_shadow_read"]
     # include/gten_hip_kvfp8.h (FP8 head-major K / V shadows of the f16 wide decoders)
     KVFP8_SYMBOLS = ["gten_hip_set_kv_shadow_fp8", "gten_hip_kv_round_fp8", "gten_hip_decoder_kv_shadow_read_fp8"]
+    # include/gten_hip_quant.h (weights quantised and packed on the device from f32 / bf16 / f16 rows)
+    QUANT_SYMBOLS = ["gten_hip_quantize_weight", "gten_hip_quant_src_bytes"]
+    SRC_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}                # GTEN_HIP_SRC_*
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -307,6 +310,8 @@ class GtenHip:
         self._kv_shadow_fp8 = _sig(L, "gten_hip_set_kv_shadow_fp8", ci, [ci])
         self._kv_round_fp8 = _sig(L, "gten_hip_kv_round_fp8", ci, [vp, ci, sz, sz])
         self._kv_shadow_read_fp8 = _sig(L, "gten_hip_decoder_kv_shadow_read_fp8", ci, [vp, ci, ci, ci, ci, vp])
+        self._quantize = _sig(L, "gten_hip_quantize_weight", ci, [vp, ci, ci, ci, ci, vp])
+        self._quant_src_bytes = _sig(L, "gten_hip_quant_src_bytes", sz, [ci, ci, ci])
         self.initialised = False
 
     # -- runtime
@@ -1160,6 +1165,29 @@ class GtenHip:
         self._check(self._pack(src.ptr, dtype, rows, cols, dst.ptr))
         self.sync()
         src.free()
+        return dst
+
+    def quant_src_bytes(self, src, rows, cols):
+        return self._quant_src_bytes(self.SRC_DTYPES[src], rows, cols)
+
+    def quantize_weight_rc(self, src_buf, src, rows, cols, dtype, dst):
+        return self._quantize(src_buf.ptr, self.SRC_DTYPES[src], rows, cols, dtype, dst.ptr)
+
+    def quantize_weight(self, elements, src, dtype, rows, cols):
+        """dense [rows][cols] elements in the source dtype `src` ("f32": float32, "f16": float16, "bf16": the raw uint16 words)
+        -> device weight in `dtype`, quantised and packed on the device (include/gten_hip_quant.h): the bytes of
+        upload_weight(convert.quantize(w, dtype, src))"""
+        want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}[src]
+        elements = np.ascontiguousarray(elements)
+        assert elements.dtype == want and elements.size == rows * cols, (elements.dtype, elements.shape)
+        src_buf = self.upload(elements)
+        dst = self.alloc(rows * self.row_bytes(dtype, cols))
+        rc = self.quantize_weight_rc(src_buf, src, rows, cols, dtype, dst)
+        said = self.last_error() if rc else ""
+        src_buf.free()
+        if rc:
+            dst.free()
+            raise GtenHipError(f"gten_hip error {rc}: {said}")
         return dst
 
     # -- operators (DeviceBuffers or views of them; pitches default to dense rows).  The `_rc` forms return the code of the

@@ -6,6 +6,7 @@
 #include "../../include/gten_host.h"
 #include "fsm_build.h"
 #include "generate.h"
+#include "quant_load.h"
 #include "shift_plan.h"
 #include "tokenizer.h"
 
@@ -13,6 +14,7 @@ struct gten_host_model {
     gten_host_config cfg;
     std::unique_ptr<gten::TinyLlama> model;
     gten::ShiftCounts shifts;            // include/gten_host_shift.h
+    gten::QuantLoader quant;             // include/gten_host_quant.h: the staging buffer of set_weight_from
 };
 
 struct gten_host_batch {

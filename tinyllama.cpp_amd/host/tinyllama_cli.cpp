@@ -33,6 +33,7 @@
 #include "json_schema.h"
 #include "generate.h"
 #include "generate_shift.h"
+#include "quant_load.h"
 #include "tokenizer.h"
 
 using namespace gten;
@@ -51,6 +52,7 @@ Optional args.
 --npred  N : Number of tokens to generate. Minimum is 1 and max is 2048. [default=768].
 --topk K : Top tokens to randomly select from during prediction. [default=50].
 --model PATH :     .gten checkpoint [default=models/tinyllama.<fp16|q8|q4>.gten].
+--from-f16 :       the --model file is the f16 checkpoint: quantise it on the device to the mode given by -q8 / -q4. Not with -f16.
 --tokenizer PATH : vocabulary file [default=tokenizer.bin].
 --seed S : seed of the top-k sampler [default: random].
 --ids :    print token ids instead of text (with --score: one `id logprob rank` line per scored id).
@@ -109,6 +111,7 @@ struct Options {
     int n_predict = 768, topk = 50, ctx = 2048;
     float temp = 0.9f;
     bool greedy = false, ids = false, seeded = false;
+    bool from_f16 = false;                   // --from-f16: the model file is f16, quantised on the device (host/quant_load.h)
     uint64_t seed = 0;
     std::vector<int32_t> ban, allow;         // --ban / --allow (bias table 0)
     int min_new = 0;
@@ -402,6 +405,7 @@ int main(int argc, char const* argv[])
         else if (arg == "--ids") o.ids = true;
         else if (arg == "-p") o.prompt = value("prompt");
         else if (arg == "--model") o.model_path = value("model");
+        else if (arg == "--from-f16") o.from_f16 = true;
         else if (arg == "--tokenizer") o.tokenizer_path = value("tokenizer");
         else if (arg == "--score") o.score_path = value("score");
         else if (arg == "--embed") o.embed_path = value("embed");
@@ -619,7 +623,8 @@ int main(int argc, char const* argv[])
         std::cerr << "--ban bans every id of --allow.\n";
         return -1;
     }
-    if (o.model_path.empty()) o.model_path = "models/tinyllama." + model_id + ".gten";
+    if (o.from_f16 && o.model_dtype == kFloat16) { std::cerr << "--from-f16 quantises an f16 file to -q8 or -q4: not with -f16.\n"; return -1; }
+    if (o.model_path.empty()) o.model_path = "models/tinyllama." + (o.from_f16 ? std::string("fp16") : model_id) + ".gten";
 
     std::ifstream checkpoint{o.model_path, std::ios::binary};
     if (!checkpoint.is_open()) {
@@ -635,7 +640,8 @@ int main(int argc, char const* argv[])
     dtype.adtype = (o.model_dtype == kFloat16) ? kFloat16 : kQint8;          // tinyllama.cpp:258-265
 
     TinyLlama model{o.score_path.empty() && o.embed_path.empty() && !o.shifting() ? o.n_predict : o.ctx, dtype};
-    model.load_from_ckpt(checkpoint);
+    if (o.from_f16) QuantLoader{}.load_gten_f16(model, checkpoint);
+    else model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
     if (!o.score_path.empty()) return run_score(o, model, tokenizer);
     if (!o.embed_path.empty()) return run_embed(o, model, tokenizer);

@@ -107,6 +107,9 @@ class GtenHost:
     KVQ4_SYMBOLS = ["gten_host_batch_kv_shadow_info", "gten_host_batch_kv_round_q4", "gten_host_batch_kv_shadow_read", "gten_host_batch_kv_rows"]
     # include/gten_host_kvfp8.h (FP8 head-major K / V shadows of an f16 batch's shared decoder, host/capi_kvfp8.cpp)
     KVFP8_SYMBOLS = ["gten_host_batch_kv_round_fp8", "gten_host_batch_kv_shadow_read_fp8"]
+    # include/gten_host_quant.h (a model's weights from unquantised elements, quantised on the device; host/capi_quant.cpp)
+    QUANT_SYMBOLS = ["gten_host_model_set_weight_from", "gten_host_model_quant_release", "gten_host_model_load_gten_f16",
+                     "gten_host_model_weight_read"]
     SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -342,6 +345,10 @@ class GtenHost:
         self._bkv_rows = _sig(L, "gten_host_batch_kv_rows", ci, [vp, ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)])
         self._bkv_round_fp8 = _sig(L, "gten_host_batch_kv_round_fp8", ci, [vp, ci, ci])
         self._bkv_shadow_read_fp8 = _sig(L, "gten_host_batch_kv_shadow_read_fp8", ci, [vp, ci, ci, ci, vp, vp])
+        self._setw_from = _sig(L, "gten_host_model_set_weight_from", ci, [vp, ci, vp, sz, ci])
+        self._quant_release = _sig(L, "gten_host_model_quant_release", ci, [vp])
+        self._loadg_f16 = _sig(L, "gten_host_model_load_gten_f16", ci, [vp, C.c_char_p])
+        self._wread = _sig(L, "gten_host_model_weight_read", ci, [vp, ci, vp, sz])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -925,6 +932,51 @@ class HostModel:
         rc = self.host._loads(self.h, seed)
         if rc:
             raise GtenHipError(f"load_synthetic rc={rc}")
+
+    # -- include/gten_host_quant.h: weights from unquantised elements, quantised on the device
+    def set_weight_from(self, idx, elements, src):
+        """weight idx from its dense elements in the source dtype `src` ("f32": float32, "f16": float16, "bf16": raw uint16
+        words); the model's weight dtype decides what they become.  The staging buffer stays until quant_release()"""
+        want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}[src]
+        elements = np.ascontiguousarray(elements)
+        if elements.dtype != want:
+            raise GtenHipError(f"set_weight_from({idx}): {elements.dtype} elements for source dtype {src}")
+        rc = self.host._setw_from(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src])
+        if rc:
+            raise GtenHipError(f"set_weight_from({idx}) rc={rc}: {self.host.hip.last_error()}")
+
+    def quant_release(self):
+        self.host._quant_release(self.h)
+
+    def load_gten_f16(self, path):
+        """an f16 .gten file into this model, whatever its weight dtype (Q8 / Q4: quantised on the device)"""
+        rc = self.host._loadg_f16(self.h, path.encode())
+        if rc:
+            raise GtenHipError(f"load_gten_f16({path}) rc={rc}")
+
+    def load_checkpoint(self, src):
+        """a Hugging Face checkpoint (one .safetensors file or a directory of shards, convert.open_checkpoint) straight into
+        this model: every tensor goes up in the checkpoint's own dtype and is quantised on the device"""
+        from . import convert
+        get, n_layers = convert.open_checkpoint(src)
+        if n_layers != self.cfg.n_layers:
+            raise GtenHipError(f"load_checkpoint({src}): {n_layers} layers, the model has {self.cfg.n_layers}")
+        for idx, (name, _) in enumerate(convert.tensor_names(n_layers)):
+            w, dt = get(name)
+            if dt == "f16":
+                w = w.astype(np.float16)                                  # (exact: the values came from f16)
+            elif dt == "bf16":
+                w = (np.ascontiguousarray(w).view(np.uint32) >> 16).astype(np.uint16)
+            self.set_weight_from(idx, w, dt)
+        self.quant_release()
+
+    def weight_read(self, idx):
+        """the bytes weight idx holds in HBM (Q8 / Q4: the packed layout)"""
+        out = np.zeros(self.weight_bytes(idx), np.uint8)
+        rc = self.host._wread(self.h, idx, _ptr(out), out.size)
+        if rc:
+            raise GtenHipError(f"weight_read({idx}) rc={rc}")
+        return out
 
     def logits(self, tokens, start_pos, want=True):
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
