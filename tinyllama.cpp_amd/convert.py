@@ -165,6 +165,62 @@ def open_checkpoint(src):
     return get, n_layers
 
 
+LORA_MAX_RANK = 64          # GTEN_HIP_LORA_MAX_RANK (include/gten_hip_lora.h)
+
+
+def open_lora(path, n_layers=None):
+    """A PEFT LoRA adapter (a directory with adapter_model.safetensors + adapter_config.json, or the .safetensors file beside
+    its config) -> ({hf weight name: (A [r][cols], B [rows][r])}, scale) for HostModel.load_checkpoint.  A and B keep the file's
+    dtype: float32, float16, or bf16 as raw uint16 words.  scale = lora_alpha / r, or / sqrt(r) with use_rslora.  Device-free.
+    What the merge on the device (include/gten_hip_lora.h) cannot honour is refused by name."""
+    import json
+    from safetensors import safe_open
+    d = path if os.path.isdir(path) else os.path.dirname(os.path.abspath(path))
+    file = os.path.join(d, "adapter_model.safetensors") if os.path.isdir(path) else path
+    with open(os.path.join(d, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    r, alpha = int(cfg["r"]), float(cfg.get("lora_alpha", cfg["r"]))
+    refusals = [(cfg.get("use_dora"), "DoRA (use_dora)"), (cfg.get("bias", "none") != "none", f"bias terms (bias = {cfg.get('bias')!r})"),
+                (cfg.get("modules_to_save"), f"modules_to_save {cfg.get('modules_to_save')}"),
+                (cfg.get("rank_pattern") or cfg.get("alpha_pattern"), "a rank_pattern / alpha_pattern (one rank and scale per adapter)"),
+                (not 1 <= r <= LORA_MAX_RANK, f"rank {r} outside 1..{LORA_MAX_RANK}")]
+    for hit, what in refusals:
+        if hit:
+            raise ValueError(f"{path}: the adapter has {what}, which cannot be merged on the device")
+    scale = alpha / (r ** 0.5 if cfg.get("use_rslora") else r)
+    linear = None if n_layers is None else {n for n, lin in tensor_names(n_layers)[1:-1] if lin}
+    parts = {}
+    with safe_open(file, framework="np") as h_np:
+        pt = None
+        for key in h_np.keys():
+            if "lora_embedding_" in key:
+                raise ValueError(f"{path}: {key} is an embedding adapter, which cannot be merged on the device")
+            if "lora_magnitude_vector" in key:
+                raise ValueError(f"{path}: {key} is a DoRA magnitude, which cannot be merged on the device")
+            head, _, tail = key.partition(".lora_")
+            if not key.startswith("base_model.model.") or tail not in ("A.weight", "B.weight"):
+                raise ValueError(f"{path}: {key} is not a lora_A / lora_B weight of a linear layer")
+            name = head[len("base_model.model."):] + ".weight"
+            if "embed_tokens" in name or name.startswith("lm_head") or (linear is not None and name not in linear):
+                raise ValueError(f"{path}: {key} adapts {name}, which takes no adapter (only q, k, v, o, gate, up, down of a block)")
+            dt = h_np.get_slice(key).get_dtype()
+            if dt in ("F32", "F16"):
+                m = np.ascontiguousarray(h_np.get_tensor(key))
+            elif dt == "BF16":
+                import torch                   # numpy has no bf16: the raw words through torch
+                pt = pt or safe_open(file, framework="pt")
+                m = pt.get_tensor(key).contiguous().view(torch.int16).numpy().view(np.uint16)
+            else:
+                raise ValueError(f"{path}: {key} has dtype {dt} (f32, f16 or bf16)")
+            parts.setdefault(name, {})[tail[0]] = m
+    out = {}
+    for name, p in parts.items():
+        if set(p) != {"A", "B"} or p["A"].dtype != p["B"].dtype or p["A"].shape[0] != r or p["B"].shape[1] != r:
+            raise ValueError(f"{path}: {name} needs lora_A [{r}][cols] and lora_B [rows][{r}] of one dtype")
+        out[name] = (p["A"], p["B"])
+    return out, scale
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])

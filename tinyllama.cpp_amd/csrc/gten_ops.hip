@@ -18,6 +18,7 @@
 #include "gten_hip_embed.h"
 #include "gten_pool_rows.h"
 #include "gten_quant.h"
+#include "gten_quant_lora.h"
 
 #include <cstdlib>
 #include <cstring>

@@ -30,6 +30,7 @@
 
 #include "../../include/gten_hip.h"
 #include "../../include/gten_hip_quant.h"
+#include "../../include/gten_hip_lora.h"
 #include "gten_types.h"
 #include "log.h"
 #include "quants.h"
@@ -147,6 +148,19 @@ struct Storage {
         settle_pending();
         need_dev();
         if (const int rc = gten_hip_quantize_weight(src_dev, src_dtype, rows, cols, dtype_code_, dev)) return rc;
+        return dev_weight_filled(dtype_code_);
+    }
+    // ... with a LoRA adapter merged in on the way (include/gten_hip_lora.h): a [rank][cols], b [rows][rank] in ab_dtype, in HBM
+    int dev_weight_from(const void* src_dev, int src_dtype, const void* a_dev, const void* b_dev, int rank, int ab_dtype, float scale,
+                        int dtype_code_, int rows, int cols)
+    {
+        settle_pending();
+        need_dev();
+        if (const int rc = gten_hip_quantize_weight_lora(src_dev, src_dtype, rows, cols, a_dev, b_dev, rank, ab_dtype, scale, dtype_code_, dev)) return rc;
+        return dev_weight_filled(dtype_code_);
+    }
+    int dev_weight_filled(int dtype_code_)
+    {
         host_newer = false;
         if (dtype_code_ == GTEN_Q8 || dtype_code_ == GTEN_Q4) packed = true;
         else dev_newer = true;
@@ -232,6 +246,13 @@ public:
         GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
         GTEN_ASSERT(is_2d() || is_1d());
         return store_->dev_weight_from(src_dev, src_dtype, dtype_code(dtype_), is_2d() ? shape_[0] : 1, shape_.back());
+    }
+    // the merged form: W + scale * B . A of a LoRA adapter whose matrices lie in HBM (a [rank][cols], b [rows][rank]); matrices only
+    int device_weight_from(const void* src_dev, int src_dtype, const void* a_dev, const void* b_dev, int rank, int ab_dtype, float scale)
+    {
+        GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
+        GTEN_ASSERT(is_2d());
+        return store_->dev_weight_from(src_dev, src_dtype, a_dev, b_dev, rank, ab_dtype, scale, dtype_code(dtype_), shape_[0], shape_[1]);
     }
     bool is_host_external() const { return store_ && store_->external; }
     // identity of the storage this handle aliases (shallow copies share it, gten/tensor.h:24-29)

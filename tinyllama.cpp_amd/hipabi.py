@@ -182,6 +182,9 @@ class GtenHip:
     # include/gten_hip_quant.h (weights quantised and packed on the device from f32 / bf16 / f16 rows)
     QUANT_SYMBOLS = ["gten_hip_quantize_weight", "gten_hip_quant_src_bytes"]
     SRC_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}                # GTEN_HIP_SRC_*
+    # include/gten_hip_lora.h (a LoRA adapter merged into a weight while it is quantised on the device)
+    LORA_SYMBOLS = ["gten_hip_quantize_weight_lora"]
+    LORA_MAX_RANK = 64                                          # GTEN_HIP_LORA_MAX_RANK
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -312,6 +315,7 @@ class GtenHip:
         self._kv_shadow_read_fp8 = _sig(L, "gten_hip_decoder_kv_shadow_read_fp8", ci, [vp, ci, ci, ci, ci, vp])
         self._quantize = _sig(L, "gten_hip_quantize_weight", ci, [vp, ci, ci, ci, ci, vp])
         self._quant_src_bytes = _sig(L, "gten_hip_quant_src_bytes", sz, [ci, ci, ci])
+        self._quantize_lora = _sig(L, "gten_hip_quantize_weight_lora", ci, [vp, ci, ci, ci, vp, vp, ci, ci, C.c_float, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -1185,6 +1189,29 @@ class GtenHip:
         rc = self.quantize_weight_rc(src_buf, src, rows, cols, dtype, dst)
         said = self.last_error() if rc else ""
         src_buf.free()
+        if rc:
+            dst.free()
+            raise GtenHipError(f"gten_hip error {rc}: {said}")
+        return dst
+
+    def quantize_weight_lora_rc(self, src_buf, src, rows, cols, a_buf, b_buf, rank, ab, scale, dtype, dst):
+        return self._quantize_lora(src_buf.ptr, self.SRC_DTYPES[src], rows, cols, a_buf.ptr, b_buf.ptr, rank, self.SRC_DTYPES[ab], float(scale), dtype, dst.ptr)
+
+    def quantize_weight_lora(self, elements, src, a, b, ab, scale, dtype, rows, cols):
+        """quantize_weight with a LoRA adapter merged in on the device (include/gten_hip_lora.h): a [rank][cols], b [rows][rank]
+        in the dtype `ab` (arrays as quantize_weight takes them), m = round_to_src(w + scale * (b @ a)) summed in ascending k
+        -> the bytes of upload_weight(convert.quantize(m, dtype, src))"""
+        want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}
+        elements, a, b = (np.ascontiguousarray(v) for v in (elements, a, b))
+        rank = a.shape[0]
+        assert elements.dtype == want[src] and elements.size == rows * cols, (elements.dtype, elements.shape)
+        assert a.dtype == want[ab] and b.dtype == want[ab] and a.shape == (rank, cols) and b.shape == (rows, rank), (a.dtype, a.shape, b.shape)
+        bufs = [self.upload(v) if v.size else self.alloc(16) for v in (elements, a, b)]       # (rank 0: nothing to upload, the call refuses)
+        dst = self.alloc(rows * self.row_bytes(dtype, cols))
+        rc = self.quantize_weight_lora_rc(bufs[0], src, rows, cols, bufs[1], bufs[2], rank, ab, scale, dtype, dst)
+        said = self.last_error() if rc else ""
+        for buf in bufs:
+            buf.free()
         if rc:
             dst.free()
             raise GtenHipError(f"gten_hip error {rc}: {said}")

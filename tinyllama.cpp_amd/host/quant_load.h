@@ -1,13 +1,15 @@
 // quant_load.h -- weights from UNQUANTISED bytes (include/gten_host_quant.h): a tensor's elements go up in the dtype they
 // have (f32 / bf16 / f16) into one staging buffer in HBM, grown on demand, and gten_hip_quantize_weight writes the model's
 // weight tensor from there -- Q8 / Q4 quantised and packed, f16 rounded; norm vectors (always f16) take the same way.
-// The one host header that names include/gten_hip_quant.h beside gten/tensor.h.
+// set_weight_from_lora merges a LoRA adapter on the way (include/gten_hip_lora.h).
+// The one host header that names include/gten_hip_quant.h and include/gten_hip_lora.h beside gten/tensor.h.
 #pragma once
 
 #include <fstream>
 #include <string>
 #include <vector>
 
+#include "../../include/gten_hip_lora.h"
 #include "../../include/gten_hip_quant.h"
 #include "tinyllama_model.h"
 
@@ -35,15 +37,44 @@ public:
         const size_t need = src_bytes(model, idx, src_dtype);
         if (!need || !bytes) return -1;
         if (nbytes != need) return -2;
-        if (need > cap_) {
-            release();
-            detail::ensure_runtime();
-            if (const int rc = gten_hip_malloc(&stage_, need)) return rc;
-            cap_ = need;
-        }
-        if (const int rc = gten_hip_memcpy_h2d(stage_, bytes, nbytes)) return rc;
+        if (const int rc = stage_source(bytes, nbytes)) return rc;
         return model.weight(idx).device_weight_from(stage_, src_dtype);
     }
+
+    // The same with a LoRA adapter merged in on the device (include/gten_host_lora.h): a [rank][cols] and b [rows][rank] in
+    // ab_dtype go up beside the source, into a second buffer of their own.  Only the seven linear weights of a block take
+    // one: -3 for embed_tokens, lm_head and the norm vectors (lora_error() names which); -1 also for a bad rank or ab_dtype.
+    int set_weight_from_lora(TinyLlama& model, int idx, const void* bytes, size_t nbytes, int src_dtype, const void* a, const void* b,
+                             int rank, int ab_dtype, float scale)
+    {
+        const size_t need = src_bytes(model, idx, src_dtype);
+        if (!need || !bytes || !a || !b || rank < 1 || rank > GTEN_HIP_LORA_MAX_RANK) return -1;
+        if (nbytes != need) return -2;
+        const int last = model.n_weights() - 1;
+        if (idx == 0 || idx >= last - 1 || (idx - 1) % 9 >= 7) {
+            lora_error_ = std::string("set_weight_from_lora: weight ") + std::to_string(idx) + " is " +
+                          (idx == 0 ? "embed_tokens" : idx == last ? "lm_head" : "a norm vector") +
+                          ": only q, k, v, o, gate, up and down of a block take an adapter";
+            return -3;
+        }
+        const Tensor& w = model.weight(idx);
+        const size_t a_bytes = gten_hip_quant_src_bytes(ab_dtype, rank, w.dimsize(1)), b_bytes = gten_hip_quant_src_bytes(ab_dtype, w.dimsize(0), rank);
+        if (!a_bytes || !b_bytes) return -1;
+        const size_t b_at = (a_bytes + 15) & ~(size_t)15;            // B starts 16-byte aligned behind A
+        if (b_at + b_bytes > ab_cap_) {
+            if (ab_) gten_hip_free(ab_);
+            ab_ = nullptr;
+            ab_cap_ = 0;
+            detail::ensure_runtime();
+            if (const int rc = gten_hip_malloc(&ab_, b_at + b_bytes)) return rc;
+            ab_cap_ = b_at + b_bytes;
+        }
+        if (const int rc = stage_source(bytes, nbytes)) return rc;
+        if (const int rc = gten_hip_memcpy_h2d(ab_, a, a_bytes)) return rc;
+        if (const int rc = gten_hip_memcpy_h2d((char*)ab_ + b_at, b, b_bytes)) return rc;
+        return model.weight(idx).device_weight_from(stage_, src_dtype, ab_, (const char*)ab_ + b_at, rank, ab_dtype, scale);
+    }
+    const char* lora_error() const { return lora_error_.c_str(); }
 
     // An f16 .gten file into a model of ANY weight dtype: TinyLlama::load_from_ckpt's framing and messages, each payload
     // checked against the tensor's f16 size and handed to set_weight_from.  An f16 model reads the file as it always did.
@@ -84,11 +115,29 @@ public:
     void release()
     {
         if (stage_) gten_hip_free(stage_);
-        stage_ = nullptr;
-        cap_ = 0;
+        if (ab_) gten_hip_free(ab_);
+        stage_ = ab_ = nullptr;
+        cap_ = ab_cap_ = 0;
     }
 
 private:
+    // the source bytes into the staging buffer, grown on demand
+    int stage_source(const void* bytes, size_t nbytes)
+    {
+        if (nbytes > cap_) {
+            if (stage_) gten_hip_free(stage_);
+            stage_ = nullptr;
+            cap_ = 0;
+            detail::ensure_runtime();
+            if (const int rc = gten_hip_malloc(&stage_, nbytes)) return rc;
+            cap_ = nbytes;
+        }
+        return gten_hip_memcpy_h2d(stage_, bytes, nbytes);
+    }
+
+    void* ab_ = nullptr;        // HBM, one adapter's A, then B from the next 16-byte boundary
+    size_t ab_cap_ = 0;
+    std::string lora_error_;
     void* stage_ = nullptr;     // HBM, source-dtype bytes of one tensor
     size_t cap_ = 0;
 };

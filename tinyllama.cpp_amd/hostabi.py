@@ -110,6 +110,8 @@ class GtenHost:
     # include/gten_host_quant.h (a model's weights from unquantised elements, quantised on the device; host/capi_quant.cpp)
     QUANT_SYMBOLS = ["gten_host_model_set_weight_from", "gten_host_model_quant_release", "gten_host_model_load_gten_f16",
                      "gten_host_model_weight_read"]
+    # include/gten_host_lora.h (a LoRA adapter merged into a linear weight while it is quantised on the device; host/capi_lora.cpp)
+    LORA_SYMBOLS = ["gten_host_model_set_weight_from_lora", "gten_host_lora_error"]
     SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -349,6 +351,8 @@ class GtenHost:
         self._quant_release = _sig(L, "gten_host_model_quant_release", ci, [vp])
         self._loadg_f16 = _sig(L, "gten_host_model_load_gten_f16", ci, [vp, C.c_char_p])
         self._wread = _sig(L, "gten_host_model_weight_read", ci, [vp, ci, vp, sz])
+        self._setw_from_lora = _sig(L, "gten_host_model_set_weight_from_lora", ci, [vp, ci, vp, sz, ci, vp, vp, ci, ci, C.c_float])
+        self._lora_error = _sig(L, "gten_host_lora_error", C.c_char_p, [vp])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -934,16 +938,32 @@ class HostModel:
             raise GtenHipError(f"load_synthetic rc={rc}")
 
     # -- include/gten_host_quant.h: weights from unquantised elements, quantised on the device
-    def set_weight_from(self, idx, elements, src):
+    def set_weight_from(self, idx, elements, src, lora=None):
         """weight idx from its dense elements in the source dtype `src` ("f32": float32, "f16": float16, "bf16": raw uint16
-        words); the model's weight dtype decides what they become.  The staging buffer stays until quant_release()"""
+        words); the model's weight dtype decides what they become.  The staging buffer stays until quant_release().
+        lora = (A, B, scale): a LoRA adapter merged in on the device (include/gten_host_lora.h) -- A [rank][cols] and
+        B [rows][rank], both float32, float16 or raw bf16 words (uint16), only for q, k, v, o, gate, up, down of a block"""
         want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}[src]
         elements = np.ascontiguousarray(elements)
         if elements.dtype != want:
             raise GtenHipError(f"set_weight_from({idx}): {elements.dtype} elements for source dtype {src}")
-        rc = self.host._setw_from(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src])
+        if lora is None:
+            rc = self.host._setw_from(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src])
+            if rc:
+                raise GtenHipError(f"set_weight_from({idx}) rc={rc}: {self.host.hip.last_error()}")
+            return
+        a, b, scale = lora
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        ab = {np.dtype(np.float32): "f32", np.dtype(np.uint16): "bf16", np.dtype(np.float16): "f16"}.get(a.dtype)
+        if ab is None or b.dtype != a.dtype or a.ndim != 2 or b.ndim != 2 or b.shape[1] != a.shape[0] or a.size + b.size == 0:
+            raise GtenHipError(f"set_weight_from({idx}): adapter A {a.dtype}{a.shape}, B {b.dtype}{b.shape}")
+        if a.shape[1] * b.shape[0] != elements.size:
+            raise GtenHipError(f"set_weight_from({idx}): adapter for {b.shape[0]} x {a.shape[1]}, {elements.size} elements")
+        rc = self.host._setw_from_lora(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src],
+                                       a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), a.shape[0], self.host.hip.SRC_DTYPES[ab], float(scale))
         if rc:
-            raise GtenHipError(f"set_weight_from({idx}) rc={rc}: {self.host.hip.last_error()}")
+            said = self.host._lora_error(self.h).decode() if rc == -3 else self.host.hip.last_error()
+            raise GtenHipError(f"set_weight_from({idx}, lora) rc={rc}: {said}")
 
     def quant_release(self):
         self.host._quant_release(self.h)
@@ -954,20 +974,27 @@ class HostModel:
         if rc:
             raise GtenHipError(f"load_gten_f16({path}) rc={rc}")
 
-    def load_checkpoint(self, src):
+    def load_checkpoint(self, src, lora=None):
         """a Hugging Face checkpoint (one .safetensors file or a directory of shards, convert.open_checkpoint) straight into
-        this model: every tensor goes up in the checkpoint's own dtype and is quantised on the device"""
+        this model: every tensor goes up in the checkpoint's own dtype and is quantised on the device.
+        lora: a PEFT adapter directory or adapter_model.safetensors file (convert.open_lora), or a pair
+        ({hf weight name: (A, B)}, scale): merged into the linear weights it names on the way (set_weight_from)"""
         from . import convert
         get, n_layers = convert.open_checkpoint(src)
         if n_layers != self.cfg.n_layers:
             raise GtenHipError(f"load_checkpoint({src}): {n_layers} layers, the model has {self.cfg.n_layers}")
-        for idx, (name, _) in enumerate(convert.tensor_names(n_layers)):
+        adapters, scale = ({}, 0.0) if lora is None else convert.open_lora(lora, n_layers) if isinstance(lora, (str, os.PathLike)) else lora
+        names = [name for name, _ in convert.tensor_names(n_layers)]
+        unknown = sorted(set(adapters) - set(names))
+        if unknown:
+            raise GtenHipError(f"load_checkpoint({src}): the adapter names {unknown[0]}, which the model does not have")
+        for idx, name in enumerate(names):
             w, dt = get(name)
             if dt == "f16":
                 w = w.astype(np.float16)                                  # (exact: the values came from f16)
             elif dt == "bf16":
                 w = (np.ascontiguousarray(w).view(np.uint32) >> 16).astype(np.uint16)
-            self.set_weight_from(idx, w, dt)
+            self.set_weight_from(idx, w, dt, lora=(*adapters[name], scale) if name in adapters else None)
         self.quant_release()
 
     def weight_read(self, idx):
