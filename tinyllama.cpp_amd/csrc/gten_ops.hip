@@ -19,6 +19,8 @@
 #include "gten_pool_rows.h"
 #include "gten_quant.h"
 #include "gten_quant_lora.h"
+#include "gten_quant_search.h"
+#include "gten_col_energy.h"
 
 #include <cstdlib>
 #include <cstring>

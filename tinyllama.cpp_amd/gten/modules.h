@@ -131,6 +131,19 @@ inline ContinuedRows& continued_rows()
     return c;
 }
 
+// Rows that a calibration collects (include/gten_host_calib.h).  While `call` is set, AttentionBlock::forward hands
+// every block whose rows it has just computed (not the recorded single-row chain: decoder steps do not collect) to it.  `call`
+// is installed by the translation unit that links the device entry point (host/capi_calib.cpp), as with PrefixedRows.
+struct CalibRows {
+    void (*call)(void* owner, const AttentionBlock& block, int start_pos) = nullptr;
+    void* owner = nullptr;
+};
+inline CalibRows& calib_rows()
+{
+    static CalibRows c;
+    return c;
+}
+
 inline bool& fused_rows_enabled()
 {
     static bool on = [] { const char* e = std::getenv("GTEN_HIP_FAST_DECODE"); return !(e && e[0] == '0'); }();
@@ -520,7 +533,9 @@ public:
             return attn_res.acv;
         }
         detail::settle_pending();
-        return forward_now(inp, start_pos);
+        Tensor out = forward_now(inp, start_pos);
+        if (const detail::CalibRows& cr = detail::calib_rows(); cr.call) cr.call(cr.owner, *this, start_pos);
+        return out;
     }
 
 private:

@@ -31,6 +31,7 @@
 #include "../../include/gten_hip.h"
 #include "../../include/gten_hip_quant.h"
 #include "../../include/gten_hip_lora.h"
+#include "../../include/gten_hip_calib.h"
 #include "gten_types.h"
 #include "log.h"
 #include "quants.h"
@@ -159,6 +160,14 @@ struct Storage {
         if (const int rc = gten_hip_quantize_weight_lora(src_dev, src_dtype, rows, cols, a_dev, b_dev, rank, ab_dtype, scale, dtype_code_, dev)) return rc;
         return dev_weight_filled(dtype_code_);
     }
+    // ... as Q4 through the delta search (include/gten_hip_calib.h): importance f32 [cols] in HBM, or null
+    int dev_weight_search(const void* src_dev, int src_dtype, const float* importance_dev, int rows, int cols)
+    {
+        settle_pending();
+        need_dev();
+        if (const int rc = gten_hip_quantize_weight_search(src_dev, src_dtype, rows, cols, importance_dev, dev)) return rc;
+        return dev_weight_filled(GTEN_Q4);
+    }
     int dev_weight_filled(int dtype_code_)
     {
         host_newer = false;
@@ -253,6 +262,13 @@ public:
         GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
         GTEN_ASSERT(is_2d());
         return store_->dev_weight_from(src_dev, src_dtype, a_dev, b_dev, rank, ab_dtype, scale, dtype_code(dtype_), shape_[0], shape_[1]);
+    }
+    // the searched form: a Q4 matrix whose deltas and quants are chosen by importance-weighted error (importance f32 [cols] in HBM)
+    int device_weight_search(const void* src_dev, int src_dtype, const float* importance_dev)
+    {
+        GTEN_ASSERT(dtype_ == kQint4);
+        GTEN_ASSERT(is_2d());
+        return store_->dev_weight_search(src_dev, src_dtype, importance_dev, shape_[0], shape_[1]);
     }
     bool is_host_external() const { return store_ && store_->external; }
     // identity of the storage this handle aliases (shallow copies share it, gten/tensor.h:24-29)

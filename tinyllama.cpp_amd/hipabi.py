@@ -185,6 +185,8 @@ class GtenHip:
     # include/gten_hip_lora.h (a LoRA adapter merged into a weight while it is quantised on the device)
     LORA_SYMBOLS = ["gten_hip_quantize_weight_lora"]
     LORA_MAX_RANK = 64                                          # GTEN_HIP_LORA_MAX_RANK
+    # include/gten_hip_calib.h (column energies of activation rows; Q4 through an importance-weighted delta search)
+    CALIB_SYMBOLS = ["gten_hip_quantize_weight_search", "gten_hip_calib_col_energy"]
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
 
@@ -316,6 +318,8 @@ class GtenHip:
         self._quantize = _sig(L, "gten_hip_quantize_weight", ci, [vp, ci, ci, ci, ci, vp])
         self._quant_src_bytes = _sig(L, "gten_hip_quant_src_bytes", sz, [ci, ci, ci])
         self._quantize_lora = _sig(L, "gten_hip_quantize_weight_lora", ci, [vp, ci, ci, ci, vp, vp, ci, ci, C.c_float, ci, vp])
+        self._quantize_search = _sig(L, "gten_hip_quantize_weight_search", ci, [vp, ci, ci, ci, vp, vp])
+        self._col_energy = _sig(L, "gten_hip_calib_col_energy", ci, [vp, ci, ci, ci, C.c_longlong, vp])
         self.initialised = False
 
     # -- runtime
@@ -1216,6 +1220,38 @@ class GtenHip:
             dst.free()
             raise GtenHipError(f"gten_hip error {rc}: {said}")
         return dst
+
+    def quantize_weight_search_rc(self, src_buf, src, rows, cols, importance_buf, dst):
+        return self._quantize_search(src_buf.ptr, self.SRC_DTYPES[src], rows, cols, importance_buf.ptr if importance_buf is not None else None, dst.ptr)
+
+    def quantize_weight_search(self, elements, src, rows, cols, importance=None):
+        """quantize_weight to Q4 through the delta search (include/gten_hip_calib.h): importance float32 [cols] or None (every
+        weight 1) -> the bytes of upload_weight(tests/calib_ref.py's search_q4(w, importance, src))"""
+        want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}[src]
+        elements = np.ascontiguousarray(elements)
+        assert elements.dtype == want and elements.size == rows * cols, (elements.dtype, elements.shape)
+        bufs = [self.upload(elements)]
+        if importance is not None:
+            importance = np.ascontiguousarray(importance, dtype=np.float32)
+            assert importance.shape == (cols,), importance.shape
+            bufs.append(self.upload(importance))
+        dst = self.alloc(rows * self.row_bytes(4, cols))
+        rc = self.quantize_weight_search_rc(bufs[0], src, rows, cols, bufs[1] if importance is not None else None, dst)
+        said = self.last_error() if rc else ""
+        for buf in bufs:
+            buf.free()
+        if rc:
+            dst.free()
+            raise GtenHipError(f"gten_hip error {rc}: {said}")
+        return dst
+
+    def calib_col_energy_rc(self, rows_buf, adtype, n_rows, cols, acc, pitch=None):
+        return self._col_energy(rows_buf.ptr, adtype, n_rows, cols, self.row_bytes(adtype, cols) if pitch is None else pitch, acc.ptr)
+
+    def calib_col_energy(self, *a, **kw):
+        """acc (float64 [cols] on the device) += the column sums of the squared elements of n_rows activation rows
+        (include/gten_hip_calib.h)"""
+        self._check(self.calib_col_energy_rc(*a, **kw))
 
     # -- operators (DeviceBuffers or views of them; pitches default to dense rows).  The `_rc` forms return the code of the
     #    call instead of raising (0 = done; otherwise last_error() names the operator): what a refusal test reads

@@ -4,6 +4,7 @@
 #include <memory>
 
 #include "../../include/gten_host.h"
+#include "calib.h"
 #include "fsm_build.h"
 #include "generate.h"
 #include "quant_load.h"
@@ -15,6 +16,7 @@ struct gten_host_model {
     std::unique_ptr<gten::TinyLlama> model;
     gten::ShiftCounts shifts;            // include/gten_host_shift.h
     gten::QuantLoader quant;             // include/gten_host_quant.h: the staging buffer of set_weight_from
+    gten::Calib calib;                   // include/gten_host_calib.h: the accumulators of a calibration
 };
 
 struct gten_host_batch {

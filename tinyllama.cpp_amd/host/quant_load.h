@@ -1,7 +1,8 @@
 // quant_load.h -- weights from UNQUANTISED bytes (include/gten_host_quant.h): a tensor's elements go up in the dtype they
 // have (f32 / bf16 / f16) into one staging buffer in HBM, grown on demand, and gten_hip_quantize_weight writes the model's
 // weight tensor from there -- Q8 / Q4 quantised and packed, f16 rounded; norm vectors (always f16) take the same way.
-// set_weight_from_lora merges a LoRA adapter on the way (include/gten_hip_lora.h).
+// set_weight_from_lora merges a LoRA adapter on the way (include/gten_hip_lora.h); set_weight_from_search writes
+// Q4 through the importance-weighted delta search (include/gten_hip_calib.h).
 // The one host header that names include/gten_hip_quant.h and include/gten_hip_lora.h beside gten/tensor.h.
 #pragma once
 
@@ -75,6 +76,29 @@ public:
         return model.weight(idx).device_weight_from(stage_, src_dtype, ab_, (const char*)ab_ + b_at, rank, ab_dtype, scale);
     }
     const char* lora_error() const { return lora_error_.c_str(); }
+
+    // A block linear of a Q4 model through the device's delta search (include/gten_host_calib.h, which checks what it takes):
+    // importance f32 [cols] goes up beside the source, into the second buffer; null: every weight 1
+    int set_weight_from_search(TinyLlama& model, int idx, const void* bytes, size_t nbytes, int src_dtype, const float* importance)
+    {
+        const size_t need = src_bytes(model, idx, src_dtype);
+        if (!need || !bytes) return -1;
+        if (nbytes != need) return -2;
+        Tensor& w = model.weight(idx);
+        const size_t imp_bytes = (size_t)w.dimsize(1) * sizeof(float);
+        if (importance && imp_bytes > ab_cap_) {
+            if (ab_) gten_hip_free(ab_);
+            ab_ = nullptr;
+            ab_cap_ = 0;
+            detail::ensure_runtime();
+            if (const int rc = gten_hip_malloc(&ab_, imp_bytes)) return rc;
+            ab_cap_ = imp_bytes;
+        }
+        if (const int rc = stage_source(bytes, nbytes)) return rc;
+        if (importance)
+            if (const int rc = gten_hip_memcpy_h2d(ab_, importance, imp_bytes)) return rc;
+        return w.device_weight_search(stage_, src_dtype, importance ? (const float*)ab_ : nullptr);
+    }
 
     // An f16 .gten file into a model of ANY weight dtype: TinyLlama::load_from_ckpt's framing and messages, each payload
     // checked against the tensor's f16 size and handed to set_weight_from.  An f16 model reads the file as it always did.

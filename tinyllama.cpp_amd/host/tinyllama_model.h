@@ -188,6 +188,7 @@ public:
         }
         return *pre_;
     }
+    TinyLlama* segment_model_if() { return pre_.get(); }      // null until something has created it
 
     // ---- scoring given ids (include/gten_host_score.h): the lm_head over EVERY computed row, in chunks of
     // at most kScoreChunk rows into an f32 scratch this object owns (row pitch padded to 16 bytes), each chunk read by

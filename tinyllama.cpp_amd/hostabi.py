@@ -112,7 +112,10 @@ class GtenHost:
                      "gten_host_model_weight_read"]
     # include/gten_host_lora.h (a LoRA adapter merged into a linear weight while it is quantised on the device; host/capi_lora.cpp)
     LORA_SYMBOLS = ["gten_host_model_set_weight_from_lora", "gten_host_lora_error"]
-    SHIFT_STREAM_MAX = 1 << 24                                   # GTEN_HOST_SHIFT_STREAM_MAX
+    # include/gten_host_calib.h (importance collected from prompt passes; linears quantised through the delta search; host/capi_calib.cpp)
+    CALIB_SYMBOLS = ["gten_host_calib_begin", "gten_host_calib_end", "gten_host_calib_rows", "gten_host_calib_read", "gten_host_calib_error",
+                     "gten_host_calib_set_weight_from"]
+    SHIFT_STREAM_MAX = 1 << 24                                  # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
     BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
@@ -353,6 +356,12 @@ class GtenHost:
         self._wread = _sig(L, "gten_host_model_weight_read", ci, [vp, ci, vp, sz])
         self._setw_from_lora = _sig(L, "gten_host_model_set_weight_from_lora", ci, [vp, ci, vp, sz, ci, vp, vp, ci, ci, C.c_float])
         self._lora_error = _sig(L, "gten_host_lora_error", C.c_char_p, [vp])
+        self._calib_begin = _sig(L, "gten_host_calib_begin", ci, [vp])
+        self._calib_end = _sig(L, "gten_host_calib_end", ci, [vp])
+        self._calib_rows = _sig(L, "gten_host_calib_rows", C.c_longlong, [vp])
+        self._calib_read = _sig(L, "gten_host_calib_read", ci, [vp, ci, ci, vp, ci])
+        self._calib_error = _sig(L, "gten_host_calib_error", C.c_char_p, [vp])
+        self._calib_setw_from = _sig(L, "gten_host_calib_set_weight_from", ci, [vp, ci, vp, sz, ci, vp, ci])
 
     def shift_error(self):
         """the text of the last refusal by an entry point of include/gten_host_shift.h"""
@@ -938,15 +947,27 @@ class HostModel:
             raise GtenHipError(f"load_synthetic rc={rc}")
 
     # -- include/gten_host_quant.h: weights from unquantised elements, quantised on the device
-    def set_weight_from(self, idx, elements, src, lora=None):
+    def set_weight_from(self, idx, elements, src, lora=None, importance=None):
         """weight idx from its dense elements in the source dtype `src` ("f32": float32, "f16": float16, "bf16": raw uint16
         words); the model's weight dtype decides what they become.  The staging buffer stays until quant_release().
         lora = (A, B, scale): a LoRA adapter merged in on the device (include/gten_host_lora.h) -- A [rank][cols] and
-        B [rows][rank], both float32, float16 or raw bf16 words (uint16), only for q, k, v, o, gate, up, down of a block"""
+        B [rows][rank], both float32, float16 or raw bf16 words (uint16), only for q, k, v, o, gate, up, down of a block.
+        importance: float32 [cols] (collect_importance) -- the weight becomes Q4 through the device's delta search
+        (include/gten_host_calib.h); only for those seven linears of a q4 model, and not together with lora"""
         want = {"f32": np.float32, "bf16": np.uint16, "f16": np.float16}[src]
         elements = np.ascontiguousarray(elements)
         if elements.dtype != want:
             raise GtenHipError(f"set_weight_from({idx}): {elements.dtype} elements for source dtype {src}")
+        if importance is not None:
+            if lora is not None:
+                raise GtenHipError(f"set_weight_from({idx}): importance together with lora is not built (merge the adapter first)")
+            importance = np.ascontiguousarray(importance, dtype=np.float32).reshape(-1)
+            rc = self.host._calib_setw_from(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src],
+                                            importance.ctypes.data_as(C.c_void_p), importance.size)
+            if rc:
+                said = self.host._calib_error(self.h).decode() if rc == -3 else self.host.hip.last_error()
+                raise GtenHipError(f"set_weight_from({idx}, importance) rc={rc}: {said}")
+            return
         if lora is None:
             rc = self.host._setw_from(self.h, idx, elements.ctypes.data_as(C.c_void_p), elements.nbytes, self.host.hip.SRC_DTYPES[src])
             if rc:
@@ -974,12 +995,48 @@ class HostModel:
         if rc:
             raise GtenHipError(f"load_gten_f16({path}) rc={rc}")
 
-    def load_checkpoint(self, src, lora=None):
+    def collect_importance(self, texts):
+        """{weight idx: float32 [cols]} for the seven linears of every block: the mean square of the activations that multiply each
+        input column over the rows of `texts` (id sequences), collected on the device during the prompt passes of score_many
+        (include/gten_host_calib.h).  q, k and v of a block share one vector, gate and up another.  What set_weight_from and
+        load_checkpoint take as importance."""
+        rc = self.host._calib_begin(self.h)
+        if rc:
+            raise GtenHipError(f"collect_importance: begin rc={rc}: {self.host.hip.last_error()}")
+        try:
+            self.score_many(texts)
+        finally:
+            rc = self.host._calib_end(self.h)
+        if rc:
+            raise GtenHipError(f"collect_importance: rc={rc}: {self.host.hip.last_error()}")
+        rows = self.calib_rows()
+        out = {}
+        for layer in range(self.cfg.n_layers):
+            vec = [(self.calib_read(layer, which) / rows).astype(np.float32) for which in range(4)]
+            for k, which in enumerate((0, 0, 0, 1, 2, 2, 3)):
+                out[1 + 9 * layer + k] = vec[which]
+        return out
+
+    def calib_rows(self):
+        """rows the last collection has seen"""
+        return int(self.host._calib_rows(self.h))
+
+    def calib_read(self, layer, which):
+        """float64 energy of layer's input `which` (0 of q|k|v, 1 of o, 2 of gate|up, 3 of down) since the last begin"""
+        out = np.zeros(self.cfg.n_ffn if which == 3 else self.cfg.n_embd, np.float64)
+        rc = self.host._calib_read(self.h, layer, which, out.ctypes.data_as(C.c_void_p), out.size)
+        if rc:
+            raise GtenHipError(f"calib_read({layer}, {which}) rc={rc}")
+        return out
+
+    def load_checkpoint(self, src, lora=None, importance=None):
         """a Hugging Face checkpoint (one .safetensors file or a directory of shards, convert.open_checkpoint) straight into
         this model: every tensor goes up in the checkpoint's own dtype and is quantised on the device.
         lora: a PEFT adapter directory or adapter_model.safetensors file (convert.open_lora), or a pair
-        ({hf weight name: (A, B)}, scale): merged into the linear weights it names on the way (set_weight_from)"""
+        ({hf weight name: (A, B)}, scale): merged into the linear weights it names on the way (set_weight_from).
+        importance: {weight idx: float32 [cols]} (collect_importance): the weights it names become Q4 through the delta search"""
         from . import convert
+        importance = importance or {}
         get, n_layers = convert.open_checkpoint(src)
         if n_layers != self.cfg.n_layers:
             raise GtenHipError(f"load_checkpoint({src}): {n_layers} layers, the model has {self.cfg.n_layers}")
@@ -994,7 +1051,7 @@ class HostModel:
                 w = w.astype(np.float16)                                  # (exact: the values came from f16)
             elif dt == "bf16":
                 w = (np.ascontiguousarray(w).view(np.uint32) >> 16).astype(np.uint16)
-            self.set_weight_from(idx, w, dt, lora=(*adapters[name], scale) if name in adapters else None)
+            self.set_weight_from(idx, w, dt, lora=(*adapters[name], scale) if name in adapters else None, importance=importance.get(idx))
         self.quant_release()
 
     def weight_read(self, idx):
