@@ -221,6 +221,147 @@ def open_lora(path, n_layers=None):
     return out, scale
 
 
+# ggml type code -> (name, bytes of a block, elements of a block): what include/gten_hip_gguf.h decodes, and the dense types
+GGML_TYPES = {0: ("F32", 4, 1), 1: ("F16", 2, 1), 30: ("BF16", 2, 1), 2: ("Q4_0", 18, 32), 6: ("Q5_0", 22, 32), 8: ("Q8_0", 34, 32),
+              12: ("Q4_K", 144, 256), 13: ("Q5_K", 176, 256), 14: ("Q6_K", 210, 256)}
+GGML_DENSE = {0: "f32", 1: "f16", 30: "bf16"}
+_GGUF_SCALARS = {0: "<B", 1: "<b", 2: "<H", 3: "<h", 4: "<I", 5: "<i", 6: "<f", 7: "<?", 10: "<Q", 11: "<q", 12: "<d"}
+_GGUF_BLOCK = {"attn_q": "self_attn.q_proj", "attn_k": "self_attn.k_proj", "attn_v": "self_attn.v_proj", "attn_output": "self_attn.o_proj",
+               "ffn_gate": "mlp.gate_proj", "ffn_up": "mlp.up_proj", "ffn_down": "mlp.down_proj", "attn_norm": "input_layernorm",
+               "ffn_norm": "post_attention_layernorm"}
+
+
+def gguf_row_map(rows, n_head):
+    """source row of every destination row of attn_q / attn_k (include/gten_hip_gguf.h): llama.cpp's converter interleaves the
+    two halves of a head's rows; n_head 0: the identity"""
+    r = np.arange(rows)
+    if not n_head:
+        return r
+    d = rows // n_head
+    return r // d * d + 2 * (r % d % (d // 2)) + r % d // (d // 2)
+
+
+def _gguf_hf_name(name):
+    """a llama-family GGUF tensor name -> the key of tensor_names, or None"""
+    fixed = {"token_embd.weight": "model.embed_tokens.weight", "output_norm.weight": "model.norm.weight", "output.weight": "lm_head.weight"}
+    if name in fixed:
+        return fixed[name]
+    part = name.split(".")
+    if len(part) == 4 and part[0] == "blk" and part[1].isdigit() and part[2] in _GGUF_BLOCK and part[3] == "weight":
+        return f"model.layers.{int(part[1])}.{_GGUF_BLOCK[part[2]]}.weight"
+    return None
+
+
+class GgufFile:
+    """open_gguf's accessor: `tensors` maps a tensor_names key to (memory-mapped block bytes uint8[], ggml type, rows, cols) -- a
+    vector has rows 1 --, `meta` holds every scalar and string key, and n_layers / n_head / n_head_kv / alignment what the loader needs"""
+
+    def __init__(self, path, tensors, meta, alignment):
+        self.path, self.tensors, self.meta, self.alignment = path, tensors, meta, alignment
+        self.n_layers = int(meta["llama.block_count"])
+        self.n_head = int(meta["llama.attention.head_count"])
+        self.n_head_kv = int(meta.get("llama.attention.head_count_kv", self.n_head))
+
+    def __getitem__(self, name):
+        return self.tensors[name]
+
+
+def open_gguf(path):
+    """A llama-family GGUF file (version 2 or 3, little-endian) -> GgufFile.  Device-free and hand-written: the header, the
+    key / value section (all 13 value types; arrays are skipped), the tensor infos, the data section at `general.alignment`.
+    Tensors are NOT dequantised: their bytes stay in the file's mapping, as HostModel.load_gguf uploads them.  A file without
+    output.weight gets token_embd's bytes as lm_head.  What cannot be loaded is refused by name."""
+    raw = np.memmap(path, np.uint8, "r")
+    at = 0
+
+    def take(fmt):
+        nonlocal at
+        if at + struct.calcsize(fmt) > raw.size:
+            raise ValueError(f"{path}: the file ends inside its header")
+        v = struct.unpack_from(fmt, raw, at)
+        at += struct.calcsize(fmt)
+        return v if len(v) > 1 else v[0]
+
+    def string():
+        nonlocal at
+        n = take("<Q")
+        if at + n > raw.size:
+            raise ValueError(f"{path}: the file ends inside its header")
+        s = bytes(raw[at:at + n]).decode("utf-8", "replace")
+        at += n
+        return s
+
+    def value(vt, keep=True):
+        nonlocal at
+        if vt in _GGUF_SCALARS:
+            return take(_GGUF_SCALARS[vt])
+        if vt == 8:
+            return string()
+        if vt == 9:
+            et, n = take("<IQ")
+            if et in _GGUF_SCALARS:
+                at += n * struct.calcsize(_GGUF_SCALARS[et])
+            else:
+                for _ in range(n):
+                    value(et, False)
+            return None
+        raise ValueError(f"{path}: key / value type {vt} is not a GGUF value type")
+
+    if raw.size < 24 or bytes(raw[:4]) != b"GGUF":
+        raise ValueError(f"{path}: not a GGUF file (magic {bytes(raw[:4])!r})")
+    at = 4
+    version = take("<I")
+    if version not in (2, 3):
+        if version & 0xFFFF == 0 and version >> 24 in (1, 2, 3):
+            raise ValueError(f"{path}: a big-endian GGUF file (version field {version:#010x}); only little-endian files are read")
+        raise ValueError(f"{path}: GGUF version {version} is not supported (2 or 3)")
+    n_tensors, n_kv = take("<QQ")
+    meta = {}
+    for _ in range(n_kv):
+        key = string()
+        v = value(take("<I"))
+        if v is not None:
+            meta[key] = v
+    alignment = int(meta.get("general.alignment", 32))
+    infos = []
+    for _ in range(n_tensors):
+        name = string()
+        n_dims = take("<I")
+        ne = [take("<Q") for _ in range(n_dims)]
+        code, offset = take("<IQ")
+        infos.append((name, ne, code, offset))
+    data0 = -(-at // alignment) * alignment
+    tensors = {}
+    for name, ne, code, offset in infos:
+        hf = _gguf_hf_name(name)
+        if hf is None:
+            continue                                              # (rope_freqs and the like: nothing this model reads)
+        if code not in GGML_TYPES:
+            raise ValueError(f"{path}: {name} has ggml type {code}, which is not supported ({', '.join(f'{n} {c}' for c, (n, _, _) in sorted(GGML_TYPES.items()))})")
+        if len(ne) not in (1, 2) or offset % alignment:
+            raise ValueError(f"{path}: {name} has the wrong shape {ne} or an offset {offset} off the alignment {alignment}")
+        _, unit, elems = GGML_TYPES[code]
+        cols, rows = ne[0], (ne[1] if len(ne) == 2 else 1)
+        if cols % elems:
+            raise ValueError(f"{path}: {name} has the wrong shape: {cols} columns are no multiple of the {elems} elements of a block of ggml type {code}")
+        nbytes = rows * (cols // elems) * unit
+        if data0 + offset + nbytes > raw.size:
+            raise ValueError(f"{path}: {name} ends behind the file")
+        tensors[hf] = (raw[data0 + offset:data0 + offset + nbytes], code, rows, cols)
+    for key in ("llama.block_count", "llama.attention.head_count"):
+        if key not in meta:
+            raise ValueError(f"{path}: the key {key} is missing")
+    if "lm_head.weight" not in tensors and "model.embed_tokens.weight" in tensors:
+        tensors["lm_head.weight"] = tensors["model.embed_tokens.weight"]
+    back = {v: k for k, v in _GGUF_BLOCK.items()}
+    for hf, _ in tensor_names(int(meta["llama.block_count"])):
+        if hf not in tensors:
+            p = hf.split(".")
+            gg = f"blk.{p[2]}.{back['.'.join(p[3:-1])]}.weight" if p[1] == "layers" else {"model.embed_tokens.weight": "token_embd.weight", "model.norm.weight": "output_norm.weight"}.get(hf, "output.weight")
+            raise ValueError(f"{path}: the tensor {gg} is missing")
+    return GgufFile(path, tensors, meta, alignment)
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])

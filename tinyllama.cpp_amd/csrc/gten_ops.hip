@@ -20,6 +20,7 @@
 #include "gten_quant.h"
 #include "gten_quant_lora.h"
 #include "gten_quant_search.h"
+#include "gten_quant_gguf.h"
 #include "gten_col_energy.h"
 
 #include <cstdlib>

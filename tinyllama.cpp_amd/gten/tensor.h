@@ -32,6 +32,7 @@
 #include "../../include/gten_hip_quant.h"
 #include "../../include/gten_hip_lora.h"
 #include "../../include/gten_hip_calib.h"
+#include "../../include/gten_hip_gguf.h"
 #include "gten_types.h"
 #include "log.h"
 #include "quants.h"
@@ -168,6 +169,14 @@ struct Storage {
         if (const int rc = gten_hip_quantize_weight_search(src_dev, src_dtype, rows, cols, importance_dev, dev)) return rc;
         return dev_weight_filled(GTEN_Q4);
     }
+    // ... from the ggml block stream of a GGUF tensor in HBM (include/gten_hip_gguf.h), decoded and row-mapped on the way
+    int dev_weight_from_gguf(const void* blocks_dev, int ggml_type, int n_head, int dtype_code_, int rows, int cols)
+    {
+        settle_pending();
+        need_dev();
+        if (const int rc = gten_hip_quantize_weight_gguf(blocks_dev, ggml_type, rows, cols, n_head, dtype_code_, dev)) return rc;
+        return dev_weight_filled(dtype_code_);
+    }
     int dev_weight_filled(int dtype_code_)
     {
         host_newer = false;
@@ -269,6 +278,13 @@ public:
         GTEN_ASSERT(dtype_ == kQint4);
         GTEN_ASSERT(is_2d());
         return store_->dev_weight_search(src_dev, src_dtype, importance_dev, shape_[0], shape_[1]);
+    }
+    // a weight matrix from the ggml block stream of its GGUF tensor in HBM: decoded, row-mapped (n_head) and quantised by one launch
+    int device_weight_from_gguf(const void* blocks_dev, int ggml_type, int n_head)
+    {
+        GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
+        GTEN_ASSERT(is_2d());
+        return store_->dev_weight_from_gguf(blocks_dev, ggml_type, n_head, dtype_code(dtype_), shape_[0], shape_[1]);
     }
     bool is_host_external() const { return store_ && store_->external; }
     // identity of the storage this handle aliases (shallow copies share it, gten/tensor.h:24-29)

@@ -187,8 +187,11 @@ class GtenHip:
     LORA_MAX_RANK = 64                                          # GTEN_HIP_LORA_MAX_RANK
     # include/gten_hip_calib.h (column energies of activation rows; Q4 through an importance-weighted delta search)
     CALIB_SYMBOLS = ["gten_hip_quantize_weight_search", "gten_hip_calib_col_energy"]
+    # include/gten_hip_gguf.h (the ggml block stream of a GGUF tensor decoded on the device while it is quantised and packed)
+    GGUF_SYMBOLS = ["gten_hip_gguf_src_bytes", "gten_hip_quantize_weight_gguf"]
+    GGML_TYPES = {"Q4_0": 2, "Q5_0": 6, "Q8_0": 8, "Q4_K": 12, "Q5_K": 13, "Q6_K": 14}      # GTEN_GGML_*
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
-    PREFIXES_MAX = 8                                             # GTEN_PREFIXES_MAX
+    PREFIXES_MAX = 8                                            # GTEN_PREFIXES_MAX
 
     def __init__(self, path=None):
         path = path or _build.HIP_LIB
@@ -320,6 +323,8 @@ class GtenHip:
         self._quantize_lora = _sig(L, "gten_hip_quantize_weight_lora", ci, [vp, ci, ci, ci, vp, vp, ci, ci, C.c_float, ci, vp])
         self._quantize_search = _sig(L, "gten_hip_quantize_weight_search", ci, [vp, ci, ci, ci, vp, vp])
         self._col_energy = _sig(L, "gten_hip_calib_col_energy", ci, [vp, ci, ci, ci, C.c_longlong, vp])
+        self._gguf_src_bytes = _sig(L, "gten_hip_gguf_src_bytes", sz, [ci, ci, ci])
+        self._quantize_gguf = _sig(L, "gten_hip_quantize_weight_gguf", ci, [vp, ci, ci, ci, ci, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -1191,6 +1196,30 @@ class GtenHip:
         src_buf = self.upload(elements)
         dst = self.alloc(rows * self.row_bytes(dtype, cols))
         rc = self.quantize_weight_rc(src_buf, src, rows, cols, dtype, dst)
+        said = self.last_error() if rc else ""
+        src_buf.free()
+        if rc:
+            dst.free()
+            raise GtenHipError(f"gten_hip error {rc}: {said}")
+        return dst
+
+    def gguf_src_bytes(self, ggml_type, rows, cols):
+        """bytes of the ggml block stream of a [rows][cols] tensor (0: a type or shape include/gten_hip_gguf.h does not decode)"""
+        return self._gguf_src_bytes(ggml_type, rows, cols)
+
+    def quantize_weight_gguf_rc(self, blocks_buf, ggml_type, rows, cols, dtype, dst, n_head=0):
+        return self._quantize_gguf(blocks_buf.ptr, ggml_type, rows, cols, n_head, dtype, dst.ptr)
+
+    def quantize_weight_gguf(self, blocks, ggml_type, rows, cols, dtype, n_head=0):
+        """the ggml block stream (uint8) of a [rows][cols] GGUF tensor of type code `ggml_type` -> device weight in `dtype`, decoded,
+        row-mapped by n_head and quantised on the device (include/gten_hip_gguf.h): the bytes of
+        upload_weight(convert.quantize(D(blocks)[row map], dtype, "f32")), or of the f16 rows for dtype F16"""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+        need = self.gguf_src_bytes(ggml_type, rows, cols)
+        assert not need or blocks.size == need, (blocks.size, need)         # (need 0: the call itself refuses the type or the shape)
+        src_buf = self.upload(blocks) if blocks.size else self.alloc(16)
+        dst = self.alloc(rows * self.row_bytes(dtype, cols))
+        rc = self.quantize_weight_gguf_rc(src_buf, ggml_type, rows, cols, dtype, dst, n_head)
         said = self.last_error() if rc else ""
         src_buf.free()
         if rc:

@@ -3,13 +3,15 @@
 // weight tensor from there -- Q8 / Q4 quantised and packed, f16 rounded; norm vectors (always f16) take the same way.
 // set_weight_from_lora merges a LoRA adapter on the way (include/gten_hip_lora.h); set_weight_from_search writes
 // Q4 through the importance-weighted delta search (include/gten_hip_calib.h).
-// The one host header that names include/gten_hip_quant.h and include/gten_hip_lora.h beside gten/tensor.h.
+// set_weight_from_gguf takes a GGUF tensor's ggml block stream, decoded on the device (include/gten_hip_gguf.h).
+// The one host header that names include/gten_hip_quant.h, include/gten_hip_lora.h and include/gten_hip_gguf.h beside gten/tensor.h.
 #pragma once
 
 #include <fstream>
 #include <string>
 #include <vector>
 
+#include "../../include/gten_hip_gguf.h"
 #include "../../include/gten_hip_lora.h"
 #include "../../include/gten_hip_quant.h"
 #include "tinyllama_model.h"
@@ -98,6 +100,26 @@ public:
         if (importance)
             if (const int rc = gten_hip_memcpy_h2d(ab_, importance, imp_bytes)) return rc;
         return w.device_weight_search(stage_, src_dtype, importance ? (const float*)ab_ : nullptr);
+    }
+
+    // Weight idx from the bytes of a GGUF tensor of ggml type `ggml_type` (include/gten_host_gguf.h).  A block format: the block
+    // stream goes up as it lies in the file and include/gten_hip_gguf.h decodes it, row-mapped by n_head, while it quantises.  The
+    // dense types (F32 0, F16 1, BF16 30 -- every norm vector) take set_weight_from.  -3: a code that is neither, a block format for
+    // a norm vector, a dense type with a row map.
+    int set_weight_from_gguf(TinyLlama& model, int idx, const void* bytes, size_t nbytes, int ggml_type, int n_head)
+    {
+        if (idx < 0 || idx >= model.n_weights() || !bytes || n_head < 0) return -1;
+        if (ggml_type == 0 || ggml_type == 1 || ggml_type == 30) {
+            if (n_head != 0) return -3;
+            return set_weight_from(model, idx, bytes, nbytes, ggml_type == 0 ? GTEN_HIP_SRC_F32 : ggml_type == 1 ? GTEN_HIP_SRC_F16 : GTEN_HIP_SRC_BF16);
+        }
+        Tensor& w = model.weight(idx);
+        if (!w.is_2d()) return -3;
+        const size_t need = gten_hip_gguf_src_bytes(ggml_type, w.dimsize(0), w.dimsize(1));
+        if (!need) return gten_hip_gguf_src_bytes(ggml_type, 1, 256) ? -2 : -3;      // the shape does not fit the format | not a format
+        if (nbytes != need) return -2;
+        if (const int rc = stage_source(bytes, nbytes)) return rc;
+        return w.device_weight_from_gguf(stage_, ggml_type, n_head);
     }
 
     // An f16 .gten file into a model of ANY weight dtype: TinyLlama::load_from_ckpt's framing and messages, each payload

@@ -33,6 +33,7 @@
 #include "json_schema.h"
 #include "generate.h"
 #include "generate_shift.h"
+#include "gguf_file.h"
 #include "quant_load.h"
 #include "tokenizer.h"
 
@@ -53,6 +54,7 @@ Optional args.
 --topk K : Top tokens to randomly select from during prediction. [default=50].
 --model PATH :     .gten checkpoint [default=models/tinyllama.<fp16|q8|q4>.gten].
 --from-f16 :       the --model file is the f16 checkpoint: quantise it on the device to the mode given by -q8 / -q4. Not with -f16.
+--from-gguf :      the --model file is a llama-family GGUF file (Q8_0, Q4_0, Q5_0, Q4_K, Q5_K, Q6_K, F32, F16, BF16 tensors): decode it on the device into the mode given by -q8 / -q4 / -f16.
 --tokenizer PATH : vocabulary file [default=tokenizer.bin].
 --seed S : seed of the top-k sampler [default: random].
 --ids :    print token ids instead of text (with --score: one `id logprob rank` line per scored id).
@@ -112,6 +114,7 @@ struct Options {
     float temp = 0.9f;
     bool greedy = false, ids = false, seeded = false;
     bool from_f16 = false;                   // --from-f16: the model file is f16, quantised on the device (host/quant_load.h)
+    bool from_gguf = false;                  // --from-gguf: the model file is a GGUF file, decoded on the device (host/gguf_file.h)
     uint64_t seed = 0;
     std::vector<int32_t> ban, allow;         // --ban / --allow (bias table 0)
     int min_new = 0;
@@ -406,6 +409,7 @@ int main(int argc, char const* argv[])
         else if (arg == "-p") o.prompt = value("prompt");
         else if (arg == "--model") o.model_path = value("model");
         else if (arg == "--from-f16") o.from_f16 = true;
+        else if (arg == "--from-gguf") o.from_gguf = true;
         else if (arg == "--tokenizer") o.tokenizer_path = value("tokenizer");
         else if (arg == "--score") o.score_path = value("score");
         else if (arg == "--embed") o.embed_path = value("embed");
@@ -624,6 +628,7 @@ int main(int argc, char const* argv[])
         return -1;
     }
     if (o.from_f16 && o.model_dtype == kFloat16) { std::cerr << "--from-f16 quantises an f16 file to -q8 or -q4: not with -f16.\n"; return -1; }
+    if (o.from_gguf && o.from_f16) { std::cerr << "--from-gguf and --from-f16 name two kinds of --model file: give one.\n"; return -1; }
     if (o.model_path.empty()) o.model_path = "models/tinyllama." + (o.from_f16 ? std::string("fp16") : model_id) + ".gten";
 
     std::ifstream checkpoint{o.model_path, std::ios::binary};
@@ -640,7 +645,10 @@ int main(int argc, char const* argv[])
     dtype.adtype = (o.model_dtype == kFloat16) ? kFloat16 : kQint8;          // tinyllama.cpp:258-265
 
     TinyLlama model{o.score_path.empty() && o.embed_path.empty() && !o.shifting() ? o.n_predict : o.ctx, dtype};
-    if (o.from_f16) QuantLoader{}.load_gten_f16(model, checkpoint);
+    if (o.from_gguf) {
+        QuantLoader quant;
+        GgufFile{checkpoint}.load_into(model, quant);
+    } else if (o.from_f16) QuantLoader{}.load_gten_f16(model, checkpoint);
     else model.load_from_ckpt(checkpoint);
     Tokenizer tokenizer{o.tokenizer_path.c_str(), 32000};
     if (!o.score_path.empty()) return run_score(o, model, tokenizer);

@@ -115,7 +115,9 @@ class GtenHost:
     # include/gten_host_calib.h (importance collected from prompt passes; linears quantised through the delta search; host/capi_calib.cpp)
     CALIB_SYMBOLS = ["gten_host_calib_begin", "gten_host_calib_end", "gten_host_calib_rows", "gten_host_calib_read", "gten_host_calib_error",
                      "gten_host_calib_set_weight_from"]
-    SHIFT_STREAM_MAX = 1 << 24                                  # GTEN_HOST_SHIFT_STREAM_MAX
+    # include/gten_host_gguf.h (a model's weight from the bytes of a GGUF tensor, decoded on the device; host/capi_gguf.cpp)
+    GGUF_SYMBOLS = ["gten_host_model_set_weight_from_gguf"]
+    SHIFT_STREAM_MAX = 1 << 24                                 # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
     BEAM_MAX = 8                                                 # GTEN_HOST_BEAM_MAX
@@ -354,6 +356,7 @@ class GtenHost:
         self._quant_release = _sig(L, "gten_host_model_quant_release", ci, [vp])
         self._loadg_f16 = _sig(L, "gten_host_model_load_gten_f16", ci, [vp, C.c_char_p])
         self._wread = _sig(L, "gten_host_model_weight_read", ci, [vp, ci, vp, sz])
+        self._setw_from_gguf = _sig(L, "gten_host_model_set_weight_from_gguf", ci, [vp, ci, vp, sz, ci, ci])
         self._setw_from_lora = _sig(L, "gten_host_model_set_weight_from_lora", ci, [vp, ci, vp, sz, ci, vp, vp, ci, ci, C.c_float])
         self._lora_error = _sig(L, "gten_host_lora_error", C.c_char_p, [vp])
         self._calib_begin = _sig(L, "gten_host_calib_begin", ci, [vp])
@@ -1052,6 +1055,43 @@ class HostModel:
             elif dt == "bf16":
                 w = (np.ascontiguousarray(w).view(np.uint32) >> 16).astype(np.uint16)
             self.set_weight_from(idx, w, dt, lora=(*adapters[name], scale) if name in adapters else None, importance=importance.get(idx))
+        self.quant_release()
+
+    def set_weight_from_gguf(self, idx, raw, ggml_type, n_head=0, name=None):
+        """weight idx from the bytes of a GGUF tensor (uint8, as they lie in the file) of ggml type code `ggml_type`
+        (include/gten_host_gguf.h): block formats are decoded, row-mapped by n_head and quantised on the device; F32 / F16 /
+        BF16 take set_weight_from's way"""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+        rc = self.host._setw_from_gguf(self.h, idx, _ptr(raw), raw.size, int(ggml_type), int(n_head))
+        if rc:
+            what = f"set_weight_from_gguf({idx}{', ' + name if name else ''}, ggml type {ggml_type})"
+            said = {-1: "bad index or argument", -2: f"{raw.size} bytes are not the tensor's size in that type (wrong shape)",
+                    -3: "a ggml type that is not supported, or one this tensor cannot take"}.get(rc) or self.host.hip.last_error()
+            raise GtenHipError(f"{what} rc={rc}: {said}")
+
+    def load_gguf(self, path, lora=None, importance=None):
+        """a llama-family GGUF file (convert.open_gguf) straight into this model: every tensor goes up as it lies in the file and
+        is decoded on the device while it is quantised (include/gten_hip_gguf.h); attn_q / attn_k come back in the Hugging Face
+        row order.  lora / importance are refused: merge or calibrate from a dense checkpoint (load_checkpoint) instead."""
+        from . import convert
+        for given, what in ((lora, "lora"), (importance, "importance")):
+            if given is not None:
+                raise GtenHipError(f"load_gguf({path}): {what}= is not built for quantised tensors: merge or calibrate from a dense checkpoint "
+                                   "(load_checkpoint) instead")
+        g = convert.open_gguf(path)
+        if g.n_layers != self.cfg.n_layers or g.n_head != self.cfg.n_heads or g.n_head_kv != self.cfg.n_kv_heads:
+            raise GtenHipError(f"load_gguf({path}): {g.n_layers} layers, {g.n_head} heads, {g.n_head_kv} K/V heads; the model has "
+                               f"{self.cfg.n_layers}, {self.cfg.n_heads}, {self.cfg.n_kv_heads}")
+        shapes = self.cfg.weight_shapes()
+        for idx, (name, _) in enumerate(convert.tensor_names(g.n_layers)):
+            raw, code, rows, cols = g[name]
+            if (rows, cols) != shapes[idx][:2]:
+                raise GtenHipError(f"load_gguf({path}): {name} has the wrong shape {rows} x {cols}, the model's is {shapes[idx][0]} x {shapes[idx][1]}")
+            n_head = g.n_head if name.endswith("q_proj.weight") else g.n_head_kv if name.endswith("k_proj.weight") else 0
+            if n_head and code in convert.GGML_DENSE:              # a dense q / k: the rows back into order here, nothing to decode
+                raw = np.ascontiguousarray(np.asarray(raw).reshape(rows, -1)[convert.gguf_row_map(rows, n_head)])
+                n_head = 0
+            self.set_weight_from_gguf(idx, raw, code, n_head, name)
         self.quant_release()
 
     def weight_read(self, idx):
