@@ -362,6 +362,108 @@ def open_gguf(path):
     return GgufFile(path, tensors, meta, alignment)
 
 
+W4_LINEARS = tuple(f"self_attn.{k}_proj" for k in ("q", "k", "v", "o")) + tuple(f"mlp.{k}_proj" for k in ("gate", "up", "down"))
+
+
+class QuantizedCheckpoint:
+    """open_quantized's accessor.  layout "gptq" | "awq", zero_offset, group_size (-1: one group), n_layers and `config` (the
+    quantisation settings as read); linear(name) / dense(name) take a tensor_names key; trivial_g_idx maps every linear that has
+    a g_idx to whether it equals k / group_size (linear() then hands None on, the device's fast form)."""
+
+    def __init__(self, src, get, n_layers, layout, zero_offset, group_size, config, raw):
+        self.src, self._get, self.n_layers, self.layout, self.zero_offset, self.group_size = src, get, n_layers, layout, zero_offset, group_size
+        self.config, self._raw, self.trivial_g_idx = config, raw, {}
+
+    def is_quantized(self, name):
+        return name.startswith("model.layers.") and name[:-len(".weight")].split(".", 3)[3] in W4_LINEARS
+
+    def dense(self, name):
+        """(f32 array, checkpoint dtype) of embed_tokens, lm_head or a norm vector"""
+        return self._get(name)
+
+    def linear(self, name):
+        """(qweight int32, qzeros int32, scales f16, g_idx int32 or None, rows N, cols K) of a block linear, shapes checked"""
+        base = name[:-len(".weight")]
+        qweight, qzeros, scales = (self._raw(f"{base}.{part}") for part in ("qweight", "qzeros", "scales"))
+        if qweight.ndim != 2 or qweight.dtype != np.int32 or qzeros.dtype != np.int32 or scales.dtype != np.float16:
+            raise ValueError(f"{self.src}: {base} needs int32 qweight and qzeros matrices and float16 scales")
+        rows, cols = (qweight.shape[1], qweight.shape[0] * 8) if self.layout == "gptq" else (qweight.shape[1] * 8, qweight.shape[0])
+        gs = self.group_size
+        if cols % 32 or rows % 8 or (gs != -1 and cols % gs):
+            raise ValueError(f"{self.src}: {base} has the wrong shape: {rows} x {cols} with group_size {gs} (cols % 32, rows % 8, cols % group_size)")
+        groups = 1 if gs == -1 else cols // gs
+        if qzeros.shape != (groups, rows // 8) or scales.shape != (groups, rows):
+            raise ValueError(f"{self.src}: {base} has the wrong shape: qzeros {qzeros.shape} and scales {scales.shape} for {groups} groups of a {rows} x {cols} weight")
+        g_idx = None
+        if self.layout == "gptq" and self._raw(f"{base}.g_idx", missing_ok=True) is not None:
+            g_idx = np.ascontiguousarray(self._raw(f"{base}.g_idx"), dtype=np.int32)
+            if g_idx.shape != (cols,):
+                raise ValueError(f"{self.src}: {base}.g_idx has the wrong shape {g_idx.shape} for {cols} input features")
+            self.trivial_g_idx[name] = bool(np.array_equal(g_idx, np.arange(cols) // (cols if gs == -1 else gs)))
+            if self.trivial_g_idx[name]:
+                g_idx = None
+        return qweight, qzeros, scales, g_idx, rows, cols
+
+
+def open_quantized(src):
+    """A GPTQ or AWQ 4-bit Hugging Face checkpoint -- one .safetensors file or a directory of them, with `quantization_config` in
+    config.json or a quantize_config.json beside it -> QuantizedCheckpoint for HostModel.load_quantized.  Device-free; nothing is
+    dequantised.  Accepted: quant_method gptq (checkpoint_format gptq | gptq_v2; desc_act and sym either way) and awq (version
+    gemm).  What include/gten_hip_w4.h cannot take is refused by name."""
+    import json
+    from safetensors import safe_open
+    d = src if os.path.isdir(src) else os.path.dirname(os.path.abspath(src))
+    cfg = None
+    if os.path.exists(os.path.join(d, "config.json")):
+        with open(os.path.join(d, "config.json")) as f:
+            cfg = json.load(f).get("quantization_config")
+    if cfg is None and os.path.exists(os.path.join(d, "quantize_config.json")):
+        with open(os.path.join(d, "quantize_config.json")) as f:
+            cfg = json.load(f)
+    if cfg is None:
+        raise ValueError(f"{src}: no quantization_config in config.json and no quantize_config.json beside the checkpoint")
+    method = str(cfg.get("quant_method", "gptq")).lower()
+    bits, gs = int(cfg.get("bits", cfg.get("w_bit", 0))), int(cfg.get("group_size", cfg.get("q_group_size", 0)))
+    if method not in ("gptq", "awq"):
+        raise ValueError(f"{src}: quant_method {method!r} is not supported (gptq or awq)")
+    if bits != 4:
+        raise ValueError(f"{src}: {bits}-bit weights are not supported (4 bits only)")
+    if gs != -1 and (gs < 32 or gs % 32):
+        raise ValueError(f"{src}: group_size {gs} is not supported (-1, or a multiple of 32 that divides the input features)")
+    if method == "gptq":
+        fmt = str(cfg.get("checkpoint_format", "gptq")).lower()
+        if cfg.get("is_marlin_format") or fmt not in ("gptq", "gptq_v2"):
+            raise ValueError(f"{src}: GPTQ checkpoint_format {'marlin' if cfg.get('is_marlin_format') else fmt!r} is a repacked form (Marlin, exllama) "
+                             "that is not supported (gptq or gptq_v2)")
+        zero_offset = 1 if fmt == "gptq" else 0
+    else:
+        version = str(cfg.get("version", "gemm")).lower()
+        if version != "gemm":
+            raise ValueError(f"{src}: AWQ version {version!r} is not supported (gemm only; not gemv, gemv_fast, marlin or exllama)")
+        if not cfg.get("zero_point", True):
+            raise ValueError(f"{src}: AWQ without zero points (zero_point false) is not supported")
+        zero_offset = 0
+    get, n_layers = open_checkpoint(src)
+    files = [src] if os.path.isfile(src) else sorted(os.path.join(src, f) for f in os.listdir(src) if f.endswith(".safetensors"))
+    handles = [safe_open(f, framework="np") for f in files]
+    index = {k: h for h in handles for k in h.keys()}
+
+    def raw(key, missing_ok=False):
+        if key not in index:
+            if missing_ok:
+                return None
+            raise ValueError(f"{src}: the tensor {key} is missing")
+        return index[key].get_tensor(key)
+
+    ck = QuantizedCheckpoint(src, get, n_layers, method, zero_offset, gs, dict(cfg), raw)
+    for name, _ in tensor_names(n_layers):
+        keys = [f"{name[:-len('.weight')]}.{part}" for part in ("qweight", "qzeros", "scales")] if ck.is_quantized(name) else [name]
+        for key in keys:
+            if key not in index:
+                raise ValueError(f"{src}: the tensor {key} is missing")
+    return ck
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])

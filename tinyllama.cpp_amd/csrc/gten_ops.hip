@@ -21,6 +21,7 @@
 #include "gten_quant_lora.h"
 #include "gten_quant_search.h"
 #include "gten_quant_gguf.h"
+#include "gten_quant_w4.h"
 #include "gten_col_energy.h"
 
 #include <cstdlib>

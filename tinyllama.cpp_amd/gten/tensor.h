@@ -33,6 +33,7 @@
 #include "../../include/gten_hip_lora.h"
 #include "../../include/gten_hip_calib.h"
 #include "../../include/gten_hip_gguf.h"
+#include "../../include/gten_hip_w4.h"
 #include "gten_types.h"
 #include "log.h"
 #include "quants.h"
@@ -177,6 +178,15 @@ struct Storage {
         if (const int rc = gten_hip_quantize_weight_gguf(blocks_dev, ggml_type, rows, cols, n_head, dtype_code_, dev)) return rc;
         return dev_weight_filled(dtype_code_);
     }
+    // ... from the qweight / qzeros / scales (/ g_idx) of a GPTQ or AWQ linear in HBM (include/gten_hip_w4.h), transposed on the way
+    int dev_weight_from_w4(const void* qweight, const void* qzeros, const void* scales, const void* g_idx, int layout, int zero_offset,
+                           int group_size, int dtype_code_, int rows, int cols)
+    {
+        settle_pending();
+        need_dev();
+        if (const int rc = gten_hip_quantize_weight_w4(qweight, qzeros, scales, g_idx, layout, zero_offset, rows, cols, group_size, dtype_code_, dev)) return rc;
+        return dev_weight_filled(dtype_code_);
+    }
     int dev_weight_filled(int dtype_code_)
     {
         host_newer = false;
@@ -285,6 +295,13 @@ public:
         GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
         GTEN_ASSERT(is_2d());
         return store_->dev_weight_from_gguf(blocks_dev, ggml_type, n_head, dtype_code(dtype_), shape_[0], shape_[1]);
+    }
+    // a weight matrix from the four tensors of its GPTQ / AWQ linear in HBM: unpacked, transposed and quantised by one launch
+    int device_weight_from_w4(const void* qweight, const void* qzeros, const void* scales, const void* g_idx, int layout, int zero_offset, int group_size)
+    {
+        GTEN_ASSERT(dtype_ == kQint8 || dtype_ == kQint4 || dtype_ == kFloat16);
+        GTEN_ASSERT(is_2d());
+        return store_->dev_weight_from_w4(qweight, qzeros, scales, g_idx, layout, zero_offset, group_size, dtype_code(dtype_), shape_[0], shape_[1]);
     }
     bool is_host_external() const { return store_ && store_->external; }
     // identity of the storage this handle aliases (shallow copies share it, gten/tensor.h:24-29)

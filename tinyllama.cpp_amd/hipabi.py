@@ -190,6 +190,9 @@ class GtenHip:
     # include/gten_hip_gguf.h (the ggml block stream of a GGUF tensor decoded on the device while it is quantised and packed)
     GGUF_SYMBOLS = ["gten_hip_gguf_src_bytes", "gten_hip_quantize_weight_gguf"]
     GGML_TYPES = {"Q4_0": 2, "Q5_0": 6, "Q8_0": 8, "Q4_K": 12, "Q5_K": 13, "Q6_K": 14}      # GTEN_GGML_*
+    # include/gten_hip_w4.h (GPTQ / AWQ 4-bit tensors unpacked and transposed on the device while they are quantised and packed)
+    W4_SYMBOLS = ["gten_hip_w4_src_bytes", "gten_hip_quantize_weight_w4"]
+    W4_LAYOUTS = {"gptq": 0, "awq": 1}                          # GTEN_W4_*
     GROUPS_MAX = 64                                             # GTEN_GROUPS_MAX
     PREFIXES_MAX = 8                                            # GTEN_PREFIXES_MAX
 
@@ -325,6 +328,8 @@ class GtenHip:
         self._col_energy = _sig(L, "gten_hip_calib_col_energy", ci, [vp, ci, ci, ci, C.c_longlong, vp])
         self._gguf_src_bytes = _sig(L, "gten_hip_gguf_src_bytes", sz, [ci, ci, ci])
         self._quantize_gguf = _sig(L, "gten_hip_quantize_weight_gguf", ci, [vp, ci, ci, ci, ci, ci, vp])
+        self._w4_src_bytes = _sig(L, "gten_hip_w4_src_bytes", sz, [ci, ci, ci, ci, ci])
+        self._quantize_w4 = _sig(L, "gten_hip_quantize_weight_w4", ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp])
         self.initialised = False
 
     # -- runtime
@@ -1222,6 +1227,37 @@ class GtenHip:
         rc = self.quantize_weight_gguf_rc(src_buf, ggml_type, rows, cols, dtype, dst, n_head)
         said = self.last_error() if rc else ""
         src_buf.free()
+        if rc:
+            dst.free()
+            raise GtenHipError(f"gten_hip error {rc}: {said}")
+        return dst
+
+    def w4_src_bytes(self, layout, which, rows, cols, group_size):
+        """bytes of qweight (which 0), qzeros (1), scales (2) or g_idx (3) of a [rows][cols] weight in layout "gptq" / "awq"
+        (0: an argument include/gten_hip_w4.h refuses)"""
+        return self._w4_src_bytes(self.W4_LAYOUTS.get(layout, -1), which, rows, cols, group_size)
+
+    def quantize_weight_w4_rc(self, qweight, qzeros, scales, g_idx, layout, zero_offset, rows, cols, group_size, dtype, dst):
+        return self._quantize_w4(qweight.ptr, qzeros.ptr, scales.ptr, g_idx.ptr if g_idx is not None else None, self.W4_LAYOUTS[layout], zero_offset,
+                                 rows, cols, group_size, dtype, dst.ptr)
+
+    def quantize_weight_w4(self, qweight, qzeros, scales, g_idx, layout, zero_offset, rows, cols, group_size, dtype):
+        """qweight / qzeros (int32), scales (f16) and g_idx (int32, or None: k / group_size) of a GPTQ / AWQ linear -> device weight
+        [rows][cols] in `dtype`, unpacked, transposed and quantised on the device (include/gten_hip_w4.h): the bytes of
+        upload_weight(convert.quantize(D, dtype, "f16")), or of the f16 rows of D for dtype F16"""
+        parts = [np.ascontiguousarray(qweight).view(np.uint8).reshape(-1), np.ascontiguousarray(qzeros).view(np.uint8).reshape(-1),
+                 np.ascontiguousarray(scales, dtype=np.float16).view(np.uint8).reshape(-1),
+                 None if g_idx is None else np.ascontiguousarray(g_idx, dtype=np.int32).view(np.uint8).reshape(-1)]
+        for which, part in enumerate(parts):
+            need = self.w4_src_bytes(layout, which, rows, cols, group_size)
+            assert part is None or not need or part.size == need, (which, part.size, need)      # (need 0: the call itself refuses)
+        bufs = [None if part is None else self.upload(part) if part.size else self.alloc(16) for part in parts]
+        dst = self.alloc(rows * self.row_bytes(dtype, cols))
+        rc = self.quantize_weight_w4_rc(*bufs, layout, zero_offset, rows, cols, group_size, dtype, dst)
+        said = self.last_error() if rc else ""
+        for buf in bufs:
+            if buf is not None:
+                buf.free()
         if rc:
             dst.free()
             raise GtenHipError(f"gten_hip error {rc}: {said}")

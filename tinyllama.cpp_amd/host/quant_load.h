@@ -4,7 +4,9 @@
 // set_weight_from_lora merges a LoRA adapter on the way (include/gten_hip_lora.h); set_weight_from_search writes
 // Q4 through the importance-weighted delta search (include/gten_hip_calib.h).
 // set_weight_from_gguf takes a GGUF tensor's ggml block stream, decoded on the device (include/gten_hip_gguf.h).
-// The one host header that names include/gten_hip_quant.h, include/gten_hip_lora.h and include/gten_hip_gguf.h beside gten/tensor.h.
+// set_weight_from_w4 takes the four tensors of a GPTQ / AWQ linear, transposed on the device (include/gten_hip_w4.h).
+// The one host header that names include/gten_hip_quant.h, include/gten_hip_lora.h, include/gten_hip_gguf.h and include/gten_hip_w4.h
+// beside gten/tensor.h.
 #pragma once
 
 #include <fstream>
@@ -14,6 +16,7 @@
 #include "../../include/gten_hip_gguf.h"
 #include "../../include/gten_hip_lora.h"
 #include "../../include/gten_hip_quant.h"
+#include "../../include/gten_hip_w4.h"
 #include "tinyllama_model.h"
 
 namespace gten {
@@ -122,6 +125,31 @@ public:
         return w.device_weight_from_gguf(stage_, ggml_type, n_head);
     }
 
+    // A block linear from the qweight / qzeros / scales (/ g_idx) of its GPTQ or AWQ layer (include/gten_host_w4.h): the pieces go up
+    // behind each other, each from a 16-byte boundary, and include/gten_hip_w4.h unpacks, transposes and quantises them in one launch.
+    // -2: a shape or group_size the layout cannot hold; -3: embed_tokens, lm_head and the norm vectors, dense in these checkpoints.
+    int set_weight_from_w4(TinyLlama& model, int idx, const void* qweight, const void* qzeros, const void* scales, const void* g_idx, int layout,
+                           int zero_offset, int group_size)
+    {
+        if (idx < 0 || idx >= model.n_weights() || !qweight || !qzeros || !scales) return -1;
+        if (idx == 0 || idx >= model.n_weights() - 2 || (idx - 1) % 9 >= 7) return -3;
+        Tensor& w = model.weight(idx);
+        const void* piece[4] = {qweight, qzeros, scales, g_idx};
+        size_t bytes[4], at[4], total = 0;
+        for (int i = 0; i < 4; i++) {
+            bytes[i] = piece[i] ? gten_hip_w4_src_bytes(layout, i, w.dimsize(0), w.dimsize(1), group_size) : 0;
+            if (piece[i] && !bytes[i]) return i == 3 ? -1 : -2;       // (a g_idx for AWQ is a bad argument, not a bad shape)
+            at[i] = total;
+            total += (bytes[i] + 15) & ~(size_t)15;
+        }
+        if (const int rc = stage_reserve(total)) return rc;
+        for (int i = 0; i < 4; i++)
+            if (piece[i])
+                if (const int rc = gten_hip_memcpy_h2d((char*)stage_ + at[i], piece[i], bytes[i])) return rc;
+        return w.device_weight_from_w4(stage_, (char*)stage_ + at[1], (char*)stage_ + at[2], g_idx ? (char*)stage_ + at[3] : nullptr, layout, zero_offset,
+                                       group_size);
+    }
+
     // An f16 .gten file into a model of ANY weight dtype: TinyLlama::load_from_ckpt's framing and messages, each payload
     // checked against the tensor's f16 size and handed to set_weight_from.  An f16 model reads the file as it always did.
     void load_gten_f16(TinyLlama& model, std::ifstream& ckpt)
@@ -167,8 +195,8 @@ public:
     }
 
 private:
-    // the source bytes into the staging buffer, grown on demand
-    int stage_source(const void* bytes, size_t nbytes)
+    // the staging buffer, grown on demand
+    int stage_reserve(size_t nbytes)
     {
         if (nbytes > cap_) {
             if (stage_) gten_hip_free(stage_);
@@ -178,6 +206,12 @@ private:
             if (const int rc = gten_hip_malloc(&stage_, nbytes)) return rc;
             cap_ = nbytes;
         }
+        return 0;
+    }
+    // the source bytes into it
+    int stage_source(const void* bytes, size_t nbytes)
+    {
+        if (const int rc = stage_reserve(nbytes)) return rc;
         return gten_hip_memcpy_h2d(stage_, bytes, nbytes);
     }
 

@@ -117,6 +117,8 @@ class GtenHost:
                      "gten_host_calib_set_weight_from"]
     # include/gten_host_gguf.h (a model's weight from the bytes of a GGUF tensor, decoded on the device; host/capi_gguf.cpp)
     GGUF_SYMBOLS = ["gten_host_model_set_weight_from_gguf"]
+    # include/gten_host_w4.h (a model's linear from the tensors of a GPTQ / AWQ 4-bit checkpoint, transposed on the device; host/capi_w4.cpp)
+    W4_SYMBOLS = ["gten_host_model_set_weight_from_w4"]
     SHIFT_STREAM_MAX = 1 << 24                                 # GTEN_HOST_SHIFT_STREAM_MAX
     # include/gten_host_beam.h (beam search, host/capi_beam.cpp; the plan: host/beam_plan.h)
     BEAM_SYMBOLS = ["gten_host_batch_beam_search", "gten_host_beam_weights", "gten_host_beam_backtrack", "gten_host_beam_finalize"]
@@ -357,6 +359,7 @@ class GtenHost:
         self._loadg_f16 = _sig(L, "gten_host_model_load_gten_f16", ci, [vp, C.c_char_p])
         self._wread = _sig(L, "gten_host_model_weight_read", ci, [vp, ci, vp, sz])
         self._setw_from_gguf = _sig(L, "gten_host_model_set_weight_from_gguf", ci, [vp, ci, vp, sz, ci, ci])
+        self._setw_from_w4 = _sig(L, "gten_host_model_set_weight_from_w4", ci, [vp, ci, vp, vp, vp, vp, ci, ci, ci])
         self._setw_from_lora = _sig(L, "gten_host_model_set_weight_from_lora", ci, [vp, ci, vp, sz, ci, vp, vp, ci, ci, C.c_float])
         self._lora_error = _sig(L, "gten_host_lora_error", C.c_char_p, [vp])
         self._calib_begin = _sig(L, "gten_host_calib_begin", ci, [vp])
@@ -1092,6 +1095,58 @@ class HostModel:
                 raw = np.ascontiguousarray(np.asarray(raw).reshape(rows, -1)[convert.gguf_row_map(rows, n_head)])
                 n_head = 0
             self.set_weight_from_gguf(idx, raw, code, n_head, name)
+        self.quant_release()
+
+    def set_weight_from_w4(self, idx, qweight, qzeros, scales, g_idx, layout, zero_offset, group_size, name=None):
+        """weight idx -- q, k, v, o, gate, up or down of a block -- from the qweight / qzeros (int32), scales (float16) and g_idx
+        (int32, or None: k / group_size) of its layer in a GPTQ ("gptq") or AWQ ("awq") checkpoint (include/gten_host_w4.h):
+        unpacked, transposed, dequantised and quantised into the model's weight dtype on the device"""
+        hip = self.host.hip
+        what = f"set_weight_from_w4({idx}{', ' + name if name else ''}, {layout})"
+        if layout not in hip.W4_LAYOUTS:
+            raise GtenHipError(f"{what}: the layout is not one of {sorted(hip.W4_LAYOUTS)}")
+        rows, cols = self.cfg.weight_shapes()[idx][:2]
+        parts = [np.ascontiguousarray(qweight), np.ascontiguousarray(qzeros), np.ascontiguousarray(scales), None if g_idx is None else np.ascontiguousarray(g_idx)]
+        for which, (part, dt) in enumerate(zip(parts, (np.int32, np.int32, np.float16, np.int32))):
+            if part is None:
+                continue
+            need = hip.w4_src_bytes(layout, which, rows, cols, group_size)
+            if part.dtype != dt or part.nbytes != need:         # (the C call takes no sizes: they are settled here)
+                raise GtenHipError(f"{what}: {('qweight', 'qzeros', 'scales', 'g_idx')[which]} is {part.dtype} x {part.size}; a {rows} x {cols} weight with "
+                                   f"group_size {group_size} takes {need} bytes of {np.dtype(dt)} (0: the shape or the group size cannot be held)")
+        rc = self.host._setw_from_w4(self.h, idx, *[None if part is None else _ptr(part) for part in parts], hip.W4_LAYOUTS[layout], int(zero_offset), int(group_size))
+        if rc:
+            said = {-1: "bad index or argument", -2: "a shape or group_size the layout cannot hold",
+                    -3: "only q, k, v, o, gate, up and down of a block are quantised in these checkpoints"}.get(rc) or hip.last_error()
+            raise GtenHipError(f"{what} rc={rc}: {said}")
+
+    def load_quantized(self, src, lora=None, importance=None):
+        """a GPTQ or AWQ 4-bit Hugging Face checkpoint (convert.open_quantized: one .safetensors file or a directory, with its config
+        JSON) straight into this model: the seven linears of every block go up as qweight / qzeros / scales (/ g_idx) and are
+        transposed on the device while they are quantised (include/gten_hip_w4.h); embed_tokens, lm_head and the norms are dense
+        and take set_weight_from.  lora / importance are refused: merge or calibrate from a dense checkpoint (load_checkpoint) instead."""
+        from . import convert
+        for given, what in ((lora, "lora"), (importance, "importance")):
+            if given is not None:
+                raise GtenHipError(f"load_quantized({src}): {what}= is not built for quantised tensors: merge or calibrate from a dense checkpoint "
+                                   "(load_checkpoint) instead")
+        ck = convert.open_quantized(src)
+        if ck.n_layers != self.cfg.n_layers:
+            raise GtenHipError(f"load_quantized({src}): {ck.n_layers} layers, the model has {self.cfg.n_layers}")
+        shapes = self.cfg.weight_shapes()
+        for idx, (name, _) in enumerate(convert.tensor_names(ck.n_layers)):
+            if ck.is_quantized(name):
+                qweight, qzeros, scales, g_idx, rows, cols = ck.linear(name)
+                if (rows, cols) != shapes[idx][:2]:
+                    raise GtenHipError(f"load_quantized({src}): {name} has the wrong shape {rows} x {cols}, the model's is {shapes[idx][0]} x {shapes[idx][1]}")
+                self.set_weight_from_w4(idx, qweight, qzeros, scales, g_idx, ck.layout, ck.zero_offset, ck.group_size, name)
+                continue
+            w, dt = ck.dense(name)
+            if dt == "f16":
+                w = w.astype(np.float16)                                  # (exact: the values came from f16)
+            elif dt == "bf16":
+                w = (np.ascontiguousarray(w).view(np.uint32) >> 16).astype(np.uint16)
+            self.set_weight_from(idx, w, dt)
         self.quant_release()
 
     def weight_read(self, idx):
